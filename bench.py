@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: CG iterations/s + SpMV effective HBM GB/s on the synthetic N=10M 7-point system.
 
-    python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]     (N>1: launched by torch.distributed.run)
+
+A plain run (N=1) sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`).  `--full` adds, in the
+same process, everything else the line used to carry: the instrumented SpMV pass with its roofline fields, the back-to-back
+SpMV, the value-codes-off form (`values_as_passed`), the small-system extra and the CPU baseline.  `--dump-outputs DIR`
+writes what the timed steps computed (dump_outputs) for output-for-output comparisons of two builds: the inputs are fixed.
 
 A "step" is one CG iteration (the reference's loop body, clcg.c:297-419) on the 3-D 7-point Laplacian
 250x200x200 (N=10 000 000, nnz=69 720 000, fp64), matrix and vectors resident in HBM before the timed
@@ -26,7 +31,7 @@ PKG = "conjugate-gradient-pyopencl_amd"
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s spec
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -39,10 +44,51 @@ def parse():
     ap.add_argument("--unfused", action="store_true", help="reference op structure (6 kernels/iteration)")
     ap.add_argument("--no-graph", action="store_true", help="plain stream launches instead of hipGraph replay (A/B)")
     ap.add_argument("--spmv-reps", type=int, default=20)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need (N=1): instrumented SpMV pass and roofline, back-to-back "
+                         "SpMV, the value-codes-off form, the small-system extra and the CPU baseline")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="N=1: after the timed steps, write what they computed (residual history, seeded sample of x) as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs is supported with --gpus 1 only")
+    return args
 
 
 NP_DTYPE = {"f32": np.float32, "f64": np.float64, "c64": np.complex64, "c128": np.complex128}
+DUMP_X_SAMPLE = 1 << 20         # --dump-outputs: entries of x written (all of x when it is shorter)
+DUMP_SEED = 12345               # ... chosen by this seed, so that every run writes the same entries
+DUMP_BUDGET = 64 << 20          # bytes of all files together
+
+
+def _real_view(a):
+    """float32 / float64 array of `a`; complex entries become a trailing (real, imag) axis"""
+    a = np.asarray(a)
+    if a.dtype.kind == "c":
+        a = np.stack([a.real, a.imag], axis=-1)
+    return np.ascontiguousarray(a)
+
+
+def dump_outputs(out_dir, x, hist):
+    """--dump-outputs: what the timed steps computed, as a caller of the solver receives it.
+      x_sample.npy        x after warmup + steps iterations at the entries of x_sample_index.npy (a fixed, seeded sample)
+      x_sample_index.npy  those entries' indices (float64, exact)
+      history.npy         delta_k = r_k . r_k for k = 0 .. warmup + steps, shape (iterations + 1, n_rhs); only its last
+                          rows if it would not fit the byte budget
+    Returns the names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = x.size
+    if n > DUMP_X_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_X_SAMPLE, replace=False))
+    else:
+        idx = np.arange(n)
+    arrays = {"x_sample": _real_view(x[idx]), "x_sample_index": idx.astype(np.float64)}
+    h = _real_view(hist)
+    room = (DUMP_BUDGET - sum(a.nbytes for a in arrays.values())) // max(1, h[:1].nbytes)
+    arrays["history"] = h[max(0, len(h) - room):]
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def host_cores():
@@ -191,7 +237,7 @@ def main():
         if shared:
             result["rehearsal"] = f"{world} ranks share {max(ndev, 1)} GPU(s): bootstrap over gloo, peer-to-peer loops only, not a scaling number"
 
-    if rank == 0:
+    if rank == 0 and args.full:
         if world == 1 and not args.no_small_system:
             try:
                 result["small_system"] = small_system_extra(pkg, ctx, torch, dev)
@@ -203,6 +249,7 @@ def main():
             except Exception as e:   # the baseline is a reported extra, never the measured path
                 result["cpu_baseline"] = {"value": None, "unit": "CG iterations/s", "cores": os.cpu_count(),
                                           "kind": "port", "sample": f"failed: {e}"}
+    if rank == 0:
         print(json.dumps(result), flush=True)
     if dist.is_initialized():
         dist.barrier()
@@ -270,6 +317,10 @@ def rate_fields(spmv_moved, spmv_csr, spmv_ms, spmv_alone_ms, iter_moved, iter_c
     }
 
 
+def residual_check(hist):
+    return {"delta_0": float(abs(hist[0, 0])), "delta_last": float(abs(hist[-1, 0])), "iterations": int(hist.shape[0] - 1)}
+
+
 def bench_single(args, pkg, ctx, torch, dev, nx, ny, nz, dtype):
     lib = pkg._lib
     n = nx * ny * nz
@@ -291,6 +342,22 @@ def bench_single(args, pkg, ctx, torch, dev, nx, ny, nz, dtype):
     dt = time.perf_counter() - t0
     hist = solver.history()
     it_s = args.steps / dt
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, solver.x(), hist)
+    res = {
+        "metric": "CG iterations/sec + SpMV effective HBM GB/s (% of 8 TB/s peak), N=10M CSR",
+        "value": it_s, "unit": "CG iterations/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt * 1e3 / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": f"3D 7-pt Laplacian {nx}x{ny}x{nz} CSR, N={n}, nnz={nnz}, {args.dtype}, 1 RHS, "
+                               f"b=5, x0=0, fixed-iteration CG ({'reference 6-op' if args.unfused else 'fused 4-launch'} loop)",
+                   "rows": n, "nnz": nnz, "parallelism": "1 GPU"},
+        "residual_check": None,
+    }
+    if not args.full:
+        res["residual_check"] = residual_check(hist)
+        solver.close()
+        return res
 
     # ---- dominant kernel: the fused SpMV (+ d.q partials).  Its launch duration is measured live, IN the CG loop:
     # an instrumented pass of the same K iterations in which every SpMV dispatch carries its own HIP start/stop event
@@ -319,17 +386,7 @@ def bench_single(args, pkg, ctx, torch, dev, nx, ny, nz, dtype):
     if spmv_ms is None:
         spmv_ms = spmv_alone_ms
     traffic, traffic_source = pmc_traffic("spmv_rowblock_vcp_kernel" if solver.value_codes > 0 else "spmv_rowblock_kernel")
-    delta0, deltak = abs(hist[0, 0]), abs(hist[-1, 0])
-    res = {
-        "metric": "CG iterations/sec + SpMV effective HBM GB/s (% of 8 TB/s peak), N=10M CSR",
-        "value": it_s, "unit": "CG iterations/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt * 1e3 / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": f"3D 7-pt Laplacian {nx}x{ny}x{nz} CSR, N={n}, nnz={nnz}, {args.dtype}, 1 RHS, "
-                               f"b=5, x0=0, fixed-iteration CG ({'reference 6-op' if args.unfused else 'fused 4-launch'} loop)",
-                   "rows": n, "nnz": nnz, "parallelism": "1 GPU"},
-        "residual_check": {"delta_0": float(delta0), "delta_last": float(deltak), "iterations": int(hist.shape[0] - 1)},
-    }
+    res["residual_check"] = residual_check(hist)
     res.update(rate_fields(spmv_moved=solver.spmv_moved_bytes, spmv_csr=spmv_bytes, spmv_ms=spmv_ms, spmv_alone_ms=spmv_alone_ms,
                            iter_moved=solver.iter_moved_bytes, iter_csr=iter_bytes, it_s=it_s, traffic=traffic,
                            traffic_source=traffic_source, n_offsets=solver.index_codes, n_values=solver.value_codes, n_pairs=solver.joint_codes))

@@ -19,8 +19,8 @@ for s in "$@"; do
     smoke) step smoke python -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) step pytest python -m pytest tests -m gpu -x -q ;;
     tests_all) step pytest python -m pytest tests -m gpu -q ;;
-    bench) step bench python bench.py --steps 100 --warmup 10 ;;
-    bench_quick) step bench python bench.py --steps 50 --warmup 10 --no-cpu-baseline ;;
+    bench) step bench python bench.py --full --steps 100 --warmup 10 ;;
+    bench_quick) step bench python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline ;;
     *) echo "unknown step $s" ;;
   esac
 done
