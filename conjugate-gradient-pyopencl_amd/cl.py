@@ -248,16 +248,24 @@ class Solver:
         check(self._lib.cgamd_solver_set_rhs(self.handle, ptr(b), ptr(x0), int(on_device)))
 
     def set_preconditioner(self, m):
-        """z = m * r between residual and search direction: the reference's PCG with a diagonal `M`
-        (helmFE_var.py:546-586, `z = M.dot(r)` branch).  m: the diagonal as a 1-D array (1/diag(A) for Jacobi), a scipy
-        sparse diagonal matrix as the reference passes it, a device buffer, or None to go back to plain CG.  Takes effect at
-        the next set_rhs; history() keeps returning r.r."""
+        """The reference's PCG preconditioner `M` (helmFE_var.py:546-586), chosen by the reference's own rule:
+        * None: plain CG again.
+        * a 1-D array (1/diag(A) for Jacobi), a device buffer, or a scipy sparse M with nnz <= size: the diagonal branch,
+          z = M.dot(r);
+        * a scipy sparse M with nnz > size: the spsolve branch, z solves M z = r.  M must be tridiagonal (no stored non-zero
+          with |i - j| > 1, e.g. the reference driver's `Htrid` on a grid of more than 10 nodes per line); it is factored once
+          on the host without pivoting (a zero pivot raises CgAmdError) and solved on the device by line sweeps.  Such handles
+          run a launched loop only (no resident loop, no device-side stop).
+        Any other M raises ValueError.  Takes effect at the next set_rhs; history() keeps returning r.r."""
         if m is None:
             check(self._lib.cgamd_solver_set_preconditioner(self.handle, None, 0))
             return
-        if hasattr(m, "diagonal") and hasattr(m, "nnz"):          # scipy sparse: must be diagonal, as in the reference
+        if hasattr(m, "diagonal") and hasattr(m, "nnz"):          # scipy sparse, as the reference passes it
+            if m.shape != (self.size, self.size):
+                raise ValueError("preconditioner M must be size x size")
             if m.nnz > m.shape[0]:
-                raise ValueError("only a diagonal M is supported (the reference's spsolve branch is out of scope)")
+                self._set_tridiag(m)
+                return
             m = m.diagonal()
         on_device = not isinstance(m, np.ndarray) and not isinstance(m, (list, tuple))
         if not on_device:
@@ -265,6 +273,20 @@ class Solver:
             if m.size != self.size:
                 raise ValueError("preconditioner diagonal must have `size` entries")
         check(self._lib.cgamd_solver_set_preconditioner(self.handle, ptr(m), int(on_device)))
+
+    def _set_tridiag(self, m):
+        """the three diagonals of a sparse M with nnz > size into cgamd_solver_set_preconditioner_tridiag"""
+        coo = m.tocoo()
+        if np.any((np.abs(coo.row.astype(np.int64) - coo.col) > 1) & (coo.data != 0)):
+            raise ValueError("only a diagonal or tridiagonal M is supported (M has stored non-zeros with |i - j| > 1; the "
+                             "reference's general spsolve branch is out of scope)")
+        n = self.size
+        lower, diag, upper = np.zeros(n, self.dtype), np.zeros(n, self.dtype), np.zeros(n, self.dtype)
+        diag[:] = m.diagonal(0)
+        if n > 1:
+            lower[1:] = m.diagonal(-1)
+            upper[:-1] = m.diagonal(1)
+        check(self._lib.cgamd_solver_set_preconditioner_tridiag(self.handle, ptr(lower), ptr(diag), ptr(upper), 0))
 
     def iterate(self, n_iterations):
         check(self._lib.cgamd_solver_iterate(self.handle, int(n_iterations)))
@@ -412,10 +434,11 @@ class Solver:
         return its
 
     def pcg(self, b, M=None, x0=None, tol=1e-6, maxit=1000, check_every=8):
-        """`PCG(A, b, M, x, tol, maxit)` of the reference (helmFE_var.py:546-586) for M = None or a diagonal M: stops when
-        sqrt(|r.r|) < tol, returns (x, i) with i the 0-based index of the last iteration run, like the reference.  The
-        residual history stays on the device and is read back every `check_every` iterations; x is taken at the first
-        iteration that met the tolerance by re-running exactly that many iterations when the check overshot it."""
+        """`PCG(A, b, M, x, tol, maxit)` of the reference (helmFE_var.py:546-586) for M = None, a diagonal M or a tridiagonal
+        sparse M (the spsolve branch; see set_preconditioner): stops when sqrt(|r.r|) < tol, returns (x, i) with i the 0-based
+        index of the last iteration run, like the reference.  The residual history stays on the device and is read back every
+        `check_every` iterations; x is taken at the first iteration that met the tolerance by re-running exactly that many
+        iterations when the check overshot it."""
         if self.n_rhs != 1:
             raise ValueError("pcg handles one right-hand side")
         self.set_preconditioner(M)

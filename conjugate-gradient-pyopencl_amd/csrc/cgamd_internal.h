@@ -353,6 +353,22 @@ int launch_pcg_aypx_beta(int dtype, int n, const void *r, void *p, const void *m
                          const void *part_rr, int P, int nrhs, const CgScalars &sc, void *rho2, void *xs, hipStream_t st);
 int launch_pcg_p_update(int dtype, int n, const void *r, void *p, const void *m, long long ld, const void *beta, int nrhs, hipStream_t st);
 int launch_pcg_delta0(int dtype, const void *part_rz, const void *part_rr, int P, int nrhs, const CgScalars &sc, void *rho2, hipStream_t st);
+// tridiagonal M (precond.hip): the factors of cgamd_solver_set_preconditioner_tridiag and the chunk plan, device arrays
+struct TriLaunch {
+    const void *nl = nullptr, *ne = nullptr, *w = nullptr;   // -l_i, -w_i c_i, w_i = 1/u_i: n values each
+    const int *cstart = nullptr;                             // nchunks + 1 chunk boundaries (rows)
+    int nchunks = 0, grid = 0;                               // grid = work-groups = r.z / r.r partials per RHS
+    bool longform = false;                                   // a segment is longer than a chunk: maps, carry, apply (3 launches)
+    void *maps = nullptr;                                    // longform: tri_maps_values(nchunks, nrhs) values
+};
+int tri_chunk_rows(int dtype);              // C: rows a chunk may span, from the first pack-aligned row of its work-group
+int tri_maps_values(int nchunks, int nrhs);
+// r -= alpha q (update; r.r partials) ; z = M^-1 r (r.z partials).  z may be q (in place).  update = false: set_rhs (z0 of r0)
+int launch_pcg_tri(int dtype, const TriLaunch &t, bool update, const void *q, void *r, void *z, long long ld, const void *alpha, int nrhs,
+                   void *part_rz, void *part_rr, hipStream_t st);
+// pcg_aypx_beta with p = z + beta p (z per right-hand side at stride ld), P thread-strided partials
+int launch_pcg_aypx_beta_z(int dtype, int n, void *p, const void *z, long long ld, const void *part_rz, const void *part_rr, int P, int nrhs,
+                           const CgScalars &sc, void *rho2, void *xs, hipStream_t st);
 // four-launch peer-to-peer iteration (see p2p.hip): SpMV with the push and the wait inside, aypx with the beta all-reduce.
 // halo_flag: device int per row block (1 = references a halo column); rotate: first row block of the visiting order
 int launch_spmv_p2p(int dtype, const SpmvPlan &plan, int n, long long nnz, const void *vals, const int *ptr, const int *cols,

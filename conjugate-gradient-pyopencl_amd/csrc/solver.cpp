@@ -11,6 +11,8 @@
 // 16 / 32 right-hand sides (f64, complex64; f32 also 64): the block is kept ROW-MAJOR inside the handle and the
 // product runs on the matrix cores (rowmajor.hip); the reference's RHS-major layout is converted in set_rhs / get_x.
 #include <algorithm>
+#include <cmath>
+#include <complex>
 #include <cstring>
 #include <vector>
 
@@ -42,6 +44,12 @@ struct cgamd_solver {
     size_t part_dq_cap = 0;      // entries per RHS
     // diagonal preconditioner (cgamd_solver_set_preconditioner): z = mdiag .* r; r.z partials; rho parity buffer
     void *mdiag = nullptr, *part_rz = nullptr, *rho2 = nullptr;
+    // tridiagonal preconditioner (cgamd_solver_set_preconditioner_tridiag): factors, chunk plan, r.z / r.r partials [2][nrhs][grid];
+    // z lives in q's storage (q is dead between the r update and the next SpMV)
+    bool tri_on = false;
+    TriLaunch tri;
+    void *tri_coef = nullptr, *tri_part = nullptr;
+    int *tri_cstart = nullptr;
     CgScalars sc;
     bool rhs_set = false;
     int iters = 0;  // iterations enqueued since set_rhs
@@ -113,7 +121,9 @@ static int validate_csr_host(int n, long long nnz, const int *ptr, const int *co
 
 // the SpMV (SpMM) launch of the iteration, bracketed by the caller's event pair when one is installed
 static void *dbuf(cgamd_solver *s, int k) { return (s->fused2 && (k & 1)) ? s->d2 : s->d; }
-static bool fused2_now(const cgamd_solver *s) { return s->fused2 && !s->rm && !s->mdiag && !(s->flags & CGAMD_UNFUSED); }
+// a preconditioner (diagonal or tridiagonal) is set: what decides the loop family; s->mdiag is read where the diagonal is used
+static bool precond_set(const cgamd_solver *s) { return s->mdiag != nullptr || s->tri_on; }
+static bool fused2_now(const cgamd_solver *s) { return s->fused2 && !s->rm && !precond_set(s) && !(s->flags & CGAMD_UNFUSED); }
 
 // k = iterations already enqueued since set_rhs (the iteration being enqueued is number k + 1)
 static int enqueue_spmv(cgamd_solver *s, int k, hipStream_t st) {
@@ -129,7 +139,7 @@ static int enqueue_spmv(cgamd_solver *s, int k, hipStream_t st) {
         rc = launch_spmv_fused(dt, s->plan, n, s->nnz, s->vals, s->ptr, s->cols, dbuf(s, k), dbuf(s, k + 1), s->r, s->q, nr, s->part_dq,
                                s->part_rr, s->vgrid, s->sc, st);
     else if (s->rm) rc = launch_spmm_rm(dt, n, s->nnz, s->vals, s->ptr, s->cols, s->d, s->q, nr, s->part_dq, s->plan.max_quad, s->rm_pace, st);
-    else if (s->flags & CGAMD_UNFUSED) rc = launch_spmv(dt, s->plan, n, s->nnz, s->vals, s->ptr, s->cols, s->d, n, s->q, n, nr, nullptr, nullptr, st);
+    else if ((s->flags & CGAMD_UNFUSED) && !s->tri_on) rc = launch_spmv(dt, s->plan, n, s->nnz, s->vals, s->ptr, s->cols, s->d, n, s->q, n, nr, nullptr, nullptr, st);
     else rc = launch_spmv(dt, s->plan, n, s->nnz, s->vals, s->ptr, s->cols, s->d, n, s->q, n, nr, s->d, s->part_dq, st);
     set_kernel_event_pair(nullptr);
     if (rc) return rc;
@@ -150,6 +160,13 @@ static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st) {
         if ((rc = launch_rm_axpy_dot(dt, n, nr, s->q, s->r, s->sc.alpha, s->part_rr, s->rm_vgrid, st))) return rc;
         if ((rc = launch_cg_beta(dt, s->part_rr, s->rm_vgrid, nr, s->sc, st))) return rc;
         return launch_rm_aypx_x(dt, n, nr, s->r, s->d, s->x, s->sc.alpha, s->sc.beta, s->rm_vgrid, st);
+    }
+    if (s->tri_on) {  // tridiagonal M (helmFE_var.py:561-562): z = M^-1 r by the line sweeps, in q's storage
+        if ((rc = enqueue_spmv(s, k, st))) return rc;
+        if ((rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st))) return rc;
+        void *prz = s->tri_part, *prr = static_cast<char *>(s->tri_part) + acc_size(dt) * (size_t)s->tri.grid * nr;
+        if ((rc = launch_pcg_tri(dt, s->tri, true, s->q, s->r, s->q, n, s->sc.alpha, nr, prz, prr, st))) return rc;
+        return launch_pcg_aypx_beta_z(dt, n, s->d, s->q, n, prz, prr, s->tri.grid, nr, s->sc, s->rho2, s->x, st);
     }
     if (s->mdiag) {   // preconditioned recurrence (helmFE_var.py:560-585); delta holds rho = r.z
         if ((rc = enqueue_spmv(s, k, st))) return rc;
@@ -188,8 +205,8 @@ static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st) {
 static void apply_wide_order(cgamd_solver *s) {
     const int E = (int)(16 / dtype_size(s->dtype));
     // (where the one-XCD resident loop applies it runs, with the strided order -- unless a preconditioner is set: that recurrence only
-    // has the chip-wide form)
-    const bool wide = s->resw.ok && (!s->res_ok || s->mdiag != nullptr);
+    // has the chip-wide form; the tridiagonal one has none)
+    const bool wide = s->resw.ok && !s->tri_on && (!s->res_ok || precond_set(s));
     const int kdq = wide ? kResWideBlocksPerRpt * s->resw.rpt : 0, krr = wide ? kdq / E : 0;
     const int vgrid = wide ? (s->n / E + kBlock - 1) / kBlock : vec_grid(s->n, s->dtype, s->nrhs);
     const int fold_max = 0;      // (alpha folded beyond 2048 partials was tried for these handles: every work-group summing 3907 partials, 1M rows 30 -> 52 us)
@@ -519,7 +536,7 @@ int cgamd_solver_destroy(cgamd_solver *s) {
         if (s->cols) (void)hipFree(s->cols);
     }
     void *bufs[] = {s->slab, s->part_dq, s->part_rr, s->sc.alpha, s->sc.beta, s->sc.delta,
-                    s->sc.history, s->sc.iter, s->mdiag, s->part_rz, s->rho2, s->sc.stage, s->sc.ticket, s->res_sync, s->resw_sync, s->codes, s->dict, s->rm_pace, s->vcodes, s->vdict, s->jcodes, s->jdict_off, s->jdict_val};
+                    s->sc.history, s->sc.iter, s->mdiag, s->part_rz, s->rho2, s->tri_coef, s->tri_part, s->tri_cstart, s->tri.maps, s->sc.stage, s->sc.ticket, s->res_sync, s->resw_sync, s->codes, s->dict, s->rm_pace, s->vcodes, s->vdict, s->jcodes, s->jdict_off, s->jdict_val};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     delete s;
@@ -533,7 +550,7 @@ int cgamd_solver_set_rhs(cgamd_solver *s, const void *b, const void *x0, int on_
     hipStream_t st = s->ctx->stream;
     const size_t vbytes = (size_t)s->n * s->nrhs * dtype_size(s->dtype);
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    const bool rm = s->rm_ok && !s->mdiag;      // the preconditioned recurrence keeps the RHS-major kernels
+    const bool rm = s->rm_ok && !precond_set(s);      // the preconditioned recurrence keeps the RHS-major kernels
     if (rm != s->rm) destroy_graphs(s);         // captured launch sequences belong to one layout
     s->rm = rm;
     int rc;
@@ -572,7 +589,11 @@ int cgamd_solver_set_rhs(cgamd_solver *s, const void *b, const void *x0, int on_
     if ((rc = launch_spmv(s->dtype, s->plan, s->n, s->nnz, s->vals, s->ptr, s->cols, s->x, s->n, s->q, s->n, s->nrhs,
                           nullptr, nullptr, st))) return rc;
     if ((rc = launch_sub(s->dtype, s->n, s->b, s->q, s->r, s->n, s->nrhs, st))) return rc;
-    if (s->mdiag) {   // z0 = M r0, p0 = z0, rho0 = r0.z0 (helmFE_var.py:562-573)
+    if (s->tri_on) {  // z0 = M^-1 r0 (the line sweeps), p0 = z0, rho0 = r0.z0
+        void *prz = s->tri_part, *prr = static_cast<char *>(s->tri_part) + acc_size(s->dtype) * (size_t)s->tri.grid * s->nrhs;
+        if ((rc = launch_pcg_tri(s->dtype, s->tri, false, nullptr, s->r, s->d, s->n, nullptr, s->nrhs, prz, prr, st))) return rc;
+        if ((rc = launch_pcg_delta0(s->dtype, prz, prr, s->tri.grid, s->nrhs, s->sc, s->rho2, st))) return rc;
+    } else if (s->mdiag) {   // z0 = M r0, p0 = z0, rho0 = r0.z0 (helmFE_var.py:562-573)
         if ((rc = launch_pcg_axpy2_dot2(s->dtype, true, s->n, s->d, s->x, s->q, s->r, s->mdiag, s->n, nullptr, s->nrhs, s->part_rz,
                                         s->part_rr, s->vgrid, st))) return rc;
         if ((rc = launch_pcg_delta0(s->dtype, s->part_rz, s->part_rr, s->vgrid, s->nrhs, s->sc, s->rho2, st))) return rc;
@@ -587,6 +608,15 @@ int cgamd_solver_set_rhs(cgamd_solver *s, const void *b, const void *x0, int on_
     return CGAMD_OK;
 }
 
+static void drop_tridiag(cgamd_solver *s) {
+    for (void *p : {s->tri_coef, s->tri_part, (void *)s->tri_cstart, s->tri.maps})
+        if (p) (void)hipFree(p);
+    s->tri_coef = s->tri_part = nullptr;
+    s->tri_cstart = nullptr;
+    s->tri = TriLaunch();
+    s->tri_on = false;
+}
+
 // z = m .* r between residual and search direction: the reference's PCG with a diagonal CSR M (helmFE_var.py:546-586;
 // pass 1/diag(A) for Jacobi).  m: `size` values of the solver's type, shared by all right-hand sides; NULL removes the
 // preconditioner.  The next cgamd_solver_set_rhs starts the preconditioned recurrence; history then holds r.r as before.
@@ -597,6 +627,7 @@ int cgamd_solver_set_preconditioner(cgamd_solver *s, const void *m, int on_devic
     CG_HIP(hipStreamSynchronize(s->ctx->stream));
     destroy_graphs(s);
     s->rhs_set = false;
+    drop_tridiag(s);
     if (!m) {
         if (s->mdiag) { (void)hipFree(s->mdiag); s->mdiag = nullptr; }
         apply_wide_order(s);
@@ -617,6 +648,126 @@ int cgamd_solver_set_preconditioner(cgamd_solver *s, const void *m, int on_devic
     return CGAMD_OK;
 }
 
+// Tridiagonal M: z solves M z = r (the reference PCG's spsolve branch, helmFE_var.py:561-562).  Factored here once, in double /
+// complex double (Thomas LU, no pivoting: u_0 = b_0, l_i = a_i / u_{i-1}, u_i = b_i - l_i c_{i-1}); the kernels get -l, -w c and
+// w = 1/u in the value type.  Rows where both couplings to the row before vanish start a segment; chunks of at most
+// tri_chunk_rows() rows start at segment starts when every segment fits one (no carry between work-groups), else they are plain
+// slices and the sweep takes its three-launch form.  Everything is checked before the handle changes.
+int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, const void *diag, const void *upper, int on_device) {
+    if (!s || !lower || !diag || !upper) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag: null argument");
+    TuneScope ts(&s->tune);
+    CG_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    CG_HIP(hipStreamSynchronize(st));
+    const int nu = s->n_user, n = s->n, dt = s->dtype;
+    const size_t vs = dtype_size(dt);
+    std::vector<unsigned char> h[3];
+    const void *src[3] = {lower, diag, upper};
+    for (int k = 0; k < 3; ++k) {
+        h[k].resize((size_t)nu * vs);
+        if (on_device) CG_HIP(hipMemcpyAsync(h[k].data(), src[k], h[k].size(), hipMemcpyDeviceToHost, st));
+        else std::memcpy(h[k].data(), src[k], h[k].size());
+    }
+    if (on_device) CG_HIP(hipStreamSynchronize(st));
+    using C = std::complex<double>;
+    auto get = [&](int k, int i) -> C {
+        const unsigned char *p = h[k].data() + (size_t)i * vs;
+        switch (dt) {
+        case CGAMD_F32: { float v; std::memcpy(&v, p, 4); return C(v, 0.); }
+        case CGAMD_F64: { double v; std::memcpy(&v, p, 8); return C(v, 0.); }
+        case CGAMD_C64: { float v[2]; std::memcpy(v, p, 8); return C(v[0], v[1]); }
+        default: { double v[2]; std::memcpy(v, p, 16); return C(v[0], v[1]); }
+        }
+    };
+    auto finite = [](C v) { return std::isfinite(v.real()) && std::isfinite(v.imag()); };
+    const int E = (int)(16 / vs);
+    const size_t pitch = ((size_t)n + 2 * E - 1) / (2 * E) * (2 * E);      // values per factor array: whole 32-byte rows of a thread
+    std::vector<unsigned char> coef(3 * pitch * vs, 0);
+    auto put = [&](int k, int i, C v) {
+        unsigned char *p = coef.data() + ((size_t)k * pitch + i) * vs;
+        switch (dt) {
+        case CGAMD_F32: { const float f = (float)v.real(); std::memcpy(p, &f, 4); break; }
+        case CGAMD_F64: { const double f = v.real(); std::memcpy(p, &f, 8); break; }
+        case CGAMD_C64: { const float f[2] = {(float)v.real(), (float)v.imag()}; std::memcpy(p, f, 8); break; }
+        default: { const double f[2] = {v.real(), v.imag()}; std::memcpy(p, f, 16); break; }
+        }
+    };
+    const bool single = dt == CGAMD_F32 || dt == CGAMD_C64;
+    auto rounds_to_zero = [&](C v) { return single ? ((float)v.real() == 0.f && (float)v.imag() == 0.f) : v == C(0., 0.); };
+    std::vector<char> l_zero((size_t)n, 1), e_zero((size_t)n, 1);      // the stored -l / -w c are 0 (as the kernels see them)
+    C u_prev(0., 0.), c_prev(0., 0.);
+    for (int i = 0; i < nu; ++i) {
+        const C a = i > 0 ? get(0, i) : C(0., 0.), b = get(1, i), c = i + 1 < nu ? get(2, i) : C(0., 0.);
+        if (!finite(a) || !finite(b) || !finite(c))
+            return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag: non-finite entry in row " + std::to_string(i));
+        const C l = i > 0 ? a / u_prev : C(0., 0.);
+        const C u = b - l * c_prev;
+        if (!finite(l) || !finite(u) || u == C(0., 0.))
+            return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag: zero or non-finite pivot in row " + std::to_string(i) +
+                                               " (the factorisation does not pivot)");
+        const C w = 1. / u;
+        if (!finite(w)) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag: pivot too small in row " + std::to_string(i));
+        put(0, i, -l);
+        put(1, i, -(w * c));
+        put(2, i, w);
+        l_zero[i] = rounds_to_zero(l);
+        e_zero[i] = rounds_to_zero(w * c);
+        u_prev = u;
+        c_prev = c;
+    }
+    // (the padding rows keep 0 everywhere: decoupled, z = 0 there)
+    // segment starts and the chunk plan
+    const int Cmax = tri_chunk_rows(dt), R = Cmax / kBlock;
+    std::vector<int> seg;
+    for (int i = 0; i < n; ++i)
+        if (i == 0 || (l_zero[i] && e_zero[i - 1])) seg.push_back(i);
+    seg.push_back(n);
+    std::vector<int> starts{0};
+    bool longform = false;
+    for (size_t k = 1; k < seg.size() && !longform; ++k) {
+        if (seg[k] - starts.back() / R * R <= Cmax) continue;        // segment k-1 still fits the current chunk
+        if (seg[k - 1] == starts.back()) longform = true;            // it alone does not fit one
+        else {
+            starts.push_back(seg[k - 1]);
+            if (seg[k] - seg[k - 1] / R * R > Cmax) longform = true;
+        }
+    }
+    if (longform) {
+        starts.clear();
+        for (int i = 0; i < n; i += Cmax) starts.push_back(i);
+    }
+    starts.push_back(n);
+    const int nchunks = (int)starts.size() - 1, grid = std::min(nchunks, 1024);
+    // the handle changes from here on
+    destroy_graphs(s);
+    s->rhs_set = false;
+    drop_tridiag(s);
+    if (s->mdiag) { (void)hipFree(s->mdiag); s->mdiag = nullptr; }
+    int rc = dmalloc(&s->tri_coef, coef.size(), "tridiagonal factors");
+    if (!rc) rc = dmalloc((void **)&s->tri_cstart, starts.size() * 4, "tridiagonal chunk plan");
+    if (!rc) rc = dmalloc(&s->tri_part, 2 * acc_size(dt) * (size_t)grid * s->nrhs, "partials_rz/rr (tridiagonal)");
+    if (!rc && longform) rc = dmalloc(&s->tri.maps, (size_t)tri_maps_values(nchunks, s->nrhs) * vs, "tridiagonal chunk maps");
+    if (!rc && !s->rho2) rc = dmalloc(&s->rho2, 2 * vs * (size_t)s->nrhs, "rho");
+    if (!rc) {
+        hipError_t e = hipMemcpyAsync(s->tri_coef, coef.data(), coef.size(), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(s->tri_cstart, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = fail(CGAMD_ERR_HIP, std::string("set_preconditioner_tridiag upload: ") + hipGetErrorString(e));
+    }
+    if (rc) {
+        drop_tridiag(s);
+        apply_wide_order(s);
+        return rc;
+    }
+    char *cb = static_cast<char *>(s->tri_coef);
+    s->tri.nl = cb; s->tri.ne = cb + pitch * vs; s->tri.w = cb + 2 * pitch * vs;
+    s->tri.cstart = s->tri_cstart;
+    s->tri.nchunks = nchunks; s->tri.grid = grid; s->tri.longform = longform;
+    s->tri_on = true;
+    apply_wide_order(s);
+    return CGAMD_OK;
+}
+
 int cgamd_solver_iterate(cgamd_solver *s, int nIterations) {
     if (!s) return fail(CGAMD_ERR_INVALID, "iterate: solver is NULL");
     TuneScope ts(&s->tune);
@@ -628,7 +779,7 @@ int cgamd_solver_iterate(cgamd_solver *s, int nIterations) {
     int left = nIterations, k = s->iters;
     const bool use_graph = !(s->flags & CGAMD_NO_GRAPH) && !s->graph_failed;
     const bool two = fused2_now(s);
-    if (s->resw.ok && !(two && s->res_ok) && !s->rm && !(s->flags & (CGAMD_NO_GRAPH | CGAMD_UNFUSED)) &&
+    if (s->resw.ok && !s->tri_on && !(two && s->res_ok) && !s->rm && !(s->flags & (CGAMD_NO_GRAPH | CGAMD_UNFUSED)) &&
         (nIterations >= std::max(1, tune().resident_wide_min) || s->tol_req > 0.)) {
         // one chip-wide resident group (single right-hand side, matrix rows in registers).  d ping-pongs inside the launch; handles
         // of the launched loops that keep d in one buffer get it back there, and the launched loops' r.r partials are rebuilt.
@@ -740,7 +891,7 @@ int cgamd_solver_iterate_tol(cgamd_solver *s, int maxIterations, double tol, int
     if (s->nrhs != 1) return fail(CGAMD_ERR_STATE, "iterate_tol: one right-hand side");
     {
         TuneScope ts(&s->tune);
-        const bool local = fused2_now(s) && s->res_ok, wide = s->resw.ok && !s->rm && !(s->res_ok && !s->mdiag);
+        const bool local = fused2_now(s) && s->res_ok, wide = s->resw.ok && !s->tri_on && !s->rm && !(s->res_ok && !precond_set(s));
         if ((!local && !wide) || (s->flags & (CGAMD_NO_GRAPH | CGAMD_UNFUSED)))
             return fail(CGAMD_ERR_STATE, "iterate_tol: this handle runs a launched loop (check the history from the host)");
     }
@@ -876,6 +1027,7 @@ int cgamd_solver_layout(cgamd_solver *s) { return s ? (s->rm ? 1 : 0) : -CGAMD_E
 int cgamd_solver_loop_launches(cgamd_solver *s) {
     if (!s) return -CGAMD_ERR_INVALID;
     TuneScope ts(&s->tune);
+    if (s->tri_on) return s->tri.longform ? 6 : 4;      // launched loop only: SpMV, cg_alpha, the sweep (3 launches in the long form), update
     if (s->flags & CGAMD_UNFUSED) return 8;
     if (s->rm) return 5;
     if (s->mdiag) return (s->resw.ok && !s->rm && !(s->flags & (CGAMD_NO_GRAPH | CGAMD_UNFUSED))) ? 1 : 4;
@@ -892,16 +1044,24 @@ long long cgamd_solver_spmv_bytes(cgamd_solver *s) {
     const long long V = (long long)dtype_size(s->dtype);
     return s->nnz * (V + 4) + ((long long)s->n_user + 1) * 4 + 2LL * s->n_user * V * s->nrhs;
 }
+// vector passes of the tridiagonal loop, counted once per right-hand side and once for the factors all of them share: SpMV
+// (p, q) 2 + sweep (r, q in; r, z out) 4 + update (z, p, x in; x, p out) 5 = 11 per RHS and nl, ne, w = 3; the long form reads
+// r again and writes z from a second sweep launch (+2 per RHS) and reads the factors twice (+3)
+static long long tri_passes(const cgamd_solver *s) {
+    return s->tri.longform ? 13LL * s->nrhs + 6 : 11LL * s->nrhs + 3;
+}
 long long cgamd_solver_iter_bytes(cgamd_solver *s, int fused) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
+    if (s->tri_on) return s->nnz * (V + 4) + ((long long)s->n_user + 1) * 4 + tri_passes(s) * s->n_user * V;
     return s->nnz * (V + 4) + ((long long)s->n_user + 1) * 4 + (fused ? 11LL : 14LL) * s->n_user * V * s->nrhs;
 }
 
 // What the handle's own kernels MOVE (the physical byte model the roofline fraction is priced on): index bytes per non-zero as
 // the SpMV really reads them (1 with the one-byte column codes, 2 with 16-bit block-relative columns, else 4) and the vector
 // passes of the launched loop the handle runs (10 with the deferred x update, 11 without, 12 preconditioned, 14 for the
-// reference's op structure).  Handles whose iterate() runs a resident loop report the launched loop they fall back to.
+// reference's op structure; the tridiagonal M: tri_passes).  Handles whose iterate() runs a resident loop report the launched loop
+// they fall back to.
 static long long index_bytes_per_nnz(const cgamd_solver *s) { return s->plan.codes ? (s->plan.codes16 ? 2 : 1) : 4; }
 // the single-RHS SpMV of this handle runs on joint codes (launch condition of spmv_impl: rows that fit one batch of the walk)
 static bool joint_form(const cgamd_solver *s) {
@@ -921,7 +1081,9 @@ long long cgamd_solver_iter_moved_bytes(cgamd_solver *s) {
     const long long V = (long long)dtype_size(s->dtype);
     const long long passes = (s->flags & CGAMD_UNFUSED) ? 14 : s->mdiag ? 12 : 10;
     const long long value_bytes = joint_form(s) ? 0 : s->plan.vcodes ? 1 : V;
-    return s->nnz * (value_bytes + index_bytes_per_nnz(s)) + ((long long)s->n_user + 1) * 4 + passes * s->n_user * V * s->nrhs;
+    const long long matrix = s->nnz * (value_bytes + index_bytes_per_nnz(s)) + ((long long)s->n_user + 1) * 4;
+    if (s->tri_on) return matrix + tri_passes(s) * s->n_user * V;
+    return matrix + passes * s->n_user * V * s->nrhs;
 }
 
 }  // extern "C"

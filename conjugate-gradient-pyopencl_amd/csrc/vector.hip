@@ -4,7 +4,8 @@
 //   ewise_kernel                  reference kernel/{real,complex}/{axpy,aypx,sub}.cl
 //   axpy_dot / aypx_beta_x        the fused loop: r -= alpha q + r.r partials; beta, x += alpha d, d = beta d + r
 //                                 (reference clcg.c:338-416); axpy2_dot / aypx_beta: the form with x updated in the r launch
-//   pcg_*                         diagonally preconditioned recurrence (reference helmFE_var.py:546-586)
+//   pcg_*                         diagonally preconditioned recurrence (reference helmFE_var.py:546-586); the tridiagonal
+//                                 form's sweep kernel is in precond.hip
 //   cg_alpha/beta/delta0          the scalar work the reference does on the host (clcg.c:274-292,317-334,376-411)
 //
 // grid-stride work-groups of 256 threads (<= 2048; streaming single-RHS systems: 512 = two per CU), 16 B per lane.  Reductions
@@ -410,7 +411,8 @@ __global__ __launch_bounds__(BLOCK) void pcg_axpy2_dot2_kernel(int n, const T *_
     if (threadIdx.x == 0) part_rr[(long long)r * gridDim.x + blockIdx.x] = trr;
 }
 
-template <typename T, int BLOCK, bool VEC>
+// ZV (tridiagonal M, precond.hip): m is z itself, one vector per right-hand side like r, and p = z + beta p
+template <typename T, int BLOCK, bool VEC, bool ZV = false>
 __global__ __launch_bounds__(BLOCK) void pcg_aypx_beta_kernel(int n, const T *__restrict__ rv, T *__restrict__ pv,
                                                               const T *__restrict__ m, long long ld,
                                                               const typename VT<T>::acc *__restrict__ part_rz,
@@ -446,18 +448,28 @@ __global__ __launch_bounds__(BLOCK) void pcg_aypx_beta_kernel(int n, const T *__
     }
     const T bt = beta_s, al = alpha[r];
     rv += (long long)r * ld; pv += (long long)r * ld; xs += (long long)r * ld;
+    if constexpr (ZV) m += (long long)r * ld;
     constexpr int E = Pack<T>::N;
     const long long stride = (long long)gridDim.x * BLOCK;
     long long i0 = (long long)blockIdx.x * BLOCK + threadIdx.x;
     if (VEC) {
         const long long npack = n / E;
         for (long long i = i0; i < npack; i += stride) {
-            const Pack<T> pr = ld_pack(rv + i * E), pm = ld_pack(m + i * E);
+            const Pack<T> pm = ld_pack(m + i * E);
             Pack<T> pp = ld_pack(pv + i * E), px = ld_pack(xs + i * E);
+            if constexpr (ZV) {
 #pragma unroll
-            for (int k = 0; k < E; ++k) {
-                px.v[k] = vadd(px.v[k], vmul(al, pp.v[k]));
-                pp.v[k] = vadd(vmul(bt, pp.v[k]), vmul(pm.v[k], pr.v[k]));
+                for (int k = 0; k < E; ++k) {
+                    px.v[k] = vadd(px.v[k], vmul(al, pp.v[k]));
+                    pp.v[k] = vadd(vmul(bt, pp.v[k]), pm.v[k]);
+                }
+            } else {
+                const Pack<T> pr = ld_pack(rv + i * E);
+#pragma unroll
+                for (int k = 0; k < E; ++k) {
+                    px.v[k] = vadd(px.v[k], vmul(al, pp.v[k]));
+                    pp.v[k] = vadd(vmul(bt, pp.v[k]), vmul(pm.v[k], pr.v[k]));
+                }
             }
             st_pack(xs + i * E, px);
             st_pack(pv + i * E, pp);
@@ -467,7 +479,8 @@ __global__ __launch_bounds__(BLOCK) void pcg_aypx_beta_kernel(int n, const T *__
     for (long long i = i0; i < n; i += stride) {
         const T pv0 = pv[i];
         xs[i] = vadd(xs[i], vmul(al, pv0));
-        pv[i] = vadd(vmul(bt, pv0), vmul(m[i], rv[i]));
+        if constexpr (ZV) pv[i] = vadd(vmul(bt, pv0), m[i]);
+        else pv[i] = vadd(vmul(bt, pv0), vmul(m[i], rv[i]));
     }
 }
 
@@ -851,6 +864,22 @@ int launch_pcg_aypx_beta(int dtype, int n, const void *r, void *p, const void *m
                          const void *part_rr, int P, int nrhs, const CgScalars &sc, void *rho2, void *xs, hipStream_t st) {
     const bool vec = vec_ok(dtype, ld, nrhs, {r, p, m, xs});
     CG_DISPATCH(dtype, pcg_aypx_impl, n, r, p, m, ld, part_rz, part_rr, P, nrhs, sc, rho2, xs, vec, st);
+}
+// the tridiagonal form: p = z + beta p with z = M^-1 r from pcg_tri (per right-hand side, stride ld); the partials are
+// pcg_tri's, summed thread-strided
+template <typename T>
+static int pcg_aypx_z_impl(int n, void *p, const void *z, long long ld, const void *part_rz, const void *part_rr, int P, int nrhs,
+                           const CgScalars &sc, void *rho2, void *xs, bool vec, hipStream_t st) {
+    dim3 g(vec_grid(n, VT<T>::dtype, nrhs), nrhs), blk(kBlock);
+    using A = typename VT<T>::acc;
+    if (vec) hipLaunchKernelGGL((pcg_aypx_beta_kernel<T, kBlock, true, true>), g, blk, 0, st, n, (const T *)nullptr, (T *)p, (const T *)z, ld, (const A *)part_rz, (const A *)part_rr, P, 0, nrhs, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter, (T *)xs, (const T *)sc.alpha);
+    else hipLaunchKernelGGL((pcg_aypx_beta_kernel<T, kBlock, false, true>), g, blk, 0, st, n, (const T *)nullptr, (T *)p, (const T *)z, ld, (const A *)part_rz, (const A *)part_rr, P, 0, nrhs, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter, (T *)xs, (const T *)sc.alpha);
+    return check_launch("pcg_aypx_beta z");
+}
+int launch_pcg_aypx_beta_z(int dtype, int n, void *p, const void *z, long long ld, const void *part_rz, const void *part_rr, int P, int nrhs,
+                           const CgScalars &sc, void *rho2, void *xs, hipStream_t st) {
+    const bool vec = vec_ok(dtype, ld, nrhs, {p, z, xs});
+    CG_DISPATCH(dtype, pcg_aypx_z_impl, n, p, z, ld, part_rz, part_rr, P, nrhs, sc, rho2, xs, vec, st);
 }
 template <typename T>
 static int pcg_delta0_impl(const void *part_rz, const void *part_rr, int P, int nrhs, const CgScalars &sc, void *rho2, hipStream_t st) {

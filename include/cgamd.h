@@ -161,6 +161,19 @@ int cgamd_solver_ld(cgamd_solver *s);
  * (cgamd_solver_loop_launches() == 1 once the preconditioner is set) run the recurrence inside that loop, with the bits of the
  * four-launch PCG loop of the same handle; cgamd_solver_iterate_tol then stops it on the device. */
 int cgamd_solver_set_preconditioner(cgamd_solver *s, const void *m, int on_device);
+/* Tridiagonal M: the reference PCG's spsolve branch (helmFE_var.py:561-562): z solves M z = r.
+ * lower[i] = M[i][i-1] (lower[0] ignored), diag[i] = M[i][i], upper[i] = M[i][i+1] (upper[size-1] ignored):
+ * `size` values each, the solver's value type, host (on_device = 0) or device memory.  M is shared by all right-hand sides, every
+ * value type.  Factored once here (Thomas LU in double / complex double, NO pivoting); CGAMD_ERR_INVALID, with the row in
+ * cgamd_last_error, on a non-finite entry or a zero / non-finite pivot -- the handle is then unchanged.  Like the diagonal form it
+ * takes effect at the next cgamd_solver_set_rhs, history keeps holding r.r and rho = r.z drives alpha and beta; it replaces a
+ * diagonal preconditioner, cgamd_solver_set_preconditioner replaces it, and cgamd_solver_set_preconditioner(s, NULL, 0) removes
+ * either (the handle then returns the bits of one that never had a preconditioner).  cgamd_solver_reload_matrix keeps it.
+ * Launched loop only: no resident loop takes the recurrence (cgamd_solver_loop_launches() = 4, or 6 when a coupled line is longer
+ * than one work-group's chunk -- 2048 rows f32, 1024 f64 / complex64, 512 complex128 -- and the sweep takes three launches);
+ * cgamd_solver_iterate_tol returns CGAMD_ERR_STATE (check the history from the host).  Padding rows (cgamd_solver_ld) are
+ * decoupled, z = 0 there. */
+int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, const void *diag, const void *upper, int on_device);
 /* convenience: set_rhs + iterate + get_x (+ history if non-NULL, (nIterations+1)*nRHS values), host arrays */
 int cgamd_solver_solve(cgamd_solver *s, const void *b, void *x, int nIterations, void *history);
 /* the solver's SpMV (optionally fused with the d.q partial reduction) on caller vectors -- bench/profiling */
