@@ -252,9 +252,11 @@ class Solver:
         * None: plain CG again.
         * a 1-D array (1/diag(A) for Jacobi), a device buffer, or a scipy sparse M with nnz <= size: the diagonal branch,
           z = M.dot(r);
-        * a scipy sparse M with nnz > size: the spsolve branch, z solves M z = r.  M must be tridiagonal (no stored non-zero
-          with |i - j| > 1, e.g. the reference driver's `Htrid` on a grid of more than 10 nodes per line); it is factored once
-          on the host without pivoting (a zero pivot raises CgAmdError) and solved on the device by line sweeps.  Such handles
+        * a scipy sparse M with nnz > size: the spsolve branch, z solves M z = r.  M must be tridiagonal along one grid axis: all
+          its stored non-zeros on |i - j| in {0, 1} (e.g. the reference driver's `Htrid` on a grid of more than 10 nodes per
+          line), or all on |i - j| in {0, s} for one s > 1 (the line preconditioner along another axis of a grid numbered x
+          fastest: s = nx for y-lines, nx * ny for z-lines).  It is factored once on the host without pivoting (a zero pivot
+          raises CgAmdError) and solved on the device, by line sweeps (s = 1) or one thread per line (s > 1).  Such handles
           run a launched loop only (no resident loop, no device-side stop).
         Any other M raises ValueError.  Takes effect at the next set_rhs; history() keeps returning r.r."""
         if m is None:
@@ -275,14 +277,24 @@ class Solver:
         check(self._lib.cgamd_solver_set_preconditioner(self.handle, ptr(m), int(on_device)))
 
     def _set_tridiag(self, m):
-        """the three diagonals of a sparse M with nnz > size into cgamd_solver_set_preconditioner_tridiag"""
+        """the three diagonals of a sparse M with nnz > size into cgamd_solver_set_preconditioner_tridiag, or, when they lie at
+        distance s > 1, into cgamd_solver_set_preconditioner_tridiag_strided"""
         coo = m.tocoo()
-        if np.any((np.abs(coo.row.astype(np.int64) - coo.col) > 1) & (coo.data != 0)):
-            raise ValueError("only a diagonal or tridiagonal M is supported (M has stored non-zeros with |i - j| > 1; the "
-                             "reference's general spsolve branch is out of scope)")
+        dist = np.unique(np.abs(coo.row.astype(np.int64) - coo.col)[coo.data != 0])
+        far = dist[dist > 1]
+        if far.size > 1 or (far.size == 1 and 1 in dist):
+            raise ValueError("only a diagonal or tridiagonal M is supported: stored non-zeros on |i - j| <= 1, or on |i - j| in "
+                             "{0, s} for one stride s (the strided tridiagonal form); M has them at distances "
+                             f"{dist[:8].tolist()} (the reference's general spsolve branch is out of scope)")
         n = self.size
         lower, diag, upper = np.zeros(n, self.dtype), np.zeros(n, self.dtype), np.zeros(n, self.dtype)
         diag[:] = m.diagonal(0)
+        if far.size == 1:
+            s = int(far[0])
+            lower[s:] = m.diagonal(-s)
+            upper[:-s] = m.diagonal(s)
+            check(self._lib.cgamd_solver_set_preconditioner_tridiag_strided(self.handle, s, ptr(lower), ptr(diag), ptr(upper), 0))
+            return
         if n > 1:
             lower[1:] = m.diagonal(-1)
             upper[:-1] = m.diagonal(1)
@@ -435,7 +447,7 @@ class Solver:
 
     def pcg(self, b, M=None, x0=None, tol=1e-6, maxit=1000, check_every=8):
         """`PCG(A, b, M, x, tol, maxit)` of the reference (helmFE_var.py:546-586) for M = None, a diagonal M or a tridiagonal
-        sparse M (the spsolve branch; see set_preconditioner): stops when sqrt(|r.r|) < tol, returns (x, i) with i the 0-based
+        sparse M along any grid axis (the spsolve branch; see set_preconditioner): stops when sqrt(|r.r|) < tol, returns (x, i) with i the 0-based
         index of the last iteration run, like the reference.  The residual history stays on the device and is read back every
         `check_every` iterations; x is taken at the first iteration that met the tolerance by re-running exactly that many
         iterations when the check overshot it."""

@@ -360,12 +360,20 @@ struct TriLaunch {
     int nchunks = 0, grid = 0;                               // grid = work-groups = r.z / r.r partials per RHS
     bool longform = false;                                   // a segment is longer than a chunk: maps, carry, apply (3 launches)
     void *maps = nullptr;                                    // longform: tri_maps_values(nchunks, nrhs) values
+    // strided form (precond_strided.hip, stride > 1): M couples rows i and i +- stride; the plan is the segment list, not chunks
+    int stride = 1;
+    const int *segs = nullptr;                               // nsegs pairs (first row, length), ordered by first row
+    int nsegs = 0;
 };
 int tri_chunk_rows(int dtype);              // C: rows a chunk may span, from the first pack-aligned row of its work-group
 int tri_maps_values(int nchunks, int nrhs);
 // r -= alpha q (update; r.r partials) ; z = M^-1 r (r.z partials).  z may be q (in place).  update = false: set_rhs (z0 of r0)
 int launch_pcg_tri(int dtype, const TriLaunch &t, bool update, const void *q, void *r, void *z, long long ld, const void *alpha, int nrhs,
                    void *part_rz, void *part_rr, hipStream_t st);
+// the same for the strided form: one thread per segment, a single launch for segments of any length
+int tri_strided_grid(int nsegs);            // work-groups = r.z / r.r partials per RHS (at most 1024)
+int launch_pcg_tri_strided(int dtype, const TriLaunch &t, bool update, const void *q, void *r, void *z, long long ld, const void *alpha,
+                           int nrhs, void *part_rz, void *part_rr, hipStream_t st);
 // pcg_aypx_beta with p = z + beta p (z per right-hand side at stride ld), P thread-strided partials
 int launch_pcg_aypx_beta_z(int dtype, int n, void *p, const void *z, long long ld, const void *part_rz, const void *part_rr, int P, int nrhs,
                            const CgScalars &sc, void *rho2, void *xs, hipStream_t st);

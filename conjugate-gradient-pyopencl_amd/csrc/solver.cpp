@@ -44,8 +44,9 @@ struct cgamd_solver {
     size_t part_dq_cap = 0;      // entries per RHS
     // diagonal preconditioner (cgamd_solver_set_preconditioner): z = mdiag .* r; r.z partials; rho parity buffer
     void *mdiag = nullptr, *part_rz = nullptr, *rho2 = nullptr;
-    // tridiagonal preconditioner (cgamd_solver_set_preconditioner_tridiag): factors, chunk plan, r.z / r.r partials [2][nrhs][grid];
-    // z lives in q's storage (q is dead between the r update and the next SpMV)
+    // tridiagonal preconditioner (cgamd_solver_set_preconditioner_tridiag and its strided form): factors, chunk plan (strided: the
+    // segment list, in tri_cstart as well), r.z / r.r partials [2][nrhs][grid]; z lives in q's storage (q is dead between the r
+    // update and the next SpMV)
     bool tri_on = false;
     TriLaunch tri;
     void *tri_coef = nullptr, *tri_part = nullptr;
@@ -147,6 +148,14 @@ static int enqueue_spmv(cgamd_solver *s, int k, hipStream_t st) {
     return CGAMD_OK;
 }
 
+// r -= alpha q (update) and z = M^-1 r of a tridiagonal M, by the kernel of its form: the scan sweep of rows i +- 1 (precond.hip) or
+// one thread per segment of rows i +- stride (precond_strided.hip)
+static int enqueue_tri_sweep(cgamd_solver *s, bool update, const void *q, void *z, void *prz, void *prr, hipStream_t st) {
+    const void *alpha = update ? s->sc.alpha : nullptr;
+    if (s->tri.stride > 1) return launch_pcg_tri_strided(s->dtype, s->tri, update, q, s->r, z, s->n, alpha, s->nrhs, prz, prr, st);
+    return launch_pcg_tri(s->dtype, s->tri, update, q, s->r, z, s->n, alpha, s->nrhs, prz, prr, st);
+}
+
 static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st) {
     const int dt = s->dtype, n = s->n, nr = s->nrhs;
     int rc;
@@ -165,7 +174,7 @@ static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st) {
         if ((rc = enqueue_spmv(s, k, st))) return rc;
         if ((rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st))) return rc;
         void *prz = s->tri_part, *prr = static_cast<char *>(s->tri_part) + acc_size(dt) * (size_t)s->tri.grid * nr;
-        if ((rc = launch_pcg_tri(dt, s->tri, true, s->q, s->r, s->q, n, s->sc.alpha, nr, prz, prr, st))) return rc;
+        if ((rc = enqueue_tri_sweep(s, true, s->q, s->q, prz, prr, st))) return rc;
         return launch_pcg_aypx_beta_z(dt, n, s->d, s->q, n, prz, prr, s->tri.grid, nr, s->sc, s->rho2, s->x, st);
     }
     if (s->mdiag) {   // preconditioned recurrence (helmFE_var.py:560-585); delta holds rho = r.z
@@ -591,7 +600,7 @@ int cgamd_solver_set_rhs(cgamd_solver *s, const void *b, const void *x0, int on_
     if ((rc = launch_sub(s->dtype, s->n, s->b, s->q, s->r, s->n, s->nrhs, st))) return rc;
     if (s->tri_on) {  // z0 = M^-1 r0 (the line sweeps), p0 = z0, rho0 = r0.z0
         void *prz = s->tri_part, *prr = static_cast<char *>(s->tri_part) + acc_size(s->dtype) * (size_t)s->tri.grid * s->nrhs;
-        if ((rc = launch_pcg_tri(s->dtype, s->tri, false, nullptr, s->r, s->d, s->n, nullptr, s->nrhs, prz, prr, st))) return rc;
+        if ((rc = enqueue_tri_sweep(s, false, nullptr, s->d, prz, prr, st))) return rc;
         if ((rc = launch_pcg_delta0(s->dtype, prz, prr, s->tri.grid, s->nrhs, s->sc, s->rho2, st))) return rc;
     } else if (s->mdiag) {   // z0 = M r0, p0 = z0, rho0 = r0.z0 (helmFE_var.py:562-573)
         if ((rc = launch_pcg_axpy2_dot2(s->dtype, true, s->n, s->d, s->x, s->q, s->r, s->mdiag, s->n, nullptr, s->nrhs, s->part_rz,
@@ -648,17 +657,17 @@ int cgamd_solver_set_preconditioner(cgamd_solver *s, const void *m, int on_devic
     return CGAMD_OK;
 }
 
-// Tridiagonal M: z solves M z = r (the reference PCG's spsolve branch, helmFE_var.py:561-562).  Factored here once, in double /
-// complex double (Thomas LU, no pivoting: u_0 = b_0, l_i = a_i / u_{i-1}, u_i = b_i - l_i c_{i-1}); the kernels get -l, -w c and
-// w = 1/u in the value type.  Rows where both couplings to the row before vanish start a segment; chunks of at most
-// tri_chunk_rows() rows start at segment starts when every segment fits one (no carry between work-groups), else they are plain
-// slices and the sweep takes its three-launch form.  Everything is checked before the handle changes.
-int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, const void *diag, const void *upper, int on_device) {
-    if (!s || !lower || !diag || !upper) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag: null argument");
-    TuneScope ts(&s->tune);
-    CG_HIP(hipSetDevice(s->ctx->device));
+// The host side both tridiagonal forms share: M's three arrays to the host and the factorisation along every chain c, c + stride,
+// c + 2 stride, ... (stride 1: the rows in order).  Rows are visited in order, so the first bad row is the one named.  Leaves the
+// factors as the kernels read them (nl, ne, w: `pitch` values each) and, per row, whether the stored -l / -w c are 0.
+struct TriFactors {
+    std::vector<unsigned char> coef;
+    std::vector<char> l_zero, e_zero;
+    size_t pitch = 0;
+};
+static int tri_factor(cgamd_solver *s, const std::string &who, int stride, const void *lower, const void *diag, const void *upper,
+                      int on_device, TriFactors &out) {
     hipStream_t st = s->ctx->stream;
-    CG_HIP(hipStreamSynchronize(st));
     const int nu = s->n_user, n = s->n, dt = s->dtype;
     const size_t vs = dtype_size(dt);
     std::vector<unsigned char> h[3];
@@ -682,9 +691,10 @@ int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, 
     auto finite = [](C v) { return std::isfinite(v.real()) && std::isfinite(v.imag()); };
     const int E = (int)(16 / vs);
     const size_t pitch = ((size_t)n + 2 * E - 1) / (2 * E) * (2 * E);      // values per factor array: whole 32-byte rows of a thread
-    std::vector<unsigned char> coef(3 * pitch * vs, 0);
+    out.pitch = pitch;
+    out.coef.assign(3 * pitch * vs, 0);
     auto put = [&](int k, int i, C v) {
-        unsigned char *p = coef.data() + ((size_t)k * pitch + i) * vs;
+        unsigned char *p = out.coef.data() + ((size_t)k * pitch + i) * vs;
         switch (dt) {
         case CGAMD_F32: { const float f = (float)v.real(); std::memcpy(p, &f, 4); break; }
         case CGAMD_F64: { const double f = v.real(); std::memcpy(p, &f, 8); break; }
@@ -694,28 +704,52 @@ int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, 
     };
     const bool single = dt == CGAMD_F32 || dt == CGAMD_C64;
     auto rounds_to_zero = [&](C v) { return single ? ((float)v.real() == 0.f && (float)v.imag() == 0.f) : v == C(0., 0.); };
-    std::vector<char> l_zero((size_t)n, 1), e_zero((size_t)n, 1);      // the stored -l / -w c are 0 (as the kernels see them)
-    C u_prev(0., 0.), c_prev(0., 0.);
+    out.l_zero.assign((size_t)n, 1);      // the stored -l / -w c are 0 (as the kernels see them)
+    out.e_zero.assign((size_t)n, 1);
+    std::vector<C> u_prev((size_t)stride, C(0., 0.)), c_prev((size_t)stride, C(0., 0.));      // of row i - stride, per chain
     for (int i = 0; i < nu; ++i) {
-        const C a = i > 0 ? get(0, i) : C(0., 0.), b = get(1, i), c = i + 1 < nu ? get(2, i) : C(0., 0.);
+        const int ch = i % stride;
+        const bool head = i < stride;
+        const C a = head ? C(0., 0.) : get(0, i), b = get(1, i), c = i < nu - stride ? get(2, i) : C(0., 0.);
         if (!finite(a) || !finite(b) || !finite(c))
-            return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag: non-finite entry in row " + std::to_string(i));
-        const C l = i > 0 ? a / u_prev : C(0., 0.);
-        const C u = b - l * c_prev;
+            return fail(CGAMD_ERR_INVALID, who + ": non-finite entry in row " + std::to_string(i));
+        const C l = head ? C(0., 0.) : a / u_prev[ch];
+        const C u = b - l * c_prev[ch];
         if (!finite(l) || !finite(u) || u == C(0., 0.))
-            return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag: zero or non-finite pivot in row " + std::to_string(i) +
+            return fail(CGAMD_ERR_INVALID, who + ": zero or non-finite pivot in row " + std::to_string(i) +
                                                " (the factorisation does not pivot)");
         const C w = 1. / u;
-        if (!finite(w)) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag: pivot too small in row " + std::to_string(i));
+        if (!finite(w)) return fail(CGAMD_ERR_INVALID, who + ": pivot too small in row " + std::to_string(i));
         put(0, i, -l);
         put(1, i, -(w * c));
         put(2, i, w);
-        l_zero[i] = rounds_to_zero(l);
-        e_zero[i] = rounds_to_zero(w * c);
-        u_prev = u;
-        c_prev = c;
+        out.l_zero[i] = rounds_to_zero(l);
+        out.e_zero[i] = rounds_to_zero(w * c);
+        u_prev[ch] = u;
+        c_prev[ch] = c;
     }
     // (the padding rows keep 0 everywhere: decoupled, z = 0 there)
+    return CGAMD_OK;
+}
+
+// Tridiagonal M: z solves M z = r (the reference PCG's spsolve branch, helmFE_var.py:561-562).  Factored here once, in double /
+// complex double (Thomas LU, no pivoting: u_0 = b_0, l_i = a_i / u_{i-1}, u_i = b_i - l_i c_{i-1}); the kernels get -l, -w c and
+// w = 1/u in the value type.  Rows where both couplings to the row before vanish start a segment; chunks of at most
+// tri_chunk_rows() rows start at segment starts when every segment fits one (no carry between work-groups), else they are plain
+// slices and the sweep takes its three-launch form.  Everything is checked before the handle changes.
+int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, const void *diag, const void *upper, int on_device) {
+    if (!s || !lower || !diag || !upper) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag: null argument");
+    TuneScope ts(&s->tune);
+    CG_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    CG_HIP(hipStreamSynchronize(st));
+    const int n = s->n, dt = s->dtype;
+    const size_t vs = dtype_size(dt);
+    TriFactors f;
+    if (int rc = tri_factor(s, "set_preconditioner_tridiag", 1, lower, diag, upper, on_device, f)) return rc;
+    const std::vector<unsigned char> &coef = f.coef;
+    const std::vector<char> &l_zero = f.l_zero, &e_zero = f.e_zero;
+    const size_t pitch = f.pitch;
     // segment starts and the chunk plan
     const int Cmax = tri_chunk_rows(dt), R = Cmax / kBlock;
     std::vector<int> seg;
@@ -763,6 +797,72 @@ int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, 
     s->tri.nl = cb; s->tri.ne = cb + pitch * vs; s->tri.w = cb + 2 * pitch * vs;
     s->tri.cstart = s->tri_cstart;
     s->tri.nchunks = nchunks; s->tri.grid = grid; s->tri.longform = longform;
+    s->tri_on = true;
+    apply_wide_order(s);
+    return CGAMD_OK;
+}
+
+// The same M at a distance: lower[i] = M[i][i-stride], upper[i] = M[i][i+stride] (a line preconditioner along the grid axis whose
+// neighbours lie `stride` rows apart).  The factorisation runs along every chain c, c + stride, ...; a chain is cut where both
+// stored couplings round to zero in the value type (the rule of the stride-1 form, at distance stride), and the plan is the list
+// of those segments (first row, length) ordered by first row: one thread of pcg_tri_strided_kernel each, whatever their length.
+// stride 1 is cgamd_solver_set_preconditioner_tridiag itself.
+int cgamd_solver_set_preconditioner_tridiag_strided(cgamd_solver *s, int stride, const void *lower, const void *diag, const void *upper,
+                                                    int on_device) {
+    if (!s || !lower || !diag || !upper) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag_strided: null argument");
+    if (stride < 1 || stride >= s->n_user)
+        return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag_strided: stride must be in [1, size - 1]");
+    if (stride == 1) return cgamd_solver_set_preconditioner_tridiag(s, lower, diag, upper, on_device);
+    TuneScope ts(&s->tune);
+    CG_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    CG_HIP(hipStreamSynchronize(st));
+    const int n = s->n, dt = s->dtype;
+    const size_t vs = dtype_size(dt);
+    TriFactors f;
+    if (int rc = tri_factor(s, "set_preconditioner_tridiag_strided", stride, lower, diag, upper, on_device, f)) return rc;
+    // row i starts a segment when it heads its chain or both couplings to row i - stride vanish; its length is known once the
+    // chain's next start (or end) is: walk the rows backwards, carrying per chain the rows seen since the last start
+    std::vector<int> segs;      // (first row, length) pairs, built last segment first
+    {
+        std::vector<int> run((size_t)stride, 0);
+        for (int i = n - 1; i >= 0; --i) {
+            int &len = run[i % stride];
+            ++len;
+            if (i < stride || (f.l_zero[i] && f.e_zero[i - stride])) {
+                segs.push_back(len);
+                segs.push_back(i);
+                len = 0;
+            }
+        }
+        std::reverse(segs.begin(), segs.end());
+    }
+    const int nsegs = (int)(segs.size() / 2), grid = tri_strided_grid(nsegs);
+    // the handle changes from here on
+    destroy_graphs(s);
+    s->rhs_set = false;
+    drop_tridiag(s);
+    if (s->mdiag) { (void)hipFree(s->mdiag); s->mdiag = nullptr; }
+    int rc = dmalloc(&s->tri_coef, f.coef.size(), "tridiagonal factors");
+    if (!rc) rc = dmalloc((void **)&s->tri_cstart, segs.size() * 4, "tridiagonal segment plan");
+    if (!rc) rc = dmalloc(&s->tri_part, 2 * acc_size(dt) * (size_t)grid * s->nrhs, "partials_rz/rr (tridiagonal)");
+    if (!rc && !s->rho2) rc = dmalloc(&s->rho2, 2 * vs * (size_t)s->nrhs, "rho");
+    if (!rc) {
+        hipError_t e = hipMemcpyAsync(s->tri_coef, f.coef.data(), f.coef.size(), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(s->tri_cstart, segs.data(), segs.size() * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = fail(CGAMD_ERR_HIP, std::string("set_preconditioner_tridiag_strided upload: ") + hipGetErrorString(e));
+    }
+    if (rc) {
+        drop_tridiag(s);
+        apply_wide_order(s);
+        return rc;
+    }
+    char *cb = static_cast<char *>(s->tri_coef);
+    s->tri.nl = cb; s->tri.ne = cb + f.pitch * vs; s->tri.w = cb + 2 * f.pitch * vs;
+    s->tri.stride = stride;
+    s->tri.segs = s->tri_cstart;
+    s->tri.nsegs = nsegs; s->tri.grid = grid;
     s->tri_on = true;
     apply_wide_order(s);
     return CGAMD_OK;
@@ -1046,8 +1146,11 @@ long long cgamd_solver_spmv_bytes(cgamd_solver *s) {
 }
 // vector passes of the tridiagonal loop, counted once per right-hand side and once for the factors all of them share: SpMV
 // (p, q) 2 + sweep (r, q in; r, z out) 4 + update (z, p, x in; x, p out) 5 = 11 per RHS and nl, ne, w = 3; the long form reads
-// r again and writes z from a second sweep launch (+2 per RHS) and reads the factors twice (+3)
+// r again and writes z from a second sweep launch (+2 per RHS) and reads the factors twice (+3).  The strided form (one thread per
+// segment) stores w y in the forward walk and reads it and r back in the backward walk: sweep (r, q in; r, w y out; w y, r in; z
+// out) 7, so 14 per RHS, and each factor once
 static long long tri_passes(const cgamd_solver *s) {
+    if (s->tri.stride > 1) return 14LL * s->nrhs + 3;
     return s->tri.longform ? 13LL * s->nrhs + 6 : 11LL * s->nrhs + 3;
 }
 long long cgamd_solver_iter_bytes(cgamd_solver *s, int fused) {

@@ -174,6 +174,25 @@ int cgamd_solver_set_preconditioner(cgamd_solver *s, const void *m, int on_devic
  * cgamd_solver_iterate_tol returns CGAMD_ERR_STATE (check the history from the host).  Padding rows (cgamd_solver_ld) are
  * decoupled, z = 0 there. */
 int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, const void *diag, const void *upper, int on_device);
+/* The same M along any grid axis: a line preconditioner whose coupled rows lie `stride` apart (stride = nx for the y-lines,
+ * nx * ny for the z-lines of a grid numbered x fastest), so that strong coupling off the fastest index needs no permutation of the
+ * matrix (which would give up the one-byte codes of the SpMV).  lower[i] = M[i][i-stride] (ignored for i < stride), diag[i] =
+ * M[i][i], upper[i] = M[i][i+stride] (ignored for i >= size - stride): `size` values each, the solver's value type, host or device
+ * memory, every value type, M shared by all right-hand sides.  stride == 1 IS cgamd_solver_set_preconditioner_tridiag (same code
+ * path, same bits); stride < 1 or stride >= size returns CGAMD_ERR_INVALID.  In every other respect the contract of the stride-1
+ * form: factored once here (Thomas LU in double / complex double, NO pivoting) along every chain c, c + stride, c + 2 stride, ...;
+ * CGAMD_ERR_INVALID with the row in cgamd_last_error on a non-finite entry or a zero / non-finite pivot, the handle then unchanged;
+ * effective at the next cgamd_solver_set_rhs; history keeps r.r, rho = r.z drives alpha and beta; it replaces a diagonal or
+ * stride-1 preconditioner and either of those replaces it, cgamd_solver_set_preconditioner(s, NULL, 0) removes it (the handle then
+ * returns the bits of one that never had a preconditioner); cgamd_solver_reload_matrix keeps it; padding rows are decoupled, z = 0
+ * there; launched loop only, cgamd_solver_loop_launches() = 4, cgamd_solver_iterate_tol returns CGAMD_ERR_STATE.
+ * A chain is cut into segments where both stored couplings round to zero in the value type -- on a grid the segments are the grid
+ * lines, nx * nz y-lines of ny rows or nx * ny z-lines of nz rows -- and the device solves ONE SEGMENT PER THREAD, consecutive
+ * segments in consecutive threads: with thousands of lines whose first rows are consecutive every step of the sweep moves whole
+ * cache lines.  A segment may have any length, but a matrix with FEW LONG segments (a 1-D chain at stride 2: two segments) is solved
+ * correctly and serially within each segment, i.e. slowly; the form is meant for grids. */
+int cgamd_solver_set_preconditioner_tridiag_strided(cgamd_solver *s, int stride, const void *lower, const void *diag,
+                                                    const void *upper, int on_device);
 /* convenience: set_rhs + iterate + get_x (+ history if non-NULL, (nIterations+1)*nRHS values), host arrays */
 int cgamd_solver_solve(cgamd_solver *s, const void *b, void *x, int nIterations, void *history);
 /* the solver's SpMV (optionally fused with the d.q partial reduction) on caller vectors -- bench/profiling */
