@@ -250,6 +250,11 @@ class Solver:
     def set_preconditioner(self, m):
         """The reference's PCG preconditioner `M` (helmFE_var.py:546-586), chosen by the reference's own rule:
         * None: plain CG again.
+        * "jacobi": 1/diag(A) of the handle's own matrix, built on the device (cgamd_solver_set_preconditioner_jacobi), then the
+          diagonal branch.
+        * ("line", stride): the tridiagonal M of the handle's own matrix, its entries at column - row in {-stride, 0, +stride}
+          (stride 1: x-lines, nx: y-lines, nx * ny: z-lines), extracted, factored and planned on the device
+          (cgamd_solver_set_preconditioner_line); the spsolve branch below without the host work.  Both follow reload_matrix.
         * a 1-D array (1/diag(A) for Jacobi), a device buffer, or a scipy sparse M with nnz <= size: the diagonal branch,
           z = M.dot(r);
         * a scipy sparse M with nnz > size: the spsolve branch, z solves M z = r.  M must be tridiagonal along one grid axis: all
@@ -261,6 +266,14 @@ class Solver:
         Any other M raises ValueError.  Takes effect at the next set_rhs; history() keeps returning r.r."""
         if m is None:
             check(self._lib.cgamd_solver_set_preconditioner(self.handle, None, 0))
+            return
+        if isinstance(m, str):
+            if m != "jacobi":
+                raise ValueError('preconditioner by name: "jacobi" or ("line", stride)')
+            check(self._lib.cgamd_solver_set_preconditioner_jacobi(self.handle))
+            return
+        if isinstance(m, tuple) and len(m) == 2 and m[0] == "line":
+            check(self._lib.cgamd_solver_set_preconditioner_line(self.handle, int(m[1])))
             return
         if hasattr(m, "diagonal") and hasattr(m, "nnz"):          # scipy sparse, as the reference passes it
             if m.shape != (self.size, self.size):
@@ -349,6 +362,12 @@ class Solver:
     @property
     def ld(self):
         return self._lib.cgamd_solver_ld(self.handle)
+
+    @property
+    def preconditioner_source(self):
+        """0: no preconditioner; 1: from the caller's arrays; 2: from the handle's matrix, built on the device; 3: from the matrix,
+        extracted on the device and factored by the host route (long segments)"""
+        return self._lib.cgamd_solver_preconditioner_source(self.handle)
 
     @property
     def spmv_bytes(self):
@@ -446,8 +465,8 @@ class Solver:
         return its
 
     def pcg(self, b, M=None, x0=None, tol=1e-6, maxit=1000, check_every=8):
-        """`PCG(A, b, M, x, tol, maxit)` of the reference (helmFE_var.py:546-586) for M = None, a diagonal M or a tridiagonal
-        sparse M along any grid axis (the spsolve branch; see set_preconditioner): stops when sqrt(|r.r|) < tol, returns (x, i) with i the 0-based
+        """`PCG(A, b, M, x, tol, maxit)` of the reference (helmFE_var.py:546-586) for M = None, a diagonal M, a tridiagonal
+        sparse M along any grid axis (the spsolve branch) or "jacobi" / ("line", stride) built from the matrix (see set_preconditioner): stops when sqrt(|r.r|) < tol, returns (x, i) with i the 0-based
         index of the last iteration run, like the reference.  The residual history stays on the device and is read back every
         `check_every` iterations; x is taken at the first iteration that met the tolerance by re-running exactly that many
         iterations when the check overshot it."""

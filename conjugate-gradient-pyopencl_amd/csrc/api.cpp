@@ -78,6 +78,7 @@ int cgamd_tune(const char *key, int value) {
     else if (k == "dev.spmm_wgs") g_tune.spmm_wgs = value;
     else if (k == "dev.spmm_lead") g_tune.spmm_lead = value;
     else if (k == "dev.spmm_wide_max") g_tune.spmm_wide_max = value;
+    else if (k == "dev.line_host_route") g_tune.dev_line_host_route = value;
     else known = false;
     });
     if (!known) return fail(CGAMD_ERR_INVALID, "tune: unknown key " + k);

@@ -134,6 +134,7 @@ struct Tuning {
     int spmm_wgs = 0;               // row-major SpMM sweep: work-groups per XCD (0 = 64)
     int spmm_lead = 0;              // row-major SpMM sweep: steps a wave may gather ahead of its XCD's slowest (0 = default, -1 = unpaced)
     int spmm_wide_max = -1;         // multi-RHS, RHS-major: largest row_blocks x nRHS for the one-work-group-per-RHS form (-1 = 4096, 0 = never)
+    int dev_line_host_route = 0;    // cgamd_solver_set_preconditioner_line: 1 = extract on the device, factor and plan by the host route (source 3)
 };
 // g_tune is the process-wide configuration cgamd_tune edits (under a mutex).  Nothing on a compute path reads it
 // directly: every solver / distributed handle copies it at creation (tune_snapshot()), and each C-ABI entry installs the
@@ -374,6 +375,27 @@ int launch_pcg_tri(int dtype, const TriLaunch &t, bool update, const void *q, vo
 int tri_strided_grid(int nsegs);            // work-groups = r.z / r.r partials per RHS (at most 1024)
 int launch_pcg_tri_strided(int dtype, const TriLaunch &t, bool update, const void *q, void *r, void *z, long long ld, const void *alpha,
                            int nrhs, void *part_rz, void *part_rr, hipStream_t st);
+// preconditioners built from the matrix on the device (precond_build.hip); n_user = the caller's rows, n = with the padding rows.
+// lower / diag / upper <- the CSR entries at column - row = -stride / 0 / +stride, entries at the same column summed (n_user values)
+int launch_line_extract(int dtype, int n_user, int stride, const void *vals, const int *ptr, const int *cols, void *lower, void *diag,
+                        void *upper, hipStream_t st);
+// m[i] = 1 / A[i][i]; *err (preset to all ones) <- the smallest row with a zero, missing or non-finite diagonal
+int launch_jacobi_extract(int dtype, int n_user, const void *vals, const int *ptr, const int *cols, void *m, unsigned long long *err,
+                          hipStream_t st);
+// flags[i] = i < stride or x[i] and y[i - stride] are both exactly zero (x, y: n values)
+int launch_line_flags(int dtype, int n, int stride, const void *x, const void *y, unsigned char *flags, hipStream_t st);
+// *longest (preset to 0) <- rows of the longest run first, first + stride, ... between flags; a walk gives up at cap rows (the word
+// then holds a value in [cap, cap + 8))
+int launch_line_longest(int n, int stride, const unsigned char *flags, int cap, int *longest, hipStream_t st);
+// Thomas factors -l, -w c, w of every pre-segment, one thread each; *err (preset to all ones) <- (row << 2) | kind of the smallest
+// failing row: kind 0 non-finite entry, 1 zero or non-finite pivot, 2 pivot too small
+int launch_line_factor(int dtype, int n_user, int stride, const unsigned char *pre, const void *lower, const void *diag,
+                       const void *upper, void *nl, void *ne, void *w, unsigned long long *err, hipStream_t st);
+// count: line_count_ints(n) ints <- the flagged rows before every 256-row block, the total in its last entry
+int line_count_ints(int n);
+int launch_line_count(int n, const unsigned char *flags, int *count, hipStream_t st);
+// the flagged rows in order: out[k] = row, or with pairs out[2 k] = row, out[2 k + 1] = rows up to the chain's next flag
+int launch_line_emit(int n, int stride, bool pairs, const unsigned char *flags, const int *block_off, int *out, hipStream_t st);
 // pcg_aypx_beta with p = z + beta p (z per right-hand side at stride ld), P thread-strided partials
 int launch_pcg_aypx_beta_z(int dtype, int n, void *p, const void *z, long long ld, const void *part_rz, const void *part_rr, int P, int nrhs,
                            const CgScalars &sc, void *rho2, void *xs, hipStream_t st);

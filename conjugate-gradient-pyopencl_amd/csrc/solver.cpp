@@ -51,6 +51,10 @@ struct cgamd_solver {
     TriLaunch tri;
     void *tri_coef = nullptr, *tri_part = nullptr;
     int *tri_cstart = nullptr;
+    // where the preconditioner in force came from (cgamd_solver_preconditioner_source: 0 none, 1 the caller's arrays, 2 / 3 the
+    // matrix) and, for one built from the matrix, what cgamd_solver_reload_matrix builds again: kind 1 = Jacobi, 2 = the lines at
+    // pre_stride
+    int pre_source = 0, pre_kind = 0, pre_stride = 0;
     CgScalars sc;
     bool rhs_set = false;
     int iters = 0;  // iterations enqueued since set_rhs
@@ -492,6 +496,10 @@ int cgamd_solver_create(cgamd_ctx *ctx, int dtype, int size, long long nnz, cons
     return CGAMD_OK;
 }
 
+static int diag_impl(cgamd_solver *s, const void *m, int on_device);
+static int line_from_matrix(cgamd_solver *s, const std::string &who, int stride);
+static int jacobi_from_matrix(cgamd_solver *s, const std::string &who);
+
 // New matrix VALUES / PATTERN of the same size into an existing handle (host arrays; the handle must own its matrix):
 // what the stateless cg() needs to reuse its cached device state -- allocations, stream, captured graphs -- from one call
 // to the next.  The pattern-dependent plan is recomputed only when the row pointers differ from the ones uploaded before.
@@ -529,6 +537,14 @@ int cgamd_solver_reload_matrix(cgamd_solver *s, const void *aValues, const int *
         if (!had && s->codes) destroy_graphs(s);
     }
     CG_HIP(hipStreamSynchronize(st));   // the host arrays may go away after return
+    if (s->pre_source >= 2) {           // a preconditioner built from the matrix follows it (one from the caller's arrays is kept)
+        const int rc = s->pre_kind == 1 ? jacobi_from_matrix(s, "reload_matrix") : line_from_matrix(s, "reload_matrix", s->pre_stride);
+        if (rc) {                       // the matrix is loaded; the old factors belong to the old one
+            const std::string why = cgamd_last_error();
+            (void)diag_impl(s, nullptr, 0);
+            return fail(rc, why);
+        }
+    }
     return CGAMD_OK;
 }
 
@@ -632,11 +648,15 @@ static void drop_tridiag(cgamd_solver *s) {
 int cgamd_solver_set_preconditioner(cgamd_solver *s, const void *m, int on_device) {
     if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner: solver is NULL");
     TuneScope ts(&s->tune);
+    return diag_impl(s, m, on_device);
+}
+static int diag_impl(cgamd_solver *s, const void *m, int on_device) {
     CG_HIP(hipSetDevice(s->ctx->device));
     CG_HIP(hipStreamSynchronize(s->ctx->stream));
     destroy_graphs(s);
     s->rhs_set = false;
     drop_tridiag(s);
+    s->pre_source = s->pre_kind = s->pre_stride = 0;
     if (!m) {
         if (s->mdiag) { (void)hipFree(s->mdiag); s->mdiag = nullptr; }
         apply_wide_order(s);
@@ -651,6 +671,7 @@ int cgamd_solver_set_preconditioner(cgamd_solver *s, const void *m, int on_devic
     if (s->n != s->n_user) CG_HIP(hipMemsetAsync(s->mdiag, 0, (size_t)s->n * vs, s->ctx->stream));
     CG_HIP(hipMemcpyAsync(s->mdiag, m, (size_t)s->n_user * vs, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->ctx->stream));
     CG_HIP(hipStreamSynchronize(s->ctx->stream));
+    s->pre_source = 1;
     if (!s->resw.ok)
         if (int rc2 = setup_resident_wide_plan(s)) return rc2;      // (skipped at creation where the one-XCD loop runs the plain recurrence)
     apply_wide_order(s);
@@ -732,31 +753,11 @@ static int tri_factor(cgamd_solver *s, const std::string &who, int stride, const
     return CGAMD_OK;
 }
 
-// Tridiagonal M: z solves M z = r (the reference PCG's spsolve branch, helmFE_var.py:561-562).  Factored here once, in double /
-// complex double (Thomas LU, no pivoting: u_0 = b_0, l_i = a_i / u_{i-1}, u_i = b_i - l_i c_{i-1}); the kernels get -l, -w c and
-// w = 1/u in the value type.  Rows where both couplings to the row before vanish start a segment; chunks of at most
-// tri_chunk_rows() rows start at segment starts when every segment fits one (no carry between work-groups), else they are plain
-// slices and the sweep takes its three-launch form.  Everything is checked before the handle changes.
-int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, const void *diag, const void *upper, int on_device) {
-    if (!s || !lower || !diag || !upper) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag: null argument");
-    TuneScope ts(&s->tune);
-    CG_HIP(hipSetDevice(s->ctx->device));
-    hipStream_t st = s->ctx->stream;
-    CG_HIP(hipStreamSynchronize(st));
-    const int n = s->n, dt = s->dtype;
-    const size_t vs = dtype_size(dt);
-    TriFactors f;
-    if (int rc = tri_factor(s, "set_preconditioner_tridiag", 1, lower, diag, upper, on_device, f)) return rc;
-    const std::vector<unsigned char> &coef = f.coef;
-    const std::vector<char> &l_zero = f.l_zero, &e_zero = f.e_zero;
-    const size_t pitch = f.pitch;
-    // segment starts and the chunk plan
+// Chunk boundaries of the stride-1 sweep from the segment list (seg: the first rows in order, then n): O(segments).  Returns
+// whether the sweep takes its long form (a segment does not fit one chunk: plain slices of Cmax rows).
+static bool tri_plan_chunks(const std::vector<int> &seg, int n, int dt, std::vector<int> &starts) {
     const int Cmax = tri_chunk_rows(dt), R = Cmax / kBlock;
-    std::vector<int> seg;
-    for (int i = 0; i < n; ++i)
-        if (i == 0 || (l_zero[i] && e_zero[i - 1])) seg.push_back(i);
-    seg.push_back(n);
-    std::vector<int> starts{0};
+    starts.assign(1, 0);
     bool longform = false;
     for (size_t k = 1; k < seg.size() && !longform; ++k) {
         if (seg[k] - starts.back() / R * R <= Cmax) continue;        // segment k-1 still fits the current chunk
@@ -771,23 +772,26 @@ int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, 
         for (int i = 0; i < n; i += Cmax) starts.push_back(i);
     }
     starts.push_back(n);
-    const int nchunks = (int)starts.size() - 1, grid = std::min(nchunks, 1024);
-    // the handle changes from here on
+    return longform;
+}
+
+// The handle takes a factored tridiagonal M over.  coef (3 x pitch values: -l, -w c, w) and plan (stride 1: count + 1 chunk
+// boundaries; stride > 1: count (first row, length) pairs) are device allocations, filled, that belong to the handle from here on
+// -- also when this fails.  Everything that can be wrong with M was checked before.
+static int tri_install(cgamd_solver *s, void *coef, size_t pitch, int *plan, int stride, int count, bool longform) {
+    const int dt = s->dtype;
+    const size_t vs = dtype_size(dt);
+    const int grid = stride == 1 ? std::min(count, 1024) : tri_strided_grid(count);
     destroy_graphs(s);
     s->rhs_set = false;
     drop_tridiag(s);
+    s->pre_source = s->pre_kind = s->pre_stride = 0;
     if (s->mdiag) { (void)hipFree(s->mdiag); s->mdiag = nullptr; }
-    int rc = dmalloc(&s->tri_coef, coef.size(), "tridiagonal factors");
-    if (!rc) rc = dmalloc((void **)&s->tri_cstart, starts.size() * 4, "tridiagonal chunk plan");
-    if (!rc) rc = dmalloc(&s->tri_part, 2 * acc_size(dt) * (size_t)grid * s->nrhs, "partials_rz/rr (tridiagonal)");
-    if (!rc && longform) rc = dmalloc(&s->tri.maps, (size_t)tri_maps_values(nchunks, s->nrhs) * vs, "tridiagonal chunk maps");
+    s->tri_coef = coef;
+    s->tri_cstart = plan;
+    int rc = dmalloc(&s->tri_part, 2 * acc_size(dt) * (size_t)grid * s->nrhs, "partials_rz/rr (tridiagonal)");
+    if (!rc && longform) rc = dmalloc(&s->tri.maps, (size_t)tri_maps_values(count, s->nrhs) * vs, "tridiagonal chunk maps");
     if (!rc && !s->rho2) rc = dmalloc(&s->rho2, 2 * vs * (size_t)s->nrhs, "rho");
-    if (!rc) {
-        hipError_t e = hipMemcpyAsync(s->tri_coef, coef.data(), coef.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(s->tri_cstart, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(CGAMD_ERR_HIP, std::string("set_preconditioner_tridiag upload: ") + hipGetErrorString(e));
-    }
     if (rc) {
         drop_tridiag(s);
         apply_wide_order(s);
@@ -795,11 +799,66 @@ int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, 
     }
     char *cb = static_cast<char *>(s->tri_coef);
     s->tri.nl = cb; s->tri.ne = cb + pitch * vs; s->tri.w = cb + 2 * pitch * vs;
-    s->tri.cstart = s->tri_cstart;
-    s->tri.nchunks = nchunks; s->tri.grid = grid; s->tri.longform = longform;
+    if (stride == 1) {
+        s->tri.cstart = s->tri_cstart;
+        s->tri.nchunks = count; s->tri.longform = longform;
+    } else {
+        s->tri.stride = stride;
+        s->tri.segs = s->tri_cstart;
+        s->tri.nsegs = count;
+    }
+    s->tri.grid = grid;
     s->tri_on = true;
+    s->pre_source = 1;
     apply_wide_order(s);
     return CGAMD_OK;
+}
+
+// host factors and a host plan to the device, then tri_install; the handle is unchanged when the upload fails
+static int tri_upload_install(cgamd_solver *s, const std::string &who, const TriFactors &f, const std::vector<int> &plan, int stride,
+                              int count, bool longform) {
+    hipStream_t st = s->ctx->stream;
+    void *coef = nullptr;
+    int *dplan = nullptr;
+    int rc = dmalloc(&coef, f.coef.size(), "tridiagonal factors");
+    if (!rc) rc = dmalloc((void **)&dplan, plan.size() * 4, stride == 1 ? "tridiagonal chunk plan" : "tridiagonal segment plan");
+    if (!rc) {
+        hipError_t e = hipMemcpyAsync(coef, f.coef.data(), f.coef.size(), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(dplan, plan.data(), plan.size() * 4, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = fail(CGAMD_ERR_HIP, who + " upload: " + hipGetErrorString(e));
+    }
+    if (rc) {
+        if (coef) (void)hipFree(coef);
+        if (dplan) (void)hipFree(dplan);
+        return rc;
+    }
+    return tri_install(s, coef, f.pitch, dplan, stride, count, longform);
+}
+
+// Tridiagonal M: z solves M z = r (the reference PCG's spsolve branch, helmFE_var.py:561-562).  Factored here once, in double /
+// complex double (Thomas LU, no pivoting: u_0 = b_0, l_i = a_i / u_{i-1}, u_i = b_i - l_i c_{i-1}); the kernels get -l, -w c and
+// w = 1/u in the value type.  Rows where both couplings to the row before vanish start a segment; chunks of at most
+// tri_chunk_rows() rows start at segment starts when every segment fits one (no carry between work-groups), else they are plain
+// slices and the sweep takes its three-launch form.  Everything is checked before the handle changes.
+static int tridiag_impl(cgamd_solver *s, const std::string &who, const void *lower, const void *diag, const void *upper, int on_device) {
+    CG_HIP(hipSetDevice(s->ctx->device));
+    CG_HIP(hipStreamSynchronize(s->ctx->stream));
+    const int n = s->n;
+    TriFactors f;
+    if (int rc = tri_factor(s, who, 1, lower, diag, upper, on_device, f)) return rc;
+    std::vector<int> seg;
+    for (int i = 0; i < n; ++i)
+        if (i == 0 || (f.l_zero[i] && f.e_zero[i - 1])) seg.push_back(i);
+    seg.push_back(n);
+    std::vector<int> starts;
+    const bool longform = tri_plan_chunks(seg, n, s->dtype, starts);
+    return tri_upload_install(s, who, f, starts, 1, (int)starts.size() - 1, longform);
+}
+int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, const void *diag, const void *upper, int on_device) {
+    if (!s || !lower || !diag || !upper) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag: null argument");
+    TuneScope ts(&s->tune);
+    return tridiag_impl(s, "set_preconditioner_tridiag", lower, diag, upper, on_device);
 }
 
 // The same M at a distance: lower[i] = M[i][i-stride], upper[i] = M[i][i+stride] (a line preconditioner along the grid axis whose
@@ -807,20 +866,14 @@ int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, 
 // stored couplings round to zero in the value type (the rule of the stride-1 form, at distance stride), and the plan is the list
 // of those segments (first row, length) ordered by first row: one thread of pcg_tri_strided_kernel each, whatever their length.
 // stride 1 is cgamd_solver_set_preconditioner_tridiag itself.
-int cgamd_solver_set_preconditioner_tridiag_strided(cgamd_solver *s, int stride, const void *lower, const void *diag, const void *upper,
-                                                    int on_device) {
-    if (!s || !lower || !diag || !upper) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag_strided: null argument");
-    if (stride < 1 || stride >= s->n_user)
-        return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag_strided: stride must be in [1, size - 1]");
-    if (stride == 1) return cgamd_solver_set_preconditioner_tridiag(s, lower, diag, upper, on_device);
-    TuneScope ts(&s->tune);
+static int tridiag_strided_impl(cgamd_solver *s, const std::string &who, int stride, const void *lower, const void *diag,
+                                const void *upper, int on_device) {
+    if (stride == 1) return tridiag_impl(s, who, lower, diag, upper, on_device);
     CG_HIP(hipSetDevice(s->ctx->device));
-    hipStream_t st = s->ctx->stream;
-    CG_HIP(hipStreamSynchronize(st));
-    const int n = s->n, dt = s->dtype;
-    const size_t vs = dtype_size(dt);
+    CG_HIP(hipStreamSynchronize(s->ctx->stream));
+    const int n = s->n;
     TriFactors f;
-    if (int rc = tri_factor(s, "set_preconditioner_tridiag_strided", stride, lower, diag, upper, on_device, f)) return rc;
+    if (int rc = tri_factor(s, who, stride, lower, diag, upper, on_device, f)) return rc;
     // row i starts a segment when it heads its chain or both couplings to row i - stride vanish; its length is known once the
     // chain's next start (or end) is: walk the rows backwards, carrying per chain the rows seen since the last start
     std::vector<int> segs;      // (first row, length) pairs, built last segment first
@@ -837,36 +890,169 @@ int cgamd_solver_set_preconditioner_tridiag_strided(cgamd_solver *s, int stride,
         }
         std::reverse(segs.begin(), segs.end());
     }
-    const int nsegs = (int)(segs.size() / 2), grid = tri_strided_grid(nsegs);
-    // the handle changes from here on
-    destroy_graphs(s);
-    s->rhs_set = false;
-    drop_tridiag(s);
-    if (s->mdiag) { (void)hipFree(s->mdiag); s->mdiag = nullptr; }
-    int rc = dmalloc(&s->tri_coef, f.coef.size(), "tridiagonal factors");
-    if (!rc) rc = dmalloc((void **)&s->tri_cstart, segs.size() * 4, "tridiagonal segment plan");
-    if (!rc) rc = dmalloc(&s->tri_part, 2 * acc_size(dt) * (size_t)grid * s->nrhs, "partials_rz/rr (tridiagonal)");
-    if (!rc && !s->rho2) rc = dmalloc(&s->rho2, 2 * vs * (size_t)s->nrhs, "rho");
-    if (!rc) {
-        hipError_t e = hipMemcpyAsync(s->tri_coef, f.coef.data(), f.coef.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(s->tri_cstart, segs.data(), segs.size() * 4, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(CGAMD_ERR_HIP, std::string("set_preconditioner_tridiag_strided upload: ") + hipGetErrorString(e));
+    return tri_upload_install(s, who, f, segs, stride, (int)(segs.size() / 2), false);
+}
+int cgamd_solver_set_preconditioner_tridiag_strided(cgamd_solver *s, int stride, const void *lower, const void *diag, const void *upper,
+                                                    int on_device) {
+    if (!s || !lower || !diag || !upper) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag_strided: null argument");
+    if (stride < 1 || stride >= s->n_user)
+        return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag_strided: stride must be in [1, size - 1]");
+    TuneScope ts(&s->tune);
+    return tridiag_strided_impl(s, stride == 1 ? "set_preconditioner_tridiag" : "set_preconditioner_tridiag_strided", stride, lower,
+                                diag, upper, on_device);
+}
+
+// ---- preconditioners built from the handle's own matrix, on the device (precond_build.hip) ----------------------------------------
+namespace {
+struct DevScratch {      // device allocations of one call, freed on return unless the handle took them
+    std::vector<void *> ptrs;
+    ~DevScratch() {
+        for (void *p : ptrs)
+            if (p) (void)hipFree(p);
     }
-    if (rc) {
-        drop_tridiag(s);
-        apply_wide_order(s);
+    int get(void **p, size_t bytes, const char *what) {
+        const int rc = dmalloc(p, bytes, what);
+        if (!rc) ptrs.push_back(*p);
         return rc;
     }
-    char *cb = static_cast<char *>(s->tri_coef);
-    s->tri.nl = cb; s->tri.ne = cb + f.pitch * vs; s->tri.w = cb + 2 * f.pitch * vs;
-    s->tri.stride = stride;
-    s->tri.segs = s->tri_cstart;
-    s->tri.nsegs = nsegs; s->tri.grid = grid;
-    s->tri_on = true;
-    apply_wide_order(s);
-    return CGAMD_OK;
+    void release(void *p) {
+        for (void *&q : ptrs)
+            if (q == p) q = nullptr;
+    }
+};
+}  // namespace
+
+// Longest pre-segment the device factorisation takes, one thread per pre-segment; beyond it cgamd_solver_set_preconditioner_line
+// extracts on the device and factors by the host route (source 3).  PROVISIONAL: the value is to be the largest segment length at
+// which `scripts/line_setup_ab.py --groups chains` finds the device no slower than the host; that table
+// (profiles/line_setup/long_segments.log) has not been measured yet.
+constexpr int kLineHostRouteRows = 65536;
+
+// M = the matrix entries at column - row in {-stride, 0, +stride}: extracted, factored and planned on the device.  Nothing on the
+// handle changes before tri_install (or the host route's); the temporaries are three n-long value arrays, n flag bytes, one int per
+// 256 rows and three words.
+static int line_from_matrix(cgamd_solver *s, const std::string &who, int stride) {
+    CG_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    CG_HIP(hipStreamSynchronize(st));
+    const int n = s->n, nu = s->n_user, dt = s->dtype;
+    const size_t vs = dtype_size(dt);
+    DevScratch tmp;
+    void *abc = nullptr, *words = nullptr;
+    unsigned char *flags = nullptr;
+    int *count = nullptr;
+    int rc = tmp.get(&abc, 3 * (size_t)n * vs, "line preconditioner: diagonals");
+    if (!rc) rc = tmp.get((void **)&flags, (size_t)n, "line preconditioner: flags");
+    if (!rc) rc = tmp.get((void **)&count, (size_t)line_count_ints(n) * 4, "line preconditioner: block counts");
+    if (!rc) rc = tmp.get(&words, 16, "line preconditioner: words");
+    if (rc) return rc;
+    char *lower = static_cast<char *>(abc), *diag = lower + (size_t)n * vs, *upper = diag + (size_t)n * vs;
+    unsigned long long *err = static_cast<unsigned long long *>(words);
+    int *longest = reinterpret_cast<int *>(err + 1);
+    CG_HIP(hipMemsetAsync(abc, 0, 3 * (size_t)n * vs, st));      // (the padding rows: no couplings)
+    CG_HIP(hipMemsetAsync(err, 0xff, 8, st));
+    CG_HIP(hipMemsetAsync(longest, 0, 4, st));
+    if ((rc = launch_line_extract(dt, nu, stride, s->vals, s->ptr, s->cols, lower, diag, upper, st))) return rc;
+    if ((rc = launch_line_flags(dt, n, stride, lower, upper, flags, st))) return rc;
+    const int route = s->tune.dev_line_host_route;       // 1 / -1: the route is forced, nothing to measure
+    int longest_h = 0;
+    if (route == 0) {
+        if ((rc = launch_line_longest(n, stride, flags, kLineHostRouteRows + 1, longest, st))) return rc;
+        CG_HIP(hipMemcpyAsync(&longest_h, longest, 4, hipMemcpyDeviceToHost, st));
+        CG_HIP(hipStreamSynchronize(st));
+    }
+    if (route > 0 || (route == 0 && longest_h > kLineHostRouteRows)) {
+        // few long segments: one thread each is slower than the host's serial loop.  The extracted diagonals go the host route.
+        rc = tridiag_strided_impl(s, who, stride, lower, diag, upper, 1);
+        if (!rc) { s->pre_source = 3; s->pre_kind = 2; s->pre_stride = stride; }
+        return rc;
+    }
+    const int E = (int)(16 / vs);
+    const size_t pitch = ((size_t)n + 2 * E - 1) / (2 * E) * (2 * E);      // as tri_factor lays the factors out
+    void *coef = nullptr;
+    if ((rc = tmp.get(&coef, 3 * pitch * vs, "tridiagonal factors"))) return rc;
+    char *nl = static_cast<char *>(coef), *ne = nl + pitch * vs, *w = ne + pitch * vs;
+    CG_HIP(hipMemsetAsync(coef, 0, 3 * pitch * vs, st));           // (the padding rows keep 0 everywhere: decoupled, z = 0 there)
+    if ((rc = launch_line_factor(dt, nu, stride, flags, lower, diag, upper, nl, ne, w, err, st))) return rc;
+    unsigned long long err_h = 0;
+    CG_HIP(hipMemcpyAsync(&err_h, err, 8, hipMemcpyDeviceToHost, st));
+    CG_HIP(hipStreamSynchronize(st));
+    if (err_h != ~0ull) {
+        const std::string row = std::to_string(err_h >> 2);
+        switch ((int)(err_h & 3)) {
+        case 0: return fail(CGAMD_ERR_INVALID, who + ": non-finite entry in row " + row);
+        case 1: return fail(CGAMD_ERR_INVALID, who + ": zero or non-finite pivot in row " + row + " (the factorisation does not pivot)");
+        default: return fail(CGAMD_ERR_INVALID, who + ": pivot too small in row " + row);
+        }
+    }
+    // the final segments, from the factors as stored: flags, the flagged rows before every block, their number
+    if ((rc = launch_line_flags(dt, n, stride, nl, ne, flags, st))) return rc;
+    if ((rc = launch_line_count(n, flags, count, st))) return rc;
+    int nsegs = 0;
+    CG_HIP(hipMemcpyAsync(&nsegs, count + line_count_ints(n) - 1, 4, hipMemcpyDeviceToHost, st));
+    CG_HIP(hipStreamSynchronize(st));
+    int *plan = nullptr;
+    int nplan = nsegs;
+    bool longform = false;
+    if (stride > 1) {       // the plan of pcg_tri_strided_kernel: (first row, length) ordered by first row
+        if ((rc = tmp.get((void **)&plan, (size_t)nsegs * 8, "tridiagonal segment plan"))) return rc;
+        if ((rc = launch_line_emit(n, stride, true, flags, count, plan, st))) return rc;
+    } else {                // the segment starts go to the host chunk planner
+        int *starts_dev = nullptr;
+        if ((rc = tmp.get((void **)&starts_dev, (size_t)nsegs * 4, "tridiagonal segment starts"))) return rc;
+        if ((rc = launch_line_emit(n, 1, false, flags, count, starts_dev, st))) return rc;
+        std::vector<int> seg((size_t)nsegs + 1), starts;
+        CG_HIP(hipMemcpyAsync(seg.data(), starts_dev, (size_t)nsegs * 4, hipMemcpyDeviceToHost, st));
+        CG_HIP(hipStreamSynchronize(st));
+        seg[(size_t)nsegs] = n;
+        longform = tri_plan_chunks(seg, n, dt, starts);
+        nplan = (int)starts.size() - 1;
+        if ((rc = tmp.get((void **)&plan, starts.size() * 4, "tridiagonal chunk plan"))) return rc;
+        CG_HIP(hipMemcpyAsync(plan, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
+        CG_HIP(hipStreamSynchronize(st));
+    }
+    CG_HIP(hipStreamSynchronize(st));
+    tmp.release(coef);
+    tmp.release(plan);
+    rc = tri_install(s, coef, pitch, plan, stride, nplan, longform);
+    if (!rc) { s->pre_source = 2; s->pre_kind = 2; s->pre_stride = stride; }
+    return rc;
 }
+int cgamd_solver_set_preconditioner_line(cgamd_solver *s, int stride) {
+    if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner_line: solver is NULL");
+    if (stride < 1 || stride >= s->n_user) return fail(CGAMD_ERR_INVALID, "set_preconditioner_line: stride must be in [1, size - 1]");
+    TuneScope ts(&s->tune);
+    return line_from_matrix(s, "set_preconditioner_line", stride);
+}
+
+// m = 1 / diag(A) on the device, then the diagonal form itself
+static int jacobi_from_matrix(cgamd_solver *s, const std::string &who) {
+    CG_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    CG_HIP(hipStreamSynchronize(st));
+    DevScratch tmp;
+    void *m = nullptr, *err = nullptr;
+    int rc = tmp.get(&m, (size_t)s->n_user * dtype_size(s->dtype), "Jacobi preconditioner");
+    if (!rc) rc = tmp.get(&err, 8, "Jacobi preconditioner: error word");
+    if (rc) return rc;
+    CG_HIP(hipMemsetAsync(err, 0xff, 8, st));
+    if ((rc = launch_jacobi_extract(s->dtype, s->n_user, s->vals, s->ptr, s->cols, m, static_cast<unsigned long long *>(err), st))) return rc;
+    unsigned long long err_h = 0;
+    CG_HIP(hipMemcpyAsync(&err_h, err, 8, hipMemcpyDeviceToHost, st));
+    CG_HIP(hipStreamSynchronize(st));
+    if (err_h != ~0ull)
+        return fail(CGAMD_ERR_INVALID, who + ": zero, missing or non-finite diagonal in row " + std::to_string(err_h));
+    rc = diag_impl(s, m, 1);
+    if (!rc) { s->pre_source = 2; s->pre_kind = 1; }
+    return rc;
+}
+int cgamd_solver_set_preconditioner_jacobi(cgamd_solver *s) {
+    if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner_jacobi: solver is NULL");
+    TuneScope ts(&s->tune);
+    return jacobi_from_matrix(s, "set_preconditioner_jacobi");
+}
+
+int cgamd_solver_preconditioner_source(cgamd_solver *s) { return s ? s->pre_source : 0; }
 
 int cgamd_solver_iterate(cgamd_solver *s, int nIterations) {
     if (!s) return fail(CGAMD_ERR_INVALID, "iterate: solver is NULL");

@@ -123,7 +123,8 @@ int cgamd_solver_create(cgamd_ctx *ctx, int dtype, int size, long long nnz, cons
 int cgamd_solver_destroy(cgamd_solver *s);
 /* new values / pattern of the SAME size (size, nnz, nRHS, dtype) into a handle that owns its matrix (created from host
  * arrays): keeps allocations, stream and -- when the row pointers are unchanged -- the plan and the captured graphs.
- * The next call must be cgamd_solver_set_rhs. */
+ * The next call must be cgamd_solver_set_rhs.  A preconditioner from the caller's arrays is kept; one built from the matrix
+ * (cgamd_solver_set_preconditioner_line / _jacobi) is built again from the new matrix. */
 int cgamd_solver_reload_matrix(cgamd_solver *s, const void *aValues, const int *aPointers, const int *aCols);
 /* b, x0: nRHS*size values, host (on_device=0) or device (on_device=1) memory; x0 may be NULL (zeros).
  * Computes r = b - A x0, d = r, delta0 = r.r  (reference clcg.c:255-292) and resets the iteration count. */
@@ -193,6 +194,37 @@ int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, 
  * correctly and serially within each segment, i.e. slowly; the form is meant for grids. */
 int cgamd_solver_set_preconditioner_tridiag_strided(cgamd_solver *s, int stride, const void *lower, const void *diag,
                                                     const void *upper, int on_device);
+/* The line preconditioner of the handle's OWN matrix: M = the entries of A at column - row in {-stride, 0, +stride} (stride 1: the
+ * x-lines; nx: the y-lines; nx * ny: the z-lines of a grid numbered x fastest), extracted, factored and planned ON THE DEVICE -- a
+ * few passes over the matrix instead of three arrays cut out on the host and a serial factorisation there.  Everything not said here
+ * is the contract of cgamd_solver_set_preconditioner_tridiag_strided: same recurrence (l = a / u_prev, u = b - l c_prev, w = 1 / u
+ * in double / complex double, -l, -w c and w rounded once to the value type), same factor layout, same segment rule, same plan, same
+ * sweep kernels (stride 1: the scan sweep, 4 or 6 launches per iteration; stride > 1: one thread per segment), same errors with the
+ * same wording -- the row named is the smallest failing one -- and nothing on the handle changes on failure (a preconditioner set
+ * before stays in force).  Factors may differ from the array entries' in the last place (the host divides through complex
+ * arithmetic); results are held to tolerances against them and are bit-stable from call to call.
+ * Every handle: one that owns its matrix or borrows it (CGAMD_MATRIX_ON_DEVICE: the values as they are at the time of the call),
+ * every value type, any nRHS, whatever codes the SpMV runs on.  stride < 1 or stride >= size returns CGAMD_ERR_INVALID.
+ * Extraction: the columns of a row may be unsorted; entries of a row at the same column are summed in stored order in double /
+ * complex double, as the SpMV adds them up; a row without a stored diagonal has diagonal 0 (a zero pivot); padding rows stay
+ * decoupled.  Temporary device memory: three `size`-long value arrays and O(size) bytes of flags, freed before return; no array of
+ * `size` values crosses to the host.
+ * The factorisation runs one thread per pre-segment (a chain cut where both couplings of A are exactly zero; the final segments
+ * refine these).  LONG SEGMENTS: when the longest pre-segment exceeds 65536 rows (a 1-D chain; a provisional limit: the table of
+ * scripts/line_setup_ab.py that is to set it, device against host per segment length, is not measured yet) the diagonals are extracted on the device and
+ * then take the host route of the array entry -- same contract, slower setup, source 3 below.
+ * cgamd_solver_reload_matrix REBUILDS a preconditioner made by this entry or by cgamd_solver_set_preconditioner_jacobi from the new
+ * matrix (same kind, same stride); if that fails the matrix is loaded, the preconditioner is removed and the call returns the error
+ * naming the row.  Preconditioners from the caller's arrays are kept as they are. */
+int cgamd_solver_set_preconditioner_line(cgamd_solver *s, int stride);
+/* Jacobi from the handle's own matrix: m[i] = 1 / A[i][i] built on the device (entries at the same column summed as above, the
+ * division in double / complex double, rounded once to the value type), then exactly cgamd_solver_set_preconditioner's diagonal
+ * form, resident loops included.  A zero, missing or non-finite diagonal returns CGAMD_ERR_INVALID naming the first such row, the
+ * handle unchanged. */
+int cgamd_solver_set_preconditioner_jacobi(cgamd_solver *s);
+/* where the preconditioner in force came from -- 0: none; 1: the caller's arrays (the three entries above); 2: the matrix, built on
+ * the device; 3: the matrix, extracted on the device but factored by the host route (long segments) */
+int cgamd_solver_preconditioner_source(cgamd_solver *s);
 /* convenience: set_rhs + iterate + get_x (+ history if non-NULL, (nIterations+1)*nRHS values), host arrays */
 int cgamd_solver_solve(cgamd_solver *s, const void *b, void *x, int nIterations, void *history);
 /* the solver's SpMV (optionally fused with the d.q partial reduction) on caller vectors -- bench/profiling */
