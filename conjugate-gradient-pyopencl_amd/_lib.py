@@ -127,6 +127,9 @@ def load():
         "cgamd_dist_get_x": (ci, [vp, vp]),
         "cgamd_dist_history": (ci, [vp, vp, ci]),
         "cgamd_dist_synchronize": (ci, [vp]),
+        "cgamd_dist_set_preconditioner": (ci, [vp, vp]),
+        "cgamd_dist_set_preconditioner_jacobi": (ci, [vp]),
+        "cgamd_dist_set_preconditioner_line": (ci, [vp, ci]),
         "cgamd_p2p_mailbox_alloc": (ci, [vp, ll, ci, pvp, vp]),
         "cgamd_p2p_mailbox_free": (ci, [vp, vp]),
         "cgamd_dist_attach_p2p": (ci, [vp, vp, vp, vp]),

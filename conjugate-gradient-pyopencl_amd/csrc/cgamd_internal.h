@@ -377,8 +377,10 @@ int launch_pcg_tri_strided(int dtype, const TriLaunch &t, bool update, const voi
                            int nrhs, void *part_rz, void *part_rr, hipStream_t st);
 // preconditioners built from the matrix on the device (precond_build.hip); n_user = the caller's rows, n = with the padding rows.
 // lower / diag / upper <- the CSR entries at column - row = -stride / 0 / +stride, entries at the same column summed (n_user values)
-int launch_line_extract(int dtype, int n_user, int stride, const void *vals, const int *ptr, const int *cols, void *lower, void *diag,
-                        void *upper, hipStream_t st);
+// (only columns below col_limit count: the halo columns of a row-partitioned matrix are numbered from n_local on and are no line
+// neighbours, whatever their distance from the row)
+int launch_line_extract(int dtype, int n_user, int stride, const void *vals, const int *ptr, const int *cols, int col_limit, void *lower,
+                        void *diag, void *upper, hipStream_t st);
 // m[i] = 1 / A[i][i]; *err (preset to all ones) <- the smallest row with a zero, missing or non-finite diagonal
 int launch_jacobi_extract(int dtype, int n_user, const void *vals, const int *ptr, const int *cols, void *m, unsigned long long *err,
                           hipStream_t st);
@@ -396,6 +398,45 @@ int line_count_ints(int n);
 int launch_line_count(int n, const unsigned char *flags, int *count, hipStream_t st);
 // the flagged rows in order: out[k] = row, or with pairs out[2 k] = row, out[2 k + 1] = rows up to the chain's next flag
 int launch_line_emit(int n, int stride, bool pairs, const unsigned char *flags, const int *block_off, int *out, hipStream_t st);
+// ---- preconditioner setup shared by the single-GPU and the row-partitioned handle (precond_setup.cpp) ----
+// a factored tridiagonal M on the device: coef = 3 x pitch values (-l, -w c, w); plan = count + 1 chunk boundaries (stride 1) or
+// count (first row, length) pairs (stride > 1).  Both allocations belong to the caller.
+struct TriBuilt {
+    void *coef = nullptr;
+    size_t pitch = 0;
+    int *plan = nullptr;
+    int stride = 1, count = 0;
+    bool longform = false;
+    int source = 0;         // 2 = factored on the device, 3 = extracted on the device and factored by the host route
+};
+void tri_built_free(TriBuilt *b);
+// from M's three arrays (nu values each, host or device), factored and planned on the host; n >= nu: rows with the padding
+int tri_build_host(hipStream_t st, int dt, int nu, int n, const std::string &who, int stride, const void *lower, const void *diag,
+                   const void *upper, int on_device, TriBuilt *out);
+// from the CSR entries at column - row in {-stride, 0, +stride} with column < col_limit, on the device; route: Tuning::dev_line_host_route
+int tri_build_from_matrix(hipStream_t st, int dt, int nu, int n, int route, const std::string &who, int stride, const void *vals,
+                          const int *ptr, const int *cols, int col_limit, TriBuilt *out);
+// m[i] = 1 / A[i][i] (m: nu device values of the caller); CGAMD_ERR_INVALID names the smallest bad row
+int jacobi_build_from_matrix(hipStream_t st, int dt, int nu, const std::string &who, const void *vals, const int *ptr, const int *cols,
+                             void *m);
+// ---- PCG of the row-partitioned loop (vector.hip, p2p.hip): z lives in q's storage for every preconditioner; part = [2][P] partials
+// (r.z, then r.r); rho2 = two-entry parity buffer of rho = r.z (entry iter & 1), delta holds rho for cg_alpha
+// r -= alpha q ; z = m .* r (stored over q) ; partials of r.z and r.r
+int launch_pcg_jacobi_z(int dtype, int n, void *q_z, void *r, const void *m, const void *alpha, void *part_rz, void *part_rr, int grid,
+                        hipStream_t st);
+// red = {r.z, r.r} summed over all ranks (accumulator type).  mode 1: delta = rho2[0] = rho, history[0] = r.r, iter = 0;
+// mode 3: beta = rho / rho2[(iter - 1) & 1], delta = rho2[iter & 1] = rho, history[iter] = r.r
+int launch_pcg_scalars(int dtype, int mode, const void *red, const CgScalars &sc, void *rho2, hipStream_t st);
+// x += alpha d ; d = z + beta d (alpha, beta from the device scalars)
+int launch_pcg_xd_update(int dtype, int n, const void *z, void *d, void *x, const CgScalars &sc, hipStream_t st);
+// peer-to-peer: the two sums in ONE round (slot set 1 carries r.r and the epoch, the kMbPcg area r.z), rank order, then the scalar
+// step of launch_pcg_scalars (one work-group; advances *epoch)
+int launch_pcg_allreduce2_p2p(int dtype, int mode, const void *part_rz, const void *part_rr, int P, char *const *mailbox, int rank,
+                              int nranks, unsigned long long *epoch, const CgScalars &sc, void *rho2, hipStream_t st);
+// four-launch loop: that round and the beta step in every work-group's prologue, then x += alpha d and d = z + beta d
+int launch_pcg_aypx_beta_p2p(int dtype, int n, const void *z, void *d, void *x, const void *part_rz, const void *part_rr, int P,
+                             char *const *mailbox, int rank, int nranks, const unsigned long long *epoch, const CgScalars &sc, void *rho2,
+                             hipStream_t st, int vec_nt = 0);
 // pcg_aypx_beta with p = z + beta p (z per right-hand side at stride ld), P thread-strided partials
 int launch_pcg_aypx_beta_z(int dtype, int n, void *p, const void *z, long long ld, const void *part_rz, const void *part_rr, int P, int nrhs,
                            const CgScalars &sc, void *rho2, void *xs, hipStream_t st);

@@ -143,6 +143,13 @@ struct cgamd_dist {
     std::vector<int> xch_dst_off;      // where my entries land in each peer's halo numbering
     SlabComm slab_comm;
     int n_cus = 0;
+    // preconditioner (cgamd_dist_set_preconditioner*): 0 none, 1 diagonal (mdiag), 2 line (tri: factors cut at the rank's row range).
+    // z = M^-1 r lives in q's storage; part_pcg = [2][pcg_P] partials of r.z and r.r; rho2 = parity buffer of rho = r.z (delta holds
+    // rho for cg_alpha, history keeps r.r)
+    int pre_kind = 0, pcg_P = 0;
+    void *mdiag = nullptr, *tri_coef = nullptr, *part_pcg = nullptr, *rho2 = nullptr;
+    int *tri_plan = nullptr;
+    TriLaunch tri;
 };
 
 static int dalloc(void **p, size_t bytes, const char *what) {
@@ -239,6 +246,35 @@ static int enqueue_tail_cg1(cgamd_dist *d, hipStream_t st) {
     return launch_cg1_tail(dt, cg1_update_args(d, p2p), p2p ? d->epochs + 3 : nullptr, st);
 }
 
+// ---- preconditioned recurrence (cgamd_dist_set_preconditioner*): the SpMV (+ d.q) and the alpha step are the plain loop's, with
+// delta = rho = r.z; then r -= alpha q and z = M^-1 r over q's storage with partials of r.z and r.r, ONE global round for the two
+// sums, beta = rho / rho_old, x += alpha d, d = z + beta d.  M is rank-local (a diagonal, or lines cut at the row range): the
+// sweep needs no communication.
+static void *pcg_prr(const cgamd_dist *d) { return static_cast<char *>(d->part_pcg) + acc_size(d->dtype) * (size_t)d->pcg_P; }
+// update = true: r -= alpha q first (z over q); false: set_rhs, z0 of r0 into `z`
+static int pcg_sweep(cgamd_dist *d, bool update, void *z, hipStream_t st) {
+    const int dt = d->dtype, n = d->n_local;
+    if (d->pre_kind == 1) {
+        if (!update) return launch_pcg_axpy2_dot2(dt, true, n, z, d->x, d->q, d->r, d->mdiag, n, nullptr, 1, d->part_pcg, pcg_prr(d), d->pcg_P, st);
+        return launch_pcg_jacobi_z(dt, n, d->q, d->r, d->mdiag, d->sc.alpha, d->part_pcg, pcg_prr(d), d->pcg_P, st);
+    }
+    const void *q = update ? d->q : nullptr, *alpha = update ? d->sc.alpha : nullptr;
+    if (d->tri.stride > 1) return launch_pcg_tri_strided(dt, d->tri, update, q, d->r, z, n, alpha, 1, d->part_pcg, pcg_prr(d), st);
+    return launch_pcg_tri(dt, d->tri, update, q, d->r, z, n, alpha, 1, d->part_pcg, pcg_prr(d), st);
+}
+// {r.z, r.r} partials -> global sums -> the scalar step (mode 1 set_rhs, 3 beta).  RCCL: local reduce of two values, ONE ncclAllReduce
+// of count 2, scalar kernel; peer-to-peer: one launch
+static int pcg_reduce2(cgamd_dist *d, int mode, hipStream_t st) {
+    if (d->p2p) {
+        if (!d->p2p_attached) return fail(CGAMD_ERR_STATE, "p2p backend: call cgamd_dist_attach_p2p first");
+        return launch_pcg_allreduce2_p2p(d->dtype, mode, d->part_pcg, pcg_prr(d), d->pcg_P, d->mailbox_dev, d->rank, d->nranks, d->epochs + 2,
+                                         d->sc, d->rho2, st);
+    }
+    if (int rc = launch_reduce_to_acc(d->dtype, d->part_pcg, d->pcg_P, 2, d->red, st)) return rc;
+    if (int rc = allreduce_scalar(d, d->red, st, 2)) return rc;
+    return launch_pcg_scalars(d->dtype, mode, d->red, d->sc, d->rho2, st);
+}
+
 static int enqueue_iteration(cgamd_dist *d, hipStream_t st) {
     if (d->cg1) return enqueue_iteration_cg1(d, st);
     const int dt = d->dtype, n = d->n_local;
@@ -250,6 +286,11 @@ static int enqueue_iteration(cgamd_dist *d, hipStream_t st) {
                                   d->rotate, d->xch, st))) return rc;
         if ((rc = launch_p2p_allreduce(dt, 2, d->part_dq, d->plan.n_partials, d->mailbox_dev, d->rank, d->nranks, 0, d->epochs + 1,
                                        d->sc, st, d->epochs, d->epochs + 2))) return rc;
+        if (d->pre_kind) {      // [r -= alpha q, z = M^-1 r, r.z, r.r], [all-reduce of both, beta, x += alpha d, d = z + beta d]
+            if ((rc = pcg_sweep(d, true, d->q, st))) return rc;
+            return launch_pcg_aypx_beta_p2p(dt, n, d->q, d->d_ext, d->x, d->part_pcg, pcg_prr(d), d->pcg_P, d->mailbox_dev, d->rank, d->nranks,
+                                            d->epochs + 2, d->sc, d->rho2, st, d->plan.vec_nt);
+        }
         if ((rc = launch_axpy_dot(dt, n, d->q, d->r, n, d->sc.alpha, 1, d->part_rr, d->vgrid, st, d->plan.vec_nt))) return rc;
         return launch_aypx_beta_p2p(dt, n, d->r, d->d_ext, d->x, d->part_rr, d->vgrid, d->mailbox_dev, d->rank, d->nranks, 1,
                                     d->epochs + 2, d->sc, st, d->plan.vec_nt);
@@ -272,6 +313,11 @@ static int enqueue_iteration(cgamd_dist *d, hipStream_t st) {
         if ((rc = launch_spmv(dt, d->plan, n, d->nnz, d->vals, d->ptr, d->cols, d->d_ext, ldx, d->q, n, 1, d->d_ext, d->part_dq, st))) return rc;
     }
     if ((rc = reduce_all(d, d->part_dq, d->plan.n_partials, 0, 2, st))) return rc;
+    if (d->pre_kind) {
+        if ((rc = pcg_sweep(d, true, d->q, st))) return rc;
+        if ((rc = pcg_reduce2(d, 3, st))) return rc;
+        return launch_pcg_xd_update(dt, n, d->q, d->d_ext, d->x, d->sc, st);
+    }
     if ((rc = launch_axpy2_dot(dt, n, d->d_ext, d->x, d->q, d->r, n, d->sc.alpha, 1, d->part_rr, d->vgrid, st, d->plan.vec_nt))) return rc;
     if ((rc = reduce_all(d, d->part_rr, d->vgrid, 1, 3, st))) return rc;
     return launch_aypx(dt, n, d->r, d->d_ext, n, d->sc.beta, 1, st);
@@ -508,7 +554,7 @@ int cgamd_dist_destroy(cgamd_dist *d) {
     if (d->dict) (void)hipFree(d->dict);
     void *bufs[] = {d->x, d->r, d->q, d->b, d->d_ext, d->sendbuf, d->part_dq, d->part_rr, d->red, d->sc.alpha,
                     d->sc.beta, d->sc.delta, d->sc.history, d->sc.iter, d->s2, d->cg1_state, d->part_cg1, d->slab_sync, d->slab_map, d->ds_own[0], d->ds_own[1],
-                    d->push_dst_dev};
+                    d->push_dst_dev, d->mdiag, d->tri_coef, d->part_pcg, d->rho2, d->tri_plan, d->tri.maps};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     delete d;
@@ -532,9 +578,14 @@ int cgamd_dist_set_rhs(cgamd_dist *d, const void *b_local, const void *x0_local)
     if ((rc = launch_spmv(d->dtype, d->plan, d->n_local, d->nnz, d->vals, d->ptr, d->cols, d->d_ext, ldx, d->q, d->n_local, 1,
                           nullptr, nullptr, st))) return rc;
     if ((rc = launch_sub(d->dtype, d->n_local, d->b, d->q, d->r, d->n_local, 1, st))) return rc;
-    CG_HIP(hipMemcpyAsync(d->d_ext, d->r, vb, hipMemcpyDeviceToDevice, st));
-    if ((rc = launch_dot_partials(d->dtype, d->n_local, d->r, d->r, d->n_local, 1, d->part_rr, d->vgrid, st))) return rc;
-    if ((rc = reduce_all(d, d->part_rr, d->vgrid, 1, 1, st))) return rc;
+    if (d->pre_kind) {      // z0 = M^-1 r0, d = z0, rho0 = all-reduced r0.z0, history[0] = r0.r0
+        if ((rc = pcg_sweep(d, false, d->d_ext, st))) return rc;
+        if ((rc = pcg_reduce2(d, 1, st))) return rc;
+    } else {
+        CG_HIP(hipMemcpyAsync(d->d_ext, d->r, vb, hipMemcpyDeviceToDevice, st));
+        if ((rc = launch_dot_partials(d->dtype, d->n_local, d->r, d->r, d->n_local, 1, d->part_rr, d->vgrid, st))) return rc;
+        if ((rc = reduce_all(d, d->part_rr, d->vgrid, 1, 1, st))) return rc;
+    }
     if (d->cg1) {       // the residual lives in d_ext; p = s = 0 (the first iteration runs with beta = 0)
         CG_HIP(hipMemsetAsync(d->r, 0, vb, st));
         CG_HIP(hipMemsetAsync(d->s2, 0, vb, st));
@@ -553,7 +604,8 @@ int cgamd_dist_iterate(cgamd_dist *d, int nIterations) {
     if (int rc = ensure_history(d, d->iters + nIterations + 1)) return rc;
     hipStream_t st = d->ctx->stream;
     int left = nIterations;
-    if (d->slab.ok && nIterations >= std::max(1, d->tune.resident_wide_min)) {
+    // (the slab loop has no preconditioned form: such a handle runs its launched loop while a preconditioner is set)
+    if (d->slab.ok && !d->pre_kind && nIterations >= std::max(1, d->tune.resident_wide_min)) {
         // the whole call in one launch per 2^15 iterations (slab.hip); same state in and out as the launched loop below
         while (left > 0) {
             const int K = std::min(left, 1 << 15);
@@ -590,6 +642,116 @@ int cgamd_dist_iterate(cgamd_dist *d, int nIterations) {
     }
     d->iters += nIterations;
     if (d->cg1 && nIterations > 0) return enqueue_tail_cg1(d, st);
+    return CGAMD_OK;
+}
+
+// ---- preconditioners.  Collective in meaning, local in execution: nothing here communicates.  They take effect at the next
+// cgamd_dist_set_rhs; a failed call leaves the handle as it was.
+static void drop_graph(cgamd_dist *d) {
+    if (d->gexec) { (void)hipGraphExecDestroy(d->gexec); d->gexec = nullptr; }
+    if (d->graph) { (void)hipGraphDestroy(d->graph); d->graph = nullptr; }
+}
+static void drop_preconditioner(cgamd_dist *d) {
+    for (void *p : {d->mdiag, d->tri_coef, (void *)d->tri_plan, d->tri.maps, d->part_pcg})
+        if (p) (void)hipFree(p);
+    d->mdiag = d->tri_coef = d->part_pcg = nullptr;
+    d->tri_plan = nullptr;
+    d->tri = TriLaunch();
+    d->pre_kind = d->pcg_P = 0;
+    drop_graph(d);
+    d->rhs_set = false;
+}
+static int pre_begin(cgamd_dist *d, const char *who) {
+    if (d->cg1)
+        return fail(CGAMD_ERR_STATE, std::string(who) + ": the single-reduction loop (CGAMD_DIST_SINGLE_REDUCTION) has no PCG form");
+    CG_HIP(hipSetDevice(d->ctx->device));
+    CG_HIP(hipStreamSynchronize(d->ctx->stream));
+    return CGAMD_OK;
+}
+// what every preconditioned loop needs besides M: P pairs of partials and the rho parity buffer
+static int pre_buffers(cgamd_dist *d, int P, void **part, void **maps, int map_values) {
+    int rc = dalloc(part, 2 * acc_size(d->dtype) * (size_t)P, "partials_rz/rr");
+    if (!rc && map_values) rc = dalloc(maps, (size_t)map_values * dtype_size(d->dtype), "tridiagonal chunk maps");
+    if (!rc && !d->rho2) rc = dalloc(&d->rho2, 2 * dtype_size(d->dtype), "rho");
+    return rc;
+}
+// the handle takes m (n_local device values, its own allocation from here on) over
+static int install_diag(cgamd_dist *d, void *m) {
+    void *part = nullptr;
+    if (int rc = pre_buffers(d, d->vgrid, &part, nullptr, 0)) {
+        if (part) (void)hipFree(part);
+        (void)hipFree(m);
+        return rc;
+    }
+    drop_preconditioner(d);
+    d->mdiag = m; d->part_pcg = part; d->pcg_P = d->vgrid; d->pre_kind = 1;
+    return CGAMD_OK;
+}
+
+int cgamd_dist_set_preconditioner(cgamd_dist *d, const void *m_local) {
+    if (!d) return fail(CGAMD_ERR_INVALID, "dist_set_preconditioner: null handle");
+    TuneScope ts(&d->tune);
+    if (!m_local) {
+        CG_HIP(hipSetDevice(d->ctx->device));
+        CG_HIP(hipStreamSynchronize(d->ctx->stream));
+        drop_preconditioner(d);
+        return CGAMD_OK;
+    }
+    if (int rc = pre_begin(d, "dist_set_preconditioner")) return rc;
+    const size_t vb = (size_t)d->n_local * dtype_size(d->dtype);
+    void *m = nullptr;
+    if (int rc = dalloc(&m, vb, "preconditioner")) return rc;
+    hipError_t e = hipMemcpyAsync(m, m_local, vb, hipMemcpyDeviceToDevice, d->ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d->ctx->stream);
+    if (e != hipSuccess) { (void)hipFree(m); return fail(CGAMD_ERR_HIP, std::string("dist_set_preconditioner: ") + hipGetErrorString(e)); }
+    return install_diag(d, m);
+}
+
+int cgamd_dist_set_preconditioner_jacobi(cgamd_dist *d) {
+    if (!d) return fail(CGAMD_ERR_INVALID, "dist_set_preconditioner_jacobi: null handle");
+    TuneScope ts(&d->tune);
+    if (int rc = pre_begin(d, "dist_set_preconditioner_jacobi")) return rc;
+    void *m = nullptr;
+    if (int rc = dalloc(&m, (size_t)d->n_local * dtype_size(d->dtype), "Jacobi preconditioner")) return rc;
+    // the diagonal of local row i is local column i: the halo columns (>= n_local) never match a row
+    if (int rc = jacobi_build_from_matrix(d->ctx->stream, d->dtype, d->n_local, "dist_set_preconditioner_jacobi", d->vals, d->ptr, d->cols, m)) {
+        (void)hipFree(m);
+        return rc;
+    }
+    return install_diag(d, m);
+}
+
+int cgamd_dist_set_preconditioner_line(cgamd_dist *d, int stride) {
+    if (!d) return fail(CGAMD_ERR_INVALID, "dist_set_preconditioner_line: null handle");
+    TuneScope ts(&d->tune);
+    if (int rc = pre_begin(d, "dist_set_preconditioner_line")) return rc;
+    if (stride < 1 || stride >= d->n_local) return fail(CGAMD_ERR_INVALID, "dist_set_preconditioner_line: stride must be in [1, size - 1]");
+    // only columns below n_local count: halo slot h is local column n_local + h, and row n_local - 1 - k coupled to a halo slot would
+    // otherwise pass for a line neighbour at the right distance.  Lines therefore end at the rank's row range.
+    TriBuilt b;
+    int rc = tri_build_from_matrix(d->ctx->stream, d->dtype, d->n_local, d->n_local, d->tune.dev_line_host_route, "dist_set_preconditioner_line",
+                                   stride, d->vals, d->ptr, d->cols, d->n_local, &b);
+    if (rc) return rc;
+    const int P = b.stride == 1 ? std::min(b.count, 1024) : tri_strided_grid(b.count);
+    void *part = nullptr, *maps = nullptr;
+    if ((rc = pre_buffers(d, P, &part, &maps, b.longform ? tri_maps_values(b.count, 1) : 0))) {
+        if (part) (void)hipFree(part);
+        if (maps) (void)hipFree(maps);
+        tri_built_free(&b);
+        return rc;
+    }
+    drop_preconditioner(d);
+    const size_t vs = dtype_size(d->dtype);
+    char *cb = static_cast<char *>(b.coef);
+    d->tri_coef = b.coef; d->tri_plan = b.plan; d->part_pcg = part; d->pcg_P = P;
+    d->tri.nl = cb; d->tri.ne = cb + b.pitch * vs; d->tri.w = cb + 2 * b.pitch * vs;
+    d->tri.grid = P; d->tri.maps = maps;
+    if (b.stride == 1) {
+        d->tri.cstart = b.plan; d->tri.nchunks = b.count; d->tri.longform = b.longform;
+    } else {
+        d->tri.stride = b.stride; d->tri.segs = b.plan; d->tri.nsegs = b.count;
+    }
+    d->pre_kind = 2;
     return CGAMD_OK;
 }
 
@@ -788,11 +950,13 @@ int cgamd_dist_index_codes(cgamd_dist *d) { return d ? d->n_offsets : -CGAMD_ERR
 // stream operations per iteration of the loop this handle runs (kernel launches, plus RCCL calls with that backend)
 int cgamd_dist_loop_launches(cgamd_dist *d) {
     if (!d) return -CGAMD_ERR_INVALID;
-    if (d->slab.ok) return 0;
+    if (d->slab.ok && !d->pre_kind) return 0;
     if (d->cg1) return d->p2p ? 2 : (d->peer.empty() ? 4 : 6);
-    if (d->direct && d->p2p_attached) return 4;
-    if (d->p2p) return d->peer.empty() ? 5 : 7;
-    return d->peer.empty() ? 9 : 11;
+    // the preconditioned loops replace launches one for one; the stride-1 line sweep in its long form is three launches, not one
+    const int extra = (d->pre_kind == 2 && d->tri.longform) ? 2 : 0;
+    if (d->direct && d->p2p_attached) return 4 + extra;
+    if (d->p2p) return (d->peer.empty() ? 5 : 7) + extra;
+    return (d->peer.empty() ? 9 : 11) + extra;
 }
 
 int cgamd_dist_p2p_error(cgamd_dist *d) {

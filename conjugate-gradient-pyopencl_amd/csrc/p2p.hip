@@ -318,6 +318,146 @@ __global__ __launch_bounds__(kScalarBlock) void p2p_allreduce_kernel(const typen
     }
 }
 
+// ---- PCG: the two sums r.z and r.r in ONE round.  Slot set 1 carries r.r and the epoch as in the plain loop; r.z travels in the
+// kMbPcg area of the same mailbox, stored by the same lane before the epoch and read after it.  Reuse is safe for the reason slot
+// set 1's is.  rho = r.z drives beta (rho_old from the parity buffer rho2, so that work-group 0 may publish the new one while the
+// others still read the old) and, through delta, the next alpha; history keeps r.r.
+CG_DEV void pcg_deposit(char *const *mailbox, int s, int rank, double2 rz, double2 rr, unsigned long long ep) {
+    unsigned long long *slot = reinterpret_cast<unsigned long long *>(mailbox[s] + kMbSlots) + (64ll + rank) * 4;
+    unsigned long long *zs = reinterpret_cast<unsigned long long *>(mailbox[s] + kMbPcg) + (long long)rank * 2;
+    st_sys(zs, (unsigned long long)__double_as_longlong(rz.x));
+    st_sys(zs + 1, (unsigned long long)__double_as_longlong(rz.y));
+    st_sys(slot, (unsigned long long)__double_as_longlong(rr.x));
+    st_sys(slot + 1, (unsigned long long)__double_as_longlong(rr.y));
+    p2p_stores_done();
+    st_sys(slot + 2, ep);
+}
+// rank s's two sums from MY mailbox, once its epoch has arrived: v[0] = r.z, v[1] = r.r
+CG_DEV void pcg_collect(char *const *mailbox, int s, int rank, unsigned long long ep, double2 (&v)[2]) {
+    const unsigned long long *in = reinterpret_cast<const unsigned long long *>(mailbox[rank] + kMbSlots) + (64ll + s) * 4;
+    const unsigned long long *zs = reinterpret_cast<const unsigned long long *>(mailbox[rank] + kMbPcg) + (long long)s * 2;
+    if (!spin_until(in + 2, ep, mailbox[rank])) st_sys(reinterpret_cast<unsigned long long *>(mailbox[rank] + kMbError), 2ULL);
+    v[0] = make_double2(__longlong_as_double((long long)ld_sys(zs)), __longlong_as_double((long long)ld_sys(zs + 1)));
+    v[1] = make_double2(__longlong_as_double((long long)ld_sys(in)), __longlong_as_double((long long)ld_sys(in + 1)));
+}
+
+// one work-group: local sums, the round, the scalar step (MODE 1 = set_rhs: delta = rho2[0] = rho, history[0] = r.r, iter = 0;
+// MODE 3 = beta of the staged loop).  Advances the slot epoch like p2p_allreduce_kernel.
+template <typename T, int MODE>
+__global__ __launch_bounds__(kScalarBlock) void pcg_allreduce2_p2p_kernel(const typename VT<T>::acc *part_rz, const typename VT<T>::acc *part_rr,
+                                                                          int P, char *const *mailbox, int rank, int nranks,
+                                                                          unsigned long long *epoch, T *delta, T *beta, T *history,
+                                                                          int history_cap, T *rho2, int *iter) {
+    using A = typename VT<T>::acc;
+    __shared__ A smem[kScalarBlock / kWave];
+    __shared__ double2 vz[64], vr[64];
+    const A lrz = sum_partials_block(part_rz, P, smem);
+    __syncthreads();
+    const A lrr = sum_partials_block(part_rr, P, smem);
+    const unsigned long long ep = *epoch + 1;
+    const int s = threadIdx.x;
+    if (s < nranks) {
+        pcg_deposit(mailbox, s, rank, to_acc2(lrz), to_acc2(lrr), ep);
+        double2 v[2];
+        pcg_collect(mailbox, s, rank, ep, v);
+        vz[s] = v[0];
+        vr[s] = v[1];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double2 tz = make_double2(0., 0.), tr = make_double2(0., 0.);
+        for (int k = 0; k < nranks; ++k) { tz.x += vz[k].x; tz.y += vz[k].y; tr.x += vr[k].x; tr.y += vr[k].y; }
+        const T rhoT = from_acc<T>(from_acc2<A>(tz)), rrT = from_acc<T>(from_acc2<A>(tr));
+        *epoch = ep;
+        if (MODE == 1) {
+            delta[0] = rhoT;
+            rho2[0] = rhoT;
+            history[0] = rrT;
+            *iter = 0;
+        } else {
+            const int it = *iter;
+            beta[0] = from_acc<T>(acc_div(to_acc(rhoT), to_acc(rho2[(it - 1) & 1])));
+            delta[0] = rhoT;
+            rho2[it & 1] = rhoT;
+            if (it < history_cap) history[it] = rrT;
+        }
+    }
+}
+
+// Four-launch loop, last launch: aypx_beta_p2p_kernel for the preconditioned recurrence.  Work-group 0 deposits both local sums in
+// every rank's mailbox; every work-group waits for all ranks' pairs in its own and adds them in rank order (bitwise the same beta
+// everywhere); then x += alpha d and d = z + beta d.  The epoch was advanced by the alpha kernel of this iteration.
+template <typename T, int BLOCK, bool VEC, int VNT = 0>
+__global__ __launch_bounds__(BLOCK) void pcg_aypx_beta_p2p_kernel(int n, const T *z, T *y, T *xs, const T *alpha,
+                                                                  const typename VT<T>::acc *part_rz, const typename VT<T>::acc *part_rr,
+                                                                  int P, char *const *mailbox, int rank, int nranks,
+                                                                  const unsigned long long *epoch, T *delta, T *beta, T *history,
+                                                                  int history_cap, T *rho2, const int *iter) {
+    using A = typename VT<T>::acc;
+    __shared__ A red[BLOCK / kWave];
+    __shared__ double2 vz[64], vr[64], loc[2];
+    __shared__ T beta_s;
+    const unsigned long long ep = *epoch;
+    const int s = threadIdx.x;
+    if (blockIdx.x == 0) {
+        A az = vzero<A>(), ar = vzero<A>();
+        for (int i = threadIdx.x; i < P; i += BLOCK) { az = vadd(az, part_rz[i]); ar = vadd(ar, part_rr[i]); }
+        const A tz = block_sum<BLOCK>(az, red);
+        if (threadIdx.x == 0) loc[0] = to_acc2(tz);
+        const A tr = block_sum<BLOCK>(ar, red);
+        if (threadIdx.x == 0) loc[1] = to_acc2(tr);
+        __syncthreads();
+        if (s < nranks) pcg_deposit(mailbox, s, rank, loc[0], loc[1], ep);
+        __syncthreads();
+    }
+    if (s < nranks) {
+        double2 v[2];
+        pcg_collect(mailbox, s, rank, ep, v);
+        vz[s] = v[0];
+        vr[s] = v[1];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double2 tz = make_double2(0., 0.), tr = make_double2(0., 0.);
+        for (int k = 0; k < nranks; ++k) { tz.x += vz[k].x; tz.y += vz[k].y; tr.x += vr[k].x; tr.y += vr[k].y; }
+        const int it = *iter;
+        const T rhoT = from_acc<T>(from_acc2<A>(tz));
+        const T bt = from_acc<T>(acc_div(to_acc(rhoT), to_acc(rho2[(it - 1) & 1])));
+        beta_s = bt;
+        if (blockIdx.x == 0) {
+            beta[0] = bt;
+            delta[0] = rhoT;            // cg_alpha divides this by d.q
+            rho2[it & 1] = rhoT;
+            if (it < history_cap) history[it] = from_acc<T>(from_acc2<A>(tr));
+        }
+    }
+    __syncthreads();
+    const T bt = beta_s, al = alpha[0];
+    constexpr int E = Pack<T>::N;
+    const long long stride = (long long)gridDim.x * BLOCK;
+    long long i0 = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (VEC) {
+        const long long npack = n / E;
+        for (long long i = i0; i < npack; i += stride) {
+            const Pack<T> pz = ld_pack(z + i * E);
+            Pack<T> py = ld_pack(y + i * E), ps = (VNT & 1) ? ld_pack_nt(xs + i * E) : ld_pack(xs + i * E);
+#pragma unroll
+            for (int k = 0; k < E; ++k) {
+                ps.v[k] = vadd(ps.v[k], vmul(al, py.v[k]));
+                py.v[k] = vadd(vmul(bt, py.v[k]), pz.v[k]);
+            }
+            if (VNT & 1) st_pack_nt(xs + i * E, ps); else st_pack(xs + i * E, ps);
+            st_pack(y + i * E, py);
+        }
+        i0 += npack * E;
+    }
+    for (long long i = i0; i < n; i += stride) {
+        const T dv = y[i];
+        xs[i] = vadd(xs[i], vmul(al, dv));
+        y[i] = vadd(vmul(bt, dv), z[i]);
+    }
+}
+
 // ---- peer-to-peer backend launchers ---------------------------------------------------------------
 static P2pExchangeArgs p2p_args(const P2pExchange &e) {
     P2pExchangeArgs a;
@@ -456,6 +596,52 @@ int launch_p2p_allreduce(int dtype, int mode, const void *partials, int grid, ch
                          unsigned long long *bump1) {
     if (nranks > 64) return fail(CGAMD_ERR_INVALID, "p2p all-reduce: at most 64 ranks");
     CG_DISPATCH(dtype, p2p_ar_impl, mode, partials, grid, mailbox, rank, nranks, which, epoch, sc, bump0, bump1, st);
+}
+
+template <typename T>
+static int pcg_ar2_impl(int mode, const void *part_rz, const void *part_rr, int P, char *const *mailbox, int rank, int nranks,
+                        unsigned long long *epoch, const CgScalars &sc, void *rho2, hipStream_t st) {
+    using A = typename VT<T>::acc;
+#define CG_AR2(M)                                                                                                                  \
+    hipLaunchKernelGGL((pcg_allreduce2_p2p_kernel<T, M>), dim3(1), dim3(kScalarBlock), 0, st, (const A *)part_rz, (const A *)part_rr, P, \
+                       mailbox, rank, nranks, epoch, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, sc.iter)
+    if (mode == 1) CG_AR2(1); else CG_AR2(3);
+#undef CG_AR2
+    return check_launch("pcg_allreduce2_p2p");
+}
+int launch_pcg_allreduce2_p2p(int dtype, int mode, const void *part_rz, const void *part_rr, int P, char *const *mailbox, int rank,
+                              int nranks, unsigned long long *epoch, const CgScalars &sc, void *rho2, hipStream_t st) {
+    if (nranks > 64) return fail(CGAMD_ERR_INVALID, "p2p all-reduce: at most 64 ranks");
+    CG_DISPATCH(dtype, pcg_ar2_impl, mode, part_rz, part_rr, P, mailbox, rank, nranks, epoch, sc, rho2, st);
+}
+
+// (every work-group spins: the grid is capped at what is resident at once, as for aypx_beta_p2p_kernel)
+template <typename T>
+static int pcg_aypx_beta_p2p_impl(int n, const void *z, void *y, void *xs, const void *part_rz, const void *part_rr, int P,
+                                  char *const *mailbox, int rank, int nranks, const unsigned long long *epoch, const CgScalars &sc,
+                                  void *rho2, bool vec, int vnt, hipStream_t st) {
+    using A = typename VT<T>::acc;
+#define CG_PAP(V, N)                                                                                                            \
+    do {                                                                                                                         \
+        static const int cap = resident_grid_cap(pcg_aypx_beta_p2p_kernel<T, kBlock, V, N>);                                    \
+        if (cap < 1) return fail(CGAMD_ERR_HIP, "pcg_aypx_beta_p2p: occupancy query failed; refusing an all-work-group spin");   \
+        const dim3 g(std::min(vec_grid(n, VT<T>::dtype), cap)), blk(kBlock);                                                    \
+        hipLaunchKernelGGL((pcg_aypx_beta_p2p_kernel<T, kBlock, V, N>), g, blk, 0, st, n, (const T *)z, (T *)y, (T *)xs,        \
+                           (const T *)sc.alpha, (const A *)part_rz, (const A *)part_rr, P, mailbox, rank, nranks, epoch,        \
+                           (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter);      \
+    } while (0)
+    if (vec && (vnt & 1)) CG_PAP(true, 1); else if (vec) CG_PAP(true, 0); else CG_PAP(false, 0);
+#undef CG_PAP
+    return check_launch("pcg_aypx_beta_p2p");
+}
+int launch_pcg_aypx_beta_p2p(int dtype, int n, const void *z, void *d, void *x, const void *part_rz, const void *part_rr, int P,
+                             char *const *mailbox, int rank, int nranks, const unsigned long long *epoch, const CgScalars &sc, void *rho2,
+                             hipStream_t st, int vec_nt) {
+    if (n <= 0) return CGAMD_OK;
+    if (nranks > 64) return fail(CGAMD_ERR_INVALID, "p2p all-reduce: at most 64 ranks");
+    const bool v = vec_ok(dtype, n, 1, {z, d, x});
+    const int vnt = tune().vec_nt >= 0 ? tune().vec_nt : vec_nt;
+    CG_DISPATCH(dtype, pcg_aypx_beta_p2p_impl, n, z, d, x, part_rz, part_rr, P, mailbox, rank, nranks, epoch, sc, rho2, v, vnt, st);
 }
 
 }  // namespace cgamd

@@ -11,7 +11,9 @@ namespace cgamd {
 // RCCL's latency (10-20 us per small collective) bounds strong scaling of a 40 us iteration; here each rank owns
 // an UNCACHED, IPC-shared "mailbox" that its peers write directly:
 //     [0,4096)      reduction slots  slot[which in 0..1][source rank] = {value.x, value.y, epoch, pad} (32 B)
-//     [4096,6144)   halo flags       flag[source rank] = epoch of the last complete boundary push
+//     [4096,4608)   halo flags       flag[source rank] = epoch of the last complete boundary push
+//     [5120,6144)   PCG              rz[source rank] = {value.x, value.y} (16 B): r.z, travelling with slot set 1 (which carries r.r
+//                                    and the epoch: both are stored before the epoch and read after it, one round for the two sums)
 //     [6144,8192)   error word
 //     [8192,16384)  single-reduction loop (cg1.hip): slot[parity][source rank] = {r.r (x, y), w.r (x, y), epoch, pad} (64 B)
 //     [16384,...)   halo entries     laid out exactly like the halo part of d_ext
@@ -26,7 +28,7 @@ namespace cgamd {
 // unchanged.  Slot reuse is safe because two full all-reduces separate consecutive uses of any slot or of the halo area.
 // Spins are bounded; a timeout sets the error word and the kernels fall through.
 // =================================================================================================
-constexpr int kMbSlots = 0, kMbHaloFlags = 4096, kMbError = 6144, kMbCg1 = 8192, kMbHalo = (int)kMailboxHeader;
+constexpr int kMbSlots = 0, kMbHaloFlags = 4096, kMbPcg = 5120, kMbError = 6144, kMbCg1 = 8192, kMbHalo = (int)kMailboxHeader;
 constexpr long long kSpinLimit = 1LL << 21;   // polls of ~1-2 us each: a few seconds, then the error word is set
 
 // all of this lane's earlier stores are acknowledged by the memory system; compiler-level ordering included

@@ -37,14 +37,15 @@ template <> CG_DEV double2 acc_one<double2>() { return make_double2(1., 0.); }
 
 template <typename T>
 __global__ __launch_bounds__(kBlock) void line_extract_kernel(int nu, int stride, const T *__restrict__ vals, const int *__restrict__ ptr,
-                                                              const int *__restrict__ cols, T *__restrict__ lower, T *__restrict__ diag,
-                                                              T *__restrict__ upper) {
+                                                              const int *__restrict__ cols, int col_limit, T *__restrict__ lower,
+                                                              T *__restrict__ diag, T *__restrict__ upper) {
     using A = typename VT<T>::acc;
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= nu) return;
     A a = vzero<A>(), b = vzero<A>(), c = vzero<A>();
     const int end = ptr[i + 1];
     for (int j = ptr[i]; j < end; ++j) {
+        if (cols[j] >= col_limit) continue;      // a halo column of a row-partitioned matrix: no line neighbour at any distance
         const long long off = (long long)cols[j] - i;
         if (off == 0) b = vadd(b, to_acc(vals[j]));
         else if (off == -(long long)stride) a = vadd(a, to_acc(vals[j]));
@@ -224,15 +225,15 @@ __global__ __launch_bounds__(kBlock) void line_emit_kernel(int n, int stride, co
 static int row_blocks(int n) { return (n + kBlock - 1) / kBlock; }
 
 template <typename T>
-static int extract_impl(int nu, int stride, const void *vals, const int *ptr, const int *cols, void *lower, void *diag, void *upper,
-                        hipStream_t st) {
+static int extract_impl(int nu, int stride, const void *vals, const int *ptr, const int *cols, int col_limit, void *lower, void *diag,
+                        void *upper, hipStream_t st) {
     hipLaunchKernelGGL((line_extract_kernel<T>), dim3(row_blocks(nu)), dim3(kBlock), 0, st, nu, stride, (const T *)vals, ptr, cols,
-                       (T *)lower, (T *)diag, (T *)upper);
+                       col_limit, (T *)lower, (T *)diag, (T *)upper);
     return check_launch("line_extract");
 }
-int launch_line_extract(int dtype, int n_user, int stride, const void *vals, const int *ptr, const int *cols, void *lower, void *diag,
-                        void *upper, hipStream_t st) {
-    CG_DISPATCH(dtype, extract_impl, n_user, stride, vals, ptr, cols, lower, diag, upper, st);
+int launch_line_extract(int dtype, int n_user, int stride, const void *vals, const int *ptr, const int *cols, int col_limit, void *lower,
+                        void *diag, void *upper, hipStream_t st) {
+    CG_DISPATCH(dtype, extract_impl, n_user, stride, vals, ptr, cols, col_limit, lower, diag, upper, st);
 }
 
 template <typename T>

@@ -678,103 +678,6 @@ static int diag_impl(cgamd_solver *s, const void *m, int on_device) {
     return CGAMD_OK;
 }
 
-// The host side both tridiagonal forms share: M's three arrays to the host and the factorisation along every chain c, c + stride,
-// c + 2 stride, ... (stride 1: the rows in order).  Rows are visited in order, so the first bad row is the one named.  Leaves the
-// factors as the kernels read them (nl, ne, w: `pitch` values each) and, per row, whether the stored -l / -w c are 0.
-struct TriFactors {
-    std::vector<unsigned char> coef;
-    std::vector<char> l_zero, e_zero;
-    size_t pitch = 0;
-};
-static int tri_factor(cgamd_solver *s, const std::string &who, int stride, const void *lower, const void *diag, const void *upper,
-                      int on_device, TriFactors &out) {
-    hipStream_t st = s->ctx->stream;
-    const int nu = s->n_user, n = s->n, dt = s->dtype;
-    const size_t vs = dtype_size(dt);
-    std::vector<unsigned char> h[3];
-    const void *src[3] = {lower, diag, upper};
-    for (int k = 0; k < 3; ++k) {
-        h[k].resize((size_t)nu * vs);
-        if (on_device) CG_HIP(hipMemcpyAsync(h[k].data(), src[k], h[k].size(), hipMemcpyDeviceToHost, st));
-        else std::memcpy(h[k].data(), src[k], h[k].size());
-    }
-    if (on_device) CG_HIP(hipStreamSynchronize(st));
-    using C = std::complex<double>;
-    auto get = [&](int k, int i) -> C {
-        const unsigned char *p = h[k].data() + (size_t)i * vs;
-        switch (dt) {
-        case CGAMD_F32: { float v; std::memcpy(&v, p, 4); return C(v, 0.); }
-        case CGAMD_F64: { double v; std::memcpy(&v, p, 8); return C(v, 0.); }
-        case CGAMD_C64: { float v[2]; std::memcpy(v, p, 8); return C(v[0], v[1]); }
-        default: { double v[2]; std::memcpy(v, p, 16); return C(v[0], v[1]); }
-        }
-    };
-    auto finite = [](C v) { return std::isfinite(v.real()) && std::isfinite(v.imag()); };
-    const int E = (int)(16 / vs);
-    const size_t pitch = ((size_t)n + 2 * E - 1) / (2 * E) * (2 * E);      // values per factor array: whole 32-byte rows of a thread
-    out.pitch = pitch;
-    out.coef.assign(3 * pitch * vs, 0);
-    auto put = [&](int k, int i, C v) {
-        unsigned char *p = out.coef.data() + ((size_t)k * pitch + i) * vs;
-        switch (dt) {
-        case CGAMD_F32: { const float f = (float)v.real(); std::memcpy(p, &f, 4); break; }
-        case CGAMD_F64: { const double f = v.real(); std::memcpy(p, &f, 8); break; }
-        case CGAMD_C64: { const float f[2] = {(float)v.real(), (float)v.imag()}; std::memcpy(p, f, 8); break; }
-        default: { const double f[2] = {v.real(), v.imag()}; std::memcpy(p, f, 16); break; }
-        }
-    };
-    const bool single = dt == CGAMD_F32 || dt == CGAMD_C64;
-    auto rounds_to_zero = [&](C v) { return single ? ((float)v.real() == 0.f && (float)v.imag() == 0.f) : v == C(0., 0.); };
-    out.l_zero.assign((size_t)n, 1);      // the stored -l / -w c are 0 (as the kernels see them)
-    out.e_zero.assign((size_t)n, 1);
-    std::vector<C> u_prev((size_t)stride, C(0., 0.)), c_prev((size_t)stride, C(0., 0.));      // of row i - stride, per chain
-    for (int i = 0; i < nu; ++i) {
-        const int ch = i % stride;
-        const bool head = i < stride;
-        const C a = head ? C(0., 0.) : get(0, i), b = get(1, i), c = i < nu - stride ? get(2, i) : C(0., 0.);
-        if (!finite(a) || !finite(b) || !finite(c))
-            return fail(CGAMD_ERR_INVALID, who + ": non-finite entry in row " + std::to_string(i));
-        const C l = head ? C(0., 0.) : a / u_prev[ch];
-        const C u = b - l * c_prev[ch];
-        if (!finite(l) || !finite(u) || u == C(0., 0.))
-            return fail(CGAMD_ERR_INVALID, who + ": zero or non-finite pivot in row " + std::to_string(i) +
-                                               " (the factorisation does not pivot)");
-        const C w = 1. / u;
-        if (!finite(w)) return fail(CGAMD_ERR_INVALID, who + ": pivot too small in row " + std::to_string(i));
-        put(0, i, -l);
-        put(1, i, -(w * c));
-        put(2, i, w);
-        out.l_zero[i] = rounds_to_zero(l);
-        out.e_zero[i] = rounds_to_zero(w * c);
-        u_prev[ch] = u;
-        c_prev[ch] = c;
-    }
-    // (the padding rows keep 0 everywhere: decoupled, z = 0 there)
-    return CGAMD_OK;
-}
-
-// Chunk boundaries of the stride-1 sweep from the segment list (seg: the first rows in order, then n): O(segments).  Returns
-// whether the sweep takes its long form (a segment does not fit one chunk: plain slices of Cmax rows).
-static bool tri_plan_chunks(const std::vector<int> &seg, int n, int dt, std::vector<int> &starts) {
-    const int Cmax = tri_chunk_rows(dt), R = Cmax / kBlock;
-    starts.assign(1, 0);
-    bool longform = false;
-    for (size_t k = 1; k < seg.size() && !longform; ++k) {
-        if (seg[k] - starts.back() / R * R <= Cmax) continue;        // segment k-1 still fits the current chunk
-        if (seg[k - 1] == starts.back()) longform = true;            // it alone does not fit one
-        else {
-            starts.push_back(seg[k - 1]);
-            if (seg[k] - seg[k - 1] / R * R > Cmax) longform = true;
-        }
-    }
-    if (longform) {
-        starts.clear();
-        for (int i = 0; i < n; i += Cmax) starts.push_back(i);
-    }
-    starts.push_back(n);
-    return longform;
-}
-
 // The handle takes a factored tridiagonal M over.  coef (3 x pitch values: -l, -w c, w) and plan (stride 1: count + 1 chunk
 // boundaries; stride > 1: count (first row, length) pairs) are device allocations, filled, that belong to the handle from here on
 // -- also when this fails.  Everything that can be wrong with M was checked before.
@@ -814,84 +717,22 @@ static int tri_install(cgamd_solver *s, void *coef, size_t pitch, int *plan, int
     return CGAMD_OK;
 }
 
-// host factors and a host plan to the device, then tri_install; the handle is unchanged when the upload fails
-static int tri_upload_install(cgamd_solver *s, const std::string &who, const TriFactors &f, const std::vector<int> &plan, int stride,
-                              int count, bool longform) {
-    hipStream_t st = s->ctx->stream;
-    void *coef = nullptr;
-    int *dplan = nullptr;
-    int rc = dmalloc(&coef, f.coef.size(), "tridiagonal factors");
-    if (!rc) rc = dmalloc((void **)&dplan, plan.size() * 4, stride == 1 ? "tridiagonal chunk plan" : "tridiagonal segment plan");
-    if (!rc) {
-        hipError_t e = hipMemcpyAsync(coef, f.coef.data(), f.coef.size(), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipMemcpyAsync(dplan, plan.data(), plan.size() * 4, hipMemcpyHostToDevice, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) rc = fail(CGAMD_ERR_HIP, who + " upload: " + hipGetErrorString(e));
-    }
-    if (rc) {
-        if (coef) (void)hipFree(coef);
-        if (dplan) (void)hipFree(dplan);
-        return rc;
-    }
-    return tri_install(s, coef, f.pitch, dplan, stride, count, longform);
-}
-
-// Tridiagonal M: z solves M z = r (the reference PCG's spsolve branch, helmFE_var.py:561-562).  Factored here once, in double /
-// complex double (Thomas LU, no pivoting: u_0 = b_0, l_i = a_i / u_{i-1}, u_i = b_i - l_i c_{i-1}); the kernels get -l, -w c and
-// w = 1/u in the value type.  Rows where both couplings to the row before vanish start a segment; chunks of at most
-// tri_chunk_rows() rows start at segment starts when every segment fits one (no carry between work-groups), else they are plain
-// slices and the sweep takes its three-launch form.  Everything is checked before the handle changes.
-static int tridiag_impl(cgamd_solver *s, const std::string &who, const void *lower, const void *diag, const void *upper, int on_device) {
+// Tridiagonal M from its three arrays (precond_setup.cpp: factored on the host, planned, uploaded), at stride 1 or at a distance:
+// lower[i] = M[i][i-stride], upper[i] = M[i][i+stride].  Everything is checked before the handle changes.
+static int tridiag_strided_impl(cgamd_solver *s, const std::string &who, int stride, const void *lower, const void *diag,
+                                const void *upper, int on_device) {
     CG_HIP(hipSetDevice(s->ctx->device));
     CG_HIP(hipStreamSynchronize(s->ctx->stream));
-    const int n = s->n;
-    TriFactors f;
-    if (int rc = tri_factor(s, who, 1, lower, diag, upper, on_device, f)) return rc;
-    std::vector<int> seg;
-    for (int i = 0; i < n; ++i)
-        if (i == 0 || (f.l_zero[i] && f.e_zero[i - 1])) seg.push_back(i);
-    seg.push_back(n);
-    std::vector<int> starts;
-    const bool longform = tri_plan_chunks(seg, n, s->dtype, starts);
-    return tri_upload_install(s, who, f, starts, 1, (int)starts.size() - 1, longform);
+    TriBuilt b;
+    if (int rc = tri_build_host(s->ctx->stream, s->dtype, s->n_user, s->n, who, stride, lower, diag, upper, on_device, &b)) return rc;
+    return tri_install(s, b.coef, b.pitch, b.plan, b.stride, b.count, b.longform);
 }
 int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, const void *diag, const void *upper, int on_device) {
     if (!s || !lower || !diag || !upper) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag: null argument");
     TuneScope ts(&s->tune);
-    return tridiag_impl(s, "set_preconditioner_tridiag", lower, diag, upper, on_device);
+    return tridiag_strided_impl(s, "set_preconditioner_tridiag", 1, lower, diag, upper, on_device);
 }
 
-// The same M at a distance: lower[i] = M[i][i-stride], upper[i] = M[i][i+stride] (a line preconditioner along the grid axis whose
-// neighbours lie `stride` rows apart).  The factorisation runs along every chain c, c + stride, ...; a chain is cut where both
-// stored couplings round to zero in the value type (the rule of the stride-1 form, at distance stride), and the plan is the list
-// of those segments (first row, length) ordered by first row: one thread of pcg_tri_strided_kernel each, whatever their length.
-// stride 1 is cgamd_solver_set_preconditioner_tridiag itself.
-static int tridiag_strided_impl(cgamd_solver *s, const std::string &who, int stride, const void *lower, const void *diag,
-                                const void *upper, int on_device) {
-    if (stride == 1) return tridiag_impl(s, who, lower, diag, upper, on_device);
-    CG_HIP(hipSetDevice(s->ctx->device));
-    CG_HIP(hipStreamSynchronize(s->ctx->stream));
-    const int n = s->n;
-    TriFactors f;
-    if (int rc = tri_factor(s, who, stride, lower, diag, upper, on_device, f)) return rc;
-    // row i starts a segment when it heads its chain or both couplings to row i - stride vanish; its length is known once the
-    // chain's next start (or end) is: walk the rows backwards, carrying per chain the rows seen since the last start
-    std::vector<int> segs;      // (first row, length) pairs, built last segment first
-    {
-        std::vector<int> run((size_t)stride, 0);
-        for (int i = n - 1; i >= 0; --i) {
-            int &len = run[i % stride];
-            ++len;
-            if (i < stride || (f.l_zero[i] && f.e_zero[i - stride])) {
-                segs.push_back(len);
-                segs.push_back(i);
-                len = 0;
-            }
-        }
-        std::reverse(segs.begin(), segs.end());
-    }
-    return tri_upload_install(s, who, f, segs, stride, (int)(segs.size() / 2), false);
-}
 int cgamd_solver_set_preconditioner_tridiag_strided(cgamd_solver *s, int stride, const void *lower, const void *diag, const void *upper,
                                                     int on_device) {
     if (!s || !lower || !diag || !upper) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag_strided: null argument");
@@ -902,120 +743,19 @@ int cgamd_solver_set_preconditioner_tridiag_strided(cgamd_solver *s, int stride,
                                 diag, upper, on_device);
 }
 
-// ---- preconditioners built from the handle's own matrix, on the device (precond_build.hip) ----------------------------------------
-namespace {
-struct DevScratch {      // device allocations of one call, freed on return unless the handle took them
-    std::vector<void *> ptrs;
-    ~DevScratch() {
-        for (void *p : ptrs)
-            if (p) (void)hipFree(p);
-    }
-    int get(void **p, size_t bytes, const char *what) {
-        const int rc = dmalloc(p, bytes, what);
-        if (!rc) ptrs.push_back(*p);
-        return rc;
-    }
-    void release(void *p) {
-        for (void *&q : ptrs)
-            if (q == p) q = nullptr;
-    }
-};
-}  // namespace
-
-// Longest pre-segment the device factorisation takes, one thread per pre-segment; beyond it cgamd_solver_set_preconditioner_line
-// extracts on the device and factors by the host route (source 3).  PROVISIONAL: the value is to be the largest segment length at
-// which `scripts/line_setup_ab.py --groups chains` finds the device no slower than the host; that table
-// (profiles/line_setup/long_segments.log) has not been measured yet.
-constexpr int kLineHostRouteRows = 65536;
-
+// ---- preconditioners built from the handle's own matrix, on the device (precond_setup.cpp, precond_build.hip) ---------------------
 // M = the matrix entries at column - row in {-stride, 0, +stride}: extracted, factored and planned on the device.  Nothing on the
-// handle changes before tri_install (or the host route's); the temporaries are three n-long value arrays, n flag bytes, one int per
-// 256 rows and three words.
+// handle changes before tri_install.
 static int line_from_matrix(cgamd_solver *s, const std::string &who, int stride) {
     CG_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
     CG_HIP(hipStreamSynchronize(st));
-    const int n = s->n, nu = s->n_user, dt = s->dtype;
-    const size_t vs = dtype_size(dt);
-    DevScratch tmp;
-    void *abc = nullptr, *words = nullptr;
-    unsigned char *flags = nullptr;
-    int *count = nullptr;
-    int rc = tmp.get(&abc, 3 * (size_t)n * vs, "line preconditioner: diagonals");
-    if (!rc) rc = tmp.get((void **)&flags, (size_t)n, "line preconditioner: flags");
-    if (!rc) rc = tmp.get((void **)&count, (size_t)line_count_ints(n) * 4, "line preconditioner: block counts");
-    if (!rc) rc = tmp.get(&words, 16, "line preconditioner: words");
+    TriBuilt b;
+    int rc = tri_build_from_matrix(st, s->dtype, s->n_user, s->n, s->tune.dev_line_host_route, who, stride, s->vals, s->ptr, s->cols,
+                                   s->n_user, &b);
     if (rc) return rc;
-    char *lower = static_cast<char *>(abc), *diag = lower + (size_t)n * vs, *upper = diag + (size_t)n * vs;
-    unsigned long long *err = static_cast<unsigned long long *>(words);
-    int *longest = reinterpret_cast<int *>(err + 1);
-    CG_HIP(hipMemsetAsync(abc, 0, 3 * (size_t)n * vs, st));      // (the padding rows: no couplings)
-    CG_HIP(hipMemsetAsync(err, 0xff, 8, st));
-    CG_HIP(hipMemsetAsync(longest, 0, 4, st));
-    if ((rc = launch_line_extract(dt, nu, stride, s->vals, s->ptr, s->cols, lower, diag, upper, st))) return rc;
-    if ((rc = launch_line_flags(dt, n, stride, lower, upper, flags, st))) return rc;
-    const int route = s->tune.dev_line_host_route;       // 1 / -1: the route is forced, nothing to measure
-    int longest_h = 0;
-    if (route == 0) {
-        if ((rc = launch_line_longest(n, stride, flags, kLineHostRouteRows + 1, longest, st))) return rc;
-        CG_HIP(hipMemcpyAsync(&longest_h, longest, 4, hipMemcpyDeviceToHost, st));
-        CG_HIP(hipStreamSynchronize(st));
-    }
-    if (route > 0 || (route == 0 && longest_h > kLineHostRouteRows)) {
-        // few long segments: one thread each is slower than the host's serial loop.  The extracted diagonals go the host route.
-        rc = tridiag_strided_impl(s, who, stride, lower, diag, upper, 1);
-        if (!rc) { s->pre_source = 3; s->pre_kind = 2; s->pre_stride = stride; }
-        return rc;
-    }
-    const int E = (int)(16 / vs);
-    const size_t pitch = ((size_t)n + 2 * E - 1) / (2 * E) * (2 * E);      // as tri_factor lays the factors out
-    void *coef = nullptr;
-    if ((rc = tmp.get(&coef, 3 * pitch * vs, "tridiagonal factors"))) return rc;
-    char *nl = static_cast<char *>(coef), *ne = nl + pitch * vs, *w = ne + pitch * vs;
-    CG_HIP(hipMemsetAsync(coef, 0, 3 * pitch * vs, st));           // (the padding rows keep 0 everywhere: decoupled, z = 0 there)
-    if ((rc = launch_line_factor(dt, nu, stride, flags, lower, diag, upper, nl, ne, w, err, st))) return rc;
-    unsigned long long err_h = 0;
-    CG_HIP(hipMemcpyAsync(&err_h, err, 8, hipMemcpyDeviceToHost, st));
-    CG_HIP(hipStreamSynchronize(st));
-    if (err_h != ~0ull) {
-        const std::string row = std::to_string(err_h >> 2);
-        switch ((int)(err_h & 3)) {
-        case 0: return fail(CGAMD_ERR_INVALID, who + ": non-finite entry in row " + row);
-        case 1: return fail(CGAMD_ERR_INVALID, who + ": zero or non-finite pivot in row " + row + " (the factorisation does not pivot)");
-        default: return fail(CGAMD_ERR_INVALID, who + ": pivot too small in row " + row);
-        }
-    }
-    // the final segments, from the factors as stored: flags, the flagged rows before every block, their number
-    if ((rc = launch_line_flags(dt, n, stride, nl, ne, flags, st))) return rc;
-    if ((rc = launch_line_count(n, flags, count, st))) return rc;
-    int nsegs = 0;
-    CG_HIP(hipMemcpyAsync(&nsegs, count + line_count_ints(n) - 1, 4, hipMemcpyDeviceToHost, st));
-    CG_HIP(hipStreamSynchronize(st));
-    int *plan = nullptr;
-    int nplan = nsegs;
-    bool longform = false;
-    if (stride > 1) {       // the plan of pcg_tri_strided_kernel: (first row, length) ordered by first row
-        if ((rc = tmp.get((void **)&plan, (size_t)nsegs * 8, "tridiagonal segment plan"))) return rc;
-        if ((rc = launch_line_emit(n, stride, true, flags, count, plan, st))) return rc;
-    } else {                // the segment starts go to the host chunk planner
-        int *starts_dev = nullptr;
-        if ((rc = tmp.get((void **)&starts_dev, (size_t)nsegs * 4, "tridiagonal segment starts"))) return rc;
-        if ((rc = launch_line_emit(n, 1, false, flags, count, starts_dev, st))) return rc;
-        std::vector<int> seg((size_t)nsegs + 1), starts;
-        CG_HIP(hipMemcpyAsync(seg.data(), starts_dev, (size_t)nsegs * 4, hipMemcpyDeviceToHost, st));
-        CG_HIP(hipStreamSynchronize(st));
-        seg[(size_t)nsegs] = n;
-        longform = tri_plan_chunks(seg, n, dt, starts);
-        nplan = (int)starts.size() - 1;
-        if ((rc = tmp.get((void **)&plan, starts.size() * 4, "tridiagonal chunk plan"))) return rc;
-        CG_HIP(hipMemcpyAsync(plan, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
-        CG_HIP(hipStreamSynchronize(st));
-    }
-    CG_HIP(hipStreamSynchronize(st));
-    tmp.release(coef);
-    tmp.release(plan);
-    rc = tri_install(s, coef, pitch, plan, stride, nplan, longform);
-    if (!rc) { s->pre_source = 2; s->pre_kind = 2; s->pre_stride = stride; }
+    rc = tri_install(s, b.coef, b.pitch, b.plan, b.stride, b.count, b.longform);
+    if (!rc) { s->pre_source = b.source; s->pre_kind = 2; s->pre_stride = stride; }
     return rc;
 }
 int cgamd_solver_set_preconditioner_line(cgamd_solver *s, int stride) {
@@ -1030,19 +770,12 @@ static int jacobi_from_matrix(cgamd_solver *s, const std::string &who) {
     CG_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
     CG_HIP(hipStreamSynchronize(st));
-    DevScratch tmp;
-    void *m = nullptr, *err = nullptr;
-    int rc = tmp.get(&m, (size_t)s->n_user * dtype_size(s->dtype), "Jacobi preconditioner");
-    if (!rc) rc = tmp.get(&err, 8, "Jacobi preconditioner: error word");
+    void *m = nullptr;
+    int rc = dmalloc(&m, (size_t)s->n_user * dtype_size(s->dtype), "Jacobi preconditioner");
     if (rc) return rc;
-    CG_HIP(hipMemsetAsync(err, 0xff, 8, st));
-    if ((rc = launch_jacobi_extract(s->dtype, s->n_user, s->vals, s->ptr, s->cols, m, static_cast<unsigned long long *>(err), st))) return rc;
-    unsigned long long err_h = 0;
-    CG_HIP(hipMemcpyAsync(&err_h, err, 8, hipMemcpyDeviceToHost, st));
-    CG_HIP(hipStreamSynchronize(st));
-    if (err_h != ~0ull)
-        return fail(CGAMD_ERR_INVALID, who + ": zero, missing or non-finite diagonal in row " + std::to_string(err_h));
-    rc = diag_impl(s, m, 1);
+    rc = jacobi_build_from_matrix(st, s->dtype, s->n_user, who, s->vals, s->ptr, s->cols, m);
+    if (!rc) rc = diag_impl(s, m, 1);
+    (void)hipFree(m);
     if (!rc) { s->pre_source = 2; s->pre_kind = 1; }
     return rc;
 }

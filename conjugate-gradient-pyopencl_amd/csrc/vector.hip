@@ -912,4 +912,136 @@ int launch_pcg_delta0(int dtype, const void *part_rz, const void *part_rr, int P
     CG_DISPATCH(dtype, pcg_delta0_impl, part_rz, part_rr, P, nrhs, sc, rho2, st);
 }
 
+// ---- PCG of the row-partitioned loop (dist.cpp) ---------------------------------------------------
+// There z = M^-1 r lives in q's storage for every preconditioner (q is dead between the r update and the next SpMV), so the
+// direction update that follows is the same for the diagonal and the line forms.  The Jacobi update: r -= alpha q, z = m .* r
+// stored over q, partials of r.z and r.r -- the expressions and the summation order of pcg_axpy2_dot2_kernel (5NV bytes; the
+// update that follows reads z instead of m and r, so the iteration moves what the single-GPU one does)
+template <typename T, int BLOCK, bool VEC>
+__global__ __launch_bounds__(BLOCK) void pcg_jacobi_z_kernel(int n, T *__restrict__ qz, T *__restrict__ rv, const T *__restrict__ m,
+                                                             const T *__restrict__ alpha, typename VT<T>::acc *__restrict__ part_rz,
+                                                             typename VT<T>::acc *__restrict__ part_rr) {
+    using A = typename VT<T>::acc;
+    __shared__ A red[BLOCK / kWave];
+    const T al = alpha[0];
+    A arz = vzero<A>(), arr = vzero<A>();
+    constexpr int E = Pack<T>::N;
+    const long long stride = (long long)gridDim.x * BLOCK;
+    long long i0 = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (VEC) {
+        const long long npack = n / E;
+        for (long long i = i0; i < npack; i += stride) {
+            Pack<T> pr = ld_pack(rv + i * E), pq = ld_pack(qz + i * E);
+            const Pack<T> pm = ld_pack(m + i * E);
+#pragma unroll
+            for (int k = 0; k < E; ++k) {
+                pr.v[k] = vsub(pr.v[k], vmul(al, pq.v[k]));
+                pq.v[k] = vmul(pm.v[k], pr.v[k]);
+                arz = vadd(arz, to_acc(vmul(pr.v[k], pq.v[k])));
+                arr = vadd(arr, to_acc(vmul(pr.v[k], pr.v[k])));
+            }
+            st_pack(rv + i * E, pr);
+            st_pack(qz + i * E, pq);
+        }
+        i0 += npack * E;
+    }
+    for (long long i = i0; i < n; i += stride) {
+        const T rn = vsub(rv[i], vmul(al, qz[i]));
+        const T z = vmul(m[i], rn);
+        rv[i] = rn;
+        qz[i] = z;
+        arz = vadd(arz, to_acc(vmul(rn, z)));
+        arr = vadd(arr, to_acc(vmul(rn, rn)));
+    }
+    const A trz = block_sum<BLOCK>(arz, red);
+    if (threadIdx.x == 0) part_rz[blockIdx.x] = trz;
+    const A trr = block_sum<BLOCK>(arr, red);
+    if (threadIdx.x == 0) part_rr[blockIdx.x] = trr;
+}
+template <typename T>
+static int pcg_jacobi_z_impl(int n, void *qz, void *r, const void *m, const void *alpha, void *part_rz, void *part_rr, int grid, bool vec,
+                             hipStream_t st) {
+    using A = typename VT<T>::acc;
+    const dim3 g(grid), blk(kBlock);
+    if (vec) hipLaunchKernelGGL((pcg_jacobi_z_kernel<T, kBlock, true>), g, blk, 0, st, n, (T *)qz, (T *)r, (const T *)m, (const T *)alpha, (A *)part_rz, (A *)part_rr);
+    else hipLaunchKernelGGL((pcg_jacobi_z_kernel<T, kBlock, false>), g, blk, 0, st, n, (T *)qz, (T *)r, (const T *)m, (const T *)alpha, (A *)part_rz, (A *)part_rr);
+    return check_launch("pcg_jacobi_z");
+}
+int launch_pcg_jacobi_z(int dtype, int n, void *q_z, void *r, const void *m, const void *alpha, void *part_rz, void *part_rr, int grid,
+                        hipStream_t st) {
+    if (n <= 0 || grid < 1) return fail(CGAMD_ERR_INVALID, "pcg_jacobi_z: empty launch");
+    const bool vec = vec_ok(dtype, n, 1, {q_z, r, m});
+    CG_DISPATCH(dtype, pcg_jacobi_z_impl, n, q_z, r, m, alpha, part_rz, part_rr, grid, vec, st);
+}
+
+// the scalar step on {r.z, r.r} already summed over the ranks (RCCL backend): MODE 1 = set_rhs, 3 = beta
+template <typename T, int MODE>
+__global__ __launch_bounds__(64) void pcg_scalars_kernel(const typename VT<T>::acc *red, T *delta, T *beta, T *history, int history_cap,
+                                                         T *rho2, int *iter) {
+    if (threadIdx.x != 0) return;
+    const T rhoT = from_acc<T>(red[0]), rrT = from_acc<T>(red[1]);
+    if (MODE == 1) {
+        delta[0] = rhoT;
+        rho2[0] = rhoT;
+        history[0] = rrT;
+        *iter = 0;
+    } else {
+        const int it = *iter;       // already advanced by cg_alpha of this iteration
+        beta[0] = from_acc<T>(acc_div(to_acc(rhoT), to_acc(rho2[(it - 1) & 1])));
+        delta[0] = rhoT;            // cg_alpha divides this by d.q
+        rho2[it & 1] = rhoT;
+        if (it < history_cap) history[it] = rrT;
+    }
+}
+template <typename T> static int pcg_scalars_impl(int mode, const void *red, const CgScalars &sc, void *rho2, hipStream_t st) {
+    using A = typename VT<T>::acc;
+    if (mode == 1) hipLaunchKernelGGL((pcg_scalars_kernel<T, 1>), dim3(1), dim3(64), 0, st, (const A *)red, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, sc.iter);
+    else hipLaunchKernelGGL((pcg_scalars_kernel<T, 3>), dim3(1), dim3(64), 0, st, (const A *)red, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, sc.iter);
+    return check_launch("pcg_scalars");
+}
+int launch_pcg_scalars(int dtype, int mode, const void *red, const CgScalars &sc, void *rho2, hipStream_t st) {
+    CG_DISPATCH(dtype, pcg_scalars_impl, mode, red, sc, rho2, st);
+}
+
+// x += alpha d ; d = z + beta d: the update of pcg_aypx_beta_kernel<ZV> with beta already on the device
+template <typename T, int BLOCK, bool VEC>
+__global__ __launch_bounds__(BLOCK) void pcg_xd_update_kernel(int n, const T *__restrict__ z, T *__restrict__ d, T *__restrict__ xs,
+                                                              const T *__restrict__ alpha, const T *__restrict__ beta) {
+    const T al = alpha[0], bt = beta[0];
+    constexpr int E = Pack<T>::N;
+    const long long stride = (long long)gridDim.x * BLOCK;
+    long long i0 = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (VEC) {
+        const long long npack = n / E;
+        for (long long i = i0; i < npack; i += stride) {
+            const Pack<T> pz = ld_pack(z + i * E);
+            Pack<T> pp = ld_pack(d + i * E), px = ld_pack(xs + i * E);
+#pragma unroll
+            for (int k = 0; k < E; ++k) {
+                px.v[k] = vadd(px.v[k], vmul(al, pp.v[k]));
+                pp.v[k] = vadd(vmul(bt, pp.v[k]), pz.v[k]);
+            }
+            st_pack(xs + i * E, px);
+            st_pack(d + i * E, pp);
+        }
+        i0 += npack * E;
+    }
+    for (long long i = i0; i < n; i += stride) {
+        const T dv = d[i];
+        xs[i] = vadd(xs[i], vmul(al, dv));
+        d[i] = vadd(vmul(bt, dv), z[i]);
+    }
+}
+template <typename T> static int pcg_xd_impl(int n, const void *z, void *d, void *x, const CgScalars &sc, bool vec, hipStream_t st) {
+    const dim3 g(vec_grid(n, VT<T>::dtype)), blk(kBlock);
+    if (vec) hipLaunchKernelGGL((pcg_xd_update_kernel<T, kBlock, true>), g, blk, 0, st, n, (const T *)z, (T *)d, (T *)x, (const T *)sc.alpha, (const T *)sc.beta);
+    else hipLaunchKernelGGL((pcg_xd_update_kernel<T, kBlock, false>), g, blk, 0, st, n, (const T *)z, (T *)d, (T *)x, (const T *)sc.alpha, (const T *)sc.beta);
+    return check_launch("pcg_xd_update");
+}
+int launch_pcg_xd_update(int dtype, int n, const void *z, void *d, void *x, const CgScalars &sc, hipStream_t st) {
+    if (n <= 0) return CGAMD_OK;
+    const bool vec = vec_ok(dtype, n, 1, {z, d, x});
+    CG_DISPATCH(dtype, pcg_xd_impl, n, z, d, x, sc, vec, st);
+}
+
 }  // namespace cgamd

@@ -178,6 +178,41 @@ def cg_loop(ops, comm, plan, b_local, x0_local, n_iterations):
     return x, torch.cat(hist)
 
 
+def pcg_loop(ops, comm, plan, b_local, x0_local, n_iterations, apply_m):
+    """The preconditioned form of `cg_loop` (what csrc/dist.cpp runs once DistSolver.set_preconditioner is in force), with a
+    RANK-LOCAL preconditioner: apply_m(r_local) -> z_local = M^-1 r_local needs no communication (a diagonal, or line solves cut at
+    the rank's row range -- block-Jacobi over the ranks, symmetric and positive definite whenever A is).  rho = r.z drives alpha
+    and beta; r.z and r.r travel in ONE all-reduce.  Returns (x_local, history[n_iterations+1]) with history[k] = global r_k . r_k,
+    as cg_loop does.  With apply_m the identity the iterates are cg_loop's, bit for bit."""
+    import torch
+    n = plan.n_local
+    x = x0_local.clone()
+    d_ext = torch.zeros(n + plan.n_halo, dtype=b_local.dtype, device=b_local.device)
+    d_ext[:n] = x
+    comm.exchange(d_ext)
+    r = b_local - ops.spmv(d_ext)
+    z = apply_m(r)
+    d_ext[:n] = z                                                   # d = z0
+    red = comm.allreduce(torch.stack([ops.dot(r, z), ops.dot(r, r)]).clone())      # the one round: {r.z, r.r}
+    rho = red[0:1].clone()
+    hist = [red[1:2].clone()]
+    for _ in range(n_iterations):
+        comm.exchange(d_ext)
+        q = ops.spmv(d_ext)
+        dq = comm.allreduce(ops.dot(d_ext[:n], q).reshape(1).clone())
+        alpha = rho / dq
+        x = x + alpha * d_ext[:n]
+        r = r - alpha * q
+        z = apply_m(r)
+        rho_old = rho
+        red = comm.allreduce(torch.stack([ops.dot(r, z), ops.dot(r, r)]).clone())
+        rho = red[0:1].clone()
+        beta = rho / rho_old
+        d_ext[:n] = beta * d_ext[:n] + z
+        hist.append(red[1:2].clone())
+    return x, torch.cat(hist)
+
+
 def cg_loop_single_reduction(ops, comm, plan, b_local, x0_local, n_iterations):
     """The single-reduction form of the same recurrence (Chronopoulos & Gear; csrc/cg1.hip is the device loop): w = A r, ONE
     all-reduce of {r.r, w.r} per iteration instead of two, the exchanged vector is r.  Same iterates in exact arithmetic; the
@@ -348,6 +383,49 @@ class DistSolver:
     def comm_ranks(self):
         """ranks of the RCCL communicator, as RCCL reports them (0: no communicator)"""
         return int(self._lib.cgamd_dist_comm_ranks(self.handle))
+
+    def set_preconditioner(self, m, group=None):
+        """Preconditioned CG from the next set_rhs on.  m: None (remove), "jacobi" (1 / diag of the rank's matrix, built on the
+        device), ("line", stride) (the local entries at column - row in {-stride, 0, +stride}; halo columns never count, so lines end
+        at the rank's row range) or a device tensor / buffer of n_local values (z = m .* r).  Collective over `group`: the C calls
+        are local, so the ranks' statuses are all-gathered afterwards; if ANY rank failed, every rank removes its preconditioner and
+        raises CgAmdError with the failing rank and its message -- ranks running different recurrences would wait for each
+        other's sums until the peer-to-peer time-outs."""
+        lib = self._lib
+        if m is None:
+            call = lambda: lib.cgamd_dist_set_preconditioner(self.handle, None)
+        elif isinstance(m, str) and m == "jacobi":
+            call = lambda: lib.cgamd_dist_set_preconditioner_jacobi(self.handle)
+        elif (isinstance(m, (tuple, list)) and len(m) == 2 and isinstance(m[0], str) and m[0] == "line"
+              and isinstance(m[1], (int, np.integer)) and not isinstance(m[1], bool)):
+            call = lambda: lib.cgamd_dist_set_preconditioner_line(self.handle, int(m[1]))
+        elif not isinstance(m, (str, tuple, list)) and (hasattr(m, "data_ptr") or hasattr(m, "ptr")):
+            count = m.numel() if hasattr(m, "numel") else getattr(m, "size", self.plan.n_local)
+            if int(count) != self.plan.n_local:
+                raise ValueError(f"set_preconditioner: {int(count)} values, the rank has {self.plan.n_local} rows")
+            if hasattr(m, "dtype") and hasattr(m, "data_ptr") and np.dtype(str(m.dtype).replace("torch.", "")) != self.dtype:
+                raise ValueError(f"set_preconditioner: values of type {m.dtype}, the solver's is {self.dtype}")
+            if hasattr(m, "is_cuda") and not m.is_cuda:
+                raise ValueError("set_preconditioner: the values must be on the device")
+            if hasattr(m, "is_cuda"):
+                import torch
+                torch.cuda.synchronize()        # torch filled the tensor on ITS stream; the library copies it on the context's
+            call = lambda: lib.cgamd_dist_set_preconditioner(self.handle, ptr(m))
+        else:
+            raise ValueError('set_preconditioner: expected None, "jacobi", ("line", stride) or n_local device values')
+        status = call()
+        mine = (int(status), lib.cgamd_last_error().decode(errors="replace") if status else "")
+        if self.plan.world > 1:
+            import torch.distributed as dist
+            everyone = [None] * self.plan.world
+            dist.all_gather_object(everyone, mine, group=group)
+        else:
+            everyone = [mine]
+        bad = [(r, e) for r, e in enumerate(everyone) if e[0] != 0]
+        if bad:
+            lib.cgamd_dist_set_preconditioner(self.handle, None)     # (a failed call left this rank's earlier one in place)
+            r, (code, text) = bad[0]
+            raise _lib.CgAmdError(code, f"set_preconditioner failed on rank {r}: {text}")
 
     def set_rhs(self, b_local, x0_local=None):
         check(self._lib.cgamd_dist_set_rhs(self.handle, ptr(b_local), ptr(x0_local)))

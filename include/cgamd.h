@@ -341,6 +341,31 @@ int cgamd_dist_iterate(cgamd_dist *d, int nIterations);
 int cgamd_dist_get_x(cgamd_dist *d, void *x_local);                                  /* device pointer */
 int cgamd_dist_history(cgamd_dist *d, void *history, int max_entries);
 int cgamd_dist_synchronize(cgamd_dist *d);
+/* Preconditioned CG on the row-partitioned handle.  The preconditioner is RANK-LOCAL (block-Jacobi over the ranks): symmetric, positive
+ * definite whenever A is, and applied without communication.  The three calls are collective in meaning -- every rank must make the
+ * same one -- but local in execution: they do not communicate, so the CALLER makes sure that all ranks succeeded before anyone
+ * iterates (ranks running different recurrences wait for each other's sums until the peer-to-peer time-outs; DistSolver.
+ * set_preconditioner all-gathers the status).  They take effect at the next cgamd_dist_set_rhs: z0 = M^-1 r0, d = z0, rho0 = the
+ * all-reduced r0.z0; rho = r.z then drives alpha and beta, and both sums of an iteration (r.z, r.r) travel in ONE all-reduce round.
+ * cgamd_dist_history keeps returning r.r.  A failed call leaves the handle as it was; contracts otherwise as the cgamd_solver_*
+ * entries of the same names.  Loops: the RCCL loop and both peer-to-peer loops, with or without CGAMD_DIST_GRAPH (a captured graph is
+ * dropped when the preconditioner changes); a CGAMD_DIST_RESIDENT handle runs its launched loop while a preconditioner is set
+ * (cgamd_dist_loop_launches says so: the slab loop has no preconditioned form); on a CGAMD_DIST_SINGLE_REDUCTION handle the three
+ * calls return CGAMD_ERR_STATE (that loop has no PCG form).
+ *   cgamd_dist_set_preconditioner        z = m_local .* r: n_local values of the handle's type, device pointer (copied); NULL removes any
+ *                                        preconditioner -- the handle then returns the bits of one that never had any.
+ *   cgamd_dist_set_preconditioner_jacobi m[i] = 1 / A_local[i][i], built on the device from the rank's matrix (the diagonal of local
+ *                                        row i is local column i).  CGAMD_ERR_INVALID names the smallest LOCAL row whose diagonal is
+ *                                        zero, missing or not finite.
+ *   cgamd_dist_set_preconditioner_line   M = the local entries at column - row in {-stride, 0, +stride} WITH column < n_local: halo
+ *                                        columns (local indices n_local ... n_local + n_halo - 1) are never line neighbours, so lines
+ *                                        end at the rank's row range (with z-slab partitions of an x-fastest grid only z-lines are
+ *                                        cut).  Extracted, factored (no pivoting) and planned on the device as for
+ *                                        cgamd_solver_set_preconditioner_line, errors with the same wording and the local row;
+ *                                        stride in [1, n_local - 1]. */
+int cgamd_dist_set_preconditioner(cgamd_dist *d, const void *m_local);
+int cgamd_dist_set_preconditioner_jacobi(cgamd_dist *d);
+int cgamd_dist_set_preconditioner_line(cgamd_dist *d, int stride);
 /* Peer-to-peer backend (CGAMD_DIST_P2P): instead of RCCL, every rank owns an uncached IPC-shared mailbox
  * (16 KiB header + n_halo values) that its peers write over xGMI; all-reduces are sums in rank order of values
  * deposited in per-rank slots (bitwise identical on all ranks).  Sequence: mailbox_alloc on every rank -> gather
@@ -358,7 +383,8 @@ int cgamd_dist_p2p_error(cgamd_dist *d);
 int cgamd_dist_enable_resident(cgamd_dist *d, long long mailbox_values, const int *rank_n_local, const int *rank_n_halo);
 /* as cgamd_solver_index_codes, for this rank's local matrix (the halo columns of a slab partition sit at constant offsets) */
 int cgamd_dist_index_codes(cgamd_dist *d);
-/* stream operations per iteration of the loop this handle runs (kernel launches, plus RCCL calls with that backend) */
+/* stream operations per iteration of the loop this handle runs (kernel launches, plus RCCL calls with that backend); with a
+ * preconditioner set, of the preconditioned loop (the same counts; two more where a stride-1 line sweep takes its long form) */
 int cgamd_dist_loop_launches(cgamd_dist *d);
 /* number of ranks of the RCCL communicator behind this handle as RCCL itself reports it (ncclCommCount);
  * 0 when the handle has no communicator (peer-to-peer backend, or one rank without peers) */
