@@ -94,6 +94,8 @@ def load():
         "cgamd_solver_solve": (ci, [vp, vp, vp, ci, vp]),
         "cgamd_solver_spmv": (ci, [vp, vp, vp, ci]),
         "cgamd_solver_spmm_rowmajor": (ci, [vp, vp, vp, ci]),
+        "cgamd_last_spmv_form": (ci, [ctypes.POINTER(ci), ci]),
+        "cgamd_solver_dot_partials": (ci, [vp, vp, ll, ctypes.POINTER(ci)]),
         "cgamd_solver_layout": (ci, [vp]),
         "cgamd_solver_loop_launches": (ci, [vp]),
         "cgamd_solver_index_codes": (ci, [vp]),

@@ -351,6 +351,29 @@ class Solver:
     def spmv(self, x, y, fused_dot=False):
         check(self._lib.cgamd_solver_spmv(self.handle, ptr(x), ptr(y), int(fused_dot)))
 
+    SPMV_FAMILIES = ("stream", "rowblock", "vc", "vcp", "chunked", "spmm")
+    SPMV_FORM_FIELDS = ("family", "vec", "width", "index_bits", "value_codes", "nt", "fused", "wide", "grid", "partials")
+
+    def last_spmv_form(self):
+        """what this thread's last SpMV launch really was (include/cgamd.h cgamd_last_spmv_form), as a dict: family by name, `width` =
+        batch length / lanes per row / SpMM group width, `index_bits` 0 / 8 / 16, `value_codes` 0 / 1 (own stream) / 2 (joint)"""
+        out = (ctypes.c_int * len(self.SPMV_FORM_FIELDS))()
+        got = self._lib.cgamd_last_spmv_form(out, len(out))
+        if got < 0:
+            check(-got)
+        form = dict(zip(self.SPMV_FORM_FIELDS, (int(v) for v in out)))
+        form["family"] = self.SPMV_FAMILIES[form["family"]] if form["family"] >= 0 else None
+        return form
+
+    def dot_partials(self):
+        """the d.q partials of the last spmv(..., fused_dot=True): (n_rhs, partials per right-hand side), float64 / complex128"""
+        per = ctypes.c_int()
+        probe = np.empty(1, np.complex128)
+        self._lib.cgamd_solver_dot_partials(self.handle, ptr(probe), 0, ctypes.byref(per))      # too small on purpose: the count
+        out = np.empty((self.n_rhs, per.value), dtype=np.complex128 if self.dtype.kind == "c" else np.float64)
+        check(self._lib.cgamd_solver_dot_partials(self.handle, ptr(out), out.size, ctypes.byref(per)))
+        return out
+
     def spmm_rowmajor(self, x, y, n_rhs):
         """Y[size][n_rhs] = A X on the matrix cores; x, y ROW-MAJOR device arrays, n_rhs in {16, 32}, f32/f64"""
         check(self._lib.cgamd_solver_spmm_rowmajor(self.handle, ptr(x), ptr(y), int(n_rhs)))

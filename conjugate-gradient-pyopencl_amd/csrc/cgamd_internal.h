@@ -163,6 +163,8 @@ int vec_grid(long long n_elems_per_rhs, int dtype, int nrhs = 1);
 // y = A x for nrhs vectors; x has leading dimension ldx (>= number of columns), y has ldy.
 // If partials != nullptr also writes per-work-group partial sums of dvec.y (unconjugated),
 // laid out partials[r * plan.grid + wg] in accumulator precision.
+constexpr int kSpmvFormFields = 10;
+void last_spmv_form(int *out, int n_out);      // what this thread's last launch_spmv launched (spmv.hip record_form)
 int launch_spmv(int dtype, const SpmvPlan &plan, int n, long long nnz, const void *vals, const int *ptr,
                 const int *cols, const void *x, long long ldx, void *y, long long ldy, int nrhs,
                 const void *dvec, void *partials, hipStream_t st, const int *rb_list = nullptr, int rb_count = 0);

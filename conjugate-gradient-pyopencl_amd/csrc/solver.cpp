@@ -1035,6 +1035,23 @@ int cgamd_solver_spmv(cgamd_solver *s, const void *x, void *y, int fused_dot) {
                        fused_dot ? x : nullptr, fused_dot ? s->part_dq : nullptr, s->ctx->stream);
 }
 
+int cgamd_last_spmv_form(int *out, int n_out) {
+    if (!out || n_out < 1) return -fail(CGAMD_ERR_INVALID, "last_spmv_form: null or empty output");
+    last_spmv_form(out, n_out);
+    return n_out < kSpmvFormFields ? n_out : kSpmvFormFields;
+}
+
+int cgamd_solver_dot_partials(cgamd_solver *s, void *out_host, long long cap_values, int *per_rhs) {
+    if (!s || !out_host || !per_rhs) return fail(CGAMD_ERR_INVALID, "dot_partials: null argument");
+    const int P = s->plan.n_partials;
+    *per_rhs = P;
+    if (cap_values < (long long)P * s->nrhs) return fail(CGAMD_ERR_INVALID, "dot_partials: output holds fewer than nRHS * partials values");
+    CG_HIP(hipSetDevice(s->ctx->device));
+    CG_HIP(hipMemcpyAsync(out_host, s->part_dq, acc_size(s->dtype) * (size_t)P * s->nrhs, hipMemcpyDeviceToHost, s->ctx->stream));
+    CG_HIP(hipStreamSynchronize(s->ctx->stream));
+    return CGAMD_OK;
+}
+
 int cgamd_solver_spmm_rowmajor(cgamd_solver *s, const void *x, void *y, int nRHS) {
     if (!s || !x || !y) return fail(CGAMD_ERR_INVALID, "spmm_rowmajor: null argument");
     TuneScope ts(&s->tune);

@@ -936,6 +936,20 @@ void set_kernel_event_pair(hipEvent_t *pair) { t_kernel_events = pair; }
         }                                                                                                                      \
     } while (0)
 
+// cgamd_last_spmv_form: what the calling thread's most recent launch_spmv launched, stored AT the launch sites of spmv_impl (the
+// template arguments of the instance that goes out, not a second reading of the plan), so that a test can assert the form it was
+// written for.  [0] family (0 stream, 1 row-block, 2 vc, 3 vcp, 4 chunked, 5 grouped SpMM; -1: nothing launched yet), [1] VEC,
+// [2] batch length / lanes per row / group width, [3] index encoding (0 aCols, 8, 16), [4] value encoding (0 aValues, 1 two
+// code streams, 2 joint), [5] NT, [6] fused d.q, [7] wide, [8] grid.x, [9] d.q partials per right-hand side (0 when not fused).
+static thread_local int t_form[kSpmvFormFields] = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+static inline void record_form(int family, bool vec, int width, int ienc, int venc, bool nt, bool fused, bool wide, unsigned gx, int parts) {
+    t_form[0] = family; t_form[1] = vec; t_form[2] = width; t_form[3] = ienc; t_form[4] = venc;
+    t_form[5] = nt; t_form[6] = fused; t_form[7] = wide; t_form[8] = (int)gx; t_form[9] = fused ? parts : 0;
+}
+void last_spmv_form(int *out, int n_out) {
+    for (int i = 0; i < n_out && i < kSpmvFormFields; ++i) out[i] = t_form[i];
+}
+
 SpmvPlan make_spmv_plan(int n) {
     SpmvPlan p;
     p.row_blocks = (n + kBlock - 1) / kBlock;
@@ -988,12 +1002,15 @@ static int spmv_impl(const SpmvPlan &plan, int n, long long nnz, const void *val
 #define CG_RB(NT, UNR)                                                                                                  \
     do {                                                                                                                \
         if (coded16) {                                                                                                  \
+            record_form(1, true, UNR, 16, 0, NT, fuse, g5.y > 1, g5.x, plan.row_blocks);                                \
             if (fuse) CG_LAUNCH_EV((spmv_rowblock_kernel<T, kBlock, NT, true, UNR, -4>), g5, block, lds, st, a);        \
             else CG_LAUNCH_EV((spmv_rowblock_kernel<T, kBlock, NT, false, UNR, -4>), g5, block, lds, st, a);            \
         } else if (coded) {                                                                                             \
+            record_form(1, true, UNR, 8, 0, NT, fuse, g5.y > 1, g5.x, plan.row_blocks);                                 \
             if (fuse) CG_LAUNCH_EV((spmv_rowblock_kernel<T, kBlock, NT, true, UNR, -3>), g5, block, lds, st, a);        \
             else CG_LAUNCH_EV((spmv_rowblock_kernel<T, kBlock, NT, false, UNR, -3>), g5, block, lds, st, a);            \
         } else {                                                                                                        \
+            record_form(1, true, UNR, 0, 0, NT, fuse, g5.y > 1, g5.x, plan.row_blocks);                                 \
             if (fuse) CG_LAUNCH_EV((spmv_rowblock_kernel<T, kBlock, NT, true, UNR, -2>), g5, block, lds, st, a);        \
             else CG_LAUNCH_EV((spmv_rowblock_kernel<T, kBlock, NT, false, UNR, -2>), g5, block, lds, st, a);            \
         }                                                                                                               \
@@ -1019,13 +1036,18 @@ static int spmv_impl(const SpmvPlan &plan, int n, long long nnz, const void *val
 #define CG_VC(NT, UNR)                                                                                                  \
     do {                                                                                                                \
         if (joint) {                                                                                                    \
+            record_form(3, true, UNR, 8, 2, NT, fuse, false, gvc.x, plan.row_blocks);                                   \
             if (fuse) CG_LAUNCH_EV((spmv_rowblock_vcp_kernel<T, kBlock, NT, true, UNR, true>), gvc, block, lds2, st, a); \
             else CG_LAUNCH_EV((spmv_rowblock_vcp_kernel<T, kBlock, NT, false, UNR, true>), gvc, block, lds2, st, a);     \
         } else if (pipe) {                                                                                              \
+            record_form(3, true, UNR, 8, 1, NT, fuse, false, gvc.x, plan.row_blocks);                                   \
             if (fuse) CG_LAUNCH_EV((spmv_rowblock_vcp_kernel<T, kBlock, NT, true, UNR, false>), gvc, block, lds2, st, a); \
             else CG_LAUNCH_EV((spmv_rowblock_vcp_kernel<T, kBlock, NT, false, UNR, false>), gvc, block, lds2, st, a);    \
-        } else if (fuse) CG_LAUNCH_EV((spmv_rowblock_vc_kernel<T, kBlock, NT, true, UNR>), gvc, block, lds2, st, a);     \
-        else CG_LAUNCH_EV((spmv_rowblock_vc_kernel<T, kBlock, NT, false, UNR>), gvc, block, lds2, st, a);                \
+        } else {                                                                                                        \
+            record_form(2, true, UNR, 8, 1, NT, fuse, false, gvc.x, plan.row_blocks);                                   \
+            if (fuse) CG_LAUNCH_EV((spmv_rowblock_vc_kernel<T, kBlock, NT, true, UNR>), gvc, block, lds2, st, a);       \
+            else CG_LAUNCH_EV((spmv_rowblock_vc_kernel<T, kBlock, NT, false, UNR>), gvc, block, lds2, st, a);           \
+        }                                                                                                               \
     } while (0)
                 if (unroll == 4) { if (nt) CG_VC(true, 4); else CG_VC(false, 4); }
                 else if (unroll == 5) { if (nt) CG_VC(true, 5); else CG_VC(false, 5); }
@@ -1058,13 +1080,18 @@ static int spmv_impl(const SpmvPlan &plan, int n, long long nnz, const void *val
 #define CG_CH(NT, L)                                                                                                     \
     do {                                                                                                                  \
         if (coded16) {                                                                                                    \
+            record_form(4, true, L, 16, 0, NT, fuse, false, g7.x, plan.row_blocks);                                       \
             if (fuse) hipLaunchKernelGGL((spmv_rowblock_chunked_kernel<T, kBlock, NT, true, L, U, 2>), g7, block, lds, st, a);      \
             else hipLaunchKernelGGL((spmv_rowblock_chunked_kernel<T, kBlock, NT, false, L, U, 2>), g7, block, lds, st, a);          \
         } else if (coded) {                                                                                               \
+            record_form(4, true, L, 8, 0, NT, fuse, false, g7.x, plan.row_blocks);                                        \
             if (fuse) hipLaunchKernelGGL((spmv_rowblock_chunked_kernel<T, kBlock, NT, true, L, U, 1>), g7, block, lds, st, a);      \
             else hipLaunchKernelGGL((spmv_rowblock_chunked_kernel<T, kBlock, NT, false, L, U, 1>), g7, block, lds, st, a);          \
-        } else if (fuse) hipLaunchKernelGGL((spmv_rowblock_chunked_kernel<T, kBlock, NT, true, L, U>), g7, block, lds, st, a);   \
-        else hipLaunchKernelGGL((spmv_rowblock_chunked_kernel<T, kBlock, NT, false, L, U>), g7, block, lds, st, a);       \
+        } else {                                                                                                          \
+            record_form(4, true, L, 0, 0, NT, fuse, false, g7.x, plan.row_blocks);                                        \
+            if (fuse) hipLaunchKernelGGL((spmv_rowblock_chunked_kernel<T, kBlock, NT, true, L, U>), g7, block, lds, st, a); \
+            else hipLaunchKernelGGL((spmv_rowblock_chunked_kernel<T, kBlock, NT, false, L, U>), g7, block, lds, st, a);   \
+        }                                                                                                                 \
     } while (0)
         if (plan.lpr == 2) { if (nt) CG_CH(true, 2); else CG_CH(false, 2); }
         else if (plan.lpr == 4) { if (nt) CG_CH(true, 4); else CG_CH(false, 4); }
@@ -1092,6 +1119,7 @@ static int spmv_impl(const SpmvPlan &plan, int n, long long nnz, const void *val
         if (rbw > RBMAX) rbw = RBMAX;
 #define CG_MM(RBW)                                                                                                         \
     do {                                                                                                                    \
+        record_form(5, true, RBW, 0, 0, nt6, fuse, false, g6.x, plan.row_blocks);                                           \
         if (fuse) {                                                                                                         \
             if (nt6) hipLaunchKernelGGL((spmm_rowblock_kernel<T, kBlock, true, true, RBW>), g6, block, lds, st, b);         \
             else hipLaunchKernelGGL((spmm_rowblock_kernel<T, kBlock, false, true, RBW>), g6, block, lds, st, b);            \
@@ -1120,9 +1148,11 @@ static int spmv_impl(const SpmvPlan &plan, int n, long long nnz, const void *val
         return check_launch("spmm_rowblock");
     }
     if (vec) {
+        record_form(0, true, 0, 0, 0, false, fuse, false, grid.x, plan.grid);      // (the stream kernel has no NT parameter)
         if (fuse) hipLaunchKernelGGL((spmv_stream_kernel<T, kBlock, kQuadsPerThread, true, true>), grid, block, dyn, st, a);
         else hipLaunchKernelGGL((spmv_stream_kernel<T, kBlock, kQuadsPerThread, true, false>), grid, block, dyn, st, a);
     } else {
+        record_form(0, false, 0, 0, 0, false, fuse, false, grid.x, plan.grid);
         if (fuse) hipLaunchKernelGGL((spmv_stream_kernel<T, kBlock, kQuadsPerThread, false, true>), grid, block, dyn, st, a);
         else hipLaunchKernelGGL((spmv_stream_kernel<T, kBlock, kQuadsPerThread, false, false>), grid, block, dyn, st, a);
     }

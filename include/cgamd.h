@@ -229,6 +229,19 @@ int cgamd_solver_preconditioner_source(cgamd_solver *s);
 int cgamd_solver_solve(cgamd_solver *s, const void *b, void *x, int nIterations, void *history);
 /* the solver's SpMV (optionally fused with the d.q partial reduction) on caller vectors -- bench/profiling */
 int cgamd_solver_spmv(cgamd_solver *s, const void *x, void *y, int fused_dot);
+/* Development entries (tests of the SpMV forms; not part of the interface).
+ * cgamd_last_spmv_form: what the CALLING THREAD's most recent SpMV launch (cgamd_solver_spmv, cgamd_spmv, an iteration's SpMV) really
+ * launched, recorded where the kernel is launched.  Writes min(n_out, 10) ints and returns that count (negative: error):
+ * [0] family: 0 generic stream, 1 row-block, 2 value-coded (vc), 3 value-coded pipelined (vcp), 4 chunked, 5 grouped SpMM, -1 none yet;
+ * [1] 16-byte loads (VEC); [2] batch length of the row walk / lanes per row (chunked) / right-hand sides per register group (SpMM);
+ * [3] index encoding: 0 aCols, 8, 16 bits; [4] value encoding: 0 aValues, 1 code stream of its own, 2 joint (offset, value) codes;
+ * [5] non-temporal matrix loads; [6] fused d.q; [7] wide (one work-group per row block AND right-hand side); [8] grid.x;
+ * [9] d.q partials written per right-hand side (0 when not fused). */
+int cgamd_last_spmv_form(int *out, int n_out);
+/* Waits for the handle's stream and copies the d.q partials of its last fused SpMV to the host: [nRHS][*per_rhs] accumulators
+ * (double; two doubles for the complex types), cap_values = accumulators `out_host` holds.  *per_rhs is set even when the
+ * capacity is too small (CGAMD_ERR_INVALID then). */
+int cgamd_solver_dot_partials(cgamd_solver *s, void *out_host, long long cap_values, int *per_rhs);
 /* SpMM on the matrix cores (BASELINE config 4, "MFMA tall-B tile path"): Y[size][nRHS] = A * X[size][nRHS] with
  * the right-hand-side block in ROW-MAJOR layout (element i of RHS r at [i*nRHS + r]); f64 with nRHS = 16 or 32, f32 with 16, 32
  * or 64, complex64 with 16 or 32; any CSR matrix.  Solvers created with such a width keep their vectors in this layout

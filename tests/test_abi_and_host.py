@@ -148,6 +148,42 @@ def test_argument_validation_without_gpu(pkg):
     assert lib.cgamd_gen_poisson2d(None, 1, 1000, None, None, None, ctypes.byref(out)) == 0 and out.value == 4_996_000
 
 
+def test_spmv_form_and_dot_partials_entries_without_gpu(pkg):
+    """the two development entries behind Solver.last_spmv_form() / dot_partials(): declared, exported, bound with the header's
+    signatures, and loud about null arguments"""
+    lib = pkg._lib.load()
+    ext = _declared_functions("cgamd.h")
+    assert "cgamd_last_spmv_form" in ext and "cgamd_solver_dot_partials" in ext
+    header = open(os.path.join(INCLUDE, "cgamd.h")).read()
+    assert "int cgamd_last_spmv_form(int *out, int n_out);" in header
+    assert "int cgamd_solver_dot_partials(cgamd_solver *s, void *out_host, long long cap_values, int *per_rhs);" in header
+    assert lib.cgamd_last_spmv_form.argtypes == [ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+    assert lib.cgamd_solver_dot_partials.argtypes == [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_int)]
+    assert lib.cgamd_last_spmv_form(None, 10) == -1 and b"last_spmv_form" in lib.cgamd_last_error()      # -CGAMD_ERR_INVALID
+    form = (ctypes.c_int * 10)()
+    assert lib.cgamd_last_spmv_form(form, 0) == -1
+    # a thread that has launched no SpMV: family -1, and only as many fields as asked for are written
+    import threading
+    got = {}
+
+    def fresh():
+        f = (ctypes.c_int * 12)(*([77] * 12))
+        got["n3"] = lib.cgamd_last_spmv_form(f, 3)
+        got["f3"] = list(f)
+        got["n12"] = lib.cgamd_last_spmv_form(f, 12)
+        got["f12"] = list(f)
+    th = threading.Thread(target=fresh)
+    th.start()
+    th.join()
+    assert got["n3"] == 3 and got["f3"] == [-1, 0, 0] + [77] * 9
+    assert got["n12"] == 10 and got["f12"] == [-1] + [0] * 9 + [77, 77]
+    per = ctypes.c_int(5)
+    buf = np.zeros(4)
+    assert lib.cgamd_solver_dot_partials(None, pkg._lib.ptr(buf), 4, ctypes.byref(per)) == 1
+    assert b"dot_partials" in lib.cgamd_last_error() and per.value == 5 and not buf.any()
+    assert {"last_spmv_form", "dot_partials"} <= set(dir(pkg.Solver))
+
+
 def test_python_module_mirrors_reference_names(pkg):
     """names and arity of the reference's cl.py (cl.py:16-44,203)"""
     import inspect

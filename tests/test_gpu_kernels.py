@@ -234,6 +234,21 @@ def test_solver_spmv_and_cg_dense_rows(pkg, gpu, dtype, n, avg, long_row):
         got = yb.get()
         scale = np.abs(sp.csr_matrix((np.abs(data), indices, indptr), shape=(n, n))) @ np.abs(x) + 1e-30
         assert np.max(np.abs(got - want) / scale) < RTOL[np.dtype(dtype)], fused
+        if fused:       # ... and the fused d.q: the partials this launch wrote, against x . y of the y it stored (tests/spmv_ref.py)
+            import spmv_ref
+            form, parts = s.last_spmv_form(), s.dot_partials()
+            assert form["fused"] == 1 and parts.shape == (1, form["partials"]) and form["family"] in ("chunked", "rowblock", "stream")
+            if form["family"] == "chunked":     # one partial per 256-row block, the restated block sum bit for bit
+                ref = spmv_ref.block_partials_chunked_in_type(x, got, dtype, form["width"])
+                assert spmv_ref.bit_equal(parts[0], ref)
+            elif form["family"] == "rowblock":
+                assert spmv_ref.bit_equal(parts[0], spmv_ref.block_partials_in_type(x, got, dtype))
+            else:                               # generic kernel: per-thread sums in a grid-dependent order, the derived bound
+                re, im, _ = spmv_ref.dot_ext(x, got, dtype)
+                _, _, s_rows = spmv_ref.spmv_ext(indptr, indices, data, x, dtype)
+                total = parts[0].astype(np.clongdouble if im is not None else np.longdouble).sum()
+                err = abs(total - (re + 1j * im if im is not None else re))
+                assert err <= spmv_ref.stream_dot_bound(x, got, dtype, ip=indptr, s_rows=s_rows[0], chunk=2048)
     s.close()
     # CG: A = |pattern| made symmetric and diagonally dominant (complex: complex-symmetric, as the recurrence expects)
     P = sp.csr_matrix((np.abs(data).astype(np.float64) + 0.1, indices, indptr), shape=(n, n))
