@@ -76,6 +76,8 @@ def load():
         "cgamd_aypx": (ci, [vp, ci, ci, vp, vp, vp, ci]),
         "cgamd_sub": (ci, [vp, ci, ci, vp, vp, vp, ci]),
         "cgamd_solver_create": (ci, [vp, ci, ci, ll, vp, vp, vp, ci, ci, pvp]),
+        "cgamd_solver_create_batched": (ci, [vp, ci, ci, ll, vp, vp, vp, ci, ci, pvp]),
+        "cgamd_solver_systems": (ci, [vp]),
         "cgamd_solver_destroy": (ci, [vp]),
         "cgamd_solver_set_rhs": (ci, [vp, vp, vp, ci]),
         "cgamd_solver_set_preconditioner": (ci, [vp, vp, ci]),

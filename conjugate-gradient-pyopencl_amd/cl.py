@@ -211,10 +211,17 @@ class Solver:
     """Matrix-resident CG handle: the reference re-uploads the matrix and re-JITs
     its kernels on every call (clcg.c:142-214, cl.py:45-46,73-84); here only b goes up and x comes down."""
 
-    def __init__(self, ctx, size, non_zeros, a_values, a_pointers, a_cols, n_rhs=1, flags=0, dtype=None):
+    def __init__(self, ctx, size, non_zeros, a_values, a_pointers, a_cols, n_rhs=1, flags=0, dtype=None, batched=False):
+        """batched=True: n_rhs systems on one pattern (cgamd_solver_create_batched) -- a_values holds n_rhs * non_zeros entries,
+        the values of system r at a_values[r * non_zeros:(r + 1) * non_zeros] in the order of a_cols, and right-hand side r
+        belongs to system r."""
         self.ctx = ctx
         self._lib = _lib.load()
+        self.batched = bool(batched)
+        self.non_zeros = int(non_zeros)
         on_device = bool(flags & _lib.MATRIX_ON_DEVICE)
+        if self.batched:
+            self._check_batched_values(a_values, int(n_rhs))
         if not on_device:
             self.dtype = np.dtype(dtype) if dtype is not None else np.dtype(a_values.dtype)
             a_values = np.ascontiguousarray(a_values, dtype=self.dtype)
@@ -227,15 +234,31 @@ class Solver:
         self._keep = (a_values, a_pointers, a_cols)      # borrowed device arrays must outlive the handle
         self.size, self.n_rhs = int(size), int(n_rhs)
         h = ctypes.c_void_p()
-        check(self._lib.cgamd_solver_create(ctx.handle, _lib.DTYPE_CODE[self.dtype], self.size, int(non_zeros),
-                                            ptr(a_values), ptr(a_pointers), ptr(a_cols), self.n_rhs, int(flags),
-                                            ctypes.byref(h)))
+        create = self._lib.cgamd_solver_create_batched if self.batched else self._lib.cgamd_solver_create
+        check(create(ctx.handle, _lib.DTYPE_CODE[self.dtype], self.size, int(non_zeros), ptr(a_values), ptr(a_pointers), ptr(a_cols),
+                     self.n_rhs, int(flags), ctypes.byref(h)))
         self.handle = h
+
+    def _check_batched_values(self, a_values, n_rhs):
+        """a batched handle's value array holds n_rhs * non_zeros entries (arrays whose length can be read; a bare address cannot)"""
+        count = a_values.numel() if hasattr(a_values, "numel") else getattr(a_values, "size", None)
+        if isinstance(a_values, DeviceBuffer):
+            count = a_values.nbytes // a_values.dtype.itemsize
+        if count is not None and not callable(count) and int(count) != n_rhs * self.non_zeros:
+            raise ValueError(f"a batched handle of {n_rhs} systems takes {n_rhs} * {self.non_zeros} = {n_rhs * self.non_zeros} "
+                             f"values (the values of system r at [r * non_zeros:(r + 1) * non_zeros]), got {int(count)}")
+
+    @property
+    def systems(self):
+        """systems of a batched handle (each right-hand side has a matrix of its own), 0 for every other handle"""
+        return self._lib.cgamd_solver_systems(self.handle)
 
     def reload_matrix(self, a_values, a_pointers, a_cols):
         """new values / pattern of the same size and non-zero count from HOST arrays into a handle that owns its matrix
-        (what the stateless cg() does between calls, include/cgamd.h)"""
+        (what the stateless cg() does between calls, include/cgamd.h); a batched handle takes n_rhs * non_zeros values"""
         a_values = np.ascontiguousarray(a_values, dtype=self.dtype)
+        if self.batched:
+            self._check_batched_values(a_values, self.n_rhs)
         a_pointers = np.ascontiguousarray(a_pointers, dtype=np.int32)
         a_cols = np.ascontiguousarray(a_cols, dtype=np.int32)
         check(self._lib.cgamd_solver_reload_matrix(self.handle, ptr(a_values), ptr(a_pointers), ptr(a_cols)))
@@ -351,7 +374,7 @@ class Solver:
     def spmv(self, x, y, fused_dot=False):
         check(self._lib.cgamd_solver_spmv(self.handle, ptr(x), ptr(y), int(fused_dot)))
 
-    SPMV_FAMILIES = ("stream", "rowblock", "vc", "vcp", "chunked", "spmm")
+    SPMV_FAMILIES = ("stream", "rowblock", "vc", "vcp", "chunked", "spmm", "batched")
     SPMV_FORM_FIELDS = ("family", "vec", "width", "index_bits", "value_codes", "nt", "fused", "wide", "grid", "partials")
 
     def last_spmv_form(self):
@@ -511,26 +534,54 @@ class Solver:
             self.set_preconditioner(None)
 
 
+def _shared_pattern(P):
+    """(indptr, indices, stacked data) of matrices on one pattern; ValueError when an item's pattern differs from that of P[0]"""
+    indptr, indices = np.asarray(P[0].indptr), np.asarray(P[0].indices)
+    for p, A in enumerate(P):
+        if not hasattr(A, "indptr"):
+            raise ValueError(f"sub-domain matrix {p} is no CSR matrix (it has no indptr)")
+        if not (np.array_equal(np.asarray(A.indptr), indptr) and np.array_equal(np.asarray(A.indices), indices)):
+            raise ValueError(f"sub-domain matrix {p} does not share the sparsity pattern of matrix 0 (indptr / indices differ): a "
+                             "batched handle carries ONE pattern; bring the matrices into canonical CSR form (sorted indices, "
+                             "explicit zeros where one of them has an entry) or solve them on handles of their own")
+    return indptr, indices, np.concatenate([np.asarray(A.data).ravel() for A in P])
+
+
 def solve_subdomains(ctx, P0, residuals, n_iterations, dtype=np.csingle, solver=None):
-    """The batched sub-domain solve of the reference's Additive-Schwarz preconditioner, `as_prec` with
-    UseCG in {2, 3} (p_h-PY_C-CL.py:1918-1937, 1938-1953): all n_my sub-domains share ONE matrix P[0];
-    their residuals are stacked RHS-major into one b, solved with n_rhs = n_my and a fixed number of
-    iterations, and split back.  P0: scipy CSR (or (indptr, indices, data)); residuals: list of arrays.
-    Pass `solver` (a Solver built for P0 with n_rhs = len(residuals)) to keep the matrix resident across
-    the outer GMRES iterations -- the reference re-uploads it on every call (clcg.c:202-211).
+    """The batched sub-domain solve of the reference's Additive-Schwarz preconditioner `as_prec`.
+
+    * UseCG in {2, 3} (p_h-PY_C-CL.py:1918-1937, 1938-1953): all n_my sub-domains share ONE matrix P[0] -- P0: scipy CSR (or
+      (indptr, indices, data)).  Their residuals are stacked RHS-major into one b, solved with n_rhs = n_my and a fixed number of
+      iterations, and split back.
+    * VarCoeff / UseCG == 4 (p_h-PY_C-CL.py:1970-1985): every sub-domain has its own P[p] on the same grid -- P0: a list or tuple
+      of len(residuals) CSR matrices (items with .indptr) on ONE sparsity pattern.  Their `data` are stacked into one batched handle
+      (Solver(..., batched=True)): one upload, one launch sequence for all sub-domains instead of the reference's loop of
+      single-system cg() calls.  ValueError, before anything touches the device, when an item's indptr / indices differ from P[0]'s.
+    residuals: list of arrays.  Pass `solver` (a Solver built for P0 with n_rhs = len(residuals); for a list of matrices a batched
+    one, whose values are then reloaded from the list) to keep the allocations and the pattern resident across the outer GMRES
+    iterations -- the reference re-uploads everything on every call (clcg.c:202-211).
     Returns a list of complex arrays shaped like the inputs (`x[p*size:(p+1)*size].astype(complex)`)."""
-    if hasattr(P0, "indptr"):
+    n_my = len(residuals)
+    batched = isinstance(P0, (list, tuple)) and len(P0) > 0 and hasattr(P0[0], "indptr")
+    if batched:
+        if len(P0) != n_my:
+            raise ValueError(f"{len(P0)} sub-domain matrices for {n_my} residuals")
+        indptr, indices, data = _shared_pattern(P0)
+        if solver is not None and not getattr(solver, "batched", False):
+            raise ValueError("a list of sub-domain matrices needs a batched Solver (Solver(..., batched=True))")
+    elif hasattr(P0, "indptr"):
         indptr, indices, data = P0.indptr, P0.indices, P0.data
     else:
         indptr, indices, data = P0
     size = len(indptr) - 1
-    n_my = len(residuals)
     b_values = np.zeros(size * n_my, dtype=dtype)
     for p in range(n_my):
         b_values[p * size:(p + 1) * size] = np.asarray(residuals[p]).ravel()
     own = solver is None
     if own:
-        solver = Solver(ctx, size, len(indices), np.asarray(data, dtype=dtype), indptr, indices, n_my)
+        solver = Solver(ctx, size, len(indices), np.asarray(data, dtype=dtype), indptr, indices, n_my, batched=batched)
+    elif batched:
+        solver.reload_matrix(np.asarray(data, dtype=dtype), indptr, indices)
     try:
         solver.set_rhs(b_values, None)
         solver.iterate(n_iterations)

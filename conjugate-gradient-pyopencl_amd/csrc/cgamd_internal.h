@@ -165,9 +165,16 @@ int vec_grid(long long n_elems_per_rhs, int dtype, int nrhs = 1);
 // laid out partials[r * plan.grid + wg] in accumulator precision.
 constexpr int kSpmvFormFields = 10;
 void last_spmv_form(int *out, int n_out);      // what this thread's last launch_spmv launched (spmv.hip record_form)
+void record_spmv_form(const int *fields);      // kSpmvFormFields ints of an SpMV launcher outside spmv.hip (batched.hip: family 6)
 int launch_spmv(int dtype, const SpmvPlan &plan, int n, long long nnz, const void *vals, const int *ptr,
                 const int *cols, const void *x, long long ldx, void *y, long long ldy, int nrhs,
                 const void *dvec, void *partials, hipStream_t st, const int *rb_list = nullptr, int rb_count = 0);
+// nsys systems on one pattern (batched.hip): y_r = A_r x_r with the values of system r at vals + r * nnz (vals: nsys * nnz entries, any
+// alignment), x_r = x + r * ldx, y_r = y + r * ldy.  partials != nullptr: the d.q partials of 256-row blocks, partials[r * plan.n_partials
+// + block] (plan.n_partials >= plan.row_blocks), the dot being dvec_r.y_r with dvec_r = dvec + r * ldx.  Uses the plan's row_blocks,
+// max_span, max_row, n_partials and nt only
+int launch_spmv_batched(int dtype, const SpmvPlan &plan, int n, long long nnz, int nsys, const void *vals, const int *ptr, const int *cols,
+                        const void *x, long long ldx, void *y, long long ldy, const void *dvec, void *partials, hipStream_t st);
 // flag[rb] = 1 when row block rb references a column >= n_local (needs the halo); kBlock rows per block
 int launch_halo_flags(int n, const int *ptr, const int *cols, int n_local, int row_blocks, int *flag, hipStream_t st);
 // partial sums of a.b -> partials[r*grid + wg]

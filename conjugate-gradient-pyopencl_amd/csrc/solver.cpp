@@ -30,6 +30,10 @@ struct cgamd_solver {
     // which keeps every right-hand side's vectors 16-byte aligned: the vectorised multi-RHS kernels and the resident loops apply
     // to any size.  The caller's arrays keep their own stride (strided copies in set_rhs / get_x).
     int n_user = 0;
+    // cgamd_solver_create_batched: nsys systems on one pattern, the values of system r at vals + r * nnz and right-hand side r its
+    // own; 0 = every other handle (one matrix for all right-hand sides).  A batched handle has nrhs == nsys, runs the launched loops
+    // only (no resident loop, no row-major layout, no codes, no preconditioner) and launches its SpMV through launch_spmv_batched.
+    int nsys = 0;
     bool own_ptr = false;   // a borrowed device matrix whose row pointers were copied to append the padding rows
     long long nnz = 0;
     void *vals = nullptr;
@@ -130,13 +134,21 @@ static void *dbuf(cgamd_solver *s, int k) { return (s->fused2 && (k & 1)) ? s->d
 static bool precond_set(const cgamd_solver *s) { return s->mdiag != nullptr || s->tri_on; }
 static bool fused2_now(const cgamd_solver *s) { return s->fused2 && !s->rm && !precond_set(s) && !(s->flags & CGAMD_UNFUSED); }
 
+// the handle's SpMV on n rows of RHS-major vectors: the batched kernel where every right-hand side has a matrix of its own
+static int handle_spmv(cgamd_solver *s, int n, const void *x, long long ldx, void *y, long long ldy, const void *dvec, void *partials,
+                       hipStream_t st) {
+    if (s->nsys)
+        return launch_spmv_batched(s->dtype, s->plan, n, s->nnz, s->nsys, s->vals, s->ptr, s->cols, x, ldx, y, ldy, dvec, partials, st);
+    return launch_spmv(s->dtype, s->plan, n, s->nnz, s->vals, s->ptr, s->cols, x, ldx, y, ldy, s->nrhs, dvec, partials, st);
+}
+
 // k = iterations already enqueued since set_rhs (the iteration being enqueued is number k + 1)
 static int enqueue_spmv(cgamd_solver *s, int k, hipStream_t st) {
     const int dt = s->dtype, n = s->n, nr = s->nrhs;
     // timed pass: the row-block kernel of a single right-hand side takes the event pair on its dispatch (kernel duration);
     // every other SpMV form is bracketed by hipEventRecord (duration + launch gaps)
     const bool fused2 = fused2_now(s);
-    const bool ext = s->ev_pair && !fused2 && !s->rm && nr == 1 && s->plan.kind == 5;
+    const bool ext = s->ev_pair && !fused2 && !s->rm && nr == 1 && s->plan.kind == 5 && !s->nsys;
     if (s->ev_pair && !ext) CG_HIP(hipEventRecord(s->ev_pair[0], st));
     if (ext) set_kernel_event_pair(s->ev_pair);
     int rc;
@@ -144,8 +156,8 @@ static int enqueue_spmv(cgamd_solver *s, int k, hipStream_t st) {
         rc = launch_spmv_fused(dt, s->plan, n, s->nnz, s->vals, s->ptr, s->cols, dbuf(s, k), dbuf(s, k + 1), s->r, s->q, nr, s->part_dq,
                                s->part_rr, s->vgrid, s->sc, st);
     else if (s->rm) rc = launch_spmm_rm(dt, n, s->nnz, s->vals, s->ptr, s->cols, s->d, s->q, nr, s->part_dq, s->plan.max_quad, s->rm_pace, st);
-    else if ((s->flags & CGAMD_UNFUSED) && !s->tri_on) rc = launch_spmv(dt, s->plan, n, s->nnz, s->vals, s->ptr, s->cols, s->d, n, s->q, n, nr, nullptr, nullptr, st);
-    else rc = launch_spmv(dt, s->plan, n, s->nnz, s->vals, s->ptr, s->cols, s->d, n, s->q, n, nr, s->d, s->part_dq, st);
+    else if ((s->flags & CGAMD_UNFUSED) && !s->tri_on) rc = handle_spmv(s, n, s->d, n, s->q, n, nullptr, nullptr, st);
+    else rc = handle_spmv(s, n, s->d, n, s->q, n, s->d, s->part_dq, st);
     set_kernel_event_pair(nullptr);
     if (rc) return rc;
     if (s->ev_pair && !ext) CG_HIP(hipEventRecord(s->ev_pair[1], st));
@@ -373,23 +385,40 @@ static int ensure_history(cgamd_solver *s, int entries) {
     return CGAMD_OK;
 }
 
-extern "C" {
+// What a batched handle's plan holds once the pattern is known: one d.q partial per 256-row block whichever kernel of batched.hip
+// runs (the vector kernels sum plan.n_partials of them per right-hand side), the cache policy priced on ALL value arrays, and none of
+// the loops or codes that assume one matrix.
+static void finalize_batched_plan(cgamd_solver *s) {
+    s->plan.n_partials = s->plan.row_blocks;
+    const size_t V = dtype_size(s->dtype), MB = (size_t)1 << 20;
+    const size_t matrix_bytes = (size_t)s->nnz * (V * (size_t)s->nsys + 4) + ((size_t)s->n + 1) * 4;
+    const size_t vector_bytes = (size_t)s->n * V * (size_t)s->nrhs;
+    s->plan.nt = tune().spmv_nt >= 0 ? (tune().spmv_nt != 0) : (matrix_bytes > 256 * MB);      // as finalize_spmv_plan decides
+    if (tune().vec_nt >= 0) s->plan.vec_nt = tune().vec_nt;
+    else if (!s->plan.nt) s->plan.vec_nt = (matrix_bytes + 5 * vector_bytes <= 200 * MB) ? 0 : 3;
+    else s->plan.vec_nt = (matrix_bytes <= 512 * MB) ? 0 : 3;
+    s->fused2 = false;
+    s->res_ok = false;
+    s->resw.ok = false;
+}
 
-int cgamd_solver_create(cgamd_ctx *ctx, int dtype, int size, long long nnz, const void *aValues, const int *aPointers,
-                        const int *aCols, int nRHS, int flags, cgamd_solver **out) {
-    if (!out) return fail(CGAMD_ERR_INVALID, "solver_create: out is NULL");
+// nsys == 0: cgamd_solver_create; nsys >= 1: cgamd_solver_create_batched (nRHS == nsys, aValues holds nsys * nnz values)
+static int create_impl(const std::string &who, cgamd_ctx *ctx, int dtype, int size, long long nnz, const void *aValues,
+                       const int *aPointers, const int *aCols, int nRHS, int nsys, int flags, cgamd_solver **out) {
+    if (!out) return fail(CGAMD_ERR_INVALID, who + ": out is NULL");
     *out = nullptr;
-    if (!ctx) return fail(CGAMD_ERR_INVALID, "solver_create: ctx is NULL");
-    if (dtype < 0 || dtype > 3) return fail(CGAMD_ERR_INVALID, "solver_create: bad dtype");
-    if (size < 1 || nnz < 0 || nRHS < 1) return fail(CGAMD_ERR_INVALID, "solver_create: bad size/nnz/nRHS");
-    if (nnz > 2147483647LL - 8192) return fail(CGAMD_ERR_INVALID, "solver_create: nnz exceeds int32 row pointers");
-    if (!aPointers || (nnz > 0 && (!aValues || !aCols))) return fail(CGAMD_ERR_INVALID, "solver_create: null matrix pointer");
+    if (!ctx) return fail(CGAMD_ERR_INVALID, who + ": ctx is NULL");
+    if (dtype < 0 || dtype > 3) return fail(CGAMD_ERR_INVALID, who + ": bad dtype");
+    if (size < 1 || nnz < 0 || nRHS < 1) return fail(CGAMD_ERR_INVALID, who + (nsys ? ": bad size/nnz/nSystems" : ": bad size/nnz/nRHS"));
+    if (nnz > 2147483647LL - 8192) return fail(CGAMD_ERR_INVALID, who + ": nnz exceeds int32 row pointers");
+    if (!aPointers || (nnz > 0 && (!aValues || !aCols))) return fail(CGAMD_ERR_INVALID, who + ": null matrix pointer");
+    const size_t nmat = nsys ? (size_t)nsys : 1;      // value arrays of nnz entries behind aValues
     CG_HIP(hipSetDevice(ctx->device));
     const size_t vs = dtype_size(dtype);
     cgamd_solver *s = new cgamd_solver();
     s->tune = tune_snapshot();
     TuneScope ts(&s->tune);
-    s->ctx = ctx; s->dtype = dtype; s->n = size; s->n_user = size; s->nnz = nnz; s->nrhs = nRHS; s->flags = flags;
+    s->ctx = ctx; s->dtype = dtype; s->n = size; s->n_user = size; s->nnz = nnz; s->nrhs = nRHS; s->nsys = nsys; s->flags = flags;
     // Row-major block + matrix-core SpMM inside the loop: by default only where the whole iteration is faster than the RHS-major
     // one (measured in one process at N = 1M, profiles/r2_experiments/spmm_ab12.log: f64 x 32 +8 %; f64 x 16, f32 x 32 equal within
     // 1 %, complex64 x 16 slower).  spmm_rowmajor = 2 takes it for every supported type, 0 never.
@@ -397,7 +426,7 @@ int cgamd_solver_create(cgamd_ctx *ctx, int dtype, int size, long long nnz, cons
     // (up to 32768 rows the resident loop is several times faster than any launched loop; between that and ~1M rows the chip-wide
     // resident groups take over when they apply, setup_resident_wide_plan)
     const bool rm_wins = dtype == CGAMD_F64 && nRHS == 32 && size > 32768;
-    s->rm_ok = nRHS > 1 && (rm_knob >= 2 || (rm_knob == 1 && rm_wins)) && !(flags & CGAMD_UNFUSED) && spmm_rm_supported(dtype, nRHS, size);
+    s->rm_ok = !nsys && nRHS > 1 && (rm_knob >= 2 || (rm_knob == 1 && rm_wins)) && !(flags & CGAMD_UNFUSED) && spmm_rm_supported(dtype, nRHS, size);
     if (s->rm_ok) s->rm_vgrid = rm_vec_grid((long long)size * nRHS, dtype);
     {
         const int E = (int)(16 / vs);      // values per 16-byte pack
@@ -425,11 +454,11 @@ int cgamd_solver_create(cgamd_ctx *ctx, int dtype, int size, long long nnz, cons
     } else {
         rc = validate_csr_host(size, nnz, aPointers, aCols);
         s->own_matrix = true;
-        if (!rc) rc = dmalloc(&s->vals, (size_t)nnz * vs + 64, "aValues");
+        if (!rc) rc = dmalloc(&s->vals, (size_t)nnz * nmat * vs + 64, "aValues");
         if (!rc) rc = dmalloc((void **)&s->ptr, (size_t)(n_int + 1) * 4, "aPointers");
         if (!rc) rc = dmalloc((void **)&s->cols, (size_t)nnz * 4 + 64, "aCols");
         if (!rc && nnz) {
-            hipError_t e = hipMemcpyAsync(s->vals, aValues, (size_t)nnz * vs, hipMemcpyHostToDevice, ctx->stream);
+            hipError_t e = hipMemcpyAsync(s->vals, aValues, (size_t)nnz * nmat * vs, hipMemcpyHostToDevice, ctx->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(s->cols, aCols, (size_t)nnz * 4, hipMemcpyHostToDevice, ctx->stream);
             if (e != hipSuccess) rc = fail(CGAMD_ERR_HIP, std::string("upload matrix: ") + hipGetErrorString(e));
         }
@@ -479,12 +508,13 @@ int cgamd_solver_create(cgamd_ctx *ctx, int dtype, int size, long long nnz, cons
     if (!rc && s->rm_ok) s->rm_nwg = spmm_rm_grid(dtype, nRHS, size, s->plan.max_quad, true);
     if (!rc && s->rm_ok) rc = dmalloc((void **)&s->rm_pace, sizeof(int) * kSpmmPaceInts, "spmm pace counters");
     if (!rc && s->rm_ok && hipMemsetAsync(s->rm_pace, 0, sizeof(int) * kSpmmPaceInts, ctx->stream) != hipSuccess) rc = fail(CGAMD_ERR_HIP, "hipMemsetAsync(spmm pace counters)");
-    if (!rc) s->fused2 = fused2_ok(s->plan, dtype, nRHS, s->vals, s->cols);
-    if (!rc) rc = setup_resident(s);
-    if (!rc) rc = setup_index_codes(s);
+    if (!rc && nsys) finalize_batched_plan(s);
+    if (!rc && !nsys) s->fused2 = fused2_ok(s->plan, dtype, nRHS, s->vals, s->cols);
+    if (!rc && !nsys) rc = setup_resident(s);
+    if (!rc && !nsys) rc = setup_index_codes(s);
     if (!rc) {
         hipError_t e = hipStreamSynchronize(ctx->stream);  // host matrix arrays may go away after return
-        if (e != hipSuccess) rc = fail(CGAMD_ERR_HIP, std::string("solver_create sync: ") + hipGetErrorString(e));
+        if (e != hipSuccess) rc = fail(CGAMD_ERR_HIP, who + " sync: " + hipGetErrorString(e));
     }
     if (rc) {
         std::string keep = cgamd_last_error();
@@ -496,7 +526,28 @@ int cgamd_solver_create(cgamd_ctx *ctx, int dtype, int size, long long nnz, cons
     return CGAMD_OK;
 }
 
+extern "C" {
+
+int cgamd_solver_create(cgamd_ctx *ctx, int dtype, int size, long long nnz, const void *aValues, const int *aPointers,
+                        const int *aCols, int nRHS, int flags, cgamd_solver **out) {
+    return create_impl("solver_create", ctx, dtype, size, nnz, aValues, aPointers, aCols, nRHS, 0, flags, out);
+}
+
+int cgamd_solver_create_batched(cgamd_ctx *ctx, int dtype, int size, long long nnz, const void *aValues, const int *aPointers,
+                                const int *aCols, int nSystems, int flags, cgamd_solver **out) {
+    if (out) *out = nullptr;
+    if (nSystems < 1) return fail(CGAMD_ERR_INVALID, "solver_create_batched: nSystems must be at least 1");
+    return create_impl("solver_create_batched", ctx, dtype, size, nnz, aValues, aPointers, aCols, nSystems, nSystems, flags, out);
+}
+
+int cgamd_solver_systems(cgamd_solver *s) { return s ? s->nsys : -CGAMD_ERR_INVALID; }
+
 static int diag_impl(cgamd_solver *s, const void *m, int on_device);
+// a batched handle (cgamd_solver_create_batched) has a matrix per right-hand side: one M shared by all of them preconditions none
+static int batched_refuses(const char *who) {
+    return fail(CGAMD_ERR_STATE, std::string(who) + ": the handle is batched (a matrix of its own per right-hand side); a preconditioner "
+                                                    "shared by all right-hand sides has no meaning for different systems");
+}
 static int line_from_matrix(cgamd_solver *s, const std::string &who, int stride);
 static int jacobi_from_matrix(cgamd_solver *s, const std::string &who);
 
@@ -513,7 +564,7 @@ int cgamd_solver_reload_matrix(cgamd_solver *s, const void *aValues, const int *
     const size_t vs = dtype_size(s->dtype);
     s->rhs_set = false;
     if (s->nnz) {
-        CG_HIP(hipMemcpyAsync(s->vals, aValues, (size_t)s->nnz * vs, hipMemcpyHostToDevice, st));
+        CG_HIP(hipMemcpyAsync(s->vals, aValues, (size_t)s->nnz * (s->nsys ? (size_t)s->nsys : 1) * vs, hipMemcpyHostToDevice, st));
         CG_HIP(hipMemcpyAsync(s->cols, aCols, (size_t)s->nnz * 4, hipMemcpyHostToDevice, st));
     }
     const bool same_ptr = s->ptr_host.size() == (size_t)s->n + 1 && memcmp(s->ptr_host.data(), aPointers, ((size_t)s->n_user + 1) * 4) == 0;
@@ -528,6 +579,11 @@ int cgamd_solver_reload_matrix(cgamd_solver *s, const void *aValues, const int *
         if ((size_t)std::max(s->plan.grid, s->plan.row_blocks) > s->part_dq_cap) return fail(CGAMD_ERR_STATE, "reload_matrix: partial buffer too small");
         if (s->rm_ok) s->rm_nwg = spmm_rm_grid(s->dtype, s->nrhs, s->n, s->plan.max_quad, true);
         s->fused2 = fused2_ok(s->plan, s->dtype, s->nrhs, s->vals, s->cols);
+        if (s->nsys) finalize_batched_plan(s);
+    }
+    if (s->nsys) {                                  // no resident loop, no codes, no preconditioner to follow the matrix
+        CG_HIP(hipStreamSynchronize(st));
+        return CGAMD_OK;
     }
     if (int rc = setup_resident(s)) return rc;      // also with unchanged row pointers: the column range of a row slice may have moved
     {                                               // the columns were replaced: their codes go with them
@@ -611,8 +667,7 @@ int cgamd_solver_set_rhs(cgamd_solver *s, const void *b, const void *x0, int on_
         else CG_HIP(hipMemsetAsync(s->x, 0, vbytes, st));
     }
     // r = b - A x0 ; d = r ; delta0 = r.r   (clcg.c:255-292)
-    if ((rc = launch_spmv(s->dtype, s->plan, s->n, s->nnz, s->vals, s->ptr, s->cols, s->x, s->n, s->q, s->n, s->nrhs,
-                          nullptr, nullptr, st))) return rc;
+    if ((rc = handle_spmv(s, s->n, s->x, s->n, s->q, s->n, nullptr, nullptr, st))) return rc;
     if ((rc = launch_sub(s->dtype, s->n, s->b, s->q, s->r, s->n, s->nrhs, st))) return rc;
     if (s->tri_on) {  // z0 = M^-1 r0 (the line sweeps), p0 = z0, rho0 = r0.z0
         void *prz = s->tri_part, *prr = static_cast<char *>(s->tri_part) + acc_size(s->dtype) * (size_t)s->tri.grid * s->nrhs;
@@ -647,6 +702,7 @@ static void drop_tridiag(cgamd_solver *s) {
 // preconditioner.  The next cgamd_solver_set_rhs starts the preconditioned recurrence; history then holds r.r as before.
 int cgamd_solver_set_preconditioner(cgamd_solver *s, const void *m, int on_device) {
     if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner: solver is NULL");
+    if (s->nsys) return m ? batched_refuses("set_preconditioner") : CGAMD_OK;      // there is none to remove
     TuneScope ts(&s->tune);
     return diag_impl(s, m, on_device);
 }
@@ -729,6 +785,7 @@ static int tridiag_strided_impl(cgamd_solver *s, const std::string &who, int str
 }
 int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, const void *diag, const void *upper, int on_device) {
     if (!s || !lower || !diag || !upper) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag: null argument");
+    if (s->nsys) return batched_refuses("set_preconditioner_tridiag");
     TuneScope ts(&s->tune);
     return tridiag_strided_impl(s, "set_preconditioner_tridiag", 1, lower, diag, upper, on_device);
 }
@@ -736,6 +793,7 @@ int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, 
 int cgamd_solver_set_preconditioner_tridiag_strided(cgamd_solver *s, int stride, const void *lower, const void *diag, const void *upper,
                                                     int on_device) {
     if (!s || !lower || !diag || !upper) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag_strided: null argument");
+    if (s->nsys) return batched_refuses("set_preconditioner_tridiag_strided");
     if (stride < 1 || stride >= s->n_user)
         return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag_strided: stride must be in [1, size - 1]");
     TuneScope ts(&s->tune);
@@ -760,6 +818,7 @@ static int line_from_matrix(cgamd_solver *s, const std::string &who, int stride)
 }
 int cgamd_solver_set_preconditioner_line(cgamd_solver *s, int stride) {
     if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner_line: solver is NULL");
+    if (s->nsys) return batched_refuses("set_preconditioner_line");
     if (stride < 1 || stride >= s->n_user) return fail(CGAMD_ERR_INVALID, "set_preconditioner_line: stride must be in [1, size - 1]");
     TuneScope ts(&s->tune);
     return line_from_matrix(s, "set_preconditioner_line", stride);
@@ -781,6 +840,7 @@ static int jacobi_from_matrix(cgamd_solver *s, const std::string &who) {
 }
 int cgamd_solver_set_preconditioner_jacobi(cgamd_solver *s) {
     if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner_jacobi: solver is NULL");
+    if (s->nsys) return batched_refuses("set_preconditioner_jacobi");
     TuneScope ts(&s->tune);
     return jacobi_from_matrix(s, "set_preconditioner_jacobi");
 }
@@ -906,6 +966,7 @@ int cgamd_solver_iterate(cgamd_solver *s, int nIterations) {
 int cgamd_solver_iterate_tol(cgamd_solver *s, int maxIterations, double tol, int *iterations_run) {
     if (!s || !iterations_run) return fail(CGAMD_ERR_INVALID, "iterate_tol: null argument");
     if (!(tol > 0.) || maxIterations < 0) return fail(CGAMD_ERR_INVALID, "iterate_tol: tol must be positive, maxIterations >= 0");
+    if (s->nsys) return fail(CGAMD_ERR_STATE, "iterate_tol: a batched handle runs a launched loop (check the history from the host)");
     if (!s->rhs_set) return fail(CGAMD_ERR_STATE, "iterate_tol: call set_rhs first");
     if (s->nrhs != 1) return fail(CGAMD_ERR_STATE, "iterate_tol: one right-hand side");
     {
@@ -1031,8 +1092,7 @@ int cgamd_solver_spmv(cgamd_solver *s, const void *x, void *y, int fused_dot) {
     TuneScope ts(&s->tune);
     CG_HIP(hipSetDevice(s->ctx->device));
     // the caller's vectors have the caller's stride; the plan fits both sizes (same row blocks, the appended rows are empty)
-    return launch_spmv(s->dtype, s->plan, s->n_user, s->nnz, s->vals, s->ptr, s->cols, x, s->n_user, y, s->n_user, s->nrhs,
-                       fused_dot ? x : nullptr, fused_dot ? s->part_dq : nullptr, s->ctx->stream);
+    return handle_spmv(s, s->n_user, x, s->n_user, y, s->n_user, fused_dot ? x : nullptr, fused_dot ? s->part_dq : nullptr, s->ctx->stream);
 }
 
 int cgamd_last_spmv_form(int *out, int n_out) {
@@ -1054,6 +1114,7 @@ int cgamd_solver_dot_partials(cgamd_solver *s, void *out_host, long long cap_val
 
 int cgamd_solver_spmm_rowmajor(cgamd_solver *s, const void *x, void *y, int nRHS) {
     if (!s || !x || !y) return fail(CGAMD_ERR_INVALID, "spmm_rowmajor: null argument");
+    if (s->nsys) return fail(CGAMD_ERR_STATE, "spmm_rowmajor: the handle is batched (a matrix of its own per right-hand side)");
     TuneScope ts(&s->tune);
     CG_HIP(hipSetDevice(s->ctx->device));
     return launch_spmm_rm(s->dtype, s->n_user, s->nnz, s->vals, s->ptr, s->cols, x, y, nRHS, nullptr, s->plan.max_quad, s->rm_pace, s->ctx->stream);
@@ -1075,10 +1136,12 @@ int cgamd_solver_loop_launches(cgamd_solver *s) {
 
 int cgamd_solver_index_codes(cgamd_solver *s) { return s ? s->n_offsets : -CGAMD_ERR_INVALID; }
 
+// value arrays the byte models count, each once (a batched handle: one per system), beside the indices, which are counted once
+static long long value_arrays(const cgamd_solver *s) { return s->nsys ? s->nsys : 1; }
 long long cgamd_solver_spmv_bytes(cgamd_solver *s) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
-    return s->nnz * (V + 4) + ((long long)s->n_user + 1) * 4 + 2LL * s->n_user * V * s->nrhs;
+    return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + 2LL * s->n_user * V * s->nrhs;
 }
 // vector passes of the tridiagonal loop, counted once per right-hand side and once for the factors all of them share: SpMV
 // (p, q) 2 + sweep (r, q in; r, z out) 4 + update (z, p, x in; x, p out) 5 = 11 per RHS and nl, ne, w = 3; the long form reads
@@ -1093,7 +1156,7 @@ long long cgamd_solver_iter_bytes(cgamd_solver *s, int fused) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
     if (s->tri_on) return s->nnz * (V + 4) + ((long long)s->n_user + 1) * 4 + tri_passes(s) * s->n_user * V;
-    return s->nnz * (V + 4) + ((long long)s->n_user + 1) * 4 + (fused ? 11LL : 14LL) * s->n_user * V * s->nrhs;
+    return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + (fused ? 11LL : 14LL) * s->n_user * V * s->nrhs;
 }
 
 // What the handle's own kernels MOVE (the physical byte model the roofline fraction is priced on): index bytes per non-zero as
@@ -1110,7 +1173,7 @@ static bool joint_form(const cgamd_solver *s) {
 long long cgamd_solver_spmv_moved_bytes(cgamd_solver *s) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
-    const long long value_bytes = joint_form(s) ? 0 : s->plan.vcodes ? 1 : V;      // value codes: one byte per entry instead of the value; joint codes: one byte for both
+    const long long value_bytes = joint_form(s) ? 0 : s->plan.vcodes ? 1 : V * value_arrays(s);      // value codes: one byte per entry instead of the value; joint codes: one byte for both
     return s->nnz * (value_bytes + index_bytes_per_nnz(s)) + ((long long)s->n_user + 1) * 4 + 2LL * s->n_user * V * s->nrhs;
 }
 int cgamd_solver_value_codes(cgamd_solver *s) { return s ? s->n_values : -CGAMD_ERR_INVALID; }
@@ -1119,7 +1182,7 @@ long long cgamd_solver_iter_moved_bytes(cgamd_solver *s) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
     const long long passes = (s->flags & CGAMD_UNFUSED) ? 14 : s->mdiag ? 12 : 10;
-    const long long value_bytes = joint_form(s) ? 0 : s->plan.vcodes ? 1 : V;
+    const long long value_bytes = joint_form(s) ? 0 : s->plan.vcodes ? 1 : V * value_arrays(s);
     const long long matrix = s->nnz * (value_bytes + index_bytes_per_nnz(s)) + ((long long)s->n_user + 1) * 4;
     if (s->tri_on) return matrix + tri_passes(s) * s->n_user * V;
     return matrix + passes * s->n_user * V * s->nrhs;

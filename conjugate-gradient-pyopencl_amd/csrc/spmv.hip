@@ -949,6 +949,10 @@ static inline void record_form(int family, bool vec, int width, int ienc, int ve
 void last_spmv_form(int *out, int n_out) {
     for (int i = 0; i < n_out && i < kSpmvFormFields; ++i) out[i] = t_form[i];
 }
+// launchers outside this file (batched.hip) record what they launched through this
+void record_spmv_form(const int *fields) {
+    for (int i = 0; i < kSpmvFormFields; ++i) t_form[i] = fields[i];
+}
 
 SpmvPlan make_spmv_plan(int n) {
     SpmvPlan p;

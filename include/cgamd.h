@@ -120,6 +120,26 @@ int cgamd_sub(cgamd_ctx *ctx, int dtype, int size, const void *a, const void *b,
 
 int cgamd_solver_create(cgamd_ctx *ctx, int dtype, int size, long long nnz, const void *aValues,
                         const int *aPointers, const int *aCols, int nRHS, int flags, cgamd_solver **out);
+/* nSystems linear systems on ONE pattern: aPointers / aCols are shared, aValues holds nSystems * nnz values, the values of
+ * system r at aValues[r * nnz + j] in the order of aCols.  Right-hand side r (b, x0, x, history column r) belongs to system r;
+ * the handle's nRHS is nSystems.  This is the reference's additive-Schwarz step with variable coefficients (as_prec with VarCoeff,
+ * p_h-PY_C-CL.py:1970-1985: a matrix P[p] per sub-domain on the same grid), which the reference solves one sub-domain after another.
+ * All four value types, any nSystems >= 1 and size >= 1; flags CGAMD_MATRIX_ON_DEVICE (the borrowed value array is nSystems * nnz
+ * long; any alignment of the element type), CGAMD_NO_GRAPH, CGAMD_UNFUSED; CSR validation as in cgamd_solver_create.  aValues need
+ * no padding: nnz * sizeof(value) may be any number of bytes.  cgamd_solver_reload_matrix takes nSystems * nnz new values.
+ * set_rhs, iterate, get_x, history, iterations_done, solve, vector, ld, spmv (y_r = A_r x_r; fused_dot: partials of x_r . y_r),
+ * dot_partials and destroy behave as on any other handle.  The handle always runs a launched loop (cgamd_solver_loop_launches() >= 2:
+ * no resident, chip-wide or two-launch loop), keeps the RHS-major layout (cgamd_solver_layout() == 0) and uses no index, value or
+ * joint codes (the three accessors return 0); its SpMV is family 6 of cgamd_last_spmv_form (csrc/batched.hip).
+ * Not served: cgamd_solver_iterate_tol and cgamd_solver_spmm_rowmajor return CGAMD_ERR_STATE; so do the five
+ * cgamd_solver_set_preconditioner* entries -- an M shared by all right-hand sides has no meaning for different systems -- except
+ * cgamd_solver_set_preconditioner(s, NULL, 0), which returns CGAMD_OK and changes nothing.  A refused call leaves the handle as it was.
+ * Byte models: every value array is counted once and the indices once, cgamd_solver_spmv_bytes = cgamd_solver_spmv_moved_bytes =
+ * nnz * (nSystems * sizeof(value) + 4) + 4 * (size + 1) + 2 * size * sizeof(value) * nSystems; the iter_* entries take the same
+ * matrix term. */
+int cgamd_solver_create_batched(cgamd_ctx *ctx, int dtype, int size, long long nnz, const void *aValues,
+                                const int *aPointers, const int *aCols, int nSystems, int flags, cgamd_solver **out);
+int cgamd_solver_systems(cgamd_solver *s);   /* nSystems of a batched handle, 0 for every other handle, negative: error */
 int cgamd_solver_destroy(cgamd_solver *s);
 /* new values / pattern of the SAME size (size, nnz, nRHS, dtype) into a handle that owns its matrix (created from host
  * arrays): keeps allocations, stream and -- when the row pointers are unchanged -- the plan and the captured graphs.
@@ -232,7 +252,8 @@ int cgamd_solver_spmv(cgamd_solver *s, const void *x, void *y, int fused_dot);
 /* Development entries (tests of the SpMV forms; not part of the interface).
  * cgamd_last_spmv_form: what the CALLING THREAD's most recent SpMV launch (cgamd_solver_spmv, cgamd_spmv, an iteration's SpMV) really
  * launched, recorded where the kernel is launched.  Writes min(n_out, 10) ints and returns that count (negative: error):
- * [0] family: 0 generic stream, 1 row-block, 2 value-coded (vc), 3 value-coded pipelined (vcp), 4 chunked, 5 grouped SpMM, -1 none yet;
+ * [0] family: 0 generic stream, 1 row-block, 2 value-coded (vc), 3 value-coded pipelined (vcp), 4 chunked, 5 grouped SpMM, 6 batched (a matrix per right-hand side:
+ * [2] batch length of the row walk, [7] 1 = the any-CSR form that reads the matrix per row), -1 none yet;
  * [1] 16-byte loads (VEC); [2] batch length of the row walk / lanes per row (chunked) / right-hand sides per register group (SpMM);
  * [3] index encoding: 0 aCols, 8, 16 bits; [4] value encoding: 0 aValues, 1 code stream of its own, 2 joint (offset, value) codes;
  * [5] non-temporal matrix loads; [6] fused d.q; [7] wide (one work-group per row block AND right-hand side); [8] grid.x;
