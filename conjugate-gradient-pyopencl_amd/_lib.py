@@ -85,6 +85,9 @@ def load():
         "cgamd_solver_set_preconditioner_tridiag_strided": (ci, [vp, ci, vp, vp, vp, ci]),
         "cgamd_solver_set_preconditioner_line": (ci, [vp, ci]),
         "cgamd_solver_set_preconditioner_jacobi": (ci, [vp]),
+        "cgamd_solver_set_preconditioner_batched": (ci, [vp, vp, ci]),
+        "cgamd_solver_set_preconditioner_batched_jacobi": (ci, [vp]),
+        "cgamd_solver_set_preconditioner_batched_line": (ci, [vp, ci]),
         "cgamd_solver_preconditioner_source": (ci, [vp]),
         "cgamd_solver_iterate": (ci, [vp, ci]),
         "cgamd_solver_iterate_timed": (ci, [vp, ci, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),

@@ -207,6 +207,42 @@ def load_and_build_kernels(ctx, n_rhs):
 
 
 # ---- persistent solver ------------------------------------------------------------------------
+def _set_preconditioner_batched(self, m):
+    """one M per system on a batched handle; the length of a host array is checked before the library is asked"""
+    if m is None:
+        check(self._lib.cgamd_solver_set_preconditioner_batched(self.handle, None, 0))
+        return
+    if isinstance(m, str) and m == "jacobi":
+        check(self._lib.cgamd_solver_set_preconditioner_batched_jacobi(self.handle))
+        return
+    if isinstance(m, tuple) and len(m) == 2 and isinstance(m[0], str) and m[0] == "line":
+        check(self._lib.cgamd_solver_set_preconditioner_batched_line(self.handle, int(m[1])))
+        return
+    if isinstance(m, (list, tuple)) and len(m) == self.n_rhs and all(hasattr(a, "diagonal") and hasattr(a, "nnz") for a in m):
+        if any(a.shape != (self.size, self.size) or a.nnz > self.size for a in m):
+            raise ValueError('a list of matrices on a batched handle gives their diagonals: n_rhs matrices of size x size with '
+                             'nnz <= size each; the lines of the systems\' own matrices are ("line", stride)')
+        m = np.stack([np.asarray(a.diagonal()) for a in m])
+    if isinstance(m, np.ndarray) or (isinstance(m, (list, tuple)) and not isinstance(m, str)):
+        try:
+            flat = np.asarray(m).reshape(-1)
+        except (TypeError, ValueError):
+            flat = None
+        if flat is None or flat.dtype == object or flat.size != self.n_rhs * self.size:
+            raise ValueError(f"a batched handle of {self.n_rhs} systems takes a preconditioner of {self.n_rhs} * {self.size} = "
+                             f"{self.n_rhs * self.size} diagonal entries (system r at [r * size:(r + 1) * size]), or \"jacobi\", "
+                             f'or ("line", stride)')
+        m = np.ascontiguousarray(flat, dtype=self.dtype)
+        check(self._lib.cgamd_solver_set_preconditioner_batched(self.handle, ptr(m), 0))
+        return
+    if isinstance(m, int) or hasattr(m, "data_ptr") or hasattr(m, "ptr"):      # a device buffer of n_rhs * size values
+        check(self._lib.cgamd_solver_set_preconditioner_batched(self.handle, ptr(m), 1))
+        return
+    raise ValueError('a batched handle takes one preconditioner per system: None, "jacobi", ("line", stride), n_rhs * size '
+                     'diagonal entries (host array or device buffer) or a list of n_rhs diagonal matrices; for the tridiagonal '
+                     'part of every system use ("line", stride)')
+
+
 class Solver:
     """Matrix-resident CG handle: the reference re-uploads the matrix and re-JITs
     its kernels on every call (clcg.c:142-214, cl.py:45-46,73-84); here only b goes up and x comes down."""
@@ -286,7 +322,15 @@ class Solver:
           fastest: s = nx for y-lines, nx * ny for z-lines).  It is factored once on the host without pivoting (a zero pivot
           raises CgAmdError) and solved on the device, by line sweeps (s = 1) or one thread per line (s > 1).  Such handles
           run a launched loop only (no resident loop, no device-side stop).
-        Any other M raises ValueError.  Takes effect at the next set_rhs; history() keeps returning r.r."""
+        Any other M raises ValueError.  Takes effect at the next set_rhs; history() keeps returning r.r.
+
+        A batched handle takes one M per system (cgamd_solver_set_preconditioner_batched*): None, "jacobi" (1 / diag(A_r)),
+        ("line", stride) (the lines of every A_r, one segment plan for all), a host array of n_rhs * size entries (1-D, or
+        (n_rhs, size): row r multiplies the residual of system r), a device buffer of that many, or a list of n_rhs scipy matrices
+        with nnz <= size each (their diagonals)."""
+        if self.batched:
+            _set_preconditioner_batched(self, m)
+            return
         if m is None:
             check(self._lib.cgamd_solver_set_preconditioner(self.handle, None, 0))
             return
@@ -547,7 +591,7 @@ def _shared_pattern(P):
     return indptr, indices, np.concatenate([np.asarray(A.data).ravel() for A in P])
 
 
-def solve_subdomains(ctx, P0, residuals, n_iterations, dtype=np.csingle, solver=None):
+def solve_subdomains(ctx, P0, residuals, n_iterations, dtype=np.csingle, solver=None, preconditioner=None):
     """The batched sub-domain solve of the reference's Additive-Schwarz preconditioner `as_prec`.
 
     * UseCG in {2, 3} (p_h-PY_C-CL.py:1918-1937, 1938-1953): all n_my sub-domains share ONE matrix P[0] -- P0: scipy CSR (or
@@ -560,9 +604,15 @@ def solve_subdomains(ctx, P0, residuals, n_iterations, dtype=np.csingle, solver=
     residuals: list of arrays.  Pass `solver` (a Solver built for P0 with n_rhs = len(residuals); for a list of matrices a batched
     one, whose values are then reloaded from the list) to keep the allocations and the pattern resident across the outer GMRES
     iterations -- the reference re-uploads everything on every call (clcg.c:202-211).
+    preconditioner (a list of matrices only): one M per sub-domain, as Solver.set_preconditioner takes it on a batched handle --
+    "jacobi", ("line", stride), n_my * size diagonal entries or a list of diagonal matrices.  It is set before the solve and removed
+    after it, also on the caller's `solver`.  ValueError for a shared matrix or a solver that is not batched.
     Returns a list of complex arrays shaped like the inputs (`x[p*size:(p+1)*size].astype(complex)`)."""
     n_my = len(residuals)
     batched = isinstance(P0, (list, tuple)) and len(P0) > 0 and hasattr(P0[0], "indptr")
+    if preconditioner is not None and (not batched or (solver is not None and not getattr(solver, "batched", False))):
+        raise ValueError("solve_subdomains: a preconditioner per sub-domain needs a list of sub-domain matrices and a batched Solver "
+                         "(one matrix shared by all residuals: Solver.pcg, or Solver.set_preconditioner on a handle of your own)")
     if batched:
         if len(P0) != n_my:
             raise ValueError(f"{len(P0)} sub-domain matrices for {n_my} residuals")
@@ -583,12 +633,16 @@ def solve_subdomains(ctx, P0, residuals, n_iterations, dtype=np.csingle, solver=
     elif batched:
         solver.reload_matrix(np.asarray(data, dtype=dtype), indptr, indices)
     try:
+        if preconditioner is not None:
+            solver.set_preconditioner(preconditioner)
         solver.set_rhs(b_values, None)
         solver.iterate(n_iterations)
         x = solver.x()
     finally:
         if own:
             solver.close()
+        elif preconditioner is not None:
+            solver.set_preconditioner(None)
     return [x[p * size:(p + 1) * size].astype(complex).reshape(np.shape(residuals[p])) for p in range(n_my)]
 
 

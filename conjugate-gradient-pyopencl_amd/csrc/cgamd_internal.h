@@ -356,16 +356,21 @@ struct P2pExchange {
     const void *my_halo = nullptr;    // halo area of MY mailbox (entry h = column n_local + h)
 };
 int p2p_push_chunks(const P2pExchange &e);
-// diagonally preconditioned CG (helmFE_var.py:546-586 with a diagonal M): see vector.hip
+// diagonally preconditioned CG (helmFE_var.py:546-586 with a diagonal M): see vector.hip.  m_pitch: values between the diagonals of
+// consecutive right-hand sides (a batched handle: m_r belongs to system r), 0 = one m shared by all
 int launch_pcg_axpy2_dot2(int dtype, bool init, int n, const void *d, void *x, const void *q, void *r, const void *m,
-                          long long ld, const void *alpha, int nrhs, void *part_rz, void *part_rr, int grid, hipStream_t st);
+                          long long ld, const void *alpha, int nrhs, void *part_rz, void *part_rr, int grid, hipStream_t st,
+                          long long m_pitch = 0);
 int launch_pcg_aypx_beta(int dtype, int n, const void *r, void *p, const void *m, long long ld, const void *part_rz,
-                         const void *part_rr, int P, int nrhs, const CgScalars &sc, void *rho2, void *xs, hipStream_t st);
+                         const void *part_rr, int P, int nrhs, const CgScalars &sc, void *rho2, void *xs, hipStream_t st,
+                         long long m_pitch = 0);
 int launch_pcg_p_update(int dtype, int n, const void *r, void *p, const void *m, long long ld, const void *beta, int nrhs, hipStream_t st);
 int launch_pcg_delta0(int dtype, const void *part_rz, const void *part_rr, int P, int nrhs, const CgScalars &sc, void *rho2, hipStream_t st);
 // tridiagonal M (precond.hip): the factors of cgamd_solver_set_preconditioner_tridiag and the chunk plan, device arrays
 struct TriLaunch {
     const void *nl = nullptr, *ne = nullptr, *w = nullptr;   // -l_i, -w_i c_i, w_i = 1/u_i: n values each
+    long long fpitch = 0;                                    // a batched handle: right-hand side r reads the factors of system r at r * fpitch
+                                                             // values into each array; 0 = one M shared by all right-hand sides
     const int *cstart = nullptr;                             // nchunks + 1 chunk boundaries (rows)
     int nchunks = 0, grid = 0;                               // grid = work-groups = r.z / r.r partials per RHS
     bool longform = false;                                   // a segment is longer than a chunk: maps, carry, apply (3 launches)
@@ -402,6 +407,18 @@ int launch_line_longest(int n, int stride, const unsigned char *flags, int cap, 
 // failing row: kind 0 non-finite entry, 1 zero or non-finite pivot, 2 pivot too small
 int launch_line_factor(int dtype, int n_user, int stride, const unsigned char *pre, const void *lower, const void *diag,
                        const void *upper, void *nl, void *ne, void *w, unsigned long long *err, hipStream_t st);
+// the same passes over nsys matrices on one pattern (the values of system r at vals + r * nnz; every per-row array of system r at
+// r * pitch values): one launch each whatever nsys.  The flags are AND-ed over the systems; the error words name the smallest
+// system, then the smallest row in it: Jacobi (system << 32) | row, factor (system << kBatchedErrSystemShift) | (row << 2) | kind
+constexpr int kBatchedErrSystemShift = 34;
+int launch_batched_line_extract(int dtype, int n_user, int stride, int nsys, long long nnz, const void *vals, const int *ptr, const int *cols,
+                                void *lower, void *diag, void *upper, long long pitch, hipStream_t st);
+int launch_batched_jacobi_extract(int dtype, int n_user, int nsys, long long nnz, const void *vals, const int *ptr, const int *cols, void *m,
+                                  long long pitch, unsigned long long *err, hipStream_t st);
+int launch_batched_line_flags(int dtype, int n, int stride, int nsys, const void *x, const void *y, long long pitch, unsigned char *flags,
+                              hipStream_t st);
+int launch_batched_line_factor(int dtype, int n_user, int stride, int nsys, const unsigned char *pre, const void *lower, const void *diag,
+                               const void *upper, void *nl, void *ne, void *w, long long pitch, unsigned long long *err, hipStream_t st);
 // count: line_count_ints(n) ints <- the flagged rows before every 256-row block, the total in its last entry
 int line_count_ints(int n);
 int launch_line_count(int n, const unsigned char *flags, int *count, hipStream_t st);
@@ -409,7 +426,8 @@ int launch_line_count(int n, const unsigned char *flags, int *count, hipStream_t
 int launch_line_emit(int n, int stride, bool pairs, const unsigned char *flags, const int *block_off, int *out, hipStream_t st);
 // ---- preconditioner setup shared by the single-GPU and the row-partitioned handle (precond_setup.cpp) ----
 // a factored tridiagonal M on the device: coef = 3 x pitch values (-l, -w c, w); plan = count + 1 chunk boundaries (stride 1) or
-// count (first row, length) pairs (stride > 1).  Both allocations belong to the caller.
+// count (first row, length) pairs (stride > 1).  Both allocations belong to the caller.  nsys > 0 (tri_build_from_matrix_batched): one
+// M per system on ONE plan, coef = 3 arrays of nsys x pitch values.
 struct TriBuilt {
     void *coef = nullptr;
     size_t pitch = 0;
@@ -417,6 +435,7 @@ struct TriBuilt {
     int stride = 1, count = 0;
     bool longform = false;
     int source = 0;         // 2 = factored on the device, 3 = extracted on the device and factored by the host route
+    int nsys = 0;
 };
 void tri_built_free(TriBuilt *b);
 // from M's three arrays (nu values each, host or device), factored and planned on the host; n >= nu: rows with the padding
@@ -425,6 +444,13 @@ int tri_build_host(hipStream_t st, int dt, int nu, int n, const std::string &who
 // from the CSR entries at column - row in {-stride, 0, +stride} with column < col_limit, on the device; route: Tuning::dev_line_host_route
 int tri_build_from_matrix(hipStream_t st, int dt, int nu, int n, int route, const std::string &who, int stride, const void *vals,
                           const int *ptr, const int *cols, int col_limit, TriBuilt *out);
+// the lines of nsys matrices on one pattern, every system factored on the device, ONE segment plan (a row starts a segment when it
+// does in every system); errors name the system and the row.  A constant number of launches and synchronisations whatever nsys
+int tri_build_from_matrix_batched(hipStream_t st, int dt, int nu, int n, int nsys, long long nnz, const std::string &who, int stride,
+                                  const void *vals, const int *ptr, const int *cols, TriBuilt *out);
+// m_r[i] = 1 / A_r[i][i] at m + r * pitch (m: nsys * pitch device values of the caller)
+int jacobi_build_from_matrix_batched(hipStream_t st, int dt, int nu, int nsys, long long nnz, const std::string &who, const void *vals,
+                                     const int *ptr, const int *cols, void *m, long long pitch);
 // m[i] = 1 / A[i][i] (m: nu device values of the caller); CGAMD_ERR_INVALID names the smallest bad row
 int jacobi_build_from_matrix(hipStream_t st, int dt, int nu, const std::string &who, const void *vals, const int *ptr, const int *cols,
                              void *m);

@@ -84,10 +84,12 @@ CG_DEV void st_rows(T *p, int row0, int lo, int hi, const T (&v)[R]) {
     }
 }
 
-// grid = (G, nRHS); work-group g takes chunks g, g + G, ... and writes one partial per dot product: P = G partials per RHS
+// grid = (G, nRHS); work-group g takes chunks g, g + G, ... and writes one partial per dot product: P = G partials per RHS.
+// fpitch: values between the factors of consecutive right-hand sides (a batched handle: M_r of system r for right-hand side r); 0 =
+// one M shared by all
 template <typename T, bool VEC, int MODE, bool UPD>
 __global__ __launch_bounds__(kBlock) void pcg_tri_kernel(const int *__restrict__ cstart, int nchunks, const T *__restrict__ nl,
-                                                         const T *__restrict__ ne, const T *__restrict__ w, const T *q, T *rv, T *z,
+                                                         const T *__restrict__ ne, const T *__restrict__ w, long long fpitch, const T *q, T *rv, T *z,
                                                          long long ld, const T *__restrict__ alpha, typename VT<T>::acc *__restrict__ part_rz,
                                                          typename VT<T>::acc *__restrict__ part_rr, T *__restrict__ maps) {
     using A = typename VT<T>::acc;
@@ -97,6 +99,7 @@ __global__ __launch_bounds__(kBlock) void pcg_tri_kernel(const int *__restrict__
     const int rhs = blockIdx.y, lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
     const long long off = (long long)rhs * ld;
     rv += off; z += off; q += off;
+    nl += rhs * fpitch; ne += rhs * fpitch; w += rhs * fpitch;
     const T one = vone<T>(), zero = vzero<T>();
     const T al = UPD ? alpha[rhs] : zero;
     A arz = vzero<A>(), arr = vzero<A>();
@@ -239,7 +242,7 @@ static int tri_impl(const TriLaunch &t, bool update, const void *q, void *r, voi
     const dim3 g(t.grid, nrhs), blk(kBlock);
     const T *nl = (const T *)t.nl, *ne = (const T *)t.ne, *w = (const T *)t.w;
     T *maps = (T *)t.maps;
-#define CG_TRI(V, M, U) hipLaunchKernelGGL((pcg_tri_kernel<T, V, M, U>), g, blk, 0, st, t.cstart, t.nchunks, nl, ne, w, (const T *)q, (T *)r, \
+#define CG_TRI(V, M, U) hipLaunchKernelGGL((pcg_tri_kernel<T, V, M, U>), g, blk, 0, st, t.cstart, t.nchunks, nl, ne, w, t.fpitch, (const T *)q, (T *)r, \
                                            (T *)z, ld, (const T *)alpha, (A *)part_rz, (A *)part_rr, maps)
     if (!t.longform) {
         if (update) { if (vec) CG_TRI(true, 0, true); else CG_TRI(false, 0, true); }

@@ -17,6 +17,8 @@
 //             thread (the host-route decision).
 // Everything is stream-ordered on the caller's stream; the callers read back single words only (longest pre-segment, error word,
 // segment count) -- and, at stride 1, the start list the host chunk planner packs.
+#include <algorithm>
+
 #include "cgamd_internal.h"
 #include "device_types.h"
 #include "launch_util.h"
@@ -86,15 +88,14 @@ __global__ __launch_bounds__(kBlock) void line_flags_kernel(int n, int stride, c
 
 constexpr int kFactorRows = 4;      // rows of a walk whose loads are issued together
 
+// the walk of one pre-segment from its first row: tri_factor's recurrence, the factors stored rounded once.  The first bad row goes
+// into *err by atomicMin as sys_bits | (row << 2) | kind (sys_bits: 0, or the system in the bits above the row for the batched form)
 template <typename T>
-__global__ __launch_bounds__(kBlock) void line_factor_kernel(int nu, int stride, const unsigned char *__restrict__ pre,
-                                                             const T *__restrict__ lower, const T *__restrict__ diag,
-                                                             const T *__restrict__ upper, T *__restrict__ nl, T *__restrict__ ne,
-                                                             T *__restrict__ w, unsigned long long *__restrict__ err) {
+CG_DEV void line_factor_walk(int nu, int stride, int first, const unsigned char *__restrict__ pre, const T *__restrict__ lower,
+                             const T *__restrict__ diag, const T *__restrict__ upper, T *__restrict__ nl, T *__restrict__ ne,
+                             T *__restrict__ w, unsigned long long *__restrict__ err, unsigned long long sys_bits) {
     using A = typename VT<T>::acc;
     constexpr int U = kFactorRows;
-    const int first = blockIdx.x * kBlock + threadIdx.x;
-    if (first >= nu || !pre[first]) return;
     const long long st = stride;
     const A zero = vzero<A>(), one = acc_one<A>();
     A u_prev = one, c_prev = zero;
@@ -118,18 +119,18 @@ __global__ __launch_bounds__(kBlock) void line_factor_kernel(int nu, int stride,
             // (a pre-segment's first row has a = 0 and c_prev = 0 exactly, or heads its chain: l = 0 and u = b, as the serial loop gets)
             const A av = i == first ? zero : to_acc(a[j]), bv = to_acc(b[j]), cv = to_acc(c[j]);
             if (!is_finite(av) || !is_finite(bv) || !is_finite(cv)) {
-                atomicMin(err, ((unsigned long long)i << 2) | 0ull);
+                atomicMin(err, sys_bits | ((unsigned long long)i << 2) | 0ull);
                 return;
             }
             const A l = i == first ? zero : acc_div(av, u_prev);
             const A u = vsub(bv, vmul(l, c_prev));
             if (!is_finite(l) || !is_finite(u) || is_zero(u)) {
-                atomicMin(err, ((unsigned long long)i << 2) | 1ull);
+                atomicMin(err, sys_bits | ((unsigned long long)i << 2) | 1ull);
                 return;
             }
             const A wi = acc_div(one, u);
             if (!is_finite(wi)) {
-                atomicMin(err, ((unsigned long long)i << 2) | 2ull);
+                atomicMin(err, sys_bits | ((unsigned long long)i << 2) | 2ull);
                 return;
             }
             nl[i] = from_acc<T>(vneg(l));
@@ -139,6 +140,16 @@ __global__ __launch_bounds__(kBlock) void line_factor_kernel(int nu, int stride,
             c_prev = cv;
         }
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void line_factor_kernel(int nu, int stride, const unsigned char *__restrict__ pre,
+                                                             const T *__restrict__ lower, const T *__restrict__ diag,
+                                                             const T *__restrict__ upper, T *__restrict__ nl, T *__restrict__ ne,
+                                                             T *__restrict__ w, unsigned long long *__restrict__ err) {
+    const int first = blockIdx.x * kBlock + threadIdx.x;
+    if (first >= nu || !pre[first]) return;
+    line_factor_walk<T>(nu, stride, first, pre, lower, diag, upper, nl, ne, w, err, 0ull);
 }
 
 // rows from a flagged row to its chain's next flagged row (or the chain's end); gives up once the count reaches cap (the result is
@@ -222,6 +233,110 @@ __global__ __launch_bounds__(kBlock) void line_emit_kernel(int n, int stride, co
     }
 }
 
+// ---- the same passes for nsys matrices on one pattern (cgamd_solver_set_preconditioner_batched_jacobi / _batched_line): the values of
+// system r at vals + r * nnz, the outputs of system r at r * pitch.  grid = (row blocks, gy): a thread takes one row (one pre-segment)
+// of the systems blockIdx.y, blockIdx.y + gy, ...; the launch count does not depend on nsys.
+
+// the entries of row i at column i + off, found in ONE pass over the row's columns: the position of the first and how many there are
+struct RowHits {
+    int first[3], count[3];      // off = -stride, 0, +stride
+};
+CG_DEV RowHits row_hits(const int *__restrict__ ptr, const int *__restrict__ cols, int i, int stride, bool diag_only) {
+    RowHits h;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { h.first[k] = -1; h.count[k] = 0; }
+    const int end = ptr[i + 1];
+    for (int j = ptr[i]; j < end; ++j) {
+        const long long off = (long long)cols[j] - i;
+        const int k = off == 0 ? 1 : diag_only ? -1 : off == -(long long)stride ? 0 : off == stride ? 2 : -1;
+        if (k < 0) continue;
+        if (h.count[k]++ == 0) h.first[k] = j;
+    }
+    return h;
+}
+// their sum in one system, in stored order from +0 in the accumulator type (as line_extract_kernel adds them up); the row is walked
+// again only where a column is stored more than once
+template <typename T>
+CG_DEV typename VT<T>::acc hit_sum(const T *__restrict__ vr, const int *__restrict__ cols, int i, long long want, int first, int count,
+                                   int end) {
+    using A = typename VT<T>::acc;
+    A a = vzero<A>();
+    if (count >= 1) a = vadd(a, to_acc(vr[first]));
+    for (int j = first + 1; count > 1 && j < end; ++j)
+        if ((long long)cols[j] - i == want) a = vadd(a, to_acc(vr[j]));
+    return a;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void batched_line_extract_kernel(int nu, int stride, int nsys, long long nnz, const T *__restrict__ vals,
+                                                                      const int *__restrict__ ptr, const int *__restrict__ cols,
+                                                                      T *__restrict__ lower, T *__restrict__ diag, T *__restrict__ upper,
+                                                                      long long pitch) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nu) return;
+    const RowHits h = row_hits(ptr, cols, i, stride, false);
+    const int end = ptr[i + 1];
+    for (int r = blockIdx.y; r < nsys; r += gridDim.y) {
+        const T *vr = vals + (long long)r * nnz;
+        const long long o = (long long)r * pitch + i;
+        lower[o] = from_acc<T>(hit_sum<T>(vr, cols, i, -(long long)stride, h.first[0], h.count[0], end));
+        diag[o] = from_acc<T>(hit_sum<T>(vr, cols, i, 0, h.first[1], h.count[1], end));
+        upper[o] = from_acc<T>(hit_sum<T>(vr, cols, i, stride, h.first[2], h.count[2], end));
+    }
+}
+
+// m_r[i] = 1 / A_r[i][i]; err = (system << 32) | row of the smallest system, then the smallest row in it, with a bad diagonal
+template <typename T>
+__global__ __launch_bounds__(kBlock) void batched_jacobi_extract_kernel(int nu, int nsys, long long nnz, const T *__restrict__ vals,
+                                                                        const int *__restrict__ ptr, const int *__restrict__ cols,
+                                                                        T *__restrict__ m, long long pitch,
+                                                                        unsigned long long *__restrict__ err) {
+    using A = typename VT<T>::acc;
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nu) return;
+    const RowHits h = row_hits(ptr, cols, i, 0, true);
+    const int end = ptr[i + 1];
+    for (int r = blockIdx.y; r < nsys; r += gridDim.y) {
+        const A b = hit_sum<T>(vals + (long long)r * nnz, cols, i, 0, h.first[1], h.count[1], end);
+        if (!is_finite(b) || is_zero(b)) {
+            atomicMin(err, ((unsigned long long)r << 32) | (unsigned long long)i);
+            continue;
+        }
+        m[(long long)r * pitch + i] = from_acc<T>(acc_div(acc_one<A>(), b));
+    }
+}
+
+// the rule of line_flags_kernel AND-ed over the systems: row i starts a (pre-)segment when it heads its chain or x_r[i] and
+// y_r[i - stride] are exactly zero in EVERY system
+template <typename T>
+__global__ __launch_bounds__(kBlock) void batched_line_flags_kernel(int n, int stride, int nsys, const T *__restrict__ x,
+                                                                    const T *__restrict__ y, long long pitch,
+                                                                    unsigned char *__restrict__ flags) {
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    bool cut = true;
+    if (i >= stride)
+        for (int r = 0; r < nsys && cut; ++r) cut = is_zero(x[(long long)r * pitch + i]) && is_zero(y[(long long)r * pitch + i - stride]);
+    flags[i] = cut ? 1 : 0;
+}
+
+// one thread per (pre-segment, system); the error word carries the system above the row: its minimum is the smallest system, then the
+// smallest row in it.  A system whose own couplings vanish inside a shared pre-segment gets l = 0 and u = b there, as on its own
+template <typename T>
+__global__ __launch_bounds__(kBlock) void batched_line_factor_kernel(int nu, int stride, int nsys, const unsigned char *__restrict__ pre,
+                                                                     const T *__restrict__ lower, const T *__restrict__ diag,
+                                                                     const T *__restrict__ upper, T *__restrict__ nl, T *__restrict__ ne,
+                                                                     T *__restrict__ w, long long pitch,
+                                                                     unsigned long long *__restrict__ err) {
+    const int first = blockIdx.x * kBlock + threadIdx.x;
+    if (first >= nu || !pre[first]) return;
+    for (int r = blockIdx.y; r < nsys; r += gridDim.y) {
+        const long long o = (long long)r * pitch;
+        line_factor_walk<T>(nu, stride, first, pre, lower + o, diag + o, upper + o, nl + o, ne + o, w + o, err,
+                            (unsigned long long)r << kBatchedErrSystemShift);
+    }
+}
+
 static int row_blocks(int n) { return (n + kBlock - 1) / kBlock; }
 
 template <typename T>
@@ -284,6 +399,60 @@ int launch_line_emit(int n, int stride, bool pairs, const unsigned char *flags, 
     if (pairs) hipLaunchKernelGGL((line_emit_kernel<true>), dim3(row_blocks(n)), dim3(kBlock), 0, st, n, stride, flags, block_off, out);
     else hipLaunchKernelGGL((line_emit_kernel<false>), dim3(row_blocks(n)), dim3(kBlock), 0, st, n, stride, flags, block_off, out);
     return check_launch("line_emit");
+}
+
+// work-groups along y for nsys systems: all of them in parallel while that leaves the launch below ~1024 work-groups
+static dim3 batched_grid(int rows, int nsys) {
+    const int rb = row_blocks(rows);
+    return dim3(rb, std::max(1, std::min(std::min(nsys, 65535), (1024 + rb - 1) / rb)));
+}
+
+template <typename T>
+static int batched_extract_impl(int nu, int stride, int nsys, long long nnz, const void *vals, const int *ptr, const int *cols, void *lower,
+                                void *diag, void *upper, long long pitch, hipStream_t st) {
+    hipLaunchKernelGGL((batched_line_extract_kernel<T>), batched_grid(nu, nsys), dim3(kBlock), 0, st, nu, stride, nsys, nnz, (const T *)vals,
+                       ptr, cols, (T *)lower, (T *)diag, (T *)upper, pitch);
+    return check_launch("batched_line_extract");
+}
+int launch_batched_line_extract(int dtype, int n_user, int stride, int nsys, long long nnz, const void *vals, const int *ptr, const int *cols,
+                                void *lower, void *diag, void *upper, long long pitch, hipStream_t st) {
+    CG_DISPATCH(dtype, batched_extract_impl, n_user, stride, nsys, nnz, vals, ptr, cols, lower, diag, upper, pitch, st);
+}
+
+template <typename T>
+static int batched_jacobi_impl(int nu, int nsys, long long nnz, const void *vals, const int *ptr, const int *cols, void *m, long long pitch,
+                               unsigned long long *err, hipStream_t st) {
+    hipLaunchKernelGGL((batched_jacobi_extract_kernel<T>), batched_grid(nu, nsys), dim3(kBlock), 0, st, nu, nsys, nnz, (const T *)vals, ptr,
+                       cols, (T *)m, pitch, err);
+    return check_launch("batched_jacobi_extract");
+}
+int launch_batched_jacobi_extract(int dtype, int n_user, int nsys, long long nnz, const void *vals, const int *ptr, const int *cols, void *m,
+                                  long long pitch, unsigned long long *err, hipStream_t st) {
+    CG_DISPATCH(dtype, batched_jacobi_impl, n_user, nsys, nnz, vals, ptr, cols, m, pitch, err, st);
+}
+
+template <typename T>
+static int batched_flags_impl(int n, int stride, int nsys, const void *x, const void *y, long long pitch, unsigned char *flags,
+                              hipStream_t st) {
+    hipLaunchKernelGGL((batched_line_flags_kernel<T>), dim3(row_blocks(n)), dim3(kBlock), 0, st, n, stride, nsys, (const T *)x, (const T *)y,
+                       pitch, flags);
+    return check_launch("batched_line_flags");
+}
+int launch_batched_line_flags(int dtype, int n, int stride, int nsys, const void *x, const void *y, long long pitch, unsigned char *flags,
+                              hipStream_t st) {
+    CG_DISPATCH(dtype, batched_flags_impl, n, stride, nsys, x, y, pitch, flags, st);
+}
+
+template <typename T>
+static int batched_factor_impl(int nu, int stride, int nsys, const unsigned char *pre, const void *lower, const void *diag, const void *upper,
+                               void *nl, void *ne, void *w, long long pitch, unsigned long long *err, hipStream_t st) {
+    hipLaunchKernelGGL((batched_line_factor_kernel<T>), batched_grid(nu, nsys), dim3(kBlock), 0, st, nu, stride, nsys, pre, (const T *)lower,
+                       (const T *)diag, (const T *)upper, (T *)nl, (T *)ne, (T *)w, pitch, err);
+    return check_launch("batched_line_factor");
+}
+int launch_batched_line_factor(int dtype, int n_user, int stride, int nsys, const unsigned char *pre, const void *lower, const void *diag,
+                               const void *upper, void *nl, void *ne, void *w, long long pitch, unsigned long long *err, hipStream_t st) {
+    CG_DISPATCH(dtype, batched_factor_impl, n_user, stride, nsys, pre, lower, diag, upper, nl, ne, w, pitch, err, st);
 }
 
 }  // namespace cgamd

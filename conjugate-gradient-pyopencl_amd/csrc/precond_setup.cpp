@@ -209,6 +209,39 @@ struct DevScratch {      // device allocations of one call, freed on return unle
 // (profiles/line_setup/long_segments.log) has not been measured yet.
 constexpr int kLineHostRouteRows = 65536;
 
+// The plan from the final segment flags: the flagged rows before every 256-row block, their number, then the ordered list -- with
+// lengths for pcg_tri_strided_kernel (stride > 1), or through the host chunk planner (stride 1).  *plan is taken from tmp.
+static int tri_plan_from_flags(hipStream_t st, int dt, int n, int stride, const unsigned char *flags, int *count, DevScratch &tmp,
+                               int **plan_out, int *nplan_out, bool *longform_out) {
+    int rc;
+    if ((rc = launch_line_count(n, flags, count, st))) return rc;
+    int nsegs = 0;
+    CG_HIP(hipMemcpyAsync(&nsegs, count + line_count_ints(n) - 1, 4, hipMemcpyDeviceToHost, st));
+    CG_HIP(hipStreamSynchronize(st));
+    int *plan = nullptr;
+    int nplan = nsegs;
+    bool longform = false;
+    if (stride > 1) {       // the plan of pcg_tri_strided_kernel: (first row, length) ordered by first row
+        if ((rc = tmp.get((void **)&plan, (size_t)nsegs * 8, "tridiagonal segment plan"))) return rc;
+        if ((rc = launch_line_emit(n, stride, true, flags, count, plan, st))) return rc;
+    } else {                // the segment starts go to the host chunk planner
+        int *starts_dev = nullptr;
+        if ((rc = tmp.get((void **)&starts_dev, (size_t)nsegs * 4, "tridiagonal segment starts"))) return rc;
+        if ((rc = launch_line_emit(n, 1, false, flags, count, starts_dev, st))) return rc;
+        std::vector<int> seg((size_t)nsegs + 1), starts;
+        CG_HIP(hipMemcpyAsync(seg.data(), starts_dev, (size_t)nsegs * 4, hipMemcpyDeviceToHost, st));
+        CG_HIP(hipStreamSynchronize(st));
+        seg[(size_t)nsegs] = n;
+        longform = tri_plan_chunks(seg, n, dt, starts);
+        nplan = (int)starts.size() - 1;
+        if ((rc = tmp.get((void **)&plan, starts.size() * 4, "tridiagonal chunk plan"))) return rc;
+        CG_HIP(hipMemcpyAsync(plan, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
+        CG_HIP(hipStreamSynchronize(st));
+    }
+    *plan_out = plan; *nplan_out = nplan; *longform_out = longform;
+    return CGAMD_OK;
+}
+
 // M = the matrix entries at column - row in {-stride, 0, +stride} among the columns below col_limit: extracted, factored and planned
 // on the device.  The temporaries are three n-long value arrays, n flag bytes, one int per 256 rows and three words.
 int tri_build_from_matrix(hipStream_t st, int dt, int nu, int n, int route, const std::string &who, int stride, const void *vals,
@@ -262,32 +295,12 @@ int tri_build_from_matrix(hipStream_t st, int dt, int nu, int n, int route, cons
         default: return fail(CGAMD_ERR_INVALID, who + ": pivot too small in row " + row);
         }
     }
-    // the final segments, from the factors as stored: flags, the flagged rows before every block, their number
+    // the final segments, from the factors as stored
     if ((rc = launch_line_flags(dt, n, stride, nl, ne, flags, st))) return rc;
-    if ((rc = launch_line_count(n, flags, count, st))) return rc;
-    int nsegs = 0;
-    CG_HIP(hipMemcpyAsync(&nsegs, count + line_count_ints(n) - 1, 4, hipMemcpyDeviceToHost, st));
-    CG_HIP(hipStreamSynchronize(st));
     int *plan = nullptr;
-    int nplan = nsegs;
+    int nplan = 0;
     bool longform = false;
-    if (stride > 1) {       // the plan of pcg_tri_strided_kernel: (first row, length) ordered by first row
-        if ((rc = tmp.get((void **)&plan, (size_t)nsegs * 8, "tridiagonal segment plan"))) return rc;
-        if ((rc = launch_line_emit(n, stride, true, flags, count, plan, st))) return rc;
-    } else {                // the segment starts go to the host chunk planner
-        int *starts_dev = nullptr;
-        if ((rc = tmp.get((void **)&starts_dev, (size_t)nsegs * 4, "tridiagonal segment starts"))) return rc;
-        if ((rc = launch_line_emit(n, 1, false, flags, count, starts_dev, st))) return rc;
-        std::vector<int> seg((size_t)nsegs + 1), starts;
-        CG_HIP(hipMemcpyAsync(seg.data(), starts_dev, (size_t)nsegs * 4, hipMemcpyDeviceToHost, st));
-        CG_HIP(hipStreamSynchronize(st));
-        seg[(size_t)nsegs] = n;
-        longform = tri_plan_chunks(seg, n, dt, starts);
-        nplan = (int)starts.size() - 1;
-        if ((rc = tmp.get((void **)&plan, starts.size() * 4, "tridiagonal chunk plan"))) return rc;
-        CG_HIP(hipMemcpyAsync(plan, starts.data(), starts.size() * 4, hipMemcpyHostToDevice, st));
-        CG_HIP(hipStreamSynchronize(st));
-    }
+    if ((rc = tri_plan_from_flags(st, dt, n, stride, flags, count, tmp, &plan, &nplan, &longform))) return rc;
     CG_HIP(hipStreamSynchronize(st));
     tmp.release(coef);
     tmp.release(plan);
@@ -310,6 +323,78 @@ int jacobi_build_from_matrix(hipStream_t st, int dt, int nu, const std::string &
     CG_HIP(hipStreamSynchronize(st));
     if (err_h != ~0ull)
         return fail(CGAMD_ERR_INVALID, who + ": zero, missing or non-finite diagonal in row " + std::to_string(err_h));
+    return CGAMD_OK;
+}
+
+// ---- the same for nsys matrices on one pattern (a batched handle) -----------------------------------------------------------------
+// Every system's lines are extracted and factored by ONE launch each (precond_build.hip, grid.y over the systems); the segment flags
+// are AND-ed over the systems, so one plan serves all of them: a system whose own couplings vanish inside a shared segment has
+// stored zeros there, which restart the sweeps' recurrences arithmetically.  Always on the device: long chains are factored serially.
+static std::string system_row(unsigned long long sys, unsigned long long row) {
+    return "system " + std::to_string(sys) + " row " + std::to_string(row);
+}
+int tri_build_from_matrix_batched(hipStream_t st, int dt, int nu, int n, int nsys, long long nnz, const std::string &who, int stride,
+                                  const void *vals, const int *ptr, const int *cols, TriBuilt *out) {
+    const size_t vs = dtype_size(dt);
+    const int E = (int)(16 / vs);
+    const size_t pitch = ((size_t)n + 2 * E - 1) / (2 * E) * (2 * E);      // per system, as tri_factor lays the factors out
+    const size_t arr = pitch * (size_t)nsys * vs;                           // one array of all systems
+    DevScratch tmp;
+    void *abc = nullptr, *words = nullptr, *coef = nullptr;
+    unsigned char *flags = nullptr;
+    int *count = nullptr;
+    int rc = tmp.get(&abc, 3 * arr, "batched line preconditioner: diagonals");
+    if (!rc) rc = tmp.get(&coef, 3 * arr, "batched tridiagonal factors");
+    if (!rc) rc = tmp.get((void **)&flags, (size_t)n, "batched line preconditioner: flags");
+    if (!rc) rc = tmp.get((void **)&count, (size_t)line_count_ints(n) * 4, "batched line preconditioner: block counts");
+    if (!rc) rc = tmp.get(&words, 16, "batched line preconditioner: words");
+    if (rc) return rc;
+    char *lower = static_cast<char *>(abc), *diag = lower + arr, *upper = diag + arr;
+    char *nl = static_cast<char *>(coef), *ne = nl + arr, *w = ne + arr;
+    unsigned long long *err = static_cast<unsigned long long *>(words);
+    CG_HIP(hipMemsetAsync(abc, 0, 3 * arr, st));       // (the padding rows: no couplings)
+    CG_HIP(hipMemsetAsync(coef, 0, 3 * arr, st));      // (... and 0 in every factor: decoupled, z = 0 there)
+    CG_HIP(hipMemsetAsync(err, 0xff, 8, st));
+    if ((rc = launch_batched_line_extract(dt, nu, stride, nsys, nnz, vals, ptr, cols, lower, diag, upper, (long long)pitch, st))) return rc;
+    if ((rc = launch_batched_line_flags(dt, n, stride, nsys, lower, upper, (long long)pitch, flags, st))) return rc;
+    if ((rc = launch_batched_line_factor(dt, nu, stride, nsys, flags, lower, diag, upper, nl, ne, w, (long long)pitch, err, st))) return rc;
+    unsigned long long err_h = 0;
+    CG_HIP(hipMemcpyAsync(&err_h, err, 8, hipMemcpyDeviceToHost, st));
+    CG_HIP(hipStreamSynchronize(st));
+    if (err_h != ~0ull) {
+        const std::string at = system_row(err_h >> kBatchedErrSystemShift, (err_h & ((1ull << kBatchedErrSystemShift) - 1)) >> 2);
+        switch ((int)(err_h & 3)) {
+        case 0: return fail(CGAMD_ERR_INVALID, who + ": non-finite entry in " + at);
+        case 1: return fail(CGAMD_ERR_INVALID, who + ": zero or non-finite pivot in " + at + " (the factorisation does not pivot)");
+        default: return fail(CGAMD_ERR_INVALID, who + ": pivot too small in " + at);
+        }
+    }
+    if ((rc = launch_batched_line_flags(dt, n, stride, nsys, nl, ne, (long long)pitch, flags, st))) return rc;
+    int *plan = nullptr;
+    int nplan = 0;
+    bool longform = false;
+    if ((rc = tri_plan_from_flags(st, dt, n, stride, flags, count, tmp, &plan, &nplan, &longform))) return rc;
+    CG_HIP(hipStreamSynchronize(st));
+    tmp.release(coef);
+    tmp.release(plan);
+    out->coef = coef; out->pitch = pitch; out->plan = plan; out->stride = stride; out->count = nplan; out->longform = longform;
+    out->source = 2; out->nsys = nsys;
+    return CGAMD_OK;
+}
+
+int jacobi_build_from_matrix_batched(hipStream_t st, int dt, int nu, int nsys, long long nnz, const std::string &who, const void *vals,
+                                     const int *ptr, const int *cols, void *m, long long pitch) {
+    DevScratch tmp;
+    void *err = nullptr;
+    int rc = tmp.get(&err, 8, "Jacobi preconditioner: error word");
+    if (rc) return rc;
+    CG_HIP(hipMemsetAsync(err, 0xff, 8, st));
+    if ((rc = launch_batched_jacobi_extract(dt, nu, nsys, nnz, vals, ptr, cols, m, pitch, static_cast<unsigned long long *>(err), st))) return rc;
+    unsigned long long err_h = 0;
+    CG_HIP(hipMemcpyAsync(&err_h, err, 8, hipMemcpyDeviceToHost, st));
+    CG_HIP(hipStreamSynchronize(st));
+    if (err_h != ~0ull)
+        return fail(CGAMD_ERR_INVALID, who + ": zero, missing or non-finite diagonal in " + system_row(err_h >> 32, err_h & 0xffffffffull));
     return CGAMD_OK;
 }
 

@@ -30,11 +30,13 @@ namespace cgamd {
 // rows per step of a walk: up to 4 vectors of that many values in registers (64 VGPRs in fp64 / complex64 / complex128, 32 in fp32)
 template <typename T> constexpr int tri_strided_rows() { return sizeof(T) == 16 ? 4 : 8; }
 
-// grid = (G, nRHS); thread t of the grid takes segments t, t + G kBlock, ...; P = G partials per RHS and dot product
+// grid = (G, nRHS); thread t of the grid takes segments t, t + G kBlock, ...; P = G partials per RHS and dot product.  fpitch: values
+// between the factors of consecutive right-hand sides (a batched handle), 0 = one M shared by all
 template <typename T, bool UPD>
 __global__ __launch_bounds__(kBlock) void pcg_tri_strided_kernel(const int2 *__restrict__ segs, int nsegs, int stride,
                                                                  const T *__restrict__ nl, const T *__restrict__ ne,
-                                                                 const T *__restrict__ w, const T *q, T *rv, T *z, long long ld,
+                                                                 const T *__restrict__ w, long long fpitch, const T *q, T *rv, T *z,
+                                                                 long long ld,
                                                                  const T *__restrict__ alpha, typename VT<T>::acc *__restrict__ part_rz,
                                                                  typename VT<T>::acc *__restrict__ part_rr) {
     using A = typename VT<T>::acc;
@@ -44,6 +46,7 @@ __global__ __launch_bounds__(kBlock) void pcg_tri_strided_kernel(const int2 *__r
     const long long off = (long long)rhs * ld;
     rv += off; z += off;
     if (UPD) q += off;
+    nl += rhs * fpitch; ne += rhs * fpitch; w += rhs * fpitch;
     const T zero = vzero<T>();
     const T al = UPD ? alpha[rhs] : zero;
     const long long st = stride;
@@ -128,7 +131,7 @@ static int tri_strided_impl(const TriLaunch &t, bool update, const void *q, void
     const dim3 g(t.grid, nrhs), blk(kBlock);
     const int2 *segs = reinterpret_cast<const int2 *>(t.segs);
 #define CG_TRIS(U) hipLaunchKernelGGL((pcg_tri_strided_kernel<T, U>), g, blk, 0, st, segs, t.nsegs, t.stride, (const T *)t.nl, (const T *)t.ne, \
-                                      (const T *)t.w, (const T *)q, (T *)r, (T *)z, ld, (const T *)alpha, (A *)part_rz, (A *)part_rr)
+                                      (const T *)t.w, t.fpitch, (const T *)q, (T *)r, (T *)z, ld, (const T *)alpha, (A *)part_rz, (A *)part_rr)
     if (update) CG_TRIS(true); else CG_TRIS(false);
 #undef CG_TRIS
     return check_launch("pcg_tri_strided");

@@ -32,7 +32,9 @@ struct cgamd_solver {
     int n_user = 0;
     // cgamd_solver_create_batched: nsys systems on one pattern, the values of system r at vals + r * nnz and right-hand side r its
     // own; 0 = every other handle (one matrix for all right-hand sides).  A batched handle has nrhs == nsys, runs the launched loops
-    // only (no resident loop, no row-major layout, no codes, no preconditioner) and launches its SpMV through launch_spmv_batched.
+    // only (no resident loop, no row-major layout, no codes) and launches its SpMV through launch_spmv_batched.  Its preconditioner is
+    // one M per system (cgamd_solver_set_preconditioner_batched*): mdiag holds nsys diagonals at stride n, tri the factors of every
+    // system at tri.fpitch on one segment plan.
     int nsys = 0;
     bool own_ptr = false;   // a borrowed device matrix whose row pointers were copied to append the padding rows
     long long nnz = 0;
@@ -132,6 +134,8 @@ static int validate_csr_host(int n, long long nnz, const int *ptr, const int *co
 static void *dbuf(cgamd_solver *s, int k) { return (s->fused2 && (k & 1)) ? s->d2 : s->d; }
 // a preconditioner (diagonal or tridiagonal) is set: what decides the loop family; s->mdiag is read where the diagonal is used
 static bool precond_set(const cgamd_solver *s) { return s->mdiag != nullptr || s->tri_on; }
+// values between the diagonals of consecutive right-hand sides in s->mdiag: a batched handle keeps one per system, else one for all
+static long long m_pitch(const cgamd_solver *s) { return s->nsys ? s->n : 0; }
 static bool fused2_now(const cgamd_solver *s) { return s->fused2 && !s->rm && !precond_set(s) && !(s->flags & CGAMD_UNFUSED); }
 
 // the handle's SpMV on n rows of RHS-major vectors: the batched kernel where every right-hand side has a matrix of its own
@@ -156,7 +160,8 @@ static int enqueue_spmv(cgamd_solver *s, int k, hipStream_t st) {
         rc = launch_spmv_fused(dt, s->plan, n, s->nnz, s->vals, s->ptr, s->cols, dbuf(s, k), dbuf(s, k + 1), s->r, s->q, nr, s->part_dq,
                                s->part_rr, s->vgrid, s->sc, st);
     else if (s->rm) rc = launch_spmm_rm(dt, n, s->nnz, s->vals, s->ptr, s->cols, s->d, s->q, nr, s->part_dq, s->plan.max_quad, s->rm_pace, st);
-    else if ((s->flags & CGAMD_UNFUSED) && !s->tri_on) rc = handle_spmv(s, n, s->d, n, s->q, n, nullptr, nullptr, st);
+    // (the preconditioned loops of a batched handle take alpha from the d.q partials whatever the flags)
+    else if ((s->flags & CGAMD_UNFUSED) && !s->tri_on && !(s->nsys && s->mdiag)) rc = handle_spmv(s, n, s->d, n, s->q, n, nullptr, nullptr, st);
     else rc = handle_spmv(s, n, s->d, n, s->q, n, s->d, s->part_dq, st);
     set_kernel_event_pair(nullptr);
     if (rc) return rc;
@@ -197,8 +202,8 @@ static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st) {
         if ((rc = enqueue_spmv(s, k, st))) return rc;
         if ((rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st))) return rc;
         if ((rc = launch_pcg_axpy2_dot2(dt, false, n, s->d, s->x, s->q, s->r, s->mdiag, n, s->sc.alpha, nr, s->part_rz, s->part_rr,
-                                        s->vgrid, st))) return rc;
-        return launch_pcg_aypx_beta(dt, n, s->r, s->d, s->mdiag, n, s->part_rz, s->part_rr, s->vgrid, nr, s->sc, s->rho2, s->x, st);
+                                        s->vgrid, st, m_pitch(s)))) return rc;
+        return launch_pcg_aypx_beta(dt, n, s->r, s->d, s->mdiag, n, s->part_rz, s->part_rr, s->vgrid, nr, s->sc, s->rho2, s->x, st, m_pitch(s));
     }
     if (!(s->flags & CGAMD_UNFUSED)) {
         if ((rc = enqueue_spmv(s, k, st))) return rc;
@@ -228,6 +233,7 @@ static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st) {
 // So iterate(15) twice and iterate(30) return the same bits although the first takes the launched loop and the second the
 // resident one.  Called whenever the wide plan may have changed; captured graphs hold grids and orders, so they go when it did.
 static void apply_wide_order(cgamd_solver *s) {
+    if (s->nsys) return;        // a batched handle has no resident loop to match
     const int E = (int)(16 / dtype_size(s->dtype));
     // (where the one-XCD resident loop applies it runs, with the strided order -- unless a preconditioner is set: that recurrence only
     // has the chip-wide form; the tridiagonal one has none)
@@ -550,6 +556,8 @@ static int batched_refuses(const char *who) {
 }
 static int line_from_matrix(cgamd_solver *s, const std::string &who, int stride);
 static int jacobi_from_matrix(cgamd_solver *s, const std::string &who);
+static int batched_line_from_matrix(cgamd_solver *s, const std::string &who, int stride);
+static int batched_jacobi_from_matrix(cgamd_solver *s, const std::string &who);
 
 // New matrix VALUES / PATTERN of the same size into an existing handle (host arrays; the handle must own its matrix):
 // what the stateless cg() needs to reuse its cached device state -- allocations, stream, captured graphs -- from one call
@@ -581,8 +589,16 @@ int cgamd_solver_reload_matrix(cgamd_solver *s, const void *aValues, const int *
         s->fused2 = fused2_ok(s->plan, s->dtype, s->nrhs, s->vals, s->cols);
         if (s->nsys) finalize_batched_plan(s);
     }
-    if (s->nsys) {                                  // no resident loop, no codes, no preconditioner to follow the matrix
+    if (s->nsys) {                                  // no resident loop, no codes; a per-system preconditioner built from the matrices follows them
         CG_HIP(hipStreamSynchronize(st));
+        if (s->pre_source >= 2) {
+            const int rc = s->pre_kind == 1 ? batched_jacobi_from_matrix(s, "reload_matrix") : batched_line_from_matrix(s, "reload_matrix", s->pre_stride);
+            if (rc) {                               // the matrices are loaded; the old factors belong to the old ones
+                const std::string why = cgamd_last_error();
+                (void)diag_impl(s, nullptr, 0);
+                return fail(rc, why);
+            }
+        }
         return CGAMD_OK;
     }
     if (int rc = setup_resident(s)) return rc;      // also with unchanged row pointers: the column range of a row slice may have moved
@@ -675,7 +691,7 @@ int cgamd_solver_set_rhs(cgamd_solver *s, const void *b, const void *x0, int on_
         if ((rc = launch_pcg_delta0(s->dtype, prz, prr, s->tri.grid, s->nrhs, s->sc, s->rho2, st))) return rc;
     } else if (s->mdiag) {   // z0 = M r0, p0 = z0, rho0 = r0.z0 (helmFE_var.py:562-573)
         if ((rc = launch_pcg_axpy2_dot2(s->dtype, true, s->n, s->d, s->x, s->q, s->r, s->mdiag, s->n, nullptr, s->nrhs, s->part_rz,
-                                        s->part_rr, s->vgrid, st))) return rc;
+                                        s->part_rr, s->vgrid, st, m_pitch(s)))) return rc;
         if ((rc = launch_pcg_delta0(s->dtype, s->part_rz, s->part_rr, s->vgrid, s->nrhs, s->sc, s->rho2, st))) return rc;
     } else {
         CG_HIP(hipMemcpyAsync(s->d, s->r, vbytes, hipMemcpyDeviceToDevice, st));
@@ -702,8 +718,9 @@ static void drop_tridiag(cgamd_solver *s) {
 // preconditioner.  The next cgamd_solver_set_rhs starts the preconditioned recurrence; history then holds r.r as before.
 int cgamd_solver_set_preconditioner(cgamd_solver *s, const void *m, int on_device) {
     if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner: solver is NULL");
-    if (s->nsys) return m ? batched_refuses("set_preconditioner") : CGAMD_OK;      // there is none to remove
-    TuneScope ts(&s->tune);
+    if (s->nsys && m) return batched_refuses("set_preconditioner");
+    if (s->nsys && !precond_set(s)) return CGAMD_OK;      // there is none to remove
+    TuneScope ts(&s->tune);       // (m == NULL also removes the per-system preconditioner of a batched handle)
     return diag_impl(s, m, on_device);
 }
 static int diag_impl(cgamd_solver *s, const void *m, int on_device) {
@@ -719,16 +736,19 @@ static int diag_impl(cgamd_solver *s, const void *m, int on_device) {
         return CGAMD_OK;
     }
     const size_t vs = dtype_size(s->dtype);
+    const size_t nm = s->nsys ? (size_t)s->nsys : 1;      // diagonals behind m: one per system of a batched handle, at the caller's stride
     int rc = CGAMD_OK;
-    if (!s->mdiag) rc = dmalloc(&s->mdiag, (size_t)s->n * vs, "preconditioner");
+    if (!s->mdiag) rc = dmalloc(&s->mdiag, (size_t)s->n * nm * vs, "preconditioner");
     if (!rc && !s->part_rz) rc = dmalloc(&s->part_rz, acc_size(s->dtype) * s->part_rr_cap * s->nrhs, "partials_rz");
     if (!rc && !s->rho2) rc = dmalloc(&s->rho2, 2 * vs * (size_t)s->nrhs, "rho");
     if (rc) return rc;
-    if (s->n != s->n_user) CG_HIP(hipMemsetAsync(s->mdiag, 0, (size_t)s->n * vs, s->ctx->stream));
-    CG_HIP(hipMemcpyAsync(s->mdiag, m, (size_t)s->n_user * vs, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->ctx->stream));
+    if (s->n != s->n_user) CG_HIP(hipMemsetAsync(s->mdiag, 0, (size_t)s->n * nm * vs, s->ctx->stream));
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (nm == 1 || s->n == s->n_user) CG_HIP(hipMemcpyAsync(s->mdiag, m, (size_t)s->n_user * nm * vs, kind, s->ctx->stream));
+    else CG_HIP(hipMemcpy2DAsync(s->mdiag, (size_t)s->n * vs, m, (size_t)s->n_user * vs, (size_t)s->n_user * vs, nm, kind, s->ctx->stream));
     CG_HIP(hipStreamSynchronize(s->ctx->stream));
     s->pre_source = 1;
-    if (!s->resw.ok)
+    if (!s->resw.ok && !s->nsys)
         if (int rc2 = setup_resident_wide_plan(s)) return rc2;      // (skipped at creation where the one-XCD loop runs the plain recurrence)
     apply_wide_order(s);
     return CGAMD_OK;
@@ -737,7 +757,7 @@ static int diag_impl(cgamd_solver *s, const void *m, int on_device) {
 // The handle takes a factored tridiagonal M over.  coef (3 x pitch values: -l, -w c, w) and plan (stride 1: count + 1 chunk
 // boundaries; stride > 1: count (first row, length) pairs) are device allocations, filled, that belong to the handle from here on
 // -- also when this fails.  Everything that can be wrong with M was checked before.
-static int tri_install(cgamd_solver *s, void *coef, size_t pitch, int *plan, int stride, int count, bool longform) {
+static int tri_install(cgamd_solver *s, void *coef, size_t pitch, int *plan, int stride, int count, bool longform, int nsys = 0) {
     const int dt = s->dtype;
     const size_t vs = dtype_size(dt);
     const int grid = stride == 1 ? std::min(count, 1024) : tri_strided_grid(count);
@@ -757,7 +777,9 @@ static int tri_install(cgamd_solver *s, void *coef, size_t pitch, int *plan, int
         return rc;
     }
     char *cb = static_cast<char *>(s->tri_coef);
-    s->tri.nl = cb; s->tri.ne = cb + pitch * vs; s->tri.w = cb + 2 * pitch * vs;
+    const size_t arr = pitch * vs * (nsys ? (size_t)nsys : 1);      // nsys > 0: every array holds the factors of all systems, `pitch` apart
+    s->tri.nl = cb; s->tri.ne = cb + arr; s->tri.w = cb + 2 * arr;
+    s->tri.fpitch = nsys ? (long long)pitch : 0;
     if (stride == 1) {
         s->tri.cstart = s->tri_cstart;
         s->tri.nchunks = count; s->tri.longform = longform;
@@ -843,6 +865,59 @@ int cgamd_solver_set_preconditioner_jacobi(cgamd_solver *s) {
     if (s->nsys) return batched_refuses("set_preconditioner_jacobi");
     TuneScope ts(&s->tune);
     return jacobi_from_matrix(s, "set_preconditioner_jacobi");
+}
+
+// ---- a batched handle: one M per system (M_r for right-hand side r), never one shared by all ------------------------------------------
+static int not_batched(const char *who, const char *shared) {
+    return fail(CGAMD_ERR_STATE, std::string(who) + ": the handle is not batched (one matrix for all right-hand sides); use " + shared);
+}
+// m: nSystems * size values, the diagonal of system r at m + r * size; NULL removes any preconditioner
+int cgamd_solver_set_preconditioner_batched(cgamd_solver *s, const void *m, int on_device) {
+    if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner_batched: solver is NULL");
+    if (!s->nsys) return not_batched("set_preconditioner_batched", "cgamd_solver_set_preconditioner");
+    if (!m && !precond_set(s)) return CGAMD_OK;
+    TuneScope ts(&s->tune);
+    return diag_impl(s, m, on_device);
+}
+// m_r = 1 / diag(A_r) of every system on the device, then the diagonal form itself
+static int batched_jacobi_from_matrix(cgamd_solver *s, const std::string &who) {
+    CG_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    CG_HIP(hipStreamSynchronize(st));
+    void *m = nullptr;
+    int rc = dmalloc(&m, (size_t)s->n_user * s->nsys * dtype_size(s->dtype), "Jacobi preconditioner");
+    if (rc) return rc;
+    rc = jacobi_build_from_matrix_batched(st, s->dtype, s->n_user, s->nsys, s->nnz, who, s->vals, s->ptr, s->cols, m, s->n_user);
+    if (!rc) rc = diag_impl(s, m, 1);
+    (void)hipFree(m);
+    if (!rc) { s->pre_source = 2; s->pre_kind = 1; }
+    return rc;
+}
+int cgamd_solver_set_preconditioner_batched_jacobi(cgamd_solver *s) {
+    if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner_batched_jacobi: solver is NULL");
+    if (!s->nsys) return not_batched("set_preconditioner_batched_jacobi", "cgamd_solver_set_preconditioner_jacobi");
+    TuneScope ts(&s->tune);
+    return batched_jacobi_from_matrix(s, "set_preconditioner_batched_jacobi");
+}
+// M_r = the lines of A_r at `stride`: every system extracted and factored on the device, one segment plan for all of them.  Nothing on
+// the handle changes before tri_install.
+static int batched_line_from_matrix(cgamd_solver *s, const std::string &who, int stride) {
+    CG_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    CG_HIP(hipStreamSynchronize(st));
+    TriBuilt b;
+    int rc = tri_build_from_matrix_batched(st, s->dtype, s->n_user, s->n, s->nsys, s->nnz, who, stride, s->vals, s->ptr, s->cols, &b);
+    if (rc) return rc;
+    rc = tri_install(s, b.coef, b.pitch, b.plan, b.stride, b.count, b.longform, b.nsys);
+    if (!rc) { s->pre_source = 2; s->pre_kind = 2; s->pre_stride = stride; }
+    return rc;
+}
+int cgamd_solver_set_preconditioner_batched_line(cgamd_solver *s, int stride) {
+    if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner_batched_line: solver is NULL");
+    if (!s->nsys) return not_batched("set_preconditioner_batched_line", "cgamd_solver_set_preconditioner_line");
+    if (stride < 1 || stride >= s->n_user) return fail(CGAMD_ERR_INVALID, "set_preconditioner_batched_line: stride must be in [1, size - 1]");
+    TuneScope ts(&s->tune);
+    return batched_line_from_matrix(s, "set_preconditioner_batched_line", stride);
 }
 
 int cgamd_solver_preconditioner_source(cgamd_solver *s) { return s ? s->pre_source : 0; }
@@ -1125,6 +1200,7 @@ int cgamd_solver_loop_launches(cgamd_solver *s) {
     if (!s) return -CGAMD_ERR_INVALID;
     TuneScope ts(&s->tune);
     if (s->tri_on) return s->tri.longform ? 6 : 4;      // launched loop only: SpMV, cg_alpha, the sweep (3 launches in the long form), update
+    if (s->nsys && s->mdiag) return 4;                   // a batched handle's PCG loop is the same four launches under every flag
     if (s->flags & CGAMD_UNFUSED) return 8;
     if (s->rm) return 5;
     if (s->mdiag) return (s->resw.ok && !s->rm && !(s->flags & (CGAMD_NO_GRAPH | CGAMD_UNFUSED))) ? 1 : 4;
@@ -1148,14 +1224,17 @@ long long cgamd_solver_spmv_bytes(cgamd_solver *s) {
 // r again and writes z from a second sweep launch (+2 per RHS) and reads the factors twice (+3).  The strided form (one thread per
 // segment) stores w y in the forward walk and reads it and r back in the backward walk: sweep (r, q in; r, w y out; w y, r in; z
 // out) 7, so 14 per RHS, and each factor once
+// (a batched handle has factors of its own per right-hand side)
 static long long tri_passes(const cgamd_solver *s) {
-    if (s->tri.stride > 1) return 14LL * s->nrhs + 3;
-    return s->tri.longform ? 13LL * s->nrhs + 6 : 11LL * s->nrhs + 3;
+    const long long f = value_arrays(s);
+    if (s->tri.stride > 1) return 14LL * s->nrhs + 3 * f;
+    return s->tri.longform ? 13LL * s->nrhs + 6 * f : 11LL * s->nrhs + 3 * f;
 }
 long long cgamd_solver_iter_bytes(cgamd_solver *s, int fused) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
-    if (s->tri_on) return s->nnz * (V + 4) + ((long long)s->n_user + 1) * 4 + tri_passes(s) * s->n_user * V;
+    if (s->tri_on) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + tri_passes(s) * s->n_user * V;
+    if (s->nsys && s->mdiag) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + 12LL * s->n_user * V * s->nrhs;
     return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + (fused ? 11LL : 14LL) * s->n_user * V * s->nrhs;
 }
 
@@ -1181,7 +1260,7 @@ int cgamd_solver_joint_codes(cgamd_solver *s) { return s ? (joint_form(s) ? s->n
 long long cgamd_solver_iter_moved_bytes(cgamd_solver *s) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
-    const long long passes = (s->flags & CGAMD_UNFUSED) ? 14 : s->mdiag ? 12 : 10;
+    const long long passes = (s->nsys && s->mdiag) ? 12 : (s->flags & CGAMD_UNFUSED) ? 14 : s->mdiag ? 12 : 10;
     const long long value_bytes = joint_form(s) ? 0 : s->plan.vcodes ? 1 : V * value_arrays(s);
     const long long matrix = s->nnz * (value_bytes + index_bytes_per_nnz(s)) + ((long long)s->n_user + 1) * 4;
     if (s->tri_on) return matrix + tri_passes(s) * s->n_user * V;

@@ -351,13 +351,14 @@ __global__ __launch_bounds__(BLOCK) void aypx_beta_x_kernel(int n, const T *__re
 //   pcg_axpy2_dot2_kernel : r -= alpha q, partials of r.(m r) and of r.r                    (4NV bytes)
 //   pcg_aypx_beta_kernel  : beta in the prologue, x += alpha p, p = m r + beta p            (6NV bytes)
 // (x += alpha p rides in the second launch, which reads p anyway: see the ten-vector-pass iteration above)
-// m[i] is what multiplies r[i] (the inverse diagonal for Jacobi), shared by all right-hand sides.  rho of the previous
+// m[i] is what multiplies r[i] (the inverse diagonal for Jacobi), shared by all right-hand sides (mp = 0) or one per right-hand
+// side at m + r * mp (a batched handle: the diagonal of system r).  rho of the previous
 // iteration is read from a two-entry parity buffer so that work-group 0 may publish the new one in the same launch.
 // =================================================================================================
 template <typename T, int BLOCK, bool VEC, bool INIT>
 __global__ __launch_bounds__(BLOCK) void pcg_axpy2_dot2_kernel(int n, const T *__restrict__ d, T *__restrict__ x,
                                                                const T *__restrict__ q, T *__restrict__ rv,
-                                                               const T *__restrict__ m, long long ld,
+                                                               const T *__restrict__ m, long long mp, long long ld,
                                                                const T *__restrict__ alpha,
                                                                typename VT<T>::acc *__restrict__ part_rz,
                                                                typename VT<T>::acc *__restrict__ part_rr) {
@@ -367,6 +368,7 @@ __global__ __launch_bounds__(BLOCK) void pcg_axpy2_dot2_kernel(int n, const T *_
     const int r = blockIdx.y;
     T *dw = const_cast<T *>(d) + (long long)r * ld;
     d += (long long)r * ld; x += (long long)r * ld; q += (long long)r * ld; rv += (long long)r * ld;
+    m += (long long)r * mp;
     const T al = INIT ? vzero<T>() : alpha[r];
     A arz = vzero<A>(), arr = vzero<A>();
     constexpr int E = Pack<T>::N;
@@ -411,10 +413,10 @@ __global__ __launch_bounds__(BLOCK) void pcg_axpy2_dot2_kernel(int n, const T *_
     if (threadIdx.x == 0) part_rr[(long long)r * gridDim.x + blockIdx.x] = trr;
 }
 
-// ZV (tridiagonal M, precond.hip): m is z itself, one vector per right-hand side like r, and p = z + beta p
+// ZV (tridiagonal M, precond.hip): m is z itself, one vector per right-hand side like r (mp = ld), and p = z + beta p
 template <typename T, int BLOCK, bool VEC, bool ZV = false>
 __global__ __launch_bounds__(BLOCK) void pcg_aypx_beta_kernel(int n, const T *__restrict__ rv, T *__restrict__ pv,
-                                                              const T *__restrict__ m, long long ld,
+                                                              const T *__restrict__ m, long long mp, long long ld,
                                                               const typename VT<T>::acc *__restrict__ part_rz,
                                                               const typename VT<T>::acc *__restrict__ part_rr, int P, int K, int nrhs,
                                                               T *delta, T *beta, T *history, int history_cap, T *rho2, const int *iter,
@@ -448,7 +450,7 @@ __global__ __launch_bounds__(BLOCK) void pcg_aypx_beta_kernel(int n, const T *__
     }
     const T bt = beta_s, al = alpha[r];
     rv += (long long)r * ld; pv += (long long)r * ld; xs += (long long)r * ld;
-    if constexpr (ZV) m += (long long)r * ld;
+    m += (long long)r * mp;
     constexpr int E = Pack<T>::N;
     const long long stride = (long long)gridDim.x * BLOCK;
     long long i0 = (long long)blockIdx.x * BLOCK + threadIdx.x;
@@ -835,35 +837,36 @@ int launch_aypx_beta(int dtype, int n, const void *x, void *y, long long ld, con
 
 // ---- diagonally preconditioned CG -----------------------------------------------------------------
 template <typename T>
-static int pcg_axpy2_impl(bool init, int n, const void *d, void *x, const void *q, void *r, const void *m, long long ld,
+static int pcg_axpy2_impl(bool init, int n, const void *d, void *x, const void *q, void *r, const void *m, long long m_pitch, long long ld,
                           const void *alpha, int nrhs, void *part_rz, void *part_rr, int grid, bool vec, hipStream_t st) {
     dim3 g(grid, nrhs), blk(kBlock);
     using A = typename VT<T>::acc;
 #define CG_PCG(V, I) hipLaunchKernelGGL((pcg_axpy2_dot2_kernel<T, kBlock, V, I>), g, blk, 0, st, n, (const T *)d, (T *)x, (const T *)q, \
-                                        (T *)r, (const T *)m, ld, (const T *)alpha, (A *)part_rz, (A *)part_rr)
+                                        (T *)r, (const T *)m, m_pitch, ld, (const T *)alpha, (A *)part_rz, (A *)part_rr)
     if (init) { if (vec) CG_PCG(true, true); else CG_PCG(false, true); }
     else { if (vec) CG_PCG(true, false); else CG_PCG(false, false); }
 #undef CG_PCG
     return check_launch("pcg_axpy2_dot2");
 }
 int launch_pcg_axpy2_dot2(int dtype, bool init, int n, const void *d, void *x, const void *q, void *r, const void *m,
-                          long long ld, const void *alpha, int nrhs, void *part_rz, void *part_rr, int grid, hipStream_t st) {
-    const bool vec = vec_ok(dtype, ld, nrhs, {d, x, q, r, m});
-    CG_DISPATCH(dtype, pcg_axpy2_impl, init, n, d, x, q, r, m, ld, alpha, nrhs, part_rz, part_rr, grid, vec, st);
+                          long long ld, const void *alpha, int nrhs, void *part_rz, void *part_rr, int grid, hipStream_t st,
+                          long long m_pitch) {
+    const bool vec = vec_ok(dtype, ld, nrhs, {d, x, q, r, m}) && ((m_pitch * (long long)dtype_size(dtype)) & 15) == 0;
+    CG_DISPATCH(dtype, pcg_axpy2_impl, init, n, d, x, q, r, m, m_pitch, ld, alpha, nrhs, part_rz, part_rr, grid, vec, st);
 }
 template <typename T>
-static int pcg_aypx_impl(int n, const void *r, void *p, const void *m, long long ld, const void *part_rz, const void *part_rr,
+static int pcg_aypx_impl(int n, const void *r, void *p, const void *m, long long m_pitch, long long ld, const void *part_rz, const void *part_rr,
                          int P, int nrhs, const CgScalars &sc, void *rho2, void *xs, bool vec, hipStream_t st) {
     dim3 g(vec_grid(n, VT<T>::dtype, nrhs), nrhs), blk(kBlock);
     using A = typename VT<T>::acc;
-    if (vec) hipLaunchKernelGGL((pcg_aypx_beta_kernel<T, kBlock, true>), g, blk, 0, st, n, (const T *)r, (T *)p, (const T *)m, ld, (const A *)part_rz, (const A *)part_rr, P, sc.krr, nrhs, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter, (T *)xs, (const T *)sc.alpha);
-    else hipLaunchKernelGGL((pcg_aypx_beta_kernel<T, kBlock, false>), g, blk, 0, st, n, (const T *)r, (T *)p, (const T *)m, ld, (const A *)part_rz, (const A *)part_rr, P, sc.krr, nrhs, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter, (T *)xs, (const T *)sc.alpha);
+    if (vec) hipLaunchKernelGGL((pcg_aypx_beta_kernel<T, kBlock, true>), g, blk, 0, st, n, (const T *)r, (T *)p, (const T *)m, m_pitch, ld, (const A *)part_rz, (const A *)part_rr, P, sc.krr, nrhs, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter, (T *)xs, (const T *)sc.alpha);
+    else hipLaunchKernelGGL((pcg_aypx_beta_kernel<T, kBlock, false>), g, blk, 0, st, n, (const T *)r, (T *)p, (const T *)m, m_pitch, ld, (const A *)part_rz, (const A *)part_rr, P, sc.krr, nrhs, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter, (T *)xs, (const T *)sc.alpha);
     return check_launch("pcg_aypx_beta");
 }
 int launch_pcg_aypx_beta(int dtype, int n, const void *r, void *p, const void *m, long long ld, const void *part_rz,
-                         const void *part_rr, int P, int nrhs, const CgScalars &sc, void *rho2, void *xs, hipStream_t st) {
-    const bool vec = vec_ok(dtype, ld, nrhs, {r, p, m, xs});
-    CG_DISPATCH(dtype, pcg_aypx_impl, n, r, p, m, ld, part_rz, part_rr, P, nrhs, sc, rho2, xs, vec, st);
+                         const void *part_rr, int P, int nrhs, const CgScalars &sc, void *rho2, void *xs, hipStream_t st, long long m_pitch) {
+    const bool vec = vec_ok(dtype, ld, nrhs, {r, p, m, xs}) && ((m_pitch * (long long)dtype_size(dtype)) & 15) == 0;
+    CG_DISPATCH(dtype, pcg_aypx_impl, n, r, p, m, m_pitch, ld, part_rz, part_rr, P, nrhs, sc, rho2, xs, vec, st);
 }
 // the tridiagonal form: p = z + beta p with z = M^-1 r from pcg_tri (per right-hand side, stride ld); the partials are
 // pcg_tri's, summed thread-strided
@@ -872,8 +875,8 @@ static int pcg_aypx_z_impl(int n, void *p, const void *z, long long ld, const vo
                            const CgScalars &sc, void *rho2, void *xs, bool vec, hipStream_t st) {
     dim3 g(vec_grid(n, VT<T>::dtype, nrhs), nrhs), blk(kBlock);
     using A = typename VT<T>::acc;
-    if (vec) hipLaunchKernelGGL((pcg_aypx_beta_kernel<T, kBlock, true, true>), g, blk, 0, st, n, (const T *)nullptr, (T *)p, (const T *)z, ld, (const A *)part_rz, (const A *)part_rr, P, 0, nrhs, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter, (T *)xs, (const T *)sc.alpha);
-    else hipLaunchKernelGGL((pcg_aypx_beta_kernel<T, kBlock, false, true>), g, blk, 0, st, n, (const T *)nullptr, (T *)p, (const T *)z, ld, (const A *)part_rz, (const A *)part_rr, P, 0, nrhs, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter, (T *)xs, (const T *)sc.alpha);
+    if (vec) hipLaunchKernelGGL((pcg_aypx_beta_kernel<T, kBlock, true, true>), g, blk, 0, st, n, (const T *)nullptr, (T *)p, (const T *)z, ld, ld, (const A *)part_rz, (const A *)part_rr, P, 0, nrhs, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter, (T *)xs, (const T *)sc.alpha);
+    else hipLaunchKernelGGL((pcg_aypx_beta_kernel<T, kBlock, false, true>), g, blk, 0, st, n, (const T *)nullptr, (T *)p, (const T *)z, ld, ld, (const A *)part_rz, (const A *)part_rr, P, 0, nrhs, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter, (T *)xs, (const T *)sc.alpha);
     return check_launch("pcg_aypx_beta z");
 }
 int launch_pcg_aypx_beta_z(int dtype, int n, void *p, const void *z, long long ld, const void *part_rz, const void *part_rr, int P, int nrhs,

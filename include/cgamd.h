@@ -131,9 +131,11 @@ int cgamd_solver_create(cgamd_ctx *ctx, int dtype, int size, long long nnz, cons
  * dot_partials and destroy behave as on any other handle.  The handle always runs a launched loop (cgamd_solver_loop_launches() >= 2:
  * no resident, chip-wide or two-launch loop), keeps the RHS-major layout (cgamd_solver_layout() == 0) and uses no index, value or
  * joint codes (the three accessors return 0); its SpMV is family 6 of cgamd_last_spmv_form (csrc/batched.hip).
- * Not served: cgamd_solver_iterate_tol and cgamd_solver_spmm_rowmajor return CGAMD_ERR_STATE; so do the five
+ * Not served: cgamd_solver_iterate_tol and cgamd_solver_spmm_rowmajor return CGAMD_ERR_STATE; so do the five shared-M
  * cgamd_solver_set_preconditioner* entries -- an M shared by all right-hand sides has no meaning for different systems -- except
- * cgamd_solver_set_preconditioner(s, NULL, 0), which returns CGAMD_OK and changes nothing.  A refused call leaves the handle as it was.
+ * cgamd_solver_set_preconditioner(s, NULL, 0), which returns CGAMD_OK and removes a per-system preconditioner if one is set.  A
+ * refused call leaves the handle as it was.  Preconditioned CG runs with one M PER SYSTEM: cgamd_solver_set_preconditioner_batched,
+ * _batched_jacobi and _batched_line below.
  * Byte models: every value array is counted once and the indices once, cgamd_solver_spmv_bytes = cgamd_solver_spmv_moved_bytes =
  * nnz * (nSystems * sizeof(value) + 4) + 4 * (size + 1) + 2 * size * sizeof(value) * nSystems; the iter_* entries take the same
  * matrix term. */
@@ -144,7 +146,8 @@ int cgamd_solver_destroy(cgamd_solver *s);
 /* new values / pattern of the SAME size (size, nnz, nRHS, dtype) into a handle that owns its matrix (created from host
  * arrays): keeps allocations, stream and -- when the row pointers are unchanged -- the plan and the captured graphs.
  * The next call must be cgamd_solver_set_rhs.  A preconditioner from the caller's arrays is kept; one built from the matrix
- * (cgamd_solver_set_preconditioner_line / _jacobi) is built again from the new matrix. */
+ * (cgamd_solver_set_preconditioner_line / _jacobi; on a batched handle _batched_line / _batched_jacobi) is built again from the new
+ * matrix. */
 int cgamd_solver_reload_matrix(cgamd_solver *s, const void *aValues, const int *aPointers, const int *aCols);
 /* b, x0: nRHS*size values, host (on_device=0) or device (on_device=1) memory; x0 may be NULL (zeros).
  * Computes r = b - A x0, d = r, delta0 = r.r  (reference clcg.c:255-292) and resets the iteration count. */
@@ -242,8 +245,45 @@ int cgamd_solver_set_preconditioner_line(cgamd_solver *s, int stride);
  * form, resident loops included.  A zero, missing or non-finite diagonal returns CGAMD_ERR_INVALID naming the first such row, the
  * handle unchanged. */
 int cgamd_solver_set_preconditioner_jacobi(cgamd_solver *s);
-/* where the preconditioner in force came from -- 0: none; 1: the caller's arrays (the three entries above); 2: the matrix, built on
- * the device; 3: the matrix, extracted on the device but factored by the host route (long segments) */
+/* Preconditioned CG on a BATCHED handle (cgamd_solver_create_batched): one M per system, M_r for right-hand side r.  The three entries
+ * are for batched handles only; on any other handle they return CGAMD_ERR_STATE naming the shared-M entry to use instead.
+ * Everything not said here is the contract of the one-matrix entries above: effective at the next cgamd_solver_set_rhs; history keeps
+ * holding r.r; rho = r.z drives alpha and beta per system; cgamd_solver_set_preconditioner_batched(s, NULL, 0) or
+ * cgamd_solver_set_preconditioner(s, NULL, 0) removes it and the handle then returns the bits of one that never had a
+ * preconditioner; a failed call leaves the handle as it was (a preconditioner set before stays in force with the same bits);
+ * cgamd_solver_iterate_tol keeps returning CGAMD_ERR_STATE; CGAMD_NO_GRAPH, CGAMD_UNFUSED (the preconditioned loop is the same four
+ * launches, d.q partials included) and CGAMD_MATRIX_ON_DEVICE (the values as they are at the time of the call) are served.
+ *   _batched         m: nSystems * size values of the handle's type, host or device, the diagonal of system r at m + r * size (the
+ *                    caller's stride is `size`; inside the handle it is cgamd_solver_ld and the padding rows are 0); z_r = m_r .* r_r.
+ *                    m == NULL removes any preconditioner.  Source 1; kept by cgamd_solver_reload_matrix.
+ *   _batched_jacobi  m_r[i] = 1 / A_r[i][i] from every system's values, by the rules of cgamd_solver_set_preconditioner_jacobi (entries
+ *                    at the same column summed in stored order in double / complex double, one rounding).  Source 2.
+ *   _batched_line    M_r = the entries of A_r at column - row in {-stride, 0, +stride}; stride outside [1, size - 1] returns
+ *                    CGAMD_ERR_INVALID.  Every system is factored with the recurrence of cgamd_solver_set_preconditioner_line (Thomas, no
+ *                    pivoting, double / complex double; -l, -w c and w each rounded once).  Source 2.
+ * Errors (CGAMD_ERR_INVALID) name the system and the row, "... in system R row I": the smallest failing system, then the smallest row in
+ * it; the wording is otherwise that of the one-matrix entries (zero, missing or non-finite diagonal; non-finite entry; zero or
+ * non-finite pivot; pivot too small).
+ * ONE SEGMENT PLAN serves all systems: row i starts a segment when i < stride or when, in EVERY system, both stored couplings to row
+ * i - stride round to zero in the value type (the one-matrix rule AND-ed over the systems; on a grid the segments are the grid
+ * lines).  A system with a further zero coupling inside a shared segment is solved correctly: its zero factors restart the
+ * recurrence arithmetically.  stride 1 takes the scan sweep on chunks built from the shared starts (cgamd_solver_loop_launches() = 4,
+ * or 6 when a shared segment is longer than a chunk), stride > 1 one thread per segment (4 launches).
+ * The setup runs on the device with a constant number of launches and host synchronisations whatever nSystems (extraction reads the
+ * pattern once per row and then the found positions in every system's values; one thread per (pre-segment, system) factors).  There is
+ * no host route and no row limit: source 3 does not occur, and LONG 1-D CHAINS ARE FACTORED AND SOLVED SERIALLY, one thread per
+ * (segment, system) in the setup -- correct, and slow.  Temporary device memory: six nSystems * size value arrays.
+ * cgamd_solver_reload_matrix rebuilds the Jacobi or line form from the nSystems * nnz new values; if that fails the matrices are
+ * loaded, the preconditioner is removed and the error is returned.
+ * Byte models (on top of the matrix term nnz * (nSystems * V + 4) + 4 * (size + 1), V = sizeof(value); moved and algorithmic alike):
+ * diagonal 12 * size * V * nSystems; line at stride > 1 (14 + 3); at stride 1 (11 + 3), in its long form (13 + 6) -- the vector passes
+ * of the one-matrix forms and the three factor arrays, now read per system. */
+int cgamd_solver_set_preconditioner_batched(cgamd_solver *s, const void *m, int on_device);
+int cgamd_solver_set_preconditioner_batched_jacobi(cgamd_solver *s);
+int cgamd_solver_set_preconditioner_batched_line(cgamd_solver *s, int stride);
+/* where the preconditioner in force came from -- 0: none; 1: the caller's arrays (the three array entries above, and
+ * cgamd_solver_set_preconditioner_batched); 2: the matrix, built on the device; 3: the matrix, extracted on the device but factored by
+ * the host route (long segments; never on a batched handle) */
 int cgamd_solver_preconditioner_source(cgamd_solver *s);
 /* convenience: set_rhs + iterate + get_x (+ history if non-NULL, (nIterations+1)*nRHS values), host arrays */
 int cgamd_solver_solve(cgamd_solver *s, const void *b, void *x, int nIterations, void *history);

@@ -12,12 +12,18 @@ device events on the handles' stream (and a host clock around the same window, e
 inside every one of `--reps` repeats, and the median over the repeats is reported with the extremes.  One JSON line per (size, form).
 The batched SpMV alone (Solver.spmv on device vectors, `--spmv-reps` launches per window) is priced on
 cgamd_solver_spmv_moved_bytes against 8 TB/s.
-usage: batched_ab.py [--sizes 128,500] [--systems 9] [--iters 400] [--warmup 50] [--reps 7]"""
+--pcg {jacobi,line}: the preconditioned leg.  (a) the batched handle with one M per system (cgamd_solver_set_preconditioner_batched_jacobi
+/ _batched_line at --stride) against (b) the nine single-system handles with the same preconditioner of their own matrix
+(cgamd_solver_set_preconditioner_jacobi / _line), same method; (c) and the SpMV part are left out.  The driver starts one child
+process per size, each under its own time limit (--step-timeout), chained: a size that fails or runs out of time ends the run.  The
+lines are appended to --out (profiles/batched/pcg_ab.log: one log for both legs) and are echoed.
+usage: batched_ab.py [--sizes 128,500] [--systems 9] [--iters 400] [--warmup 50] [--reps 7] [--pcg jacobi|line [--stride 1]]"""
 import argparse
 import importlib
 import json
 import os
 import statistics
+import subprocess
 import sys
 import time
 
@@ -34,7 +40,33 @@ ap.add_argument("--iters", type=int, default=400)
 ap.add_argument("--warmup", type=int, default=50)
 ap.add_argument("--reps", type=int, default=7)
 ap.add_argument("--spmv-reps", type=int, default=200)
+ap.add_argument("--pcg", default="", choices=("", "jacobi", "line"), help="preconditioned leg: batched PCG against single-system PCG handles")
+ap.add_argument("--stride", type=int, default=1, help="--pcg line: distance of the coupled rows (1: the x-lines of the grid)")
+ap.add_argument("--step-timeout", type=int, default=300, help="--pcg: time limit of one size, in seconds")
+ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batched", "pcg_ab.log"))
+ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
 args = ap.parse_args()
+if args.pcg and not args.child:         # the driver: opens no GPU itself
+    head = f"# scripts/batched_ab.py --pcg {args.pcg}" + (f" --stride {args.stride}" if args.pcg == "line" else "")
+    lines = [head + f" --systems {args.systems} --iters {args.iters} --warmup {args.warmup} --reps {args.reps}"]
+    for side in args.sizes.split(","):
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--pcg", args.pcg, "--stride", str(args.stride), "--sizes", side,
+               "--systems", str(args.systems), "--iters", str(args.iters), "--warmup", str(args.warmup), "--reps", str(args.reps)]
+        try:
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.step_timeout)
+        except subprocess.TimeoutExpired:
+            lines.append(f"# size {side} ran into its time limit of {args.step_timeout} s; stopped here")
+            break
+        lines += [l for l in r.stdout.splitlines() if l.startswith("{")]
+        if r.returncode != 0:
+            lines.append(f"# size {side} failed with exit status {r.returncode}; stopped here\n" + r.stderr[-2000:])
+            break
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "a") as f:          # one log for both legs: every run adds its header and lines
+        f.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+    sys.exit(1 if lines[-1].startswith("# size") else 0)
+M = None if not args.pcg else "jacobi" if args.pcg == "jacobi" else ("line", args.stride)
 pkg = importlib.import_module("conjugate-gradient-pyopencl_amd")
 lib = pkg._lib.load()
 ctx = pkg.Context(0)
@@ -84,8 +116,12 @@ for side in (int(v) for v in args.sizes.split(",")):
         "sequence": [pkg.Solver(ctx, n, nnz, vals[r], ip, ix, 1, flags=flags, dtype=DT) for r in range(nsys)],
         "shared": [pkg.Solver(ctx, n, nnz, vals[0], ip, ix, nsys, flags=flags, dtype=DT)],
     }
+    if M is not None:
+        del forms["shared"]             # one matrix for all right-hand sides has no per-system M
     for name, hs in forms.items():
         for h in hs:
+            if M is not None:
+                h.set_preconditioner(M)
             h.set_rhs(b if h.n_rhs == nsys else b1, None, on_device=True)
             h.iterate(args.warmup)
     ctx.synchronize()
@@ -107,7 +143,19 @@ for side in (int(v) for v in args.sizes.split(",")):
                "iter_moved_bytes": sum(h.iter_moved_bytes for h in hs)}
         if name == "batched":
             rec["delta_vs_sequence_after_warmup_max_rel"] = agree
+        if M is not None:
+            rec["pcg"] = args.pcg if args.pcg == "jacobi" else f"line, stride {args.stride}"
+            rec["preconditioner_source"] = hs[0].preconditioner_source
         print(json.dumps(rec), flush=True)
+    if M is not None:                   # the preconditioned leg ends here
+        ma, mb = (statistics.median(times[k]["ev" if stream is not None else "wall"]) for k in ("batched", "sequence"))
+        print(json.dumps({"rows": n, "systems": nsys, "pcg": args.pcg, "batched_over_sequence_speedup": round(mb / ma, 3)}), flush=True)
+        for hs in forms.values():
+            for h in hs:
+                h.close()
+        del forms, vals, stack
+        torch.cuda.empty_cache()
+        continue
     ma, mb, mc = (statistics.median(times[k]["ev" if stream is not None else "wall"]) for k in ("batched", "sequence", "shared"))
     print(json.dumps({"rows": n, "systems": nsys, "batched_over_sequence_speedup": round(mb / ma, 3),
                       "batched_over_shared_time_ratio": round(ma / mc, 3)}), flush=True)
