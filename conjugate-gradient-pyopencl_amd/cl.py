@@ -554,6 +554,42 @@ class Solver:
             self.iterate(its)
         return its
 
+    def _tolerances(self, tol):
+        """`tol` as the float64 array cgamd_solver_iterate_until takes: one tolerance for all right-hand sides or n_rhs of them, all
+        positive.  ValueError otherwise, before anything touches the device."""
+        t = np.ascontiguousarray(np.asarray(tol, dtype=np.float64).reshape(-1))
+        if t.size not in (1, self.n_rhs):
+            raise ValueError(f"tol must be a scalar or have n_rhs = {self.n_rhs} entries, got {t.size}")
+        if not np.all(t > 0):
+            raise ValueError("every tolerance must be positive")
+        return t
+
+    def iterate_until(self, tol, maxit, check_every=8):
+        """At most `maxit` more iterations with a stop per right-hand side ON THE DEVICE (cgamd_solver_iterate_until): right-hand
+        side r stops in the first iteration whose sqrt(|r.r|) is not >= tol[r] (or NaN) and keeps the x of exactly that iteration
+        while the others run on.  tol: a scalar or n_rhs values.  The host looks at one device word per `check_every` iterations,
+        one chunk behind the device; the result does not depend on it.  Returns the iterations of every right-hand side since
+        set_rhs (int array of n_rhs).  May be repeated; once a right-hand side has stopped, iterate() raises until the next
+        set_rhs."""
+        t = self._tolerances(tol)
+        if int(maxit) < 0 or int(check_every) < 0:
+            raise ValueError("maxit and check_every must not be negative")
+        its = np.zeros(self.n_rhs, dtype=np.intc)
+        check(self._lib.cgamd_solver_iterate_until(self.handle, int(maxit), t.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(t.size),
+                                                   int(check_every), its.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return its
+
+    def solve_until(self, b, x0=None, tol=1e-5, maxit=1000, check_every=8):
+        """The reference's tolerance-stopping sub-solver (p_h-PY_C-CL.py:1338-1369; with a preconditioner set, PCG's stop,
+        helmFE_var.py:580-584) for ALL right-hand sides of the handle in one solve, batched handles included: each stops on its own
+        tolerance (`tol`: a scalar or n_rhs values) in the iteration the reference stops in, and its x is the iterate of that
+        iteration.  Returns (x, iterations per right-hand side, history); the history column of a right-hand side that stopped
+        early repeats its last entry down to the last row."""
+        self._tolerances(tol)
+        self.set_rhs(b, x0)
+        its = self.iterate_until(tol, maxit, check_every)
+        return self.x(), its, self.history()
+
     def pcg(self, b, M=None, x0=None, tol=1e-6, maxit=1000, check_every=8):
         """`PCG(A, b, M, x, tol, maxit)` of the reference (helmFE_var.py:546-586) for M = None, a diagonal M, a tridiagonal
         sparse M along any grid axis (the spsolve branch) or "jacobi" / ("line", stride) built from the matrix (see set_preconditioner): stops when sqrt(|r.r|) < tol, returns (x, i) with i the 0-based
@@ -591,7 +627,8 @@ def _shared_pattern(P):
     return indptr, indices, np.concatenate([np.asarray(A.data).ravel() for A in P])
 
 
-def solve_subdomains(ctx, P0, residuals, n_iterations, dtype=np.csingle, solver=None, preconditioner=None):
+def solve_subdomains(ctx, P0, residuals, n_iterations, dtype=np.csingle, solver=None, preconditioner=None, tol=None,
+                     return_iterations=False):
     """The batched sub-domain solve of the reference's Additive-Schwarz preconditioner `as_prec`.
 
     * UseCG in {2, 3} (p_h-PY_C-CL.py:1918-1937, 1938-1953): all n_my sub-domains share ONE matrix P[0] -- P0: scipy CSR (or
@@ -607,8 +644,19 @@ def solve_subdomains(ctx, P0, residuals, n_iterations, dtype=np.csingle, solver=
     preconditioner (a list of matrices only): one M per sub-domain, as Solver.set_preconditioner takes it on a batched handle --
     "jacobi", ("line", stride), n_my * size diagonal entries or a list of diagonal matrices.  It is set before the solve and removed
     after it, also on the caller's `solver`.  ValueError for a shared matrix or a solver that is not batched.
-    Returns a list of complex arrays shaped like the inputs (`x[p*size:(p+1)*size].astype(complex)`)."""
+    tol (a scalar or one value per sub-domain): every sub-domain stops on its own, on the device, in the first iteration whose
+    sqrt(|r.r|) is below its tolerance -- the reference's `CG(P[0], z[p].ravel(), tol=CGtol, maxit=CGMaxIT)` per sub-domain
+    (p_h-PY_C-CL.py:1916-1921) in one batched solve (Solver.iterate_until); n_iterations is then the cap.  tol=None: exactly
+    n_iterations iterations for all, as before.  ValueError for a tol of another length, before anything touches the device.
+    Returns a list of complex arrays shaped like the inputs (`x[p*size:(p+1)*size].astype(complex)`); with return_iterations=True
+    the pair (that list, the iterations of every sub-domain as an int array)."""
     n_my = len(residuals)
+    if tol is not None:
+        tol = np.ascontiguousarray(np.asarray(tol, dtype=np.float64).reshape(-1))
+        if tol.size not in (1, n_my):
+            raise ValueError(f"solve_subdomains: tol must be a scalar or have one entry per sub-domain ({n_my}), got {tol.size}")
+        if not np.all(tol > 0):
+            raise ValueError("solve_subdomains: every tolerance must be positive")
     batched = isinstance(P0, (list, tuple)) and len(P0) > 0 and hasattr(P0[0], "indptr")
     if preconditioner is not None and (not batched or (solver is not None and not getattr(solver, "batched", False))):
         raise ValueError("solve_subdomains: a preconditioner per sub-domain needs a list of sub-domain matrices and a batched Solver "
@@ -636,14 +684,19 @@ def solve_subdomains(ctx, P0, residuals, n_iterations, dtype=np.csingle, solver=
         if preconditioner is not None:
             solver.set_preconditioner(preconditioner)
         solver.set_rhs(b_values, None)
-        solver.iterate(n_iterations)
+        if tol is None:
+            solver.iterate(n_iterations)
+            its = np.full(n_my, int(n_iterations), dtype=np.intc)
+        else:
+            its = solver.iterate_until(tol, n_iterations)
         x = solver.x()
     finally:
         if own:
             solver.close()
         elif preconditioner is not None:
             solver.set_preconditioner(None)
-    return [x[p * size:(p + 1) * size].astype(complex).reshape(np.shape(residuals[p])) for p in range(n_my)]
+    out = [x[p * size:(p + 1) * size].astype(complex).reshape(np.shape(residuals[p])) for p in range(n_my)]
+    return (out, its) if return_iterations else out
 
 
 # ---- reference entry points --------------------------------------------------------------------

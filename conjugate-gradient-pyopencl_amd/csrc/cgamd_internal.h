@@ -206,13 +206,24 @@ struct CgScalars {
     const void *pcg_m = nullptr;
     void *pcg_rho2 = nullptr;
 };
+// Per-right-hand-side stop of cgamd_solver_iterate_until (stop_device.h): one device record per handle.  Launchers that take a
+// `const CgStop *` run the guarded instantiation of their kernel when it is given and the unguarded one -- the code of
+// cgamd_solver_iterate -- when it is NULL.
+struct CgStop {
+    int *nactive = nullptr;         // right-hand sides still iterating: the word the host reads back after every chunk
+    const double *tol = nullptr;    // double[nrhs], in device memory so that captured launches serve every call
+    int *stop = nullptr;            // int[nrhs]: the iteration right-hand side r stopped in, 0 = still iterating.  Written by the
+                                    // beta launch only and read as an exit condition by every OTHER launch
+    int *live = nullptr;            // int[nrhs]: 0 once the alpha step of a later iteration has seen stop[r]: the exit condition of
+                                    // the beta launch, which must not read the word it writes
+};
 // ten-vector-pass iteration (x update deferred into the aypx launch): see vector.hip
 int launch_axpy_dot(int dtype, int n, const void *q, void *r, long long ld, const void *alpha, int nrhs, void *partials, int grid,
-                    hipStream_t st, int vec_nt = 3);
+                    hipStream_t st, int vec_nt = 3, const CgStop *stop = nullptr);
 int launch_axpy_dot_alpha(int dtype, int n, const void *q, void *r, long long ld, const void *part_dq, int P, const CgScalars &sc,
-                          int nrhs, void *partials, int grid, hipStream_t st);
+                          int nrhs, void *partials, int grid, hipStream_t st, const CgStop *stop = nullptr);
 int launch_aypx_beta_x(int dtype, int n, const void *x, void *y, void *xs, long long ld, const void *partials, int P, int nrhs,
-                       const CgScalars &sc, hipStream_t st, int vec_nt = 3);
+                       const CgScalars &sc, hipStream_t st, int vec_nt = 3, const CgStop *stop = nullptr);
 // small systems: alpha = delta / sum(part_dq) in the prologue (three-launch iteration); fold_alpha_ok says when
 bool fold_alpha_ok(int n_partials, int fold_max = 0);      // fold_max 0 = the default limit (2048 partials)
 // two-launch iteration (spmv.hip "Two-launch iteration"): the SpMV launch computes beta and d_new = beta d_old + r on the
@@ -228,7 +239,7 @@ int launch_axpy2_dot_alpha(int dtype, int n, const void *d, void *x, const void 
 // delta[r] = sum partials ; history[0][r] = delta[r] ; *iter = 0
 int launch_cg_delta0(int dtype, const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st);
 // alpha[r] = delta[r] / sum partials_dq
-int launch_cg_alpha(int dtype, const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st);
+int launch_cg_alpha(int dtype, const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st, const CgStop *stop = nullptr);
 // dn = sum partials_rr ; beta = dn/delta ; delta = dn ; history[++iter] = dn
 int launch_cg_beta(int dtype, const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st);
 
@@ -360,10 +371,10 @@ int p2p_push_chunks(const P2pExchange &e);
 // consecutive right-hand sides (a batched handle: m_r belongs to system r), 0 = one m shared by all
 int launch_pcg_axpy2_dot2(int dtype, bool init, int n, const void *d, void *x, const void *q, void *r, const void *m,
                           long long ld, const void *alpha, int nrhs, void *part_rz, void *part_rr, int grid, hipStream_t st,
-                          long long m_pitch = 0);
+                          long long m_pitch = 0, const CgStop *stop = nullptr);
 int launch_pcg_aypx_beta(int dtype, int n, const void *r, void *p, const void *m, long long ld, const void *part_rz,
                          const void *part_rr, int P, int nrhs, const CgScalars &sc, void *rho2, void *xs, hipStream_t st,
-                         long long m_pitch = 0);
+                         long long m_pitch = 0, const CgStop *stop = nullptr);
 int launch_pcg_p_update(int dtype, int n, const void *r, void *p, const void *m, long long ld, const void *beta, int nrhs, hipStream_t st);
 int launch_pcg_delta0(int dtype, const void *part_rz, const void *part_rr, int P, int nrhs, const CgScalars &sc, void *rho2, hipStream_t st);
 // tridiagonal M (precond.hip): the factors of cgamd_solver_set_preconditioner_tridiag and the chunk plan, device arrays
@@ -384,11 +395,11 @@ int tri_chunk_rows(int dtype);              // C: rows a chunk may span, from th
 int tri_maps_values(int nchunks, int nrhs);
 // r -= alpha q (update; r.r partials) ; z = M^-1 r (r.z partials).  z may be q (in place).  update = false: set_rhs (z0 of r0)
 int launch_pcg_tri(int dtype, const TriLaunch &t, bool update, const void *q, void *r, void *z, long long ld, const void *alpha, int nrhs,
-                   void *part_rz, void *part_rr, hipStream_t st);
+                   void *part_rz, void *part_rr, hipStream_t st, const CgStop *stop = nullptr);
 // the same for the strided form: one thread per segment, a single launch for segments of any length
 int tri_strided_grid(int nsegs);            // work-groups = r.z / r.r partials per RHS (at most 1024)
 int launch_pcg_tri_strided(int dtype, const TriLaunch &t, bool update, const void *q, void *r, void *z, long long ld, const void *alpha,
-                           int nrhs, void *part_rz, void *part_rr, hipStream_t st);
+                           int nrhs, void *part_rz, void *part_rr, hipStream_t st, const CgStop *stop = nullptr);
 // preconditioners built from the matrix on the device (precond_build.hip); n_user = the caller's rows, n = with the padding rows.
 // lower / diag / upper <- the CSR entries at column - row = -stride / 0 / +stride, entries at the same column summed (n_user values)
 // (only columns below col_limit count: the halo columns of a row-partitioned matrix are numbered from n_local on and are no line
@@ -474,7 +485,7 @@ int launch_pcg_aypx_beta_p2p(int dtype, int n, const void *z, void *d, void *x, 
                              hipStream_t st, int vec_nt = 0);
 // pcg_aypx_beta with p = z + beta p (z per right-hand side at stride ld), P thread-strided partials
 int launch_pcg_aypx_beta_z(int dtype, int n, void *p, const void *z, long long ld, const void *part_rz, const void *part_rr, int P, int nrhs,
-                           const CgScalars &sc, void *rho2, void *xs, hipStream_t st);
+                           const CgScalars &sc, void *rho2, void *xs, hipStream_t st, const CgStop *stop = nullptr);
 // four-launch peer-to-peer iteration (see p2p.hip): SpMV with the push and the wait inside, aypx with the beta all-reduce.
 // halo_flag: device int per row block (1 = references a halo column); rotate: first row block of the visiting order
 int launch_spmv_p2p(int dtype, const SpmvPlan &plan, int n, long long nnz, const void *vals, const int *ptr, const int *cols,

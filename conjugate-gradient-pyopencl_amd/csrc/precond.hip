@@ -25,6 +25,7 @@
 #include "device_types.h"
 #include "device_mem.h"
 #include "reduce_device.h"
+#include "stop_device.h"
 #include "launch_util.h"
 
 namespace cgamd {
@@ -87,13 +88,15 @@ CG_DEV void st_rows(T *p, int row0, int lo, int hi, const T (&v)[R]) {
 // grid = (G, nRHS); work-group g takes chunks g, g + G, ... and writes one partial per dot product: P = G partials per RHS.
 // fpitch: values between the factors of consecutive right-hand sides (a batched handle: M_r of system r for right-hand side r); 0 =
 // one M shared by all
-template <typename T, bool VEC, int MODE, bool UPD>
+// GUARD: the instantiation cgamd_solver_iterate_until launches; a right-hand side that has stopped keeps its r, z and partials
+template <typename T, bool VEC, int MODE, bool UPD, bool GUARD = false>
 __global__ __launch_bounds__(kBlock) void pcg_tri_kernel(const int *__restrict__ cstart, int nchunks, const T *__restrict__ nl,
                                                          const T *__restrict__ ne, const T *__restrict__ w, long long fpitch, const T *q, T *rv, T *z,
                                                          long long ld, const T *__restrict__ alpha, typename VT<T>::acc *__restrict__ part_rz,
-                                                         typename VT<T>::acc *__restrict__ part_rr, T *__restrict__ maps) {
+                                                         typename VT<T>::acc *__restrict__ part_rr, T *__restrict__ maps, CgStop gd) {
     using A = typename VT<T>::acc;
     constexpr int R = tri_rows<T>(), NW = kBlock / kWave;
+    if (GUARD && gd.stop[blockIdx.y] != 0) return;
     __shared__ T fa[NW], fb[NW], bp[NW], bu[NW], bv[NW];
     __shared__ A red[NW];
     const int rhs = blockIdx.y, lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
@@ -237,13 +240,27 @@ int tri_maps_values(int nchunks, int nrhs) { return nchunks * nrhs * kTriMaps; }
 
 template <typename T>
 static int tri_impl(const TriLaunch &t, bool update, const void *q, void *r, void *z, long long ld, const void *alpha, int nrhs,
-                    void *part_rz, void *part_rr, bool vec, hipStream_t st) {
+                    void *part_rz, void *part_rr, bool vec, hipStream_t st, const CgStop *stop) {
     using A = typename VT<T>::acc;
     const dim3 g(t.grid, nrhs), blk(kBlock);
     const T *nl = (const T *)t.nl, *ne = (const T *)t.ne, *w = (const T *)t.w;
     T *maps = (T *)t.maps;
-#define CG_TRI(V, M, U) hipLaunchKernelGGL((pcg_tri_kernel<T, V, M, U>), g, blk, 0, st, t.cstart, t.nchunks, nl, ne, w, t.fpitch, (const T *)q, (T *)r, \
-                                           (T *)z, ld, (const T *)alpha, (A *)part_rz, (A *)part_rr, maps)
+    const CgStop none;
+#define CG_TRIG(V, M, U, G) hipLaunchKernelGGL((pcg_tri_kernel<T, V, M, U, G>), g, blk, 0, st, t.cstart, t.nchunks, nl, ne, w, t.fpitch, (const T *)q, (T *)r, \
+                                               (T *)z, ld, (const T *)alpha, (A *)part_rz, (A *)part_rr, maps, G ? *stop : none)
+#define CG_TRI(V, M, U) CG_TRIG(V, M, U, false)
+    if (stop && update) {       // the loop of cgamd_solver_iterate_until (the carry launch in between only rewrites a frozen column's chunk maps)
+        if (!t.longform) {
+            if (vec) CG_TRIG(true, 0, true, true); else CG_TRIG(false, 0, true, true);
+            return check_launch("pcg_tri");
+        }
+        if (vec) CG_TRIG(true, 1, true, true); else CG_TRIG(false, 1, true, true);
+        if (int rc = check_launch("pcg_tri maps")) return rc;
+        hipLaunchKernelGGL((pcg_tri_carry_kernel<T>), dim3((nrhs + 63) / 64), dim3(64), 0, st, t.nchunks, nrhs, maps);
+        if (int rc = check_launch("pcg_tri carry")) return rc;
+        if (vec) CG_TRIG(true, 2, false, true); else CG_TRIG(false, 2, false, true);
+        return check_launch("pcg_tri apply");
+    }
     if (!t.longform) {
         if (update) { if (vec) CG_TRI(true, 0, true); else CG_TRI(false, 0, true); }
         else { if (vec) CG_TRI(true, 0, false); else CG_TRI(false, 0, false); }
@@ -256,12 +273,13 @@ static int tri_impl(const TriLaunch &t, bool update, const void *q, void *r, voi
     if (int rc = check_launch("pcg_tri carry")) return rc;
     if (vec) CG_TRI(true, 2, false); else CG_TRI(false, 2, false);
 #undef CG_TRI
+#undef CG_TRIG
     return check_launch("pcg_tri apply");
 }
 int launch_pcg_tri(int dtype, const TriLaunch &t, bool update, const void *q, void *r, void *z, long long ld, const void *alpha, int nrhs,
-                   void *part_rz, void *part_rr, hipStream_t st) {
+                   void *part_rz, void *part_rr, hipStream_t st, const CgStop *stop) {
     const bool vec = vec_ok(dtype, ld, nrhs, {q, r, z});
-    CG_DISPATCH(dtype, tri_impl, t, update, q, r, z, ld, alpha, nrhs, part_rz, part_rr, vec, st);
+    CG_DISPATCH(dtype, tri_impl, t, update, q, r, z, ld, alpha, nrhs, part_rz, part_rr, vec, st, stop);
 }
 
 }  // namespace cgamd

@@ -23,6 +23,7 @@
 #include "cgamd_internal.h"
 #include "device_types.h"
 #include "reduce_device.h"
+#include "stop_device.h"
 #include "launch_util.h"
 
 namespace cgamd {
@@ -32,17 +33,19 @@ template <typename T> constexpr int tri_strided_rows() { return sizeof(T) == 16 
 
 // grid = (G, nRHS); thread t of the grid takes segments t, t + G kBlock, ...; P = G partials per RHS and dot product.  fpitch: values
 // between the factors of consecutive right-hand sides (a batched handle), 0 = one M shared by all
-template <typename T, bool UPD>
+// GUARD: the instantiation cgamd_solver_iterate_until launches; a right-hand side that has stopped keeps its r, z and partials
+template <typename T, bool UPD, bool GUARD = false>
 __global__ __launch_bounds__(kBlock) void pcg_tri_strided_kernel(const int2 *__restrict__ segs, int nsegs, int stride,
                                                                  const T *__restrict__ nl, const T *__restrict__ ne,
                                                                  const T *__restrict__ w, long long fpitch, const T *q, T *rv, T *z,
                                                                  long long ld,
                                                                  const T *__restrict__ alpha, typename VT<T>::acc *__restrict__ part_rz,
-                                                                 typename VT<T>::acc *__restrict__ part_rr) {
+                                                                 typename VT<T>::acc *__restrict__ part_rr, CgStop gd) {
     using A = typename VT<T>::acc;
     constexpr int U = tri_strided_rows<T>();
     __shared__ A red[kBlock / kWave];
     const int rhs = blockIdx.y;
+    if (GUARD && gd.stop[rhs] != 0) return;
     const long long off = (long long)rhs * ld;
     rv += off; z += off;
     if (UPD) q += off;
@@ -126,19 +129,20 @@ int tri_strided_grid(int nsegs) { return std::max(1, std::min((nsegs + kBlock - 
 
 template <typename T>
 static int tri_strided_impl(const TriLaunch &t, bool update, const void *q, void *r, void *z, long long ld, const void *alpha, int nrhs,
-                            void *part_rz, void *part_rr, hipStream_t st) {
+                            void *part_rz, void *part_rr, hipStream_t st, const CgStop *stop) {
     using A = typename VT<T>::acc;
     const dim3 g(t.grid, nrhs), blk(kBlock);
     const int2 *segs = reinterpret_cast<const int2 *>(t.segs);
-#define CG_TRIS(U) hipLaunchKernelGGL((pcg_tri_strided_kernel<T, U>), g, blk, 0, st, segs, t.nsegs, t.stride, (const T *)t.nl, (const T *)t.ne, \
-                                      (const T *)t.w, t.fpitch, (const T *)q, (T *)r, (T *)z, ld, (const T *)alpha, (A *)part_rz, (A *)part_rr)
-    if (update) CG_TRIS(true); else CG_TRIS(false);
+    const CgStop none;
+#define CG_TRIS(U, G) hipLaunchKernelGGL((pcg_tri_strided_kernel<T, U, G>), g, blk, 0, st, segs, t.nsegs, t.stride, (const T *)t.nl, (const T *)t.ne, \
+                                         (const T *)t.w, t.fpitch, (const T *)q, (T *)r, (T *)z, ld, (const T *)alpha, (A *)part_rz, (A *)part_rr, G ? *stop : none)
+    if (update && stop) CG_TRIS(true, true); else if (update) CG_TRIS(true, false); else CG_TRIS(false, false);
 #undef CG_TRIS
     return check_launch("pcg_tri_strided");
 }
 int launch_pcg_tri_strided(int dtype, const TriLaunch &t, bool update, const void *q, void *r, void *z, long long ld, const void *alpha,
-                           int nrhs, void *part_rz, void *part_rr, hipStream_t st) {
-    CG_DISPATCH(dtype, tri_strided_impl, t, update, q, r, z, ld, alpha, nrhs, part_rz, part_rr, st);
+                           int nrhs, void *part_rz, void *part_rr, hipStream_t st, const CgStop *stop) {
+    CG_DISPATCH(dtype, tri_strided_impl, t, update, q, r, z, ld, alpha, nrhs, part_rz, part_rr, st, stop);
 }
 
 }  // namespace cgamd

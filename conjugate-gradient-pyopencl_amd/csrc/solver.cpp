@@ -100,6 +100,19 @@ struct cgamd_solver {
     // cgamd_solver_iterate_tol: tolerance of the device-side stop for the call in progress (0 = none), and what it reported
     double tol_req = 0.;
     bool tol_served = false, tol_stopped = false;
+    // cgamd_solver_iterate_until: the device record of the per-right-hand-side stop (CgStop: allocated at the first call, armed once
+    // per set_rhs), its pinned host mirror, and the captured chunk of guarded iterations.  until_mode: since the first call after
+    // set_rhs the handle runs its three / four-launch loop only (d in one buffer, updated at the end of every iteration);
+    // until_stopped: a right-hand side has stopped, so the columns are at different iterations and only iterate_until goes on.
+    void *stop_rec = nullptr;
+    CgStop stop;
+    bool stop_armed = false, until_mode = false, until_stopped = false;
+    std::vector<int> stop_host;     // stop[] as the last call read it
+    int *until_pin = nullptr;       // pinned: [0..1] the active counts of the chunks in flight, [2] *iter, [3..] stop[], then the record image
+    hipEvent_t until_ev[2] = {nullptr, nullptr};
+    hipGraphExec_t gT = nullptr;
+    hipGraph_t gTg = nullptr;
+    int gT_len = 0;
 };
 
 static void destroy_graphs(cgamd_solver *s) {
@@ -111,6 +124,9 @@ static void destroy_graphs(cgamd_solver *s) {
         s->g1[p] = s->gU[p] = nullptr;
         s->g1g[p] = s->gUg[p] = nullptr;
     }
+    if (s->gT) (void)hipGraphExecDestroy(s->gT);
+    if (s->gTg) (void)hipGraphDestroy(s->gTg);
+    s->gT = nullptr; s->gTg = nullptr; s->gT_len = 0;
 }
 
 static int dmalloc(void **p, size_t bytes, const char *what) {
@@ -131,12 +147,12 @@ static int validate_csr_host(int n, long long nnz, const int *ptr, const int *co
 }
 
 // the SpMV (SpMM) launch of the iteration, bracketed by the caller's event pair when one is installed
-static void *dbuf(cgamd_solver *s, int k) { return (s->fused2 && (k & 1)) ? s->d2 : s->d; }
+static void *dbuf(cgamd_solver *s, int k) { return (s->fused2 && !s->until_mode && (k & 1)) ? s->d2 : s->d; }
 // a preconditioner (diagonal or tridiagonal) is set: what decides the loop family; s->mdiag is read where the diagonal is used
 static bool precond_set(const cgamd_solver *s) { return s->mdiag != nullptr || s->tri_on; }
 // values between the diagonals of consecutive right-hand sides in s->mdiag: a batched handle keeps one per system, else one for all
 static long long m_pitch(const cgamd_solver *s) { return s->nsys ? s->n : 0; }
-static bool fused2_now(const cgamd_solver *s) { return s->fused2 && !s->rm && !precond_set(s) && !(s->flags & CGAMD_UNFUSED); }
+static bool fused2_now(const cgamd_solver *s) { return s->fused2 && !s->rm && !precond_set(s) && !(s->flags & CGAMD_UNFUSED) && !s->until_mode; }
 
 // the handle's SpMV on n rows of RHS-major vectors: the batched kernel where every right-hand side has a matrix of its own
 static int handle_spmv(cgamd_solver *s, int n, const void *x, long long ldx, void *y, long long ldy, const void *dvec, void *partials,
@@ -224,6 +240,36 @@ static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st) {
     if ((rc = launch_dot_partials(dt, n, s->r, s->r, n, nr, s->part_rr, s->vgrid, st))) return rc;
     if ((rc = launch_cg_beta(dt, s->part_rr, s->vgrid, nr, s->sc, st))) return rc;
     return launch_aypx(dt, n, s->r, s->d, n, s->sc.beta, nr, st);
+}
+
+// One iteration of cgamd_solver_iterate_until: the three / four-launch loop of enqueue_iteration for the handle's preconditioner, with
+// the guarded instantiation of every kernel that writes x, r, d, a scalar, the history or the counter (stop_device.h).  The SpMV is
+// the unguarded one: q of a frozen right-hand side is recomputed from its frozen d and read by nothing.
+static int enqueue_iteration_until(cgamd_solver *s, hipStream_t st) {
+    const int dt = s->dtype, n = s->n, nr = s->nrhs;
+    const CgStop *g = &s->stop;
+    int rc;
+    if ((rc = handle_spmv(s, n, s->d, n, s->q, n, s->d, s->part_dq, st))) return rc;
+    if (s->tri_on) {
+        if ((rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st, g))) return rc;
+        void *prz = s->tri_part, *prr = static_cast<char *>(s->tri_part) + acc_size(dt) * (size_t)s->tri.grid * nr;
+        if (s->tri.stride > 1) rc = launch_pcg_tri_strided(dt, s->tri, true, s->q, s->r, s->q, n, s->sc.alpha, nr, prz, prr, st, g);
+        else rc = launch_pcg_tri(dt, s->tri, true, s->q, s->r, s->q, n, s->sc.alpha, nr, prz, prr, st, g);
+        if (rc) return rc;
+        return launch_pcg_aypx_beta_z(dt, n, s->d, s->q, n, prz, prr, s->tri.grid, nr, s->sc, s->rho2, s->x, st, g);
+    }
+    if (s->mdiag) {
+        if ((rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st, g))) return rc;
+        if ((rc = launch_pcg_axpy2_dot2(dt, false, n, s->d, s->x, s->q, s->r, s->mdiag, n, s->sc.alpha, nr, s->part_rz, s->part_rr, s->vgrid, st,
+                                        m_pitch(s), g))) return rc;
+        return launch_pcg_aypx_beta(dt, n, s->r, s->d, s->mdiag, n, s->part_rz, s->part_rr, s->vgrid, nr, s->sc, s->rho2, s->x, st, m_pitch(s), g);
+    }
+    const bool fold = fold_alpha_ok(s->plan.n_partials, s->plan.fold_max);
+    if (!fold && (rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st, g))) return rc;
+    if (fold) rc = launch_axpy_dot_alpha(dt, n, s->q, s->r, n, s->part_dq, s->plan.n_partials, s->sc, nr, s->part_rr, s->vgrid, st, g);
+    else rc = launch_axpy_dot(dt, n, s->q, s->r, n, s->sc.alpha, nr, s->part_rr, s->vgrid, st, s->plan.vec_nt, g);
+    if (rc) return rc;
+    return launch_aypx_beta_x(dt, n, s->r, s->d, s->x, n, s->part_rr, s->vgrid, nr, s->sc, st, s->plan.vec_nt, g);
 }
 
 // the resident loop applies where the two-launch loop does and the matrix slices fit LDS (needs the row pointers on the host)
@@ -357,12 +403,12 @@ static int setup_resident_one_xcd(cgamd_solver *s) {
     return CGAMD_OK;
 }
 
-static int capture(cgamd_solver *s, int k0, int iters, hipGraph_t *g, hipGraphExec_t *ge) {
+static int capture(cgamd_solver *s, int k0, int iters, hipGraph_t *g, hipGraphExec_t *ge, bool guarded = false) {
     hipStream_t st = s->ctx->stream;
     hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
     if (e != hipSuccess) return fail(CGAMD_ERR_HIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(e));
     int rc = CGAMD_OK;
-    for (int i = 0; i < iters && rc == CGAMD_OK; ++i) rc = enqueue_iteration(s, k0 + i, st);
+    for (int i = 0; i < iters && rc == CGAMD_OK; ++i) rc = guarded ? enqueue_iteration_until(s, st) : enqueue_iteration(s, k0 + i, st);
     e = hipStreamEndCapture(st, g);
     if (rc != CGAMD_OK) return rc;
     if (e != hipSuccess) return fail(CGAMD_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
@@ -636,6 +682,10 @@ int cgamd_solver_destroy(cgamd_solver *s) {
                     s->sc.history, s->sc.iter, s->mdiag, s->part_rz, s->rho2, s->tri_coef, s->tri_part, s->tri_cstart, s->tri.maps, s->sc.stage, s->sc.ticket, s->res_sync, s->resw_sync, s->codes, s->dict, s->rm_pace, s->vcodes, s->vdict, s->jcodes, s->jdict_off, s->jdict_val};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
+    if (s->stop_rec) (void)hipFree(s->stop_rec);
+    if (s->until_pin) (void)hipHostFree(s->until_pin);
+    for (hipEvent_t e : s->until_ev)
+        if (e) (void)hipEventDestroy(e);
     delete s;
     return CGAMD_OK;
 }
@@ -649,6 +699,8 @@ int cgamd_solver_set_rhs(cgamd_solver *s, const void *b, const void *x0, int on_
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     const bool rm = s->rm_ok && !precond_set(s);      // the preconditioned recurrence keeps the RHS-major kernels
     if (rm != s->rm) destroy_graphs(s);         // captured launch sequences belong to one layout
+    if (s->until_mode && s->fused2) destroy_graphs(s);      // (captured while the two-launch loop was set aside: iterate_until)
+    s->until_mode = s->until_stopped = s->stop_armed = false;
     s->rm = rm;
     int rc;
     if (rm) {
@@ -927,13 +979,14 @@ int cgamd_solver_iterate(cgamd_solver *s, int nIterations) {
     TuneScope ts(&s->tune);
     if (!s->rhs_set) return fail(CGAMD_ERR_STATE, "iterate: call set_rhs first");
     if (nIterations < 0) return fail(CGAMD_ERR_INVALID, "iterate: negative iteration count");
+    if (s->until_stopped) return fail(CGAMD_ERR_STATE, "iterate: iterate_until has stopped a right-hand side (the columns are at different iterations): go on with iterate_until, or call set_rhs");
     CG_HIP(hipSetDevice(s->ctx->device));
     if (int rc = ensure_history(s, s->iters + nIterations + 1)) return rc;
     hipStream_t st = s->ctx->stream;
     int left = nIterations, k = s->iters;
     const bool use_graph = !(s->flags & CGAMD_NO_GRAPH) && !s->graph_failed;
     const bool two = fused2_now(s);
-    if (s->resw.ok && !s->tri_on && !(two && s->res_ok) && !s->rm && !(s->flags & (CGAMD_NO_GRAPH | CGAMD_UNFUSED)) &&
+    if (s->resw.ok && !s->until_mode && !s->tri_on && !(two && s->res_ok) && !s->rm && !(s->flags & (CGAMD_NO_GRAPH | CGAMD_UNFUSED)) &&
         (nIterations >= std::max(1, tune().resident_wide_min) || s->tol_req > 0.)) {
         // one chip-wide resident group (single right-hand side, matrix rows in registers).  d ping-pongs inside the launch; handles
         // of the launched loops that keep d in one buffer get it back there, and the launched loops' r.r partials are rebuilt.
@@ -1044,6 +1097,7 @@ int cgamd_solver_iterate_tol(cgamd_solver *s, int maxIterations, double tol, int
     if (s->nsys) return fail(CGAMD_ERR_STATE, "iterate_tol: a batched handle runs a launched loop (check the history from the host)");
     if (!s->rhs_set) return fail(CGAMD_ERR_STATE, "iterate_tol: call set_rhs first");
     if (s->nrhs != 1) return fail(CGAMD_ERR_STATE, "iterate_tol: one right-hand side");
+    if (s->until_mode) return fail(CGAMD_ERR_STATE, "iterate_tol: iterate_until runs this right-hand side on the launched loop until the next set_rhs");
     {
         TuneScope ts(&s->tune);
         const bool local = fused2_now(s) && s->res_ok, wide = s->resw.ok && !s->tri_on && !s->rm && !(s->res_ok && !precond_set(s));
@@ -1062,6 +1116,123 @@ int cgamd_solver_iterate_tol(cgamd_solver *s, int maxIterations, double tol, int
     return CGAMD_OK;
 }
 
+
+// Per-right-hand-side tolerance stop ON THE DEVICE for the launched loops (include/cgamd.h): every right-hand side stops in the
+// first iteration whose sqrt|r.r| fails >= tol[r] and is frozen there while the others run on -- the reference's sub-domain loop
+// `r[p] = CG(P[0], z[p].ravel(), tol=CGtol, maxit=CGMaxIT)` (p_h-PY_C-CL.py:1916-1921, 1338-1369) as ONE batched solve.  The
+// host enqueues chunks of checkEvery iterations and, after each, an asynchronous read of the record's active count; it waits for
+// the count of chunk c - 1 only once chunk c is in the stream, so the device never idles on the host, and it never waits per
+// iteration.  Iterations enqueued after the last stop change nothing on the device (stop_device.h), so the result does not depend
+// on checkEvery, and until(a); until(b) leaves the bits of until(a + b).
+int cgamd_solver_iterate_until(cgamd_solver *s, int maxIterations, const double *tol, int nTol, int checkEvery, int *iterations_run) {
+    // (what can be judged without the handle comes first)
+    if (maxIterations < 0 || checkEvery < 0) return fail(CGAMD_ERR_INVALID, "iterate_until: negative maxIterations or checkEvery");
+    if (nTol < 1) return fail(CGAMD_ERR_INVALID, "iterate_until: nTol must be 1 or nRHS");
+    if (!s || !tol || !iterations_run) return fail(CGAMD_ERR_INVALID, "iterate_until: NULL solver, tol or iterations_run");
+    if (nTol != 1 && nTol != s->nrhs) return fail(CGAMD_ERR_INVALID, "iterate_until: nTol must be 1 or nRHS");
+    for (int i = 0; i < nTol; ++i)
+        if (!(tol[i] > 0.)) return fail(CGAMD_ERR_INVALID, "iterate_until: every tolerance must be positive");
+    TuneScope ts(&s->tune);
+    if (!s->rhs_set) return fail(CGAMD_ERR_STATE, "iterate_until: call set_rhs first");
+    if (s->rm) return fail(CGAMD_ERR_STATE, "iterate_until: the handle keeps its right-hand sides interleaved (row-major layout)");
+    if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, "iterate_until: CGAMD_UNFUSED replays the reference's kernel sequence, which has no guarded form");
+    const int nr = s->nrhs;
+    if (maxIterations == 0) {
+        for (int r = 0; r < nr; ++r) iterations_run[r] = (s->stop_armed && s->stop_host[r]) ? s->stop_host[r] : s->iters;
+        return CGAMD_OK;
+    }
+    CG_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    // the record: [nactive, pad x3] [tol: nr doubles] [stop: nr ints] [live: nr ints]
+    const size_t rec_bytes = 16 + (size_t)nr * 16;
+    const size_t pin_ints = 4 + (size_t)nr + (size_t)(nr & 1);     // the record image follows, 8-byte aligned
+    if (!s->stop_rec) {
+        if (int rc = dmalloc(&s->stop_rec, rec_bytes, "stop record")) return rc;
+        char *base = static_cast<char *>(s->stop_rec);
+        s->stop.nactive = reinterpret_cast<int *>(base);
+        s->stop.tol = reinterpret_cast<const double *>(base + 16);
+        s->stop.stop = reinterpret_cast<int *>(base + 16 + (size_t)nr * 8);
+        s->stop.live = s->stop.stop + nr;
+        CG_HIP(hipHostMalloc((void **)&s->until_pin, pin_ints * 4 + rec_bytes, hipHostMallocDefault));
+        for (hipEvent_t &e : s->until_ev) CG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        s->stop_host.assign((size_t)nr, 0);
+    }
+    if (int rc = ensure_history(s, s->iters + maxIterations + 1)) return rc;
+    if (!s->until_mode) {       // from here to the next set_rhs the handle runs its three / four-launch loop
+        if (fused2_now(s) && s->iters > 0) {
+            // the two-launch loop (and the resident loops that stand in for it) leave d = beta d + r of the last iteration to the
+            // next SpMV launch: done here with the beta that iteration recorded, the very expression (vaypx), into the one buffer
+            void *cur = dbuf(s, s->iters);
+            if (int rc = launch_aypx(s->dtype, s->n, s->r, cur, s->n, s->sc.beta, nr, st)) return rc;
+            if (cur != s->d) CG_HIP(hipMemcpyAsync(s->d, cur, (size_t)s->n * nr * dtype_size(s->dtype), hipMemcpyDeviceToDevice, st));
+        }
+        if (s->fused2) destroy_graphs(s);       // captured per parity of the two-launch loop
+        s->until_mode = true;
+    }
+    {                           // arm once per set_rhs; the tolerances of this call (a stopped right-hand side stays stopped whatever they are)
+        char *img = reinterpret_cast<char *>(s->until_pin + pin_ints);
+        double *tl = reinterpret_cast<double *>(img + 16);
+        for (int r = 0; r < nr; ++r) tl[r] = tol[nTol == 1 ? 0 : r];
+        if (!s->stop_armed) {
+            int *hd = reinterpret_cast<int *>(img), *sp = reinterpret_cast<int *>(img + 16 + (size_t)nr * 8);
+            hd[0] = nr; hd[1] = hd[2] = hd[3] = 0;
+            for (int r = 0; r < nr; ++r) { sp[r] = 0; sp[nr + r] = 1; }
+            CG_HIP(hipMemcpyAsync(s->stop_rec, img, rec_bytes, hipMemcpyHostToDevice, st));
+            std::fill(s->stop_host.begin(), s->stop_host.end(), 0);
+            s->stop_armed = true;
+        } else {
+            CG_HIP(hipMemcpyAsync(static_cast<char *>(s->stop_rec) + 16, tl, (size_t)nr * 8, hipMemcpyHostToDevice, st));
+        }
+    }
+    const int chunk = checkEvery ? checkEvery : 8;
+    const bool use_graph = !(s->flags & CGAMD_NO_GRAPH) && !s->graph_failed;
+    volatile int *active = s->until_pin;
+    int rc = CGAMD_OK, enq = 0;
+    bool none_left = false;
+    for (int c = 0; enq < maxIterations && !none_left && !rc; ++c) {
+        const int len = std::min(chunk, maxIterations - enq);
+        bool replayed = false;
+        if (use_graph && !s->graph_failed && len == chunk) {
+            if (s->gT && s->gT_len != chunk) {
+                (void)hipGraphExecDestroy(s->gT); (void)hipGraphDestroy(s->gTg);
+                s->gT = nullptr; s->gTg = nullptr;
+            }
+            if (!s->gT) {
+                if (capture(s, 0, chunk, &s->gTg, &s->gT, true) == CGAMD_OK) s->gT_len = chunk;
+                else { s->graph_failed = true; destroy_graphs(s); }
+            }
+            if (s->gT) {
+                CG_HIP(hipGraphLaunch(s->gT, st));
+                replayed = true;
+            }
+        }
+        for (int i = 0; i < len && !replayed && !rc; ++i) rc = enqueue_iteration_until(s, st);
+        if (rc) break;
+        enq += len;
+        CG_HIP(hipMemcpyAsync(s->until_pin + (c & 1), s->stop.nactive, sizeof(int), hipMemcpyDeviceToHost, st));
+        CG_HIP(hipEventRecord(s->until_ev[c & 1], st));
+        if (c > 0) {            // chunk c is in the stream: now the count chunk c - 1 left
+            CG_HIP(hipEventSynchronize(s->until_ev[(c - 1) & 1]));
+            none_left = active[(c - 1) & 1] == 0;
+        }
+    }
+    if (rc) {                   // part of an iteration may be in the stream: the handle demands a fresh set_rhs
+        (void)hipStreamSynchronize(st);
+        s->rhs_set = false;
+        return rc;
+    }
+    CG_HIP(hipMemcpyAsync(s->until_pin + 2, s->sc.iter, sizeof(int), hipMemcpyDeviceToHost, st));
+    CG_HIP(hipMemcpyAsync(s->until_pin + 3, s->stop.stop, sizeof(int) * (size_t)nr, hipMemcpyDeviceToHost, st));
+    CG_HIP(hipStreamSynchronize(st));
+    s->iters = s->until_pin[2];
+    for (int r = 0; r < nr; ++r) {
+        s->stop_host[r] = s->until_pin[3 + r];
+        if (s->stop_host[r]) s->until_stopped = true;
+        iterations_run[r] = s->stop_host[r] ? s->stop_host[r] : s->iters;
+    }
+    return CGAMD_OK;
+}
+
 // nIterations plain-launch iterations of the SAME launch sequence cgamd_solver_iterate replays (enqueue_iteration), with a
 // HIP event pair around every SpMV launch on the solver's stream: the in-loop duration of the dominant kernel
 // (bench.py's roofline).  Synchronises.
@@ -1070,6 +1241,7 @@ int cgamd_solver_iterate_timed(cgamd_solver *s, int nIterations, float *spmv_ms_
     TuneScope ts(&s->tune);
     if (!s->rhs_set) return fail(CGAMD_ERR_STATE, "iterate_timed: call set_rhs first");
     if (nIterations < 1) return fail(CGAMD_ERR_INVALID, "iterate_timed: needs >= 1 iteration");
+    if (s->until_stopped) return fail(CGAMD_ERR_STATE, "iterate_timed: iterate_until has stopped a right-hand side: go on with iterate_until, or call set_rhs");
     CG_HIP(hipSetDevice(s->ctx->device));
     if (int rc = ensure_history(s, s->iters + nIterations + 1)) return rc;
     hipStream_t st = s->ctx->stream;

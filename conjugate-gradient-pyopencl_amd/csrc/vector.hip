@@ -16,6 +16,7 @@
 #include "device_mem.h"
 #include "spmv_device.h"
 #include "reduce_device.h"
+#include "stop_device.h"
 #include "launch_util.h"
 
 #include <hip/hip_ext.h>
@@ -147,22 +148,33 @@ CG_DEV void axpy_dot_body(int n, const T *__restrict__ q, T *__restrict__ rv, lo
     const A tot = block_sum<BLOCK>(acc, red);
     if (threadIdx.x == 0) partials[(long long)r * gridDim.x + blockIdx.x] = tot;
 }
-template <typename T, int BLOCK, bool VEC, int VNT = 0>
+// GUARD (here and below): the instantiation cgamd_solver_iterate_until launches -- a right-hand side that has stopped is left alone
+// (stop_device.h); GUARD = false is the code of cgamd_solver_iterate
+template <typename T, int BLOCK, bool VEC, int VNT = 0, bool GUARD = false>
 __global__ __launch_bounds__(BLOCK) void axpy_dot_kernel(int n, const T *__restrict__ q, T *__restrict__ rv, long long ld,
-                                                         const T *__restrict__ alpha, typename VT<T>::acc *__restrict__ partials) {
+                                                         const T *__restrict__ alpha, typename VT<T>::acc *__restrict__ partials,
+                                                         CgStop g) {
     __shared__ typename VT<T>::acc red[BLOCK / kWave];
+    if (GUARD && g.stop[blockIdx.y] != 0) return;
     axpy_dot_body<T, BLOCK, VEC, VNT>(n, q, rv, ld, alpha[blockIdx.y], partials, red);
 }
 // small systems: alpha in the prologue (see axpy2_dot_alpha_kernel)
-template <typename T, int BLOCK, bool VEC>
+template <typename T, int BLOCK, bool VEC, bool GUARD = false>
 __global__ __launch_bounds__(BLOCK) void axpy_dot_alpha_kernel(int n, const T *__restrict__ q, T *__restrict__ rv, long long ld,
                                                                const typename VT<T>::acc *__restrict__ part_dq, int P, int K,
                                                                const T *__restrict__ delta, T *alpha, int *iter,
-                                                               typename VT<T>::acc *__restrict__ partials) {
+                                                               typename VT<T>::acc *__restrict__ partials, CgStop g) {
     using A = typename VT<T>::acc;
     __shared__ A red[BLOCK / kWave];
     __shared__ T alpha_s;
     const int r = blockIdx.y;
+    if (GUARD) {        // the alpha step of this iteration: the counter, then the frozen right-hand sides leave (nothing here writes stop[])
+        if (blockIdx.x == 0 && threadIdx.x == 0 && r == 0) stop_advance(g, iter);
+        if (g.stop[r] != 0) {
+            if (blockIdx.x == 0 && threadIdx.x == 0) stop_retire(g, r);
+            return;
+        }
+    }
     {
         const A acc = thread_partials<BLOCK>(part_dq + (long long)r * P, P, K);
         const A dq = block_sum<BLOCK>(acc, red);
@@ -172,7 +184,7 @@ __global__ __launch_bounds__(BLOCK) void axpy_dot_alpha_kernel(int n, const T *_
             alpha_s = al;
             if (blockIdx.x == 0) {
                 alpha[r] = al;
-                if (r == 0) *iter = *iter + 1;
+                if (!GUARD && r == 0) *iter = *iter + 1;
             }
         }
         __syncthreads();
@@ -290,15 +302,19 @@ __global__ __launch_bounds__(BLOCK) void aypx_beta_kernel(int n, const T *__rest
 }
 
 // the same with the deferred x += alpha d (ten-vector-pass iteration): xs = solution vector, alpha of THIS iteration
-template <typename T, int BLOCK, bool VEC, int VNT>
+template <typename T, int BLOCK, bool VEC, int VNT, bool GUARD = false>
 __global__ __launch_bounds__(BLOCK) void aypx_beta_x_kernel(int n, const T *__restrict__ x, T *__restrict__ y, T *__restrict__ xs,
                                                             long long ld, const typename VT<T>::acc *__restrict__ partials, int P, int K,
                                                             int nrhs, const T *__restrict__ alpha, T *delta, T *beta, T *history,
-                                                            int history_cap, const int *iter) {
+                                                            int history_cap, const int *iter, CgStop g) {
     using A = typename VT<T>::acc;
     __shared__ A red[BLOCK / kWave];
     __shared__ T beta_s;
     const int r = blockIdx.y;
+    if (GUARD && g.live[r] == 0) {      // frozen before this iteration (live[] is written by the alpha step only)
+        if (blockIdx.x == 0 && threadIdx.x == 0) stop_repeat_history(g, r, *iter, nrhs, history, history_cap);
+        return;
+    }
     {
         const A acc = thread_partials<BLOCK>(partials + (long long)r * P, P, K);
         const A tot = block_sum<BLOCK>(acc, red);
@@ -312,6 +328,7 @@ __global__ __launch_bounds__(BLOCK) void aypx_beta_x_kernel(int n, const T *__re
                 beta[r] = b;
                 delta[r] = dnT;
                 if (it < history_cap) history[(long long)it * nrhs + r] = dnT;
+                if (GUARD) stop_decide(g, r, it, dnT);      // the updates below belong to this iteration whatever is decided
             }
         }
         __syncthreads();
@@ -355,17 +372,18 @@ __global__ __launch_bounds__(BLOCK) void aypx_beta_x_kernel(int n, const T *__re
 // side at m + r * mp (a batched handle: the diagonal of system r).  rho of the previous
 // iteration is read from a two-entry parity buffer so that work-group 0 may publish the new one in the same launch.
 // =================================================================================================
-template <typename T, int BLOCK, bool VEC, bool INIT>
+template <typename T, int BLOCK, bool VEC, bool INIT, bool GUARD = false>
 __global__ __launch_bounds__(BLOCK) void pcg_axpy2_dot2_kernel(int n, const T *__restrict__ d, T *__restrict__ x,
                                                                const T *__restrict__ q, T *__restrict__ rv,
                                                                const T *__restrict__ m, long long mp, long long ld,
                                                                const T *__restrict__ alpha,
                                                                typename VT<T>::acc *__restrict__ part_rz,
-                                                               typename VT<T>::acc *__restrict__ part_rr) {
+                                                               typename VT<T>::acc *__restrict__ part_rr, CgStop g) {
     // INIT: no update, d = m r instead (set_rhs: p0 = z0), same two dot products
     using A = typename VT<T>::acc;
     __shared__ A red[BLOCK / kWave];
     const int r = blockIdx.y;
+    if (GUARD && g.stop[r] != 0) return;
     T *dw = const_cast<T *>(d) + (long long)r * ld;
     d += (long long)r * ld; x += (long long)r * ld; q += (long long)r * ld; rv += (long long)r * ld;
     m += (long long)r * mp;
@@ -414,17 +432,21 @@ __global__ __launch_bounds__(BLOCK) void pcg_axpy2_dot2_kernel(int n, const T *_
 }
 
 // ZV (tridiagonal M, precond.hip): m is z itself, one vector per right-hand side like r (mp = ld), and p = z + beta p
-template <typename T, int BLOCK, bool VEC, bool ZV = false>
+template <typename T, int BLOCK, bool VEC, bool ZV = false, bool GUARD = false>
 __global__ __launch_bounds__(BLOCK) void pcg_aypx_beta_kernel(int n, const T *__restrict__ rv, T *__restrict__ pv,
                                                               const T *__restrict__ m, long long mp, long long ld,
                                                               const typename VT<T>::acc *__restrict__ part_rz,
                                                               const typename VT<T>::acc *__restrict__ part_rr, int P, int K, int nrhs,
                                                               T *delta, T *beta, T *history, int history_cap, T *rho2, const int *iter,
-                                                              T *__restrict__ xs, const T *__restrict__ alpha) {
+                                                              T *__restrict__ xs, const T *__restrict__ alpha, CgStop g) {
     using A = typename VT<T>::acc;
     __shared__ A red[BLOCK / kWave];
     __shared__ T beta_s;
     const int r = blockIdx.y;
+    if (GUARD && g.live[r] == 0) {      // frozen before this iteration: rho, its parity buffer and p stay what the stopping iteration left
+        if (blockIdx.x == 0 && threadIdx.x == 0) stop_repeat_history(g, r, *iter, nrhs, history, history_cap);
+        return;
+    }
     {
         const A acc = thread_partials<BLOCK>(part_rz + (long long)r * P, P, K);
         const A rho = block_sum<BLOCK>(acc, red);
@@ -444,6 +466,7 @@ __global__ __launch_bounds__(BLOCK) void pcg_aypx_beta_kernel(int n, const T *__
                 delta[r] = rhoT;                                   // cg_alpha divides this by p.q
                 rho2[(long long)(it & 1) * nrhs + r] = rhoT;
                 if (it < history_cap) history[(long long)it * nrhs + r] = from_acc<T>(acc2);   // r.r: what the stopping test looks at
+                if (GUARD) stop_decide(g, r, it, from_acc<T>(acc2));
             }
         }
         __syncthreads();
@@ -533,17 +556,24 @@ __global__ __launch_bounds__(kScalarBlock) void cg_delta0_kernel(const typename 
 
 // alpha[r] = delta[r] / (d.q)[r].  Block 0 also advances the iteration counter: the counter is only READ by
 // the cg_beta kernel of the same iteration (a later launch), never inside this launch.
-template <typename T>
+template <typename T, bool GUARD = false>
 __global__ __launch_bounds__(kScalarBlock) void cg_alpha_kernel(const typename VT<T>::acc *partials, int grid, int K, int nrhs,
-                                                       const T *delta, T *alpha, int *iter) {
+                                                       const T *delta, T *alpha, int *iter, CgStop g) {
     __shared__ typename VT<T>::acc smem[kScalarBlock / kWave];
     const int r = blockIdx.x;
+    if (GUARD) {        // (see axpy_dot_alpha_kernel)
+        if (threadIdx.x == 0 && r == 0) stop_advance(g, iter);
+        if (g.stop[r] != 0) {
+            if (threadIdx.x == 0) stop_retire(g, r);
+            return;
+        }
+    }
     const auto dq = sum_partials_block(partials + (long long)r * grid, grid, smem, K);
     if (threadIdx.x == 0) {
         // the reference rounds dq to the value type before dividing (clcg.c:318-327)
         const T dqT = from_acc<T>(dq);
         alpha[r] = from_acc<T>(acc_div(to_acc(delta[r]), to_acc(dqT)));
-        if (r == 0) *iter = *iter + 1;
+        if (!GUARD && r == 0) *iter = *iter + 1;
     }
 }
 
@@ -552,14 +582,21 @@ __global__ __launch_bounds__(kScalarBlock) void cg_alpha_kernel(const typename V
 // the scalar step -- the result does not depend on which work-group came last.  One work-group needed 5 rounds of 8 loads
 // per thread (8 us); this needs one (4.5 us).
 constexpr int kAlphaParts = 32;
-template <typename T>
+template <typename T, bool GUARD = false>
 __global__ __launch_bounds__(kScalarBlock) void cg_alpha2_kernel(const typename VT<T>::acc *partials, int grid, int nrhs,
                                                         const T *delta, T *alpha, int *iter,
-                                                        typename VT<T>::acc *stage, unsigned *ticket) {
+                                                        typename VT<T>::acc *stage, unsigned *ticket, CgStop g) {
     using A = typename VT<T>::acc;
     __shared__ A smem[kScalarBlock / kWave];
     __shared__ bool last;
     const int r = blockIdx.y, part = blockIdx.x;
+    if (GUARD) {        // all kAlphaParts work-groups of a right-hand side read the same stop[r]: none or all of them take a ticket
+        if (part == 0 && threadIdx.x == 0 && r == 0) stop_advance(g, iter);
+        if (g.stop[r] != 0) {
+            if (part == 0 && threadIdx.x == 0) stop_retire(g, r);
+            return;
+        }
+    }
     const int per = (grid + kAlphaParts - 1) / kAlphaParts;
     const int lo = min(part * per, grid), hi = min(lo + per, grid);
     const A sum = sum_partials_block(partials + (long long)r * grid + lo, hi - lo, smem);
@@ -579,7 +616,7 @@ __global__ __launch_bounds__(kScalarBlock) void cg_alpha2_kernel(const typename 
             }
             const T dqT = from_acc<T>(from_acc2<A>(tot));
             alpha[r] = from_acc<T>(acc_div(to_acc(delta[r]), to_acc(dqT)));
-            if (r == 0) *iter = *iter + 1;
+            if (!GUARD && r == 0) *iter = *iter + 1;
         }
     }
 }
@@ -711,51 +748,61 @@ static int axpy2_alpha_impl(int n, const void *d, void *x, const void *q, void *
 }
 template <typename T>
 static int axpy_dot_impl(int n, const void *q, void *r, long long ld, const void *alpha, int nrhs, void *partials, int grid, bool vec,
-                         int vnt, hipStream_t st) {
+                         int vnt, hipStream_t st, const CgStop *stop) {
     dim3 g(grid, nrhs), blk(kBlock);
     auto *pp = static_cast<typename VT<T>::acc *>(partials);
-    if (vec && (vnt & 2)) hipLaunchKernelGGL((axpy_dot_kernel<T, kBlock, true, 2>), g, blk, 0, st, n, (const T *)q, (T *)r, ld, (const T *)alpha, pp);
-    else if (vec) hipLaunchKernelGGL((axpy_dot_kernel<T, kBlock, true, 0>), g, blk, 0, st, n, (const T *)q, (T *)r, ld, (const T *)alpha, pp);
-    else hipLaunchKernelGGL((axpy_dot_kernel<T, kBlock, false, 0>), g, blk, 0, st, n, (const T *)q, (T *)r, ld, (const T *)alpha, pp);
+    const CgStop none;
+#define CG_AD(V, N, G) hipLaunchKernelGGL((axpy_dot_kernel<T, kBlock, V, N, G>), g, blk, 0, st, n, (const T *)q, (T *)r, ld, (const T *)alpha, pp, G ? *stop : none)
+    if (stop) { if (vec && (vnt & 2)) CG_AD(true, 2, true); else if (vec) CG_AD(true, 0, true); else CG_AD(false, 0, true); }
+    else if (vec && (vnt & 2)) CG_AD(true, 2, false);
+    else if (vec) CG_AD(true, 0, false);
+    else CG_AD(false, 0, false);
+#undef CG_AD
     return check_launch("axpy_dot");
 }
 int launch_axpy_dot(int dtype, int n, const void *q, void *r, long long ld, const void *alpha, int nrhs, void *partials, int grid,
-                    hipStream_t st, int vec_nt) {
+                    hipStream_t st, int vec_nt, const CgStop *stop) {
     const bool vec = vec_ok(dtype, ld, nrhs, {q, r});
     const int vnt = tune().vec_nt >= 0 ? tune().vec_nt : vec_nt;
-    CG_DISPATCH(dtype, axpy_dot_impl, n, q, r, ld, alpha, nrhs, partials, grid, vec, vnt, st);
+    CG_DISPATCH(dtype, axpy_dot_impl, n, q, r, ld, alpha, nrhs, partials, grid, vec, vnt, st, stop);
 }
 template <typename T>
 static int axpy_dot_alpha_impl(int n, const void *q, void *r, long long ld, const void *part_dq, int P, const CgScalars &sc, int nrhs,
-                               void *partials, int grid, bool vec, hipStream_t st) {
+                               void *partials, int grid, bool vec, hipStream_t st, const CgStop *stop) {
     dim3 g(grid, nrhs), blk(kBlock);
     using A = typename VT<T>::acc;
-    if (vec) hipLaunchKernelGGL((axpy_dot_alpha_kernel<T, kBlock, true>), g, blk, 0, st, n, (const T *)q, (T *)r, ld, (const A *)part_dq, P, sc.kdq, (const T *)sc.delta, (T *)sc.alpha, sc.iter, (A *)partials);
-    else hipLaunchKernelGGL((axpy_dot_alpha_kernel<T, kBlock, false>), g, blk, 0, st, n, (const T *)q, (T *)r, ld, (const A *)part_dq, P, sc.kdq, (const T *)sc.delta, (T *)sc.alpha, sc.iter, (A *)partials);
+    const CgStop none;
+#define CG_ADA(V, G) hipLaunchKernelGGL((axpy_dot_alpha_kernel<T, kBlock, V, G>), g, blk, 0, st, n, (const T *)q, (T *)r, ld, (const A *)part_dq, P, sc.kdq, (const T *)sc.delta, (T *)sc.alpha, sc.iter, (A *)partials, G ? *stop : none)
+    if (stop) { if (vec) CG_ADA(true, true); else CG_ADA(false, true); }
+    else if (vec) CG_ADA(true, false);
+    else CG_ADA(false, false);
+#undef CG_ADA
     return check_launch("axpy_dot_alpha");
 }
 int launch_axpy_dot_alpha(int dtype, int n, const void *q, void *r, long long ld, const void *part_dq, int P, const CgScalars &sc,
-                          int nrhs, void *partials, int grid, hipStream_t st) {
+                          int nrhs, void *partials, int grid, hipStream_t st, const CgStop *stop) {
     const bool vec = vec_ok(dtype, ld, nrhs, {q, r});
-    CG_DISPATCH(dtype, axpy_dot_alpha_impl, n, q, r, ld, part_dq, P, sc, nrhs, partials, grid, vec, st);
+    CG_DISPATCH(dtype, axpy_dot_alpha_impl, n, q, r, ld, part_dq, P, sc, nrhs, partials, grid, vec, st, stop);
 }
 template <typename T>
 static int aypx_beta_x_impl(int n, const void *x, void *y, void *xs, long long ld, const void *partials, int P, int nrhs,
-                            const CgScalars &sc, bool vec, int vnt, hipStream_t st) {
+                            const CgScalars &sc, bool vec, int vnt, hipStream_t st, const CgStop *stop) {
     dim3 g(vec_grid(n, VT<T>::dtype, nrhs), nrhs), blk(kBlock);
     auto *pp = static_cast<const typename VT<T>::acc *>(partials);
-#define CG_AX(V, N) hipLaunchKernelGGL((aypx_beta_x_kernel<T, kBlock, V, N>), g, blk, 0, st, n, (const T *)x, (T *)y, (T *)xs, ld, pp, P, sc.krr, nrhs, \
-                                       (const T *)sc.alpha, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (const int *)sc.iter)
-    if (vec && (vnt & 1)) CG_AX(true, 1); else if (vec) CG_AX(true, 0); else CG_AX(false, 0);
+    const CgStop none;
+#define CG_AX(V, N, G) hipLaunchKernelGGL((aypx_beta_x_kernel<T, kBlock, V, N, G>), g, blk, 0, st, n, (const T *)x, (T *)y, (T *)xs, ld, pp, P, sc.krr, nrhs, \
+                                          (const T *)sc.alpha, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (const int *)sc.iter, G ? *stop : none)
+    if (stop) { if (vec && (vnt & 1)) CG_AX(true, 1, true); else if (vec) CG_AX(true, 0, true); else CG_AX(false, 0, true); }
+    else if (vec && (vnt & 1)) CG_AX(true, 1, false); else if (vec) CG_AX(true, 0, false); else CG_AX(false, 0, false);
 #undef CG_AX
     return check_launch("aypx_beta_x");
 }
 int launch_aypx_beta_x(int dtype, int n, const void *x, void *y, void *xs, long long ld, const void *partials, int P, int nrhs,
-                       const CgScalars &sc, hipStream_t st, int vec_nt) {
+                       const CgScalars &sc, hipStream_t st, int vec_nt, const CgStop *stop) {
     if (n <= 0) return CGAMD_OK;
     const bool v = vec_ok(dtype, ld, nrhs, {x, y, xs});
     const int vnt = tune().vec_nt >= 0 ? tune().vec_nt : vec_nt;
-    CG_DISPATCH(dtype, aypx_beta_x_impl, n, x, y, xs, ld, partials, P, nrhs, sc, v, vnt, st);
+    CG_DISPATCH(dtype, aypx_beta_x_impl, n, x, y, xs, ld, partials, P, nrhs, sc, v, vnt, st, stop);
 }
 bool fold_alpha_ok(int n_partials, int fold_max) { return tune().dev_no_fold_alpha == 0 && n_partials <= (fold_max > 0 ? fold_max : kFoldAlphaMax); }
 int launch_axpy2_dot_alpha(int dtype, int n, const void *d, void *x, const void *q, void *r, long long ld, const void *part_dq,
@@ -778,18 +825,24 @@ template <typename T> static int delta0_impl(const void *partials, int grid, int
 int launch_cg_delta0(int dtype, const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st) {
     CG_DISPATCH(dtype, delta0_impl, partials, grid, nrhs, s, st);
 }
-template <typename T> static int alpha_impl(const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st) {
+template <typename T> static int alpha_impl(const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st, const CgStop *stop) {
     using A = typename VT<T>::acc;
-    if (s.stage && s.ticket && grid >= 16384)
-        hipLaunchKernelGGL((cg_alpha2_kernel<T>), dim3(kAlphaParts, nrhs), dim3(kScalarBlock), 0, st, static_cast<const A *>(partials),
-                           grid, nrhs, (const T *)s.delta, (T *)s.alpha, s.iter, (A *)s.stage, s.ticket);
-    else
-        hipLaunchKernelGGL((cg_alpha_kernel<T>), dim3(nrhs), dim3(kScalarBlock), 0, st, static_cast<const A *>(partials),
-                           grid, s.kdq, nrhs, (const T *)s.delta, (T *)s.alpha, s.iter);
+    const CgStop none;
+    if (s.stage && s.ticket && grid >= 16384) {
+#define CG_A2(G) hipLaunchKernelGGL((cg_alpha2_kernel<T, G>), dim3(kAlphaParts, nrhs), dim3(kScalarBlock), 0, st, static_cast<const A *>(partials), \
+                                    grid, nrhs, (const T *)s.delta, (T *)s.alpha, s.iter, (A *)s.stage, s.ticket, G ? *stop : none)
+        if (stop) CG_A2(true); else CG_A2(false);
+#undef CG_A2
+    } else {
+#define CG_A1(G) hipLaunchKernelGGL((cg_alpha_kernel<T, G>), dim3(nrhs), dim3(kScalarBlock), 0, st, static_cast<const A *>(partials), \
+                                    grid, s.kdq, nrhs, (const T *)s.delta, (T *)s.alpha, s.iter, G ? *stop : none)
+        if (stop) CG_A1(true); else CG_A1(false);
+#undef CG_A1
+    }
     return check_launch("cg_alpha");
 }
-int launch_cg_alpha(int dtype, const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st) {
-    CG_DISPATCH(dtype, alpha_impl, partials, grid, nrhs, s, st);
+int launch_cg_alpha(int dtype, const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st, const CgStop *stop) {
+    CG_DISPATCH(dtype, alpha_impl, partials, grid, nrhs, s, st, stop);
 }
 template <typename T> static int beta_impl(const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st) {
     hipLaunchKernelGGL((cg_beta_kernel<T>), dim3(nrhs), dim3(kScalarBlock), 0, st, static_cast<const typename VT<T>::acc *>(partials),
@@ -838,51 +891,62 @@ int launch_aypx_beta(int dtype, int n, const void *x, void *y, long long ld, con
 // ---- diagonally preconditioned CG -----------------------------------------------------------------
 template <typename T>
 static int pcg_axpy2_impl(bool init, int n, const void *d, void *x, const void *q, void *r, const void *m, long long m_pitch, long long ld,
-                          const void *alpha, int nrhs, void *part_rz, void *part_rr, int grid, bool vec, hipStream_t st) {
+                          const void *alpha, int nrhs, void *part_rz, void *part_rr, int grid, bool vec, hipStream_t st, const CgStop *stop) {
     dim3 g(grid, nrhs), blk(kBlock);
     using A = typename VT<T>::acc;
-#define CG_PCG(V, I) hipLaunchKernelGGL((pcg_axpy2_dot2_kernel<T, kBlock, V, I>), g, blk, 0, st, n, (const T *)d, (T *)x, (const T *)q, \
-                                        (T *)r, (const T *)m, m_pitch, ld, (const T *)alpha, (A *)part_rz, (A *)part_rr)
-    if (init) { if (vec) CG_PCG(true, true); else CG_PCG(false, true); }
-    else { if (vec) CG_PCG(true, false); else CG_PCG(false, false); }
+    const CgStop none;
+#define CG_PCG(V, I, G) hipLaunchKernelGGL((pcg_axpy2_dot2_kernel<T, kBlock, V, I, G>), g, blk, 0, st, n, (const T *)d, (T *)x, (const T *)q, \
+                                           (T *)r, (const T *)m, m_pitch, ld, (const T *)alpha, (A *)part_rz, (A *)part_rr, G ? *stop : none)
+    if (init) { if (vec) CG_PCG(true, true, false); else CG_PCG(false, true, false); }
+    else if (stop) { if (vec) CG_PCG(true, false, true); else CG_PCG(false, false, true); }
+    else { if (vec) CG_PCG(true, false, false); else CG_PCG(false, false, false); }
 #undef CG_PCG
     return check_launch("pcg_axpy2_dot2");
 }
 int launch_pcg_axpy2_dot2(int dtype, bool init, int n, const void *d, void *x, const void *q, void *r, const void *m,
                           long long ld, const void *alpha, int nrhs, void *part_rz, void *part_rr, int grid, hipStream_t st,
-                          long long m_pitch) {
+                          long long m_pitch, const CgStop *stop) {
     const bool vec = vec_ok(dtype, ld, nrhs, {d, x, q, r, m}) && ((m_pitch * (long long)dtype_size(dtype)) & 15) == 0;
-    CG_DISPATCH(dtype, pcg_axpy2_impl, init, n, d, x, q, r, m, m_pitch, ld, alpha, nrhs, part_rz, part_rr, grid, vec, st);
+    CG_DISPATCH(dtype, pcg_axpy2_impl, init, n, d, x, q, r, m, m_pitch, ld, alpha, nrhs, part_rz, part_rr, grid, vec, st, stop);
 }
 template <typename T>
 static int pcg_aypx_impl(int n, const void *r, void *p, const void *m, long long m_pitch, long long ld, const void *part_rz, const void *part_rr,
-                         int P, int nrhs, const CgScalars &sc, void *rho2, void *xs, bool vec, hipStream_t st) {
+                         int P, int nrhs, const CgScalars &sc, void *rho2, void *xs, bool vec, hipStream_t st, const CgStop *stop) {
     dim3 g(vec_grid(n, VT<T>::dtype, nrhs), nrhs), blk(kBlock);
     using A = typename VT<T>::acc;
-    if (vec) hipLaunchKernelGGL((pcg_aypx_beta_kernel<T, kBlock, true>), g, blk, 0, st, n, (const T *)r, (T *)p, (const T *)m, m_pitch, ld, (const A *)part_rz, (const A *)part_rr, P, sc.krr, nrhs, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter, (T *)xs, (const T *)sc.alpha);
-    else hipLaunchKernelGGL((pcg_aypx_beta_kernel<T, kBlock, false>), g, blk, 0, st, n, (const T *)r, (T *)p, (const T *)m, m_pitch, ld, (const A *)part_rz, (const A *)part_rr, P, sc.krr, nrhs, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter, (T *)xs, (const T *)sc.alpha);
+    const CgStop none;
+#define CG_PA(V, G) hipLaunchKernelGGL((pcg_aypx_beta_kernel<T, kBlock, V, false, G>), g, blk, 0, st, n, (const T *)r, (T *)p, (const T *)m, m_pitch, ld, (const A *)part_rz, (const A *)part_rr, P, sc.krr, nrhs, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter, (T *)xs, (const T *)sc.alpha, G ? *stop : none)
+    if (stop) { if (vec) CG_PA(true, true); else CG_PA(false, true); }
+    else if (vec) CG_PA(true, false);
+    else CG_PA(false, false);
+#undef CG_PA
     return check_launch("pcg_aypx_beta");
 }
 int launch_pcg_aypx_beta(int dtype, int n, const void *r, void *p, const void *m, long long ld, const void *part_rz,
-                         const void *part_rr, int P, int nrhs, const CgScalars &sc, void *rho2, void *xs, hipStream_t st, long long m_pitch) {
+                         const void *part_rr, int P, int nrhs, const CgScalars &sc, void *rho2, void *xs, hipStream_t st, long long m_pitch,
+                         const CgStop *stop) {
     const bool vec = vec_ok(dtype, ld, nrhs, {r, p, m, xs}) && ((m_pitch * (long long)dtype_size(dtype)) & 15) == 0;
-    CG_DISPATCH(dtype, pcg_aypx_impl, n, r, p, m, m_pitch, ld, part_rz, part_rr, P, nrhs, sc, rho2, xs, vec, st);
+    CG_DISPATCH(dtype, pcg_aypx_impl, n, r, p, m, m_pitch, ld, part_rz, part_rr, P, nrhs, sc, rho2, xs, vec, st, stop);
 }
 // the tridiagonal form: p = z + beta p with z = M^-1 r from pcg_tri (per right-hand side, stride ld); the partials are
 // pcg_tri's, summed thread-strided
 template <typename T>
 static int pcg_aypx_z_impl(int n, void *p, const void *z, long long ld, const void *part_rz, const void *part_rr, int P, int nrhs,
-                           const CgScalars &sc, void *rho2, void *xs, bool vec, hipStream_t st) {
+                           const CgScalars &sc, void *rho2, void *xs, bool vec, hipStream_t st, const CgStop *stop) {
     dim3 g(vec_grid(n, VT<T>::dtype, nrhs), nrhs), blk(kBlock);
     using A = typename VT<T>::acc;
-    if (vec) hipLaunchKernelGGL((pcg_aypx_beta_kernel<T, kBlock, true, true>), g, blk, 0, st, n, (const T *)nullptr, (T *)p, (const T *)z, ld, ld, (const A *)part_rz, (const A *)part_rr, P, 0, nrhs, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter, (T *)xs, (const T *)sc.alpha);
-    else hipLaunchKernelGGL((pcg_aypx_beta_kernel<T, kBlock, false, true>), g, blk, 0, st, n, (const T *)nullptr, (T *)p, (const T *)z, ld, ld, (const A *)part_rz, (const A *)part_rr, P, 0, nrhs, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter, (T *)xs, (const T *)sc.alpha);
+    const CgStop none;
+#define CG_PZ(V, G) hipLaunchKernelGGL((pcg_aypx_beta_kernel<T, kBlock, V, true, G>), g, blk, 0, st, n, (const T *)nullptr, (T *)p, (const T *)z, ld, ld, (const A *)part_rz, (const A *)part_rr, P, 0, nrhs, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter, (T *)xs, (const T *)sc.alpha, G ? *stop : none)
+    if (stop) { if (vec) CG_PZ(true, true); else CG_PZ(false, true); }
+    else if (vec) CG_PZ(true, false);
+    else CG_PZ(false, false);
+#undef CG_PZ
     return check_launch("pcg_aypx_beta z");
 }
 int launch_pcg_aypx_beta_z(int dtype, int n, void *p, const void *z, long long ld, const void *part_rz, const void *part_rr, int P, int nrhs,
-                           const CgScalars &sc, void *rho2, void *xs, hipStream_t st) {
+                           const CgScalars &sc, void *rho2, void *xs, hipStream_t st, const CgStop *stop) {
     const bool vec = vec_ok(dtype, ld, nrhs, {p, z, xs});
-    CG_DISPATCH(dtype, pcg_aypx_z_impl, n, p, z, ld, part_rz, part_rr, P, nrhs, sc, rho2, xs, vec, st);
+    CG_DISPATCH(dtype, pcg_aypx_z_impl, n, p, z, ld, part_rz, part_rr, P, nrhs, sc, rho2, xs, vec, st, stop);
 }
 template <typename T>
 static int pcg_delta0_impl(const void *part_rz, const void *part_rr, int P, int nrhs, const CgScalars &sc, void *rho2, hipStream_t st) {

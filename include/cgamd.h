@@ -163,6 +163,32 @@ int cgamd_solver_iterate(cgamd_solver *s, int nIterations);
  * sqrt|r.r| < tol (or NaN), at most maxIterations; *iterations_run = iterations of this call; x is the iterate of exactly that
  * many (reference: the `tol` loop of p_h-PY_C-CL.py:1338-1369).  CGAMD_ERR_STATE if the handle runs a launched loop. */
 int cgamd_solver_iterate_tol(cgamd_solver *s, int maxIterations, double tol, int *iterations_run);
+/* Tolerance stop PER RIGHT-HAND SIDE on the device, for the LAUNCHED loops: the reference's sub-domain loop
+ * `r[p] = CG(P[0], z[p].ravel(), tol=CGtol, maxit=CGMaxIT)` (p_h-PY_C-CL.py:1916-1921, the `tol` loop at 1338-1369; PCG:
+ * helmFE_var.py:580-584) as one batched solve.  Right-hand side r stops in the first iteration k >= 1 of such a call for which
+ * !(sqrt|delta_k[r]| >= tol_r), delta_k = r_k . r_k (unconjugated) being the value the history records -- with a preconditioner
+ * still r.r, not rho; NaN stops; the test is evaluated in double.  tol: nTol = 1 (one for all) or nRHS positive values, host
+ * memory.  A stopped right-hand side is FROZEN: cgamd_solver_get_x returns for its column the iterate of exactly its stopping
+ * iteration -- the bits of set_rhs; iterate(its_r) on this handle -- while the others run on until each has stopped or
+ * maxIterations iterations of this call are done.  iterations_run[r] (nRHS ints): iterations of right-hand side r since set_rhs,
+ * its stopping iteration or the handle's count; cgamd_solver_iterations_done is their maximum.  History rows k <= its_r of column r
+ * are those of a fixed-count run, rows its_r < k <= iterations_done repeat delta_{its_r}.  maxIterations == 0 returns the current
+ * counts at once.
+ * The call synchronises, but never per iteration: it enqueues chunks of checkEvery iterations (0 = 8), reads one device word -- the
+ * number of active right-hand sides -- asynchronously after each, and waits for the word of chunk c - 1 once chunk c is enqueued.
+ * Iterations enqueued after the last stop change nothing, so the result does not depend on checkEvery.  The call may follow
+ * cgamd_solver_iterate calls (their iterations are not examined again) and may be repeated: until(a); until(b) leaves the bits of
+ * until(a + b); a stopped right-hand side stays stopped until the next cgamd_solver_set_rhs, whatever the later tolerances.  Once
+ * a right-hand side has stopped, cgamd_solver_iterate, _iterate_timed and _iterate_tol return CGAMD_ERR_STATE until
+ * cgamd_solver_set_rhs (the columns are at different iterations).
+ * Served: every handle whose vectors are RHS-major (cgamd_solver_layout() == 0) -- all value types, any nRHS, diagonal and
+ * tridiagonal (stride 1 short and long form, stride > 1) preconditioners, batched handles with and without a per-system
+ * preconditioner, CGAMD_NO_GRAPH, CGAMD_MATRIX_ON_DEVICE.  The call runs the handle's three / four-launch loop (six with the long
+ * sweep); a handle whose cgamd_solver_iterate takes a resident or the two-launch loop runs that launched loop from this call to the
+ * next cgamd_solver_set_rhs, with the same bits (cgamd_solver_iterate_tol then returns CGAMD_ERR_STATE).
+ * CGAMD_ERR_INVALID: NULL s / tol / iterations_run, nTol not in {1, nRHS}, a tolerance that is not > 0, negative maxIterations or
+ * checkEvery.  CGAMD_ERR_STATE, the handle untouched: row-major layout (cgamd_solver_layout() == 1), CGAMD_UNFUSED, no set_rhs. */
+int cgamd_solver_iterate_until(cgamd_solver *s, int maxIterations, const double *tol, int nTol, int checkEvery, int *iterations_run);
 /* nIterations iterations with plain launches and a HIP event pair around every SpMV launch on the solver's stream;
  * returns the average in-loop SpMV duration (and optionally the average iteration time), in ms.  Synchronises. */
 int cgamd_solver_iterate_timed(cgamd_solver *s, int nIterations, float *spmv_ms_avg, float *iter_ms_avg);
