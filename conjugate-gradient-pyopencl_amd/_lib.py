@@ -103,6 +103,7 @@ def load():
         "cgamd_solver_dot_partials": (ci, [vp, vp, ll, ctypes.POINTER(ci)]),
         "cgamd_solver_layout": (ci, [vp]),
         "cgamd_solver_loop_launches": (ci, [vp]),
+        "cgamd_solver_x_lag": (ci, [vp]),
         "cgamd_solver_index_codes": (ci, [vp]),
         "cgamd_solver_value_codes": (ci, [vp]),
         "cgamd_solver_joint_codes": (ci, [vp]),

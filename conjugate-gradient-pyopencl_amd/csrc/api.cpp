@@ -36,6 +36,8 @@ int cgamd_tune(const char *key, int value) {
     if (!key) return fail(CGAMD_ERR_INVALID, "tune: null key");
     const std::string k(key);
     bool known = true;
+    if (k == "dev.x_lag" && value != -1 && value != 0 && value != 1 && value != 2 && value != 4 && value != 8)
+        return fail(CGAMD_ERR_INVALID, "tune: dev.x_lag takes -1 (default rule), 0 or 1 (off), 2, 4 or 8");
     g_tune_generation.fetch_add(1, std::memory_order_relaxed);     // cached cg() handles were created under the old configuration
     tune_set([&](Tuning &g_tune) {
     // public keys (include/cgamd.h)
@@ -56,6 +58,8 @@ int cgamd_tune(const char *key, int value) {
     else if (k == "vec_grid") g_tune.vec_grid = value;
     // development hooks: tests, rehearsals, profiling (not part of the documented interface)
     else if (k == "dev.no_fold_alpha") g_tune.dev_no_fold_alpha = value;
+    else if (k == "dev.x_lag") g_tune.dev_x_lag = value;
+    else if (k == "dev.x_lag_dnt") g_tune.dev_x_lag_dnt = value;
     else if (k == "dev.generic_spmv") g_tune.dev_generic_spmv = value;
     else if (k == "dev.value_codes") g_tune.value_codes = value;
     else if (k == "dev.vc_pipe") g_tune.dev_vc_pipe = value;

@@ -112,6 +112,10 @@ struct Tuning {
     int vec_grid = 0;       // vector kernels: work-groups, 0 = auto
     // ---- development hooks ("dev." keys): tests, rehearsals, profiling
     int dev_no_fold_alpha = 0;      // 1: small systems keep the separate cg_alpha launch (the four-launch family at sizes that would fold it)
+    int dev_x_lag = -1;             // captured runs of the three / four-launch loop bring x up to date once per this many iterations: 2, 4 or 8;
+                                    // 0 / 1 = every iteration; -1 = the default rule (solver.cpp x_lag_wanted)
+    int dev_x_lag_dnt = 1;          // ... the last step of a group loads the direction buffers, read for the last time, non-temporally where x streams
+                                    // too (0 = plain loads: A/B, profiles/x_lag/ab.log: lag 4 5970 -> 6059 it/s at 10M rows fp64, no difference at 100M)
     int value_codes = 1;            // one-byte value codes on top of the one-byte column codes where the matrix has at most 256 distinct entries (0 = off: A/B, tests)
     int dev_joint_codes = 1;        // value-coded SpMV: one byte per non-zero naming the (offset, value) pair where at most 256 pairs occur (0 = two bytes: A/B)
     int dev_vc_pipe = 1;            // value-coded SpMV: gathers pipelined across the row blocks of a work-group (0 = one block at a time: A/B)
@@ -224,6 +228,17 @@ int launch_axpy_dot_alpha(int dtype, int n, const void *q, void *r, long long ld
                           int nrhs, void *partials, int grid, hipStream_t st, const CgStop *stop = nullptr);
 int launch_aypx_beta_x(int dtype, int n, const void *x, void *y, void *xs, long long ld, const void *partials, int P, int nrhs,
                        const CgScalars &sc, hipStream_t st, int vec_nt = 3, const CgStop *stop = nullptr);
+// x brought up to date once per group of `lag` iterations (vector.hip): the d step of every group iteration but the last,
+// d_out = beta d_in + r with d_in kept, and the group's last step, x += alpha_0 dirs[0] + ... + alpha_{lag-1} dirs[lag-1] in
+// iteration order, dirs[0] = beta dirs[lag-1] + r.  lag 2, 4 or 8.  sc.alpha is the ring of kLagMax * nrhs values; group
+// iteration j keeps its alpha in slot lag_alpha_slot(j, lag), so that a group's last iteration leaves it where every other
+// loop does (slot 0)
+constexpr int kLagMax = 8;
+constexpr int lag_alpha_slot(int j, int lag) { return (j + 1) % lag; }
+int launch_aypx_beta_out(int dtype, int n, const void *r, const void *d_in, void *d_out, long long ld, const void *partials, int P,
+                         int nrhs, const CgScalars &sc, hipStream_t st, int vec_nt = 3);
+int launch_aypx_beta_xlag(int dtype, int n, int lag, const void *r, void *const *dirs, void *xs, long long ld, const void *partials, int P,
+                          int nrhs, const CgScalars &sc, hipStream_t st, int vec_nt = 3);
 // small systems: alpha = delta / sum(part_dq) in the prologue (three-launch iteration); fold_alpha_ok says when
 bool fold_alpha_ok(int n_partials, int fold_max = 0);      // fold_max 0 = the default limit (2048 partials)
 // two-launch iteration (spmv.hip "Two-launch iteration"): the SpMV launch computes beta and d_new = beta d_old + r on the

@@ -79,6 +79,12 @@ struct cgamd_solver {
     // two-launch loop (small systems): d of iteration k lives in dbuf[k & 1] (dbuf[0] = d, the initial r); decided at creation
     bool fused2 = false;
     void *d2 = nullptr;
+    // x brought up to date once per x_lag iterations inside a captured U-iteration graph of the three / four-launch loop (vector.hip):
+    // direction buffer 0 = d, 1 = d2, 2 .. x_lag - 1 in dlag.  Decided by setup_x_lag; 1 = x updated in every iteration
+    int x_lag = 1;
+    void *dlag = nullptr;
+    size_t dlag_pitch = 0;
+    int dlag_bufs = 0;
     // resident loop (resident.hip): iterate() calls of a small system in ONE launch; decided with fused2
     bool res_ok = false;
     ResidentPlan res;
@@ -163,7 +169,8 @@ static int handle_spmv(cgamd_solver *s, int n, const void *x, long long ldx, voi
 }
 
 // k = iterations already enqueued since set_rhs (the iteration being enqueued is number k + 1)
-static int enqueue_spmv(cgamd_solver *s, int k, hipStream_t st) {
+// dvec: the direction the product is taken of where it is not s->d (a group iteration of the deferred x update)
+static int enqueue_spmv(cgamd_solver *s, int k, hipStream_t st, void *dvec = nullptr) {
     const int dt = s->dtype, n = s->n, nr = s->nrhs;
     // timed pass: the row-block kernel of a single right-hand side takes the event pair on its dispatch (kernel duration);
     // every other SpMV form is bracketed by hipEventRecord (duration + launch gaps)
@@ -178,7 +185,7 @@ static int enqueue_spmv(cgamd_solver *s, int k, hipStream_t st) {
     else if (s->rm) rc = launch_spmm_rm(dt, n, s->nnz, s->vals, s->ptr, s->cols, s->d, s->q, nr, s->part_dq, s->plan.max_quad, s->rm_pace, st);
     // (the preconditioned loops of a batched handle take alpha from the d.q partials whatever the flags)
     else if ((s->flags & CGAMD_UNFUSED) && !s->tri_on && !(s->nsys && s->mdiag)) rc = handle_spmv(s, n, s->d, n, s->q, n, nullptr, nullptr, st);
-    else rc = handle_spmv(s, n, s->d, n, s->q, n, s->d, s->part_dq, st);
+    else rc = handle_spmv(s, n, dvec ? dvec : s->d, n, s->q, n, dvec ? dvec : s->d, s->part_dq, st);
     set_kernel_event_pair(nullptr);
     if (rc) return rc;
     if (s->ev_pair && !ext) CG_HIP(hipEventRecord(s->ev_pair[1], st));
@@ -193,9 +200,41 @@ static int enqueue_tri_sweep(cgamd_solver *s, bool update, const void *q, void *
     return launch_pcg_tri(s->dtype, s->tri, update, q, s->r, z, s->n, alpha, s->nrhs, prz, prr, st);
 }
 
-static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st) {
+// Deferred x update: the lag the captured U-iteration graphs of this handle run with NOW (1 = none).  s->x_lag is what creation
+// decided and allocated for; the loop family may have changed since (a preconditioner, the row-major layout)
+static int x_lag_now(const cgamd_solver *s) {
+    if (s->x_lag < 2 || s->nsys || s->rm || precond_set(s) || (s->flags & (CGAMD_UNFUSED | CGAMD_NO_GRAPH)) || fused2_now(s)) return 1;
+    return s->U % s->x_lag == 0 ? s->x_lag : 1;
+}
+static void *lag_dir(const cgamd_solver *s, int j) {
+    return j == 0 ? s->d : j == 1 ? s->d2 : static_cast<char *>(s->dlag) + (size_t)(j - 2) * s->dlag_pitch;
+}
+
+// iteration j of a group of `lag` inside a captured graph: the SpMV on direction buffer j, alpha in its slot of the ring, the r
+// update, and the d step into buffer j + 1 -- or, last of the group, the step that brings x up to date and writes buffer 0 = s->d
+static int enqueue_lag_iteration(cgamd_solver *s, int k, int lag, int j, hipStream_t st) {
     const int dt = s->dtype, n = s->n, nr = s->nrhs;
     int rc;
+    CgScalars sc = s->sc;
+    sc.alpha = static_cast<char *>(s->sc.alpha) + dtype_size(dt) * (size_t)nr * lag_alpha_slot(j, lag);
+    if ((rc = enqueue_spmv(s, k, st, lag_dir(s, j)))) return rc;
+    const bool fold = fold_alpha_ok(s->plan.n_partials, s->plan.fold_max);
+    if (!fold && (rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, sc, st))) return rc;
+    if (fold) rc = launch_axpy_dot_alpha(dt, n, s->q, s->r, n, s->part_dq, s->plan.n_partials, sc, nr, s->part_rr, s->vgrid, st);
+    else rc = launch_axpy_dot(dt, n, s->q, s->r, n, sc.alpha, nr, s->part_rr, s->vgrid, st, s->plan.vec_nt);
+    if (rc) return rc;
+    if (j + 1 < lag)
+        return launch_aypx_beta_out(dt, n, s->r, lag_dir(s, j), lag_dir(s, j + 1), n, s->part_rr, s->vgrid, nr, s->sc, st, s->plan.vec_nt);
+    void *dirs[kLagMax];
+    for (int i = 0; i < lag; ++i) dirs[i] = lag_dir(s, i);
+    return launch_aypx_beta_xlag(dt, n, lag, s->r, dirs, s->x, n, s->part_rr, s->vgrid, nr, s->sc, st, s->plan.vec_nt);
+}
+
+// lag >= 2 (capture of a U-iteration graph only): this is iteration k % lag of a group of the deferred x update
+static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st, int lag = 1) {
+    const int dt = s->dtype, n = s->n, nr = s->nrhs;
+    int rc;
+    if (lag >= 2) return enqueue_lag_iteration(s, k, lag, k % lag, st);
     if (fused2_now(s)) {   // two launches: [beta, d = beta d + r, q = A d, d.q] and [alpha, x += alpha d, r -= alpha q, r.r]
         if ((rc = enqueue_spmv(s, k, st))) return rc;
         return launch_axpy2_dot_alpha(dt, n, dbuf(s, k + 1), s->x, s->q, s->r, n, s->part_dq, s->plan.n_partials, s->sc, nr, s->part_rr, s->vgrid, st);
@@ -403,12 +442,36 @@ static int setup_resident_one_xcd(cgamd_solver *s) {
     return CGAMD_OK;
 }
 
+// The lag of the deferred x update this handle is to run with, and its direction buffers beyond d and d2 (allocated here, never
+// inside a capture).  dev.x_lag forces 2 / 4 / 8 (0, 1: off); the default rule (-1) turns it on where the loop is the four-launch
+// form (alpha not folded: more than 2048 d.q partials, vectors far beyond the caches) with the lag the three legs of
+// profiles/x_lag/ab.log speak for: 10M rows fp64 5784 it/s without, 6059 with 4, 6094 with 8; fp32 10252 / 10892 / 10872; 100M rows
+// fp64 521.3 / 573.4 / 558.7.  8 wins the first by 0.6 %, 4 the other two (by 2.6 % at 100M rows) with two extra vectors instead of six.
+// A handle whose buffers cannot be allocated runs without: cgamd_solver_x_lag says 1.
+constexpr int kXLagDefault = 4;
+static void setup_x_lag(cgamd_solver *s) {
+    const int knob = s->tune.dev_x_lag;
+    // (a handle the chip-wide resident loop takes over launches a graph for the few calls too short for that loop only)
+    int lag = knob >= 0 ? std::max(knob, 1) : (fold_alpha_ok(s->plan.n_partials, s->plan.fold_max) || s->resw.ok ? 1 : kXLagDefault);
+    if (s->nsys || (s->flags & (CGAMD_UNFUSED | CGAMD_NO_GRAPH)) || lag > kLagMax || s->U % lag != 0) lag = 1;
+    if (lag - 2 > s->dlag_bufs) {
+        if (s->dlag) { (void)hipStreamSynchronize(s->ctx->stream); (void)hipFree(s->dlag); s->dlag = nullptr; s->dlag_bufs = 0; }
+        s->dlag_pitch = ((size_t)s->n * s->nrhs * dtype_size(s->dtype) + 4095) & ~(size_t)4095;      // as in the handle's slab
+        if (hipMalloc(&s->dlag, s->dlag_pitch * (size_t)(lag - 2)) == hipSuccess) s->dlag_bufs = lag - 2;
+        else { (void)hipGetLastError(); s->dlag = nullptr; lag = 1; }
+    }
+    if (lag != s->x_lag) destroy_graphs(s);
+    s->x_lag = lag;
+}
+
 static int capture(cgamd_solver *s, int k0, int iters, hipGraph_t *g, hipGraphExec_t *ge, bool guarded = false) {
     hipStream_t st = s->ctx->stream;
     hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
     if (e != hipSuccess) return fail(CGAMD_ERR_HIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(e));
     int rc = CGAMD_OK;
-    for (int i = 0; i < iters && rc == CGAMD_OK; ++i) rc = guarded ? enqueue_iteration_until(s, st) : enqueue_iteration(s, k0 + i, st);
+    // whole groups of the deferred x update, so that nothing is pending when the graph ends (k0 = 0 there: no parity)
+    const int lag = (!guarded && iters == s->U && k0 == 0) ? x_lag_now(s) : 1;
+    for (int i = 0; i < iters && rc == CGAMD_OK; ++i) rc = guarded ? enqueue_iteration_until(s, st) : enqueue_iteration(s, k0 + i, st, lag);
     e = hipStreamEndCapture(st, g);
     if (rc != CGAMD_OK) return rc;
     if (e != hipSuccess) return fail(CGAMD_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
@@ -545,7 +608,7 @@ static int create_impl(const std::string &who, cgamd_ctx *ctx, int dtype, int si
     // (handles the chip-wide resident loop may take over size their vector launches one pack per thread: apply_wide_order)
     s->part_rr_cap = (size_t)std::max(std::max(s->vgrid, s->rm_vgrid), n_int <= (1 << 20) + 4096 ? (int)((n_int / (16 / vs) + kBlock - 1) / kBlock) : 0);
     if (!rc) rc = dmalloc(&s->part_rr, acc_size(dtype) * s->part_rr_cap * nRHS, "partials_rr");
-    if (!rc) rc = dmalloc(&s->sc.alpha, vs * nRHS, "alpha");
+    if (!rc) rc = dmalloc(&s->sc.alpha, vs * nRHS * kLagMax, "alpha");      // slot 0 is alpha; the rest: the ring of the deferred x update
     if (!rc) rc = dmalloc(&s->sc.beta, vs * nRHS, "beta");
     if (!rc) rc = dmalloc(&s->sc.delta, vs * nRHS, "delta");
     if (!rc) rc = dmalloc((void **)&s->sc.iter, 64, "iter");
@@ -564,6 +627,7 @@ static int create_impl(const std::string &who, cgamd_ctx *ctx, int dtype, int si
     if (!rc && !nsys) s->fused2 = fused2_ok(s->plan, dtype, nRHS, s->vals, s->cols);
     if (!rc && !nsys) rc = setup_resident(s);
     if (!rc && !nsys) rc = setup_index_codes(s);
+    if (!rc) setup_x_lag(s);
     if (!rc) {
         hipError_t e = hipStreamSynchronize(ctx->stream);  // host matrix arrays may go away after return
         if (e != hipSuccess) rc = fail(CGAMD_ERR_HIP, who + " sync: " + hipGetErrorString(e));
@@ -654,6 +718,7 @@ int cgamd_solver_reload_matrix(cgamd_solver *s, const void *aValues, const int *
         if (int rc = setup_index_codes(s)) return rc;
         if (!had && s->codes) destroy_graphs(s);
     }
+    setup_x_lag(s);                     // (the default rule follows the number of d.q partials and the resident plan)
     CG_HIP(hipStreamSynchronize(st));   // the host arrays may go away after return
     if (s->pre_source >= 2) {           // a preconditioner built from the matrix follows it (one from the caller's arrays is kept)
         const int rc = s->pre_kind == 1 ? jacobi_from_matrix(s, "reload_matrix") : line_from_matrix(s, "reload_matrix", s->pre_stride);
@@ -679,7 +744,7 @@ int cgamd_solver_destroy(cgamd_solver *s) {
         if (s->cols) (void)hipFree(s->cols);
     }
     void *bufs[] = {s->slab, s->part_dq, s->part_rr, s->sc.alpha, s->sc.beta, s->sc.delta,
-                    s->sc.history, s->sc.iter, s->mdiag, s->part_rz, s->rho2, s->tri_coef, s->tri_part, s->tri_cstart, s->tri.maps, s->sc.stage, s->sc.ticket, s->res_sync, s->resw_sync, s->codes, s->dict, s->rm_pace, s->vcodes, s->vdict, s->jcodes, s->jdict_off, s->jdict_val};
+                    s->sc.history, s->sc.iter, s->mdiag, s->part_rz, s->rho2, s->tri_coef, s->tri_part, s->tri_cstart, s->tri.maps, s->sc.stage, s->sc.ticket, s->res_sync, s->resw_sync, s->dlag, s->codes, s->dict, s->rm_pace, s->vcodes, s->vdict, s->jcodes, s->jdict_off, s->jdict_val};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (s->stop_rec) (void)hipFree(s->stop_rec);
@@ -1382,6 +1447,11 @@ int cgamd_solver_loop_launches(cgamd_solver *s) {
     return fold_alpha_ok(s->plan.n_partials, s->plan.fold_max) ? 3 : 4;
 }
 
+int cgamd_solver_x_lag(cgamd_solver *s) {
+    if (!s) return -CGAMD_ERR_INVALID;
+    return x_lag_now(s);
+}
+
 int cgamd_solver_index_codes(cgamd_solver *s) { return s ? s->n_offsets : -CGAMD_ERR_INVALID; }
 
 // value arrays the byte models count, each once (a batched handle: one per system), beside the indices, which are counted once
@@ -1433,9 +1503,13 @@ long long cgamd_solver_iter_moved_bytes(cgamd_solver *s) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
     const long long passes = (s->nsys && s->mdiag) ? 12 : (s->flags & CGAMD_UNFUSED) ? 14 : s->mdiag ? 12 : 10;
+    const long long lag = x_lag_now(s);
     const long long value_bytes = joint_form(s) ? 0 : s->plan.vcodes ? 1 : V * value_arrays(s);
     const long long matrix = s->nnz * (value_bytes + index_bytes_per_nnz(s)) + ((long long)s->n_user + 1) * 4;
     if (s->tri_on) return matrix + tri_passes(s) * s->n_user * V;
+    // the deferred x update: the d steps of a group of L iterations move 4 L + 1 vectors instead of 5 L, the steady state of a
+    // handle iterated in multiples of U: (9 L + 1) / L passes per iteration
+    if (lag >= 2) return matrix + (9 * lag + 1) * s->n_user * V * s->nrhs / lag;
     return matrix + passes * s->n_user * V * s->nrhs;
 }
 

@@ -4,6 +4,7 @@
 //   ewise_kernel                  reference kernel/{real,complex}/{axpy,aypx,sub}.cl
 //   axpy_dot / aypx_beta_x        the fused loop: r -= alpha q + r.r partials; beta, x += alpha d, d = beta d + r
 //                                 (reference clcg.c:338-416); axpy2_dot / aypx_beta: the form with x updated in the r launch
+//   aypx_beta_out / _xlag         the d steps of a captured group of L iterations that brings x up to date once, at its end
 //   pcg_*                         diagonally preconditioned recurrence (reference helmFE_var.py:546-586); the tridiagonal
 //                                 form's sweep kernel is in precond.hip
 //   cg_alpha/beta/delta0          the scalar work the reference does on the host (clcg.c:274-292,317-334,376-411)
@@ -358,6 +359,123 @@ __global__ __launch_bounds__(BLOCK) void aypx_beta_x_kernel(int n, const T *__re
         const T dv = y[i];
         xs[i] = vadd(xs[i], vmul(al, dv));
         y[i] = vaypx(bt, dv, x[i]);
+    }
+}
+
+// ---- x brought up to date once per group of L iterations ------------------------------------------------------
+// x is read by nothing inside the loop, so inside a captured run of iterations it need not exist between them: the
+// directions d_0 .. d_{L-1} of a group are kept (every d step but the last writes d_{j+1} beside d_j instead of over it)
+// and the group's last d step forms x = ((x + alpha_0 d_0) + alpha_1 d_1) + ... -- per element the very operations, in the
+// very order, of L aypx_beta_x launches (-ffp-contract=off), so x is bit-identical.  Vector passes of the d steps of a
+// group: 3 (L - 1) + L + 4 instead of 5 L.  Both kernels open with the prologue of aypx_beta_x_kernel: beta from the r.r
+// partials in every work-group, work-group 0 records beta, delta and history[iter].
+template <typename T, int BLOCK>
+CG_DEV T lag_beta_prologue(const typename VT<T>::acc *__restrict__ partials, int P, int K, int nrhs, T *delta, T *beta, T *history,
+                           int history_cap, const int *iter, typename VT<T>::acc *red, T *beta_s) {
+    using A = typename VT<T>::acc;
+    const int r = blockIdx.y;
+    const A acc = thread_partials<BLOCK>(partials + (long long)r * P, P, K);
+    const A tot = block_sum<BLOCK>(acc, red);
+    if (threadIdx.x == 0) {
+        const int it = *iter;
+        const T dnT = from_acc<T>(tot);
+        const T dold = history[(long long)(it - 1) * nrhs + r];
+        const T b = from_acc<T>(acc_div(to_acc(dnT), to_acc(dold)));
+        *beta_s = b;
+        if (blockIdx.x == 0) {
+            beta[r] = b;
+            delta[r] = dnT;
+            if (it < history_cap) history[(long long)it * nrhs + r] = dnT;
+        }
+    }
+    __syncthreads();
+    return *beta_s;
+}
+
+// a step without x: dout = beta din + r, din kept (VNT bit 0: din is not read again before the group's last step, L - 1 - j
+// iterations away)
+template <typename T, int BLOCK, bool VEC, int VNT>
+__global__ __launch_bounds__(BLOCK) void aypx_beta_out_kernel(int n, const T *__restrict__ rv, const T *__restrict__ din, T *__restrict__ dout,
+                                                              long long ld, const typename VT<T>::acc *__restrict__ partials, int P, int K,
+                                                              int nrhs, T *delta, T *beta, T *history, int history_cap, const int *iter) {
+    __shared__ typename VT<T>::acc red[BLOCK / kWave];
+    __shared__ T beta_s;
+    const T bt = lag_beta_prologue<T, BLOCK>(partials, P, K, nrhs, delta, beta, history, history_cap, iter, red, &beta_s);
+    const long long off = (long long)blockIdx.y * ld;
+    rv += off; din += off; dout += off;
+    constexpr int E = Pack<T>::N;
+    const long long stride = (long long)gridDim.x * BLOCK;
+    long long i0 = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (VEC) {
+        const long long npack = n / E;
+        for (long long i = i0; i < npack; i += stride) {
+            const Pack<T> pr = ld_pack(rv + i * E);
+            Pack<T> pd = (VNT & 1) ? ld_pack_nt(din + i * E) : ld_pack(din + i * E);
+#pragma unroll
+            for (int k = 0; k < E; ++k) pd.v[k] = vaypx(bt, pd.v[k], pr.v[k]);
+            st_pack(dout + i * E, pd);
+        }
+        i0 += npack * E;
+    }
+    for (long long i = i0; i < n; i += stride) dout[i] = vaypx(bt, din[i], rv[i]);
+}
+
+// the group's last step.  d0 = direction buffer 0 (d_0 of the group; receives the next group's first direction: every element is
+// read, then written, by the same thread), older.d[j - 1] = buffer j for 0 < j < L; alpha of group iteration j at
+// alpha[lag_alpha_slot(j, L) * nrhs + r].  VNT bit 0: x non-temporal (as in aypx_beta_x_kernel); bit 2 (with bit 0): the direction
+// buffers, all read for the last time, as well
+template <typename T, int N> struct LagDirs { const T *d[N]; };
+template <typename T, int BLOCK, bool VEC, int VNT, int L>
+__global__ __launch_bounds__(BLOCK) void aypx_beta_xlag_kernel(int n, const T *__restrict__ rv, T *d0, const LagDirs<T, L - 1> older,
+                                                               T *__restrict__ xs, long long ld,
+                                                               const typename VT<T>::acc *__restrict__ partials, int P, int K, int nrhs,
+                                                               const T *__restrict__ alpha, T *delta, T *beta, T *history,
+                                                               int history_cap, const int *iter) {
+    __shared__ typename VT<T>::acc red[BLOCK / kWave];
+    __shared__ T beta_s;
+    const T bt = lag_beta_prologue<T, BLOCK>(partials, P, K, nrhs, delta, beta, history, history_cap, iter, red, &beta_s);
+    const int r = blockIdx.y;
+    const long long off = (long long)r * ld;
+    T al[L];
+    const T *dj[L];
+    dj[0] = d0 + off;
+#pragma unroll
+    for (int j = 0; j < L; ++j) {
+        al[j] = alpha[(long long)lag_alpha_slot(j, L) * nrhs + r];
+        if (j > 0) dj[j] = older.d[j - 1] + off;
+    }
+    rv += off; d0 += off; xs += off;
+    constexpr int E = Pack<T>::N;
+    const long long stride = (long long)gridDim.x * BLOCK;
+    long long i0 = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (VEC) {
+        const long long npack = n / E;
+        for (long long i = i0; i < npack; i += stride) {
+            const Pack<T> pr = ld_pack(rv + i * E);
+            Pack<T> ps = (VNT & 1) ? ld_pack_nt(xs + i * E) : ld_pack(xs + i * E);
+            Pack<T> pd[L];
+#pragma unroll
+            for (int j = 0; j < L; ++j) pd[j] = (VNT & 4) ? ld_pack_nt(dj[j] + i * E) : ld_pack(dj[j] + i * E);
+#pragma unroll
+            for (int k = 0; k < E; ++k) {
+#pragma unroll
+                for (int j = 0; j < L; ++j) ps.v[k] = vadd(ps.v[k], vmul(al[j], pd[j].v[k]));
+                pd[0].v[k] = vaypx(bt, pd[L - 1].v[k], pr.v[k]);
+            }
+            if (VNT & 1) st_pack_nt(xs + i * E, ps); else st_pack(xs + i * E, ps);
+            st_pack(d0 + i * E, pd[0]);
+        }
+        i0 += npack * E;
+    }
+    for (long long i = i0; i < n; i += stride) {
+        T xv = xs[i], dl = vzero<T>();
+#pragma unroll
+        for (int j = 0; j < L; ++j) {
+            dl = dj[j][i];
+            xv = vadd(xv, vmul(al[j], dl));
+        }
+        xs[i] = xv;
+        d0[i] = vaypx(bt, dl, rv[i]);
     }
 }
 
@@ -803,6 +921,58 @@ int launch_aypx_beta_x(int dtype, int n, const void *x, void *y, void *xs, long 
     const bool v = vec_ok(dtype, ld, nrhs, {x, y, xs});
     const int vnt = tune().vec_nt >= 0 ? tune().vec_nt : vec_nt;
     CG_DISPATCH(dtype, aypx_beta_x_impl, n, x, y, xs, ld, partials, P, nrhs, sc, v, vnt, st, stop);
+}
+template <typename T>
+static int aypx_beta_out_impl(int n, const void *r, const void *din, void *dout, long long ld, const void *partials, int P, int nrhs,
+                              const CgScalars &sc, bool vec, int vnt, hipStream_t st) {
+    dim3 g(vec_grid(n, VT<T>::dtype, nrhs), nrhs), blk(kBlock);
+    auto *pp = static_cast<const typename VT<T>::acc *>(partials);
+#define CG_AO(V, N) hipLaunchKernelGGL((aypx_beta_out_kernel<T, kBlock, V, N>), g, blk, 0, st, n, (const T *)r, (const T *)din, (T *)dout, ld, pp, P, sc.krr, \
+                                       nrhs, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (const int *)sc.iter)
+    if (vec && (vnt & 1)) CG_AO(true, 1); else if (vec) CG_AO(true, 0); else CG_AO(false, 0);
+#undef CG_AO
+    return check_launch("aypx_beta_out");
+}
+int launch_aypx_beta_out(int dtype, int n, const void *r, const void *d_in, void *d_out, long long ld, const void *partials, int P,
+                         int nrhs, const CgScalars &sc, hipStream_t st, int vec_nt) {
+    if (n <= 0) return CGAMD_OK;
+    if (d_in == d_out) return fail(CGAMD_ERR_INVALID, "aypx_beta_out: the step is out of place");
+    const bool v = vec_ok(dtype, ld, nrhs, {r, d_in, d_out});
+    const int vnt = tune().vec_nt >= 0 ? tune().vec_nt : vec_nt;
+    CG_DISPATCH(dtype, aypx_beta_out_impl, n, r, d_in, d_out, ld, partials, P, nrhs, sc, v, vnt, st);
+}
+template <typename T, int L>
+static int aypx_beta_xlag_run(int n, const void *r, void *const *dirs, void *xs, long long ld, const void *partials, int P, int nrhs,
+                              const CgScalars &sc, bool vec, int vnt, hipStream_t st) {
+    dim3 g(vec_grid(n, VT<T>::dtype, nrhs), nrhs), blk(kBlock);
+    auto *pp = static_cast<const typename VT<T>::acc *>(partials);
+    LagDirs<T, L - 1> older;
+    for (int j = 1; j < L; ++j) older.d[j - 1] = (const T *)dirs[j];
+#define CG_XL(V, N) hipLaunchKernelGGL((aypx_beta_xlag_kernel<T, kBlock, V, N, L>), g, blk, 0, st, n, (const T *)r, (T *)dirs[0], older, (T *)xs, ld, pp, P, \
+                                       sc.krr, nrhs, (const T *)sc.alpha, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (const int *)sc.iter)
+    if (!vec) CG_XL(false, 0);
+    else if ((vnt & 5) == 5) CG_XL(true, 5);      // (bit 2 only where x streams too: working sets beyond the caches)
+    else if (vnt & 1) CG_XL(true, 1);
+    else CG_XL(true, 0);
+#undef CG_XL
+    return check_launch("aypx_beta_xlag");
+}
+template <typename T>
+static int aypx_beta_xlag_impl(int lag, int n, const void *r, void *const *dirs, void *xs, long long ld, const void *partials, int P, int nrhs,
+                               const CgScalars &sc, bool vec, int vnt, hipStream_t st) {
+    if (lag == 2) return aypx_beta_xlag_run<T, 2>(n, r, dirs, xs, ld, partials, P, nrhs, sc, vec, vnt, st);
+    if (lag == 4) return aypx_beta_xlag_run<T, 4>(n, r, dirs, xs, ld, partials, P, nrhs, sc, vec, vnt, st);
+    return aypx_beta_xlag_run<T, 8>(n, r, dirs, xs, ld, partials, P, nrhs, sc, vec, vnt, st);
+}
+int launch_aypx_beta_xlag(int dtype, int n, int lag, const void *r, void *const *dirs, void *xs, long long ld, const void *partials, int P,
+                          int nrhs, const CgScalars &sc, hipStream_t st, int vec_nt) {
+    if (lag != 2 && lag != 4 && lag != 8) return fail(CGAMD_ERR_INVALID, "aypx_beta_xlag: groups of 2, 4 or 8 iterations");
+    if (n <= 0) return CGAMD_OK;
+    bool v = vec_ok(dtype, ld, nrhs, {r, xs});
+    for (int j = 0; j < lag; ++j) v = v && aligned16(dirs[j]);
+    // (bit 2, the direction buffers' last-use loads, is this step's own: the dev.x_lag_dnt hook)
+    const int vnt = ((tune().vec_nt >= 0 ? tune().vec_nt : vec_nt) & 3) | (tune().dev_x_lag_dnt ? 4 : 0);
+    CG_DISPATCH(dtype, aypx_beta_xlag_impl, lag, n, r, dirs, xs, ld, partials, P, nrhs, sc, v, vnt, st);
 }
 bool fold_alpha_ok(int n_partials, int fold_max) { return tune().dev_no_fold_alpha == 0 && n_partials <= (fold_max > 0 ? fold_max : kFoldAlphaMax); }
 int launch_axpy2_dot_alpha(int dtype, int n, const void *d, void *x, const void *q, void *r, long long ld, const void *part_dq,

@@ -344,6 +344,13 @@ int cgamd_solver_layout(cgamd_solver *s);
  * which return the same bits), 2 / 3 / 4 / 5 = the
  * loops of DESIGN.md section 4, 8 = the reference's op structure (CGAMD_UNFUSED); negative: error */
 int cgamd_solver_loop_launches(cgamd_solver *s);
+/* L >= 2: the handle's captured runs of 8 iterations (three / four-launch loop, no preconditioner) bring x up to date once per L
+ * iterations instead of in every one: x is read by nothing inside the loop, so the directions of a group are kept and its last
+ * iteration applies all L updates in iteration order.  Every call returns with nothing pending and x, r, d,
+ * the scalars and the history bit-identical to L = 1.  By default (L = 4) on the four-launch loop of large systems (more than 2048 d.q
+ * partials, i.e. beyond 524k rows) that no resident loop takes; costs (L - 2) * size * nRHS values of device memory beside the
+ * handle's vectors -- a handle that cannot have them runs L = 1.  1 = x is updated in every iteration; negative: error */
+int cgamd_solver_x_lag(cgamd_solver *s);
 /* > 0: this handle's single-RHS SpMV reads one-byte column codes instead of aCols (4 -> 1 byte of index traffic per non-zero),
  * the value is the number of distinct (column - row) offsets of the matrix (at most 256; stencil / structured-grid FE matrices
  * have 5 to 27).  Built at create / reload for matrices above 32 MB (tuning key "index_codes_min_mb"; smaller systems run
@@ -368,7 +375,7 @@ long long cgamd_solver_spmv_bytes(cgamd_solver *s);
 long long cgamd_solver_iter_bytes(cgamd_solver *s, int fused);
 /* the bytes this handle's own kernels move per SpMV / per iteration of its launched loop: index bytes per non-zero as the SpMV
  * reads them (1 with one-byte column codes, 2 with 16-bit block-relative columns, 4 with aCols) and the loop's own vector passes
- * (10 by default).  This is the figure a roofline FRACTION is priced on; the SURVEY 8(d) figures above are the
+ * (10 by default; (9 L + 1) / L in the steady state of a handle with cgamd_solver_x_lag() = L >= 2).  This is the figure a roofline FRACTION is priced on; the SURVEY 8(d) figures above are the
  * reference's CSR byte model (an "effective" rate). */
 long long cgamd_solver_spmv_moved_bytes(cgamd_solver *s);
 long long cgamd_solver_iter_moved_bytes(cgamd_solver *s);
