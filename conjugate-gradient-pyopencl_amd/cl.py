@@ -419,17 +419,20 @@ class Solver:
         check(self._lib.cgamd_solver_spmv(self.handle, ptr(x), ptr(y), int(fused_dot)))
 
     SPMV_FAMILIES = ("stream", "rowblock", "vc", "vcp", "chunked", "spmm", "batched")
+    SPMV_FAMILIES_EXTRA = ("rowcode",)      # family numbers from len(SPMV_FAMILIES) on
     SPMV_FORM_FIELDS = ("family", "vec", "width", "index_bits", "value_codes", "nt", "fused", "wide", "grid", "partials")
 
     def last_spmv_form(self):
         """what this thread's last SpMV launch really was (include/cgamd.h cgamd_last_spmv_form), as a dict: family by name, `width` =
-        batch length / lanes per row / SpMM group width, `index_bits` 0 / 8 / 16, `value_codes` 0 / 1 (own stream) / 2 (joint)"""
+        batch length / lanes per row / SpMM group width, `index_bits` 0 / 8 / 16, `value_codes` 0 / 1 (own stream) / 2 (joint) / 3 (one row-pattern
+        byte per row)"""
         out = (ctypes.c_int * len(self.SPMV_FORM_FIELDS))()
         got = self._lib.cgamd_last_spmv_form(out, len(out))
         if got < 0:
             check(-got)
         form = dict(zip(self.SPMV_FORM_FIELDS, (int(v) for v in out)))
-        form["family"] = self.SPMV_FAMILIES[form["family"]] if form["family"] >= 0 else None
+        names = self.SPMV_FAMILIES + self.SPMV_FAMILIES_EXTRA
+        form["family"] = names[form["family"]] if form["family"] >= 0 else None
         return form
 
     def dot_partials(self):
@@ -477,6 +480,11 @@ class Solver:
     def joint_codes(self):
         """distinct (offset, value) pairs when the SpMV reads one joint code byte per non-zero, else 0"""
         return self._lib.cgamd_solver_joint_codes(self.handle)
+
+    @property
+    def row_codes(self):
+        """distinct row patterns when the SpMV reads one pattern byte per row (no per-non-zero bytes, no row pointers), else 0"""
+        return self._lib.cgamd_solver_row_codes(self.handle)
 
     def iter_bytes(self, fused=False):
         return self._lib.cgamd_solver_iter_bytes(self.handle, int(fused))

@@ -59,6 +59,13 @@ struct SpmvPlan {
     const unsigned char *jcodes = nullptr;  // [nnz + pad]
     const int *jdict_off = nullptr;         // [256] offsets
     const void *jdict_val = nullptr;        // [256] values
+    // one-byte ROW-PATTERN codes (build_row_codes): row i multiplies the rdict_len[c] pairs (rdict_off[c][j], rdict_val[c][j]), c = rcodes[i]
+    const unsigned char *rcodes = nullptr;  // [n + pad]
+    const int *rdict_len = nullptr;         // [256] entries of the pattern
+    const int *rdict_off = nullptr;         // [256][8] column offsets in BYTES (times the size of a value)
+    const void *rdict_val = nullptr;        // [256][8] values
+    int n_patterns = 0;                     // patterns that occur (the kernel stages only these)
+    const int *rcodes_for = nullptr;        // the aPointers array the codes were made from (with codes_for / vcodes_for: the matrix)
 };
 SpmvPlan make_spmv_plan(int n);
 // fills plan->max_span / chunk_span from the matrix structure; synchronises `st`; scratch_dev: >= 32 bytes
@@ -78,6 +85,16 @@ int build_index_codes(int n, long long nnz, const int *ptr_dev, const int *cols_
 // whose row blocks span fewer than 65 536 columns: *codes_out 2 nnz + 64 bytes, *base_out one int per row block; null when not codable
 int build_joint_codes(int dtype, long long nnz, const unsigned char *codes, const unsigned char *vcodes, const int *dict, const void *vdict,
                       hipStream_t st, unsigned char **jcodes_out, int **joff_out, void **jval_out, int *n_pairs);
+// one byte per ROW naming its pattern (index_codes.hip "ROW-PATTERN codes"), from the joint codes and the row pointers of a matrix whose
+// longest row has at most 7 entries.  *rcodes_out: n + 64 bytes; *rdict_out: ONE allocation of row_dict_bytes, values [256][8] first,
+// then the byte offsets [256][8] (row_dict_off_at), then the lengths [256] (row_dict_len_at); both null beyond 256 patterns
+constexpr size_t row_dict_off_at(size_t value_size) { return 256 * 8 * value_size; }
+constexpr size_t row_dict_len_at(size_t value_size) { return row_dict_off_at(value_size) + 256 * 8 * sizeof(int); }
+constexpr size_t row_dict_bytes(size_t value_size) { return row_dict_len_at(value_size) + 256 * sizeof(int); }
+// n rows, the first n_user the caller's (the rest appended and empty): *n_patterns = dictionary entries, *n_user_patterns = patterns of
+// the caller's rows
+int build_row_codes(int dtype, int n, int n_user, const int *ptr_dev, const unsigned char *jcodes, const int *joff, const void *jval, hipStream_t st,
+                    unsigned char **rcodes_out, void **rdict_out, int *n_patterns, int *n_user_patterns);
 int build_value_codes(int dtype, long long nnz, const void *vals_dev, hipStream_t st, unsigned char **vcodes_out, void **vdict_out, int *n_values);
 int build_index_codes16(int n, long long nnz, const int *ptr_dev, const int *cols_dev, hipStream_t st, unsigned char **codes_out, int **base_out);
 void finalize_spmv_plan(SpmvPlan *plan, int dtype, int nrhs, int n, long long nnz, const void *vals, const int *cols);
@@ -118,6 +135,8 @@ struct Tuning {
                                     // too (0 = plain loads: A/B, profiles/x_lag/ab.log: lag 4 5970 -> 6059 it/s at 10M rows fp64, no difference at 100M)
     int value_codes = 1;            // one-byte value codes on top of the one-byte column codes where the matrix has at most 256 distinct entries (0 = off: A/B, tests)
     int dev_joint_codes = 1;        // value-coded SpMV: one byte per non-zero naming the (offset, value) pair where at most 256 pairs occur (0 = two bytes: A/B)
+    int dev_row_codes = 1;          // joint-coded SpMV: one byte per ROW naming its pattern where at most 256 row patterns occur (0 = joint codes: A/B)
+    int dev_row_codes_min_mb = 32;  // ... for matrices above this size (its own threshold: index_codes_min_mb = 0 alone keeps the joint form)
     int dev_vc_pipe = 1;            // value-coded SpMV: gathers pipelined across the row blocks of a work-group (0 = one block at a time: A/B)
     int dev_generic_spmv = 0;       // 1: the generic chunked CSR stream for every matrix (the row-block kernels' fallback, tested against them)
     int resident_lock = 1;          // 0: no per-GPU serialisation of resident launches (ranks of ONE job sharing a GPU in a rehearsal)

@@ -414,4 +414,144 @@ int build_joint_codes(int dtype, long long nnz, const unsigned char *codes, cons
     return build_joint_codes_impl<float2>(nnz, codes, vcodes, dict, vdict, st, jcodes_out, joff_out, jval_out, n_pairs);
 }
 
+// -------------------------------------------------------------------------------------------------
+// ROW-PATTERN codes: a row's pattern is its sequence of joint codes in stored order -- the (offset, value) pairs it multiplies, one
+// after the other.  A constant-coefficient stencil has few of them (the 7-point Laplacian 27: interior, 6 faces, 12 edges, 8 corners;
+// the 5-point one 9), so where no row is longer than 7 entries and at most 256 patterns occur, ONE byte per ROW names the pattern and
+// the SpMV streams n bytes of matrix instead of nnz bytes and the row pointers.  The key of a row is one 64-bit word: the length in
+// byte 0, the joint codes in bytes 1 .. 7, unused bytes 0 (rows without entries: key 0).  Passes as for the value codes: insert into
+// an open-addressing table (stops at the 257th key), one work-group numbers the keys BY ASCENDING KEY (a dump of the dictionary is
+// the same run to run; the SpMV does not depend on the numbering) and writes the dictionary, encode.
+// -------------------------------------------------------------------------------------------------
+constexpr int kRSlots = 2048;
+constexpr unsigned long long kREmpty = ~0ULL;      // (length byte 255: no row has it)
+CG_DEV unsigned rhash(unsigned long long k) {
+    k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 29;
+    return (unsigned)k & (kRSlots - 1);
+}
+CG_DEV unsigned long long row_key(const int *__restrict__ ptr, const unsigned char *__restrict__ jcodes, long long row) {
+    const int s = ptr[row], len = ptr[row + 1] - s;        // (len <= 7: the caller checked the longest row)
+    unsigned long long key = (unsigned long long)len;
+    for (int j = 0; j < len; ++j) key |= (unsigned long long)jcodes[s + j] << (8 * (j + 1));
+    return key;
+}
+// state: [0] number of distinct keys, [1] failure flag, [2] set when one of the caller's rows (row < n_user) has no entry: the rows a
+// handle appends (pad_rows) are empty too, and the length-0 pattern they bring is not one of the caller's matrix
+__global__ __launch_bounds__(256) void rowcode_insert_kernel(int n, int n_user, const int *__restrict__ ptr, const unsigned char *__restrict__ jcodes,
+                                                             unsigned long long *table, int *state) {
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long row = (long long)blockIdx.x * 256 + threadIdx.x; row < n; row += stride) {
+        if (__hip_atomic_load(state + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+        const unsigned long long key = row_key(ptr, jcodes, row);
+        if (key == 0 && row < n_user && !__hip_atomic_load(state + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicExch(state + 2, 1);
+        unsigned s = rhash(key);
+        for (int probe = 0; probe < kRSlots; ++probe, s = (s + 1) & (kRSlots - 1)) {
+            unsigned long long cur = __hip_atomic_load(table + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (cur == key) break;
+            if (cur == kREmpty) {
+                cur = atomicCAS(table + s, kREmpty, key);
+                if (cur == kREmpty) {                       // a new pattern
+                    if (atomicAdd(state, 1) >= 256) atomicExch(state + 1, 1);
+                    break;
+                }
+                if (cur == key) break;
+            }
+        }
+    }
+}
+// one work-group: occupied slot -> number of smaller keys in the table; dictionary entry of that number (unused slots stay 0)
+template <typename T>
+__global__ __launch_bounds__(1024) void rowcode_number_kernel(const unsigned long long *table, const int *__restrict__ joff, const T *__restrict__ jval,
+                                                              unsigned short *slot_code, int *rlen, int *roff, T *rval) {
+    __shared__ unsigned long long keys[kRSlots];
+    for (int s = threadIdx.x; s < kRSlots; s += 1024) keys[s] = table[s];
+    __syncthreads();
+    for (int s = threadIdx.x; s < kRSlots; s += 1024) {
+        const unsigned long long key = keys[s];
+        if (key == kREmpty) continue;
+        int code = 0;
+        for (int o = 0; o < kRSlots; ++o) code += keys[o] < key;        // (empty slots hold the largest word)
+        slot_code[s] = (unsigned short)code;
+        if (code >= 256) continue;                                      // (cannot happen: the caller checked the count)
+        const int len = (int)(key & 255);
+        rlen[code] = len;
+        for (int j = 0; j < len; ++j) {
+            const int jc = (int)((key >> (8 * (j + 1))) & 255);
+            roff[code * 8 + j] = joff[jc] * (int)sizeof(T);             // byte offsets, as the kernel adds them
+            rval[code * 8 + j] = jval[jc];
+        }
+    }
+}
+__global__ __launch_bounds__(256) void rowcode_encode_kernel(int n, const int *__restrict__ ptr, const unsigned char *__restrict__ jcodes,
+                                                             const unsigned long long *__restrict__ table, const unsigned short *__restrict__ slot_code,
+                                                             unsigned char *__restrict__ rcodes) {
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long row = (long long)blockIdx.x * 256 + threadIdx.x; row < n; row += stride) {
+        const unsigned long long key = row_key(ptr, jcodes, row);
+        unsigned s = rhash(key);
+        while (table[s] != key) s = (s + 1) & (kRSlots - 1);     // present: the insert pass put it there
+        rcodes[row] = (unsigned char)slot_code[s];
+    }
+}
+
+template <typename T>
+static int build_row_codes_impl(int n, int n_user, const int *ptr, const unsigned char *jcodes, const int *joff, const void *jval, hipStream_t st,
+                                unsigned char **rcodes_out, void **rdict_out, int *n_patterns, int *n_user_patterns) {
+    char *scratch = nullptr;
+    const size_t tb = sizeof(unsigned long long) * kRSlots, sb = sizeof(unsigned short) * kRSlots;
+    CG_HIP(hipMalloc((void **)&scratch, tb + sb + 16));
+    auto *table = reinterpret_cast<unsigned long long *>(scratch);
+    auto *slot_code = reinterpret_cast<unsigned short *>(scratch + tb);
+    int *state = reinterpret_cast<int *>(scratch + tb + sb);
+    int h[3] = {0, 1, 0};
+    hipError_t e = hipMemsetAsync(table, 0xff, tb, st);
+    if (e == hipSuccess) e = hipMemsetAsync(state, 0, 12, st);
+    const int grid = (int)std::min<long long>((n + 255LL) / 256, 4096);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(rowcode_insert_kernel, dim3(grid), dim3(256), 0, st, n, n_user, ptr, jcodes, table, state);
+        e = hipMemcpyAsync(h, state, 12, hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess || h[1] != 0 || h[0] < 1 || h[0] > 256) {
+        (void)hipFree(scratch);
+        return e == hipSuccess ? CGAMD_OK : fail(CGAMD_ERR_HIP, std::string("build_row_codes: ") + hipGetErrorString(e));
+    }
+    unsigned char *rcodes = nullptr;
+    char *rdict = nullptr;
+    const size_t db = row_dict_bytes(sizeof(T));
+    e = hipMalloc((void **)&rcodes, (size_t)n + 64);
+    if (e == hipSuccess) e = hipMalloc((void **)&rdict, db);
+    if (e == hipSuccess) e = hipMemsetAsync(rcodes + (size_t)n, 0, 64, st);
+    if (e == hipSuccess) e = hipMemsetAsync(rdict, 0, db, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL((rowcode_number_kernel<T>), dim3(1), dim3(1024), 0, st, table, joff, static_cast<const T *>(jval), slot_code,
+                           reinterpret_cast<int *>(rdict + row_dict_len_at(sizeof(T))), reinterpret_cast<int *>(rdict + row_dict_off_at(sizeof(T))),
+                           reinterpret_cast<T *>(rdict));
+        hipLaunchKernelGGL(rowcode_encode_kernel, dim3(grid), dim3(256), 0, st, n, ptr, jcodes, table, slot_code, rcodes);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(scratch);
+    if (e != hipSuccess) {
+        if (rcodes) (void)hipFree(rcodes);
+        if (rdict) (void)hipFree(rdict);
+        return fail(CGAMD_ERR_HIP, std::string("build_row_codes: ") + hipGetErrorString(e));
+    }
+    *rcodes_out = rcodes; *rdict_out = rdict; *n_patterns = h[0];
+    *n_user_patterns = h[0] - ((n > n_user && !h[2]) ? 1 : 0);
+    return CGAMD_OK;
+}
+// *rcodes_out (n + 64 bytes) and *rdict_out (row_dict_bytes: values [256][8] | byte offsets [256][8] | lengths [256]) are device
+// allocations the caller frees; both null when the rows have more than 256 patterns.  n rows of which the first n_user are the
+// caller's: *n_patterns counts the dictionary entries (what the kernel stages), *n_user_patterns the patterns of the caller's rows
+// (one fewer where only the appended rows are empty).  The caller has checked that no row is longer than 7 entries.  Synchronises `st`.
+int build_row_codes(int dtype, int n, int n_user, const int *ptr_dev, const unsigned char *jcodes, const int *joff, const void *jval, hipStream_t st,
+                    unsigned char **rcodes_out, void **rdict_out, int *n_patterns, int *n_user_patterns) {
+    *rcodes_out = nullptr; *rdict_out = nullptr; *n_patterns = 0; *n_user_patterns = 0;
+    if (n <= 0 || !jcodes || dtype == CGAMD_C128) return CGAMD_OK;
+    if (dtype == CGAMD_F32) return build_row_codes_impl<float>(n, n_user, ptr_dev, jcodes, joff, jval, st, rcodes_out, rdict_out, n_patterns, n_user_patterns);
+    if (dtype == CGAMD_F64) return build_row_codes_impl<double>(n, n_user, ptr_dev, jcodes, joff, jval, st, rcodes_out, rdict_out, n_patterns, n_user_patterns);
+    return build_row_codes_impl<float2>(n, n_user, ptr_dev, jcodes, joff, jval, st, rcodes_out, rdict_out, n_patterns, n_user_patterns);
+}
+
 }  // namespace cgamd

@@ -103,6 +103,9 @@ struct cgamd_solver {
     int *jdict_off = nullptr;
     void *jdict_val = nullptr;
     int n_pairs = 0;
+    unsigned char *rcodes = nullptr;  // one-byte row-pattern codes where at most 256 patterns of at most 7 entries occur (build_row_codes)
+    void *rdict = nullptr;            // their dictionary: values, byte offsets, lengths (row_dict_bytes)
+    int n_patterns = 0, n_user_patterns = 0;     // dictionary entries; patterns of the caller's rows (the appended empty rows may add one)
     // cgamd_solver_iterate_tol: tolerance of the device-side stop for the call in progress (0 = none), and what it reported
     double tol_req = 0.;
     bool tol_served = false, tol_stopped = false;
@@ -370,6 +373,11 @@ static int setup_index_codes(cgamd_solver *s) {
     if (s->jdict_val) { (void)hipFree(s->jdict_val); s->jdict_val = nullptr; }
     s->plan.jcodes = nullptr; s->plan.jdict_off = nullptr; s->plan.jdict_val = nullptr;
     s->n_pairs = 0;
+    if (s->rcodes) { (void)hipFree(s->rcodes); s->rcodes = nullptr; }
+    if (s->rdict) { (void)hipFree(s->rdict); s->rdict = nullptr; }
+    s->plan.rcodes = nullptr; s->plan.rdict_len = nullptr; s->plan.rdict_off = nullptr; s->plan.rdict_val = nullptr; s->plan.n_patterns = 0;
+    s->plan.rcodes_for = nullptr;
+    s->n_patterns = 0; s->n_user_patterns = 0;
     const size_t matrix_bytes = (size_t)s->nnz * (dtype_size(s->dtype) + 4);
     // a handle whose iterations run in the chip-wide resident loop (matrix in registers) would pay the two coding passes at every
     // create / reload (the stateless cg() reloads per call) for the few launched SpMVs around it
@@ -388,6 +396,22 @@ static int setup_index_codes(cgamd_solver *s) {
                 if (int rc = build_joint_codes(s->dtype, s->nnz, s->codes, s->vcodes, s->dict, s->vdict, s->ctx->stream, &s->jcodes, &s->jdict_off,
                                                &s->jdict_val, &s->n_pairs)) return rc;
                 if (s->jcodes) { s->plan.jcodes = s->jcodes; s->plan.jdict_off = s->jdict_off; s->plan.jdict_val = s->jdict_val; }
+                // ... and one byte per ROW where the rows fit a 64-bit pattern key and few patterns occur (stencils: 9, 27); a threshold
+                // of its own, so that index_codes_min_mb = 0 alone keeps the joint form on a small matrix
+                const size_t vsz = dtype_size(s->dtype);
+                if (s->jcodes && s->nrhs == 1 && s->plan.kind == 5 && s->plan.max_row > 0 && s->plan.max_row <= 7 && s->tune.dev_row_codes &&
+                    s->tune.dev_row_codes_min_mb >= 0 && matrix_bytes > ((size_t)s->tune.dev_row_codes_min_mb << 20) &&
+                    (unsigned long long)s->n * vsz < (1ULL << 30)) {
+                    if (int rc = build_row_codes(s->dtype, s->n, s->n_user, s->ptr, s->jcodes, s->jdict_off, s->jdict_val, s->ctx->stream, &s->rcodes,
+                                                 &s->rdict, &s->n_patterns, &s->n_user_patterns)) return rc;
+                    if (s->rcodes) {
+                        const char *rd = static_cast<const char *>(s->rdict);
+                        s->plan.rcodes = s->rcodes; s->plan.rdict_val = rd; s->plan.n_patterns = s->n_patterns;
+                        s->plan.rdict_off = reinterpret_cast<const int *>(rd + row_dict_off_at(vsz));
+                        s->plan.rdict_len = reinterpret_cast<const int *>(rd + row_dict_len_at(vsz));
+                        s->plan.rcodes_for = s->ptr;
+                    }
+                }
             }
         }
         return CGAMD_OK;
@@ -744,7 +768,7 @@ int cgamd_solver_destroy(cgamd_solver *s) {
         if (s->cols) (void)hipFree(s->cols);
     }
     void *bufs[] = {s->slab, s->part_dq, s->part_rr, s->sc.alpha, s->sc.beta, s->sc.delta,
-                    s->sc.history, s->sc.iter, s->mdiag, s->part_rz, s->rho2, s->tri_coef, s->tri_part, s->tri_cstart, s->tri.maps, s->sc.stage, s->sc.ticket, s->res_sync, s->resw_sync, s->dlag, s->codes, s->dict, s->rm_pace, s->vcodes, s->vdict, s->jcodes, s->jdict_off, s->jdict_val};
+                    s->sc.history, s->sc.iter, s->mdiag, s->part_rz, s->rho2, s->tri_coef, s->tri_part, s->tri_cstart, s->tri.maps, s->sc.stage, s->sc.ticket, s->res_sync, s->resw_sync, s->dlag, s->codes, s->dict, s->rm_pace, s->vcodes, s->vdict, s->jcodes, s->jdict_off, s->jdict_val, s->rcodes, s->rdict};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (s->stop_rec) (void)hipFree(s->stop_rec);
@@ -1491,21 +1515,25 @@ static bool joint_form(const cgamd_solver *s) {
     const int fit = s->plan.max_row <= 0 ? 8 : s->plan.max_row <= 4 ? 4 : s->plan.max_row == 5 ? 5 : s->plan.max_row <= 7 ? 7 : 8;
     return s->plan.jcodes && s->nrhs == 1 && s->plan.max_row > 0 && s->plan.max_row <= fit && dtype_size(s->dtype) <= 8;
 }
+// ... on row-pattern codes (spmv_impl takes that form before the joint one)
+static bool row_form(const cgamd_solver *s) { return joint_form(s) && s->plan.rcodes && s->plan.rcodes_for == s->ptr && s->tune.dev_row_codes != 0 && s->tune.dev_vc_pipe != 0; }
 long long cgamd_solver_spmv_moved_bytes(cgamd_solver *s) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
+    if (row_form(s)) return (long long)s->n_user + 2LL * s->n_user * V;       // one code byte per row, x read, y written: no per-non-zero bytes, no row pointers
     const long long value_bytes = joint_form(s) ? 0 : s->plan.vcodes ? 1 : V * value_arrays(s);      // value codes: one byte per entry instead of the value; joint codes: one byte for both
     return s->nnz * (value_bytes + index_bytes_per_nnz(s)) + ((long long)s->n_user + 1) * 4 + 2LL * s->n_user * V * s->nrhs;
 }
 int cgamd_solver_value_codes(cgamd_solver *s) { return s ? s->n_values : -CGAMD_ERR_INVALID; }
 int cgamd_solver_joint_codes(cgamd_solver *s) { return s ? (joint_form(s) ? s->n_pairs : 0) : -CGAMD_ERR_INVALID; }
+int cgamd_solver_row_codes(cgamd_solver *s) { return s ? (row_form(s) ? s->n_user_patterns : 0) : -CGAMD_ERR_INVALID; }
 long long cgamd_solver_iter_moved_bytes(cgamd_solver *s) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
     const long long passes = (s->nsys && s->mdiag) ? 12 : (s->flags & CGAMD_UNFUSED) ? 14 : s->mdiag ? 12 : 10;
     const long long lag = x_lag_now(s);
     const long long value_bytes = joint_form(s) ? 0 : s->plan.vcodes ? 1 : V * value_arrays(s);
-    const long long matrix = s->nnz * (value_bytes + index_bytes_per_nnz(s)) + ((long long)s->n_user + 1) * 4;
+    const long long matrix = row_form(s) ? (long long)s->n_user : s->nnz * (value_bytes + index_bytes_per_nnz(s)) + ((long long)s->n_user + 1) * 4;
     if (s->tri_on) return matrix + tri_passes(s) * s->n_user * V;
     // the deferred x update: the d steps of a group of L iterations move 4 L + 1 vectors instead of 5 L, the steady state of a
     // handle iterated in multiples of U: (9 L + 1) / L passes per iteration

@@ -580,6 +580,129 @@ __global__ __launch_bounds__(BLOCK) void spmv_rowblock_vcp_kernel(SpmvArgs<T> a)
 }
 
 // -------------------------------------------------------------------------------------------------
+// ROW-PATTERN codes (build_row_codes): one byte per ROW names the row's pattern -- its (byte offset, value) pairs in stored order.
+// Per launch the kernel streams n code bytes, reads x and writes y: no row pointers, no per-non-zero bytes, no code staging and no
+// barrier per row block in front of the gathers.  The dictionary (only the patterns that occur: 27 for the 7-point Laplacian, 2.7 KB
+// in fp64) goes into LDS once per work-group -- the one barrier before the walk -- which takes kVcBlocks row blocks like the joint
+// form (same schedule, same grid).
+// A wave whose 64 rows are all live and share ONE pattern (three quarters of the waves of the 250 x 200 x 200 grid) walks it with
+// wave-uniform length, offsets and values: exactly `len` steps, each one contiguous 64-value load and one multiply-add, no masked
+// slot and no per-entry look-up.  Every other wave (pattern changes inside it, the ragged end of the matrix) looks its lanes'
+// patterns up in LDS and walks 7 masked slots as the joint kernel does.  Both do sum = vfma(val_j, x[row + off_j], sum) from zero in
+// stored order on the bits of the joint dictionary: same y, same d.q partials (one per 256-row block, the tree of block_sum<256>;
+// the four blocks' trees meet behind one barrier, as in the vc kernel) as every other one-lane-per-row form.
+// -------------------------------------------------------------------------------------------------
+template <typename T> struct RowcodeArgs {
+    int n, row_blocks, cycle, n_patterns;
+    const T *x;
+    T *y;
+    const T *dvec;
+    typename VT<T>::acc *partials;
+    const unsigned char *rcodes;    // [n + pad]
+    const int *rdict_len;           // [256]
+    const int *rdict_off;           // [256][8] byte offsets
+    const T *rdict_val;             // [256][8]
+};
+constexpr int kRowSlots = 7;      // longest coded row
+template <typename T, int BLOCK, bool NT, bool FUSE_DOT>
+__global__ __launch_bounds__(BLOCK) void spmv_rowcode_kernel(RowcodeArgs<T> a) {
+    using A = typename VT<T>::acc;
+    extern __shared__ __attribute__((aligned(16))) char dyn_smem[];       // [np][8] values | [np][8] byte offsets | [np] lengths
+    __shared__ A red[kVcBlocks][BLOCK / kWave];
+    static_assert(BLOCK == 256, "row blocks of 256 rows");
+    const int t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
+    const int supers = (a.row_blocks + kVcBlocks - 1) / kVcBlocks;
+    const int srb = rowblock_of(blockIdx.x, supers, a.cycle);
+    if (srb < 0) return;
+    const int rb0 = srb * kVcBlocks, nb = min(kVcBlocks, a.row_blocks - rb0);
+    const int np = a.n_patterns;
+    T *sval = reinterpret_cast<T *>(dyn_smem);
+    int *soff = reinterpret_cast<int *>(dyn_smem + (size_t)np * 8 * sizeof(T));
+    int *slen = soff + np * 8;
+    // the code bytes of all four blocks first: independent loads, in flight while the dictionary is staged
+    int code[kVcBlocks];
+#pragma unroll
+    for (int i = 0; i < kVcBlocks; ++i) {
+        const int rc = min((rb0 + min(i, nb - 1)) * BLOCK + t, a.n - 1);
+        code[i] = NT ? __builtin_nontemporal_load(a.rcodes + rc) : a.rcodes[rc];
+    }
+    for (int k = t; k < np * 8; k += BLOCK) { sval[k] = a.rdict_val[k]; soff[k] = a.rdict_off[k]; }
+    if (t < np) slen[t] = a.rdict_len[t];         // (at most 256 patterns)
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(a.x), 0, 0x7ffffffc, 0x00020000);
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t xrs_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(FUSE_DOT ? a.dvec : a.x), 0, 0x7ffffffc, 0x00020000);
+    __syncthreads();
+    [[maybe_unused]] A dotw[kVcBlocks];
+#pragma unroll
+    for (int i = 0; i < kVcBlocks; ++i) {
+        dotw[i] = vzero<A>();
+        if (i >= nb) continue;                      // (uniform; the last work-group of the matrix may hold fewer row blocks)
+        const int row = (rb0 + i) * BLOCK + t;
+        const bool live = row < a.n;
+        const unsigned row8 = (unsigned)min(row, a.n - 1) * (unsigned)sizeof(T);
+        [[maybe_unused]] T dv = vzero<T>();
+        if (FUSE_DOT) dv = buf_gather<T>(xrs_d, row8);
+        const int c = code[i], c0 = __builtin_amdgcn_readfirstlane(c);
+        T sum = vzero<T>();
+        const bool uniform = __all(live && c == c0);
+        // the pattern's 8 offset slots in two 16-byte LDS reads and its values in 16-byte reads, all issued before the first gather (a
+        // uniform wave reads at one address: a broadcast); slots past the row's end hold 0 in the dictionary
+        const int cc = uniform ? c0 : c;
+        const int len = uniform ? __builtin_amdgcn_readfirstlane(slen[c0]) : (live ? slen[c] : 0);
+        int po[8];
+        T pv[8];
+        {
+            const i32x4 o0 = *reinterpret_cast<const i32x4 *>(soff + cc * 8), o1 = *reinterpret_cast<const i32x4 *>(soff + cc * 8 + 4);
+            po[0] = o0.x; po[1] = o0.y; po[2] = o0.z; po[3] = o0.w; po[4] = o1.x; po[5] = o1.y; po[6] = o1.z; po[7] = o1.w;
+            using V = typename Chunk16<T>::V;
+            constexpr int EPC = 16 / (int)sizeof(T);
+#pragma unroll
+            for (int k = 0; k < 8 / EPC; ++k) {
+                const V v = *reinterpret_cast<const V *>(sval + cc * 8 + k * EPC);
+                __builtin_memcpy(&pv[k * EPC], &v, 16);
+            }
+        }
+        T xv[kRowSlots];
+        if (uniform) {
+            // one pattern for the whole wave: length, offsets and values are wave-uniform; exactly len steps, no masked slot
+#pragma unroll
+            for (int j = 0; j < kRowSlots; ++j)
+                if (j < len) xv[j] = buf_gather<T>(xrs, row8 + (unsigned)po[j]);
+#pragma unroll
+            for (int j = 0; j < kRowSlots; ++j)
+                if (j < len) sum = vfma(pv[j], xv[j], sum);
+        } else {
+            // each lane its own pattern; slots past the row's end gather the row's own entry and are dropped
+#pragma unroll
+            for (int j = 0; j < kRowSlots; ++j) xv[j] = buf_gather<T>(xrs, j < len ? row8 + (unsigned)po[j] : row8);
+#pragma unroll
+            for (int j = 0; j < kRowSlots; ++j) {
+                const T nxt = vfma(pv[j], xv[j], sum);
+                sum = vsel(j < len, nxt, sum);
+            }
+        }
+        A dot1 = vzero<A>();
+        if (live) {
+            a.y[row] = sum;
+            if (FUSE_DOT) dot1 = to_acc(vmul(dv, sum));
+        }
+        if (FUSE_DOT) dotw[i] = wave_sum(dot1);
+    }
+    if (FUSE_DOT) {                         // block_sum<256> of every block behind one barrier (same tree, same order; red is written once)
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < kVcBlocks; ++i) red[i][wave] = dotw[i];
+        }
+        __syncthreads();
+        if (t < nb) {
+            A v = red[t][0];
+#pragma unroll
+            for (int w = 1; w < BLOCK / kWave; ++w) v = vadd(v, red[t][w]);
+            a.partials[rb0 + t] = v;
+        }
+    }
+}
+
+// -------------------------------------------------------------------------------------------------
 // The same kernel for DENSER rows (a 256-row slice no longer fits LDS: > ~21 non-zeros per row in fp64).  The work-group
 // still owns 256 rows and writes one d.q partial, but stages and walks them in LPR chunks of 256/LPR rows, LPR = 2, 4 or
 // 8 lanes per row: lane l of a row takes entries s+l, s+l+LPR, ... (consecutive lanes -> consecutive entries -> for
@@ -938,9 +1061,9 @@ void set_kernel_event_pair(hipEvent_t *pair) { t_kernel_events = pair; }
 
 // cgamd_last_spmv_form: what the calling thread's most recent launch_spmv launched, stored AT the launch sites of spmv_impl (the
 // template arguments of the instance that goes out, not a second reading of the plan), so that a test can assert the form it was
-// written for.  [0] family (0 stream, 1 row-block, 2 vc, 3 vcp, 4 chunked, 5 grouped SpMM; -1: nothing launched yet), [1] VEC,
+// written for.  [0] family (0 stream, 1 row-block, 2 vc, 3 vcp, 4 chunked, 5 grouped SpMM, 7 row-pattern codes; -1: nothing launched yet), [1] VEC,
 // [2] batch length / lanes per row / group width, [3] index encoding (0 aCols, 8, 16), [4] value encoding (0 aValues, 1 two
-// code streams, 2 joint), [5] NT, [6] fused d.q, [7] wide, [8] grid.x, [9] d.q partials per right-hand side (0 when not fused).
+// code streams, 2 joint, 3 one pattern byte per row), [5] NT, [6] fused d.q, [7] wide, [8] grid.x, [9] d.q partials per right-hand side (0 when not fused).
 static thread_local int t_form[kSpmvFormFields] = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 static inline void record_form(int family, bool vec, int width, int ienc, int venc, bool nt, bool fused, bool wide, unsigned gx, int parts) {
     t_form[0] = family; t_form[1] = vec; t_form[2] = width; t_form[3] = ienc; t_form[4] = venc;
@@ -1036,6 +1159,24 @@ static int spmv_impl(const SpmvPlan &plan, int n, long long nnz, const void *val
                 const bool pipe = plan.max_row > 0 && plan.max_row <= unroll && tune().dev_vc_pipe != 0;
                 // ... and where at most 256 (offset, value) pairs occur: one joint code byte per non-zero
                 const bool joint = pipe && plan.jcodes && tune().dev_joint_codes != 0;
+                // ... and where the rows follow at most 256 patterns: one byte per ROW (build_row_codes), no row pointers and no code staging
+                if (joint && plan.rcodes && plan.rcodes_for == ptr && tune().dev_row_codes != 0) {
+                    RowcodeArgs<T> ra;
+                    ra.n = n; ra.row_blocks = plan.row_blocks; ra.cycle = cyc; ra.n_patterns = plan.n_patterns;
+                    ra.x = a.x; ra.y = a.y; ra.dvec = a.dvec; ra.partials = a.partials;
+                    ra.rcodes = plan.rcodes; ra.rdict_len = plan.rdict_len; ra.rdict_off = plan.rdict_off;
+                    ra.rdict_val = static_cast<const T *>(plan.rdict_val);
+                    const size_t ldsr = (size_t)plan.n_patterns * (8 * sizeof(T) + 8 * sizeof(int) + sizeof(int));
+                    record_form(7, true, unroll, 8, 3, nt, fuse, false, gvc.x, plan.row_blocks);
+                    if (nt) {
+                        if (fuse) CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, true, true>), gvc, block, ldsr, st, ra);
+                        else CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, true, false>), gvc, block, ldsr, st, ra);
+                    } else {
+                        if (fuse) CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, false, true>), gvc, block, ldsr, st, ra);
+                        else CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, false, false>), gvc, block, ldsr, st, ra);
+                    }
+                    return check_launch("spmv_rowcode");
+                }
                 if (joint) { a.codes = plan.jcodes; a.dict = plan.jdict_off; a.vdict = static_cast<const T *>(plan.jdict_val); a.vcodes = nullptr; }
 #define CG_VC(NT, UNR)                                                                                                  \
     do {                                                                                                                \

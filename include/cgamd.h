@@ -368,6 +368,12 @@ int cgamd_solver_value_codes(cgamd_solver *s);
  * longest row fits one batch of the row walk (constant-coefficient stencils: as many pairs as offsets); the value is the number of
  * pairs.  0: it reads the column codes and the value codes (2 bytes), or aCols / aValues. */
 int cgamd_solver_joint_codes(cgamd_solver *s);
+/* > 0: the SpMV reads ONE byte per ROW that names the row's pattern -- its (column offset, value) pairs in stored order -- instead of a
+ * byte per non-zero and the row pointers: matrices that run on joint codes, above 32 MB (cgamd_tune("dev.row_codes_min_mb")), with rows
+ * of at most 7 entries and at most 256 distinct patterns (the 7-point Laplacian has 27, the 5-point one 9); the value is the number of
+ * patterns.  Same products in the same order: same bits.  0: another form runs (cgamd_tune("dev.row_codes", 0) keeps the joint one).
+ * cgamd_last_spmv_form reports it as family 7, [2] batch length, [3] 8, [4] 3. */
+int cgamd_solver_row_codes(cgamd_solver *s);
 int cgamd_transpose(cgamd_ctx *ctx, int dtype, int rows, int cols, const void *in, void *out);
 /* algorithmic HBM bytes of one SpMV / one CG iteration of this solver (SURVEY §8d formulae: 14 vector passes for the
  * reference's op structure, 11 for its "fused minimum"; the default loop here moves 10) */
