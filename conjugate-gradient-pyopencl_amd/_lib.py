@@ -101,6 +101,8 @@ def load():
         "cgamd_solver_spmm_rowmajor": (ci, [vp, vp, vp, ci]),
         "cgamd_last_spmv_form": (ci, [ctypes.POINTER(ci), ci]),
         "cgamd_solver_dot_partials": (ci, [vp, vp, ll, ctypes.POINTER(ci)]),
+        "cgamd_solver_step_plan": (ci, [vp, ctypes.POINTER(ci), ci]),
+        "cgamd_solver_step_state": (ci, [vp, ci, vp, ll, ctypes.POINTER(ll)]),
         "cgamd_solver_layout": (ci, [vp]),
         "cgamd_solver_loop_launches": (ci, [vp]),
         "cgamd_solver_x_lag": (ci, [vp]),

@@ -444,6 +444,34 @@ class Solver:
         check(self._lib.cgamd_solver_dot_partials(self.handle, ptr(out), out.size, ctypes.byref(per)))
         return out
 
+    STEP_PLAN_FIELDS = ("n", "ld", "vgrid", "n_partials", "kdq", "krr", "fold", "alpha2", "vec", "vec_nt", "x_lag")
+    STEP_STATES = ("part_rr", "part_rz", "alpha", "beta", "delta", "rho2", "iter")
+
+    def step_plan(self):
+        """what the vector and scalar launches of this handle use now (include/cgamd.h cgamd_solver_step_plan), as a dict of ints"""
+        out = (ctypes.c_int * len(self.STEP_PLAN_FIELDS))()
+        got = self._lib.cgamd_solver_step_plan(self.handle, out, len(out))
+        if got < 0:
+            check(-got)
+        return dict(zip(self.STEP_PLAN_FIELDS, (int(v) for v in out)))
+
+    def step_state(self, which):
+        """one piece of the iteration's state, copied from the device after its stream has drained (cgamd_solver_step_state):
+        "part_rr" / "part_rz": (n_rhs, vgrid) float64 / complex128; "alpha", "beta", "delta": (n_rhs,) and "rho2": (2, n_rhs) of the
+        handle's type; "iter": the iteration counter as an int"""
+        idx = self.STEP_STATES.index(which)
+        count = ctypes.c_longlong()
+        probe = np.empty(1, np.complex128)
+        self._lib.cgamd_solver_step_state(self.handle, idx, ptr(probe), 0, ctypes.byref(count))      # too small on purpose: the count
+        if count.value < 1:
+            check(self._lib.cgamd_solver_step_state(self.handle, idx, ptr(probe), 0, ctypes.byref(count)))
+        acc = np.complex128 if self.dtype.kind == "c" else np.float64
+        out = np.empty(count.value, dtype=acc if idx < 2 else np.intc if idx == 6 else self.dtype)
+        check(self._lib.cgamd_solver_step_state(self.handle, idx, ptr(out), out.size, ctypes.byref(count)))
+        if idx == 6:
+            return int(out[0])
+        return out.reshape((self.n_rhs, -1) if idx < 2 else (2, self.n_rhs) if idx == 5 else (self.n_rhs,))
+
     def spmm_rowmajor(self, x, y, n_rhs):
         """Y[size][n_rhs] = A X on the matrix cores; x, y ROW-MAJOR device arrays, n_rhs in {16, 32}, f32/f64"""
         check(self._lib.cgamd_solver_spmm_rowmajor(self.handle, ptr(x), ptr(y), int(n_rhs)))

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "cgamd_internal.h"
+#include "launch_util.h"
 
 using namespace cgamd;
 
@@ -1444,6 +1445,79 @@ int cgamd_solver_dot_partials(cgamd_solver *s, void *out_host, long long cap_val
     if (cap_values < (long long)P * s->nrhs) return fail(CGAMD_ERR_INVALID, "dot_partials: output holds fewer than nRHS * partials values");
     CG_HIP(hipSetDevice(s->ctx->device));
     CG_HIP(hipMemcpyAsync(out_host, s->part_dq, acc_size(s->dtype) * (size_t)P * s->nrhs, hipMemcpyDeviceToHost, s->ctx->stream));
+    CG_HIP(hipStreamSynchronize(s->ctx->stream));
+    return CGAMD_OK;
+}
+
+// ---- test-facing record of the vector and scalar steps (tests/test_gpu_cg_steps.py) ------------------------------------------------
+// Neither entry launches a kernel or changes the handle.  Both refuse a handle whose stream is being captured: a copy or a
+// synchronisation there would end the capture with an error.
+static int step_not_capturing(cgamd_solver *s, const char *who) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const hipError_t e = hipStreamIsCapturing(s->ctx->stream, &cs);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(CGAMD_ERR_HIP, std::string(who) + ": hipStreamIsCapturing: " + hipGetErrorString(e)); }
+    if (cs != hipStreamCaptureStatusNone) return fail(CGAMD_ERR_INVALID, std::string(who) + ": the handle's stream is being captured");
+    return CGAMD_OK;
+}
+// Row-major and tridiagonal handles launch their vector and scalar steps with grids of their own (rm_nwg / rm_vgrid, tri.grid) and keep
+// their partials elsewhere (tri_part): neither entry describes them, both refuse them
+static int step_launched_rhs_major(cgamd_solver *s, const char *who) {
+    if (s->rm || (s->rm_ok && !precond_set(s)) || s->tri_on)
+        return fail(CGAMD_ERR_INVALID, std::string(who) + ": not recorded for row-major and tridiagonal handles");
+    return CGAMD_OK;
+}
+
+// What enqueue_iteration / cgamd_solver_set_rhs pass to the launchers of vector.hip NOW, read from the fields and through the
+// functions they read them from: s->n (size and leading dimension of every launch), s->vgrid, plan.n_partials, sc.kdq / sc.krr,
+// fold_alpha_ok (the folded alpha), the condition of alpha_impl for the two-level cg_alpha2 (vector.hip: stage && ticket &&
+// grid >= 16384, the grid being plan.n_partials in every loop but the UNFUSED one, whose d.q partials are the vgrid of
+// dot_partials), vec_ok on the handle's vectors (and the diagonal of a Jacobi handle, as launch_pcg_* ask), the vec_nt the
+// launchers resolve, x_lag_now.
+constexpr int kStepPlanFields = 11;
+int cgamd_solver_step_plan(cgamd_solver *s, int *out, int n_out) {
+    if (!s || !out || n_out < 1) return -fail(CGAMD_ERR_INVALID, "step_plan: null or empty output");
+    TuneScope ts(&s->tune);
+    if (int rc = step_not_capturing(s, "step_plan")) return -rc;
+    if (int rc = step_launched_rhs_major(s, "step_plan")) return -rc;
+    // the branches of enqueue_iteration that are left: the diagonal preconditioner first, then the UNFUSED flag (eight launches, alpha
+    // from the vgrid partials of dot_partials), else the folded or the separate alpha on the SpMV's d.q partials
+    const bool unfused = (s->flags & CGAMD_UNFUSED) && !s->mdiag;
+    const int alpha_grid = unfused ? s->vgrid : s->plan.n_partials;
+    const bool fold = !unfused && !s->mdiag && fold_alpha_ok(s->plan.n_partials, s->plan.fold_max);
+    bool vec = vec_ok(s->dtype, s->n, s->nrhs, {s->x, s->r, s->d, s->q});
+    if (s->mdiag) vec = vec && aligned16(s->mdiag) && ((m_pitch(s) * (long long)dtype_size(s->dtype)) & 15) == 0;
+    const int f[kStepPlanFields] = {s->n, s->n, s->vgrid, s->plan.n_partials, s->sc.kdq, s->sc.krr, fold ? 1 : 0,
+                                    (!fold && s->sc.stage && s->sc.ticket && alpha_grid >= 16384) ? 1 : 0, vec ? 1 : 0,
+                                    tune().vec_nt >= 0 ? tune().vec_nt : s->plan.vec_nt, x_lag_now(s)};
+    const int k = n_out < kStepPlanFields ? n_out : kStepPlanFields;
+    for (int i = 0; i < k; ++i) out[i] = f[i];
+    return k;
+}
+
+// which: 0 r.r partials [nRHS][vgrid], 1 r.z partials [nRHS][vgrid] (a Jacobi handle), in the accumulator type; 2 alpha (slot 0),
+// 3 beta, 4 delta [nRHS], 5 the rho parity buffer [2][nRHS], in the value type; 6 the iteration counter (one int)
+int cgamd_solver_step_state(cgamd_solver *s, int which, void *out_host, long long cap_values, long long *count) {
+    if (!s || !out_host || !count) return fail(CGAMD_ERR_INVALID, "step_state: null argument");
+    if (int rc = step_not_capturing(s, "step_state")) return rc;
+    if (int rc = step_launched_rhs_major(s, "step_state")) return rc;
+    const void *src = nullptr;
+    size_t each = dtype_size(s->dtype);
+    long long values = s->nrhs;
+    switch (which) {
+    case 0: src = s->part_rr; each = acc_size(s->dtype); values = (long long)s->vgrid * s->nrhs; break;
+    case 1: src = s->part_rz; each = acc_size(s->dtype); values = (long long)s->vgrid * s->nrhs; break;
+    case 2: src = s->sc.alpha; break;
+    case 3: src = s->sc.beta; break;
+    case 4: src = s->sc.delta; break;
+    case 5: src = s->rho2; values = 2LL * s->nrhs; break;
+    case 6: src = s->sc.iter; each = sizeof(int); values = 1; break;
+    default: return fail(CGAMD_ERR_INVALID, "step_state: which is 0 .. 6");
+    }
+    if (!src) return fail(CGAMD_ERR_INVALID, "step_state: the handle has no such buffer (r.z partials and the rho buffer need a diagonal preconditioner)");
+    *count = values;
+    if (cap_values < values) return fail(CGAMD_ERR_INVALID, "step_state: output holds fewer values than the state has");
+    CG_HIP(hipSetDevice(s->ctx->device));
+    CG_HIP(hipMemcpyAsync(out_host, src, each * (size_t)values, hipMemcpyDeviceToHost, s->ctx->stream));
     CG_HIP(hipStreamSynchronize(s->ctx->stream));
     return CGAMD_OK;
 }

@@ -329,6 +329,24 @@ int cgamd_last_spmv_form(int *out, int n_out);
  * (double; two doubles for the complex types), cap_values = accumulators `out_host` holds.  *per_rhs is set even when the
  * capacity is too small (CGAMD_ERR_INVALID then). */
 int cgamd_solver_dot_partials(cgamd_solver *s, void *out_host, long long cap_values, int *per_rhs);
+/* Development entries of the same standing (tests of the vector and scalar steps of an iteration; not part of the interface).  Neither
+ * launches a kernel or changes the handle; both return CGAMD_ERR_INVALID while the handle's stream is being captured, and for handles
+ * that keep their block row-major or run the tridiagonal preconditioner (their steps launch with grids of their own, not recorded).
+ * cgamd_solver_step_plan: what the vector and scalar launches of this handle use NOW, read from the fields the launch sites read.
+ * Writes min(n_out, 11) ints and returns that count (negative: error): [0] working size n (rows including appended ones), [1] leading
+ * dimension of the handle's vectors, [2] r.r / r.z partials per right-hand side (grid.x of the vector launches), [3] d.q partials per
+ * right-hand side as the SpMV writes them (a CGAMD_UNFUSED handle sums the [2] partials of its own dot launch instead, see [7]), [4] / [5] order of the prologue sums over the d.q / r.r partials: 0 thread-strided, K > 0 member-blocked, K
+ * consecutive partials per thread, [6] alpha folded into the r update's prologue, [7] the two-level cg_alpha2 is the alpha launch (the
+ * launcher's rule, restated: not folded and at least 16384 partials to sum),
+ * [8] 16-byte packs (0: the scalar form), [9] the streaming hints (vec_nt) the launchers resolve, [10] iterations per deferred x update
+ * of a captured group (1: every iteration).
+ * cgamd_solver_step_state: waits for the handle's stream and copies one piece of the iteration's state to the host.  which: 0 the r.r
+ * partials, 1 the r.z partials (diagonal preconditioner), [nRHS][plan 2] accumulators (double; two doubles for the complex types);
+ * 2 alpha, 3 beta, 4 delta: nRHS values of the handle's type; 5 the rho parity buffer, [2][nRHS] values; 6 the iteration counter, one
+ * int.  cap_values = values `out_host` holds; *count is set to the number the state has even when the capacity is too small
+ * (CGAMD_ERR_INVALID then). */
+int cgamd_solver_step_plan(cgamd_solver *s, int *out, int n_out);
+int cgamd_solver_step_state(cgamd_solver *s, int which, void *out_host, long long cap_values, long long *count);
 /* SpMM on the matrix cores (BASELINE config 4, "MFMA tall-B tile path"): Y[size][nRHS] = A * X[size][nRHS] with
  * the right-hand-side block in ROW-MAJOR layout (element i of RHS r at [i*nRHS + r]); f64 with nRHS = 16 or 32, f32 with 16, 32
  * or 64, complex64 with 16 or 32; any CSR matrix.  Solvers created with such a width keep their vectors in this layout

@@ -184,6 +184,31 @@ def test_spmv_form_and_dot_partials_entries_without_gpu(pkg):
     assert {"last_spmv_form", "dot_partials"} <= set(dir(pkg.Solver))
 
 
+def test_step_plan_and_step_state_entries_without_gpu(pkg):
+    """the two development entries behind Solver.step_plan() / step_state(): declared, exported, bound with the header's signatures,
+    and loud about null arguments (nothing is written then)"""
+    lib = pkg._lib.load()
+    ext = _declared_functions("cgamd.h")
+    assert "cgamd_solver_step_plan" in ext and "cgamd_solver_step_state" in ext
+    header = open(os.path.join(INCLUDE, "cgamd.h")).read()
+    assert "int cgamd_solver_step_plan(cgamd_solver *s, int *out, int n_out);" in header
+    assert "int cgamd_solver_step_state(cgamd_solver *s, int which, void *out_host, long long cap_values, long long *count);" in header
+    assert {"cgamd_solver_step_plan", "cgamd_solver_step_state"} <= _exports(pkg.LIB_PATH)
+    assert {"cgamd_solver_step_plan", "cgamd_solver_step_state"} <= _exports(pkg.LEGACY_LIB_PATH)
+    assert lib.cgamd_solver_step_plan.argtypes == [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+    assert lib.cgamd_solver_step_state.argtypes == [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong,
+                                                    ctypes.POINTER(ctypes.c_longlong)]
+    plan = (ctypes.c_int * 11)(*([77] * 11))
+    assert lib.cgamd_solver_step_plan(None, plan, 11) == -1 and b"step_plan" in lib.cgamd_last_error()      # -CGAMD_ERR_INVALID
+    assert list(plan) == [77] * 11
+    count = ctypes.c_longlong(5)
+    buf = np.zeros(4)
+    assert lib.cgamd_solver_step_state(None, 0, pkg._lib.ptr(buf), 4, ctypes.byref(count)) == 1
+    assert b"step_state" in lib.cgamd_last_error() and count.value == 5 and not buf.any()
+    assert {"step_plan", "step_state"} <= set(dir(pkg.Solver))
+    assert len(pkg.Solver.STEP_PLAN_FIELDS) == 11 and len(pkg.Solver.STEP_STATES) == 7
+
+
 def test_python_module_mirrors_reference_names(pkg):
     """names and arity of the reference's cl.py (cl.py:16-44,203)"""
     import inspect
