@@ -121,6 +121,9 @@ def load():
         "cgamd_cg_last_timing": (ci, [ctypes.POINTER(ctypes.c_double)]),
         "cgamd_cg_release_cache": (ci, []),
         "cgamd_solver_reload_matrix": (ci, [vp, vp, vp, vp]),
+        "cgamd_solver_refresh_values": (ci, [vp, vp, ci]),
+        "cgamd_solver_last_refresh": (ci, [vp]),
+        "cgamd_solver_graph_captures": (ci, [vp]),
         "cgamd_gen_laplace3d": (ci, [vp, ci, ci, ci, ci, ll, ll, vp, vp, vp, ctypes.POINTER(ll)]),
         "cgamd_gen_poisson2d": (ci, [vp, ci, ci, vp, vp, vp, ctypes.POINTER(ll)]),
         "cgamd_gen_helm_fe_var": (ci, [vp, ci, ci, ctypes.c_double, vp, ctypes.c_double, ci, ci, vp, vp, vp, ctypes.POINTER(ll)]),
@@ -142,6 +145,8 @@ def load():
         "cgamd_dist_set_preconditioner": (ci, [vp, vp]),
         "cgamd_dist_set_preconditioner_jacobi": (ci, [vp]),
         "cgamd_dist_set_preconditioner_line": (ci, [vp, ci]),
+        "cgamd_dist_refresh_values": (ci, [vp]),
+        "cgamd_dist_last_refresh": (ci, [vp]),
         "cgamd_p2p_mailbox_alloc": (ci, [vp, ll, ci, pvp, vp]),
         "cgamd_p2p_mailbox_free": (ci, [vp, vp]),
         "cgamd_dist_attach_p2p": (ci, [vp, vp, vp, vp]),

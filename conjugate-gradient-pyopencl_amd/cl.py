@@ -255,7 +255,7 @@ class Solver:
         self._lib = _lib.load()
         self.batched = bool(batched)
         self.non_zeros = int(non_zeros)
-        on_device = bool(flags & _lib.MATRIX_ON_DEVICE)
+        on_device = self._on_device = bool(flags & _lib.MATRIX_ON_DEVICE)
         if self.batched:
             self._check_batched_values(a_values, int(n_rhs))
         if not on_device:
@@ -298,6 +298,52 @@ class Solver:
         a_pointers = np.ascontiguousarray(a_pointers, dtype=np.int32)
         a_cols = np.ascontiguousarray(a_cols, dtype=np.int32)
         check(self._lib.cgamd_solver_reload_matrix(self.handle, ptr(a_values), ptr(a_pointers), ptr(a_cols)))
+
+    def refresh_values(self, a_values=None):
+        """new VALUES on the same pattern (cgamd_solver_refresh_values): the codes of the SpMV and a preconditioner built from the
+        matrix follow them; the next call must be set_rhs.  None: the borrowed device array (flags MATRIX_ON_DEVICE) was changed in
+        place -- the only form such a handle takes besides the borrowed array itself.  A handle that owns its matrix takes a numpy
+        array (host route) or a torch device tensor / DeviceBuffer (copied on the device); a batched one n_rhs * non_zeros values."""
+        if a_values is None:
+            if not self._on_device:
+                raise ValueError("refresh_values: a handle that owns its matrix takes the new values (a host array or a device buffer); "
+                                 "None means 'the borrowed device array changed in place'")
+            if getattr(self._keep[0], "is_cuda", False):
+                import torch
+                torch.cuda.synchronize()        # torch rewrote the tensor on ITS stream; the library reads it on the context's
+            check(self._lib.cgamd_solver_refresh_values(self.handle, None, 0))
+            return
+        if isinstance(a_values, int) or hasattr(a_values, "data_ptr") or hasattr(a_values, "ptr"):
+            if getattr(a_values, "is_cuda", True) is False:
+                a_values = a_values.numpy()
+            else:
+                if self.batched and not self._on_device:
+                    self._check_batched_values(a_values, self.n_rhs)
+                elif not self._on_device and hasattr(a_values, "numel") and int(a_values.numel()) != self.non_zeros:
+                    raise ValueError(f"refresh_values: {int(a_values.numel())} values, the matrix has {self.non_zeros} non-zeros")
+                if hasattr(a_values, "is_cuda"):
+                    import torch
+                    torch.cuda.synchronize()    # torch wrote the tensor on ITS stream; the library reads it on the context's
+                check(self._lib.cgamd_solver_refresh_values(self.handle, ptr(a_values), 1))
+                return
+        a_values = np.ascontiguousarray(a_values, dtype=self.dtype)
+        if self.batched:
+            self._check_batched_values(a_values, self.n_rhs)
+        elif a_values.size != self.non_zeros:
+            raise ValueError(f"refresh_values: {a_values.size} values, the matrix has {self.non_zeros} non-zeros")
+        check(self._lib.cgamd_solver_refresh_values(self.handle, ptr(a_values), 0))
+
+    @property
+    def last_refresh(self):
+        """what the last refresh_values did (cgamd_solver_last_refresh): 0 nothing to do, 1 dictionaries rewritten in place (arrays and
+        graphs kept), 2 value / joint / row codes built again, 3 the values do not qualify (the SpMV reads aValues)"""
+        return self._lib.cgamd_solver_last_refresh(self.handle)
+
+    @property
+    def graph_captures(self):
+        """iteration graphs captured since the handle was created (cgamd_solver_graph_captures): unchanged across calls that replay
+        the graphs the handle has, e.g. across a refresh_values that rewrote the dictionaries only"""
+        return self._lib.cgamd_solver_graph_captures(self.handle)
 
     def set_rhs(self, b, x0=None, on_device=False):
         if not on_device:

@@ -91,11 +91,20 @@ int build_joint_codes(int dtype, long long nnz, const unsigned char *codes, cons
 constexpr size_t row_dict_off_at(size_t value_size) { return 256 * 8 * value_size; }
 constexpr size_t row_dict_len_at(size_t value_size) { return row_dict_off_at(value_size) + 256 * 8 * sizeof(int); }
 constexpr size_t row_dict_bytes(size_t value_size) { return row_dict_len_at(value_size) + 256 * sizeof(int); }
+// behind what the SpMV reads, for refresh_value_dicts only: the joint code of every pattern slot [256][8], one byte each; likewise the
+// joint dictionary *joff_out holds 512 ints, [256 + c] = the value code of pair c
+constexpr size_t row_dict_jmap_at(size_t value_size) { return row_dict_bytes(value_size); }
+constexpr size_t row_dict_alloc_bytes(size_t value_size) { return row_dict_jmap_at(value_size) + 256 * 8; }
 // n rows, the first n_user the caller's (the rest appended and empty): *n_patterns = dictionary entries, *n_user_patterns = patterns of
 // the caller's rows
 int build_row_codes(int dtype, int n, int n_user, const int *ptr_dev, const unsigned char *jcodes, const int *joff, const void *jval, hipStream_t st,
                     unsigned char **rcodes_out, void **rdict_out, int *n_patterns, int *n_user_patterns);
 int build_value_codes(int dtype, long long nnz, const void *vals_dev, hipStream_t st, unsigned char **vcodes_out, void **vdict_out, int *n_values);
+// the values changed in place on the same pattern: one pass checks that every equal-value class of the codes is still one and, if so
+// (*kept), rewrites vdict and -- where given -- jval (behind joff) and the values of rdict IN PLACE; else nothing is written and the
+// caller rebuilds (index_codes.hip "REFRESH").  Synchronises `st`.
+int refresh_value_dicts(int dtype, long long nnz, const void *vals_dev, const unsigned char *vcodes, void *vdict, int n_pairs, const int *joff,
+                        void *jval, int n_patterns, void *rdict, hipStream_t st, bool *kept);
 int build_index_codes16(int n, long long nnz, const int *ptr_dev, const int *cols_dev, hipStream_t st, unsigned char **codes_out, int **base_out);
 void finalize_spmv_plan(SpmvPlan *plan, int dtype, int nrhs, int n, long long nnz, const void *vals, const int *cols);
 constexpr int kChunkBytes = 32 * 1024;      // kind 7: preferred LDS chunk slice (4-5 work-groups per CU)

@@ -147,6 +147,10 @@ struct cgamd_dist {
     // z = M^-1 r lives in q's storage; part_pcg = [2][pcg_P] partials of r.z and r.r; rho2 = parity buffer of rho = r.z (delta holds
     // rho for cg_alpha, history keeps r.r)
     int pre_kind = 0, pcg_P = 0;
+    // a preconditioner built from the rank's matrix, which cgamd_dist_refresh_values builds again: 0 none (or the caller's values),
+    // 1 Jacobi, 2 the lines at pre_stride
+    int pre_from_matrix = 0, pre_stride = 0;
+    int last_refresh = 0;   // what the last cgamd_dist_refresh_values did (cgamd_dist_last_refresh)
     void *mdiag = nullptr, *tri_coef = nullptr, *part_pcg = nullptr, *rho2 = nullptr;
     int *tri_plan = nullptr;
     TriLaunch tri;
@@ -324,6 +328,27 @@ static int enqueue_iteration(cgamd_dist *d, hipStream_t st) {
 }
 
 // classify the row blocks once: boundary = references a halo column
+// the one-byte value codes on top of the column codes, for the values now in d->vals (create, refresh_values): the handle has none
+// when this is called.  Every copy of the two pointers the handle keeps follows: the SpMV plan, the slab plan in force, the pending one.
+static bool value_codes_apply(const cgamd_dist *d) { return d->codes && d->tune.value_codes && d->plan.kind == 5 && d->dtype != CGAMD_C128; }
+static void publish_value_codes(cgamd_dist *d) {
+    d->plan.vcodes = d->vcodes; d->plan.vdict = d->vdict; d->plan.vcodes_for = d->vcodes ? d->vals : nullptr;
+    d->slab.vcodes = d->vcodes; d->slab.vdict = d->vdict;
+    d->slab_plan_.vcodes = d->vcodes; d->slab_plan_.vdict = d->vdict;
+}
+static void drop_value_codes(cgamd_dist *d) {
+    if (d->vcodes) { (void)hipFree(d->vcodes); d->vcodes = nullptr; }
+    if (d->vdict) { (void)hipFree(d->vdict); d->vdict = nullptr; }
+    d->n_values = 0;
+    publish_value_codes(d);
+}
+static int setup_value_codes(cgamd_dist *d) {
+    if (!value_codes_apply(d)) return CGAMD_OK;
+    const int rc = build_value_codes(d->dtype, d->nnz, d->vals, d->ctx->stream, &d->vcodes, &d->vdict, &d->n_values);
+    publish_value_codes(d);
+    return rc;
+}
+
 static int classify_row_blocks(cgamd_dist *d, std::vector<int> *interior, std::vector<int> *boundary) {
     const int nb = d->plan.row_blocks;
     int *flags_dev = nullptr;
@@ -473,10 +498,7 @@ int cgamd_dist_create(cgamd_ctx *ctx, const void *id128, int rank, int nranks, i
         (size_t)nnz_local * (dtype_size(dtype) + 4) > ((size_t)d->tune.index_codes_min_mb << 20)) {
         rc = build_index_codes(n_local, nnz_local, d->ptr, d->cols, ctx->stream, &d->codes, &d->dict, &d->n_offsets);
         if (!rc && d->codes) { d->plan.codes = d->codes; d->plan.dict = d->dict; d->plan.codes_for = d->cols; }
-        if (!rc && d->codes && d->tune.value_codes && d->plan.kind == 5) {
-            rc = build_value_codes(dtype, nnz_local, d->vals, ctx->stream, &d->vcodes, &d->vdict, &d->n_values);
-            if (!rc && d->vcodes) { d->plan.vcodes = d->vcodes; d->plan.vdict = d->vdict; d->plan.vcodes_for = d->vals; }
-        }
+        if (!rc) rc = setup_value_codes(d);
     }
     if (!rc && d->cg1) {
         if (!cg1_supported(d->plan, d->vals, d->cols))
@@ -491,7 +513,7 @@ int cgamd_dist_create(cgamd_ctx *ctx, const void *id128, int rank, int nranks, i
         if (d->tune.slab_cus > 0) d->n_cus = std::min(d->n_cus, d->tune.slab_cus);
         SlabPlan sp;
         if (slab_plan(dtype, n_local, d->n_cus, d->plan, d->codes != nullptr, &sp)) {
-            sp.vcodes = d->vcodes; sp.vdict = d->vdict;
+            sp.vcodes = d->vcodes; sp.vdict = d->vdict;      // (publish_value_codes keeps both copies current)
             rc = dalloc(&d->slab_sync, sp.sync_bytes, "slab sync words");
             if (!rc && d->peer.empty() && nranks == 1) {     // nothing to exchange: plain buffers, usable at once
                 for (int b = 0; b < 2 && !rc; ++b) rc = dalloc(&d->ds_own[b], (size_t)n_local * vs, "published d");
@@ -658,6 +680,7 @@ static void drop_preconditioner(cgamd_dist *d) {
     d->tri_plan = nullptr;
     d->tri = TriLaunch();
     d->pre_kind = d->pcg_P = 0;
+    d->pre_from_matrix = d->pre_stride = 0;
     drop_graph(d);
     d->rhs_set = false;
 }
@@ -718,7 +741,9 @@ int cgamd_dist_set_preconditioner_jacobi(cgamd_dist *d) {
         (void)hipFree(m);
         return rc;
     }
-    return install_diag(d, m);
+    const int rc = install_diag(d, m);
+    if (!rc) d->pre_from_matrix = 1;
+    return rc;
 }
 
 int cgamd_dist_set_preconditioner_line(cgamd_dist *d, int stride) {
@@ -752,8 +777,59 @@ int cgamd_dist_set_preconditioner_line(cgamd_dist *d, int stride) {
         d->tri.stride = b.stride; d->tri.segs = b.plan; d->tri.nsegs = b.count;
     }
     d->pre_kind = 2;
+    d->pre_from_matrix = 2; d->pre_stride = stride;
     return CGAMD_OK;
 }
+
+// The rank's matrix values changed in place on the same pattern (include/cgamd.h).  Rank-local: nothing here communicates; collective
+// in meaning: every rank calls it.  What was made from the values follows them: the value codes (dictionary rewritten in place where
+// the equal-value classes are intact, else rebuilt or dropped, with the captured graph) and a preconditioner built from the matrix.
+int cgamd_dist_refresh_values(cgamd_dist *d) {
+    if (!d) return fail(CGAMD_ERR_INVALID, "dist_refresh_values: null handle");
+    TuneScope ts(&d->tune);
+    CG_HIP(hipSetDevice(d->ctx->device));
+    hipStream_t st = d->ctx->stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return fail(CGAMD_ERR_HIP, "dist_refresh_values: hipStreamIsCapturing failed"); }
+    if (cs != hipStreamCaptureStatusNone) return fail(CGAMD_ERR_INVALID, "dist_refresh_values: the handle's stream is being captured");
+    CG_HIP(hipStreamSynchronize(st));
+    d->rhs_set = false;
+    d->last_refresh = 0;
+    if (value_codes_apply(d) && d->nnz > 0) {
+        bool kept = false;
+        int rc = CGAMD_OK;
+        if (d->vcodes) rc = refresh_value_dicts(d->dtype, d->nnz, d->vals, d->vcodes, d->vdict, 0, nullptr, nullptr, 0, nullptr, st, &kept);
+        if (!rc && kept) d->last_refresh = 1;
+        else {
+            const bool had = d->vcodes != nullptr;
+            drop_value_codes(d);
+            if (!rc) rc = setup_value_codes(d);
+            if (rc) drop_value_codes(d);
+            if (had || d->vcodes) drop_graph(d);        // the captured launches hold the old array, or read aValues
+            if (rc) {       // the values are in force, read as they are; factors of the old ones must not stay
+                d->last_refresh = -rc;
+                if (d->pre_from_matrix) {
+                    const std::string why = cgamd_last_error();
+                    drop_preconditioner(d);
+                    return fail(rc, why);
+                }
+                return rc;
+            }
+            d->last_refresh = d->vcodes ? 2 : 3;
+        }
+    }
+    if (d->pre_from_matrix) {
+        const int stride = d->pre_stride;
+        const int rc = d->pre_from_matrix == 1 ? cgamd_dist_set_preconditioner_jacobi(d) : cgamd_dist_set_preconditioner_line(d, stride);
+        if (rc) {           // the values are in force; the old factors belong to the old ones
+            const std::string why = cgamd_last_error();
+            drop_preconditioner(d);
+            return fail(rc, why);
+        }
+    }
+    return CGAMD_OK;
+}
+int cgamd_dist_last_refresh(cgamd_dist *d) { return d ? d->last_refresh : -CGAMD_ERR_INVALID; }
 
 int cgamd_dist_get_x(cgamd_dist *d, void *x_local) {
     if (!d || !x_local) return fail(CGAMD_ERR_INVALID, "dist_get_x: null argument");

@@ -334,6 +334,7 @@ __global__ __launch_bounds__(256) void pair_mark_kernel(long long nnz, const uns
 template <typename T>
 __global__ __launch_bounds__(1024) void pair_number_kernel(const unsigned char *present, const int *__restrict__ dict, const T *__restrict__ vdict,
                                                            unsigned short *pair_code, int *joff, T *jval, int *count) {
+    // joff[256 + code]: the value code of pair `code` (joint_value_map; what refresh_value_dicts rewrites jval from)
     __shared__ int wsum[16];
     const int t = threadIdx.x;
     int mine = 0;
@@ -349,7 +350,7 @@ __global__ __launch_bounds__(1024) void pair_number_kernel(const unsigned char *
         const int p = t * 64 + k;
         if (present[p]) {
             pair_code[p] = (unsigned short)code;
-            if (code < 256) { joff[code] = dict[p >> 8]; jval[code] = vdict[p & 255]; }
+            if (code < 256) { joff[code] = dict[p >> 8]; jval[code] = vdict[p & 255]; joff[256 + code] = p & 255; }
             ++code;
         }
     }
@@ -374,9 +375,9 @@ static int build_joint_codes_impl(long long nnz, const unsigned char *codes, con
     void *jval = nullptr;
     int h = 0;
     hipError_t e = hipMemsetAsync(scratch, 0, 65536 * 3 + 16, st);
-    if (e == hipSuccess) e = hipMalloc((void **)&joff, 256 * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void **)&joff, 512 * sizeof(int));
     if (e == hipSuccess) e = hipMalloc(&jval, 256 * sizeof(T));
-    if (e == hipSuccess) e = hipMemsetAsync(joff, 0, 256 * sizeof(int), st);
+    if (e == hipSuccess) e = hipMemsetAsync(joff, 0, 512 * sizeof(int), st);
     if (e == hipSuccess) e = hipMemsetAsync(jval, 0, 256 * sizeof(T), st);
     const int grid = (int)std::min<long long>((nnz + 255) / 256, 4096);
     if (e == hipSuccess) {
@@ -462,7 +463,7 @@ __global__ __launch_bounds__(256) void rowcode_insert_kernel(int n, int n_user, 
 // one work-group: occupied slot -> number of smaller keys in the table; dictionary entry of that number (unused slots stay 0)
 template <typename T>
 __global__ __launch_bounds__(1024) void rowcode_number_kernel(const unsigned long long *table, const int *__restrict__ joff, const T *__restrict__ jval,
-                                                              unsigned short *slot_code, int *rlen, int *roff, T *rval) {
+                                                              unsigned short *slot_code, int *rlen, int *roff, T *rval, unsigned char *rjmap) {
     __shared__ unsigned long long keys[kRSlots];
     for (int s = threadIdx.x; s < kRSlots; s += 1024) keys[s] = table[s];
     __syncthreads();
@@ -479,6 +480,7 @@ __global__ __launch_bounds__(1024) void rowcode_number_kernel(const unsigned lon
             const int jc = (int)((key >> (8 * (j + 1))) & 255);
             roff[code * 8 + j] = joff[jc] * (int)sizeof(T);             // byte offsets, as the kernel adds them
             rval[code * 8 + j] = jval[jc];
+            rjmap[code * 8 + j] = (unsigned char)jc;                    // (row_dict_jmap_at: what refresh_value_dicts rewrites rval from)
         }
     }
 }
@@ -518,7 +520,7 @@ static int build_row_codes_impl(int n, int n_user, const int *ptr, const unsigne
     }
     unsigned char *rcodes = nullptr;
     char *rdict = nullptr;
-    const size_t db = row_dict_bytes(sizeof(T));
+    const size_t db = row_dict_alloc_bytes(sizeof(T));
     e = hipMalloc((void **)&rcodes, (size_t)n + 64);
     if (e == hipSuccess) e = hipMalloc((void **)&rdict, db);
     if (e == hipSuccess) e = hipMemsetAsync(rcodes + (size_t)n, 0, 64, st);
@@ -526,7 +528,7 @@ static int build_row_codes_impl(int n, int n_user, const int *ptr, const unsigne
     if (e == hipSuccess) {
         hipLaunchKernelGGL((rowcode_number_kernel<T>), dim3(1), dim3(1024), 0, st, table, joff, static_cast<const T *>(jval), slot_code,
                            reinterpret_cast<int *>(rdict + row_dict_len_at(sizeof(T))), reinterpret_cast<int *>(rdict + row_dict_off_at(sizeof(T))),
-                           reinterpret_cast<T *>(rdict));
+                           reinterpret_cast<T *>(rdict), reinterpret_cast<unsigned char *>(rdict + row_dict_jmap_at(sizeof(T))));
         hipLaunchKernelGGL(rowcode_encode_kernel, dim3(grid), dim3(256), 0, st, n, ptr, jcodes, table, slot_code, rcodes);
         e = hipGetLastError();
     }
@@ -541,7 +543,7 @@ static int build_row_codes_impl(int n, int n_user, const int *ptr, const unsigne
     *n_user_patterns = h[0] - ((n > n_user && !h[2]) ? 1 : 0);
     return CGAMD_OK;
 }
-// *rcodes_out (n + 64 bytes) and *rdict_out (row_dict_bytes: values [256][8] | byte offsets [256][8] | lengths [256]) are device
+// *rcodes_out (n + 64 bytes) and *rdict_out (row_dict_alloc_bytes: values [256][8] | byte offsets [256][8] | lengths [256] | joint codes [256][8]) are device
 // allocations the caller frees; both null when the rows have more than 256 patterns.  n rows of which the first n_user are the
 // caller's: *n_patterns counts the dictionary entries (what the kernel stages), *n_user_patterns the patterns of the caller's rows
 // (one fewer where only the appended rows are empty).  The caller has checked that no row is longer than 7 entries.  Synchronises `st`.
@@ -552,6 +554,130 @@ int build_row_codes(int dtype, int n, int n_user, const int *ptr_dev, const unsi
     if (dtype == CGAMD_F32) return build_row_codes_impl<float>(n, n_user, ptr_dev, jcodes, joff, jval, st, rcodes_out, rdict_out, n_patterns, n_user_patterns);
     if (dtype == CGAMD_F64) return build_row_codes_impl<double>(n, n_user, ptr_dev, jcodes, joff, jval, st, rcodes_out, rdict_out, n_patterns, n_user_patterns);
     return build_row_codes_impl<float2>(n, n_user, ptr_dev, jcodes, joff, jval, st, rcodes_out, rdict_out, n_patterns, n_user_patterns);
+}
+
+// -------------------------------------------------------------------------------------------------
+// REFRESH: the matrix values changed in place on the same pattern (cgamd_solver_refresh_values).  Where every equal-value class of
+// the old matrix is still one (a constant-coefficient operator with rescaled coefficients: new tau in I + tau L, a new wavenumber),
+// the code ARRAYS are still right and only the dictionaries are stale.  One pass over vals and vcodes decides it: the first non-zero
+// of a class claims the class's new value bits in a 256-entry table (compare-and-swap on the bits; kVEmpty = unclaimed, and a matrix
+// that holds that NaN pattern is not coded, as for the builder), every other one compares against the claim, a mismatch raises the
+// flag.  Values are compared as bits (-0.0 and +0.0 differ).  A work-group keeps the claims it has seen in LDS, so the table in
+// memory is touched once per (work-group, class).  With the flag clear one work-group rewrites vdict from the table, jdict_val from
+// vdict (joint code -> value code) and the values of rdict from jdict_val (pattern slot -> joint code), all IN PLACE: no pointer a
+// captured graph holds changes.  Classes that now hold equal values keep their codes; the products are formed from the same bits.
+// -------------------------------------------------------------------------------------------------
+CG_DEV void refresh_claim(unsigned long long key, unsigned code, unsigned long long *stab, unsigned long long *table, int *flag) {
+    unsigned long long cur = __hip_atomic_load(stab + code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (cur == key && key != kVEmpty) return;
+    if (key != kVEmpty && cur == kVEmpty) {             // not seen by this work-group yet: claim, or read the claim
+        cur = __hip_atomic_load(table + code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (cur == kVEmpty) {
+            cur = atomicCAS(table + code, kVEmpty, key);
+            if (cur == kVEmpty) cur = key;
+        }
+        __hip_atomic_store(stab + code, cur, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (cur == key) return;
+    }
+    atomicExch(flag, 1);                                // the class split (or the matrix holds the pattern the builder refuses)
+}
+// vals is 16-byte aligned: value codes are built for plan.kind == 5 only (value_codes_apply in solver.cpp / dist.cpp), and
+// finalize_spmv_plan chooses that kind only for 16-byte aligned aValues and aCols, so no handle carries value codes of an unaligned
+// array (refresh_value_dicts still checks, and answers "rebuild").  One 16-byte load of E = 16 / sizeof(T) values and one E-byte load
+// of their codes per step; the nnz % E last non-zeros go one by one
+template <typename T>
+__global__ __launch_bounds__(256) void refresh_check_kernel(long long nnz, const T *__restrict__ vals, const unsigned char *__restrict__ vcodes,
+                                                            unsigned long long *table, int *flag) {
+    __shared__ unsigned long long stab[256];
+    stab[threadIdx.x] = __hip_atomic_load(table + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    constexpr int E = (int)(16 / sizeof(T));
+    const long long packs = nnz / E, stride = (long long)gridDim.x * 256;
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < packs; p += stride) {
+        if (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+        const uint4 w = *reinterpret_cast<const uint4 *>(vals + p * E);
+        if constexpr (sizeof(T) == 4) {
+            unsigned c;
+            __builtin_memcpy(&c, vcodes + p * 4, 4);       // (vcodes is an allocation of its own: p * 4 is 4-byte aligned)
+            refresh_claim(w.x, c & 255, stab, table, flag);
+            refresh_claim(w.y, (c >> 8) & 255, stab, table, flag);
+            refresh_claim(w.z, (c >> 16) & 255, stab, table, flag);
+            refresh_claim(w.w, c >> 24, stab, table, flag);
+        } else {
+            unsigned short c;
+            __builtin_memcpy(&c, vcodes + p * 2, 2);
+            refresh_claim(((unsigned long long)w.y << 32) | w.x, c & 255u, stab, table, flag);
+            refresh_claim(((unsigned long long)w.w << 32) | w.z, c >> 8, stab, table, flag);
+        }
+    }
+    const long long j = packs * E + threadIdx.x;
+    if (blockIdx.x == 0 && j < nnz) refresh_claim(value_key(vals[j]), vcodes[j], stab, table, flag);
+}
+// one work-group.  jmap: joint code -> value code [n_pairs]; rlen / rjmap: pattern lengths and pattern slot -> joint code
+template <typename T>
+__global__ __launch_bounds__(256) void refresh_dicts_kernel(const unsigned long long *__restrict__ table, T *vdict, int n_pairs, const int *__restrict__ jmap,
+                                                            T *jval, int n_patterns, const int *__restrict__ rlen,
+                                                            const unsigned char *__restrict__ rjmap, T *rval) {
+    __shared__ T sv[256], sj[256];
+    const int t = threadIdx.x;
+    const unsigned long long key = table[t];
+    T v = vdict[t];                                     // (codes no non-zero carries keep their entry)
+    if (key != kVEmpty) {
+        if constexpr (sizeof(T) == 4) { const unsigned b = (unsigned)key; __builtin_memcpy(&v, &b, 4); }
+        else __builtin_memcpy(&v, &key, 8);
+        vdict[t] = v;
+    }
+    sv[t] = v;
+    __syncthreads();
+    if (!jval) return;
+    if (t < n_pairs) { sj[t] = sv[jmap[t] & 255]; jval[t] = sj[t]; }
+    __syncthreads();
+    if (!rval) return;
+    for (int p = t; p < n_patterns * 8; p += 256)
+        if ((p & 7) < rlen[p >> 3]) rval[p] = sj[rjmap[p]];
+}
+template <typename T>
+static int refresh_value_dicts_impl(long long nnz, const void *vals, const unsigned char *vcodes, void *vdict, int n_pairs, const int *joff, void *jval,
+                                    int n_patterns, void *rdict, hipStream_t st, bool *kept) {
+    char *scratch = nullptr;
+    const size_t tb = sizeof(unsigned long long) * 256;
+    CG_HIP(hipMalloc((void **)&scratch, tb + 16));
+    auto *table = reinterpret_cast<unsigned long long *>(scratch);
+    int *flag = reinterpret_cast<int *>(scratch + tb);
+    int h = 1;
+    hipError_t e = hipMemsetAsync(table, 0xff, tb, st);
+    if (e == hipSuccess) e = hipMemsetAsync(flag, 0, 16, st);
+    const long long packs = nnz / (long long)(16 / sizeof(T));
+    const int grid = (int)std::max<long long>(1, std::min<long long>((packs + 255) / 256, kMaxGrid));
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL((refresh_check_kernel<T>), dim3(grid), dim3(256), 0, st, nnz, static_cast<const T *>(vals), vcodes, table, flag);
+        e = hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && h == 0) {
+        char *rd = static_cast<char *>(rdict);
+        hipLaunchKernelGGL((refresh_dicts_kernel<T>), dim3(1), dim3(256), 0, st, table, static_cast<T *>(vdict), n_pairs, joff ? joff + 256 : nullptr,
+                           static_cast<T *>(jval), n_patterns, rd ? reinterpret_cast<const int *>(rd + row_dict_len_at(sizeof(T))) : nullptr,
+                           rd ? reinterpret_cast<const unsigned char *>(rd + row_dict_jmap_at(sizeof(T))) : nullptr, reinterpret_cast<T *>(rd));
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    (void)hipFree(scratch);
+    if (e != hipSuccess) return fail(CGAMD_ERR_HIP, std::string("refresh_value_dicts: ") + hipGetErrorString(e));
+    *kept = h == 0;
+    return CGAMD_OK;
+}
+// vals [nnz] against the value codes made from the array's earlier contents: *kept = every class still holds one value, and the
+// dictionaries (vdict; jdict_val behind joff, rdict where the handle has them, else null / 0) now hold the new values.  *kept false:
+// nothing was written, the caller rebuilds the codes.  Synchronises `st`.
+int refresh_value_dicts(int dtype, long long nnz, const void *vals_dev, const unsigned char *vcodes, void *vdict, int n_pairs, const int *joff,
+                        void *jval, int n_patterns, void *rdict, hipStream_t st, bool *kept) {
+    *kept = false;
+    if (nnz <= 0 || !vcodes || !vdict || dtype == CGAMD_C128 || !aligned16(vals_dev)) return CGAMD_OK;
+    if (!joff || !jval) { joff = nullptr; jval = nullptr; rdict = nullptr; }
+    if (dtype == CGAMD_F32) return refresh_value_dicts_impl<float>(nnz, vals_dev, vcodes, vdict, n_pairs, joff, jval, n_patterns, rdict, st, kept);
+    if (dtype == CGAMD_F64) return refresh_value_dicts_impl<double>(nnz, vals_dev, vcodes, vdict, n_pairs, joff, jval, n_patterns, rdict, st, kept);
+    return refresh_value_dicts_impl<float2>(nnz, vals_dev, vcodes, vdict, n_pairs, joff, jval, n_patterns, rdict, st, kept);
 }
 
 }  // namespace cgamd

@@ -123,6 +123,8 @@ struct cgamd_solver {
     hipGraphExec_t gT = nullptr;
     hipGraph_t gTg = nullptr;
     int gT_len = 0;
+    int last_refresh = 0;           // what the last cgamd_solver_refresh_values did (cgamd_solver_last_refresh)
+    int captures = 0;               // graphs captured since creation (cgamd_solver_graph_captures)
 };
 
 static void destroy_graphs(cgamd_solver *s) {
@@ -359,12 +361,8 @@ static int setup_resident_wide_plan(cgamd_solver *s) {
     return CGAMD_OK;
 }
 
-// (re)build the one-byte column codes for the matrix now in s->cols; dropped when they do not apply
-static int setup_index_codes(cgamd_solver *s) {
-    if (s->codes) { (void)hipFree(s->codes); s->codes = nullptr; }
-    if (s->dict) { (void)hipFree(s->dict); s->dict = nullptr; }
-    s->plan.codes = nullptr; s->plan.dict = nullptr; s->plan.codes_for = nullptr; s->plan.codes16 = false;
-    s->n_offsets = 0;
+// the codes made from the VALUES (value, joint and row-pattern codes): freed, the plan reads aValues again
+static void drop_value_codes(cgamd_solver *s) {
     if (s->vcodes) { (void)hipFree(s->vcodes); s->vcodes = nullptr; }
     if (s->vdict) { (void)hipFree(s->vdict); s->vdict = nullptr; }
     s->plan.vcodes = nullptr; s->plan.vdict = nullptr; s->plan.vcodes_for = nullptr;
@@ -379,6 +377,49 @@ static int setup_index_codes(cgamd_solver *s) {
     s->plan.rcodes = nullptr; s->plan.rdict_len = nullptr; s->plan.rdict_off = nullptr; s->plan.rdict_val = nullptr; s->plan.n_patterns = 0;
     s->plan.rcodes_for = nullptr;
     s->n_patterns = 0; s->n_user_patterns = 0;
+}
+// a handle whose SpMV reads one-byte column codes may carry codes of its values on top
+static bool value_codes_apply(const cgamd_solver *s) {
+    return s->codes && !s->plan.codes16 && !s->nsys && s->tune.value_codes && s->plan.kind == 5 && s->dtype != CGAMD_C128;
+}
+// the ladder on top of the one-byte column codes, for the values now in s->vals (create, reload_matrix, refresh_values); the handle
+// has none of these codes when this is called (drop_value_codes)
+static int setup_value_codes(cgamd_solver *s) {
+    if (!value_codes_apply(s)) return CGAMD_OK;
+    const size_t matrix_bytes = (size_t)s->nnz * (dtype_size(s->dtype) + 4);
+    // matrices of at most 256 distinct entries (constant-coefficient stencils): one-byte value codes as well, 2 bytes per non-zero
+    if (int rc = build_value_codes(s->dtype, s->nnz, s->vals, s->ctx->stream, &s->vcodes, &s->vdict, &s->n_values)) return rc;
+    if (s->vcodes) { s->plan.vcodes = s->vcodes; s->plan.vdict = s->vdict; s->plan.vcodes_for = s->vals; }
+    if (!s->vcodes || !s->tune.dev_joint_codes) return CGAMD_OK;
+    if (int rc = build_joint_codes(s->dtype, s->nnz, s->codes, s->vcodes, s->dict, s->vdict, s->ctx->stream, &s->jcodes, &s->jdict_off,
+                                   &s->jdict_val, &s->n_pairs)) return rc;
+    if (s->jcodes) { s->plan.jcodes = s->jcodes; s->plan.jdict_off = s->jdict_off; s->plan.jdict_val = s->jdict_val; }
+    // ... and one byte per ROW where the rows fit a 64-bit pattern key and few patterns occur (stencils: 9, 27); a threshold
+    // of its own, so that index_codes_min_mb = 0 alone keeps the joint form on a small matrix
+    const size_t vsz = dtype_size(s->dtype);
+    if (s->jcodes && s->nrhs == 1 && s->plan.kind == 5 && s->plan.max_row > 0 && s->plan.max_row <= 7 && s->tune.dev_row_codes &&
+        s->tune.dev_row_codes_min_mb >= 0 && matrix_bytes > ((size_t)s->tune.dev_row_codes_min_mb << 20) &&
+        (unsigned long long)s->n * vsz < (1ULL << 30)) {
+        if (int rc = build_row_codes(s->dtype, s->n, s->n_user, s->ptr, s->jcodes, s->jdict_off, s->jdict_val, s->ctx->stream, &s->rcodes,
+                                     &s->rdict, &s->n_patterns, &s->n_user_patterns)) return rc;
+        if (s->rcodes) {
+            const char *rd = static_cast<const char *>(s->rdict);
+            s->plan.rcodes = s->rcodes; s->plan.rdict_val = rd; s->plan.n_patterns = s->n_patterns;
+            s->plan.rdict_off = reinterpret_cast<const int *>(rd + row_dict_off_at(vsz));
+            s->plan.rdict_len = reinterpret_cast<const int *>(rd + row_dict_len_at(vsz));
+            s->plan.rcodes_for = s->ptr;
+        }
+    }
+    return CGAMD_OK;
+}
+
+// (re)build the one-byte column codes for the matrix now in s->cols, and the value codes on top; dropped when they do not apply
+static int setup_index_codes(cgamd_solver *s) {
+    if (s->codes) { (void)hipFree(s->codes); s->codes = nullptr; }
+    if (s->dict) { (void)hipFree(s->dict); s->dict = nullptr; }
+    s->plan.codes = nullptr; s->plan.dict = nullptr; s->plan.codes_for = nullptr; s->plan.codes16 = false;
+    s->n_offsets = 0;
+    drop_value_codes(s);
     const size_t matrix_bytes = (size_t)s->nnz * (dtype_size(s->dtype) + 4);
     // a handle whose iterations run in the chip-wide resident loop (matrix in registers) would pay the two coding passes at every
     // create / reload (the stateless cg() reloads per call) for the few launched SpMVs around it
@@ -389,33 +430,7 @@ static int setup_index_codes(cgamd_solver *s) {
     if (int rc = build_index_codes(s->n, s->nnz, s->ptr, s->cols, s->ctx->stream, &s->codes, &s->dict, &s->n_offsets)) return rc;
     if (s->codes) {
         s->plan.codes = s->codes; s->plan.dict = s->dict; s->plan.codes_for = s->cols; s->plan.codes16 = false;
-        // matrices of at most 256 distinct entries (constant-coefficient stencils): one-byte value codes as well, 2 bytes per non-zero
-        if (s->tune.value_codes && s->plan.kind == 5) {
-            if (int rc = build_value_codes(s->dtype, s->nnz, s->vals, s->ctx->stream, &s->vcodes, &s->vdict, &s->n_values)) return rc;
-            if (s->vcodes) { s->plan.vcodes = s->vcodes; s->plan.vdict = s->vdict; s->plan.vcodes_for = s->vals; }
-            if (s->vcodes && s->tune.dev_joint_codes) {
-                if (int rc = build_joint_codes(s->dtype, s->nnz, s->codes, s->vcodes, s->dict, s->vdict, s->ctx->stream, &s->jcodes, &s->jdict_off,
-                                               &s->jdict_val, &s->n_pairs)) return rc;
-                if (s->jcodes) { s->plan.jcodes = s->jcodes; s->plan.jdict_off = s->jdict_off; s->plan.jdict_val = s->jdict_val; }
-                // ... and one byte per ROW where the rows fit a 64-bit pattern key and few patterns occur (stencils: 9, 27); a threshold
-                // of its own, so that index_codes_min_mb = 0 alone keeps the joint form on a small matrix
-                const size_t vsz = dtype_size(s->dtype);
-                if (s->jcodes && s->nrhs == 1 && s->plan.kind == 5 && s->plan.max_row > 0 && s->plan.max_row <= 7 && s->tune.dev_row_codes &&
-                    s->tune.dev_row_codes_min_mb >= 0 && matrix_bytes > ((size_t)s->tune.dev_row_codes_min_mb << 20) &&
-                    (unsigned long long)s->n * vsz < (1ULL << 30)) {
-                    if (int rc = build_row_codes(s->dtype, s->n, s->n_user, s->ptr, s->jcodes, s->jdict_off, s->jdict_val, s->ctx->stream, &s->rcodes,
-                                                 &s->rdict, &s->n_patterns, &s->n_user_patterns)) return rc;
-                    if (s->rcodes) {
-                        const char *rd = static_cast<const char *>(s->rdict);
-                        s->plan.rcodes = s->rcodes; s->plan.rdict_val = rd; s->plan.n_patterns = s->n_patterns;
-                        s->plan.rdict_off = reinterpret_cast<const int *>(rd + row_dict_off_at(vsz));
-                        s->plan.rdict_len = reinterpret_cast<const int *>(rd + row_dict_len_at(vsz));
-                        s->plan.rcodes_for = s->ptr;
-                    }
-                }
-            }
-        }
-        return CGAMD_OK;
+        return setup_value_codes(s);
     }
     // more than 256 distinct offsets (unstructured patterns, Matrix-Market inputs): 16-bit columns relative to the row block's first
     if (s->tune.index_codes16 == 0) return CGAMD_OK;
@@ -493,6 +508,7 @@ static int capture(cgamd_solver *s, int k0, int iters, hipGraph_t *g, hipGraphEx
     hipStream_t st = s->ctx->stream;
     hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
     if (e != hipSuccess) return fail(CGAMD_ERR_HIP, std::string("hipStreamBeginCapture: ") + hipGetErrorString(e));
+    ++s->captures;
     int rc = CGAMD_OK;
     // whole groups of the deferred x update, so that nothing is pending when the graph ends (k0 = 0 there: no parity)
     const int lag = (!guarded && iters == s->U && k0 == 0) ? x_lag_now(s) : 1;
@@ -755,6 +771,78 @@ int cgamd_solver_reload_matrix(cgamd_solver *s, const void *aValues, const int *
     }
     return CGAMD_OK;
 }
+
+// New VALUES on the SAME pattern (include/cgamd.h): everything made from the values follows them -- the value, joint and row-pattern
+// codes and a preconditioner built from the matrix -- and nothing made from the pattern alone is touched (no validation, no plan, no
+// resident scan, no x lag, the column codes stay).  Returns the outcome through s->last_refresh.
+static int refresh_codes(cgamd_solver *s) {
+    s->last_refresh = 0;
+    if (!value_codes_apply(s) || s->nnz <= 0) return CGAMD_OK;
+    if (s->vcodes) {        // classes intact: the dictionaries are rewritten in place, arrays, pointers and captured graphs stay
+        bool kept = false;
+        if (int rc = refresh_value_dicts(s->dtype, s->nnz, s->vals, s->vcodes, s->vdict, s->n_pairs, s->jcodes ? s->jdict_off : nullptr,
+                                         s->jcodes ? s->jdict_val : nullptr, s->n_patterns, s->rcodes ? s->rdict : nullptr, s->ctx->stream, &kept)) {
+            destroy_graphs(s);      // (what the dictionaries hold is unknown: the SpMV reads aValues)
+            drop_value_codes(s);
+            return rc;
+        }
+        if (kept) { s->last_refresh = 1; return CGAMD_OK; }
+    }
+    const bool had = s->vcodes != nullptr;
+    if (had) destroy_graphs(s);     // captured launches hold the old code arrays
+    drop_value_codes(s);
+    const int rc = setup_value_codes(s);
+    if (!had && s->vcodes) destroy_graphs(s);
+    if (rc) { drop_value_codes(s); return rc; }
+    s->last_refresh = s->vcodes ? 2 : 3;
+    return CGAMD_OK;
+}
+int cgamd_solver_refresh_values(cgamd_solver *s, const void *aValues, int on_device) {
+    if (!s) return fail(CGAMD_ERR_INVALID, "refresh_values: solver is NULL");
+    if (s->own_matrix && !aValues) return fail(CGAMD_ERR_INVALID, "refresh_values: the handle owns its matrix: aValues is NULL");
+    if (!s->own_matrix && aValues && (aValues != s->vals || !on_device))
+        return fail(CGAMD_ERR_INVALID, "refresh_values: the handle borrows its value array (CGAMD_MATRIX_ON_DEVICE): copy the new values into "
+                                       "that array and pass NULL (or the array itself, on_device = 1); borrowing another array needs a new handle");
+    TuneScope ts(&s->tune);
+    CG_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        const hipError_t e = hipStreamIsCapturing(st, &cs);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(CGAMD_ERR_HIP, std::string("refresh_values: hipStreamIsCapturing: ") + hipGetErrorString(e)); }
+        if (cs != hipStreamCaptureStatusNone) return fail(CGAMD_ERR_INVALID, "refresh_values: the handle's stream is being captured");
+    }
+    s->rhs_set = false;
+    s->last_refresh = 0;
+    CG_HIP(hipStreamSynchronize(st));       // nothing of the handle's still reads the old values
+    if (s->own_matrix && s->nnz) {
+        const size_t bytes = (size_t)s->nnz * (s->nsys ? (size_t)s->nsys : 1) * dtype_size(s->dtype);
+        CG_HIP(hipMemcpyAsync(s->vals, aValues, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        CG_HIP(hipStreamSynchronize(st));   // the caller's array may go away (or change) after return
+    }
+    if (int rc = refresh_codes(s)) {        // the values are in force, read as they are; factors of the old ones must not stay
+        s->last_refresh = -rc;
+        if (s->pre_source >= 2) {
+            const std::string why = cgamd_last_error();
+            (void)diag_impl(s, nullptr, 0);
+            return fail(rc, why);
+        }
+        return rc;
+    }
+    if (s->pre_source >= 2) {               // a preconditioner built from the matrix follows it (one from the caller's arrays is kept)
+        int rc;
+        if (s->nsys) rc = s->pre_kind == 1 ? batched_jacobi_from_matrix(s, "refresh_values") : batched_line_from_matrix(s, "refresh_values", s->pre_stride);
+        else rc = s->pre_kind == 1 ? jacobi_from_matrix(s, "refresh_values") : line_from_matrix(s, "refresh_values", s->pre_stride);
+        if (rc) {                           // the values are in force; the old factors belong to the old ones
+            const std::string why = cgamd_last_error();
+            (void)diag_impl(s, nullptr, 0);
+            return fail(rc, why);
+        }
+    }
+    return CGAMD_OK;
+}
+int cgamd_solver_last_refresh(cgamd_solver *s) { return s ? s->last_refresh : -CGAMD_ERR_INVALID; }
+int cgamd_solver_graph_captures(cgamd_solver *s) { return s ? s->captures : -CGAMD_ERR_INVALID; }
 
 int cgamd_solver_destroy(cgamd_solver *s) {
     if (!s) return CGAMD_OK;

@@ -427,6 +427,34 @@ class DistSolver:
             r, (code, text) = bad[0]
             raise _lib.CgAmdError(code, f"set_preconditioner failed on rank {r}: {text}")
 
+    def refresh_values(self, group=None):
+        """The rank's matrix values (the borrowed tensor) were changed in place on the same pattern: the value codes and a "jacobi"
+        / ("line", stride) preconditioner follow them (cgamd_dist_refresh_values); the next call must be set_rhs.  Collective over
+        `group` like set_preconditioner: the C call is local, the statuses are all-gathered; if ANY rank failed (a zero diagonal
+        under the new values), every rank removes its preconditioner and raises CgAmdError with the failing rank and its message."""
+        lib = self._lib
+        if hasattr(self._keep[1], "is_cuda"):
+            import torch
+            torch.cuda.synchronize()        # torch wrote the values on ITS stream; the library reads them on the context's
+        status = lib.cgamd_dist_refresh_values(self.handle)
+        mine = (int(status), lib.cgamd_last_error().decode(errors="replace") if status else "")
+        if self.plan.world > 1:
+            import torch.distributed as dist
+            everyone = [None] * self.plan.world
+            dist.all_gather_object(everyone, mine, group=group)
+        else:
+            everyone = [mine]
+        bad = [(r, e) for r, e in enumerate(everyone) if e[0] != 0]
+        if bad:
+            lib.cgamd_dist_set_preconditioner(self.handle, None)
+            r, (code, text) = bad[0]
+            raise _lib.CgAmdError(code, f"refresh_values failed on rank {r}: {text}")
+
+    @property
+    def last_refresh(self):
+        """what this rank's last refresh_values did (cgamd_dist_last_refresh; ranks may differ)"""
+        return int(self._lib.cgamd_dist_last_refresh(self.handle))
+
     def set_rhs(self, b_local, x0_local=None):
         check(self._lib.cgamd_dist_set_rhs(self.handle, ptr(b_local), ptr(x0_local)))
         self.iterations = 0

@@ -97,7 +97,11 @@ int cgamd_sub(cgamd_ctx *ctx, int dtype, int size, const void *a, const void *b,
 
 /* ---- persistent solver handle ------------------------
  * flags for cgamd_solver_create */
-#define CGAMD_MATRIX_ON_DEVICE 1   /* aValues/aPointers/aCols are device pointers, borrowed (not copied) */
+#define CGAMD_MATRIX_ON_DEVICE 1   /* aValues/aPointers/aCols are device pointers, borrowed (not copied).  A borrowed value array may
+                                    * be changed only between solves, and every change must be followed by cgamd_solver_refresh_values
+                                    * before the next cgamd_solver_set_rhs: the handle keeps re-encodings of the values (value, joint
+                                    * and row-pattern codes) and preconditioners built from them, which that call brings up to date.
+                                    * aPointers / aCols must not change while the handle lives */
 #define CGAMD_NO_GRAPH 2           /* plain stream launches instead of hipGraph replay */
 #define CGAMD_UNFUSED 4            /* reference op structure: spmv, vdot, axpy, axpy, vdot, aypx (6 kernels) */
 #define CGAMD_DIST_NO_OVERLAP 32    /* cgamd_dist_create: exchange first, then one SpMV (no interior/boundary overlap) */
@@ -149,6 +153,35 @@ int cgamd_solver_destroy(cgamd_solver *s);
  * (cgamd_solver_set_preconditioner_line / _jacobi; on a batched handle _batched_line / _batched_jacobi) is built again from the new
  * matrix. */
 int cgamd_solver_reload_matrix(cgamd_solver *s, const void *aValues, const int *aPointers, const int *aCols);
+/* New VALUES on the SAME pattern.  Everything the handle made from the values follows them (the value, joint and row-pattern codes
+ * of the SpMV, a preconditioner built from the matrix); nothing made from the pattern alone is touched: no CSR validation, no plan,
+ * no resident-plan scan, no change of the x lag, the column codes stay.
+ *   a handle that BORROWS its matrix (CGAMD_MATRIX_ON_DEVICE): aValues is NULL, or the borrowed pointer itself with on_device = 1 --
+ *     "the array I lent you has changed in place".  Any other pointer: CGAMD_ERR_INVALID, handle untouched (copy the new values into
+ *     the borrowed array; another array needs a new handle, pointer alignment decides kernel forms).
+ *   a handle that OWNS its matrix: aValues holds nnz values (a batched handle: nSystems * nnz), host (on_device = 0) or device
+ *     (on_device = 1, copied on the handle's stream) memory.  NULL: CGAMD_ERR_INVALID.
+ * The call waits for the handle's stream before it reads the values; a caller who wrote the borrowed array on ANOTHER stream orders
+ * that write before this call (synchronise that stream, or make the handle's stream wait for it).  The next call must be
+ * cgamd_solver_set_rhs (cgamd_solver_iterate returns CGAMD_ERR_STATE until then).  Inside a stream capture: CGAMD_ERR_INVALID.
+ * Codes: where every class of equal values of the old matrix still holds one value (a constant-coefficient operator with rescaled
+ * coefficients) one pass over the values finds that out and only the dictionaries are rewritten, in place: no code array, no pointer
+ * and no captured graph changes.  cgamd_solver_value_codes / _joint_codes / _row_codes then keep reporting the dictionary entries in
+ * use, which may exceed the number of distinct values / pairs / patterns when classes have merged.  Otherwise the three codes are
+ * freed and built again as at creation (the graphs are captured again); values that no longer qualify (more than 256 of them, or
+ * the all-ones NaN pattern) run the form that reads aValues, and a handle that had no value codes gains them when the new values
+ * qualify.  Results are, bit for bit, those of a fresh handle created from the new values.
+ * Preconditioners: one from the caller's arrays is kept; one built from the matrix (cgamd_solver_set_preconditioner_jacobi / _line,
+ * _batched_jacobi / _batched_line) is built again from the new values, same kind and stride.  If that fails the values are in force,
+ * the preconditioner is removed and the error naming the row (batched: the system and the row) is returned. */
+int cgamd_solver_refresh_values(cgamd_solver *s, const void *aValues, int on_device);
+/* what the last cgamd_solver_refresh_values did: 0 no refresh yet, or the handle carries no codes of its values (multi-RHS, batched,
+ * complex128, below the size thresholds, handles of the resident loops that build none); 1 dictionaries rewritten, arrays and graphs
+ * kept; 2 value, joint and row codes built again; 3 the new values do not qualify, the SpMV reads aValues; negative: error */
+int cgamd_solver_last_refresh(cgamd_solver *s);
+/* iteration graphs this handle has captured since it was created (0 with CGAMD_NO_GRAPH).  A handle replays the graphs it has; the
+ * count grows only when something invalidated them -- so it does not grow across a refresh that kept them (outcome 1). */
+int cgamd_solver_graph_captures(cgamd_solver *s);
 /* b, x0: nRHS*size values, host (on_device=0) or device (on_device=1) memory; x0 may be NULL (zeros).
  * Computes r = b - A x0, d = r, delta0 = r.r  (reference clcg.c:255-292) and resets the iteration count. */
 int cgamd_solver_set_rhs(cgamd_solver *s, const void *b, const void *x0, int on_device);
@@ -380,7 +413,9 @@ int cgamd_solver_x_lag(cgamd_solver *s);
 int cgamd_solver_index_codes(cgamd_solver *s);
 /* distinct matrix entries behind the one-byte VALUE codes of the handle's single-RHS SpMV (matrices of at most 256 distinct entries
  * that also run on one-byte column codes: 2 bytes per non-zero from memory, same bits); 0 = the SpMV reads aValues.
- * (cgamd_tune("dev.value_codes", 0) turns the form off for A/B runs.) */
+ * (cgamd_tune("dev.value_codes", 0) turns the form off for A/B runs.)  After a cgamd_solver_refresh_values that rewrote the
+ * dictionaries in place (cgamd_solver_last_refresh() == 1) this accessor, cgamd_solver_joint_codes and cgamd_solver_row_codes report
+ * the dictionary ENTRIES IN USE, which exceed the number of distinct values / pairs / patterns when classes of values have merged. */
 int cgamd_solver_value_codes(cgamd_solver *s);
 /* > 0: the SpMV reads ONE byte per non-zero that names the (column offset, value) pair -- matrices with at most 256 distinct pairs whose
  * longest row fits one batch of the row walk (constant-coefficient stencils: as many pairs as offsets); the value is the number of
@@ -497,6 +532,14 @@ int cgamd_dist_synchronize(cgamd_dist *d);
 int cgamd_dist_set_preconditioner(cgamd_dist *d, const void *m_local);
 int cgamd_dist_set_preconditioner_jacobi(cgamd_dist *d);
 int cgamd_dist_set_preconditioner_line(cgamd_dist *d, int stride);
+/* The rank's matrix values (always borrowed) were changed in place on the same pattern: as cgamd_solver_refresh_values(s, NULL, 0).
+ * Same contract: change the values only between solves, call this on EVERY rank before the next cgamd_dist_set_rhs.  Rank-local (it
+ * does not communicate; DistSolver.refresh_values all-gathers the status).  The value codes follow on every loop (RCCL, both
+ * peer-to-peer forms, single-reduction, slab); a captured graph is dropped when the code array was replaced; a Jacobi or line
+ * preconditioner built from the matrix is built again, and removed if that fails.  cgamd_dist_last_refresh: as
+ * cgamd_solver_last_refresh (the outcome may differ from rank to rank). */
+int cgamd_dist_refresh_values(cgamd_dist *d);
+int cgamd_dist_last_refresh(cgamd_dist *d);
 /* Peer-to-peer backend (CGAMD_DIST_P2P): instead of RCCL, every rank owns an uncached IPC-shared mailbox
  * (16 KiB header + n_halo values) that its peers write over xGMI; all-reduces are sums in rank order of values
  * deposited in per-rank slots (bitwise identical on all ranks).  Sequence: mailbox_alloc on every rank -> gather
