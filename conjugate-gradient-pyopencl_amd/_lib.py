@@ -139,6 +139,8 @@ def load():
         "cgamd_dist_destroy": (ci, [vp]),
         "cgamd_dist_set_rhs": (ci, [vp, vp, vp]),
         "cgamd_dist_iterate": (ci, [vp, ci]),
+        "cgamd_dist_iterate_until": (ci, [vp, ci, ctypes.c_double, ci, ctypes.POINTER(ci)]),
+        "cgamd_dist_iterations_done": (ci, [vp]),
         "cgamd_dist_get_x": (ci, [vp, vp]),
         "cgamd_dist_history": (ci, [vp, vp, ci]),
         "cgamd_dist_synchronize": (ci, [vp]),

@@ -215,11 +215,13 @@ int launch_dot_partials(int dtype, int n, const void *a, const void *b, long lon
 // result[r] = sum partials (value type)
 int launch_reduce_to_value(int dtype, const void *partials, int grid, int nrhs, void *result, hipStream_t st);
 int launch_axpy(int dtype, int n, const void *x, void *y, long long ld, const void *a, int sign, int nrhs, hipStream_t st);
-int launch_aypx(int dtype, int n, const void *x, void *y, long long ld, const void *a, int nrhs, hipStream_t st);
+struct CgStop;
+// (stop: the guarded form of the row-partitioned loops, cgamd_dist_iterate_until -- y is left alone once live[r] is cleared)
+int launch_aypx(int dtype, int n, const void *x, void *y, long long ld, const void *a, int nrhs, hipStream_t st, const CgStop *stop = nullptr);
 int launch_sub(int dtype, int n, const void *a, const void *b, void *res, long long ld, int nrhs, hipStream_t st);
 // fused x += alpha d ; r -= alpha q ; partials(r.r)
 int launch_axpy2_dot(int dtype, int n, const void *d, void *x, const void *q, void *r, long long ld,
-                     const void *alpha, int nrhs, void *partials, int grid, hipStream_t st, int vec_nt = 3);
+                     const void *alpha, int nrhs, void *partials, int grid, hipStream_t st, int vec_nt = 3, const CgStop *stop = nullptr);
 
 // device-resident scalar state of one CG run
 struct CgScalars {
@@ -238,7 +240,7 @@ struct CgScalars {
     const void *pcg_m = nullptr;
     void *pcg_rho2 = nullptr;
 };
-// Per-right-hand-side stop of cgamd_solver_iterate_until (stop_device.h): one device record per handle.  Launchers that take a
+// Per-right-hand-side stop of cgamd_solver_iterate_until and cgamd_dist_iterate_until (stop_device.h): one device record per handle.  Launchers that take a
 // `const CgStop *` run the guarded instantiation of their kernel when it is given and the unguarded one -- the code of
 // cgamd_solver_iterate -- when it is NULL.
 struct CgStop {
@@ -284,7 +286,7 @@ int launch_cg_delta0(int dtype, const void *partials, int grid, int nrhs, const 
 // alpha[r] = delta[r] / sum partials_dq
 int launch_cg_alpha(int dtype, const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st, const CgStop *stop = nullptr);
 // dn = sum partials_rr ; beta = dn/delta ; delta = dn ; history[++iter] = dn
-int launch_cg_beta(int dtype, const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st);
+int launch_cg_beta(int dtype, const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st, const CgStop *stop = nullptr);
 
 // d = beta d + r with beta = (sum of the P r.r partials) / history[iter-1] computed in every work-group's prologue;
 // work-group 0 records delta, beta and history[iter] (the cg_beta launch folded into aypx)
@@ -512,20 +514,20 @@ int jacobi_build_from_matrix(hipStream_t st, int dt, int nu, const std::string &
 // (r.z, then r.r); rho2 = two-entry parity buffer of rho = r.z (entry iter & 1), delta holds rho for cg_alpha
 // r -= alpha q ; z = m .* r (stored over q) ; partials of r.z and r.r
 int launch_pcg_jacobi_z(int dtype, int n, void *q_z, void *r, const void *m, const void *alpha, void *part_rz, void *part_rr, int grid,
-                        hipStream_t st);
+                        hipStream_t st, const CgStop *stop = nullptr);
 // red = {r.z, r.r} summed over all ranks (accumulator type).  mode 1: delta = rho2[0] = rho, history[0] = r.r, iter = 0;
 // mode 3: beta = rho / rho2[(iter - 1) & 1], delta = rho2[iter & 1] = rho, history[iter] = r.r
-int launch_pcg_scalars(int dtype, int mode, const void *red, const CgScalars &sc, void *rho2, hipStream_t st);
+int launch_pcg_scalars(int dtype, int mode, const void *red, const CgScalars &sc, void *rho2, hipStream_t st, const CgStop *stop = nullptr);
 // x += alpha d ; d = z + beta d (alpha, beta from the device scalars)
-int launch_pcg_xd_update(int dtype, int n, const void *z, void *d, void *x, const CgScalars &sc, hipStream_t st);
+int launch_pcg_xd_update(int dtype, int n, const void *z, void *d, void *x, const CgScalars &sc, hipStream_t st, const CgStop *stop = nullptr);
 // peer-to-peer: the two sums in ONE round (slot set 1 carries r.r and the epoch, the kMbPcg area r.z), rank order, then the scalar
 // step of launch_pcg_scalars (one work-group; advances *epoch)
 int launch_pcg_allreduce2_p2p(int dtype, int mode, const void *part_rz, const void *part_rr, int P, char *const *mailbox, int rank,
-                              int nranks, unsigned long long *epoch, const CgScalars &sc, void *rho2, hipStream_t st);
+                              int nranks, unsigned long long *epoch, const CgScalars &sc, void *rho2, hipStream_t st, const CgStop *stop = nullptr);
 // four-launch loop: that round and the beta step in every work-group's prologue, then x += alpha d and d = z + beta d
 int launch_pcg_aypx_beta_p2p(int dtype, int n, const void *z, void *d, void *x, const void *part_rz, const void *part_rr, int P,
                              char *const *mailbox, int rank, int nranks, const unsigned long long *epoch, const CgScalars &sc, void *rho2,
-                             hipStream_t st, int vec_nt = 0);
+                             hipStream_t st, int vec_nt = 0, const CgStop *stop = nullptr);
 // pcg_aypx_beta with p = z + beta p (z per right-hand side at stride ld), P thread-strided partials
 int launch_pcg_aypx_beta_z(int dtype, int n, void *p, const void *z, long long ld, const void *part_rz, const void *part_rr, int P, int nrhs,
                            const CgScalars &sc, void *rho2, void *xs, hipStream_t st, const CgStop *stop = nullptr);
@@ -537,13 +539,13 @@ int launch_spmv_p2p(int dtype, const SpmvPlan &plan, int n, long long nnz, const
 int spmv_p2p_grid(const SpmvPlan &plan);
 int launch_aypx_beta_p2p(int dtype, int n, const void *x, void *y, void *xs, const void *partials, int P, char *const *mailbox,
                          int rank, int nranks, int which, const unsigned long long *epoch, const CgScalars &sc, hipStream_t st,
-                         int vec_nt = 0);
+                         int vec_nt = 0, const CgStop *stop = nullptr);
 int launch_p2p_exchange(int dtype, const P2pExchange &e, void *v_ext, hipStream_t st);
 // global sum (rank order) of the local sum of `partials`, followed in the same launch by the scalar step that consumes
 // it: mode 1 = cg_delta0, 2 = cg_alpha, 3 = cg_beta; which in {0,1} selects the slot set
 int launch_p2p_allreduce(int dtype, int mode, const void *partials, int grid, char *const *mailbox, int rank, int nranks,
                          int which, unsigned long long *epoch, const CgScalars &sc, hipStream_t st,
-                         unsigned long long *bump0 = nullptr, unsigned long long *bump1 = nullptr);
+                         unsigned long long *bump0 = nullptr, unsigned long long *bump1 = nullptr, const CgStop *stop = nullptr);
 
 // ---- single-reduction (Chronopoulos-Gear) loop of the row-partitioned solver (cg1.hip): w = A r with r.w and r.r partials
 // ([2][row_blocks]); one global exchange per iteration in the prologue of the update launch

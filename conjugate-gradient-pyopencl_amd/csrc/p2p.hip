@@ -7,6 +7,7 @@
 #include "reduce_device.h"
 #include "launch_util.h"
 #include "p2p_device.h"
+#include "stop_device.h"
 
 #include <hip/hip_ext.h>
 
@@ -189,12 +190,15 @@ __global__ __launch_bounds__(BLOCK) void spmv_rowblock_p2p_kernel(SpmvP2pArgs<T>
 // its own mailbox and adds them in rank order (bitwise the same beta everywhere).  The epoch was advanced by the alpha
 // kernel of this iteration, so it is read-only here; slots are safe to reuse because a peer can only publish its next
 // value after it has seen my next d.q, which I publish after this launch has completed.
-template <typename T, int BLOCK, bool VEC, int VNT = 0>
+// GUARD (cgamd_dist_iterate_until, stop_device.h with one right-hand side): the round above runs whatever was decided -- deposit, spin
+// and collect are what the PEERS wait for -- and only then do the work-groups of a frozen handle leave, on live[0] (cleared by the
+// alpha step one iteration after the stop, never written here).  Thread 0 of work-group 0 decides from the dnT it records.
+template <typename T, int BLOCK, bool VEC, int VNT = 0, bool GUARD = false>
 __global__ __launch_bounds__(BLOCK) void aypx_beta_p2p_kernel(int n, const T *x, T *y, T *xs, const T *alpha,
                                                               const typename VT<T>::acc *partials, int P,
                                                               char *const *mailbox, int rank, int nranks, int which,
                                                               const unsigned long long *epoch, T *delta, T *beta, T *history,
-                                                              int history_cap, const int *iter) {
+                                                              int history_cap, const int *iter, CgStop g) {
     using A = typename VT<T>::acc;
     __shared__ A red[BLOCK / kWave];
     __shared__ double vx[64], vy[64];
@@ -223,6 +227,7 @@ __global__ __launch_bounds__(BLOCK) void aypx_beta_p2p_kernel(int n, const T *x,
         vy[s] = __longlong_as_double((long long)ld_sys(in + 1));
     }
     __syncthreads();
+    if (GUARD && g.live[0] == 0) return;        // this work-group's share of the round is done
     if (threadIdx.x == 0) {
         double2 tot2 = make_double2(0., 0.);
         for (int k = 0; k < nranks; ++k) { tot2.x += vx[k]; tot2.y += vy[k]; }
@@ -235,6 +240,7 @@ __global__ __launch_bounds__(BLOCK) void aypx_beta_p2p_kernel(int n, const T *x,
             beta[0] = bt;
             delta[0] = dnT;
             if (it < history_cap) history[it] = dnT;
+            if (GUARD) stop_decide(g, 0, it, dnT);      // the deferred x += alpha d below belongs to this iteration whatever is decided
         }
     }
     __syncthreads();
@@ -268,12 +274,15 @@ __global__ __launch_bounds__(BLOCK) void aypx_beta_p2p_kernel(int n, const T *x,
 // local partials -> sum over all ranks, in rank order on every rank (bitwise identical everywhere):
 // one work-group; thread s < nranks writes my value into rank s's slot, then waits for rank s's value in mine.
 // The scalar step that consumes the sum rides in the same launch (MODE): 1 = cg_delta0, 2 = cg_alpha, 3 = cg_beta.
-template <typename T, int MODE>
+// GUARD (cgamd_dist_iterate_until): the round and the epoch bumps are unconditional; MODE 2 is the alpha step of stop_device.h (the
+// counter moves while the handle is active, a stopped handle is retired and keeps its alpha), MODE 3 the deciding launch of the
+// staged loop (it leaves its scalars alone once live[0] is cleared)
+template <typename T, int MODE, bool GUARD = false>
 __global__ __launch_bounds__(kScalarBlock) void p2p_allreduce_kernel(const typename VT<T>::acc *partials, int grid,
                                                                      char *const *mailbox, int rank, int nranks, int which,
                                                                      unsigned long long *epoch, T *delta, T *alpha, T *beta,
                                                                      T *history, int history_cap, int *iter,
-                                                                     unsigned long long *bump0, unsigned long long *bump1) {
+                                                                     unsigned long long *bump0, unsigned long long *bump1, CgStop g) {
     using A = typename VT<T>::acc;
     __shared__ A smem[kScalarBlock / kWave];
     __shared__ double vx[64], vy[64];
@@ -305,15 +314,21 @@ __global__ __launch_bounds__(kScalarBlock) void p2p_allreduce_kernel(const typen
             history[0] = from_acc<T>(tot);
             *iter = 0;
         } else if (MODE == 2) {                // cg_alpha (clcg.c:317-327)
+            if (GUARD) {
+                stop_advance(g, iter);
+                if (g.stop[0] != 0) { stop_retire(g, 0); return; }
+            }
             const T dqT = from_acc<T>(tot);
             alpha[0] = from_acc<T>(acc_div(to_acc(delta[0]), to_acc(dqT)));
-            *iter = *iter + 1;
+            if (!GUARD) *iter = *iter + 1;
         } else {                               // cg_beta (clcg.c:376-391)
+            if (GUARD && g.live[0] == 0) return;
             const int it = *iter;
             const T dnT = from_acc<T>(tot);
             beta[0] = from_acc<T>(acc_div(to_acc(dnT), to_acc(delta[0])));
             delta[0] = dnT;
             if (it < history_cap) history[it] = dnT;
+            if (GUARD) stop_decide(g, 0, it, dnT);
         }
     }
 }
@@ -343,11 +358,12 @@ CG_DEV void pcg_collect(char *const *mailbox, int s, int rank, unsigned long lon
 
 // one work-group: local sums, the round, the scalar step (MODE 1 = set_rhs: delta = rho2[0] = rho, history[0] = r.r, iter = 0;
 // MODE 3 = beta of the staged loop).  Advances the slot epoch like p2p_allreduce_kernel.
-template <typename T, int MODE>
+// GUARD (cgamd_dist_iterate_until, MODE 3): the deciding launch of the staged PCG loop, as p2p_allreduce_kernel MODE 3
+template <typename T, int MODE, bool GUARD = false>
 __global__ __launch_bounds__(kScalarBlock) void pcg_allreduce2_p2p_kernel(const typename VT<T>::acc *part_rz, const typename VT<T>::acc *part_rr,
                                                                           int P, char *const *mailbox, int rank, int nranks,
                                                                           unsigned long long *epoch, T *delta, T *beta, T *history,
-                                                                          int history_cap, T *rho2, int *iter) {
+                                                                          int history_cap, T *rho2, int *iter, CgStop g) {
     using A = typename VT<T>::acc;
     __shared__ A smem[kScalarBlock / kWave];
     __shared__ double2 vz[64], vr[64];
@@ -375,11 +391,13 @@ __global__ __launch_bounds__(kScalarBlock) void pcg_allreduce2_p2p_kernel(const 
             history[0] = rrT;
             *iter = 0;
         } else {
+            if (GUARD && g.live[0] == 0) return;
             const int it = *iter;
             beta[0] = from_acc<T>(acc_div(to_acc(rhoT), to_acc(rho2[(it - 1) & 1])));
             delta[0] = rhoT;
             rho2[it & 1] = rhoT;
             if (it < history_cap) history[it] = rrT;
+            if (GUARD) stop_decide(g, 0, it, rrT);
         }
     }
 }
@@ -387,12 +405,13 @@ __global__ __launch_bounds__(kScalarBlock) void pcg_allreduce2_p2p_kernel(const 
 // Four-launch loop, last launch: aypx_beta_p2p_kernel for the preconditioned recurrence.  Work-group 0 deposits both local sums in
 // every rank's mailbox; every work-group waits for all ranks' pairs in its own and adds them in rank order (bitwise the same beta
 // everywhere); then x += alpha d and d = z + beta d.  The epoch was advanced by the alpha kernel of this iteration.
-template <typename T, int BLOCK, bool VEC, int VNT = 0>
+// GUARD: as aypx_beta_p2p_kernel -- the round first, then the frozen handle's work-groups leave on live[0]; the decision looks at r.r
+template <typename T, int BLOCK, bool VEC, int VNT = 0, bool GUARD = false>
 __global__ __launch_bounds__(BLOCK) void pcg_aypx_beta_p2p_kernel(int n, const T *z, T *y, T *xs, const T *alpha,
                                                                   const typename VT<T>::acc *part_rz, const typename VT<T>::acc *part_rr,
                                                                   int P, char *const *mailbox, int rank, int nranks,
                                                                   const unsigned long long *epoch, T *delta, T *beta, T *history,
-                                                                  int history_cap, T *rho2, const int *iter) {
+                                                                  int history_cap, T *rho2, const int *iter, CgStop g) {
     using A = typename VT<T>::acc;
     __shared__ A red[BLOCK / kWave];
     __shared__ double2 vz[64], vr[64], loc[2];
@@ -417,6 +436,7 @@ __global__ __launch_bounds__(BLOCK) void pcg_aypx_beta_p2p_kernel(int n, const T
         vr[s] = v[1];
     }
     __syncthreads();
+    if (GUARD && g.live[0] == 0) return;        // this work-group's share of the round is done
     if (threadIdx.x == 0) {
         double2 tz = make_double2(0., 0.), tr = make_double2(0., 0.);
         for (int k = 0; k < nranks; ++k) { tz.x += vz[k].x; tz.y += vz[k].y; tr.x += vr[k].x; tr.y += vr[k].y; }
@@ -428,7 +448,9 @@ __global__ __launch_bounds__(BLOCK) void pcg_aypx_beta_p2p_kernel(int n, const T
             beta[0] = bt;
             delta[0] = rhoT;            // cg_alpha divides this by d.q
             rho2[it & 1] = rhoT;
-            if (it < history_cap) history[it] = from_acc<T>(from_acc2<A>(tr));
+            const T rrT = from_acc<T>(from_acc2<A>(tr));
+            if (it < history_cap) history[it] = rrT;
+            if (GUARD) stop_decide(g, 0, it, rrT);
         }
     }
     __syncthreads();
@@ -543,29 +565,32 @@ template <typename K> static int resident_grid_cap(K kernel) {
 }
 template <typename T>
 static int aypx_beta_p2p_impl(int n, const void *x, void *y, void *xs, const void *partials, int P, char *const *mailbox, int rank,
-                              int nranks, int which, const unsigned long long *epoch, const CgScalars &sc, bool vec, int vnt, hipStream_t st) {
+                              int nranks, int which, const unsigned long long *epoch, const CgScalars &sc, bool vec, int vnt, hipStream_t st,
+                              const CgStop *stop) {
     auto *pp = static_cast<const typename VT<T>::acc *>(partials);
-#define CG_AP(V, N)                                                                                                          \
+    const CgStop none;
+#define CG_AP(V, N, G)                                                                                                       \
     do {                                                                                                                      \
-        static const int cap = resident_grid_cap(aypx_beta_p2p_kernel<T, kBlock, V, N>);                                     \
-        if (cap < 1) return fail(CGAMD_ERR_HIP, "aypx_beta_p2p: occupancy query failed; refusing an all-work-group spin");    \
-        const dim3 g(std::min(vec_grid(n, VT<T>::dtype), cap)), blk(kBlock);                                                 \
-        hipLaunchKernelGGL((aypx_beta_p2p_kernel<T, kBlock, V, N>), g, blk, 0, st, n, (const T *)x, (T *)y, (T *)xs,         \
+        static const int cap = resident_grid_cap(aypx_beta_p2p_kernel<T, kBlock, V, N, G>);   \
+        if (cap < 1) return fail(CGAMD_ERR_HIP, "aypx_beta_p2p: occupancy query failed; refusing an all-work-group spin");   \
+        const dim3 g(std::min(vec_grid(n, VT<T>::dtype), cap)), blk(kBlock);   \
+        hipLaunchKernelGGL((aypx_beta_p2p_kernel<T, kBlock, V, N, G>), g, blk, 0, st, n, (const T *)x, (T *)y, (T *)xs,      \
                            (const T *)sc.alpha, pp, P, mailbox, rank, nranks, which, epoch, (T *)sc.delta, (T *)sc.beta,     \
-                           (T *)sc.history, sc.history_cap, (const int *)sc.iter);                                           \
+                           (T *)sc.history, sc.history_cap, (const int *)sc.iter, G ? *stop : none);                         \
     } while (0)
-    if (vec && (vnt & 1)) CG_AP(true, 1); else if (vec) CG_AP(true, 0); else CG_AP(false, 0);
+    if (stop) { if (vec && (vnt & 1)) CG_AP(true, 1, true); else if (vec) CG_AP(true, 0, true); else CG_AP(false, 0, true); }
+    else if (vec && (vnt & 1)) CG_AP(true, 1, false); else if (vec) CG_AP(true, 0, false); else CG_AP(false, 0, false);
 #undef CG_AP
     return check_launch("aypx_beta_p2p");
 }
 int launch_aypx_beta_p2p(int dtype, int n, const void *x, void *y, void *xs, const void *partials, int P, char *const *mailbox,
                          int rank, int nranks, int which, const unsigned long long *epoch, const CgScalars &sc, hipStream_t st,
-                         int vec_nt) {
+                         int vec_nt, const CgStop *stop) {
     if (n <= 0) return CGAMD_OK;
     if (nranks > 64) return fail(CGAMD_ERR_INVALID, "p2p all-reduce: at most 64 ranks");
     const bool v = vec_ok(dtype, n, 1, {x, y, xs});
     const int vnt = tune().vec_nt >= 0 ? tune().vec_nt : vec_nt;
-    CG_DISPATCH(dtype, aypx_beta_p2p_impl, n, x, y, xs, partials, P, mailbox, rank, nranks, which, epoch, sc, v, vnt, st);
+    CG_DISPATCH(dtype, aypx_beta_p2p_impl, n, x, y, xs, partials, P, mailbox, rank, nranks, which, epoch, sc, v, vnt, st, stop);
 }
 
 template <typename T> static int p2p_exchange_impl(const P2pExchange &e, void *v_ext, hipStream_t st) {
@@ -582,66 +607,73 @@ int launch_p2p_exchange(int dtype, const P2pExchange &e, void *v_ext, hipStream_
 template <typename T>
 static int p2p_ar_impl(int mode, const void *partials, int grid, char *const *mailbox, int rank, int nranks, int which,
                        unsigned long long *epoch, const CgScalars &sc, unsigned long long *bump0, unsigned long long *bump1,
-                       hipStream_t st) {
+                       hipStream_t st, const CgStop *stop) {
     auto *pp = static_cast<const typename VT<T>::acc *>(partials);
-#define CG_AR(M)                                                                                                            \
-    hipLaunchKernelGGL((p2p_allreduce_kernel<T, M>), dim3(1), dim3(kScalarBlock), 0, st, pp, grid, mailbox, rank, nranks, which, \
-                       epoch, (T *)sc.delta, (T *)sc.alpha, (T *)sc.beta, (T *)sc.history, sc.history_cap, sc.iter, bump0, bump1)
-    if (mode == 1) CG_AR(1); else if (mode == 2) CG_AR(2); else CG_AR(3);
+    const CgStop none;
+#define CG_AR(M, G)                                                                                                         \
+    hipLaunchKernelGGL((p2p_allreduce_kernel<T, M, G>), dim3(1), dim3(kScalarBlock), 0, st, pp, grid, mailbox, rank, nranks, which, \
+                       epoch, (T *)sc.delta, (T *)sc.alpha, (T *)sc.beta, (T *)sc.history, sc.history_cap, sc.iter, bump0, bump1, G ? *stop : none)
+    if (mode == 1) CG_AR(1, false);
+    else if (stop) { if (mode == 2) CG_AR(2, true); else CG_AR(3, true); }
+    else if (mode == 2) CG_AR(2, false); else CG_AR(3, false);
 #undef CG_AR
     return check_launch("p2p_allreduce");
 }
 int launch_p2p_allreduce(int dtype, int mode, const void *partials, int grid, char *const *mailbox, int rank, int nranks,
                          int which, unsigned long long *epoch, const CgScalars &sc, hipStream_t st, unsigned long long *bump0,
-                         unsigned long long *bump1) {
+                         unsigned long long *bump1, const CgStop *stop) {
     if (nranks > 64) return fail(CGAMD_ERR_INVALID, "p2p all-reduce: at most 64 ranks");
-    CG_DISPATCH(dtype, p2p_ar_impl, mode, partials, grid, mailbox, rank, nranks, which, epoch, sc, bump0, bump1, st);
+    CG_DISPATCH(dtype, p2p_ar_impl, mode, partials, grid, mailbox, rank, nranks, which, epoch, sc, bump0, bump1, st, stop);
 }
 
 template <typename T>
 static int pcg_ar2_impl(int mode, const void *part_rz, const void *part_rr, int P, char *const *mailbox, int rank, int nranks,
-                        unsigned long long *epoch, const CgScalars &sc, void *rho2, hipStream_t st) {
+                        unsigned long long *epoch, const CgScalars &sc, void *rho2, hipStream_t st, const CgStop *stop) {
     using A = typename VT<T>::acc;
-#define CG_AR2(M)                                                                                                                  \
-    hipLaunchKernelGGL((pcg_allreduce2_p2p_kernel<T, M>), dim3(1), dim3(kScalarBlock), 0, st, (const A *)part_rz, (const A *)part_rr, P, \
-                       mailbox, rank, nranks, epoch, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, sc.iter)
-    if (mode == 1) CG_AR2(1); else CG_AR2(3);
+    const CgStop none;
+#define CG_AR2(M, G)                                                                                                               \
+    hipLaunchKernelGGL((pcg_allreduce2_p2p_kernel<T, M, G>), dim3(1), dim3(kScalarBlock), 0, st, (const A *)part_rz, (const A *)part_rr, P, \
+                       mailbox, rank, nranks, epoch, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, sc.iter, G ? *stop : none)
+    if (mode == 1) CG_AR2(1, false); else if (stop) CG_AR2(3, true); else CG_AR2(3, false);
 #undef CG_AR2
     return check_launch("pcg_allreduce2_p2p");
 }
 int launch_pcg_allreduce2_p2p(int dtype, int mode, const void *part_rz, const void *part_rr, int P, char *const *mailbox, int rank,
-                              int nranks, unsigned long long *epoch, const CgScalars &sc, void *rho2, hipStream_t st) {
+                              int nranks, unsigned long long *epoch, const CgScalars &sc, void *rho2, hipStream_t st, const CgStop *stop) {
     if (nranks > 64) return fail(CGAMD_ERR_INVALID, "p2p all-reduce: at most 64 ranks");
-    CG_DISPATCH(dtype, pcg_ar2_impl, mode, part_rz, part_rr, P, mailbox, rank, nranks, epoch, sc, rho2, st);
+    CG_DISPATCH(dtype, pcg_ar2_impl, mode, part_rz, part_rr, P, mailbox, rank, nranks, epoch, sc, rho2, st, stop);
 }
 
 // (every work-group spins: the grid is capped at what is resident at once, as for aypx_beta_p2p_kernel)
 template <typename T>
 static int pcg_aypx_beta_p2p_impl(int n, const void *z, void *y, void *xs, const void *part_rz, const void *part_rr, int P,
                                   char *const *mailbox, int rank, int nranks, const unsigned long long *epoch, const CgScalars &sc,
-                                  void *rho2, bool vec, int vnt, hipStream_t st) {
+                                  void *rho2, bool vec, int vnt, hipStream_t st, const CgStop *stop) {
     using A = typename VT<T>::acc;
-#define CG_PAP(V, N)                                                                                                            \
+    const CgStop none;
+#define CG_PAP(V, N, G)                                                                                                         \
     do {                                                                                                                         \
-        static const int cap = resident_grid_cap(pcg_aypx_beta_p2p_kernel<T, kBlock, V, N>);                                    \
+        static const int cap = resident_grid_cap(pcg_aypx_beta_p2p_kernel<T, kBlock, V, N, G>);   \
         if (cap < 1) return fail(CGAMD_ERR_HIP, "pcg_aypx_beta_p2p: occupancy query failed; refusing an all-work-group spin");   \
-        const dim3 g(std::min(vec_grid(n, VT<T>::dtype), cap)), blk(kBlock);                                                    \
-        hipLaunchKernelGGL((pcg_aypx_beta_p2p_kernel<T, kBlock, V, N>), g, blk, 0, st, n, (const T *)z, (T *)y, (T *)xs,        \
+        const dim3 g(std::min(vec_grid(n, VT<T>::dtype), cap)), blk(kBlock);   \
+        hipLaunchKernelGGL((pcg_aypx_beta_p2p_kernel<T, kBlock, V, N, G>), g, blk, 0, st, n, (const T *)z, (T *)y, (T *)xs,     \
                            (const T *)sc.alpha, (const A *)part_rz, (const A *)part_rr, P, mailbox, rank, nranks, epoch,        \
-                           (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter);      \
+                           (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, (const int *)sc.iter,       \
+                           G ? *stop : none);                                                                                    \
     } while (0)
-    if (vec && (vnt & 1)) CG_PAP(true, 1); else if (vec) CG_PAP(true, 0); else CG_PAP(false, 0);
+    if (stop) { if (vec && (vnt & 1)) CG_PAP(true, 1, true); else if (vec) CG_PAP(true, 0, true); else CG_PAP(false, 0, true); }
+    else if (vec && (vnt & 1)) CG_PAP(true, 1, false); else if (vec) CG_PAP(true, 0, false); else CG_PAP(false, 0, false);
 #undef CG_PAP
     return check_launch("pcg_aypx_beta_p2p");
 }
 int launch_pcg_aypx_beta_p2p(int dtype, int n, const void *z, void *d, void *x, const void *part_rz, const void *part_rr, int P,
                              char *const *mailbox, int rank, int nranks, const unsigned long long *epoch, const CgScalars &sc, void *rho2,
-                             hipStream_t st, int vec_nt) {
+                             hipStream_t st, int vec_nt, const CgStop *stop) {
     if (n <= 0) return CGAMD_OK;
     if (nranks > 64) return fail(CGAMD_ERR_INVALID, "p2p all-reduce: at most 64 ranks");
     const bool v = vec_ok(dtype, n, 1, {z, d, x});
     const int vnt = tune().vec_nt >= 0 ? tune().vec_nt : vec_nt;
-    CG_DISPATCH(dtype, pcg_aypx_beta_p2p_impl, n, z, d, x, part_rz, part_rr, P, mailbox, rank, nranks, epoch, sc, rho2, v, vnt, st);
+    CG_DISPATCH(dtype, pcg_aypx_beta_p2p_impl, n, z, d, x, part_rz, part_rr, P, mailbox, rank, nranks, epoch, sc, rho2, v, vnt, st, stop);
 }
 
 }  // namespace cgamd

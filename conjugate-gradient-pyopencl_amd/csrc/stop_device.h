@@ -15,6 +15,11 @@
 // frozen right-hand side 0 does not hold the others' history rows back, and launches after the last stop change nothing at all.
 // A frozen right-hand side repeats its last history entry in the rows the others go on to fill: the beta prologues read
 // history[iter - 1] of their own column only, and a read-back of `iterations_done + 1` rows holds no unwritten value.
+//
+// cgamd_dist_iterate_until (dist.cpp) is the same scheme with one right-hand side and rr = the GLOBALLY reduced r.r, which every rank
+// holds bit for bit.  There an exit never sits in front of a mailbox store, a spin, an epoch update or an RCCL call: the kernels that
+// carry a reduction round (p2p.hip) finish their share of it first and leave afterwards; the staged and RCCL loops update x before
+// the deciding launch, and the d step that follows it leaves on live[] like a beta launch.
 #pragma once
 #include "cgamd_internal.h"
 #include "device_types.h"

@@ -70,12 +70,14 @@ CG_DEV void axpy2_dot_body(int n, const T *__restrict__ d, T *__restrict__ x, co
     if (threadIdx.x == 0) partials[(long long)r * gridDim.x + blockIdx.x] = tot;
 }
 
-template <typename T, int BLOCK, bool VEC, int VNT = 0>
+// GUARD: the instantiation cgamd_dist_iterate_until launches (staged and RCCL loops) -- see axpy_dot_kernel
+template <typename T, int BLOCK, bool VEC, int VNT = 0, bool GUARD = false>
 __global__ __launch_bounds__(BLOCK) void axpy2_dot_kernel(int n, const T *__restrict__ d, T *__restrict__ x,
                                                           const T *__restrict__ q, T *__restrict__ rv, long long ld,
                                                           const T *__restrict__ alpha,
-                                                          typename VT<T>::acc *__restrict__ partials) {
+                                                          typename VT<T>::acc *__restrict__ partials, CgStop g) {
     __shared__ typename VT<T>::acc red[BLOCK / kWave];
+    if (GUARD && g.stop[blockIdx.y] != 0) return;
     axpy2_dot_body<T, BLOCK, VEC, VNT>(n, d, x, q, rv, ld, alpha[blockIdx.y], partials, red);
 }
 
@@ -251,6 +253,32 @@ __global__ __launch_bounds__(BLOCK) void ewise_kernel(int n, const T *__restrict
     }
     for (long long i = i0; i < n; i += stride)
         y[i] = f(x[i], OP != 3 ? y[i] : vzero<T>(), OP == 3 ? b2[i] : vzero<T>());
+}
+
+// y = a y + x (ewise_kernel OP 2, the very expression) of cgamd_dist_iterate_until's staged and RCCL loops: the d step that FOLLOWS
+// the deciding beta launch, so it leaves on live[] like a beta-side launch (the stopping iteration still gets its d)
+template <typename T, int BLOCK, bool VEC>
+__global__ __launch_bounds__(BLOCK) void aypx_live_kernel(int n, const T *__restrict__ x, T *__restrict__ y, long long ld,
+                                                          const T *__restrict__ alpha, CgStop g) {
+    const int r = blockIdx.y;
+    if (g.live[r] == 0) return;
+    x += (long long)r * ld; y += (long long)r * ld;
+    const T al = alpha[r];
+    constexpr int E = Pack<T>::N;
+    const long long stride = (long long)gridDim.x * BLOCK;
+    long long i0 = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (VEC) {
+        const long long npack = n / E;
+        for (long long i = i0; i < npack; i += stride) {
+            const Pack<T> px = ld_pack(x + i * E);
+            Pack<T> py = ld_pack(y + i * E);
+#pragma unroll
+            for (int k = 0; k < E; ++k) py.v[k] = vaypx(al, py.v[k], px.v[k]);
+            st_pack(y + i * E, py);
+        }
+        i0 += npack * E;
+    }
+    for (long long i = i0; i < n; i += stride) y[i] = vaypx(al, y[i], x[i]);
 }
 
 // d = beta d + r with beta computed in the prologue (replaces the cg_beta launch of the 5-launch loop):
@@ -739,11 +767,14 @@ __global__ __launch_bounds__(kScalarBlock) void cg_alpha2_kernel(const typename 
     }
 }
 
-template <typename T>
+// GUARD (cgamd_dist_iterate_until, RCCL loop): the deciding launch -- it leaves on live[], which the alpha step clears one iteration
+// after the stop, and writes stop[] from the history entry it records (stop_device.h)
+template <typename T, bool GUARD = false>
 __global__ __launch_bounds__(kScalarBlock) void cg_beta_kernel(const typename VT<T>::acc *partials, int grid, int nrhs, T *delta,
-                                                      T *beta, T *history, int history_cap, const int *iter) {
+                                                      T *beta, T *history, int history_cap, const int *iter, CgStop g) {
     __shared__ typename VT<T>::acc smem[kScalarBlock / kWave];
     const int r = blockIdx.x;
+    if (GUARD && g.live[r] == 0) return;
     const auto dn = sum_partials_block(partials + (long long)r * grid, grid, smem);
     if (threadIdx.x == 0) {
         const int it = *iter;   // already advanced by cg_alpha of this iteration
@@ -751,6 +782,7 @@ __global__ __launch_bounds__(kScalarBlock) void cg_beta_kernel(const typename VT
         beta[r] = from_acc<T>(acc_div(to_acc(dnT), to_acc(delta[r])));   // clcg.c:389-391
         delta[r] = dnT;
         if (it < history_cap) history[(long long)it * nrhs + r] = dnT;
+        if (GUARD) stop_decide(g, r, it, dnT);
     }
 }
 
@@ -832,9 +864,16 @@ int launch_axpy(int dtype, int n, const void *x, void *y, long long ld, const vo
     if (sign) { CG_DISPATCH(dtype, axpy_p, n, x, y, ld, a, nrhs, v, st); }
     CG_DISPATCH(dtype, axpy_m, n, x, y, ld, a, nrhs, v, st);
 }
-int launch_aypx(int dtype, int n, const void *x, void *y, long long ld, const void *a, int nrhs, hipStream_t st) {
+template <typename T> static int aypx_live_impl(int n, const void *x, void *y, long long ld, const void *a, int nrhs, bool vec, hipStream_t st, const CgStop *stop) {
+    dim3 g(vec_grid(n, VT<T>::dtype, nrhs), nrhs), blk(kBlock);
+    if (vec) hipLaunchKernelGGL((aypx_live_kernel<T, kBlock, true>), g, blk, 0, st, n, (const T *)x, (T *)y, ld, (const T *)a, *stop);
+    else hipLaunchKernelGGL((aypx_live_kernel<T, kBlock, false>), g, blk, 0, st, n, (const T *)x, (T *)y, ld, (const T *)a, *stop);
+    return check_launch("aypx (guarded)");
+}
+int launch_aypx(int dtype, int n, const void *x, void *y, long long ld, const void *a, int nrhs, hipStream_t st, const CgStop *stop) {
     if (n <= 0) return CGAMD_OK;
     const bool v = vec_ok(dtype, ld, nrhs, {x, y});
+    if (stop) { CG_DISPATCH(dtype, aypx_live_impl, n, x, y, ld, a, nrhs, v, st, stop); }
     CG_DISPATCH(dtype, aypx_i, n, x, y, ld, a, nrhs, v, st);
 }
 int launch_sub(int dtype, int n, const void *a, const void *b, void *res, long long ld, int nrhs, hipStream_t st) {
@@ -845,14 +884,21 @@ int launch_sub(int dtype, int n, const void *a, const void *b, void *res, long l
 
 template <typename T>
 static int axpy2_impl(int n, const void *d, void *x, const void *q, void *r, long long ld, const void *alpha, int nrhs,
-                      void *partials, int grid, bool vec, int vnt, hipStream_t st) {
+                      void *partials, int grid, bool vec, int vnt, hipStream_t st, const CgStop *stop) {
     dim3 g(grid, nrhs), blk(kBlock);
     auto *pp = static_cast<typename VT<T>::acc *>(partials);
-    if (vec && vnt == 1) hipLaunchKernelGGL((axpy2_dot_kernel<T, kBlock, true, 1>), g, blk, 0, st, n, (const T *)d, (T *)x, (const T *)q, (T *)r, ld, (const T *)alpha, pp);
-    else if (vec && vnt == 2) hipLaunchKernelGGL((axpy2_dot_kernel<T, kBlock, true, 2>), g, blk, 0, st, n, (const T *)d, (T *)x, (const T *)q, (T *)r, ld, (const T *)alpha, pp);
-    else if (vec && vnt == 3) hipLaunchKernelGGL((axpy2_dot_kernel<T, kBlock, true, 3>), g, blk, 0, st, n, (const T *)d, (T *)x, (const T *)q, (T *)r, ld, (const T *)alpha, pp);
-    else if (vec) hipLaunchKernelGGL((axpy2_dot_kernel<T, kBlock, true>), g, blk, 0, st, n, (const T *)d, (T *)x, (const T *)q, (T *)r, ld, (const T *)alpha, pp);
-    else hipLaunchKernelGGL((axpy2_dot_kernel<T, kBlock, false>), g, blk, 0, st, n, (const T *)d, (T *)x, (const T *)q, (T *)r, ld, (const T *)alpha, pp);
+    const CgStop none;
+#define CG_A2D(V, N, G) hipLaunchKernelGGL((axpy2_dot_kernel<T, kBlock, V, N, G>), g, blk, 0, st, n, (const T *)d, (T *)x, (const T *)q, (T *)r, ld, (const T *)alpha, pp, G ? *stop : none)
+    if (stop) {
+        if (vec && vnt == 1) CG_A2D(true, 1, true); else if (vec && vnt == 2) CG_A2D(true, 2, true); else if (vec && vnt == 3) CG_A2D(true, 3, true);
+        else if (vec) CG_A2D(true, 0, true); else CG_A2D(false, 0, true);
+    }
+    else if (vec && vnt == 1) CG_A2D(true, 1, false);
+    else if (vec && vnt == 2) CG_A2D(true, 2, false);
+    else if (vec && vnt == 3) CG_A2D(true, 3, false);
+    else if (vec) CG_A2D(true, 0, false);
+    else CG_A2D(false, 0, false);
+#undef CG_A2D
     return check_launch("axpy2_dot");
 }
 template <typename T>
@@ -981,10 +1027,10 @@ int launch_axpy2_dot_alpha(int dtype, int n, const void *d, void *x, const void 
     CG_DISPATCH(dtype, axpy2_alpha_impl, n, d, x, q, r, ld, part_dq, P, sc, nrhs, partials, grid, vec, st);
 }
 int launch_axpy2_dot(int dtype, int n, const void *d, void *x, const void *q, void *r, long long ld, const void *alpha,
-                     int nrhs, void *partials, int grid, hipStream_t st, int vec_nt) {
+                     int nrhs, void *partials, int grid, hipStream_t st, int vec_nt, const CgStop *stop) {
     const bool vec = vec_ok(dtype, ld, nrhs, {d, x, q, r});
     const int vnt = tune().vec_nt >= 0 ? tune().vec_nt : vec_nt;
-    CG_DISPATCH(dtype, axpy2_impl, n, d, x, q, r, ld, alpha, nrhs, partials, grid, vec, vnt, st);
+    CG_DISPATCH(dtype, axpy2_impl, n, d, x, q, r, ld, alpha, nrhs, partials, grid, vec, vnt, st, stop);
 }
 
 template <typename T> static int delta0_impl(const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st) {
@@ -1014,13 +1060,16 @@ template <typename T> static int alpha_impl(const void *partials, int grid, int 
 int launch_cg_alpha(int dtype, const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st, const CgStop *stop) {
     CG_DISPATCH(dtype, alpha_impl, partials, grid, nrhs, s, st, stop);
 }
-template <typename T> static int beta_impl(const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st) {
-    hipLaunchKernelGGL((cg_beta_kernel<T>), dim3(nrhs), dim3(kScalarBlock), 0, st, static_cast<const typename VT<T>::acc *>(partials),
-                       grid, nrhs, (T *)s.delta, (T *)s.beta, (T *)s.history, s.history_cap, s.iter);
+template <typename T> static int beta_impl(const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st, const CgStop *stop) {
+    const CgStop none;
+#define CG_B(G) hipLaunchKernelGGL((cg_beta_kernel<T, G>), dim3(nrhs), dim3(kScalarBlock), 0, st, static_cast<const typename VT<T>::acc *>(partials), \
+                                   grid, nrhs, (T *)s.delta, (T *)s.beta, (T *)s.history, s.history_cap, s.iter, G ? *stop : none)
+    if (stop) CG_B(true); else CG_B(false);
+#undef CG_B
     return check_launch("cg_beta");
 }
-int launch_cg_beta(int dtype, const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st) {
-    CG_DISPATCH(dtype, beta_impl, partials, grid, nrhs, s, st);
+int launch_cg_beta(int dtype, const void *partials, int grid, int nrhs, const CgScalars &s, hipStream_t st, const CgStop *stop) {
+    CG_DISPATCH(dtype, beta_impl, partials, grid, nrhs, s, st, stop);
 }
 
 int launch_reduce_to_acc(int dtype, const void *partials, int grid, int nrhs, void *out, hipStream_t st) {
@@ -1154,12 +1203,14 @@ int launch_pcg_delta0(int dtype, const void *part_rz, const void *part_rr, int P
 // direction update that follows is the same for the diagonal and the line forms.  The Jacobi update: r -= alpha q, z = m .* r
 // stored over q, partials of r.z and r.r -- the expressions and the summation order of pcg_axpy2_dot2_kernel (5NV bytes; the
 // update that follows reads z instead of m and r, so the iteration moves what the single-GPU one does)
-template <typename T, int BLOCK, bool VEC>
+// GUARD (cgamd_dist_iterate_until): an r update -- it leaves on stop[], like axpy_dot_kernel
+template <typename T, int BLOCK, bool VEC, bool GUARD = false>
 __global__ __launch_bounds__(BLOCK) void pcg_jacobi_z_kernel(int n, T *__restrict__ qz, T *__restrict__ rv, const T *__restrict__ m,
                                                              const T *__restrict__ alpha, typename VT<T>::acc *__restrict__ part_rz,
-                                                             typename VT<T>::acc *__restrict__ part_rr) {
+                                                             typename VT<T>::acc *__restrict__ part_rr, CgStop g) {
     using A = typename VT<T>::acc;
     __shared__ A red[BLOCK / kWave];
+    if (GUARD && g.stop[0] != 0) return;
     const T al = alpha[0];
     A arz = vzero<A>(), arr = vzero<A>();
     constexpr int E = Pack<T>::N;
@@ -1197,25 +1248,31 @@ __global__ __launch_bounds__(BLOCK) void pcg_jacobi_z_kernel(int n, T *__restric
 }
 template <typename T>
 static int pcg_jacobi_z_impl(int n, void *qz, void *r, const void *m, const void *alpha, void *part_rz, void *part_rr, int grid, bool vec,
-                             hipStream_t st) {
+                             hipStream_t st, const CgStop *stop) {
     using A = typename VT<T>::acc;
     const dim3 g(grid), blk(kBlock);
-    if (vec) hipLaunchKernelGGL((pcg_jacobi_z_kernel<T, kBlock, true>), g, blk, 0, st, n, (T *)qz, (T *)r, (const T *)m, (const T *)alpha, (A *)part_rz, (A *)part_rr);
-    else hipLaunchKernelGGL((pcg_jacobi_z_kernel<T, kBlock, false>), g, blk, 0, st, n, (T *)qz, (T *)r, (const T *)m, (const T *)alpha, (A *)part_rz, (A *)part_rr);
+    const CgStop none;
+#define CG_JZ(V, G) hipLaunchKernelGGL((pcg_jacobi_z_kernel<T, kBlock, V, G>), g, blk, 0, st, n, (T *)qz, (T *)r, (const T *)m, (const T *)alpha, (A *)part_rz, (A *)part_rr, G ? *stop : none)
+    if (stop) { if (vec) CG_JZ(true, true); else CG_JZ(false, true); }
+    else if (vec) CG_JZ(true, false);
+    else CG_JZ(false, false);
+#undef CG_JZ
     return check_launch("pcg_jacobi_z");
 }
 int launch_pcg_jacobi_z(int dtype, int n, void *q_z, void *r, const void *m, const void *alpha, void *part_rz, void *part_rr, int grid,
-                        hipStream_t st) {
+                        hipStream_t st, const CgStop *stop) {
     if (n <= 0 || grid < 1) return fail(CGAMD_ERR_INVALID, "pcg_jacobi_z: empty launch");
     const bool vec = vec_ok(dtype, n, 1, {q_z, r, m});
-    CG_DISPATCH(dtype, pcg_jacobi_z_impl, n, q_z, r, m, alpha, part_rz, part_rr, grid, vec, st);
+    CG_DISPATCH(dtype, pcg_jacobi_z_impl, n, q_z, r, m, alpha, part_rz, part_rr, grid, vec, st, stop);
 }
 
 // the scalar step on {r.z, r.r} already summed over the ranks (RCCL backend): MODE 1 = set_rhs, 3 = beta
-template <typename T, int MODE>
+// GUARD (cgamd_dist_iterate_until, MODE 3): the deciding launch of the RCCL PCG loop (see cg_beta_kernel)
+template <typename T, int MODE, bool GUARD = false>
 __global__ __launch_bounds__(64) void pcg_scalars_kernel(const typename VT<T>::acc *red, T *delta, T *beta, T *history, int history_cap,
-                                                         T *rho2, int *iter) {
+                                                         T *rho2, int *iter, CgStop g) {
     if (threadIdx.x != 0) return;
+    if (GUARD && g.live[0] == 0) return;
     const T rhoT = from_acc<T>(red[0]), rrT = from_acc<T>(red[1]);
     if (MODE == 1) {
         delta[0] = rhoT;
@@ -1228,22 +1285,29 @@ __global__ __launch_bounds__(64) void pcg_scalars_kernel(const typename VT<T>::a
         delta[0] = rhoT;            // cg_alpha divides this by d.q
         rho2[it & 1] = rhoT;
         if (it < history_cap) history[it] = rrT;
+        if (GUARD) stop_decide(g, 0, it, rrT);
     }
 }
-template <typename T> static int pcg_scalars_impl(int mode, const void *red, const CgScalars &sc, void *rho2, hipStream_t st) {
+template <typename T> static int pcg_scalars_impl(int mode, const void *red, const CgScalars &sc, void *rho2, hipStream_t st, const CgStop *stop) {
     using A = typename VT<T>::acc;
-    if (mode == 1) hipLaunchKernelGGL((pcg_scalars_kernel<T, 1>), dim3(1), dim3(64), 0, st, (const A *)red, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, sc.iter);
-    else hipLaunchKernelGGL((pcg_scalars_kernel<T, 3>), dim3(1), dim3(64), 0, st, (const A *)red, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, sc.iter);
+    const CgStop none;
+#define CG_PS(M, G) hipLaunchKernelGGL((pcg_scalars_kernel<T, M, G>), dim3(1), dim3(64), 0, st, (const A *)red, (T *)sc.delta, (T *)sc.beta, (T *)sc.history, sc.history_cap, (T *)rho2, sc.iter, G ? *stop : none)
+    if (mode == 1) CG_PS(1, false);
+    else if (stop) CG_PS(3, true);
+    else CG_PS(3, false);
+#undef CG_PS
     return check_launch("pcg_scalars");
 }
-int launch_pcg_scalars(int dtype, int mode, const void *red, const CgScalars &sc, void *rho2, hipStream_t st) {
-    CG_DISPATCH(dtype, pcg_scalars_impl, mode, red, sc, rho2, st);
+int launch_pcg_scalars(int dtype, int mode, const void *red, const CgScalars &sc, void *rho2, hipStream_t st, const CgStop *stop) {
+    CG_DISPATCH(dtype, pcg_scalars_impl, mode, red, sc, rho2, st, stop);
 }
 
 // x += alpha d ; d = z + beta d: the update of pcg_aypx_beta_kernel<ZV> with beta already on the device
-template <typename T, int BLOCK, bool VEC>
+// GUARD (cgamd_dist_iterate_until): it follows the deciding launch and carries the stopping iteration's x += alpha d, so it leaves on live[]
+template <typename T, int BLOCK, bool VEC, bool GUARD = false>
 __global__ __launch_bounds__(BLOCK) void pcg_xd_update_kernel(int n, const T *__restrict__ z, T *__restrict__ d, T *__restrict__ xs,
-                                                              const T *__restrict__ alpha, const T *__restrict__ beta) {
+                                                              const T *__restrict__ alpha, const T *__restrict__ beta, CgStop g) {
+    if (GUARD && g.live[0] == 0) return;
     const T al = alpha[0], bt = beta[0];
     constexpr int E = Pack<T>::N;
     const long long stride = (long long)gridDim.x * BLOCK;
@@ -1269,16 +1333,20 @@ __global__ __launch_bounds__(BLOCK) void pcg_xd_update_kernel(int n, const T *__
         d[i] = vadd(vmul(bt, dv), z[i]);
     }
 }
-template <typename T> static int pcg_xd_impl(int n, const void *z, void *d, void *x, const CgScalars &sc, bool vec, hipStream_t st) {
+template <typename T> static int pcg_xd_impl(int n, const void *z, void *d, void *x, const CgScalars &sc, bool vec, hipStream_t st, const CgStop *stop) {
     const dim3 g(vec_grid(n, VT<T>::dtype)), blk(kBlock);
-    if (vec) hipLaunchKernelGGL((pcg_xd_update_kernel<T, kBlock, true>), g, blk, 0, st, n, (const T *)z, (T *)d, (T *)x, (const T *)sc.alpha, (const T *)sc.beta);
-    else hipLaunchKernelGGL((pcg_xd_update_kernel<T, kBlock, false>), g, blk, 0, st, n, (const T *)z, (T *)d, (T *)x, (const T *)sc.alpha, (const T *)sc.beta);
+    const CgStop none;
+#define CG_XD(V, G) hipLaunchKernelGGL((pcg_xd_update_kernel<T, kBlock, V, G>), g, blk, 0, st, n, (const T *)z, (T *)d, (T *)x, (const T *)sc.alpha, (const T *)sc.beta, G ? *stop : none)
+    if (stop) { if (vec) CG_XD(true, true); else CG_XD(false, true); }
+    else if (vec) CG_XD(true, false);
+    else CG_XD(false, false);
+#undef CG_XD
     return check_launch("pcg_xd_update");
 }
-int launch_pcg_xd_update(int dtype, int n, const void *z, void *d, void *x, const CgScalars &sc, hipStream_t st) {
+int launch_pcg_xd_update(int dtype, int n, const void *z, void *d, void *x, const CgScalars &sc, hipStream_t st, const CgStop *stop) {
     if (n <= 0) return CGAMD_OK;
     const bool vec = vec_ok(dtype, n, 1, {z, d, x});
-    CG_DISPATCH(dtype, pcg_xd_impl, n, z, d, x, sc, vec, st);
+    CG_DISPATCH(dtype, pcg_xd_impl, n, z, d, x, sc, vec, st, stop);
 }
 
 }  // namespace cgamd

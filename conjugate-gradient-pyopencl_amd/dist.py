@@ -16,6 +16,8 @@ boundary exchange for A*d; this module is that (new design, no reference counter
   4. `cg_loop`              the same recurrence written against two small interfaces (local ops, comm);
                             used by the CPU/gloo tests with the oracle's kernels, and usable on GPUs as a
                             slow cross-check of the C loop (per-iteration torch.distributed calls).
+  5. `DistSolver.solve_until` / `iterate_until`: the C loop solved to a tolerance, the stop decided on the device from the
+                            all-reduced r.r (cgamd_dist_iterate_until); `cg_loop_until` / `pcg_loop_until` are its host mirrors.
 
 Everything in steps 1-2 is backend agnostic (CPU tensors + gloo, or CUDA tensors + nccl).
 """
@@ -211,6 +213,83 @@ def pcg_loop(ops, comm, plan, b_local, x0_local, n_iterations, apply_m):
         d_ext[:n] = beta * d_ext[:n] + z
         hist.append(red[1:2].clone())
     return x, torch.cat(hist)
+
+
+def _stops(delta, tol):
+    """the stopping rule of cgamd_dist_iterate_until on the all-reduced r.r (a 1-element tensor): !(sqrt|delta| >= tol), in double;
+    NaN stops"""
+    v = complex(delta.reshape(-1)[0].item())
+    return not (np.sqrt(np.abs(v)) >= tol)
+
+
+def cg_loop_until(ops, comm, plan, b_local, x0_local, tol, maxit):
+    """`cg_loop` solved to a tolerance (host mirror of cgamd_dist_iterate_until): the same recurrence, line for line, left in the
+    first iteration k >= 1 whose all-reduced r_k . r_k fails sqrt|r.r| >= tol (NaN fails it), after at most `maxit` iterations.
+    The decision is taken from the all-reduced value, which every rank holds alike, so the ranks leave together.
+    Returns (x_local, history[its + 1], its): the iterate and the history of exactly `its` iterations of `cg_loop`."""
+    import torch
+    n = plan.n_local
+    x = x0_local.clone()
+    d_ext = torch.zeros(n + plan.n_halo, dtype=b_local.dtype, device=b_local.device)
+    d_ext[:n] = x
+    comm.exchange(d_ext)
+    r = b_local - ops.spmv(d_ext)                                   # clcg.c:255-260
+    d_ext[:n] = r                                                   # :264
+    delta_new = comm.allreduce(ops.dot(r, r).reshape(1).clone())    # :268-279 + all-reduce
+    hist = [delta_new.clone()]
+    its = 0
+    for _ in range(maxit):                                          # :297
+        comm.exchange(d_ext)                                        # boundary exchange of d
+        q = ops.spmv(d_ext)                                         # :299-305
+        dq = comm.allreduce(ops.dot(d_ext[:n], q).reshape(1).clone())   # :309-324 + all-reduce
+        alpha = delta_new / dq                                      # :326-327
+        x = x + alpha * d_ext[:n]                                   # :338-342
+        r = r - alpha * q                                           # :345-349
+        delta_old = delta_new
+        delta_new = comm.allreduce(ops.dot(r, r).reshape(1).clone())    # :369-387 + all-reduce
+        beta = delta_new / delta_old                                # :389-391
+        d_ext[:n] = beta * d_ext[:n] + r                            # :415
+        hist.append(delta_new.clone())
+        its += 1
+        if _stops(delta_new, tol):
+            break
+    return x, torch.cat(hist), its
+
+
+def pcg_loop_until(ops, comm, plan, b_local, x0_local, tol, maxit, apply_m):
+    """`pcg_loop` solved to a tolerance, by the rule of `cg_loop_until`: the test looks at r.r (what the history records), not at
+    rho.  Returns (x_local, history[its + 1], its)."""
+    import torch
+    n = plan.n_local
+    x = x0_local.clone()
+    d_ext = torch.zeros(n + plan.n_halo, dtype=b_local.dtype, device=b_local.device)
+    d_ext[:n] = x
+    comm.exchange(d_ext)
+    r = b_local - ops.spmv(d_ext)
+    z = apply_m(r)
+    d_ext[:n] = z                                                   # d = z0
+    red = comm.allreduce(torch.stack([ops.dot(r, z), ops.dot(r, r)]).clone())      # the one round: {r.z, r.r}
+    rho = red[0:1].clone()
+    hist = [red[1:2].clone()]
+    its = 0
+    for _ in range(maxit):
+        comm.exchange(d_ext)
+        q = ops.spmv(d_ext)
+        dq = comm.allreduce(ops.dot(d_ext[:n], q).reshape(1).clone())
+        alpha = rho / dq
+        x = x + alpha * d_ext[:n]
+        r = r - alpha * q
+        z = apply_m(r)
+        rho_old = rho
+        red = comm.allreduce(torch.stack([ops.dot(r, z), ops.dot(r, r)]).clone())
+        rho = red[0:1].clone()
+        beta = rho / rho_old
+        d_ext[:n] = beta * d_ext[:n] + z
+        hist.append(red[1:2].clone())
+        its += 1
+        if _stops(red[1:2], tol):
+            break
+    return x, torch.cat(hist), its
 
 
 def cg_loop_single_reduction(ops, comm, plan, b_local, x0_local, n_iterations):
@@ -462,6 +541,63 @@ class DistSolver:
     def iterate(self, n):
         check(self._lib.cgamd_dist_iterate(self.handle, int(n)))
         self.iterations += int(n)
+
+    @staticmethod
+    def _until_args(tol, maxit, check_every):
+        """ValueError before the library is touched"""
+        for name, v in (("maxit", maxit), ("check_every", check_every)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"iterate_until: {name} must be an integer, got {v!r}")
+            if v < 0:
+                raise ValueError(f"iterate_until: {name} must be >= 0, got {v}")
+        try:
+            tol = float(tol)
+        except (TypeError, ValueError):
+            raise ValueError(f"iterate_until: tol must be a positive number, got {tol!r}") from None
+        if not tol > 0.0:       # (NaN included)
+            raise ValueError(f"iterate_until: tol must be > 0, got {tol}")
+        return tol, int(maxit), int(check_every)
+
+    def iterate_until(self, tol, maxit, check_every=8, group=None):
+        """Up to `maxit` more iterations, stopped ON THE DEVICE in the first one whose global sqrt|r.r| fails >= tol
+        (cgamd_dist_iterate_until, include/cgamd.h): x() is then the iterate of exactly that iteration and history() ends with it.
+        Returns the iterations since set_rhs -- after a stop, the stopping iteration.  The call synchronises once per `check_every`
+        iterations (0 = 8), never per iteration.  Collective over `group`: every rank makes the same call; the (status, iterations)
+        pairs are all-gathered and CgAmdError names the first rank that failed or disagrees.  A stopped solver stays stopped until
+        set_rhs: iterate raises, a further iterate_until returns the same count."""
+        tol, maxit, check_every = self._until_args(tol, maxit, check_every)
+        lib = self._lib
+        its = ctypes.c_int(-1)
+        status = lib.cgamd_dist_iterate_until(self.handle, maxit, tol, check_every, ctypes.byref(its))
+        mine = (int(status), int(its.value), lib.cgamd_last_error().decode(errors="replace") if status else "")
+        if self.plan.world > 1:
+            import torch.distributed as dist
+            everyone = [None] * self.plan.world
+            dist.all_gather_object(everyone, mine, group=group)
+        else:
+            everyone = [mine]
+        for r, (code, _, text) in enumerate(everyone):
+            if code != 0:
+                raise _lib.CgAmdError(code, f"iterate_until failed on rank {r}: {text}")
+        for r, (_, k, _) in enumerate(everyone):
+            if k != everyone[0][1]:
+                raise _lib.CgAmdError(_lib.ERR_STATE, f"iterate_until: rank {r} is at iteration {k}, rank 0 at {everyone[0][1]}")
+        self.iterations = int(its.value)
+        return self.iterations
+
+    def solve_until(self, b_local, x0_local=None, tol=1e-5, maxit=1000, check_every=8, group=None):
+        """set_rhs, then iterate_until: solve to sqrt|r.r| < tol in at most `maxit` iterations.  Returns the iterations run."""
+        tol, maxit, check_every = self._until_args(tol, maxit, check_every)
+        self.set_rhs(b_local, x0_local)
+        return self.iterate_until(tol, maxit, check_every, group=group)
+
+    @property
+    def iterations_done(self):
+        """iterations since set_rhs as the library counts them; after a stop, the stopping iteration"""
+        got = int(self._lib.cgamd_dist_iterations_done(self.handle))
+        if got < 0:
+            check(-got)
+        return got
 
     def synchronize(self):
         check(self._lib.cgamd_dist_synchronize(self.handle))

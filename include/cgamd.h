@@ -503,7 +503,37 @@ int cgamd_dist_create(cgamd_ctx *ctx, const void *id128, int rank, int nranks, i
                       int flags, cgamd_dist **out);
 int cgamd_dist_destroy(cgamd_dist *d);
 int cgamd_dist_set_rhs(cgamd_dist *d, const void *b_local, const void *x0_local);   /* device pointers */
+/* nIterations more iterations, asynchronous.  CGAMD_ERR_STATE without a cgamd_dist_set_rhs, and on a handle that
+ * cgamd_dist_iterate_until has stopped (it stays stopped until the next cgamd_dist_set_rhs). */
 int cgamd_dist_iterate(cgamd_dist *d, int nIterations);
+/* Tolerance stop on the device for the row-partitioned handle: the single-right-hand-side case of cgamd_solver_iterate_until (the
+ * reference's `tol` loop, p_h-PY_C-CL.py:1338-1369; PCG: helmFE_var.py:580-584).  COLLECTIVE IN MEANING: every rank makes the same
+ * call with the same arguments.  The handle stops in the first iteration k >= 1 of such a call for which
+ * !(sqrt|delta_k| >= tol), delta_k being the GLOBALLY reduced unconjugated r_k . r_k, exactly the value the history records -- with
+ * a preconditioner still r.r, not rho; NaN stops; the test is evaluated in double.  The reduced value is bit-identical on every rank
+ * (rank-ordered sums of the peer-to-peer rounds, one result of an RCCL all-reduce), so all ranks stop in the same iteration without a
+ * further exchange.  After a stop cgamd_dist_get_x returns the local rows of the iterate of exactly the stopping iteration -- the bits
+ * of set_rhs; iterate(its) on this handle's launched loop -- *iterations_run and cgamd_dist_iterations_done are its, and
+ * cgamd_dist_history returns rows 0..its, bit-identical to a fixed-count run.  Without a stop *iterations_run is the handle's count
+ * (iterations since cgamd_dist_set_rhs).  maxIterations == 0 returns the count at once.
+ * The call synchronises, but never per iteration: it enqueues chunks of checkEvery iterations (0 = 8), copies one device word -- still
+ * active: 1 / 0 -- asynchronously to pinned memory after each, and waits for the word of chunk c - 1 once chunk c is enqueued.
+ * Iterations enqueued after the stop change nothing, so the result does not depend on checkEvery.  COMMUNICATION NEVER DEPENDS ON
+ * THE STOP: after it every enqueued iteration still runs its halo push and wait, every all-reduce round (RCCL or mailbox slots) and
+ * every epoch bump on every rank; only the writes of x, r, d, the scalars, the history and the counter are guarded, so no rank waits
+ * for one that left early.  The call may follow cgamd_dist_iterate calls (their iterations are not examined again) and may be
+ * repeated: until(a); until(b) leaves the bits of until(a + b).  A stopped handle stays stopped until the next cgamd_dist_set_rhs:
+ * cgamd_dist_iterate returns CGAMD_ERR_STATE, a further cgamd_dist_iterate_until returns its at once, whatever the new tolerance.
+ * Served: the RCCL loop and both peer-to-peer loops (four-launch and CGAMD_DIST_P2P_STAGED), with or without a preconditioner,
+ * CGAMD_DIST_NO_OVERLAP, CGAMD_DIST_GRAPH (the guarded iterations run as plain launches).  A CGAMD_DIST_RESIDENT handle runs its
+ * LAUNCHED loop in this call, as it does while a preconditioner is set; the slab loop has no stop, and its iterates are not the
+ * launched loop's bit for bit, so "the bits of set_rhs; iterate(its)" there means iterate calls the launched loop serves.
+ * CGAMD_ERR_INVALID: NULL d or iterations_run, tol not > 0 (NaN included), negative maxIterations or checkEvery.  CGAMD_ERR_STATE,
+ * the handle untouched: no cgamd_dist_set_rhs; a CGAMD_DIST_SINGLE_REDUCTION handle (that loop runs another recurrence and a tail
+ * launch per call; it has no guarded form).  A failed launch or a peer-to-peer time-out (cgamd_dist_p2p_error; CGAMD_ERR_COMM) ends
+ * the call with that error, and the handle demands a fresh cgamd_dist_set_rhs. */
+int cgamd_dist_iterate_until(cgamd_dist *d, int maxIterations, double tol, int checkEvery, int *iterations_run);
+int cgamd_dist_iterations_done(cgamd_dist *d);   /* iterations since set_rhs; after a stop: the stopping iteration; negative: error */
 int cgamd_dist_get_x(cgamd_dist *d, void *x_local);                                  /* device pointer */
 int cgamd_dist_history(cgamd_dist *d, void *history, int max_entries);
 int cgamd_dist_synchronize(cgamd_dist *d);
