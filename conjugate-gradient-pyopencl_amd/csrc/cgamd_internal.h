@@ -251,6 +251,34 @@ struct CgStop {
     int *live = nullptr;            // int[nrhs]: 0 once the alpha step of a later iteration has seen stop[r]: the exit condition of
                                     // the beta launch, which must not read the word it writes
 };
+// Host side of the stop (stop_run.cpp), one per handle: the record, the pinned words the host reads while the device runs on, and
+// the driver of a call.  A call is alloc, arm, chunks, read, then the owner's stream synchronise; the owner clears `armed` in set_rhs.
+// (Hidden: the libraries export what they exported before these functions were shared.)
+#pragma GCC visibility push(hidden)
+struct StopRun {
+    void *rec = nullptr;            // the device record: [nactive, pad x3] [tol: nr doubles] [stop: nr ints] [live: nr ints]
+    CgStop view;                    // pointers into it: what the guarded launchers take
+    int nr = 0;
+    int *pin = nullptr;             // pinned: [0..1] the active counts of the chunks in flight, [2] free for a word the owner reads
+                                    // back with stop[], then `stopped` and the image the record is armed from
+    int *stopped = nullptr;         // int[nr] in the pinned block: stop[] as the last call read it, 0 again once armed anew
+    hipEvent_t ev[2] = {nullptr, nullptr};      // behind the two active counts
+    bool armed = false;
+    int enqueued = 0;               // what the last stop_run_chunks left: iterations it put into the stream (also when it failed),
+    bool active = true;             // and false once it has seen an active count of 0
+};
+// the record for nr right-hand sides, the pinned block and the events, whatever of them the handle does not have yet
+int stop_run_alloc(StopRun &sr, int nr);
+// arms the record once per set_rhs (everything active, nothing stopped); later calls only bring their tolerances.  nTol: 1 or nr
+int stop_run_arm(StopRun &sr, const double *tol, int nTol, hipStream_t st);
+// Chunks of `chunk` iterations, at most maxIterations in all: enqueue(len) puts len guarded iterations into the stream; after each
+// chunk the active count is read back asynchronously, and the host waits for the count of chunk c - 1 only once chunk c is in the
+// stream, so the device never idles on the host.  Leaves sr.enqueued and sr.active
+int stop_run_chunks(StopRun &sr, int maxIterations, int chunk, hipStream_t st, const std::function<int(int)> &enqueue);
+// stop[] into sr.stopped, asynchronously: valid after the owner's stream synchronise
+int stop_run_read(StopRun &sr, hipStream_t st);
+void stop_run_free(StopRun &sr);
+#pragma GCC visibility pop
 // ten-vector-pass iteration (x update deferred into the aypx launch): see vector.hip
 int launch_axpy_dot(int dtype, int n, const void *q, void *r, long long ld, const void *alpha, int nrhs, void *partials, int grid,
                     hipStream_t st, int vec_nt = 3, const CgStop *stop = nullptr);

@@ -154,14 +154,10 @@ struct cgamd_dist {
     void *mdiag = nullptr, *tri_coef = nullptr, *part_pcg = nullptr, *rho2 = nullptr;
     int *tri_plan = nullptr;
     TriLaunch tri;
-    // cgamd_dist_iterate_until: the device record of the stop (CgStop with one right-hand side: allocated at the first call, armed once
-    // per set_rhs), the pinned words in flight ([0], [1]: the active word after chunks of either parity, [2]: stop[0]; the record's
-    // image behind them) and the events behind the words.  until_stopped: the handle is frozen until the next set_rhs
-    void *stop_rec = nullptr;
-    CgStop stop;
-    int *until_pin = nullptr;
-    hipEvent_t until_ev[2] = {nullptr, nullptr};
-    bool stop_armed = false, until_stopped = false;
+    // cgamd_dist_iterate_until: the stop (StopRun with one right-hand side: allocated at the first call, armed once per set_rhs).
+    // until_stopped: the handle is frozen until the next set_rhs
+    StopRun stop;
+    bool until_stopped = false;
 };
 
 static int dalloc(void **p, size_t bytes, const char *what) {
@@ -288,8 +284,14 @@ static int pcg_reduce2(cgamd_dist *d, int mode, hipStream_t st, const CgStop *g 
     return launch_pcg_scalars(d->dtype, mode, d->red, d->sc, d->rho2, st, g);
 }
 
-static int enqueue_iteration(cgamd_dist *d, hipStream_t st) {
-    if (d->cg1) return enqueue_iteration_cg1(d, st);
+// One iteration of the handle's launched loop and preconditioner.  g (cgamd_dist_iterate_until): the same launches with the guarded
+// instantiation of every kernel that writes x, r, the local part of d_ext, a scalar, the history or the counter (stop_device.h, one
+// right-hand side).  COMMUNICATION NEVER DEPENDS ON THE STOP: g reaches kernels only -- the halo push and wait (inside the SpMV
+// launch, or the exchange launches / RCCL calls), every all-reduce round, every epoch bump and the overlap's fork / join run after
+// the stop exactly as before it -- with d frozen the peers receive the same halo values and the sums repeat -- so no rank waits for
+// one that left early, because none does.  The SpMV is the unguarded one: q of a frozen handle is recomputed and read by nothing.
+static int enqueue_iteration(cgamd_dist *d, hipStream_t st, const CgStop *g = nullptr) {
+    if (d->cg1) return enqueue_iteration_cg1(d, st);        // (no guarded form: cgamd_dist_iterate_until refuses such a handle)
     const int dt = d->dtype, n = d->n_local;
     const long long ldx = (long long)d->n_local + d->n_halo;
     int rc;
@@ -298,15 +300,15 @@ static int enqueue_iteration(cgamd_dist *d, hipStream_t st) {
         if ((rc = launch_spmv_p2p(dt, d->plan, n, d->nnz, d->vals, d->ptr, d->cols, d->d_ext, d->q, d->part_dq, d->halo_flag,
                                   d->rotate, d->xch, st))) return rc;
         if ((rc = launch_p2p_allreduce(dt, 2, d->part_dq, d->plan.n_partials, d->mailbox_dev, d->rank, d->nranks, 0, d->epochs + 1,
-                                       d->sc, st, d->epochs, d->epochs + 2))) return rc;
+                                       d->sc, st, d->epochs, d->epochs + 2, g))) return rc;
         if (d->pre_kind) {      // [r -= alpha q, z = M^-1 r, r.z, r.r], [all-reduce of both, beta, x += alpha d, d = z + beta d]
-            if ((rc = pcg_sweep(d, true, d->q, st))) return rc;
+            if ((rc = pcg_sweep(d, true, d->q, st, g))) return rc;
             return launch_pcg_aypx_beta_p2p(dt, n, d->q, d->d_ext, d->x, d->part_pcg, pcg_prr(d), d->pcg_P, d->mailbox_dev, d->rank, d->nranks,
-                                            d->epochs + 2, d->sc, d->rho2, st, d->plan.vec_nt);
+                                            d->epochs + 2, d->sc, d->rho2, st, d->plan.vec_nt, g);
         }
-        if ((rc = launch_axpy_dot(dt, n, d->q, d->r, n, d->sc.alpha, 1, d->part_rr, d->vgrid, st, d->plan.vec_nt))) return rc;
+        if ((rc = launch_axpy_dot(dt, n, d->q, d->r, n, d->sc.alpha, 1, d->part_rr, d->vgrid, st, d->plan.vec_nt, g))) return rc;
         return launch_aypx_beta_p2p(dt, n, d->r, d->d_ext, d->x, d->part_rr, d->vgrid, d->mailbox_dev, d->rank, d->nranks, 1,
-                                    d->epochs + 2, d->sc, st, d->plan.vec_nt);
+                                    d->epochs + 2, d->sc, st, d->plan.vec_nt, g);
     }
     if (d->overlap) {
         // fork: the exchange runs on the comm stream while the row blocks that reference no halo column are
@@ -325,63 +327,13 @@ static int enqueue_iteration(cgamd_dist *d, hipStream_t st) {
         if ((rc = exchange(d, d->d_ext, st))) return rc;
         if ((rc = launch_spmv(dt, d->plan, n, d->nnz, d->vals, d->ptr, d->cols, d->d_ext, ldx, d->q, n, 1, d->d_ext, d->part_dq, st))) return rc;
     }
-    if ((rc = reduce_all(d, d->part_dq, d->plan.n_partials, 0, 2, st))) return rc;
-    if (d->pre_kind) {
-        if ((rc = pcg_sweep(d, true, d->q, st))) return rc;
-        if ((rc = pcg_reduce2(d, 3, st))) return rc;
-        return launch_pcg_xd_update(dt, n, d->q, d->d_ext, d->x, d->sc, st);
-    }
-    if ((rc = launch_axpy2_dot(dt, n, d->d_ext, d->x, d->q, d->r, n, d->sc.alpha, 1, d->part_rr, d->vgrid, st, d->plan.vec_nt))) return rc;
-    if ((rc = reduce_all(d, d->part_rr, d->vgrid, 1, 3, st))) return rc;
-    return launch_aypx(dt, n, d->r, d->d_ext, n, d->sc.beta, 1, st);
-}
-
-// One iteration of cgamd_dist_iterate_until: enqueue_iteration's launch sequence for the handle's loop and preconditioner, launch for
-// launch, with the guarded instantiation of every kernel that writes x, r, the local part of d_ext, a scalar, the history or the
-// counter (stop_device.h, one right-hand side).  COMMUNICATION NEVER DEPENDS ON THE STOP: the halo push and wait (inside the SpMV
-// launch, or the exchange launches / RCCL calls), every all-reduce round, every epoch bump and the overlap's fork / join run after
-// the stop exactly as before it -- with d frozen the peers receive the same halo values and the sums repeat -- so no rank waits for
-// one that left early, because none does.  The SpMV is the unguarded one: q of a frozen handle is recomputed and read by nothing.
-static int enqueue_iteration_until(cgamd_dist *d, hipStream_t st) {
-    const int dt = d->dtype, n = d->n_local;
-    const long long ldx = (long long)d->n_local + d->n_halo;
-    const CgStop *g = &d->stop;
-    int rc;
-    if (d->direct && d->p2p_attached) {
-        if ((rc = launch_spmv_p2p(dt, d->plan, n, d->nnz, d->vals, d->ptr, d->cols, d->d_ext, d->q, d->part_dq, d->halo_flag,
-                                  d->rotate, d->xch, st))) return rc;
-        if ((rc = launch_p2p_allreduce(dt, 2, d->part_dq, d->plan.n_partials, d->mailbox_dev, d->rank, d->nranks, 0, d->epochs + 1,
-                                       d->sc, st, d->epochs, d->epochs + 2, g))) return rc;
-        if (d->pre_kind) {
-            if ((rc = pcg_sweep(d, true, d->q, st, g))) return rc;
-            return launch_pcg_aypx_beta_p2p(dt, n, d->q, d->d_ext, d->x, d->part_pcg, pcg_prr(d), d->pcg_P, d->mailbox_dev, d->rank, d->nranks,
-                                            d->epochs + 2, d->sc, d->rho2, st, d->plan.vec_nt, g);
-        }
-        if ((rc = launch_axpy_dot(dt, n, d->q, d->r, n, d->sc.alpha, 1, d->part_rr, d->vgrid, st, d->plan.vec_nt, g))) return rc;
-        return launch_aypx_beta_p2p(dt, n, d->r, d->d_ext, d->x, d->part_rr, d->vgrid, d->mailbox_dev, d->rank, d->nranks, 1,
-                                    d->epochs + 2, d->sc, st, d->plan.vec_nt, g);
-    }
-    if (d->overlap) {       // (the fork / join of enqueue_iteration, unchanged)
-        CG_HIP(hipEventRecord(d->ev_fork, st));
-        CG_HIP(hipStreamWaitEvent(d->comm_stream, d->ev_fork, 0));
-        if ((rc = exchange(d, d->d_ext, d->comm_stream))) return rc;
-        CG_HIP(hipEventRecord(d->ev_join, d->comm_stream));
-        if ((rc = launch_spmv(dt, d->plan, n, d->nnz, d->vals, d->ptr, d->cols, d->d_ext, ldx, d->q, n, 1, d->d_ext, d->part_dq, st,
-                              d->interior_list, d->n_interior))) return rc;
-        CG_HIP(hipStreamWaitEvent(st, d->ev_join, 0));
-        if ((rc = launch_spmv(dt, d->plan, n, d->nnz, d->vals, d->ptr, d->cols, d->d_ext, ldx, d->q, n, 1, d->d_ext, d->part_dq, st,
-                              d->boundary_list, d->n_boundary))) return rc;
-    } else {
-        if ((rc = exchange(d, d->d_ext, st))) return rc;
-        if ((rc = launch_spmv(dt, d->plan, n, d->nnz, d->vals, d->ptr, d->cols, d->d_ext, ldx, d->q, n, 1, d->d_ext, d->part_dq, st))) return rc;
-    }
     if ((rc = reduce_all(d, d->part_dq, d->plan.n_partials, 0, 2, st, g))) return rc;
-    if (d->pre_kind) {      // (x += alpha d rides in the last launch, which leaves on live[]: the stopping iteration still gets it)
+    if (d->pre_kind) {      // (guarded: x += alpha d rides in the last launch, which leaves on live[]: the stopping iteration still gets it)
         if ((rc = pcg_sweep(d, true, d->q, st, g))) return rc;
         if ((rc = pcg_reduce2(d, 3, st, g))) return rc;
         return launch_pcg_xd_update(dt, n, d->q, d->d_ext, d->x, d->sc, st, g);
     }
-    // (x is updated BEFORE the deciding launch here: the stopping iteration's x is in place when stop[] is written)
+    // (guarded: x is updated BEFORE the deciding launch here, so the stopping iteration's x is in place when stop[] is written)
     if ((rc = launch_axpy2_dot(dt, n, d->d_ext, d->x, d->q, d->r, n, d->sc.alpha, 1, d->part_rr, d->vgrid, st, d->plan.vec_nt, g))) return rc;
     if ((rc = reduce_all(d, d->part_rr, d->vgrid, 1, 3, st, g))) return rc;
     return launch_aypx(dt, n, d->r, d->d_ext, n, d->sc.beta, 1, st, g);
@@ -627,10 +579,7 @@ int cgamd_dist_destroy(cgamd_dist *d) {
     if (d->comm_stream) { (void)hipStreamSynchronize(d->comm_stream); (void)hipStreamDestroy(d->comm_stream); }
     if (d->ev_fork) (void)hipEventDestroy(d->ev_fork);
     if (d->ev_join) (void)hipEventDestroy(d->ev_join);
-    for (hipEvent_t e : d->until_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (d->until_pin) (void)hipHostFree(d->until_pin);
-    if (d->stop_rec) (void)hipFree(d->stop_rec);
+    stop_run_free(d->stop);
     if (d->interior_list) (void)hipFree(d->interior_list);
     if (d->boundary_list) (void)hipFree(d->boundary_list);
     if (d->halo_flag) (void)hipFree(d->halo_flag);
@@ -678,7 +627,7 @@ int cgamd_dist_set_rhs(cgamd_dist *d, const void *b_local, const void *x0_local)
     }
     d->rhs_set = true;
     d->iters = 0;
-    d->stop_armed = d->until_stopped = false;
+    d->stop.armed = d->until_stopped = false;
     return CGAMD_OK;
 }
 
@@ -737,7 +686,7 @@ int cgamd_dist_iterate(cgamd_dist *d, int nIterations) {
 // of cgamd_solver_iterate_until, decided from the GLOBALLY reduced r.r -- bit-identical on every rank, so all ranks stop in the same
 // iteration without a further exchange, and every rank enqueues the same chunks because each waits for the word of a specific chunk
 // at a specific point of its enqueue sequence.  Iterations enqueued after the stop keep the whole protocol running and change
-// nothing (enqueue_iteration_until), so the result does not depend on checkEvery, and until(a); until(b) leaves the bits of
+// nothing (enqueue_iteration with the record), so the result does not depend on checkEvery, and until(a); until(b) leaves the bits of
 // until(a + b).
 int cgamd_dist_iterate_until(cgamd_dist *d, int maxIterations, double tol, int checkEvery, int *iterations_run) {
     if (maxIterations < 0 || checkEvery < 0) return fail(CGAMD_ERR_INVALID, "dist_iterate_until: negative maxIterations or checkEvery");
@@ -755,65 +704,31 @@ int cgamd_dist_iterate_until(cgamd_dist *d, int maxIterations, double tol, int c
     }
     CG_HIP(hipSetDevice(d->ctx->device));
     hipStream_t st = d->ctx->stream;
-    // the record: [nactive, pad x3] [tol] [stop, live]; pinned: 8 ints of words in flight, then the record's image
-    constexpr size_t rec_bytes = 32, pin_ints = 8;
-    if (!d->stop_rec) {
-        if (int rc = dalloc(&d->stop_rec, rec_bytes, "stop record")) return rc;
-        char *base = static_cast<char *>(d->stop_rec);
-        d->stop.nactive = reinterpret_cast<int *>(base);
-        d->stop.tol = reinterpret_cast<const double *>(base + 16);
-        d->stop.stop = reinterpret_cast<int *>(base + 24);
-        d->stop.live = d->stop.stop + 1;
-    }
-    if (!d->until_pin) CG_HIP(hipHostMalloc((void **)&d->until_pin, pin_ints * 4 + rec_bytes, hipHostMallocDefault));
-    for (hipEvent_t &e : d->until_ev)
-        if (!e) CG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (int rc = stop_run_alloc(d->stop, 1)) return rc;
     if (int rc = ensure_history(d, d->iters + maxIterations + 1)) return rc;
-    {                           // arm once per set_rhs; the tolerance of this call
-        char *img = reinterpret_cast<char *>(d->until_pin + pin_ints);
-        *reinterpret_cast<double *>(img + 16) = tol;
-        if (!d->stop_armed) {
-            int *hd = reinterpret_cast<int *>(img), *sp = reinterpret_cast<int *>(img + 24);
-            hd[0] = 1; hd[1] = hd[2] = hd[3] = 0;
-            sp[0] = 0; sp[1] = 1;
-            CG_HIP(hipMemcpyAsync(d->stop_rec, img, rec_bytes, hipMemcpyHostToDevice, st));
-            d->stop_armed = true;
-        } else {
-            CG_HIP(hipMemcpyAsync(static_cast<char *>(d->stop_rec) + 16, img + 16, 8, hipMemcpyHostToDevice, st));
-        }
-    }
-    const int chunk = checkEvery ? checkEvery : 8;
-    volatile int *active = d->until_pin;
-    int rc = CGAMD_OK, enq = 0;
-    bool none_left = false;
-    for (int c = 0; enq < maxIterations && !none_left && !rc; ++c) {
-        const int len = std::min(chunk, maxIterations - enq);
-        for (int i = 0; i < len && !rc; ++i) rc = enqueue_iteration_until(d, st);
-        if (rc) break;
-        enq += len;
-        CG_HIP(hipMemcpyAsync(d->until_pin + (c & 1), d->stop.nactive, sizeof(int), hipMemcpyDeviceToHost, st));
-        CG_HIP(hipEventRecord(d->until_ev[c & 1], st));
-        if (c > 0) {            // chunk c is in the stream: now the word chunk c - 1 left
-            CG_HIP(hipEventSynchronize(d->until_ev[(c - 1) & 1]));
-            none_left = active[(c - 1) & 1] == 0;
-        }
-    }
-    if (rc) {                   // part of an iteration may be in the stream: the handle demands a fresh set_rhs
-        const std::string why = cgamd_last_error();
+    if (int rc = stop_run_arm(d->stop, &tol, 1, st)) return rc;
+    // (plain launches, every rank the same chunks: each waits for the word of a specific chunk at a specific point of its sequence)
+    auto enqueue = [&](int len) -> int {
+        for (int i = 0; i < len; ++i)
+            if (int rc = enqueue_iteration(d, st, &d->stop.view)) return rc;
+        return CGAMD_OK;
+    };
+    if (int rc = stop_run_chunks(d->stop, maxIterations, checkEvery ? checkEvery : 8, st, enqueue)) {
+        const std::string why = cgamd_last_error();     // part of an iteration may be in the stream: the handle demands a fresh set_rhs
         (void)hipStreamSynchronize(st);
         d->rhs_set = false;
         return fail(rc, why);
     }
-    CG_HIP(hipMemcpyAsync(d->until_pin + 2, d->stop.stop, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (int rc = stop_run_read(d->stop, st)) return rc;
     hipError_t e = hipStreamSynchronize(st);
     if (e != hipSuccess) { d->rhs_set = false; return fail(CGAMD_ERR_HIP, std::string("dist_iterate_until: ") + hipGetErrorString(e)); }
     if (const int perr = cgamd_dist_p2p_error(d)) {
         d->rhs_set = false;
         return fail(CGAMD_ERR_COMM, "dist_iterate_until: a bounded spin of the peer-to-peer protocol timed out (error word " + std::to_string(perr) + ")");
     }
-    const int stopped_at = d->until_pin[2];
+    const int stopped_at = d->stop.stopped[0];
     if (stopped_at) { d->iters = stopped_at; d->until_stopped = true; }
-    else d->iters += enq;
+    else d->iters += d->stop.enqueued;
     *iterations_run = d->iters;
     return CGAMD_OK;
 }

@@ -110,16 +110,12 @@ struct cgamd_solver {
     // cgamd_solver_iterate_tol: tolerance of the device-side stop for the call in progress (0 = none), and what it reported
     double tol_req = 0.;
     bool tol_served = false, tol_stopped = false;
-    // cgamd_solver_iterate_until: the device record of the per-right-hand-side stop (CgStop: allocated at the first call, armed once
-    // per set_rhs), its pinned host mirror, and the captured chunk of guarded iterations.  until_mode: since the first call after
-    // set_rhs the handle runs its three / four-launch loop only (d in one buffer, updated at the end of every iteration);
-    // until_stopped: a right-hand side has stopped, so the columns are at different iterations and only iterate_until goes on.
-    void *stop_rec = nullptr;
-    CgStop stop;
-    bool stop_armed = false, until_mode = false, until_stopped = false;
-    std::vector<int> stop_host;     // stop[] as the last call read it
-    int *until_pin = nullptr;       // pinned: [0..1] the active counts of the chunks in flight, [2] *iter, [3..] stop[], then the record image
-    hipEvent_t until_ev[2] = {nullptr, nullptr};
+    // cgamd_solver_iterate_until: the per-right-hand-side stop (StopRun: allocated at the first call, armed once per set_rhs) and the
+    // captured chunk of guarded iterations.  until_mode: since the first call after set_rhs the handle runs its three / four-launch
+    // loop only (d in one buffer, updated at the end of every iteration); until_stopped: a right-hand side has stopped, so the columns
+    // are at different iterations and only iterate_until goes on.
+    StopRun stop;
+    bool until_mode = false, until_stopped = false;
     hipGraphExec_t gT = nullptr;
     hipGraph_t gTg = nullptr;
     int gT_len = 0;
@@ -200,10 +196,16 @@ static int enqueue_spmv(cgamd_solver *s, int k, hipStream_t st, void *dvec = nul
 
 // r -= alpha q (update) and z = M^-1 r of a tridiagonal M, by the kernel of its form: the scan sweep of rows i +- 1 (precond.hip) or
 // one thread per segment of rows i +- stride (precond_strided.hip)
-static int enqueue_tri_sweep(cgamd_solver *s, bool update, const void *q, void *z, void *prz, void *prr, hipStream_t st) {
+struct TriPartials { void *rz, *rr; };
+// the r.z and r.r partials of the sweeps: the two halves of s->tri_part, [nrhs][grid] each
+static TriPartials tri_partials(const cgamd_solver *s) {
+    return {s->tri_part, static_cast<char *>(s->tri_part) + acc_size(s->dtype) * (size_t)s->tri.grid * s->nrhs};
+}
+static int enqueue_tri_sweep(cgamd_solver *s, bool update, const void *q, void *z, hipStream_t st, const CgStop *g = nullptr) {
     const void *alpha = update ? s->sc.alpha : nullptr;
-    if (s->tri.stride > 1) return launch_pcg_tri_strided(s->dtype, s->tri, update, q, s->r, z, s->n, alpha, s->nrhs, prz, prr, st);
-    return launch_pcg_tri(s->dtype, s->tri, update, q, s->r, z, s->n, alpha, s->nrhs, prz, prr, st);
+    const TriPartials p = tri_partials(s);
+    if (s->tri.stride > 1) return launch_pcg_tri_strided(s->dtype, s->tri, update, q, s->r, z, s->n, alpha, s->nrhs, p.rz, p.rr, st, g);
+    return launch_pcg_tri(s->dtype, s->tri, update, q, s->r, z, s->n, alpha, s->nrhs, p.rz, p.rr, st, g);
 }
 
 // Deferred x update: the lag the captured U-iteration graphs of this handle run with NOW (1 = none).  s->x_lag is what creation
@@ -237,9 +239,15 @@ static int enqueue_lag_iteration(cgamd_solver *s, int k, int lag, int j, hipStre
 }
 
 // lag >= 2 (capture of a U-iteration graph only): this is iteration k % lag of a group of the deferred x update
-static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st, int lag = 1) {
+// g (cgamd_solver_iterate_until): the same launches with the guarded instantiation of every kernel that writes x, r, d, a scalar, the
+// history or the counter (stop_device.h).  The SpMV is the unguarded one: q of a frozen right-hand side is recomputed from its frozen
+// d and read by nothing.  Only the loops of a handle in until_mode have a guarded form -- the tridiagonal, the diagonal and the three /
+// four-launch one; any other loop with a stop record is an error, never a silent unguarded run.
+static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st, int lag = 1, const CgStop *g = nullptr) {
     const int dt = s->dtype, n = s->n, nr = s->nrhs;
     int rc;
+    if (g && (lag >= 2 || fused2_now(s) || s->rm || (s->flags & CGAMD_UNFUSED)))
+        return fail(CGAMD_ERR_STATE, "iterate_until: the loop this handle runs now has no guarded form");
     if (lag >= 2) return enqueue_lag_iteration(s, k, lag, k % lag, st);
     if (fused2_now(s)) {   // two launches: [beta, d = beta d + r, q = A d, d.q] and [alpha, x += alpha d, r -= alpha q, r.r]
         if ((rc = enqueue_spmv(s, k, st))) return rc;
@@ -254,28 +262,28 @@ static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st, int lag = 1
     }
     if (s->tri_on) {  // tridiagonal M (helmFE_var.py:561-562): z = M^-1 r by the line sweeps, in q's storage
         if ((rc = enqueue_spmv(s, k, st))) return rc;
-        if ((rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st))) return rc;
-        void *prz = s->tri_part, *prr = static_cast<char *>(s->tri_part) + acc_size(dt) * (size_t)s->tri.grid * nr;
-        if ((rc = enqueue_tri_sweep(s, true, s->q, s->q, prz, prr, st))) return rc;
-        return launch_pcg_aypx_beta_z(dt, n, s->d, s->q, n, prz, prr, s->tri.grid, nr, s->sc, s->rho2, s->x, st);
+        if ((rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st, g))) return rc;
+        if ((rc = enqueue_tri_sweep(s, true, s->q, s->q, st, g))) return rc;
+        const TriPartials p = tri_partials(s);
+        return launch_pcg_aypx_beta_z(dt, n, s->d, s->q, n, p.rz, p.rr, s->tri.grid, nr, s->sc, s->rho2, s->x, st, g);
     }
     if (s->mdiag) {   // preconditioned recurrence (helmFE_var.py:560-585); delta holds rho = r.z
         if ((rc = enqueue_spmv(s, k, st))) return rc;
-        if ((rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st))) return rc;
+        if ((rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st, g))) return rc;
         if ((rc = launch_pcg_axpy2_dot2(dt, false, n, s->d, s->x, s->q, s->r, s->mdiag, n, s->sc.alpha, nr, s->part_rz, s->part_rr,
-                                        s->vgrid, st, m_pitch(s)))) return rc;
-        return launch_pcg_aypx_beta(dt, n, s->r, s->d, s->mdiag, n, s->part_rz, s->part_rr, s->vgrid, nr, s->sc, s->rho2, s->x, st, m_pitch(s));
+                                        s->vgrid, st, m_pitch(s), g))) return rc;
+        return launch_pcg_aypx_beta(dt, n, s->r, s->d, s->mdiag, n, s->part_rz, s->part_rr, s->vgrid, nr, s->sc, s->rho2, s->x, st, m_pitch(s), g);
     }
     if (!(s->flags & CGAMD_UNFUSED)) {
         if ((rc = enqueue_spmv(s, k, st))) return rc;
         const bool fold = fold_alpha_ok(s->plan.n_partials, s->plan.fold_max);      // small system: alpha in the next launch's prologue
-        if (!fold && (rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st))) return rc;
+        if (!fold && (rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st, g))) return rc;
         // r -= alpha q (+ r.r) ; then beta, x += alpha d, d = beta d + r : 3 + 5 vector passes (x is read by nothing inside the loop, so
         // its update rides in the aypx launch, which reads d anyway)
-        if (fold) rc = launch_axpy_dot_alpha(dt, n, s->q, s->r, n, s->part_dq, s->plan.n_partials, s->sc, nr, s->part_rr, s->vgrid, st);
-        else rc = launch_axpy_dot(dt, n, s->q, s->r, n, s->sc.alpha, nr, s->part_rr, s->vgrid, st, s->plan.vec_nt);
+        if (fold) rc = launch_axpy_dot_alpha(dt, n, s->q, s->r, n, s->part_dq, s->plan.n_partials, s->sc, nr, s->part_rr, s->vgrid, st, g);
+        else rc = launch_axpy_dot(dt, n, s->q, s->r, n, s->sc.alpha, nr, s->part_rr, s->vgrid, st, s->plan.vec_nt, g);
         if (rc) return rc;
-        return launch_aypx_beta_x(dt, n, s->r, s->d, s->x, n, s->part_rr, s->vgrid, nr, s->sc, st, s->plan.vec_nt);
+        return launch_aypx_beta_x(dt, n, s->r, s->d, s->x, n, s->part_rr, s->vgrid, nr, s->sc, st, s->plan.vec_nt, g);
     }
     if ((rc = enqueue_spmv(s, k, st))) return rc;
     if ((rc = launch_dot_partials(dt, n, s->d, s->q, n, nr, s->part_rr, s->vgrid, st))) return rc;
@@ -285,36 +293,6 @@ static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st, int lag = 1
     if ((rc = launch_dot_partials(dt, n, s->r, s->r, n, nr, s->part_rr, s->vgrid, st))) return rc;
     if ((rc = launch_cg_beta(dt, s->part_rr, s->vgrid, nr, s->sc, st))) return rc;
     return launch_aypx(dt, n, s->r, s->d, n, s->sc.beta, nr, st);
-}
-
-// One iteration of cgamd_solver_iterate_until: the three / four-launch loop of enqueue_iteration for the handle's preconditioner, with
-// the guarded instantiation of every kernel that writes x, r, d, a scalar, the history or the counter (stop_device.h).  The SpMV is
-// the unguarded one: q of a frozen right-hand side is recomputed from its frozen d and read by nothing.
-static int enqueue_iteration_until(cgamd_solver *s, hipStream_t st) {
-    const int dt = s->dtype, n = s->n, nr = s->nrhs;
-    const CgStop *g = &s->stop;
-    int rc;
-    if ((rc = handle_spmv(s, n, s->d, n, s->q, n, s->d, s->part_dq, st))) return rc;
-    if (s->tri_on) {
-        if ((rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st, g))) return rc;
-        void *prz = s->tri_part, *prr = static_cast<char *>(s->tri_part) + acc_size(dt) * (size_t)s->tri.grid * nr;
-        if (s->tri.stride > 1) rc = launch_pcg_tri_strided(dt, s->tri, true, s->q, s->r, s->q, n, s->sc.alpha, nr, prz, prr, st, g);
-        else rc = launch_pcg_tri(dt, s->tri, true, s->q, s->r, s->q, n, s->sc.alpha, nr, prz, prr, st, g);
-        if (rc) return rc;
-        return launch_pcg_aypx_beta_z(dt, n, s->d, s->q, n, prz, prr, s->tri.grid, nr, s->sc, s->rho2, s->x, st, g);
-    }
-    if (s->mdiag) {
-        if ((rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st, g))) return rc;
-        if ((rc = launch_pcg_axpy2_dot2(dt, false, n, s->d, s->x, s->q, s->r, s->mdiag, n, s->sc.alpha, nr, s->part_rz, s->part_rr, s->vgrid, st,
-                                        m_pitch(s), g))) return rc;
-        return launch_pcg_aypx_beta(dt, n, s->r, s->d, s->mdiag, n, s->part_rz, s->part_rr, s->vgrid, nr, s->sc, s->rho2, s->x, st, m_pitch(s), g);
-    }
-    const bool fold = fold_alpha_ok(s->plan.n_partials, s->plan.fold_max);
-    if (!fold && (rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st, g))) return rc;
-    if (fold) rc = launch_axpy_dot_alpha(dt, n, s->q, s->r, n, s->part_dq, s->plan.n_partials, s->sc, nr, s->part_rr, s->vgrid, st, g);
-    else rc = launch_axpy_dot(dt, n, s->q, s->r, n, s->sc.alpha, nr, s->part_rr, s->vgrid, st, s->plan.vec_nt, g);
-    if (rc) return rc;
-    return launch_aypx_beta_x(dt, n, s->r, s->d, s->x, n, s->part_rr, s->vgrid, nr, s->sc, st, s->plan.vec_nt, g);
 }
 
 // the resident loop applies where the two-launch loop does and the matrix slices fit LDS (needs the row pointers on the host)
@@ -512,7 +490,7 @@ static int capture(cgamd_solver *s, int k0, int iters, hipGraph_t *g, hipGraphEx
     int rc = CGAMD_OK;
     // whole groups of the deferred x update, so that nothing is pending when the graph ends (k0 = 0 there: no parity)
     const int lag = (!guarded && iters == s->U && k0 == 0) ? x_lag_now(s) : 1;
-    for (int i = 0; i < iters && rc == CGAMD_OK; ++i) rc = guarded ? enqueue_iteration_until(s, st) : enqueue_iteration(s, k0 + i, st, lag);
+    for (int i = 0; i < iters && rc == CGAMD_OK; ++i) rc = enqueue_iteration(s, k0 + i, st, lag, guarded ? &s->stop.view : nullptr);
     e = hipStreamEndCapture(st, g);
     if (rc != CGAMD_OK) return rc;
     if (e != hipSuccess) return fail(CGAMD_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
@@ -860,10 +838,7 @@ int cgamd_solver_destroy(cgamd_solver *s) {
                     s->sc.history, s->sc.iter, s->mdiag, s->part_rz, s->rho2, s->tri_coef, s->tri_part, s->tri_cstart, s->tri.maps, s->sc.stage, s->sc.ticket, s->res_sync, s->resw_sync, s->dlag, s->codes, s->dict, s->rm_pace, s->vcodes, s->vdict, s->jcodes, s->jdict_off, s->jdict_val, s->rcodes, s->rdict};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
-    if (s->stop_rec) (void)hipFree(s->stop_rec);
-    if (s->until_pin) (void)hipHostFree(s->until_pin);
-    for (hipEvent_t e : s->until_ev)
-        if (e) (void)hipEventDestroy(e);
+    stop_run_free(s->stop);
     delete s;
     return CGAMD_OK;
 }
@@ -878,7 +853,7 @@ int cgamd_solver_set_rhs(cgamd_solver *s, const void *b, const void *x0, int on_
     const bool rm = s->rm_ok && !precond_set(s);      // the preconditioned recurrence keeps the RHS-major kernels
     if (rm != s->rm) destroy_graphs(s);         // captured launch sequences belong to one layout
     if (s->until_mode && s->fused2) destroy_graphs(s);      // (captured while the two-launch loop was set aside: iterate_until)
-    s->until_mode = s->until_stopped = s->stop_armed = false;
+    s->until_mode = s->until_stopped = s->stop.armed = false;
     s->rm = rm;
     int rc;
     if (rm) {
@@ -916,9 +891,9 @@ int cgamd_solver_set_rhs(cgamd_solver *s, const void *b, const void *x0, int on_
     if ((rc = handle_spmv(s, s->n, s->x, s->n, s->q, s->n, nullptr, nullptr, st))) return rc;
     if ((rc = launch_sub(s->dtype, s->n, s->b, s->q, s->r, s->n, s->nrhs, st))) return rc;
     if (s->tri_on) {  // z0 = M^-1 r0 (the line sweeps), p0 = z0, rho0 = r0.z0
-        void *prz = s->tri_part, *prr = static_cast<char *>(s->tri_part) + acc_size(s->dtype) * (size_t)s->tri.grid * s->nrhs;
-        if ((rc = enqueue_tri_sweep(s, false, nullptr, s->d, prz, prr, st))) return rc;
-        if ((rc = launch_pcg_delta0(s->dtype, prz, prr, s->tri.grid, s->nrhs, s->sc, s->rho2, st))) return rc;
+        if ((rc = enqueue_tri_sweep(s, false, nullptr, s->d, st))) return rc;
+        const TriPartials p = tri_partials(s);
+        if ((rc = launch_pcg_delta0(s->dtype, p.rz, p.rr, s->tri.grid, s->nrhs, s->sc, s->rho2, st))) return rc;
     } else if (s->mdiag) {   // z0 = M r0, p0 = z0, rho0 = r0.z0 (helmFE_var.py:562-573)
         if ((rc = launch_pcg_axpy2_dot2(s->dtype, true, s->n, s->d, s->x, s->q, s->r, s->mdiag, s->n, nullptr, s->nrhs, s->part_rz,
                                         s->part_rr, s->vgrid, st, m_pitch(s)))) return rc;
@@ -1316,25 +1291,12 @@ int cgamd_solver_iterate_until(cgamd_solver *s, int maxIterations, const double 
     if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, "iterate_until: CGAMD_UNFUSED replays the reference's kernel sequence, which has no guarded form");
     const int nr = s->nrhs;
     if (maxIterations == 0) {
-        for (int r = 0; r < nr; ++r) iterations_run[r] = (s->stop_armed && s->stop_host[r]) ? s->stop_host[r] : s->iters;
+        for (int r = 0; r < nr; ++r) iterations_run[r] = (s->stop.armed && s->stop.stopped[r]) ? s->stop.stopped[r] : s->iters;
         return CGAMD_OK;
     }
     CG_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
-    // the record: [nactive, pad x3] [tol: nr doubles] [stop: nr ints] [live: nr ints]
-    const size_t rec_bytes = 16 + (size_t)nr * 16;
-    const size_t pin_ints = 4 + (size_t)nr + (size_t)(nr & 1);     // the record image follows, 8-byte aligned
-    if (!s->stop_rec) {
-        if (int rc = dmalloc(&s->stop_rec, rec_bytes, "stop record")) return rc;
-        char *base = static_cast<char *>(s->stop_rec);
-        s->stop.nactive = reinterpret_cast<int *>(base);
-        s->stop.tol = reinterpret_cast<const double *>(base + 16);
-        s->stop.stop = reinterpret_cast<int *>(base + 16 + (size_t)nr * 8);
-        s->stop.live = s->stop.stop + nr;
-        CG_HIP(hipHostMalloc((void **)&s->until_pin, pin_ints * 4 + rec_bytes, hipHostMallocDefault));
-        for (hipEvent_t &e : s->until_ev) CG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        s->stop_host.assign((size_t)nr, 0);
-    }
+    if (int rc = stop_run_alloc(s->stop, nr)) return rc;
     if (int rc = ensure_history(s, s->iters + maxIterations + 1)) return rc;
     if (!s->until_mode) {       // from here to the next set_rhs the handle runs its three / four-launch loop
         if (fused2_now(s) && s->iters > 0) {
@@ -1347,29 +1309,11 @@ int cgamd_solver_iterate_until(cgamd_solver *s, int maxIterations, const double 
         if (s->fused2) destroy_graphs(s);       // captured per parity of the two-launch loop
         s->until_mode = true;
     }
-    {                           // arm once per set_rhs; the tolerances of this call (a stopped right-hand side stays stopped whatever they are)
-        char *img = reinterpret_cast<char *>(s->until_pin + pin_ints);
-        double *tl = reinterpret_cast<double *>(img + 16);
-        for (int r = 0; r < nr; ++r) tl[r] = tol[nTol == 1 ? 0 : r];
-        if (!s->stop_armed) {
-            int *hd = reinterpret_cast<int *>(img), *sp = reinterpret_cast<int *>(img + 16 + (size_t)nr * 8);
-            hd[0] = nr; hd[1] = hd[2] = hd[3] = 0;
-            for (int r = 0; r < nr; ++r) { sp[r] = 0; sp[nr + r] = 1; }
-            CG_HIP(hipMemcpyAsync(s->stop_rec, img, rec_bytes, hipMemcpyHostToDevice, st));
-            std::fill(s->stop_host.begin(), s->stop_host.end(), 0);
-            s->stop_armed = true;
-        } else {
-            CG_HIP(hipMemcpyAsync(static_cast<char *>(s->stop_rec) + 16, tl, (size_t)nr * 8, hipMemcpyHostToDevice, st));
-        }
-    }
+    if (int rc = stop_run_arm(s->stop, tol, nTol, st)) return rc;
     const int chunk = checkEvery ? checkEvery : 8;
     const bool use_graph = !(s->flags & CGAMD_NO_GRAPH) && !s->graph_failed;
-    volatile int *active = s->until_pin;
-    int rc = CGAMD_OK, enq = 0;
-    bool none_left = false;
-    for (int c = 0; enq < maxIterations && !none_left && !rc; ++c) {
-        const int len = std::min(chunk, maxIterations - enq);
-        bool replayed = false;
+    // a whole chunk is one captured graph (gT), replayed by every later call with the same checkEvery; the tail is plain launches
+    auto enqueue = [&](int len) -> int {
         if (use_graph && !s->graph_failed && len == chunk) {
             if (s->gT && s->gT_len != chunk) {
                 (void)hipGraphExecDestroy(s->gT); (void)hipGraphDestroy(s->gTg);
@@ -1381,32 +1325,26 @@ int cgamd_solver_iterate_until(cgamd_solver *s, int maxIterations, const double 
             }
             if (s->gT) {
                 CG_HIP(hipGraphLaunch(s->gT, st));
-                replayed = true;
+                return CGAMD_OK;
             }
         }
-        for (int i = 0; i < len && !replayed && !rc; ++i) rc = enqueue_iteration_until(s, st);
-        if (rc) break;
-        enq += len;
-        CG_HIP(hipMemcpyAsync(s->until_pin + (c & 1), s->stop.nactive, sizeof(int), hipMemcpyDeviceToHost, st));
-        CG_HIP(hipEventRecord(s->until_ev[c & 1], st));
-        if (c > 0) {            // chunk c is in the stream: now the count chunk c - 1 left
-            CG_HIP(hipEventSynchronize(s->until_ev[(c - 1) & 1]));
-            none_left = active[(c - 1) & 1] == 0;
-        }
-    }
-    if (rc) {                   // part of an iteration may be in the stream: the handle demands a fresh set_rhs
-        (void)hipStreamSynchronize(st);
+        for (int i = 0; i < len; ++i)
+            if (int rc = enqueue_iteration(s, i, st, 1, &s->stop.view)) return rc;
+        return CGAMD_OK;
+    };
+    if (int rc = stop_run_chunks(s->stop, maxIterations, chunk, st, enqueue)) {
+        (void)hipStreamSynchronize(st);     // part of an iteration may be in the stream: the handle demands a fresh set_rhs
         s->rhs_set = false;
         return rc;
     }
-    CG_HIP(hipMemcpyAsync(s->until_pin + 2, s->sc.iter, sizeof(int), hipMemcpyDeviceToHost, st));
-    CG_HIP(hipMemcpyAsync(s->until_pin + 3, s->stop.stop, sizeof(int) * (size_t)nr, hipMemcpyDeviceToHost, st));
+    // (columns may have stopped in different iterations: the count comes from the device, not from what was enqueued)
+    CG_HIP(hipMemcpyAsync(s->stop.pin + 2, s->sc.iter, sizeof(int), hipMemcpyDeviceToHost, st));
+    if (int rc = stop_run_read(s->stop, st)) return rc;
     CG_HIP(hipStreamSynchronize(st));
-    s->iters = s->until_pin[2];
+    s->iters = s->stop.pin[2];
     for (int r = 0; r < nr; ++r) {
-        s->stop_host[r] = s->until_pin[3 + r];
-        if (s->stop_host[r]) s->until_stopped = true;
-        iterations_run[r] = s->stop_host[r] ? s->stop_host[r] : s->iters;
+        if (s->stop.stopped[r]) s->until_stopped = true;
+        iterations_run[r] = s->stop.stopped[r] ? s->stop.stopped[r] : s->iters;
     }
     return CGAMD_OK;
 }

@@ -357,6 +357,32 @@ def test_after_iterate_calls_and_under_a_smaller_tolerance(pkg, gpu):
         s.close()
 
 
+@pytest.mark.parametrize("graph", [True, False], ids=["graph", "no_graph"])
+@pytest.mark.parametrize("pre", [None, "jacobi"])
+def test_iterate_goes_on_after_an_iterate_until_that_stopped_nothing(pkg, gpu, pre, graph):
+    """set_rhs; iterate_until(tol, 7, check_every=3); iterate(9) leaves the bits of set_rhs; iterate(16) on the same handle: two
+    replayed chunks and one iteration of plain guarded launches, then a plain iterate on the handle still in the three-launch loop
+    iterate_until put it in (its graphs captured anew there).  Three right-hand sides that all stay active (the scaled copies, no
+    zero column: that one stops by the NaN rule and the handle then refuses iterate)."""
+    s, n = solver(pkg, gpu[0], "poisson24", np.float64, 3, flags=0 if graph else pkg._lib.NO_GRAPH)
+    try:
+        if pre is not None:
+            s.set_preconditioner(pre)
+        b = np.ascontiguousarray(rhs_block("poisson24", 4, np.float64)[0][:3]).reshape(-1)      # b, 0.1 b, 0.01 b
+        s.set_rhs(b)
+        s.iterate(16)
+        X, H = s.x().copy(), s.history().copy()
+        assert H.shape == (17, 3) and s.iterations_done() == 16 and np.all(np.isfinite(H))
+        s.set_rhs(b)
+        assert s.iterate_until(np.full(3, 1e-200), 7, check_every=3).tolist() == [7, 7, 7]
+        s.iterate(9)
+        assert s.iterations_done() == 16
+        assert same(s.x(), X), "x"
+        assert same(s.history(), H), "history"
+    finally:
+        s.close()
+
+
 # ---- preconditioned handles --------------------------------------------------------------------------------------------------------------
 def test_diagonal_pcg(pkg, gpu):
     s, n = solver(pkg, gpu[0], "poisson24", np.float64, 5)
