@@ -18,6 +18,7 @@ DTYPE_CODE = {np.dtype(np.float32): F32, np.dtype(np.float64): F64,
 CODE_DTYPE = {v: k for k, v in DTYPE_CODE.items()}
 
 MATRIX_ON_DEVICE, NO_GRAPH, UNFUSED, DIST_GRAPH, DIST_NO_OVERLAP, DIST_P2P, DIST_P2P_STAGED, DIST_SINGLE_REDUCTION, DIST_RESIDENT = 1, 2, 4, 8, 32, 64, 128, 256, 512
+HERMITIAN = 16      # CGAMD_HERMITIAN: Solver(..., hermitian=True), the conjugated recurrence for complex Hermitian positive-definite matrices
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_IO, ERR_COMM, ERR_STATE = range(8)      # cgamd_status (include/cgamd.h)
 
 
@@ -78,6 +79,8 @@ def load():
         "cgamd_solver_create": (ci, [vp, ci, ci, ll, vp, vp, vp, ci, ci, pvp]),
         "cgamd_solver_create_batched": (ci, [vp, ci, ci, ll, vp, vp, vp, ci, ci, pvp]),
         "cgamd_solver_systems": (ci, [vp]),
+        "cgamd_solver_hermitian": (ci, [vp]),
+        "cgamd_solver_hermitian_scalars": (ci, [vp, vp, vp]),
         "cgamd_solver_destroy": (ci, [vp]),
         "cgamd_solver_set_rhs": (ci, [vp, vp, vp, ci]),
         "cgamd_solver_set_preconditioner": (ci, [vp, vp, ci]),

@@ -247,10 +247,15 @@ class Solver:
     """Matrix-resident CG handle: the reference re-uploads the matrix and re-JITs
     its kernels on every call (clcg.c:142-214, cl.py:45-46,73-84); here only b goes up and x comes down."""
 
-    def __init__(self, ctx, size, non_zeros, a_values, a_pointers, a_cols, n_rhs=1, flags=0, dtype=None, batched=False):
+    def __init__(self, ctx, size, non_zeros, a_values, a_pointers, a_cols, n_rhs=1, flags=0, dtype=None, batched=False, hermitian=False):
         """batched=True: n_rhs systems on one pattern (cgamd_solver_create_batched) -- a_values holds n_rhs * non_zeros entries,
         the values of system r at a_values[r * non_zeros:(r + 1) * non_zeros] in the order of a_cols, and right-hand side r
-        belongs to system r."""
+        belongs to system r.
+        hermitian=True (flag HERMITIAN): the matrix is complex Hermitian positive definite -- CG with the conjugated inner product
+        <a, b> = sum conj(a_i) b_i instead of the reference's unconjugated recurrence, which does not converge on such a matrix.
+        history() is then r^H r (real, >= 0).  Real value types: accepted, changes nothing."""
+        if hermitian:
+            flags = int(flags) | _lib.HERMITIAN
         self.ctx = ctx
         self._lib = _lib.load()
         self.batched = bool(batched)
@@ -288,6 +293,18 @@ class Solver:
     def systems(self):
         """systems of a batched handle (each right-hand side has a matrix of its own), 0 for every other handle"""
         return self._lib.cgamd_solver_systems(self.handle)
+
+    @property
+    def hermitian(self):
+        """1 when the handle runs the conjugated recurrence (created with hermitian=True / HERMITIAN on a complex type), else 0"""
+        return self._lib.cgamd_solver_hermitian(self.handle)
+
+    def hermitian_scalars(self):
+        """(alpha, beta) of the last iteration of a hermitian handle, n_rhs values each (development accessor: step_state describes
+        the other loops and refuses these handles)"""
+        a, b = np.empty(self.n_rhs, dtype=self.dtype), np.empty(self.n_rhs, dtype=self.dtype)
+        check(self._lib.cgamd_solver_hermitian_scalars(self.handle, ptr(a), ptr(b)))
+        return a, b
 
     def reload_matrix(self, a_values, a_pointers, a_cols):
         """new values / pattern of the same size and non-zero count from HOST arrays into a handle that owns its matrix
@@ -448,7 +465,8 @@ class Solver:
         return int(self._lib.cgamd_solver_iterations_done(self.handle))
 
     def history(self):
-        """delta_k = r_k . r_k (unconjugated) for k = 0..iterations; shape (iterations+1, n_rhs)."""
+        """delta_k = r_k . r_k (unconjugated; a hermitian handle: r_k^H r_k, imaginary part +0) for k = 0..iterations; shape
+        (iterations+1, n_rhs)."""
         n = self._lib.cgamd_solver_iterations_done(self.handle) + 1
         out = np.empty((n, self.n_rhs), dtype=self.dtype)
         got = self._lib.cgamd_solver_history(self.handle, ptr(out), n)

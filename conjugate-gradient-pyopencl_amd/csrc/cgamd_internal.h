@@ -450,6 +450,24 @@ int launch_pcg_aypx_beta(int dtype, int n, const void *r, void *p, const void *m
                          long long m_pitch = 0, const CgStop *stop = nullptr);
 int launch_pcg_p_update(int dtype, int n, const void *r, void *p, const void *m, long long ld, const void *beta, int nrhs, hipStream_t st);
 int launch_pcg_delta0(int dtype, const void *part_rz, const void *part_rr, int P, int nrhs, const CgScalars &sc, void *rho2, hipStream_t st);
+// ---- CGAMD_HERMITIAN handles (hermitian.hip): CG with <a, b> = sum conj(a_i) b_i, complex value types only.  dc = conj(d) is kept
+// beside d, so that the fused dot of every SpMV kernel yields d^H q; alpha, beta, delta and rho are real (imaginary part +0).
+// m == nullptr: no preconditioner; else z = m .* r with m at pitch m_pitch per right-hand side (0 = shared), rho = Re(r^H z) kept
+// in sc.delta and in the parity buffer rho2, part_rz its partials.  history holds r^H r in both cases.
+// set_rhs: d = r (d = m .* r), dc = conj(d), partials of r^H r (and r^H z); then delta0 / rho0, history[0], iter = 0
+int launch_herm_init(int dtype, int n, const void *r, void *d, void *dc, const void *m, long long m_pitch, long long ld, int nrhs,
+                     void *part_rz, void *part_rr, int grid, hipStream_t st);
+int launch_herm_delta0(int dtype, bool pre, const void *part_rz, const void *part_rr, int P, int nrhs, const CgScalars &sc, void *rho2,
+                       hipStream_t st);
+// alpha = delta / Re(sum of the d^H q partials); advances the counter (guarded: the alpha-step duties of stop_device.h)
+int launch_herm_alpha(int dtype, const void *part_dq, int P, int nrhs, const CgScalars &sc, hipStream_t st, const CgStop *stop = nullptr);
+// r -= alpha q ; partials of r^H r (and of r^H (m .* r))
+int launch_herm_axpy_dot(int dtype, int n, const void *q, void *r, const void *m, long long m_pitch, long long ld, const void *alpha,
+                         int nrhs, void *part_rz, void *part_rr, int grid, hipStream_t st, const CgStop *stop = nullptr);
+// beta, delta, history[iter] and the stop decision in the prologue; x += alpha d ; d = beta d + r (d = beta d + m .* r) ; dc = conj(d)
+int launch_herm_aypx_beta_x(int dtype, int n, const void *r, void *d, void *dc, void *xs, const void *m, long long m_pitch, long long ld,
+                            const void *part_rz, const void *part_rr, int P, int nrhs, const CgScalars &sc, void *rho2, hipStream_t st,
+                            const CgStop *stop = nullptr);
 // tridiagonal M (precond.hip): the factors of cgamd_solver_set_preconditioner_tridiag and the chunk plan, device arrays
 struct TriLaunch {
     const void *nl = nullptr, *ne = nullptr, *w = nullptr;   // -l_i, -w_i c_i, w_i = 1/u_i: n values each

@@ -1,6 +1,9 @@
 // oclcgex -- command-line front end with the reference's argv (reference main.c:13-61):
-//     oclcgex <matrix.mtx> <nRHS> <isComplex> <nIterations> [--double] [--device N] [--quiet] [--history <file>]
+//     oclcgex <matrix.mtx> <nRHS> <isComplex> <nIterations> [--double] [--device N] [--quiet] [--history <file>] [--hermitian]
 // Matrix-Market file -> symmetric storage expanded -> CSR; b[r*n+i] = (r+1)*5, x0 = 0 (main.c:41-46).
+// --hermitian: the matrix is complex Hermitian positive definite (a `hermitian` file): CG with conjugated inner products
+// (CGAMD_HERMITIAN), the history then being r_k^H r_k.  Never chosen from the file's symmetry field: the default is the reference's
+// unconjugated recurrence for every file, as it always was.
 // The reference prints nothing and discards x; this front end adds the residual history and timing.
 // Values are cast to single precision as the reference does (main.c:49-53) unless --double is given.
 // --history <file>: the whole residual history delta_k[r] = r_k.r_k (k = 0..nIterations, r < nRHS; what the reference computes and
@@ -16,12 +19,12 @@
 
 int main(int argc, char *argv[]) {
     if (argc < 5) {
-        fprintf(stderr, "Usage: %s <input matrix file> <number of RHS> <is complex> <number of iterations> [--double] [--device N] [--quiet] [--history <file>]\n", argv[0]);
+        fprintf(stderr, "Usage: %s <input matrix file> <number of RHS> <is complex> <number of iterations> [--double] [--device N] [--quiet] [--history <file>] [--hermitian]\n", argv[0]);
         return 1;
     }
     const char *path = argv[1];
     const int nRHS = atoi(argv[2]), isComplex = atoi(argv[3]), nIterations = atoi(argv[4]);
-    bool dbl = false, quiet = false;
+    bool dbl = false, quiet = false, hermitian = false;
     int device = 0;
     const char *history_path = nullptr;
     for (int i = 5; i < argc; ++i) {
@@ -29,6 +32,7 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "--quiet")) quiet = true;
         else if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--history") && i + 1 < argc) history_path = argv[++i];
+        else if (!strcmp(argv[i], "--hermitian")) hermitian = true;
     }
     if (nRHS < 1 || nIterations < 0) { fprintf(stderr, "bad nRHS / nIterations\n"); return 1; }
 
@@ -58,7 +62,17 @@ int main(int argc, char *argv[]) {
         for (int i = 0; i < n; ++i) put(b.data(), (size_t)r * n + i, (r + 1) * 5.0, 0.0);   // main.c:44
 
     const auto t0 = std::chrono::steady_clock::now();
-    const int rc = cgamd_cg(dtype, n, nnz, a.data(), b.data(), ptr, cols, x.data(), nRHS, nIterations, hist.data(), device);
+    int rc;
+    if (!hermitian) rc = cgamd_cg(dtype, n, nnz, a.data(), b.data(), ptr, cols, x.data(), nRHS, nIterations, hist.data(), device);
+    else {      // a handle of its own, created with the flag (cgamd_cg has no flags): the same upload, solve and download
+        cgamd_ctx *ctx = nullptr;
+        cgamd_solver *s = nullptr;
+        rc = cgamd_ctx_create(device, &ctx);
+        if (rc == CGAMD_OK) rc = cgamd_solver_create(ctx, dtype, n, nnz, a.data(), ptr, cols, nRHS, CGAMD_HERMITIAN, &s);
+        if (rc == CGAMD_OK) rc = cgamd_solver_solve(s, b.data(), x.data(), nIterations, hist.data());
+        cgamd_solver_destroy(s);
+        if (ctx) cgamd_ctx_destroy(ctx);
+    }
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     cgamd_mm_free(vals); cgamd_mm_free(ptr); cgamd_mm_free(cols);
     if (rc != CGAMD_OK) { fprintf(stderr, "error -- cg failed (%d): %s\n", rc, cgamd_last_error()); return 2; }

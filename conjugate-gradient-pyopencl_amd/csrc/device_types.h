@@ -3,7 +3,7 @@
 // Four value types: float, double, float2 (complex64, interleaved re/im),
 // double2 (complex128).  Complex arithmetic is componentwise exactly as the
 // reference defines it (kernel/complex/cmplx.h:6-25); the dot product is
-// UNCONJUGATED (kernel/complex/vdot.cl:15).
+// UNCONJUGATED (kernel/complex/vdot.cl:15) everywhere but in hermitian.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -51,6 +51,13 @@ CG_DEV float vmul(float a, float b) { return a * b; }
 CG_DEV double vmul(double a, double b) { return a * b; }
 CG_DEV float2 vmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
 CG_DEV double2 vmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+
+// complex conjugate (the identity on the real types): CGAMD_HERMITIAN handles form <a, b> as vmul(vconj(a), b) (hermitian.hip), so
+// that <a, a> has an imaginary part of exactly +0 (a.x a.y + (-a.y) a.x, both products rounded alike)
+CG_DEV float vconj(float a) { return a; }
+CG_DEV double vconj(double a) { return a; }
+CG_DEV float2 vconj(float2 a) { return make_float2(a.x, -a.y); }
+CG_DEV double2 vconj(double2 a) { return make_double2(a.x, -a.y); }
 
 // c ? a : b, component-wise (a ?: on the HIP vector structs is lowered through scratch memory)
 CG_DEV float vsel(bool c, float a, float b) { return c ? a : b; }

@@ -446,6 +446,8 @@ int cgamd_dist_create(cgamd_ctx *ctx, const void *id128, int rank, int nranks, i
                       int flags, cgamd_dist **out) {
     if (!out) return fail(CGAMD_ERR_INVALID, "dist_create: out is NULL");
     *out = nullptr;
+    if (flags & CGAMD_HERMITIAN)
+        return fail(CGAMD_ERR_INVALID, "dist_create: CGAMD_HERMITIAN is a flag of the single-GPU handle (the row-partitioned loops run the unconjugated recurrence only)");
     if (!ctx) return fail(CGAMD_ERR_INVALID, "dist_create: ctx is NULL");
     if (dtype < 0 || dtype > 3) return fail(CGAMD_ERR_INVALID, "dist_create: bad dtype");
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(CGAMD_ERR_INVALID, "dist_create: bad rank/nranks");

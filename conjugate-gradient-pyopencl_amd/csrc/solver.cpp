@@ -8,6 +8,7 @@
 //   axpy2_dot  x += alpha d ; r -= alpha q ; partials of r.r (clcg.c:338-374)
 //   aypx_beta  beta = delta_new/delta_old ; history ; d = beta d + r   (clcg.c:376-415; beta in the prologue)
 // CGAMD_UNFUSED replays the reference's own op structure (spmv, vdot, axpy, axpy, vdot, aypx).
+// CGAMD_HERMITIAN (complex types): the conjugated recurrence on four launches of its own (hermitian.hip), the SpMV unchanged.
 // 16 / 32 right-hand sides (f64, complex64; f32 also 64): the block is kept ROW-MAJOR inside the handle and the
 // product runs on the matrix cores (rowmajor.hip); the reference's RHS-major layout is converted in set_rhs / get_x.
 #include <algorithm>
@@ -37,6 +38,10 @@ struct cgamd_solver {
     // one M per system (cgamd_solver_set_preconditioner_batched*): mdiag holds nsys diagonals at stride n, tri the factors of every
     // system at tri.fpitch on one segment plan.
     int nsys = 0;
+    // CGAMD_HERMITIAN on a complex value type (hermitian.hip): the conjugated recurrence, on a four-launch loop of its own -- no
+    // resident, chip-wide or two-launch loop, no row-major layout, no deferred x update.  dc = conj(d), the vector of the SpMV's fused
+    // dot, lives in the d2 slot, which those loops alone use.  Never set for the real types: the flag changes nothing there.
+    bool herm = false;
     bool own_ptr = false;   // a borrowed device matrix whose row pointers were copied to append the padding rows
     long long nnz = 0;
     void *vals = nullptr;
@@ -187,6 +192,7 @@ static int enqueue_spmv(cgamd_solver *s, int k, hipStream_t st, void *dvec = nul
     else if (s->rm) rc = launch_spmm_rm(dt, n, s->nnz, s->vals, s->ptr, s->cols, s->d, s->q, nr, s->part_dq, s->plan.max_quad, s->rm_pace, st);
     // (the preconditioned loops of a batched handle take alpha from the d.q partials whatever the flags)
     else if ((s->flags & CGAMD_UNFUSED) && !s->tri_on && !(s->nsys && s->mdiag)) rc = handle_spmv(s, n, s->d, n, s->q, n, nullptr, nullptr, st);
+    else if (s->herm) rc = handle_spmv(s, n, s->d, n, s->q, n, s->d2, s->part_dq, st);       // the dot against dc = conj(d): d^H q
     else rc = handle_spmv(s, n, dvec ? dvec : s->d, n, s->q, n, dvec ? dvec : s->d, s->part_dq, st);
     set_kernel_event_pair(nullptr);
     if (rc) return rc;
@@ -260,6 +266,13 @@ static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st, int lag = 1
         if ((rc = launch_cg_beta(dt, s->part_rr, s->rm_vgrid, nr, s->sc, st))) return rc;
         return launch_rm_aypx_x(dt, n, nr, s->r, s->d, s->x, s->sc.alpha, s->sc.beta, s->rm_vgrid, st);
     }
+    if (s->herm) {    // conjugated recurrence (hermitian.hip), with or without a diagonal M; delta holds rho
+        if ((rc = enqueue_spmv(s, k, st))) return rc;
+        if ((rc = launch_herm_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st, g))) return rc;
+        if ((rc = launch_herm_axpy_dot(dt, n, s->q, s->r, s->mdiag, m_pitch(s), n, s->sc.alpha, nr, s->part_rz, s->part_rr, s->vgrid, st, g))) return rc;
+        return launch_herm_aypx_beta_x(dt, n, s->r, s->d, s->d2, s->x, s->mdiag, m_pitch(s), n, s->part_rz, s->part_rr, s->vgrid, nr, s->sc,
+                                       s->rho2, st, g);
+    }
     if (s->tri_on) {  // tridiagonal M (helmFE_var.py:561-562): z = M^-1 r by the line sweeps, in q's storage
         if ((rc = enqueue_spmv(s, k, st))) return rc;
         if ((rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st, g))) return rc;
@@ -313,7 +326,7 @@ static void apply_wide_order(cgamd_solver *s) {
     if (kdq == s->sc.kdq && krr == s->sc.krr && vgrid == s->vgrid && fold_max == s->plan.fold_max) return;
     destroy_graphs(s);
     s->sc.kdq = kdq; s->sc.krr = krr; s->vgrid = vgrid; s->plan.fold_max = fold_max;
-    s->fused2 = fused2_ok(s->plan, s->dtype, s->nrhs, s->vals, s->cols);
+    s->fused2 = !s->herm && fused2_ok(s->plan, s->dtype, s->nrhs, s->vals, s->cols);
 }
 
 // the resident loop applies where the two-launch loop does and the matrix slices fit LDS (needs the row pointers on the host)
@@ -428,6 +441,7 @@ static int setup_resident_one_xcd(cgamd_solver *s);
 static int setup_resident_local(cgamd_solver *s) {
     s->res_ok = false;
     s->resw.ok = false;
+    if (s->herm) return CGAMD_OK;       // the conjugated recurrence has no resident form
     if (int rc = setup_resident_one_xcd(s)) return rc;
     // where the one-XCD loop applies the chip-wide plan is only needed once a preconditioner is set (that recurrence has no one-XCD
     // form): cgamd_solver_set_preconditioner asks for it then -- the stateless cg() entry reloads per call and would pay the scan
@@ -471,7 +485,7 @@ static void setup_x_lag(cgamd_solver *s) {
     const int knob = s->tune.dev_x_lag;
     // (a handle the chip-wide resident loop takes over launches a graph for the few calls too short for that loop only)
     int lag = knob >= 0 ? std::max(knob, 1) : (fold_alpha_ok(s->plan.n_partials, s->plan.fold_max) || s->resw.ok ? 1 : kXLagDefault);
-    if (s->nsys || (s->flags & (CGAMD_UNFUSED | CGAMD_NO_GRAPH)) || lag > kLagMax || s->U % lag != 0) lag = 1;
+    if (s->nsys || s->herm || (s->flags & (CGAMD_UNFUSED | CGAMD_NO_GRAPH)) || lag > kLagMax || s->U % lag != 0) lag = 1;
     if (lag - 2 > s->dlag_bufs) {
         if (s->dlag) { (void)hipStreamSynchronize(s->ctx->stream); (void)hipFree(s->dlag); s->dlag = nullptr; s->dlag_bufs = 0; }
         s->dlag_pitch = ((size_t)s->n * s->nrhs * dtype_size(s->dtype) + 4095) & ~(size_t)4095;      // as in the handle's slab
@@ -547,9 +561,13 @@ static int create_impl(const std::string &who, cgamd_ctx *ctx, int dtype, int si
     if (nnz > 2147483647LL - 8192) return fail(CGAMD_ERR_INVALID, who + ": nnz exceeds int32 row pointers");
     if (!aPointers || (nnz > 0 && (!aValues || !aCols))) return fail(CGAMD_ERR_INVALID, who + ": null matrix pointer");
     const size_t nmat = nsys ? (size_t)nsys : 1;      // value arrays of nnz entries behind aValues
+    const bool herm = (flags & CGAMD_HERMITIAN) && (dtype == CGAMD_C64 || dtype == CGAMD_C128);     // real types: Hermitian is symmetric
+    if (herm && (flags & CGAMD_UNFUSED))
+        return fail(CGAMD_ERR_INVALID, who + ": CGAMD_UNFUSED replays the reference's unconjugated kernel sequence; it has no CGAMD_HERMITIAN form");
     CG_HIP(hipSetDevice(ctx->device));
     const size_t vs = dtype_size(dtype);
     cgamd_solver *s = new cgamd_solver();
+    s->herm = herm;
     s->tune = tune_snapshot();
     TuneScope ts(&s->tune);
     s->ctx = ctx; s->dtype = dtype; s->n = size; s->n_user = size; s->nnz = nnz; s->nrhs = nRHS; s->nsys = nsys; s->flags = flags;
@@ -560,7 +578,7 @@ static int create_impl(const std::string &who, cgamd_ctx *ctx, int dtype, int si
     // (up to 32768 rows the resident loop is several times faster than any launched loop; between that and ~1M rows the chip-wide
     // resident groups take over when they apply, setup_resident_wide_plan)
     const bool rm_wins = dtype == CGAMD_F64 && nRHS == 32 && size > 32768;
-    s->rm_ok = !nsys && nRHS > 1 && (rm_knob >= 2 || (rm_knob == 1 && rm_wins)) && !(flags & CGAMD_UNFUSED) && spmm_rm_supported(dtype, nRHS, size);
+    s->rm_ok = !nsys && !herm && nRHS > 1 && (rm_knob >= 2 || (rm_knob == 1 && rm_wins)) && !(flags & CGAMD_UNFUSED) && spmm_rm_supported(dtype, nRHS, size);
     if (s->rm_ok) s->rm_vgrid = rm_vec_grid((long long)size * nRHS, dtype);
     {
         const int E = (int)(16 / vs);      // values per 16-byte pack
@@ -643,7 +661,7 @@ static int create_impl(const std::string &who, cgamd_ctx *ctx, int dtype, int si
     if (!rc && s->rm_ok) rc = dmalloc((void **)&s->rm_pace, sizeof(int) * kSpmmPaceInts, "spmm pace counters");
     if (!rc && s->rm_ok && hipMemsetAsync(s->rm_pace, 0, sizeof(int) * kSpmmPaceInts, ctx->stream) != hipSuccess) rc = fail(CGAMD_ERR_HIP, "hipMemsetAsync(spmm pace counters)");
     if (!rc && nsys) finalize_batched_plan(s);
-    if (!rc && !nsys) s->fused2 = fused2_ok(s->plan, dtype, nRHS, s->vals, s->cols);
+    if (!rc && !nsys) s->fused2 = !s->herm && fused2_ok(s->plan, dtype, nRHS, s->vals, s->cols);
     if (!rc && !nsys) rc = setup_resident(s);
     if (!rc && !nsys) rc = setup_index_codes(s);
     if (!rc) setup_x_lag(s);
@@ -676,6 +694,7 @@ int cgamd_solver_create_batched(cgamd_ctx *ctx, int dtype, int size, long long n
 }
 
 int cgamd_solver_systems(cgamd_solver *s) { return s ? s->nsys : -CGAMD_ERR_INVALID; }
+int cgamd_solver_hermitian(cgamd_solver *s) { return s ? (s->herm ? 1 : 0) : -CGAMD_ERR_INVALID; }
 
 static int diag_impl(cgamd_solver *s, const void *m, int on_device);
 // a batched handle (cgamd_solver_create_batched) has a matrix per right-hand side: one M shared by all of them preconditions none
@@ -683,6 +702,11 @@ static int batched_refuses(const char *who) {
     return fail(CGAMD_ERR_STATE, std::string(who) + ": the handle is batched (a matrix of its own per right-hand side); a preconditioner "
                                                     "shared by all right-hand sides has no meaning for different systems");
 }
+// what a CGAMD_HERMITIAN handle does not serve: refused before anything on the handle changes
+static int herm_refuses(const char *who, const char *why) {
+    return fail(CGAMD_ERR_STATE, std::string(who) + ": the handle runs the conjugated recurrence (CGAMD_HERMITIAN), " + why);
+}
+constexpr const char *kHermNoLines = "whose preconditioner is diagonal: the line sweeps form the unconjugated r.z and r.r";
 static int line_from_matrix(cgamd_solver *s, const std::string &who, int stride);
 static int jacobi_from_matrix(cgamd_solver *s, const std::string &who);
 static int batched_line_from_matrix(cgamd_solver *s, const std::string &who, int stride);
@@ -715,7 +739,7 @@ int cgamd_solver_reload_matrix(cgamd_solver *s, const void *aValues, const int *
         finalize_spmv_plan(&s->plan, s->dtype, s->nrhs, s->n, s->nnz, s->vals, s->cols);
         if ((size_t)std::max(s->plan.grid, s->plan.row_blocks) > s->part_dq_cap) return fail(CGAMD_ERR_STATE, "reload_matrix: partial buffer too small");
         if (s->rm_ok) s->rm_nwg = spmm_rm_grid(s->dtype, s->nrhs, s->n, s->plan.max_quad, true);
-        s->fused2 = fused2_ok(s->plan, s->dtype, s->nrhs, s->vals, s->cols);
+        s->fused2 = !s->herm && fused2_ok(s->plan, s->dtype, s->nrhs, s->vals, s->cols);
         if (s->nsys) finalize_batched_plan(s);
     }
     if (s->nsys) {                                  // no resident loop, no codes; a per-system preconditioner built from the matrices follows them
@@ -890,7 +914,10 @@ int cgamd_solver_set_rhs(cgamd_solver *s, const void *b, const void *x0, int on_
     // r = b - A x0 ; d = r ; delta0 = r.r   (clcg.c:255-292)
     if ((rc = handle_spmv(s, s->n, s->x, s->n, s->q, s->n, nullptr, nullptr, st))) return rc;
     if ((rc = launch_sub(s->dtype, s->n, s->b, s->q, s->r, s->n, s->nrhs, st))) return rc;
-    if (s->tri_on) {  // z0 = M^-1 r0 (the line sweeps), p0 = z0, rho0 = r0.z0
+    if (s->herm) {    // d0 = r0 (d0 = m .* r0), dc = conj(d0), delta0 = r0^H r0, rho0 (hermitian.hip)
+        if ((rc = launch_herm_init(s->dtype, s->n, s->r, s->d, s->d2, s->mdiag, m_pitch(s), s->n, s->nrhs, s->part_rz, s->part_rr, s->vgrid, st))) return rc;
+        if ((rc = launch_herm_delta0(s->dtype, s->mdiag != nullptr, s->part_rz, s->part_rr, s->vgrid, s->nrhs, s->sc, s->rho2, st))) return rc;
+    } else if (s->tri_on) {  // z0 = M^-1 r0 (the line sweeps), p0 = z0, rho0 = r0.z0
         if ((rc = enqueue_tri_sweep(s, false, nullptr, s->d, st))) return rc;
         const TriPartials p = tri_partials(s);
         if ((rc = launch_pcg_delta0(s->dtype, p.rz, p.rr, s->tri.grid, s->nrhs, s->sc, s->rho2, st))) return rc;
@@ -953,7 +980,7 @@ static int diag_impl(cgamd_solver *s, const void *m, int on_device) {
     else CG_HIP(hipMemcpy2DAsync(s->mdiag, (size_t)s->n * vs, m, (size_t)s->n_user * vs, (size_t)s->n_user * vs, nm, kind, s->ctx->stream));
     CG_HIP(hipStreamSynchronize(s->ctx->stream));
     s->pre_source = 1;
-    if (!s->resw.ok && !s->nsys)
+    if (!s->resw.ok && !s->nsys && !s->herm)
         if (int rc2 = setup_resident_wide_plan(s)) return rc2;      // (skipped at creation where the one-XCD loop runs the plain recurrence)
     apply_wide_order(s);
     return CGAMD_OK;
@@ -1013,6 +1040,7 @@ static int tridiag_strided_impl(cgamd_solver *s, const std::string &who, int str
 int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, const void *diag, const void *upper, int on_device) {
     if (!s || !lower || !diag || !upper) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag: null argument");
     if (s->nsys) return batched_refuses("set_preconditioner_tridiag");
+    if (s->herm) return herm_refuses("set_preconditioner_tridiag", kHermNoLines);
     TuneScope ts(&s->tune);
     return tridiag_strided_impl(s, "set_preconditioner_tridiag", 1, lower, diag, upper, on_device);
 }
@@ -1021,6 +1049,7 @@ int cgamd_solver_set_preconditioner_tridiag_strided(cgamd_solver *s, int stride,
                                                     int on_device) {
     if (!s || !lower || !diag || !upper) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag_strided: null argument");
     if (s->nsys) return batched_refuses("set_preconditioner_tridiag_strided");
+    if (s->herm) return herm_refuses("set_preconditioner_tridiag_strided", kHermNoLines);
     if (stride < 1 || stride >= s->n_user)
         return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag_strided: stride must be in [1, size - 1]");
     TuneScope ts(&s->tune);
@@ -1046,6 +1075,7 @@ static int line_from_matrix(cgamd_solver *s, const std::string &who, int stride)
 int cgamd_solver_set_preconditioner_line(cgamd_solver *s, int stride) {
     if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner_line: solver is NULL");
     if (s->nsys) return batched_refuses("set_preconditioner_line");
+    if (s->herm) return herm_refuses("set_preconditioner_line", kHermNoLines);
     if (stride < 1 || stride >= s->n_user) return fail(CGAMD_ERR_INVALID, "set_preconditioner_line: stride must be in [1, size - 1]");
     TuneScope ts(&s->tune);
     return line_from_matrix(s, "set_preconditioner_line", stride);
@@ -1120,6 +1150,7 @@ static int batched_line_from_matrix(cgamd_solver *s, const std::string &who, int
 int cgamd_solver_set_preconditioner_batched_line(cgamd_solver *s, int stride) {
     if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner_batched_line: solver is NULL");
     if (!s->nsys) return not_batched("set_preconditioner_batched_line", "cgamd_solver_set_preconditioner_line");
+    if (s->herm) return herm_refuses("set_preconditioner_batched_line", kHermNoLines);
     if (stride < 1 || stride >= s->n_user) return fail(CGAMD_ERR_INVALID, "set_preconditioner_batched_line: stride must be in [1, size - 1]");
     TuneScope ts(&s->tune);
     return batched_line_from_matrix(s, "set_preconditioner_batched_line", stride);
@@ -1248,6 +1279,7 @@ int cgamd_solver_iterate_tol(cgamd_solver *s, int maxIterations, double tol, int
     if (!s || !iterations_run) return fail(CGAMD_ERR_INVALID, "iterate_tol: null argument");
     if (!(tol > 0.) || maxIterations < 0) return fail(CGAMD_ERR_INVALID, "iterate_tol: tol must be positive, maxIterations >= 0");
     if (s->nsys) return fail(CGAMD_ERR_STATE, "iterate_tol: a batched handle runs a launched loop (check the history from the host)");
+    if (s->herm) return herm_refuses("iterate_tol", "which has no resident loop: use cgamd_solver_iterate_until");
     if (!s->rhs_set) return fail(CGAMD_ERR_STATE, "iterate_tol: call set_rhs first");
     if (s->nrhs != 1) return fail(CGAMD_ERR_STATE, "iterate_tol: one right-hand side");
     if (s->until_mode) return fail(CGAMD_ERR_STATE, "iterate_tol: iterate_until runs this right-hand side on the launched loop until the next set_rhs");
@@ -1490,6 +1522,7 @@ static int step_not_capturing(cgamd_solver *s, const char *who) {
 static int step_launched_rhs_major(cgamd_solver *s, const char *who) {
     if (s->rm || (s->rm_ok && !precond_set(s)) || s->tri_on)
         return fail(CGAMD_ERR_INVALID, std::string(who) + ": not recorded for row-major and tridiagonal handles");
+    if (s->herm) return fail(CGAMD_ERR_INVALID, std::string(who) + ": not recorded for CGAMD_HERMITIAN handles (steps of their own, hermitian.hip)");
     return CGAMD_OK;
 }
 
@@ -1548,6 +1581,19 @@ int cgamd_solver_step_state(cgamd_solver *s, int which, void *out_host, long lon
     return CGAMD_OK;
 }
 
+// alpha and beta of a CGAMD_HERMITIAN handle (step_state describes the other loops' steps and refuses these handles)
+int cgamd_solver_hermitian_scalars(cgamd_solver *s, void *alpha_host, void *beta_host) {
+    if (!s) return fail(CGAMD_ERR_INVALID, "hermitian_scalars: solver is NULL");
+    if (!s->herm) return fail(CGAMD_ERR_STATE, "hermitian_scalars: the handle does not run the conjugated recurrence (use cgamd_solver_step_state)");
+    if (int rc = step_not_capturing(s, "hermitian_scalars")) return rc;
+    CG_HIP(hipSetDevice(s->ctx->device));
+    const size_t bytes = dtype_size(s->dtype) * (size_t)s->nrhs;
+    if (alpha_host) CG_HIP(hipMemcpyAsync(alpha_host, s->sc.alpha, bytes, hipMemcpyDeviceToHost, s->ctx->stream));
+    if (beta_host) CG_HIP(hipMemcpyAsync(beta_host, s->sc.beta, bytes, hipMemcpyDeviceToHost, s->ctx->stream));
+    CG_HIP(hipStreamSynchronize(s->ctx->stream));
+    return CGAMD_OK;
+}
+
 int cgamd_solver_spmm_rowmajor(cgamd_solver *s, const void *x, void *y, int nRHS) {
     if (!s || !x || !y) return fail(CGAMD_ERR_INVALID, "spmm_rowmajor: null argument");
     if (s->nsys) return fail(CGAMD_ERR_STATE, "spmm_rowmajor: the handle is batched (a matrix of its own per right-hand side)");
@@ -1560,6 +1606,7 @@ int cgamd_solver_layout(cgamd_solver *s) { return s ? (s->rm ? 1 : 0) : -CGAMD_E
 int cgamd_solver_loop_launches(cgamd_solver *s) {
     if (!s) return -CGAMD_ERR_INVALID;
     TuneScope ts(&s->tune);
+    if (s->herm) return 4;                               // SpMV, herm_alpha, herm_axpy_dot, herm_aypx_beta_x under every flag
     if (s->tri_on) return s->tri.longform ? 6 : 4;      // launched loop only: SpMV, cg_alpha, the sweep (3 launches in the long form), update
     if (s->nsys && s->mdiag) return 4;                   // a batched handle's PCG loop is the same four launches under every flag
     if (s->flags & CGAMD_UNFUSED) return 8;
@@ -1600,6 +1647,8 @@ long long cgamd_solver_iter_bytes(cgamd_solver *s, int fused) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
     if (s->tri_on) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + tri_passes(s) * s->n_user * V;
+    // the conjugated recurrence: the launched loop's 10 passes (12 with a diagonal M) and conj(d), written by the d step and read by the SpMV's dot
+    if (s->herm) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + (s->mdiag ? 14LL : 12LL) * s->n_user * V * s->nrhs;
     if (s->nsys && s->mdiag) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + 12LL * s->n_user * V * s->nrhs;
     return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + (fused ? 11LL : 14LL) * s->n_user * V * s->nrhs;
 }
@@ -1630,7 +1679,7 @@ int cgamd_solver_row_codes(cgamd_solver *s) { return s ? (row_form(s) ? s->n_use
 long long cgamd_solver_iter_moved_bytes(cgamd_solver *s) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
-    const long long passes = (s->nsys && s->mdiag) ? 12 : (s->flags & CGAMD_UNFUSED) ? 14 : s->mdiag ? 12 : 10;
+    const long long passes = s->herm ? (s->mdiag ? 14 : 12) : (s->nsys && s->mdiag) ? 12 : (s->flags & CGAMD_UNFUSED) ? 14 : s->mdiag ? 12 : 10;
     const long long lag = x_lag_now(s);
     const long long value_bytes = joint_form(s) ? 0 : s->plan.vcodes ? 1 : V * value_arrays(s);
     const long long matrix = row_form(s) ? (long long)s->n_user : s->nnz * (value_bytes + index_bytes_per_nnz(s)) + ((long long)s->n_user + 1) * 4;

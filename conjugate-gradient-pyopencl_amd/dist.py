@@ -363,6 +363,9 @@ class DistSolver:
                  `group` at construction: the 64-byte IPC handles and the landing offsets are all-gathered)."""
 
     def __init__(self, ctx, plan, indptr_local, values, dtype, unique_id=None, flags=0, comm="rccl", group=None):
+        if int(flags) & _lib.HERMITIAN:     # (before anything touches a device; cgamd_dist_create refuses the flag as well)
+            raise ValueError("the row-partitioned solver runs the unconjugated recurrence only: HERMITIAN is a flag of the single-GPU "
+                             "Solver (Solver(..., hermitian=True))")
         import torch
         self.ctx, self.plan, self.dtype = ctx, plan, np.dtype(dtype)
         self._lib = _lib.load()

@@ -104,6 +104,10 @@ int cgamd_sub(cgamd_ctx *ctx, int dtype, int size, const void *a, const void *b,
                                     * aPointers / aCols must not change while the handle lives */
 #define CGAMD_NO_GRAPH 2           /* plain stream launches instead of hipGraph replay */
 #define CGAMD_UNFUSED 4            /* reference op structure: spmv, vdot, axpy, axpy, vdot, aypx (6 kernels) */
+#define CGAMD_HERMITIAN 16         /* cgamd_solver_create / cgamd_solver_create_batched: CG for a complex HERMITIAN positive-definite
+                                    * matrix -- every inner product of the recurrence conjugated, <a, b> = sum conj(a_i) b_i -- in place of
+                                    * the reference's unconjugated recurrence (COCG, for complex-symmetric matrices).  See "Hermitian
+                                    * systems" below cgamd_solver_hermitian.  Accepted and without effect on the real value types */
 #define CGAMD_DIST_NO_OVERLAP 32    /* cgamd_dist_create: exchange first, then one SpMV (no interior/boundary overlap) */
 #define CGAMD_DIST_P2P 64            /* cgamd_dist_create: no RCCL; peers write each other's IPC mailboxes (attach_p2p) */
 #define CGAMD_DIST_GRAPH 8         /* cgamd_dist_create: replay each iteration (incl. RCCL ops) from a hipGraph */
@@ -146,6 +150,30 @@ int cgamd_solver_create(cgamd_ctx *ctx, int dtype, int size, long long nnz, cons
 int cgamd_solver_create_batched(cgamd_ctx *ctx, int dtype, int size, long long nnz, const void *aValues,
                                 const int *aPointers, const int *aCols, int nSystems, int flags, cgamd_solver **out);
 int cgamd_solver_systems(cgamd_solver *s);   /* nSystems of a batched handle, 0 for every other handle, negative: error */
+/* ---- Hermitian systems (CGAMD_HERMITIAN, csrc/hermitian.hip) ----
+ * 1 when the handle runs the conjugated recurrence (created with CGAMD_HERMITIAN on CGAMD_C64 / CGAMD_C128), 0 otherwise -- also for
+ * the real value types with the flag, where Hermitian is symmetric and the handle runs the loops and gives the bits it gives without
+ * it; negative: error.
+ * The recurrence: delta_k = r_k^H r_k (the history stores it with an imaginary part of exactly +0; it is never negative),
+ * alpha = rho / Re(d^H q), beta = rho' / rho with rho = delta, both REAL and stored in the value type with imaginary part +0.  With a
+ * diagonal M: z = m .* r, rho = Re(r^H z), and the history keeps r^H r.  The caller vouches for A = A^H being positive definite and
+ * for m being real and positive: neither is validated (nor is the symmetry of the matrix of any other handle).
+ * Such a handle runs a launched loop only: cgamd_solver_loop_launches() == 4, cgamd_solver_x_lag() == 1, cgamd_solver_layout() == 0 at
+ * every nRHS; no resident, chip-wide or two-launch loop.  CGAMD_NO_GRAPH and CGAMD_MATRIX_ON_DEVICE are served;
+ * CGAMD_UNFUSED | CGAMD_HERMITIAN on a complex type is CGAMD_ERR_INVALID at creation.  The SpMV forms, index, value, joint and
+ * row-pattern codes included, are the ones any handle on that matrix takes.
+ * Served: set_rhs (with x0), iterate, iterate_timed, get_x, history, solve, iterate_until (sqrt|delta| is the true 2-norm of r),
+ * refresh_values and reload_matrix, cgamd_solver_set_preconditioner and _jacobi, on batched handles _batched and _batched_jacobi, any
+ * nRHS.  Not served, CGAMD_ERR_STATE with the handle untouched: cgamd_solver_iterate_tol and the tridiagonal / line preconditioner
+ * entries (_tridiag, _tridiag_strided, _line, _batched_line); cgamd_solver_step_plan / _step_state: CGAMD_ERR_INVALID.
+ * cgamd_solver_spmv(..., fused_dot) stays the development entry it is (unconjugated x.y).  cgamd_dist_create refuses the flag
+ * (CGAMD_ERR_INVALID).  Byte models: cgamd_solver_iter_bytes and cgamd_solver_iter_moved_bytes count 12 vector passes, 14 with a
+ * diagonal M: the launched loop's 10 / 12 and conj(d), written by the d step and read by the SpMV's fused dot. */
+int cgamd_solver_hermitian(cgamd_solver *s);
+/* development accessor (tests): alpha and beta of the last iteration, nRHS values of the handle's type each, copied to the host
+ * after the handle's stream has drained; either pointer may be NULL.  CGAMD_HERMITIAN handles only (CGAMD_ERR_STATE otherwise: the
+ * other handles have cgamd_solver_step_state) */
+int cgamd_solver_hermitian_scalars(cgamd_solver *s, void *alpha_host, void *beta_host);
 int cgamd_solver_destroy(cgamd_solver *s);
 /* new values / pattern of the SAME size (size, nnz, nRHS, dtype) into a handle that owns its matrix (created from host
  * arrays): keeps allocations, stream and -- when the row pointers are unchanged -- the plan and the captured graphs.
