@@ -115,6 +115,14 @@ def load():
         "cgamd_solver_row_codes": (ci, [vp]),
         "cgamd_solver_iterate_tol": (ci, [vp, ci, ctypes.c_double, ctypes.POINTER(ci)]),
         "cgamd_solver_iterate_until": (ci, [vp, ci, ctypes.POINTER(ctypes.c_double), ci, ci, ctypes.POINTER(ci)]),
+        "cgamd_solver_replace_residual": (ci, [vp, vp]),
+        "cgamd_mixed_create": (ci, [vp, ci, ci, ll, vp, vp, vp, ci, ci, pvp]),
+        "cgamd_mixed_destroy": (ci, [vp]),
+        "cgamd_mixed_outer": (vp, [vp]),
+        "cgamd_mixed_inner": (vp, [vp]),
+        "cgamd_mixed_solve": (ci, [vp, vp, vp, ci, ctypes.POINTER(ctypes.c_double), ci, ci, ctypes.c_double, ci, ci, ctypes.POINTER(ci),
+                                   ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci), ctypes.POINTER(ci)]),
+        "cgamd_mixed_scales": (ci, [vp, ctypes.POINTER(ctypes.c_double)]),
         "cgamd_transpose": (ci, [vp, ci, ci, ci, vp, vp]),
         "cgamd_solver_spmv_bytes": (ll, [vp]),
         "cgamd_solver_iter_bytes": (ll, [vp, ci]),

@@ -446,6 +446,21 @@ class Solver:
     def iterate(self, n_iterations):
         check(self._lib.cgamd_solver_iterate(self.handle, int(n_iterations)))
 
+    def replace_residual(self, r):
+        """Residual replacement with the direction kept (cgamd_solver_replace_residual): r := `r`, x := 0, delta := r.r (rho := r.z
+        with a diagonal M), d stays; the iteration count and the history restart and every right-hand side is active again.  iterate()
+        and iterate_until() then continue the recurrence from (0, r, d).  r: n_rhs * size values of the handle's type -- a device
+        array (torch tensor, DeviceBuffer, address), or a numpy array, which is uploaded first (the call then waits for the stream)."""
+        if isinstance(r, np.ndarray):
+            buf = DeviceBuffer(self.ctx, hostbuf=np.ascontiguousarray(r.reshape(-1), dtype=self.dtype))
+            try:
+                check(self._lib.cgamd_solver_replace_residual(self.handle, ptr(buf)))
+                self.ctx.synchronize()
+            finally:
+                buf.release()
+            return
+        check(self._lib.cgamd_solver_replace_residual(self.handle, ptr(r)))
+
     def iterate_timed(self, n_iterations):
         """n_iterations plain-launch iterations with HIP events around every SpMV: (avg SpMV ms, avg iteration ms)"""
         a, b = ctypes.c_float(), ctypes.c_float()
@@ -592,8 +607,8 @@ class Solver:
         return self._lib.cgamd_solver_iter_moved_bytes(self.handle)
 
     def close(self):
-        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
-            self._lib.cgamd_solver_destroy(self.handle)
+        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None) and not getattr(self, "_borrowed", False):
+            self._lib.cgamd_solver_destroy(self.handle)     # (the two handles of a MixedSolver belong to it)
         self.handle = None
 
     def __del__(self):
@@ -712,6 +727,96 @@ class Solver:
             return self.x(), its - 1
         finally:
             self.set_preconditioner(None)
+
+
+class MixedInfo:
+    """what MixedSolver.solve reports, per right-hand side: `iterations` (inner iterations of the segments the column was open in),
+    `resnorm` (sqrt|r.r| of the TRUE fp64 / complex128 residual of the x returned), `status` (0 reached the tolerance, 1 the budget ran
+    out, 2 a non-finite residual), `scales` (the power of two its residual was scaled by); `replacements`: the segments run"""
+
+    def __init__(self, iterations, resnorm, status, replacements, scales):
+        self.iterations, self.resnorm, self.status, self.replacements, self.scales = iterations, resnorm, status, int(replacements), scales
+
+    def __repr__(self):
+        return (f"MixedInfo(iterations={self.iterations.tolist()}, resnorm={self.resnorm.tolist()}, status={self.status.tolist()}, "
+                f"replacements={self.replacements}, scales={self.scales.tolist()})")
+
+
+class MixedSolver:
+    """Mixed-precision CG (cgamd_mixed_*, include/cgamd.h): the recurrence in float32 / complex64 on `.inner`, x and the true residual
+    in float64 / complex128 on `.outer`, joined by residual replacement with the search direction kept -- an fp64-accurate answer at
+    close to the fp32 loop's byte rate.  a_values: float64 or complex128.  flags: NO_GRAPH, MATRIX_ON_DEVICE (dtype= is then required;
+    the lo copy of the values is taken at creation, a changed matrix needs a new MixedSolver).  Preconditioners go on the inner
+    handle: `m.inner.set_preconditioner("jacobi")` or a diagonal; line preconditioners are refused by solve()."""
+
+    def __init__(self, ctx, size, non_zeros, a_values, a_pointers, a_cols, n_rhs=1, flags=0, dtype=None):
+        self.ctx = ctx
+        self._lib = _lib.load()
+        on_device = bool(int(flags) & _lib.MATRIX_ON_DEVICE)
+        if not on_device:
+            self.dtype = np.dtype(dtype) if dtype is not None else np.dtype(a_values.dtype)
+            a_values = np.ascontiguousarray(a_values, dtype=self.dtype)
+            a_pointers = np.ascontiguousarray(a_pointers, dtype=np.intc)
+            a_cols = np.ascontiguousarray(a_cols, dtype=np.intc)
+        else:
+            if dtype is None:
+                raise ValueError("dtype is required for device-resident matrices")
+            self.dtype = np.dtype(dtype)
+        self._keep = (a_values, a_pointers, a_cols)
+        self.size, self.n_rhs, self.non_zeros = int(size), int(n_rhs), int(non_zeros)
+        h = ctypes.c_void_p()
+        check(self._lib.cgamd_mixed_create(ctx.handle, _lib.DTYPE_CODE[self.dtype], self.size, self.non_zeros, ptr(a_values), ptr(a_pointers),
+                                           ptr(a_cols), self.n_rhs, int(flags), ctypes.byref(h)))
+        self.handle = h
+        lo = np.dtype(np.complex64 if self.dtype.kind == "c" else np.float32)
+        self.outer = self._wrap(self._lib.cgamd_mixed_outer(h), self.dtype, on_device)
+        self.inner = self._wrap(self._lib.cgamd_mixed_inner(h), lo, True)
+
+    def _wrap(self, handle, dtype, on_device):
+        s = Solver.__new__(Solver)
+        s.ctx, s._lib, s.batched, s.non_zeros, s._on_device, s.dtype = self.ctx, self._lib, False, self.non_zeros, on_device, dtype
+        s._keep, s.size, s.n_rhs, s._borrowed = (), self.size, self.n_rhs, True
+        s.handle = ctypes.c_void_p(handle)
+        return s
+
+    def solve(self, b, x0=None, tol=1e-10, maxit=1000, delta=0.1, max_segment=0, check_every=8):
+        """Solve to sqrt|r.r| < tol (a scalar or n_rhs values, ABSOLUTE, on the true residual) within `maxit` inner iterations; returns
+        (x, MixedInfo).  delta: the drop of the inner residual after which it is replaced; max_segment: cap of a segment's iterations
+        (0 = none).  The result does not depend on check_every."""
+        t = np.ascontiguousarray(np.asarray(tol, dtype=np.float64).reshape(-1))
+        if t.size not in (1, self.n_rhs):
+            raise ValueError(f"tol must be a scalar or have n_rhs = {self.n_rhs} entries, got {t.size}")
+        if not np.all(t > 0):
+            raise ValueError("every tolerance must be positive")
+        b = np.ascontiguousarray(np.asarray(b).reshape(-1), dtype=self.dtype)
+        if b.size != self.size * self.n_rhs:
+            raise ValueError(f"b holds {b.size} values, the handle takes n_rhs * size = {self.size * self.n_rhs}")
+        x = np.zeros_like(b) if x0 is None else np.array(np.asarray(x0).reshape(-1), dtype=self.dtype, order="C", copy=True)
+        if x.size != b.size:
+            raise ValueError(f"x0 holds {x.size} values, b {b.size}")
+        its, status = np.zeros(self.n_rhs, dtype=np.intc), np.zeros(self.n_rhs, dtype=np.intc)
+        res, scales = np.zeros(self.n_rhs), np.zeros(self.n_rhs)
+        repl = ctypes.c_int(0)
+        pd, pi = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+        check(self._lib.cgamd_mixed_solve(self.handle, ptr(b), ptr(x), 0, t.ctypes.data_as(pd), int(t.size), int(maxit), float(delta),
+                                          int(max_segment), int(check_every), its.ctypes.data_as(pi), res.ctypes.data_as(pd),
+                                          status.ctypes.data_as(pi), ctypes.byref(repl)))
+        check(self._lib.cgamd_mixed_scales(self.handle, scales.ctypes.data_as(pd)))
+        return x, MixedInfo(its, res, status, repl.value, scales)
+
+    def close(self):
+        if getattr(self, "handle", None) and getattr(self.ctx, "handle", None):
+            self._lib.cgamd_mixed_destroy(self.handle)
+        self.handle = None
+        for s in (getattr(self, "outer", None), getattr(self, "inner", None)):
+            if s is not None:
+                s.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def _shared_pattern(P):

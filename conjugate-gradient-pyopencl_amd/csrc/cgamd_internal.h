@@ -633,7 +633,33 @@ long long poisson2d_ptr(long long i, int N);
 // kind 0 rhs, 1 rhsL, 2 rhsA of helmFE_var.py:333-389 on an N x N node grid; b: N * N values of `dtype` (device)
 int launch_gen_rhs(int dtype, int kind, int N, double k, void *b, hipStream_t st);
 
+// ---- mixed-precision solve (mixed.hip, mixed.cpp): an fp32 / complex64 loop under an fp64 / complex128 x and true residual.
+// dtype_hi: CGAMD_F64 (lo = float) or CGAMD_C128 (lo = float2).  n values per right-hand side, grid = (G, nrhs), every sum in fixed
+// order; the two sides have leading dimensions of their own, both whole 16-byte packs where the 16-byte form is to run.
+// x_hi[i] += scale[r] * HI(x_lo[i]) for the right-hand sides with mask[r] != 0; the others are not read or written.  scale: powers of two
+int launch_mixed_accumulate(int dtype_hi, int n, void *x_hi, long long ld_hi, const void *x_lo, long long ld_lo, const double *scale,
+                            const int *mask, int nrhs, hipStream_t st);
+// r_lo[i] = LO(r_hi[i] * inv_scale[r]) for i < n, 0 for n <= i < ld_lo
+int launch_mixed_round_down(int dtype_hi, int n, const void *r_hi, long long ld_hi, void *r_lo, long long ld_lo, const double *inv_scale,
+                            int nrhs, hipStream_t st);
+// out[r] = sum |v_i|^2 in double (conjugated); partials: mixed_norm2_grid(n) doubles per right-hand side
+int mixed_norm2_grid(int dtype_hi, int n);
+int launch_mixed_norm2(int dtype_hi, int n, const void *v, long long ld, int nrhs, double *partials, double *out, hipStream_t st);
+// lo[j] = LO(hi[j]), count values: the inner handle's copy of the matrix
+int launch_mixed_round_values(int dtype_hi, long long count, const void *hi, void *lo, hipStream_t st);
+
 }  // namespace cgamd
+
+// ---- what mixed.cpp needs of its two handles beyond the C ABI (solver.cpp) ----
+#pragma GCC visibility push(hidden)
+namespace cgamd {
+const void *solver_matrix(cgamd_solver *s, const int **ptr, const int **cols);      // the device arrays the handle's SpMV reads
+int solver_restart(cgamd_solver *s);        // set_rhs again from the b and the x the handle holds (x as written through cgamd_solver_vector)
+int solver_set_rhs_ld(cgamd_solver *s, const void *b, long long ldb);                // set_rhs(b, NULL, on_device) with b at stride ldb
+int solver_replace_residual_ld(cgamd_solver *s, const void *r_new, long long ldr);  // cgamd_solver_replace_residual, r_new at stride ldr
+int solver_replace_planned(cgamd_solver *s);        // would replace_residual refuse this handle after its next set_rhs?  (changes nothing)
+}  // namespace cgamd
+#pragma GCC visibility pop
 
 // ---- context (shared by api.cpp / solver.cpp / dist.cpp) ---------------------------
 struct cgamd_ctx {

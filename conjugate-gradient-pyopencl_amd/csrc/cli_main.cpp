@@ -1,9 +1,12 @@
 // oclcgex -- command-line front end with the reference's argv (reference main.c:13-61):
 //     oclcgex <matrix.mtx> <nRHS> <isComplex> <nIterations> [--double] [--device N] [--quiet] [--history <file>] [--hermitian]
+//             [--mixed --tol T]
 // Matrix-Market file -> symmetric storage expanded -> CSR; b[r*n+i] = (r+1)*5, x0 = 0 (main.c:41-46).
 // --hermitian: the matrix is complex Hermitian positive definite (a `hermitian` file): CG with conjugated inner products
 // (CGAMD_HERMITIAN), the history then being r_k^H r_k.  Never chosen from the file's symmetry field: the default is the reference's
 // unconjugated recurrence for every file, as it always was.
+// --double --mixed --tol T: the mixed-precision solve (cgamd_mixed_solve: fp32 / complex64 loop, fp64 / complex128 x and residual
+// replacement) to T ||b|| within nIterations; prints every right-hand side's iterations, status and TRUE residual, and the replacements.
 // The reference prints nothing and discards x; this front end adds the residual history and timing.
 // Values are cast to single precision as the reference does (main.c:49-53) unless --double is given.
 // --history <file>: the whole residual history delta_k[r] = r_k.r_k (k = 0..nIterations, r < nRHS; what the reference computes and
@@ -19,12 +22,13 @@
 
 int main(int argc, char *argv[]) {
     if (argc < 5) {
-        fprintf(stderr, "Usage: %s <input matrix file> <number of RHS> <is complex> <number of iterations> [--double] [--device N] [--quiet] [--history <file>] [--hermitian]\n", argv[0]);
+        fprintf(stderr, "Usage: %s <input matrix file> <number of RHS> <is complex> <number of iterations> [--double] [--device N] [--quiet] [--history <file>] [--hermitian] [--mixed --tol T]\n", argv[0]);
         return 1;
     }
     const char *path = argv[1];
     const int nRHS = atoi(argv[2]), isComplex = atoi(argv[3]), nIterations = atoi(argv[4]);
-    bool dbl = false, quiet = false, hermitian = false;
+    bool dbl = false, quiet = false, hermitian = false, mixed = false;
+    double rel_tol = 0.;
     int device = 0;
     const char *history_path = nullptr;
     for (int i = 5; i < argc; ++i) {
@@ -33,6 +37,12 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--history") && i + 1 < argc) history_path = argv[++i];
         else if (!strcmp(argv[i], "--hermitian")) hermitian = true;
+        else if (!strcmp(argv[i], "--mixed")) mixed = true;
+        else if (!strcmp(argv[i], "--tol") && i + 1 < argc) rel_tol = atof(argv[++i]);
+    }
+    if (mixed && (!dbl || hermitian || !(rel_tol > 0.) || history_path)) {
+        fprintf(stderr, "--mixed needs --double and --tol T with T > 0, and goes with neither --hermitian nor --history\n");
+        return 1;
     }
     if (nRHS < 1 || nIterations < 0) { fprintf(stderr, "bad nRHS / nIterations\n"); return 1; }
 
@@ -63,7 +73,20 @@ int main(int argc, char *argv[]) {
 
     const auto t0 = std::chrono::steady_clock::now();
     int rc;
-    if (!hermitian) rc = cgamd_cg(dtype, n, nnz, a.data(), b.data(), ptr, cols, x.data(), nRHS, nIterations, hist.data(), device);
+    std::vector<int> m_its(nRHS, 0), m_status(nRHS, 0);
+    std::vector<double> m_res(nRHS, 0.), m_tol(nRHS, 0.);
+    int m_repl = 0;
+    if (mixed) {        // b is real: ||b|| = sqrt(n) * 5 (r + 1)
+        cgamd_ctx *ctx = nullptr;
+        cgamd_mixed *m = nullptr;
+        for (int r = 0; r < nRHS; ++r) m_tol[r] = rel_tol * std::sqrt((double)n) * (r + 1) * 5.0;
+        rc = cgamd_ctx_create(device, &ctx);
+        if (rc == CGAMD_OK) rc = cgamd_mixed_create(ctx, dtype, n, nnz, a.data(), ptr, cols, nRHS, 0, &m);
+        if (rc == CGAMD_OK) rc = cgamd_mixed_solve(m, b.data(), x.data(), 0, m_tol.data(), nRHS, nIterations, 0., 0, 0, m_its.data(), m_res.data(),
+                                                   m_status.data(), &m_repl);
+        cgamd_mixed_destroy(m);
+        if (ctx) cgamd_ctx_destroy(ctx);
+    } else if (!hermitian) rc = cgamd_cg(dtype, n, nnz, a.data(), b.data(), ptr, cols, x.data(), nRHS, nIterations, hist.data(), device);
     else {      // a handle of its own, created with the flag (cgamd_cg has no flags): the same upload, solve and download
         cgamd_ctx *ctx = nullptr;
         cgamd_solver *s = nullptr;
@@ -87,6 +110,17 @@ int main(int argc, char *argv[]) {
             fprintf(stderr, "error -- could not write the residual history to %s\n", history_path);
             return 3;
         }
+    }
+    if (mixed) {
+        if (!quiet) {
+            printf("matrix %s: n=%d nnz=%lld %s, nRHS=%d, mixed precision %s, at most %d iterations\n", path, n, nnz, fileComplex ? "complex" : "real",
+                   nRHS, dtype == CGAMD_F64 ? "f32 under f64" : "c64 under c128", nIterations);
+            for (int r = 0; r < nRHS; ++r)
+                printf("rhs %d: iterations %d status %d true residual %.6e tolerance %.6e\n", r, m_its[r], m_status[r], m_res[r], m_tol[r]);
+            printf("replacements %d\n", m_repl);
+            printf("wall %.3f s\n", sec);
+        }
+        return 0;
     }
     if (!quiet) {
         auto mag = [&](size_t idx) {

@@ -867,14 +867,17 @@ int cgamd_solver_destroy(cgamd_solver *s) {
     return CGAMD_OK;
 }
 
-int cgamd_solver_set_rhs(cgamd_solver *s, const void *b, const void *x0, int on_device) {
-    if (!s || !b) return fail(CGAMD_ERR_INVALID, "set_rhs: null argument");
+// set_rhs with the caller's blocks at leading dimension ldb (the public entry: `size`).  b == NULL (the mixed solve's outer handle,
+// mixed.cpp): b and x stay what the handle holds -- x as a caller of cgamd_solver_vector left it -- and the recurrence starts from
+// them with the same launches, so the bits are those of set_rhs(b, x)
+static int set_rhs_impl(cgamd_solver *s, const void *b, const void *x0, int on_device, long long ldb) {
     TuneScope ts(&s->tune);
     CG_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
     const size_t vbytes = (size_t)s->n * s->nrhs * dtype_size(s->dtype);
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     const bool rm = s->rm_ok && !precond_set(s);      // the preconditioned recurrence keeps the RHS-major kernels
+    if (rm && (!b || ldb != s->n_user)) return fail(CGAMD_ERR_STATE, "the handle keeps its right-hand sides interleaved (row-major layout)");
     if (rm != s->rm) destroy_graphs(s);         // captured launch sequences belong to one layout
     if (s->until_mode && s->fused2) destroy_graphs(s);      // (captured while the two-launch loop was set aside: iterate_until)
     s->until_mode = s->until_stopped = s->stop.armed = false;
@@ -901,11 +904,12 @@ int cgamd_solver_set_rhs(cgamd_solver *s, const void *b, const void *x0, int on_
         s->iters = 0;
         return CGAMD_OK;
     }
-    if (s->n != s->n_user) {     // caller's blocks are [nrhs][size]; the handle's carry the padding rows (b and x stay 0 there)
+    if (!b) {                    // (restart: b and x are in place)
+    } else if (s->n != ldb) {    // caller's blocks are [nrhs][size]; the handle's carry the padding rows (b and x stay 0 there)
         const size_t vs = dtype_size(s->dtype);
-        CG_HIP(hipMemcpy2DAsync(s->b, (size_t)s->n * vs, b, (size_t)s->n_user * vs, (size_t)s->n_user * vs, (size_t)s->nrhs, kind, st));
+        CG_HIP(hipMemcpy2DAsync(s->b, (size_t)s->n * vs, b, (size_t)ldb * vs, (size_t)s->n_user * vs, (size_t)s->nrhs, kind, st));
         CG_HIP(hipMemsetAsync(s->x, 0, vbytes, st));
-        if (x0) CG_HIP(hipMemcpy2DAsync(s->x, (size_t)s->n * vs, x0, (size_t)s->n_user * vs, (size_t)s->n_user * vs, (size_t)s->nrhs, kind, st));
+        if (x0) CG_HIP(hipMemcpy2DAsync(s->x, (size_t)s->n * vs, x0, (size_t)ldb * vs, (size_t)s->n_user * vs, (size_t)s->nrhs, kind, st));
     } else {
         CG_HIP(hipMemcpyAsync(s->b, b, vbytes, kind, st));
         if (x0) CG_HIP(hipMemcpyAsync(s->x, x0, vbytes, kind, st));
@@ -934,6 +938,10 @@ int cgamd_solver_set_rhs(cgamd_solver *s, const void *b, const void *x0, int on_
     s->rhs_set = true;
     s->iters = 0;
     return CGAMD_OK;
+}
+int cgamd_solver_set_rhs(cgamd_solver *s, const void *b, const void *x0, int on_device) {
+    if (!s || !b) return fail(CGAMD_ERR_INVALID, "set_rhs: null argument");
+    return set_rhs_impl(s, b, x0, on_device, s->n_user);
 }
 
 static void drop_tridiag(cgamd_solver *s) {
@@ -1302,6 +1310,72 @@ int cgamd_solver_iterate_tol(cgamd_solver *s, int maxIterations, double tol, int
 }
 
 
+// From here to the next set_rhs the handle runs its three / four-launch loop only, d in ONE buffer and final in memory (what
+// cgamd_solver_iterate_until and cgamd_solver_replace_residual share)
+static int enter_until_mode(cgamd_solver *s, hipStream_t st) {
+    if (s->until_mode) return CGAMD_OK;
+    if (fused2_now(s) && s->iters > 0) {
+        // the two-launch loop (and the resident loops that stand in for it) leave d = beta d + r of the last iteration to the
+        // next SpMV launch: done here with the beta that iteration recorded, the very expression (vaypx), into the one buffer
+        void *cur = dbuf(s, s->iters);
+        if (int rc = launch_aypx(s->dtype, s->n, s->r, cur, s->n, s->sc.beta, s->nrhs, st)) return rc;
+        if (cur != s->d) CG_HIP(hipMemcpyAsync(s->d, cur, (size_t)s->n * s->nrhs * dtype_size(s->dtype), hipMemcpyDeviceToDevice, st));
+    }
+    if (s->fused2) destroy_graphs(s);       // captured per parity of the two-launch loop
+    s->until_mode = true;
+    return CGAMD_OK;
+}
+
+// Residual replacement (include/cgamd.h; the "reliable updates" of van der Vorst and Ye): the recurrence goes on from (0, r_new, d).
+// What the entry does not serve is refused before anything on the handle changes.  planned: the question is asked BEFORE the set_rhs
+// that will precede the call (the mixed solve, mixed.cpp), so the layout is the one that set_rhs will decide
+static int step_not_capturing(cgamd_solver *s, const char *who);
+static int replace_refuses(const cgamd_solver *s, bool planned) {
+    const std::string who = "replace_residual: ";
+    if (!planned && !s->rhs_set) return fail(CGAMD_ERR_STATE, who + "call set_rhs first");
+    if (planned ? (s->rm_ok && !precond_set(s)) : s->rm)
+        return fail(CGAMD_ERR_STATE, who + "the handle keeps its right-hand sides interleaved (row-major layout)");
+    if (s->tri_on) return fail(CGAMD_ERR_STATE, who + "a tridiagonal / line preconditioner is set; the entry serves no preconditioner or a diagonal one");
+    if (s->herm) return herm_refuses("replace_residual", "which the entry does not serve");
+    if (s->nsys) return fail(CGAMD_ERR_STATE, who + "the handle is batched");
+    if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, who + "CGAMD_UNFUSED replays the reference's kernel sequence");
+    return CGAMD_OK;
+}
+// r_new at leading dimension ldr: `size` (the public entry), or the handle's own with zero padding rows (mixed.cpp)
+static int replace_residual_impl(cgamd_solver *s, const void *r_new, long long ldr) {
+    TuneScope ts(&s->tune);
+    if (int rc = replace_refuses(s, false)) return rc;
+    CG_HIP(hipSetDevice(s->ctx->device));
+    if (int rc = step_not_capturing(s, "replace_residual")) return rc;
+    hipStream_t st = s->ctx->stream;
+    const size_t vs = dtype_size(s->dtype), vbytes = (size_t)s->n * s->nrhs * vs;
+    if (int rc = enter_until_mode(s, st)) return rc;        // d = beta d + r of the OLD residual is part of the direction that is kept
+    if (ldr != s->n) {
+        CG_HIP(hipMemsetAsync(s->r, 0, vbytes, st));        // the padding rows
+        CG_HIP(hipMemcpy2DAsync(s->r, (size_t)s->n * vs, r_new, (size_t)ldr * vs, (size_t)s->n_user * vs, (size_t)s->nrhs, hipMemcpyDeviceToDevice, st));
+    } else {
+        CG_HIP(hipMemcpyAsync(s->r, r_new, vbytes, hipMemcpyDeviceToDevice, st));
+    }
+    CG_HIP(hipMemsetAsync(s->x, 0, vbytes, st));
+    // delta0 (rho0) by the launches of set_rhs, in their order; d is read and written by none of them
+    int rc;
+    if (s->mdiag) {     // z = m .* r lands in q, which is dead between iterations
+        if ((rc = launch_pcg_axpy2_dot2(s->dtype, true, s->n, s->q, s->x, s->q, s->r, s->mdiag, s->n, nullptr, s->nrhs, s->part_rz, s->part_rr,
+                                        s->vgrid, st, m_pitch(s)))) return rc;
+        if ((rc = launch_pcg_delta0(s->dtype, s->part_rz, s->part_rr, s->vgrid, s->nrhs, s->sc, s->rho2, st))) return rc;
+    } else {
+        if ((rc = launch_dot_partials(s->dtype, s->n, s->r, s->r, s->n, s->nrhs, s->part_rr, s->vgrid, st))) return rc;
+        if ((rc = launch_cg_delta0(s->dtype, s->part_rr, s->vgrid, s->nrhs, s->sc, st))) return rc;
+    }
+    s->iters = 0;
+    s->until_stopped = s->stop.armed = false;
+    return CGAMD_OK;
+}
+int cgamd_solver_replace_residual(cgamd_solver *s, const void *r_new) {
+    if (!s || !r_new) return fail(CGAMD_ERR_INVALID, "replace_residual: null argument");
+    return replace_residual_impl(s, r_new, s->n_user);
+}
+
 // Per-right-hand-side tolerance stop ON THE DEVICE for the launched loops (include/cgamd.h): every right-hand side stops in the
 // first iteration whose sqrt|r.r| fails >= tol[r] and is frozen there while the others run on -- the reference's sub-domain loop
 // `r[p] = CG(P[0], z[p].ravel(), tol=CGtol, maxit=CGMaxIT)` (p_h-PY_C-CL.py:1916-1921, 1338-1369) as ONE batched solve.  The
@@ -1330,17 +1404,7 @@ int cgamd_solver_iterate_until(cgamd_solver *s, int maxIterations, const double 
     hipStream_t st = s->ctx->stream;
     if (int rc = stop_run_alloc(s->stop, nr)) return rc;
     if (int rc = ensure_history(s, s->iters + maxIterations + 1)) return rc;
-    if (!s->until_mode) {       // from here to the next set_rhs the handle runs its three / four-launch loop
-        if (fused2_now(s) && s->iters > 0) {
-            // the two-launch loop (and the resident loops that stand in for it) leave d = beta d + r of the last iteration to the
-            // next SpMV launch: done here with the beta that iteration recorded, the very expression (vaypx), into the one buffer
-            void *cur = dbuf(s, s->iters);
-            if (int rc = launch_aypx(s->dtype, s->n, s->r, cur, s->n, s->sc.beta, nr, st)) return rc;
-            if (cur != s->d) CG_HIP(hipMemcpyAsync(s->d, cur, (size_t)s->n * nr * dtype_size(s->dtype), hipMemcpyDeviceToDevice, st));
-        }
-        if (s->fused2) destroy_graphs(s);       // captured per parity of the two-launch loop
-        s->until_mode = true;
-    }
+    if (int rc = enter_until_mode(s, st)) return rc;
     if (int rc = stop_run_arm(s->stop, tol, nTol, st)) return rc;
     const int chunk = checkEvery ? checkEvery : 8;
     const bool use_graph = !(s->flags & CGAMD_NO_GRAPH) && !s->graph_failed;
@@ -1466,7 +1530,8 @@ int cgamd_solver_ld(cgamd_solver *s) { return s ? s->n : -CGAMD_ERR_INVALID; }
 
 void *cgamd_solver_vector(cgamd_solver *s, int which) {
     if (!s) return nullptr;
-    switch (which) { case 0: return s->x; case 1: return s->r; case 2: return dbuf(s, s->iters); case 3: return s->q; default: return nullptr; }
+    // (d ping-pongs only while the two-launch loop runs: with a preconditioner set the direction is in the one buffer)
+    switch (which) { case 0: return s->x; case 1: return s->r; case 2: return fused2_now(s) ? dbuf(s, s->iters) : s->d; case 3: return s->q; default: return nullptr; }
 }
 
 int cgamd_solver_solve(cgamd_solver *s, const void *b, void *x, int nIterations, void *history) {
@@ -1691,3 +1756,21 @@ long long cgamd_solver_iter_moved_bytes(cgamd_solver *s) {
 }
 
 }  // extern "C"
+
+// ---- what the mixed-precision solve (mixed.cpp) needs of its two handles beyond the C ABI (cgamd_internal.h) ----
+namespace cgamd {
+const void *solver_matrix(cgamd_solver *s, const int **ptr, const int **cols) {
+    *ptr = s->ptr; *cols = s->cols;
+    return s->vals;
+}
+int solver_restart(cgamd_solver *s) {
+    if (!s->rhs_set) return fail(CGAMD_ERR_STATE, "mixed_solve: the outer handle has no right-hand side");
+    return set_rhs_impl(s, nullptr, nullptr, 1, s->n);
+}
+int solver_set_rhs_ld(cgamd_solver *s, const void *b, long long ldb) { return set_rhs_impl(s, b, nullptr, 1, ldb); }
+int solver_replace_residual_ld(cgamd_solver *s, const void *r_new, long long ldr) { return replace_residual_impl(s, r_new, ldr); }
+int solver_replace_planned(cgamd_solver *s) {
+    TuneScope ts(&s->tune);
+    return replace_refuses(s, true);
+}
+}  // namespace cgamd

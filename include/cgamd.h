@@ -250,6 +250,24 @@ int cgamd_solver_iterate_tol(cgamd_solver *s, int maxIterations, double tol, int
  * CGAMD_ERR_INVALID: NULL s / tol / iterations_run, nTol not in {1, nRHS}, a tolerance that is not > 0, negative maxIterations or
  * checkEvery.  CGAMD_ERR_STATE, the handle untouched: row-major layout (cgamd_solver_layout() == 1), CGAMD_UNFUSED, no set_rhs. */
 int cgamd_solver_iterate_until(cgamd_solver *s, int maxIterations, const double *tol, int nTol, int checkEvery, int *iterations_run);
+/* Residual replacement with the search direction kept (van der Vorst and Ye, "reliable updates"): hands a running handle a new
+ * residual without resetting its direction, so that a caller who keeps x and the true residual elsewhere -- in a wider type, see
+ * cgamd_mixed_solve -- goes on in the SAME Krylov space.  r_new: a DEVICE pointer to nRHS * size values of the handle's type at stride
+ * `size`.  Enqueued on the handle's stream (no host synchronisation).  It sets r := r_new (padding rows 0), x := 0, delta := r.r and,
+ * with a diagonal M, z = m .* r and rho := r.z; d STAYS AS IT IS.  The iteration counter is 0 again, the history restarts with row 0 =
+ * r.r, the stop record of cgamd_solver_iterate_until is disarmed and every right-hand side is active again.  The sums are taken by the
+ * launches, and in the order, by which cgamd_solver_set_rhs takes delta0 and rho0: history row 0 and delta are the bits a fresh
+ * handle shows after set_rhs(b = r_new, x0 = NULL).  cgamd_solver_iterate and _iterate_until then continue the recurrence from
+ * (0, r_new, d): the first beta is rho_1 / rho_0 of the NEW residual.
+ * From this call to the next cgamd_solver_set_rhs the handle runs the launched loop cgamd_solver_iterate_until runs, d in one buffer
+ * and final in memory.  A handle that has just iterated on its two-launch or a resident loop holds the direction of its last
+ * iteration and leaves d = beta d + r to the next SpMV launch: the call completes that step first (with the OLD residual, which is
+ * part of the direction that is kept), exactly as cgamd_solver_iterate_until does, and cgamd_solver_vector(s, 2) then names that buffer.
+ * Served: RHS-major handles (cgamd_solver_layout() == 0), all four value types, any nRHS, no preconditioner or a diagonal one,
+ * CGAMD_NO_GRAPH, CGAMD_MATRIX_ON_DEVICE.  CGAMD_ERR_STATE, the handle untouched: no cgamd_solver_set_rhs yet, row-major layout, a
+ * tridiagonal / line preconditioner, CGAMD_HERMITIAN on a complex type, batched handles, CGAMD_UNFUSED.  CGAMD_ERR_INVALID: NULL
+ * arguments, or a call while the handle's stream is being captured. */
+int cgamd_solver_replace_residual(cgamd_solver *s, const void *r_new);
 /* nIterations iterations with plain launches and a HIP event pair around every SpMV launch on the solver's stream;
  * returns the average in-loop SpMV duration (and optionally the average iteration time), in ms.  Synchronises. */
 int cgamd_solver_iterate_timed(cgamd_solver *s, int nIterations, float *spmv_ms_avg, float *iter_ms_avg);
@@ -466,6 +484,49 @@ long long cgamd_solver_iter_bytes(cgamd_solver *s, int fused);
  * reference's CSR byte model (an "effective" rate). */
 long long cgamd_solver_spmv_moved_bytes(cgamd_solver *s);
 long long cgamd_solver_iter_moved_bytes(cgamd_solver *s);
+
+/* ---- Mixed precision (csrc/mixed.cpp, csrc/mixed.hip): an fp64 / complex128 answer at close to the fp32 / complex64 loop's byte rate.
+ * The loops are bound by bytes and most of them are vectors; fp32 alone stalls near 1e-6 ||b||.  Here the recurrence runs in the lo
+ * type on the INNER handle while x and the true residual r = b - A x are kept in the hi type on the OUTER handle; whenever the inner
+ * residual has dropped by `delta` the inner x is added into the outer x, the true residual is recomputed, rounded down and handed
+ * back through cgamd_solver_replace_residual -- the search direction is kept, so no Krylov space is thrown away (a restarted iterative
+ * refinement took 1.3 - 1.7 x the fp64 iteration count on the Poisson systems tried, this scheme 1.0 - 1.17 x).
+ * cgamd_mixed_create: dtype_hi CGAMD_F64 (lo: CGAMD_F32) or CGAMD_C128 (lo: CGAMD_C64); any other dtype: CGAMD_ERR_INVALID.  flags:
+ * CGAMD_NO_GRAPH and CGAMD_MATRIX_ON_DEVICE; any other flag (CGAMD_UNFUSED, CGAMD_HERMITIAN, ...): CGAMD_ERR_INVALID.  Both are judged
+ * before a device is touched.  The outer handle is an ordinary handle of the hi type (with CGAMD_MATRIX_ON_DEVICE it borrows the
+ * caller's arrays); the inner handle is an ordinary lo handle on the values rounded once, on the device, at create -- a copy the mixed
+ * handle owns.  CHANGING THE BORROWED VALUES NEEDS A NEW MIXED HANDLE: the lo copy does not follow them (no refresh_values here).
+ * Preconditioners go on the inner handle through the existing entries, cgamd_solver_set_preconditioner(cgamd_mixed_inner(m), ...) and
+ * _jacobi; the handles cgamd_mixed_outer / _inner return belong to the mixed handle and die with it.
+ * cgamd_mixed_solve: b and x hold nRHS * size values of the hi type at stride `size`, host (on_device = 0) or device memory; x is
+ * in / out: the initial guess, then the solution.  tol: nTol = 1 or nRHS positive values (host).  Per right-hand side r:
+ *   1. r_hi = b - A x_hi and delta = r_hi . r_hi, the bits of cgamd_solver_set_rhs(outer, b, x_hi); res_r = sqrt|delta| (the
+ *      unconjugated measure cgamd_solver_iterate_until uses).  !(res_r >= tol_r): done, status 0 -- at the start: x is x0 unchanged,
+ *      iterations 0; a non-finite res_r: status 2.  s_r = 2^ilogb(sqrt(sum |r_hi,i|^2)), fixed for the whole solve.
+ *   2. first segment: cgamd_solver_set_rhs(inner, LO(r_hi / s_r)); 3. later ones: cgamd_solver_replace_residual(inner, LO(r_hi / s_r)).
+ *   4. cgamd_solver_iterate_until(inner, min(budget left, maxSegment), t, ...) with t_r = max(delta * start_r, tol_r / s_r), start_r =
+ *      sqrt|history row 0| of the segment.  A right-hand side that is done gets t_r = DBL_MAX: it stops after one iteration and is
+ *      masked out of step 5 (its x is not touched again).
+ *   5. x_hi += s_r * HI(x_lo) (exact product, one rounding), then step 1 with the new x_hi.  iterations[r] adds up the column's
+ *      iterations of the segments in which it was open; *replacements counts the segments.
+ *   6. The solve ends when every right-hand side is done, or when maxIterations is used up -- counted as the sum of the inner
+ *      handle's iteration counts over the segments; right-hand sides still open then have status 1, x is the accumulated iterate
+ *      and resnorm its TRUE residual norm.  resnorm[r] is always sqrt|r_hi . r_hi| of the x returned.
+ * delta: in [0, 1), 0 = 0.1.  maxSegment: 0 = no cap.  checkEvery: as in cgamd_solver_iterate_until; the result does not depend on
+ * it, and is the same bits from run to run.  The host synchronises once per segment, beside the waits of cgamd_solver_iterate_until.
+ * Errors: what the inner handle does not serve (a tridiagonal / line preconditioner, a row-major width) is returned as the
+ * CGAMD_ERR_STATE of cgamd_solver_replace_residual before anything is touched; x is unchanged on every error.  Not served: Hermitian,
+ * batched and row-partitioned handles, cgamd_solver_refresh_values on either handle.
+ * cgamd_mixed_scales: s_r of the last solve, nRHS doubles. */
+typedef struct cgamd_mixed cgamd_mixed;
+int cgamd_mixed_create(cgamd_ctx *ctx, int dtype_hi, int size, long long nnz, const void *aValues_hi, const int *aPointers,
+                       const int *aCols, int nRHS, int flags, cgamd_mixed **out);
+int cgamd_mixed_destroy(cgamd_mixed *m);
+cgamd_solver *cgamd_mixed_outer(cgamd_mixed *m);
+cgamd_solver *cgamd_mixed_inner(cgamd_mixed *m);
+int cgamd_mixed_solve(cgamd_mixed *m, const void *b, void *x, int on_device, const double *tol, int nTol, int maxIterations, double delta,
+                      int maxSegment, int checkEvery, int *iterations, double *resnorm, int *status, int *replacements);
+int cgamd_mixed_scales(cgamd_mixed *m, double *scales);
 
 /* one-call typed solve on host arrays: cg() generalised to all four dtypes, with history and status */
 int cgamd_cg(int dtype, int size, long long nnz, const void *aValues, const void *b, const int *aPointers,
