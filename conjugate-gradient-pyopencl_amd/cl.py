@@ -593,6 +593,11 @@ class Solver:
         """distinct row patterns when the SpMV reads one pattern byte per row (no per-non-zero bytes, no row pointers), else 0"""
         return self._lib.cgamd_solver_row_codes(self.handle)
 
+    @property
+    def row_pipe(self):
+        """row blocks whose gathers the row-coded SpMV keeps in flight per wave (1, 2 or 4); 0 when another form runs"""
+        return self._lib.cgamd_solver_row_pipe(self.handle)
+
     def iter_bytes(self, fused=False):
         return self._lib.cgamd_solver_iter_bytes(self.handle, int(fused))
 

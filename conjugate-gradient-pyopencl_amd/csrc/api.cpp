@@ -38,6 +38,8 @@ int cgamd_tune(const char *key, int value) {
     bool known = true;
     if (k == "dev.x_lag" && value != -1 && value != 0 && value != 1 && value != 2 && value != 4 && value != 8)
         return fail(CGAMD_ERR_INVALID, "tune: dev.x_lag takes -1 (default rule), 0 or 1 (off), 2, 4 or 8");
+    if (k == "dev.row_pipe" && value != 0 && value != 1 && value != 2 && value != 4)
+        return fail(CGAMD_ERR_INVALID, "tune: dev.row_pipe takes 0 (default rule), 1, 2 or 4");
     g_tune_generation.fetch_add(1, std::memory_order_relaxed);     // cached cg() handles were created under the old configuration
     tune_set([&](Tuning &g_tune) {
     // public keys (include/cgamd.h)
@@ -66,6 +68,7 @@ int cgamd_tune(const char *key, int value) {
     else if (k == "dev.joint_codes") g_tune.dev_joint_codes = value;
     else if (k == "dev.row_codes") g_tune.dev_row_codes = value;
     else if (k == "dev.row_codes_min_mb") g_tune.dev_row_codes_min_mb = value;
+    else if (k == "dev.row_pipe") g_tune.dev_row_pipe = value;
     else if (k == "dev.resident_lock") g_tune.resident_lock = value;
     else if (k == "dev.slab_cus") g_tune.slab_cus = value;
     else if (k == "dev.slab_trim") g_tune.slab_trim = value;

@@ -146,6 +146,7 @@ struct Tuning {
     int dev_joint_codes = 1;        // value-coded SpMV: one byte per non-zero naming the (offset, value) pair where at most 256 pairs occur (0 = two bytes: A/B)
     int dev_row_codes = 1;          // joint-coded SpMV: one byte per ROW naming its pattern where at most 256 row patterns occur (0 = joint codes: A/B)
     int dev_row_codes_min_mb = 32;  // ... for matrices above this size (its own threshold: index_codes_min_mb = 0 alone keeps the joint form)
+    int dev_row_pipe = 0;           // row-coded SpMV: row blocks whose gathers are in flight per wave, 1, 2 or 4 (0 = the default rule, row_pipe_depth)
     int dev_vc_pipe = 1;            // value-coded SpMV: gathers pipelined across the row blocks of a work-group (0 = one block at a time: A/B)
     int dev_generic_spmv = 0;       // 1: the generic chunked CSR stream for every matrix (the row-block kernels' fallback, tested against them)
     int resident_lock = 1;          // 0: no per-GPU serialisation of resident launches (ranks of ONE job sharing a GPU in a rehearsal)
@@ -174,6 +175,11 @@ struct Tuning {
 // created under, whatever other threads set meanwhile (reference threading model: one thread per device, each with its own
 // context and solver, p_h-PY_C-CL-multi-GPU.py:2149-2179).  tune() = the installed copy, or a per-thread snapshot of the
 // global one for handle-less entries.
+// the depth the row-coded SpMV launches with under dev.row_pipe = `knob`: 1, 2 and 4 as given, anything else the default rule --
+// by the size of a value, as measured (profiles/row_pipe/): 4-byte values all four blocks; 8-byte values one block at a
+// time (two measured 0.1 to 1.1 % faster in one process, but the plain benchmark did not separate it from the parent build by the
+// margin asked for, so the depth of 8-byte values stays at 1)
+inline int row_pipe_depth(int knob, size_t value_bytes) { return knob == 1 || knob == 2 || knob == 4 ? knob : value_bytes <= 4 ? 4 : 1; }
 extern Tuning g_tune;
 Tuning tune_snapshot();
 const Tuning &tune();

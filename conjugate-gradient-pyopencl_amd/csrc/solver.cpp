@@ -1741,6 +1741,7 @@ long long cgamd_solver_spmv_moved_bytes(cgamd_solver *s) {
 int cgamd_solver_value_codes(cgamd_solver *s) { return s ? s->n_values : -CGAMD_ERR_INVALID; }
 int cgamd_solver_joint_codes(cgamd_solver *s) { return s ? (joint_form(s) ? s->n_pairs : 0) : -CGAMD_ERR_INVALID; }
 int cgamd_solver_row_codes(cgamd_solver *s) { return s ? (row_form(s) ? s->n_user_patterns : 0) : -CGAMD_ERR_INVALID; }
+int cgamd_solver_row_pipe(cgamd_solver *s) { return s ? (row_form(s) ? row_pipe_depth(s->tune.dev_row_pipe, dtype_size(s->dtype)) : 0) : -CGAMD_ERR_INVALID; }
 long long cgamd_solver_iter_moved_bytes(cgamd_solver *s) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);

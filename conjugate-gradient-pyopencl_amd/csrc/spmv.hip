@@ -585,12 +585,9 @@ __global__ __launch_bounds__(BLOCK) void spmv_rowblock_vcp_kernel(SpmvArgs<T> a)
 // barrier per row block in front of the gathers.  The dictionary (only the patterns that occur: 27 for the 7-point Laplacian, 2.7 KB
 // in fp64) goes into LDS once per work-group -- the one barrier before the walk -- which takes kVcBlocks row blocks like the joint
 // form (same schedule, same grid).
-// A wave whose 64 rows are all live and share ONE pattern (three quarters of the waves of the 250 x 200 x 200 grid) walks it with
-// wave-uniform length, offsets and values: exactly `len` steps, each one contiguous 64-value load and one multiply-add, no masked
-// slot and no per-entry look-up.  Every other wave (pattern changes inside it, the ragged end of the matrix) looks its lanes'
-// patterns up in LDS and walks 7 masked slots as the joint kernel does.  Both do sum = vfma(val_j, x[row + off_j], sum) from zero in
-// stored order on the bits of the joint dictionary: same y, same d.q partials (one per 256-row block, the tree of block_sum<256>;
-// the four blocks' trees meet behind one barrier, as in the vc kernel) as every other one-lane-per-row form.
+// Every lane looks its row's pattern up in LDS and walks 7 masked slots as the joint kernel does: sum = vfma(val_j, x[row + off_j],
+// sum) from zero in stored order on the bits of the joint dictionary: same y, same d.q partials (one per 256-row block, the tree of
+// block_sum<256>; the four blocks' trees meet behind one barrier, as in the vc kernel) as every other one-lane-per-row form.
 // -------------------------------------------------------------------------------------------------
 template <typename T> struct RowcodeArgs {
     int n, row_blocks, cycle, n_patterns;
@@ -604,12 +601,27 @@ template <typename T> struct RowcodeArgs {
     const T *rdict_val;             // [256][8]
 };
 constexpr int kRowSlots = 7;      // longest coded row
-template <typename T, int BLOCK, bool NT, bool FUSE_DOT>
+// PIPELINED like the vcp kernel, and cheaper to have: all four blocks' gather addresses follow from four code bytes that sit in registers
+// before the barrier.  The walk is split into issue(i) -- the pattern's offsets out of LDS, the block's d load and its 7 gathers -- and
+// consume(i) -- the pattern's values out of LDS again, the sum, the y store and the wave's d.q sum; DEPTH blocks' gathers are in flight
+// per wave: 1 = issue(0) consume(0) issue(1) ..., 2 = the vcp kernel's order, 4 = every issue, then every consume.  vmcnt
+// retires in order: consuming block i does not wait for block i + 1.
+// One branch-free walk serves every wave: slot j of a row of `len` entries gathers x[row + off_j] for j < len and the row's own entry
+// otherwise, and sum = vsel(j < len, vfma(val_j, x_j, sum), sum) has the bits of an `if (j < len)` chain.  A wave whose rows share
+// one pattern (three quarters of the waves of the 250 x 200 x 200 grid) reads the dictionary at one LDS address (a broadcast) and
+// gathers 64 contiguous values per slot.  Live across the pipeline: xv[DEPTH][7], dv[DEPTH], the codes and the lengths; offsets live
+// only inside issue().
+// Measured (profiles/row_pipe/): the first form of this kernel -- such a uniform wave on a path of its own with
+// wave-uniform length, offsets and values, behind a scalar branch per block; one block at a time; fp64 68 VGPRs, 7 waves per SIMD --
+// took 60.3 us on the headline; this one 57.2 / 56.0 / 58.1 us at depth 1 / 2 / 4 (fp64 46 / 62 / 90 VGPRs, 8 / 8 / 5 waves per SIMD).
+// The chain of four gather round trips is not what bounds it; the default depth is row_pipe_depth()'s.
+template <typename T, int BLOCK, bool NT, bool FUSE_DOT, int DEPTH>
 __global__ __launch_bounds__(BLOCK) void spmv_rowcode_kernel(RowcodeArgs<T> a) {
     using A = typename VT<T>::acc;
     extern __shared__ __attribute__((aligned(16))) char dyn_smem[];       // [np][8] values | [np][8] byte offsets | [np] lengths
     __shared__ A red[kVcBlocks][BLOCK / kWave];
     static_assert(BLOCK == 256, "row blocks of 256 rows");
+    static_assert(DEPTH == 1 || DEPTH == 2 || DEPTH == 4, "blocks in flight");
     const int t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
     const int supers = (a.row_blocks + kVcBlocks - 1) / kVcBlocks;
     const int srb = rowblock_of(blockIdx.x, supers, a.cycle);
@@ -630,62 +642,62 @@ __global__ __launch_bounds__(BLOCK) void spmv_rowcode_kernel(RowcodeArgs<T> a) {
     if (t < np) slen[t] = a.rdict_len[t];         // (at most 256 patterns)
     const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(a.x), 0, 0x7ffffffc, 0x00020000);
     [[maybe_unused]] const __amdgpu_buffer_rsrc_t xrs_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(FUSE_DOT ? a.dvec : a.x), 0, 0x7ffffffc, 0x00020000);
+    // the code bytes are awaited HERE, in every wave, with the dictionary (whose staging waits for everything in the waves that take
+    // part in it): the compiler then places no wait for a code byte between the gathers of two blocks
+    __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
-    [[maybe_unused]] A dotw[kVcBlocks];
-#pragma unroll
-    for (int i = 0; i < kVcBlocks; ++i) {
-        dotw[i] = vzero<A>();
-        if (i >= nb) continue;                      // (uniform; the last work-group of the matrix may hold fewer row blocks)
+    // one block's gathers in flight: the values of x, d and the row's length (0: a row past the matrix, or a block past the last one
+    // of the matrix in its last work-group -- its slots gather the clamped row's own entry and nothing of it is stored)
+    struct Gath { T xv[kRowSlots]; T dv; int len; };
+    auto issue = [&](int i) -> Gath {
+        Gath g;
         const int row = (rb0 + i) * BLOCK + t;
-        const bool live = row < a.n;
         const unsigned row8 = (unsigned)min(row, a.n - 1) * (unsigned)sizeof(T);
-        [[maybe_unused]] T dv = vzero<T>();
-        if (FUSE_DOT) dv = buf_gather<T>(xrs_d, row8);
-        const int c = code[i], c0 = __builtin_amdgcn_readfirstlane(c);
-        T sum = vzero<T>();
-        const bool uniform = __all(live && c == c0);
-        // the pattern's 8 offset slots in two 16-byte LDS reads and its values in 16-byte reads, all issued before the first gather (a
-        // uniform wave reads at one address: a broadcast); slots past the row's end hold 0 in the dictionary
-        const int cc = uniform ? c0 : c;
-        const int len = uniform ? __builtin_amdgcn_readfirstlane(slen[c0]) : (live ? slen[c] : 0);
-        int po[8];
-        T pv[8];
+        const int c = code[i];
+        g.len = (row < a.n && i < nb) ? slen[c] : 0;
+        // the pattern's 8 offset slots in two 16-byte LDS reads (slots past the row's end hold 0 in the dictionary)
+        const i32x4 o0 = *reinterpret_cast<const i32x4 *>(soff + c * 8), o1 = *reinterpret_cast<const i32x4 *>(soff + c * 8 + 4);
+        const int po[8] = {o0.x, o0.y, o0.z, o0.w, o1.x, o1.y, o1.z, o1.w};
+        g.dv = vzero<T>();
+        if (FUSE_DOT) g.dv = buf_gather<T>(xrs_d, row8);
+#pragma unroll
+        for (int j = 0; j < kRowSlots; ++j) g.xv[j] = buf_gather<T>(xrs, j < g.len ? row8 + (unsigned)po[j] : row8);
+        return g;
+    };
+    [[maybe_unused]] A dotw[kVcBlocks];
+    auto consume = [&](int i, const Gath &g) {
+        const int row = (rb0 + i) * BLOCK + t;
+        const int c = code[i];
+        T pv[8];                                    // the pattern's values in 16-byte LDS reads
         {
-            const i32x4 o0 = *reinterpret_cast<const i32x4 *>(soff + cc * 8), o1 = *reinterpret_cast<const i32x4 *>(soff + cc * 8 + 4);
-            po[0] = o0.x; po[1] = o0.y; po[2] = o0.z; po[3] = o0.w; po[4] = o1.x; po[5] = o1.y; po[6] = o1.z; po[7] = o1.w;
             using V = typename Chunk16<T>::V;
             constexpr int EPC = 16 / (int)sizeof(T);
 #pragma unroll
             for (int k = 0; k < 8 / EPC; ++k) {
-                const V v = *reinterpret_cast<const V *>(sval + cc * 8 + k * EPC);
+                const V v = *reinterpret_cast<const V *>(sval + c * 8 + k * EPC);
                 __builtin_memcpy(&pv[k * EPC], &v, 16);
             }
         }
-        T xv[kRowSlots];
-        if (uniform) {
-            // one pattern for the whole wave: length, offsets and values are wave-uniform; exactly len steps, no masked slot
+        T sum = vzero<T>();
 #pragma unroll
-            for (int j = 0; j < kRowSlots; ++j)
-                if (j < len) xv[j] = buf_gather<T>(xrs, row8 + (unsigned)po[j]);
-#pragma unroll
-            for (int j = 0; j < kRowSlots; ++j)
-                if (j < len) sum = vfma(pv[j], xv[j], sum);
-        } else {
-            // each lane its own pattern; slots past the row's end gather the row's own entry and are dropped
-#pragma unroll
-            for (int j = 0; j < kRowSlots; ++j) xv[j] = buf_gather<T>(xrs, j < len ? row8 + (unsigned)po[j] : row8);
-#pragma unroll
-            for (int j = 0; j < kRowSlots; ++j) {
-                const T nxt = vfma(pv[j], xv[j], sum);
-                sum = vsel(j < len, nxt, sum);
-            }
+        for (int j = 0; j < kRowSlots; ++j) {
+            const T nxt = vfma(pv[j], g.xv[j], sum);
+            sum = vsel(j < g.len, nxt, sum);
         }
         A dot1 = vzero<A>();
-        if (live) {
+        if (row < a.n && i < nb) {
             a.y[row] = sum;
-            if (FUSE_DOT) dot1 = to_acc(vmul(dv, sum));
+            if (FUSE_DOT) dot1 = to_acc(vmul(g.dv, sum));
         }
         if (FUSE_DOT) dotw[i] = wave_sum(dot1);
+    };
+    Gath g[DEPTH];
+#pragma unroll
+    for (int i = 0; i < DEPTH; ++i) g[i] = issue(i);
+#pragma unroll
+    for (int i = 0; i < kVcBlocks; ++i) {
+        consume(i, g[i % DEPTH]);
+        if (i + DEPTH < kVcBlocks) g[i % DEPTH] = issue(i + DEPTH);
     }
     if (FUSE_DOT) {                         // block_sum<256> of every block behind one barrier (same tree, same order; red is written once)
         if (lane == 0) {
@@ -1168,13 +1180,22 @@ static int spmv_impl(const SpmvPlan &plan, int n, long long nnz, const void *val
                     ra.rdict_val = static_cast<const T *>(plan.rdict_val);
                     const size_t ldsr = (size_t)plan.n_patterns * (8 * sizeof(T) + 8 * sizeof(int) + sizeof(int));
                     record_form(7, true, unroll, 8, 3, nt, fuse, false, gvc.x, plan.row_blocks);
-                    if (nt) {
-                        if (fuse) CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, true, true>), gvc, block, ldsr, st, ra);
-                        else CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, true, false>), gvc, block, ldsr, st, ra);
-                    } else {
-                        if (fuse) CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, false, true>), gvc, block, ldsr, st, ra);
-                        else CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, false, false>), gvc, block, ldsr, st, ra);
-                    }
+#define CG_RC(DEPTH)                                                                                                    \
+    do {                                                                                                                \
+        if (nt) {                                                                                                       \
+            if (fuse) CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, true, true, DEPTH>), gvc, block, ldsr, st, ra);      \
+            else CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, true, false, DEPTH>), gvc, block, ldsr, st, ra);          \
+        } else {                                                                                                        \
+            if (fuse) CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, false, true, DEPTH>), gvc, block, ldsr, st, ra);     \
+            else CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, false, false, DEPTH>), gvc, block, ldsr, st, ra);         \
+        }                                                                                                               \
+    } while (0)
+                    // row blocks whose gathers are in flight per wave (dev.row_pipe; 0 = the default rule)
+                    const int depth = row_pipe_depth(tune().dev_row_pipe, sizeof(T));
+                    if (depth == 1) CG_RC(1);
+                    else if (depth == 2) CG_RC(2);
+                    else CG_RC(4);
+#undef CG_RC
                     return check_launch("spmv_rowcode");
                 }
                 if (joint) { a.codes = plan.jcodes; a.dict = plan.jdict_off; a.vdict = static_cast<const T *>(plan.jdict_val); a.vcodes = nullptr; }

@@ -473,6 +473,10 @@ int cgamd_solver_joint_codes(cgamd_solver *s);
  * patterns.  Same products in the same order: same bits.  0: another form runs (cgamd_tune("dev.row_codes", 0) keeps the joint one).
  * cgamd_last_spmv_form reports it as family 7, [2] batch length, [3] 8, [4] 3. */
 int cgamd_solver_row_codes(cgamd_solver *s);
+/* the number of row blocks (1, 2 or 4 of the 4 a work-group takes) whose gathers the handle's row-coded SpMV keeps in flight per wave:
+ * the default, or what cgamd_tune("dev.row_pipe") forced when the handle was created.  Every depth forms the same bits.  0: the handle
+ * does not run the row-coded form. */
+int cgamd_solver_row_pipe(cgamd_solver *s);
 int cgamd_transpose(cgamd_ctx *ctx, int dtype, int rows, int cols, const void *in, void *out);
 /* algorithmic HBM bytes of one SpMV / one CG iteration of this solver (SURVEY §8d formulae: 14 vector passes for the
  * reference's op structure, 11 for its "fused minimum"; the default loop here moves 10) */
