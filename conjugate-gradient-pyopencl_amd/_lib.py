@@ -91,6 +91,11 @@ def load():
         "cgamd_solver_set_preconditioner_batched": (ci, [vp, vp, ci]),
         "cgamd_solver_set_preconditioner_batched_jacobi": (ci, [vp]),
         "cgamd_solver_set_preconditioner_batched_line": (ci, [vp, ci]),
+        "cgamd_solver_set_preconditioner_multigrid": (ci, [vp, ci, ci, ci, ci, ctypes.c_double, ci]),
+        "cgamd_solver_mg_levels": (ci, [vp]),
+        "cgamd_solver_mg_level": (ci, [vp, ci, ctypes.POINTER(ll)]),
+        "cgamd_solver_mg_level_matrix": (ci, [vp, ci, vp, vp, vp]),
+        "cgamd_solver_mg_apply": (ci, [vp, vp, vp]),
         "cgamd_solver_preconditioner_source": (ci, [vp]),
         "cgamd_solver_iterate": (ci, [vp, ci]),
         "cgamd_solver_iterate_timed": (ci, [vp, ci, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),

@@ -377,6 +377,11 @@ class Solver:
         * ("line", stride): the tridiagonal M of the handle's own matrix, its entries at column - row in {-stride, 0, +stride}
           (stride 1: x-lines, nx: y-lines, nx * ny: z-lines), extracted, factored and planned on the device
           (cgamd_solver_set_preconditioner_line); the spsolve branch below without the host work.  Both follow reload_matrix.
+        * ("multigrid", (nx, ny, nz)) or ("multigrid", (nx, ny, nz), {"smooth_steps": 1, "over_correction": 1.6, "min_rows": 512}):
+          one aggregation-multigrid V-cycle on the grid the rows number x fastest (nx * ny * nz == size; 2-D: (nx, ny) or nz = 1),
+          the hierarchy built on the device from the handle's matrix (cgamd_solver_set_preconditioner_multigrid): the
+          preconditioner for isotropic stencil systems, where it cuts the iteration count by a multiple.  Follows reload_matrix and
+          refresh_values.  mg_levels() lists the hierarchy.
         * a 1-D array (1/diag(A) for Jacobi), a device buffer, or a scipy sparse M with nnz <= size: the diagonal branch,
           z = M.dot(r);
         * a scipy sparse M with nnz > size: the spsolve branch, z solves M z = r.  M must be tridiagonal along one grid axis: all
@@ -405,6 +410,15 @@ class Solver:
         if isinstance(m, tuple) and len(m) == 2 and m[0] == "line":
             check(self._lib.cgamd_solver_set_preconditioner_line(self.handle, int(m[1])))
             return
+        if isinstance(m, tuple) and len(m) in (2, 3) and m[0] == "multigrid":
+            dims = tuple(int(d) for d in m[1]) + (1,) * (3 - len(m[1]))
+            opts = dict(m[2]) if len(m) == 3 else {}
+            unknown = set(opts) - {"smooth_steps", "over_correction", "min_rows"}
+            if len(dims) != 3 or unknown:
+                raise ValueError('("multigrid", (nx, ny, nz)[, {"smooth_steps": 1, "over_correction": 1.6, "min_rows": 512}])')
+            check(self._lib.cgamd_solver_set_preconditioner_multigrid(self.handle, dims[0], dims[1], dims[2], int(opts.get("smooth_steps", 0)),
+                                                                      float(opts.get("over_correction", 0.0)), int(opts.get("min_rows", 0))))
+            return
         if hasattr(m, "diagonal") and hasattr(m, "nnz"):          # scipy sparse, as the reference passes it
             if m.shape != (self.size, self.size):
                 raise ValueError("preconditioner M must be size x size")
@@ -418,6 +432,37 @@ class Solver:
             if m.size != self.size:
                 raise ValueError("preconditioner diagonal must have `size` entries")
         check(self._lib.cgamd_solver_set_preconditioner(self.handle, ptr(m), int(on_device)))
+
+    def mg_levels(self):
+        """the multigrid hierarchy in force: a list of dicts (rows, nnz, nx, ny, nz, lmax), level 0 first; [] without one"""
+        out = []
+        for l in range(max(0, self._lib.cgamd_solver_mg_levels(self.handle))):
+            info = (ctypes.c_longlong * 6)()
+            check(self._lib.cgamd_solver_mg_level(self.handle, l, info))
+            out.append({"rows": int(info[0]), "nnz": int(info[1]), "nx": int(info[2]), "ny": int(info[3]), "nz": int(info[4]),
+                        "lmax": float(np.array([info[5]], dtype=np.int64).view(np.float64)[0])})
+        return out
+
+    def mg_level_matrix(self, level):
+        """(indptr, indices, data) of a level of the multigrid hierarchy, copied to the host (development accessor: tests)"""
+        info = self.mg_levels()[level]
+        ip, ix = np.empty(info["rows"] + 1, np.int32), np.empty(info["nnz"], np.int32)
+        da = np.empty(info["nnz"], self.dtype)
+        check(self._lib.cgamd_solver_mg_level_matrix(self.handle, int(level), ptr(ip), ptr(ix), ptr(da)))
+        return ip, ix, da
+
+    def mg_apply(self, r):
+        """z = one V-cycle of r: n_rhs * size values, host array in and out (development accessor: tests)"""
+        r = np.ascontiguousarray(np.asarray(r).reshape(-1), dtype=self.dtype)
+        if r.size != self.n_rhs * self.size:
+            raise ValueError("mg_apply takes n_rhs * size values")
+        rd, zd = DeviceBuffer(self.ctx, hostbuf=r), DeviceBuffer(self.ctx, nbytes=r.nbytes, dtype=self.dtype)
+        try:
+            check(self._lib.cgamd_solver_mg_apply(self.handle, ptr(rd), ptr(zd)))
+            return zd.get()
+        finally:
+            rd.release()
+            zd.release()
 
     def _set_tridiag(self, m):
         """the three diagonals of a sparse M with nnz > size into cgamd_solver_set_preconditioner_tridiag, or, when they lie at
@@ -712,7 +757,7 @@ class Solver:
 
     def pcg(self, b, M=None, x0=None, tol=1e-6, maxit=1000, check_every=8):
         """`PCG(A, b, M, x, tol, maxit)` of the reference (helmFE_var.py:546-586) for M = None, a diagonal M, a tridiagonal
-        sparse M along any grid axis (the spsolve branch) or "jacobi" / ("line", stride) built from the matrix (see set_preconditioner): stops when sqrt(|r.r|) < tol, returns (x, i) with i the 0-based
+        sparse M along any grid axis (the spsolve branch) or "jacobi" / ("line", stride) / ("multigrid", dims) built from the matrix (see set_preconditioner): stops when sqrt(|r.r|) < tol, returns (x, i) with i the 0-based
         index of the last iteration run, like the reference.  The residual history stays on the device and is read back every
         `check_every` iterations; x is taken at the first iteration that met the tolerance by re-running exactly that many
         iterations when the check overshot it."""

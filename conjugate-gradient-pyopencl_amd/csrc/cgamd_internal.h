@@ -1,4 +1,4 @@
-// Host-side internal interfaces between the kernel launchers (spmv.hip, vector.hip, p2p.hip, cg1.hip, index_codes.hip, rowmajor.hip, resident.hip, slab.hip), the solver
+// Host-side internal interfaces between the kernel launchers (spmv.hip, vector.hip, p2p.hip, cg1.hip, index_codes.hip, rowmajor.hip, resident.hip, slab.hip, multigrid.hip), the solver
 // (solver.cpp), the C ABI (api.cpp) and the multi-GPU loop (dist.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -562,6 +562,45 @@ int jacobi_build_from_matrix_batched(hipStream_t st, int dt, int nu, int nsys, l
 // m[i] = 1 / A[i][i] (m: nu device values of the caller); CGAMD_ERR_INVALID names the smallest bad row
 int jacobi_build_from_matrix(hipStream_t st, int dt, int nu, const std::string &who, const void *vals, const int *ptr, const int *cols,
                              void *m);
+// ---- aggregation multigrid preconditioner on grid systems (multigrid.hip, multigrid_setup.cpp) ----
+// a grid numbered x fastest and the grid of its 2 x 2 x 2 aggregates: fine node (x, y, z) -> coarse node (x >> 1, y >> 1, z >> 1)
+struct MgGrid { int nx = 1, ny = 1, nz = 1, cnx = 1, cny = 1, cnz = 1; };
+constexpr int kMgMaxRow = 64;       // most distinct columns of a coarse row
+constexpr int kMgMaxLevels = 16;
+// count[I] <- distinct coarse columns of coarse row I (nc rows); *err (preset to all ones) <- the smallest row with more than kMgMaxRow
+int launch_mg_count(const MgGrid &g, int nc, const int *ptr, const int *cols, int *count, unsigned long long *err, hipStream_t st);
+// n counts -> n + 1 row pointers in place (one work-group); *overflow (preset to 0) <- 1 when the total does not fit an int
+int launch_mg_scan(int n, int *counts_to_ptr, int *overflow, hipStream_t st);
+// the coarse columns (ascending) and values: fine rows ascending, entries in stored order, summed in the accumulator type, rounded once
+int launch_mg_fill(int dtype, const MgGrid &g, int nc, const void *vals, const int *ptr, const int *cols, const int *ptrc, int *colsc,
+                   void *valsc, hipStream_t st);
+// *out (preset to 0) <- the bits of max_i |dinv_i| sum_j |a_ij| (double)
+int launch_mg_gershgorin(int dtype, int n, const void *vals, const int *ptr, const void *dinv, unsigned long long *out, hipStream_t st);
+// one Chebyshev step on n rows of nrhs vectors at stride ld (mode 0: from x = 0, 1: first step from x != 0, 2: a later step; w = A x)
+int launch_mg_cheb(int dtype, int mode, int n, long long ld, int nrhs, const void *dinv, const void *b, const void *w, void *d, void *x,
+                   double c0, double c1, bool store_d, hipStream_t st);
+// bc = P^T (b - w), then the coarse level's first smoothing step from zero: xc = (dc =) c1 dinvc bc
+int launch_mg_restrict(int dtype, const MgGrid &g, int nc, long long ldf, long long ldc, int nrhs, const void *b, const void *w, void *bc,
+                       const void *dinvc, void *xc, void *dc, double c1, bool store_d, hipStream_t st);
+// x += omega P e on the nf rows of the fine grid
+int launch_mg_prolong(int dtype, const MgGrid &g, int nf, long long ldf, long long ldc, int nrhs, const void *e, void *x, double omega,
+                      hipStream_t st);
+// The hierarchy of one handle.  Level 0 borrows the handle's matrix and the plan of its SpMV (codes included: build again whenever
+// they change); the coarse levels own theirs.  nu = the caller's rows, n = with the padding rows (z = 0 there)
+struct MgHierarchy;
+struct MgParams { int nx = 1, ny = 1, nz = 1, smooth_steps = 1, min_rows = 512; double omega = 1.6; };
+int mg_build(hipStream_t st, int dt, int nu, int n, int nrhs, const SpmvPlan &plan0, long long nnz, const void *vals, const int *ptr,
+             const int *cols, const MgParams &p, const std::string &who, MgHierarchy **out);
+void mg_free(MgHierarchy *h);
+// z = M^-1 r: nrhs vectors of n rows at stride n each, the padding rows of r zero; a linear chain of launches on st
+int mg_vcycle(const MgHierarchy *h, const void *r, void *z, hipStream_t st);
+// what one V-cycle launches and moves: kernels, fine-level SpMVs (priced by the handle), and the bytes of everything else
+struct MgCost { int launches = 0, spmv0 = 0; long long bytes = 0; };
+MgCost mg_cost(const MgHierarchy *h);
+int mg_levels(const MgHierarchy *h);
+// info: rows, nnz, nx, ny, nz, the bits of the double lmax
+int mg_level_info(const MgHierarchy *h, int level, long long info[6]);
+int mg_level_matrix(const MgHierarchy *h, int level, int *ptr, int *cols, void *vals, hipStream_t st);
 // ---- PCG of the row-partitioned loop (vector.hip, p2p.hip): z lives in q's storage for every preconditioner; part = [2][P] partials
 // (r.z, then r.r); rho2 = two-entry parity buffer of rho = r.z (entry iter & 1), delta holds rho for cg_alpha
 // r -= alpha q ; z = m .* r (stored over q) ; partials of r.z and r.r

@@ -1,0 +1,253 @@
+// Aggregation multigrid preconditioner on grid systems: the hierarchy of a handle and its V-cycle as a chain of launches
+// (cgamd_solver_set_preconditioner_multigrid; kernels in multigrid.hip, the algorithm stated in include/cgamd.h and DESIGN.md).
+// The host reads back single words only: the coarse non-zero count, the error words and the Gershgorin bound of every level.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "cgamd_internal.h"
+
+namespace cgamd {
+
+namespace {
+struct MgLevel {
+    int n = 0, nu = 0;          // rows the kernels work on (level 0: with the padding rows) / rows of the grid
+    long long nnz = 0, ld = 0;
+    MgGrid grid;                // this level's dims (nx, ny, nz) and its aggregates' (cnx, cny, cnz)
+    const void *vals = nullptr;
+    const int *ptr = nullptr, *cols = nullptr;
+    SpmvPlan plan;
+    void *dinv = nullptr;
+    double lmax = 0.;
+    void *x = nullptr, *b = nullptr, *w = nullptr, *d = nullptr;      // level 0: x and b are the caller's z and r
+    int steps = 1;
+    std::vector<double> c0, c1; // Chebyshev coefficients of step k (c0[0] unused)
+};
+}  // namespace
+
+struct MgHierarchy {
+    int dtype = 0, nrhs = 1;
+    MgParams p;
+    std::vector<MgLevel> lv;
+    std::vector<void *> owned;
+    ~MgHierarchy() {
+        for (void *q : owned)
+            if (q) (void)hipFree(q);
+    }
+    int get(void **q, size_t bytes, const char *what) {
+        const hipError_t e = hipMalloc(q, bytes ? bytes : 16);
+        if (e != hipSuccess)
+            return fail(CGAMD_ERR_ALLOC, std::string("hipMalloc(multigrid ") + what + ", " + std::to_string(bytes) + " B): " + hipGetErrorString(e));
+        owned.push_back(*q);
+        return CGAMD_OK;
+    }
+};
+
+constexpr double kMgKappaSmooth = 4., kMgKappaCoarsest = 30.;
+constexpr int kMgCoarsestSteps = 8;
+
+// the smoother polynomial on [lmax / kappa, lmax]: step 0 scales by 1 / theta, step k by (rho_k rho_{k-1}, 2 rho_k / delta)
+static void cheb_coefficients(double lmax, double kappa, int steps, std::vector<double> *c0, std::vector<double> *c1) {
+    const double lmin = lmax / kappa, theta = (lmax + lmin) / 2., delta = (lmax - lmin) / 2., sigma = theta / delta;
+    c0->assign((size_t)steps, 0.);
+    c1->assign((size_t)steps, 0.);
+    double rho = 1. / sigma;
+    (*c1)[0] = 1. / theta;
+    for (int k = 1; k < steps; ++k) {
+        const double rho_k = 1. / (2. * sigma - rho);
+        (*c0)[(size_t)k] = rho_k * rho;
+        (*c1)[(size_t)k] = 2. * rho_k / delta;
+        rho = rho_k;
+    }
+}
+
+// dinv and the Gershgorin bound of a level whose matrix is in place
+static int level_diagonal(MgHierarchy *h, MgLevel &L, int level, unsigned long long *word, const std::string &who, hipStream_t st) {
+    const size_t vs = dtype_size(h->dtype);
+    if (int rc = h->get(&L.dinv, (size_t)L.n * vs, "dinv")) return rc;
+    CG_HIP(hipMemsetAsync(L.dinv, 0, (size_t)L.n * vs, st));
+    if (int rc = jacobi_build_from_matrix(st, h->dtype, L.nu, who + ": level " + std::to_string(level), L.vals, L.ptr, L.cols, L.dinv)) return rc;
+    CG_HIP(hipMemsetAsync(word, 0, 8, st));
+    if (int rc = launch_mg_gershgorin(h->dtype, L.nu, L.vals, L.ptr, L.dinv, word, st)) return rc;
+    unsigned long long bits = 0;
+    CG_HIP(hipMemcpyAsync(&bits, word, 8, hipMemcpyDeviceToHost, st));
+    CG_HIP(hipStreamSynchronize(st));
+    std::memcpy(&L.lmax, &bits, 8);
+    if (!std::isfinite(L.lmax) || !(L.lmax > 0.))
+        return fail(CGAMD_ERR_INVALID, who + ": level " + std::to_string(level) + ": the Gershgorin bound of D^-1 A is not a positive finite number");
+    return CGAMD_OK;
+}
+
+int mg_build(hipStream_t st, int dt, int nu, int n, int nrhs, const SpmvPlan &plan0, long long nnz, const void *vals, const int *ptr,
+             const int *cols, const MgParams &p, const std::string &who, MgHierarchy **out) {
+    *out = nullptr;
+    const size_t vs = dtype_size(dt);
+    const int E = (int)(16 / vs);
+    MgHierarchy *h = new MgHierarchy;
+    struct Guard { MgHierarchy *h; ~Guard() { delete h; } } guard{h};
+    h->dtype = dt; h->nrhs = nrhs; h->p = p;
+    void *words = nullptr;      // [0] error word / Gershgorin bits, [1] scan overflow flag, [2..] scratch of compute_spmv_plan
+    if (int rc = h->get(&words, 64, "setup words")) return rc;
+    unsigned long long *word = static_cast<unsigned long long *>(words);
+    int *flag = reinterpret_cast<int *>(word + 1), *scratch = reinterpret_cast<int *>(word + 2);
+
+    MgLevel L0;
+    L0.n = n; L0.nu = nu; L0.nnz = nnz; L0.ld = n;
+    L0.grid.nx = p.nx; L0.grid.ny = p.ny; L0.grid.nz = p.nz;
+    L0.vals = vals; L0.ptr = ptr; L0.cols = cols; L0.plan = plan0;
+    h->lv.push_back(L0);
+    if (int rc = level_diagonal(h, h->lv[0], 0, word, who, st)) return rc;
+
+    while (h->lv.back().nu > p.min_rows && (int)h->lv.size() < kMgMaxLevels) {
+        const int level = (int)h->lv.size();
+        MgGrid &g = h->lv.back().grid;
+        g.cnx = (g.nx + 1) / 2; g.cny = (g.ny + 1) / 2; g.cnz = (g.nz + 1) / 2;
+        const long long ncl = (long long)g.cnx * g.cny * g.cnz;
+        if (ncl >= h->lv.back().nu) break;      // (a single node: nothing left to aggregate)
+        const int nc = (int)ncl;
+        const MgLevel &F = h->lv.back();
+        MgLevel C;
+        C.n = C.nu = nc;
+        C.ld = ((long long)nc + E - 1) / E * E;
+        C.grid.nx = g.cnx; C.grid.ny = g.cny; C.grid.nz = g.cnz;
+        void *ptrc = nullptr, *colsc = nullptr, *valsc = nullptr;
+        if (int rc = h->get(&ptrc, ((size_t)nc + 1 + 64) * 4, "row pointers")) return rc;
+        CG_HIP(hipMemsetAsync(word, 0xff, 8, st));
+        CG_HIP(hipMemsetAsync(flag, 0, 4, st));
+        if (int rc = launch_mg_count(g, nc, F.ptr, F.cols, static_cast<int *>(ptrc), word, st)) return rc;
+        if (int rc = launch_mg_scan(nc, static_cast<int *>(ptrc), flag, st)) return rc;
+        unsigned long long err_h = 0;
+        int back[2] = {0, 0};     // overflow flag, coarse nnz
+        CG_HIP(hipMemcpyAsync(&err_h, word, 8, hipMemcpyDeviceToHost, st));
+        CG_HIP(hipMemcpyAsync(&back[0], flag, 4, hipMemcpyDeviceToHost, st));
+        CG_HIP(hipMemcpyAsync(&back[1], static_cast<int *>(ptrc) + nc, 4, hipMemcpyDeviceToHost, st));
+        CG_HIP(hipStreamSynchronize(st));
+        if (err_h != ~0ull)
+            return fail(CGAMD_ERR_INVALID, who + ": level " + std::to_string(level) + ": coarse row " + std::to_string(err_h) + " has more than " +
+                                               std::to_string(kMgMaxRow) + " distinct columns");
+        if (back[0]) return fail(CGAMD_ERR_INVALID, who + ": level " + std::to_string(level) + ": the coarse matrix has more than 2^31 - 1 entries");
+        C.nnz = back[1];
+        // (64 entries of zeroed padding behind both arrays, as the handle's own matrix carries for the row-block kernels)
+        if (int rc = h->get(&colsc, ((size_t)C.nnz + 64) * 4, "columns")) return rc;
+        if (int rc = h->get(&valsc, ((size_t)C.nnz + 64) * vs, "values")) return rc;
+        CG_HIP(hipMemsetAsync(colsc, 0, ((size_t)C.nnz + 64) * 4, st));
+        CG_HIP(hipMemsetAsync(valsc, 0, ((size_t)C.nnz + 64) * vs, st));
+        if (int rc = launch_mg_fill(dt, g, nc, F.vals, F.ptr, F.cols, static_cast<int *>(ptrc), static_cast<int *>(colsc), valsc, st)) return rc;
+        C.vals = valsc; C.ptr = static_cast<int *>(ptrc); C.cols = static_cast<int *>(colsc);
+        C.plan = make_spmv_plan(nc);
+        if (int rc = compute_spmv_plan(C.ptr, C.cols, nc, scratch, st, &C.plan)) return rc;
+        finalize_spmv_plan(&C.plan, dt, nrhs, nc, C.nnz, C.vals, C.cols);
+        h->lv.push_back(C);
+        if (int rc = level_diagonal(h, h->lv.back(), level, word, who, st)) return rc;
+    }
+
+    const int nl = (int)h->lv.size();
+    for (int l = 0; l < nl; ++l) {
+        MgLevel &L = h->lv[(size_t)l];
+        const bool coarsest = l == nl - 1;
+        L.steps = coarsest ? kMgCoarsestSteps : p.smooth_steps;
+        cheb_coefficients(L.lmax, coarsest ? kMgKappaCoarsest : kMgKappaSmooth, L.steps, &L.c0, &L.c1);
+        const size_t bytes = (size_t)L.ld * (size_t)nrhs * vs;
+        if (int rc = h->get(&L.w, bytes, "w")) return rc;
+        CG_HIP(hipMemsetAsync(L.w, 0, bytes, st));
+        if (L.steps > 1) {
+            if (int rc = h->get(&L.d, bytes, "d")) return rc;
+            CG_HIP(hipMemsetAsync(L.d, 0, bytes, st));
+        }
+        if (l > 0) {
+            if (int rc = h->get(&L.x, bytes, "x")) return rc;
+            if (int rc = h->get(&L.b, bytes, "b")) return rc;
+            CG_HIP(hipMemsetAsync(L.x, 0, bytes, st));
+            CG_HIP(hipMemsetAsync(L.b, 0, bytes, st));
+        }
+    }
+    CG_HIP(hipStreamSynchronize(st));
+    guard.h = nullptr;
+    *out = h;
+    return CGAMD_OK;
+}
+
+void mg_free(MgHierarchy *h) { delete h; }
+
+// The V-cycle, walked once for the launches (st) or once for the tally (cost != nullptr: nothing is launched)
+static int mg_walk(const MgHierarchy *h, const void *r, void *z, hipStream_t st, MgCost *cost) {
+    const int dt = h->dtype, nr = h->nrhs, nl = (int)h->lv.size();
+    const long long V = (long long)dtype_size(dt);
+    auto vec = [&](const MgLevel &L, int passes, int shared) {       // passes over nrhs-wide vectors, shared = over dinv
+        if (cost) { ++cost->launches; cost->bytes += ((long long)passes * nr + shared) * L.n * V; }
+    };
+    auto spmv = [&](const MgLevel &L, int l, const void *x, void *w) -> int {
+        if (cost) {
+            ++cost->launches;
+            if (l == 0) ++cost->spmv0;
+            else cost->bytes += L.nnz * (V + 4) + ((long long)L.n + 1) * 4 + 2LL * L.n * V * nr;
+            return CGAMD_OK;
+        }
+        return launch_spmv(dt, L.plan, L.n, L.nnz, L.vals, L.ptr, L.cols, x, L.ld, w, L.ld, nr, nullptr, nullptr, st);
+    };
+    auto later_steps = [&](const MgLevel &L, int l, const void *b, void *x) -> int {       // steps 1 .. steps - 1 of a smoothing
+        for (int k = 1; k < L.steps; ++k) {
+            if (int rc = spmv(L, l, x, L.w)) return rc;
+            vec(L, 7, 1);
+            if (!cost)
+                if (int rc = launch_mg_cheb(dt, 2, L.n, L.ld, nr, L.dinv, b, L.w, L.d, x, L.c0[(size_t)k], L.c1[(size_t)k], true, st)) return rc;
+        }
+        return CGAMD_OK;
+    };
+    for (int l = 0; l < nl; ++l) {
+        const MgLevel &L = h->lv[(size_t)l];
+        const void *b = l == 0 ? r : L.b;
+        void *x = l == 0 ? z : L.x;
+        if (l == 0) {       // (the first step of every coarse level rides in the restriction that makes its b)
+            vec(L, 2 + (L.steps > 1), 1);
+            if (!cost)
+                if (int rc = launch_mg_cheb(dt, 0, L.n, L.ld, nr, L.dinv, b, nullptr, L.d, x, 0., L.c1[0], L.steps > 1, st)) return rc;
+        }
+        if (int rc = later_steps(L, l, b, x)) return rc;
+        if (l == nl - 1) break;
+        const MgLevel &C = h->lv[(size_t)l + 1];
+        if (int rc = spmv(L, l, x, L.w)) return rc;
+        if (cost) { ++cost->launches; cost->bytes += 2LL * nr * L.nu * V + ((2LL + (C.steps > 1)) * nr + 1) * C.n * V; }
+        else if (int rc = launch_mg_restrict(dt, L.grid, C.nu, L.ld, C.ld, nr, b, L.w, C.b, C.dinv, C.x, C.d, C.c1[0], C.steps > 1, st)) return rc;
+    }
+    for (int l = nl - 2; l >= 0; --l) {
+        const MgLevel &L = h->lv[(size_t)l], &C = h->lv[(size_t)l + 1];
+        const void *b = l == 0 ? r : L.b;
+        void *x = l == 0 ? z : L.x;
+        if (cost) { ++cost->launches; cost->bytes += 2LL * nr * L.nu * V + (long long)nr * C.n * V; }
+        else if (int rc = launch_mg_prolong(dt, L.grid, L.nu, L.ld, C.ld, nr, C.x, x, h->p.omega, st)) return rc;
+        if (int rc = spmv(L, l, x, L.w)) return rc;
+        vec(L, 4 + (L.steps > 1), 1);
+        if (!cost)
+            if (int rc = launch_mg_cheb(dt, 1, L.n, L.ld, nr, L.dinv, b, L.w, L.d, x, 0., L.c1[0], L.steps > 1, st)) return rc;
+        if (int rc = later_steps(L, l, b, x)) return rc;
+    }
+    return CGAMD_OK;
+}
+
+int mg_vcycle(const MgHierarchy *h, const void *r, void *z, hipStream_t st) { return mg_walk(h, r, z, st, nullptr); }
+MgCost mg_cost(const MgHierarchy *h) {
+    MgCost c;
+    (void)mg_walk(h, nullptr, nullptr, nullptr, &c);
+    return c;
+}
+int mg_levels(const MgHierarchy *h) { return (int)h->lv.size(); }
+int mg_level_info(const MgHierarchy *h, int level, long long info[6]) {
+    if (level < 0 || level >= (int)h->lv.size()) return fail(CGAMD_ERR_INVALID, "mg_level: no such level");
+    const MgLevel &L = h->lv[(size_t)level];
+    info[0] = L.nu; info[1] = L.nnz; info[2] = L.grid.nx; info[3] = L.grid.ny; info[4] = L.grid.nz;
+    std::memcpy(&info[5], &L.lmax, 8);
+    return CGAMD_OK;
+}
+int mg_level_matrix(const MgHierarchy *h, int level, int *ptr, int *cols, void *vals, hipStream_t st) {
+    if (level < 0 || level >= (int)h->lv.size()) return fail(CGAMD_ERR_INVALID, "mg_level_matrix: no such level");
+    const MgLevel &L = h->lv[(size_t)level];
+    if (ptr) CG_HIP(hipMemcpyAsync(ptr, L.ptr, ((size_t)L.nu + 1) * 4, hipMemcpyDeviceToHost, st));
+    if (cols) CG_HIP(hipMemcpyAsync(cols, L.cols, (size_t)L.nnz * 4, hipMemcpyDeviceToHost, st));
+    if (vals) CG_HIP(hipMemcpyAsync(vals, L.vals, (size_t)L.nnz * dtype_size(h->dtype), hipMemcpyDeviceToHost, st));
+    CG_HIP(hipStreamSynchronize(st));
+    return CGAMD_OK;
+}
+
+}  // namespace cgamd

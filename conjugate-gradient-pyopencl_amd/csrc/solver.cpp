@@ -67,6 +67,11 @@ struct cgamd_solver {
     // matrix) and, for one built from the matrix, what cgamd_solver_reload_matrix builds again: kind 1 = Jacobi, 2 = the lines at
     // pre_stride
     int pre_source = 0, pre_kind = 0, pre_stride = 0;
+    // aggregation multigrid preconditioner (cgamd_solver_set_preconditioner_multigrid; multigrid_setup.cpp): the hierarchy and what it
+    // was built with (pre_kind 3: refresh_values / reload_matrix build it again).  z lives in q's storage, like the line sweeps';
+    // r.r partials in part_rr, r.z partials in part_rz, vgrid of each
+    MgHierarchy *mg = nullptr;
+    MgParams mg_params;
     CgScalars sc;
     bool rhs_set = false;
     int iters = 0;  // iterations enqueued since set_rhs
@@ -142,6 +147,11 @@ static void destroy_graphs(cgamd_solver *s) {
     s->gT = nullptr; s->gTg = nullptr; s->gT_len = 0;
 }
 
+static void drop_multigrid(cgamd_solver *s) {
+    if (s->mg) mg_free(s->mg);
+    s->mg = nullptr;
+}
+
 static int dmalloc(void **p, size_t bytes, const char *what) {
     hipError_t e = hipMalloc(p, bytes ? bytes : 16);
     if (e != hipSuccess)
@@ -162,7 +172,7 @@ static int validate_csr_host(int n, long long nnz, const int *ptr, const int *co
 // the SpMV (SpMM) launch of the iteration, bracketed by the caller's event pair when one is installed
 static void *dbuf(cgamd_solver *s, int k) { return (s->fused2 && !s->until_mode && (k & 1)) ? s->d2 : s->d; }
 // a preconditioner (diagonal or tridiagonal) is set: what decides the loop family; s->mdiag is read where the diagonal is used
-static bool precond_set(const cgamd_solver *s) { return s->mdiag != nullptr || s->tri_on; }
+static bool precond_set(const cgamd_solver *s) { return s->mdiag != nullptr || s->tri_on || s->mg != nullptr; }
 // values between the diagonals of consecutive right-hand sides in s->mdiag: a batched handle keeps one per system, else one for all
 static long long m_pitch(const cgamd_solver *s) { return s->nsys ? s->n : 0; }
 static bool fused2_now(const cgamd_solver *s) { return s->fused2 && !s->rm && !precond_set(s) && !(s->flags & CGAMD_UNFUSED) && !s->until_mode; }
@@ -273,6 +283,15 @@ static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st, int lag = 1
         return launch_herm_aypx_beta_x(dt, n, s->r, s->d, s->d2, s->x, s->mdiag, m_pitch(s), n, s->part_rz, s->part_rr, s->vgrid, nr, s->sc,
                                        s->rho2, st, g);
     }
+    if (s->mg) {      // multigrid M: r -= alpha q (+ r.r), z = V-cycle(r) in q's storage, r.z, then the tridiagonal loop's last launch
+        if ((rc = enqueue_spmv(s, k, st))) return rc;
+        if ((rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st, g))) return rc;
+        if ((rc = launch_axpy_dot(dt, n, s->q, s->r, n, s->sc.alpha, nr, s->part_rr, s->vgrid, st, s->plan.vec_nt, g))) return rc;
+        // (unguarded under iterate_until: z of a frozen right-hand side is read by nothing that writes)
+        if ((rc = mg_vcycle(s->mg, s->r, s->q, st))) return rc;
+        if ((rc = launch_dot_partials(dt, n, s->r, s->q, n, nr, s->part_rz, s->vgrid, st))) return rc;
+        return launch_pcg_aypx_beta_z(dt, n, s->d, s->q, n, s->part_rz, s->part_rr, s->vgrid, nr, s->sc, s->rho2, s->x, st, g);
+    }
     if (s->tri_on) {  // tridiagonal M (helmFE_var.py:561-562): z = M^-1 r by the line sweeps, in q's storage
         if ((rc = enqueue_spmv(s, k, st))) return rc;
         if ((rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st, g))) return rc;
@@ -319,7 +338,7 @@ static void apply_wide_order(cgamd_solver *s) {
     const int E = (int)(16 / dtype_size(s->dtype));
     // (where the one-XCD resident loop applies it runs, with the strided order -- unless a preconditioner is set: that recurrence only
     // has the chip-wide form; the tridiagonal one has none)
-    const bool wide = s->resw.ok && !s->tri_on && (!s->res_ok || precond_set(s));
+    const bool wide = s->resw.ok && !s->tri_on && !s->mg && (!s->res_ok || precond_set(s));
     const int kdq = wide ? kResWideBlocksPerRpt * s->resw.rpt : 0, krr = wide ? kdq / E : 0;
     const int vgrid = wide ? (s->n / E + kBlock - 1) / kBlock : vec_grid(s->n, s->dtype, s->nrhs);
     const int fold_max = 0;      // (alpha folded beyond 2048 partials was tried for these handles: every work-group summing 3907 partials, 1M rows 30 -> 52 us)
@@ -711,6 +730,13 @@ static int line_from_matrix(cgamd_solver *s, const std::string &who, int stride)
 static int jacobi_from_matrix(cgamd_solver *s, const std::string &who);
 static int batched_line_from_matrix(cgamd_solver *s, const std::string &who, int stride);
 static int batched_jacobi_from_matrix(cgamd_solver *s, const std::string &who);
+static int multigrid_from_matrix(cgamd_solver *s, const std::string &who, const MgParams &p);
+static int step_not_capturing(cgamd_solver *s, const char *who);
+// the preconditioner a non-batched handle built from its matrix, built again from the matrix as it is now
+static int rebuild_from_matrix(cgamd_solver *s, const std::string &who) {
+    if (s->pre_kind == 3) return multigrid_from_matrix(s, who, s->mg_params);
+    return s->pre_kind == 1 ? jacobi_from_matrix(s, who) : line_from_matrix(s, who, s->pre_stride);
+}
 
 // New matrix VALUES / PATTERN of the same size into an existing handle (host arrays; the handle must own its matrix):
 // what the stateless cg() needs to reuse its cached device state -- allocations, stream, captured graphs -- from one call
@@ -764,7 +790,7 @@ int cgamd_solver_reload_matrix(cgamd_solver *s, const void *aValues, const int *
     setup_x_lag(s);                     // (the default rule follows the number of d.q partials and the resident plan)
     CG_HIP(hipStreamSynchronize(st));   // the host arrays may go away after return
     if (s->pre_source >= 2) {           // a preconditioner built from the matrix follows it (one from the caller's arrays is kept)
-        const int rc = s->pre_kind == 1 ? jacobi_from_matrix(s, "reload_matrix") : line_from_matrix(s, "reload_matrix", s->pre_stride);
+        const int rc = rebuild_from_matrix(s, "reload_matrix");
         if (rc) {                       // the matrix is loaded; the old factors belong to the old one
             const std::string why = cgamd_last_error();
             (void)diag_impl(s, nullptr, 0);
@@ -834,7 +860,7 @@ int cgamd_solver_refresh_values(cgamd_solver *s, const void *aValues, int on_dev
     if (s->pre_source >= 2) {               // a preconditioner built from the matrix follows it (one from the caller's arrays is kept)
         int rc;
         if (s->nsys) rc = s->pre_kind == 1 ? batched_jacobi_from_matrix(s, "refresh_values") : batched_line_from_matrix(s, "refresh_values", s->pre_stride);
-        else rc = s->pre_kind == 1 ? jacobi_from_matrix(s, "refresh_values") : line_from_matrix(s, "refresh_values", s->pre_stride);
+        else rc = rebuild_from_matrix(s, "refresh_values");
         if (rc) {                           // the values are in force; the old factors belong to the old ones
             const std::string why = cgamd_last_error();
             (void)diag_impl(s, nullptr, 0);
@@ -852,6 +878,7 @@ int cgamd_solver_destroy(cgamd_solver *s) {
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
     destroy_graphs(s);
+    drop_multigrid(s);
     if (s->own_ptr && s->ptr) (void)hipFree(s->ptr);
     if (s->own_matrix) {
         if (s->vals) (void)hipFree(s->vals);
@@ -921,6 +948,11 @@ static int set_rhs_impl(cgamd_solver *s, const void *b, const void *x0, int on_d
     if (s->herm) {    // d0 = r0 (d0 = m .* r0), dc = conj(d0), delta0 = r0^H r0, rho0 (hermitian.hip)
         if ((rc = launch_herm_init(s->dtype, s->n, s->r, s->d, s->d2, s->mdiag, m_pitch(s), s->n, s->nrhs, s->part_rz, s->part_rr, s->vgrid, st))) return rc;
         if ((rc = launch_herm_delta0(s->dtype, s->mdiag != nullptr, s->part_rz, s->part_rr, s->vgrid, s->nrhs, s->sc, s->rho2, st))) return rc;
+    } else if (s->mg) {      // z0 = V-cycle(r0), p0 = z0, rho0 = r0.z0; the partials by the launches of an iteration
+        if ((rc = mg_vcycle(s->mg, s->r, s->d, st))) return rc;
+        if ((rc = launch_dot_partials(s->dtype, s->n, s->r, s->r, s->n, s->nrhs, s->part_rr, s->vgrid, st))) return rc;
+        if ((rc = launch_dot_partials(s->dtype, s->n, s->r, s->d, s->n, s->nrhs, s->part_rz, s->vgrid, st))) return rc;
+        if ((rc = launch_pcg_delta0(s->dtype, s->part_rz, s->part_rr, s->vgrid, s->nrhs, s->sc, s->rho2, st))) return rc;
     } else if (s->tri_on) {  // z0 = M^-1 r0 (the line sweeps), p0 = z0, rho0 = r0.z0
         if ((rc = enqueue_tri_sweep(s, false, nullptr, s->d, st))) return rc;
         const TriPartials p = tri_partials(s);
@@ -969,6 +1001,7 @@ static int diag_impl(cgamd_solver *s, const void *m, int on_device) {
     destroy_graphs(s);
     s->rhs_set = false;
     drop_tridiag(s);
+    drop_multigrid(s);
     s->pre_source = s->pre_kind = s->pre_stride = 0;
     if (!m) {
         if (s->mdiag) { (void)hipFree(s->mdiag); s->mdiag = nullptr; }
@@ -1004,6 +1037,7 @@ static int tri_install(cgamd_solver *s, void *coef, size_t pitch, int *plan, int
     destroy_graphs(s);
     s->rhs_set = false;
     drop_tridiag(s);
+    drop_multigrid(s);
     s->pre_source = s->pre_kind = s->pre_stride = 0;
     if (s->mdiag) { (void)hipFree(s->mdiag); s->mdiag = nullptr; }
     s->tri_coef = coef;
@@ -1110,6 +1144,95 @@ int cgamd_solver_set_preconditioner_jacobi(cgamd_solver *s) {
     return jacobi_from_matrix(s, "set_preconditioner_jacobi");
 }
 
+// ---- aggregation multigrid on a grid system (multigrid_setup.cpp): the hierarchy is built from the matrix as it is now, on the
+// device; nothing on the handle changes before it stands
+static int multigrid_from_matrix(cgamd_solver *s, const std::string &who, const MgParams &p) {
+    CG_HIP(hipSetDevice(s->ctx->device));
+    hipStream_t st = s->ctx->stream;
+    CG_HIP(hipStreamSynchronize(st));
+    MgHierarchy *h = nullptr;
+    int rc = mg_build(st, s->dtype, s->n_user, s->n, s->nrhs, s->plan, s->nnz, s->vals, s->ptr, s->cols, p, who, &h);
+    if (rc) return rc;
+    const size_t vs = dtype_size(s->dtype);
+    if (!s->part_rz) rc = dmalloc(&s->part_rz, acc_size(s->dtype) * s->part_rr_cap * s->nrhs, "partials_rz");
+    if (!rc && !s->rho2) rc = dmalloc(&s->rho2, 2 * vs * (size_t)s->nrhs, "rho");
+    if (rc) { mg_free(h); return rc; }
+    destroy_graphs(s);
+    s->rhs_set = false;
+    drop_tridiag(s);
+    drop_multigrid(s);
+    if (s->mdiag) { (void)hipFree(s->mdiag); s->mdiag = nullptr; }
+    s->mg = h;
+    s->mg_params = p;
+    s->pre_source = 2; s->pre_kind = 3; s->pre_stride = 0;
+    apply_wide_order(s);
+    return CGAMD_OK;
+}
+int cgamd_solver_set_preconditioner_multigrid(cgamd_solver *s, int nx, int ny, int nz, int smooth_steps, double over_correction, int min_rows) {
+    const std::string who = "set_preconditioner_multigrid";
+    if (!s) return fail(CGAMD_ERR_INVALID, who + ": solver is NULL");
+    if (s->nsys) return batched_refuses("set_preconditioner_multigrid");
+    if (s->herm) return herm_refuses("set_preconditioner_multigrid", "which the V-cycle does not serve");
+    if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, who + ": CGAMD_UNFUSED replays the reference's kernel sequence");
+    if (s->rm_ok) return fail(CGAMD_ERR_STATE, who + ": the handle keeps its right-hand sides interleaved (row-major layout)");
+    if (nx < 1 || ny < 1 || nz < 1) return fail(CGAMD_ERR_INVALID, who + ": every grid dimension must be at least 1");
+    const long long plane = (long long)nx * ny;
+    if (plane > 2147483647LL || plane * nz != (long long)s->n_user)
+        return fail(CGAMD_ERR_INVALID, who + ": nx * ny * nz must equal the size of the system");
+    if (smooth_steps < 0 || smooth_steps > 4) return fail(CGAMD_ERR_INVALID, who + ": smooth_steps must be in 0 ... 4 (0 = the default, 1)");
+    if (!std::isfinite(over_correction) || over_correction < 0.) return fail(CGAMD_ERR_INVALID, who + ": over_correction must be finite and not negative (0 = the default, 1.6)");
+    if (min_rows < 0) return fail(CGAMD_ERR_INVALID, who + ": min_rows must not be negative (0 = the default, 512)");
+    MgParams p;
+    p.nx = nx; p.ny = ny; p.nz = nz;
+    if (smooth_steps) p.smooth_steps = smooth_steps;
+    if (over_correction != 0.) p.omega = over_correction;
+    if (min_rows) p.min_rows = min_rows;
+    TuneScope ts(&s->tune);
+    return multigrid_from_matrix(s, who, p);
+}
+int cgamd_solver_mg_levels(cgamd_solver *s) {
+    if (!s) return -CGAMD_ERR_INVALID;
+    return s->mg ? mg_levels(s->mg) : 0;
+}
+static int mg_wanted(cgamd_solver *s, const char *who) {
+    if (!s) return fail(CGAMD_ERR_INVALID, std::string(who) + ": solver is NULL");
+    if (!s->mg) return fail(CGAMD_ERR_STATE, std::string(who) + ": no multigrid preconditioner is set");
+    return CGAMD_OK;
+}
+int cgamd_solver_mg_level(cgamd_solver *s, int level, long long info[6]) {
+    if (int rc = mg_wanted(s, "mg_level")) return rc;
+    if (!info) return fail(CGAMD_ERR_INVALID, "mg_level: info is NULL");
+    return mg_level_info(s->mg, level, info);
+}
+int cgamd_solver_mg_level_matrix(cgamd_solver *s, int level, int *ptr, int *cols, void *vals) {
+    if (int rc = mg_wanted(s, "mg_level_matrix")) return rc;
+    CG_HIP(hipSetDevice(s->ctx->device));
+    return mg_level_matrix(s->mg, level, ptr, cols, vals, s->ctx->stream);
+}
+// one V-cycle on caller vectors (nRHS * size values each, device memory, stride `size`), through buffers with the handle's padding
+int cgamd_solver_mg_apply(cgamd_solver *s, const void *r_dev, void *z_dev) {
+    if (int rc = mg_wanted(s, "mg_apply")) return rc;
+    if (!r_dev || !z_dev) return fail(CGAMD_ERR_INVALID, "mg_apply: null argument");
+    TuneScope ts(&s->tune);
+    CG_HIP(hipSetDevice(s->ctx->device));
+    if (int rc = step_not_capturing(s, "mg_apply")) return rc;
+    hipStream_t st = s->ctx->stream;
+    const size_t vs = dtype_size(s->dtype), row = (size_t)s->n * vs, bytes = row * (size_t)s->nrhs;
+    void *buf = nullptr;
+    if (int rc = dmalloc(&buf, 2 * bytes, "mg_apply vectors")) return rc;
+    void *r = buf, *z = static_cast<char *>(buf) + bytes;
+    int rc = CGAMD_OK;
+    hipError_t e = hipMemsetAsync(buf, 0, 2 * bytes, st);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(r, row, r_dev, (size_t)s->n_user * vs, (size_t)s->n_user * vs, (size_t)s->nrhs, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) rc = mg_vcycle(s->mg, r, z, st);
+    if (e == hipSuccess && !rc) e = hipMemcpy2DAsync(z_dev, (size_t)s->n_user * vs, z, row, (size_t)s->n_user * vs, (size_t)s->nrhs, hipMemcpyDeviceToDevice, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    if (rc) return rc;
+    if (e != hipSuccess || e2 != hipSuccess) return fail(CGAMD_ERR_HIP, std::string("mg_apply: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+    return CGAMD_OK;
+}
+
 // ---- a batched handle: one M per system (M_r for right-hand side r), never one shared by all ------------------------------------------
 static int not_batched(const char *who, const char *shared) {
     return fail(CGAMD_ERR_STATE, std::string(who) + ": the handle is not batched (one matrix for all right-hand sides); use " + shared);
@@ -1178,7 +1301,7 @@ int cgamd_solver_iterate(cgamd_solver *s, int nIterations) {
     int left = nIterations, k = s->iters;
     const bool use_graph = !(s->flags & CGAMD_NO_GRAPH) && !s->graph_failed;
     const bool two = fused2_now(s);
-    if (s->resw.ok && !s->until_mode && !s->tri_on && !(two && s->res_ok) && !s->rm && !(s->flags & (CGAMD_NO_GRAPH | CGAMD_UNFUSED)) &&
+    if (s->resw.ok && !s->until_mode && !s->tri_on && !s->mg && !(two && s->res_ok) && !s->rm && !(s->flags & (CGAMD_NO_GRAPH | CGAMD_UNFUSED)) &&
         (nIterations >= std::max(1, tune().resident_wide_min) || s->tol_req > 0.)) {
         // one chip-wide resident group (single right-hand side, matrix rows in registers).  d ping-pongs inside the launch; handles
         // of the launched loops that keep d in one buffer get it back there, and the launched loops' r.r partials are rebuilt.
@@ -1293,7 +1416,7 @@ int cgamd_solver_iterate_tol(cgamd_solver *s, int maxIterations, double tol, int
     if (s->until_mode) return fail(CGAMD_ERR_STATE, "iterate_tol: iterate_until runs this right-hand side on the launched loop until the next set_rhs");
     {
         TuneScope ts(&s->tune);
-        const bool local = fused2_now(s) && s->res_ok, wide = s->resw.ok && !s->tri_on && !s->rm && !(s->res_ok && !precond_set(s));
+        const bool local = fused2_now(s) && s->res_ok, wide = s->resw.ok && !s->tri_on && !s->mg && !s->rm && !(s->res_ok && !precond_set(s));
         if ((!local && !wide) || (s->flags & (CGAMD_NO_GRAPH | CGAMD_UNFUSED)))
             return fail(CGAMD_ERR_STATE, "iterate_tol: this handle runs a launched loop (check the history from the host)");
     }
@@ -1336,6 +1459,7 @@ static int replace_refuses(const cgamd_solver *s, bool planned) {
     if (planned ? (s->rm_ok && !precond_set(s)) : s->rm)
         return fail(CGAMD_ERR_STATE, who + "the handle keeps its right-hand sides interleaved (row-major layout)");
     if (s->tri_on) return fail(CGAMD_ERR_STATE, who + "a tridiagonal / line preconditioner is set; the entry serves no preconditioner or a diagonal one");
+    if (s->mg) return fail(CGAMD_ERR_STATE, who + "a multigrid preconditioner is set; the entry serves no preconditioner or a diagonal one");
     if (s->herm) return herm_refuses("replace_residual", "which the entry does not serve");
     if (s->nsys) return fail(CGAMD_ERR_STATE, who + "the handle is batched");
     if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, who + "CGAMD_UNFUSED replays the reference's kernel sequence");
@@ -1585,7 +1709,7 @@ static int step_not_capturing(cgamd_solver *s, const char *who) {
 // Row-major and tridiagonal handles launch their vector and scalar steps with grids of their own (rm_nwg / rm_vgrid, tri.grid) and keep
 // their partials elsewhere (tri_part): neither entry describes them, both refuse them
 static int step_launched_rhs_major(cgamd_solver *s, const char *who) {
-    if (s->rm || (s->rm_ok && !precond_set(s)) || s->tri_on)
+    if (s->rm || (s->rm_ok && !precond_set(s)) || s->tri_on || s->mg)
         return fail(CGAMD_ERR_INVALID, std::string(who) + ": not recorded for row-major and tridiagonal handles");
     if (s->herm) return fail(CGAMD_ERR_INVALID, std::string(who) + ": not recorded for CGAMD_HERMITIAN handles (steps of their own, hermitian.hip)");
     return CGAMD_OK;
@@ -1672,6 +1796,7 @@ int cgamd_solver_loop_launches(cgamd_solver *s) {
     if (!s) return -CGAMD_ERR_INVALID;
     TuneScope ts(&s->tune);
     if (s->herm) return 4;                               // SpMV, herm_alpha, herm_axpy_dot, herm_aypx_beta_x under every flag
+    if (s->mg) return 5 + mg_cost(s->mg).launches;       // SpMV, cg_alpha, r update, the V-cycle's chain, r.z, update
     if (s->tri_on) return s->tri.longform ? 6 : 4;      // launched loop only: SpMV, cg_alpha, the sweep (3 launches in the long form), update
     if (s->nsys && s->mdiag) return 4;                   // a batched handle's PCG loop is the same four launches under every flag
     if (s->flags & CGAMD_UNFUSED) return 8;
@@ -1703,6 +1828,12 @@ long long cgamd_solver_spmv_bytes(cgamd_solver *s) {
 // segment) stores w y in the forward walk and reads it and r back in the backward walk: sweep (r, q in; r, w y out; w y, r in; z
 // out) 7, so 14 per RHS, and each factor once
 // (a batched handle has factors of its own per right-hand side)
+// the multigrid loop: SpMV (p, q) 2 + r update (q, r in; r out) 3 + r.z (r, z) 2 + update (z, p, x in; x, p out) 5 = 12 passes per RHS,
+// and the V-cycle: its fine-level SpMVs at the price of this handle's SpMV, everything else as multigrid_setup.cpp counts it
+static long long mg_bytes(const cgamd_solver *s, long long spmv_bytes) {
+    const MgCost c = mg_cost(s->mg);
+    return 12LL * s->n_user * (long long)dtype_size(s->dtype) * s->nrhs + c.spmv0 * spmv_bytes + c.bytes;
+}
 static long long tri_passes(const cgamd_solver *s) {
     const long long f = value_arrays(s);
     if (s->tri.stride > 1) return 14LL * s->nrhs + 3 * f;
@@ -1711,6 +1842,7 @@ static long long tri_passes(const cgamd_solver *s) {
 long long cgamd_solver_iter_bytes(cgamd_solver *s, int fused) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
+    if (s->mg) return s->nnz * (V + 4) + ((long long)s->n_user + 1) * 4 + mg_bytes(s, cgamd_solver_spmv_bytes(s));
     if (s->tri_on) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + tri_passes(s) * s->n_user * V;
     // the conjugated recurrence: the launched loop's 10 passes (12 with a diagonal M) and conj(d), written by the d step and read by the SpMV's dot
     if (s->herm) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + (s->mdiag ? 14LL : 12LL) * s->n_user * V * s->nrhs;
@@ -1749,6 +1881,7 @@ long long cgamd_solver_iter_moved_bytes(cgamd_solver *s) {
     const long long lag = x_lag_now(s);
     const long long value_bytes = joint_form(s) ? 0 : s->plan.vcodes ? 1 : V * value_arrays(s);
     const long long matrix = row_form(s) ? (long long)s->n_user : s->nnz * (value_bytes + index_bytes_per_nnz(s)) + ((long long)s->n_user + 1) * 4;
+    if (s->mg) return matrix + mg_bytes(s, cgamd_solver_spmv_moved_bytes(s));
     if (s->tri_on) return matrix + tri_passes(s) * s->n_user * V;
     // the deferred x update: the d steps of a group of L iterations move 4 L + 1 vectors instead of 5 L, the steady state of a
     // handle iterated in multiples of U: (9 L + 1) / L passes per iteration

@@ -386,6 +386,52 @@ int cgamd_solver_set_preconditioner_jacobi(cgamd_solver *s);
 int cgamd_solver_set_preconditioner_batched(cgamd_solver *s, const void *m, int on_device);
 int cgamd_solver_set_preconditioner_batched_jacobi(cgamd_solver *s);
 int cgamd_solver_set_preconditioner_batched_line(cgamd_solver *s, int stride);
+/* ---- Aggregation multigrid for grid systems (csrc/multigrid.hip, csrc/multigrid_setup.cpp) ----
+ * z = M^-1 r is one V-cycle on a hierarchy built ON THE DEVICE from the handle's own matrix: the preconditioner that cuts the
+ * NUMBER of iterations of an isotropic stencil system, where Jacobi does nothing and the lines pay off only under anisotropy.
+ * The rows are the nodes of an nx x ny x nz grid numbered x fastest (nx * ny * nz == size; nz = 1 or ny = nz = 1: 2-D, 1-D).
+ *   Aggregates: fine node (x, y, z) -> coarse node (x >> 1, y >> 1, z >> 1) of the ceil(nx / 2) x ceil(ny / 2) x ceil(nz / 2) grid, x
+ *     fastest; an axis of length 1 stays 1; odd lengths leave aggregates of 1, 2 or 4 nodes at the far faces.  Coarsening repeats
+ *     while a level has more than min_rows rows, at most 16 levels.  Padding rows (cgamd_solver_ld) belong to no aggregate, z = 0 there.
+ *   Coarse matrices: A_c = P^T A P with piecewise-constant P -- entry (I, J) is the sum of the fine entries (i, j) with agg(i) = I,
+ *     agg(j) = J, fine rows ascending and entries in stored order, in double / complex double, rounded once.  Columns ascending,
+ *     structural zeros kept.  A coarse row with more than 64 distinct columns: CGAMD_ERR_INVALID naming the level and the row.
+ *   Per level: dinv = 1 / diag by the rules and with the error wording of cgamd_solver_set_preconditioner_jacobi (the level is named
+ *     too), and lmax = max_i |dinv_i| sum_j |a_ij| in double, the Gershgorin bound of D^-1 A.
+ *   Smoother S_s(b, x) on [lmax / kappa, lmax], theta = (lmax + lmin) / 2, delta = (lmax - lmin) / 2, sigma = theta / delta, rho_0 =
+ *     1 / sigma: first step d = (1 / theta) (dinv (b - A x)) (x = 0: dinv b, no product), x += d; step k >= 1: rho_k = 1 / (2 sigma -
+ *     rho_{k-1}), d = (rho_k rho_{k-1}) d + (2 rho_k / delta) (dinv (b - A x)), x += d.  The coefficients are computed on the host in
+ *     double and passed rounded to the real type.  kappa = 4 and smooth_steps steps on every level but the coarsest, which takes
+ *     kappa = 30 and 8 steps from x = 0.
+ *   V(l): x = S(b, 0); b_{l+1}[I] = sum over i in I, ascending, of (b - A x)[i]; e = V(l + 1); x[i] += over_correction e[agg(i)];
+ *     x = S(b, x).
+ * Every sum has a fixed order: the same bits from run to run and however a solve is cut into calls.  The cycle is a linear chain of
+ * launches inside the handle's captured iteration graphs (CGAMD_NO_GRAPH: plain launches, same bits).
+ * smooth_steps 0 ... 4 (0 = 1), over_correction finite and >= 0 (0 = 1.6), min_rows >= 0 (0 = 512).  Takes effect at the next
+ * cgamd_solver_set_rhs; history keeps r.r, rho = r.z drives alpha and beta; replaces any other preconditioner and is replaced by any
+ * other; cgamd_solver_set_preconditioner(s, NULL, 0) removes it and the handle then returns the bits of one that never had it.  On
+ * failure the handle is unchanged.  cgamd_solver_preconditioner_source() reports 2.  cgamd_solver_refresh_values and
+ * cgamd_solver_reload_matrix build the hierarchy again from the new values; if that fails the preconditioner is removed and the error
+ * returned.  Launched loop only: per iteration SpMV, cg_alpha, r update, the V-cycle, r.z, update -- cgamd_solver_loop_launches() = 5 +
+ * the cycle's launches (5 per level above the coarsest, 1 on level 0, 14 on the coarsest, with one smoothing step).
+ * Served: all four value types, any nRHS (RHS-major), CGAMD_MATRIX_ON_DEVICE, CGAMD_NO_GRAPH, cgamd_solver_iterate_until (the V-cycle
+ * runs unguarded: z of a frozen right-hand side is read by nothing that writes).  CGAMD_ERR_INVALID: nx * ny * nz != size, a
+ * dimension < 1, smooth_steps outside 0 ... 4, over_correction not finite or negative, min_rows negative.  CGAMD_ERR_STATE, the handle
+ * untouched: batched handles, CGAMD_HERMITIAN on a complex type, handles that keep their block row-major, CGAMD_UNFUSED; with the
+ * preconditioner set, cgamd_solver_iterate_tol and cgamd_solver_replace_residual (and so cgamd_mixed_solve).
+ * Byte models (cgamd_solver_iter_bytes / _iter_moved_bytes), V = sizeof(value): matrix + 12 size V nRHS + m_0 SpMV_0 + sum over the
+ * coarse levels l of m_l (nnz_l (V + 4) + 4 (n_l + 1) + 2 n_l V nRHS) + the vector passes of the cycle's own kernels; m_l = SpMVs
+ * of a cycle on level l (2 smooth_steps; 7 on the coarsest), SpMV_0 = cgamd_solver_spmv_bytes / _spmv_moved_bytes of this handle. */
+int cgamd_solver_set_preconditioner_multigrid(cgamd_solver *s, int nx, int ny, int nz, int smooth_steps, double over_correction, int min_rows);
+/* levels of the hierarchy in force (0: no multigrid preconditioner; negative: error) */
+int cgamd_solver_mg_levels(cgamd_solver *s);
+/* info: rows, non-zeros, nx, ny, nz of the level and, in info[5], the bits of the double lmax */
+int cgamd_solver_mg_level(cgamd_solver *s, int level, long long info[6]);
+/* Development entries (tests; same standing as cgamd_solver_step_state).  _mg_level_matrix: the CSR arrays of a level to the host
+ * (rows + 1 ints, nnz ints, nnz values; any pointer may be NULL); synchronises.  _mg_apply: z = one V-cycle of r on caller vectors,
+ * device pointers to nRHS * size values at stride `size`; synchronises. */
+int cgamd_solver_mg_level_matrix(cgamd_solver *s, int level, int *ptr, int *cols, void *vals);
+int cgamd_solver_mg_apply(cgamd_solver *s, const void *r_dev, void *z_dev);
 /* where the preconditioner in force came from -- 0: none; 1: the caller's arrays (the three array entries above, and
  * cgamd_solver_set_preconditioner_batched); 2: the matrix, built on the device; 3: the matrix, extracted on the device but factored by
  * the host route (long segments; never on a batched handle) */
