@@ -96,6 +96,8 @@ def load():
         "cgamd_solver_mg_level": (ci, [vp, ci, ctypes.POINTER(ll)]),
         "cgamd_solver_mg_level_matrix": (ci, [vp, ci, vp, vp, vp]),
         "cgamd_solver_mg_apply": (ci, [vp, vp, vp]),
+        "cgamd_solver_set_preconditioner_amg": (ci, [vp, ci, ctypes.c_double, ci, ctypes.c_double, ci]),
+        "cgamd_solver_mg_aggregates": (ci, [vp, ci, vp, ctypes.POINTER(ci)]),
         "cgamd_solver_preconditioner_source": (ci, [vp]),
         "cgamd_solver_iterate": (ci, [vp, ci]),
         "cgamd_solver_iterate_timed": (ci, [vp, ci, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),

@@ -382,6 +382,10 @@ class Solver:
           the hierarchy built on the device from the handle's matrix (cgamd_solver_set_preconditioner_multigrid): the
           preconditioner for isotropic stencil systems, where it cuts the iteration count by a multiple.  Follows reload_matrix and
           refresh_values.  mg_levels() lists the hierarchy.
+        * "amg" or ("amg", {"passes": 3, "strength": 0.25, "smooth_steps": 1, "over_correction": 1.6, "min_rows": 512}): the same
+          V-cycle on aggregates matched from the matrix itself on the device (cgamd_solver_set_preconditioner_amg): no grid
+          needed -- a Matrix-Market file, a permuted grid matrix, a mesh -- and anisotropy is followed, not crossed.  Follows
+          reload_matrix and refresh_values (aggregates included).  mg_levels() and mg_aggregates(level) list the hierarchy.
         * a 1-D array (1/diag(A) for Jacobi), a device buffer, or a scipy sparse M with nnz <= size: the diagonal branch,
           z = M.dot(r);
         * a scipy sparse M with nnz > size: the spsolve branch, z solves M z = r.  M must be tridiagonal along one grid axis: all
@@ -402,9 +406,18 @@ class Solver:
         if m is None:
             check(self._lib.cgamd_solver_set_preconditioner(self.handle, None, 0))
             return
+        named_amg = isinstance(m, str) and m == "amg"
+        if named_amg or (isinstance(m, tuple) and len(m) == 2 and m[0] == "amg"):
+            opts = {} if named_amg else dict(m[1])
+            if set(opts) - {"passes", "strength", "smooth_steps", "over_correction", "min_rows"}:
+                raise ValueError('"amg" or ("amg", {"passes": 3, "strength": 0.25, "smooth_steps": 1, "over_correction": 1.6, "min_rows": 512})')
+            check(self._lib.cgamd_solver_set_preconditioner_amg(self.handle, int(opts.get("passes", 0)), float(opts.get("strength", 0.0)),
+                                                                int(opts.get("smooth_steps", 0)), float(opts.get("over_correction", 0.0)),
+                                                                int(opts.get("min_rows", 0))))
+            return
         if isinstance(m, str):
             if m != "jacobi":
-                raise ValueError('preconditioner by name: "jacobi" or ("line", stride)')
+                raise ValueError('preconditioner by name: "jacobi", "amg" or ("line", stride)')
             check(self._lib.cgamd_solver_set_preconditioner_jacobi(self.handle))
             return
         if isinstance(m, tuple) and len(m) == 2 and m[0] == "line":
@@ -450,6 +463,14 @@ class Solver:
         da = np.empty(info["nnz"], self.dtype)
         check(self._lib.cgamd_solver_mg_level_matrix(self.handle, int(level), ptr(ip), ptr(ix), ptr(da)))
         return ip, ix, da
+
+    def mg_aggregates(self, level):
+        """(agg, n_coarse): the map of the rows of `level` to the rows of level + 1 of the hierarchy in force (an algebraic
+        hierarchy's stored map or a grid hierarchy's boxes), copied to the host (development accessor: tests)"""
+        agg = np.empty(self.mg_levels()[level]["rows"], np.int32)
+        nc = ctypes.c_int(0)
+        check(self._lib.cgamd_solver_mg_aggregates(self.handle, int(level), ptr(agg), ctypes.byref(nc)))
+        return agg, int(nc.value)
 
     def mg_apply(self, r):
         """z = one V-cycle of r: n_rhs * size values, host array in and out (development accessor: tests)"""
@@ -757,7 +778,7 @@ class Solver:
 
     def pcg(self, b, M=None, x0=None, tol=1e-6, maxit=1000, check_every=8):
         """`PCG(A, b, M, x, tol, maxit)` of the reference (helmFE_var.py:546-586) for M = None, a diagonal M, a tridiagonal
-        sparse M along any grid axis (the spsolve branch) or "jacobi" / ("line", stride) / ("multigrid", dims) built from the matrix (see set_preconditioner): stops when sqrt(|r.r|) < tol, returns (x, i) with i the 0-based
+        sparse M along any grid axis (the spsolve branch) or "jacobi" / ("line", stride) / ("multigrid", dims) / "amg" built from the matrix (see set_preconditioner): stops when sqrt(|r.r|) < tol, returns (x, i) with i the 0-based
         index of the last iteration run, like the reference.  The residual history stays on the device and is read back every
         `check_every` iterations; x is taken at the first iteration that met the tolerance by re-running exactly that many
         iterations when the check overshot it."""

@@ -587,8 +587,38 @@ int launch_mg_prolong(int dtype, const MgGrid &g, int nf, long long ldf, long lo
                       hipStream_t st);
 // The hierarchy of one handle.  Level 0 borrows the handle's matrix and the plan of its SpMV (codes included: build again whenever
 // they change); the coarse levels own theirs.  nu = the caller's rows, n = with the padding rows (z = 0 there)
+// ---- algebraic aggregates (amg.hip): handshake matching from the matrix, then the same Galerkin sums and V-cycle through stored maps
+constexpr int kAmgWidth = 8;        // most members of an aggregate (2^passes); the stride of the member lists
+constexpr int kAmgMaxRounds = 32;   // matching rounds of a pass
+// smax[i] <- the largest s_ij = -Re(a_ij) > 0 over the stored entries j != i of row i, 0 without one
+int launch_amg_smax(int dtype, int n, const void *vals, const int *ptr, const int *cols, double *smax, hipStream_t st);
+// pick[i] <- the best strong unmatched neighbour of every unmatched row (-1: none), from the matching as it stands
+int launch_amg_pick(int dtype, int n, double theta, const void *vals, const int *ptr, const int *cols, const double *smax, const int *match,
+                    int *pick, hipStream_t st);
+// match[i] <- j where pick[i] == j and pick[j] == i; *formed (preset to 0) <- 1 when there was such a pair
+int launch_amg_handshake(int n, const int *pick, int *match, int *formed, hipStream_t st);
+// flag[i] <- 1 for the smallest member of every aggregate
+int launch_amg_roots(int n, const int *match, int *flag, hipStream_t st);
+// rank = the flags scanned: pmap[i] <- the coarse id of row i; pairs[2 I], pairs[2 I + 1] <- root and partner (-1) of aggregate I
+int launch_amg_number(int n, const int *match, const int *rank, int *pmap, int *pairs, hipStream_t st);
+// agg_out[i] <- pmap[agg_in[i]] (agg_in == nullptr: pmap[i]); in place serves
+int launch_amg_compose(int n, const int *pmap, const int *agg_in, int *agg_out, hipStream_t st);
+// out <- the member lists (kAmgWidth per aggregate, ascending, -1 behind the last) of the pairs' members' lists merged (old == nullptr:
+// the members themselves)
+int launch_amg_members(int nc, const int *pairs, const int *old, int *out, hipStream_t st);
+// launch_mg_count / launch_mg_fill with the rows of coarse row I from mem[I * width ...] (-1 ends the list) and the coarse column agg[col]
+int launch_amg_count(int nc, int width, const int *mem, const int *agg, const int *ptr, const int *cols, int *count, unsigned long long *err,
+                     hipStream_t st);
+int launch_amg_fill(int dtype, int nc, int width, const int *mem, const int *agg, const void *vals, const int *ptr, const int *cols,
+                    const int *ptrc, int *colsc, void *valsc, hipStream_t st);
+// launch_mg_restrict / launch_mg_prolong through the member lists (kAmgWidth per coarse row) / the map
+int launch_amg_restrict(int dtype, int nc, const int *mem, long long ldf, long long ldc, int nrhs, const void *b, const void *w, void *bc,
+                        const void *dinvc, void *xc, void *dc, double c1, bool store_d, hipStream_t st);
+int launch_amg_prolong(int dtype, int nf, const int *agg, long long ldf, long long ldc, int nrhs, const void *e, void *x, double omega,
+                       hipStream_t st);
 struct MgHierarchy;
-struct MgParams { int nx = 1, ny = 1, nz = 1, smooth_steps = 1, min_rows = 512; double omega = 1.6; };
+// algebraic: aggregates by `passes` passes of matching at strength `theta` (cgamd_solver_set_preconditioner_amg), nx, ny, nz unused
+struct MgParams { int nx = 1, ny = 1, nz = 1, smooth_steps = 1, min_rows = 512; double omega = 1.6; bool algebraic = false; int passes = 3; double theta = 0.25; };
 int mg_build(hipStream_t st, int dt, int nu, int n, int nrhs, const SpmvPlan &plan0, long long nnz, const void *vals, const int *ptr,
              const int *cols, const MgParams &p, const std::string &who, MgHierarchy **out);
 void mg_free(MgHierarchy *h);
@@ -601,6 +631,8 @@ int mg_levels(const MgHierarchy *h);
 // info: rows, nnz, nx, ny, nz, the bits of the double lmax
 int mg_level_info(const MgHierarchy *h, int level, long long info[6]);
 int mg_level_matrix(const MgHierarchy *h, int level, int *ptr, int *cols, void *vals, hipStream_t st);
+// the map level -> level + 1 to the host (rows of the level ints; the box map of a grid hierarchy), *n_coarse = rows of level + 1
+int mg_aggregates(const MgHierarchy *h, int level, int *agg_host, int *n_coarse, hipStream_t st);
 // ---- PCG of the row-partitioned loop (vector.hip, p2p.hip): z lives in q's storage for every preconditioner; part = [2][P] partials
 // (r.z, then r.r); rho2 = two-entry parity buffer of rho = r.z (entry iter & 1), delta holds rho for cg_alpha
 // r -= alpha q ; z = m .* r (stored over q) ; partials of r.z and r.r

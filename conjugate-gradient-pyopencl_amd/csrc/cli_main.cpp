@@ -1,6 +1,6 @@
 // oclcgex -- command-line front end with the reference's argv (reference main.c:13-61):
 //     oclcgex <matrix.mtx> <nRHS> <isComplex> <nIterations> [--double] [--device N] [--quiet] [--history <file>] [--hermitian]
-//             [--mixed --tol T] [--multigrid NX NY NZ]
+//             [--mixed --tol T] [--multigrid NX NY NZ] [--amg]
 // Matrix-Market file -> symmetric storage expanded -> CSR; b[r*n+i] = (r+1)*5, x0 = 0 (main.c:41-46).
 // --hermitian: the matrix is complex Hermitian positive definite (a `hermitian` file): CG with conjugated inner products
 // (CGAMD_HERMITIAN), the history then being r_k^H r_k.  Never chosen from the file's symmetry field: the default is the reference's
@@ -9,7 +9,8 @@
 // replacement) to T ||b|| within nIterations; prints every right-hand side's iterations, status and TRUE residual, and the replacements.
 // --multigrid NX NY NZ: the rows are the nodes of an NX x NY x NZ grid numbered x fastest (NX * NY * NZ = n): PCG with one
 // aggregation-multigrid V-cycle as the preconditioner (cgamd_solver_set_preconditioner_multigrid, defaults), the history still r.r.
-// Goes with --hermitian on real matrices only (the library refuses the complex conjugated recurrence) and not with --mixed.
+// --amg: the same V-cycle on aggregates matched from the matrix itself (cgamd_solver_set_preconditioner_amg, defaults): no grid needed.
+// Both go with --hermitian on real matrices only (the library refuses the complex conjugated recurrence) and not with --mixed.
 // The reference prints nothing and discards x; this front end adds the residual history and timing.
 // Values are cast to single precision as the reference does (main.c:49-53) unless --double is given.
 // --history <file>: the whole residual history delta_k[r] = r_k.r_k (k = 0..nIterations, r < nRHS; what the reference computes and
@@ -25,12 +26,12 @@
 
 int main(int argc, char *argv[]) {
     if (argc < 5) {
-        fprintf(stderr, "Usage: %s <input matrix file> <number of RHS> <is complex> <number of iterations> [--double] [--device N] [--quiet] [--history <file>] [--hermitian] [--mixed --tol T] [--multigrid NX NY NZ]\n", argv[0]);
+        fprintf(stderr, "Usage: %s <input matrix file> <number of RHS> <is complex> <number of iterations> [--double] [--device N] [--quiet] [--history <file>] [--hermitian] [--mixed --tol T] [--multigrid NX NY NZ] [--amg]\n", argv[0]);
         return 1;
     }
     const char *path = argv[1];
     const int nRHS = atoi(argv[2]), isComplex = atoi(argv[3]), nIterations = atoi(argv[4]);
-    bool dbl = false, quiet = false, hermitian = false, mixed = false, multigrid = false;
+    bool dbl = false, quiet = false, hermitian = false, mixed = false, multigrid = false, amg = false;
     int mg_dims[3] = {0, 0, 0};
     double rel_tol = 0.;
     int device = 0;
@@ -43,6 +44,7 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "--hermitian")) hermitian = true;
         else if (!strcmp(argv[i], "--mixed")) mixed = true;
         else if (!strcmp(argv[i], "--tol") && i + 1 < argc) rel_tol = atof(argv[++i]);
+        else if (!strcmp(argv[i], "--amg")) amg = true;
         else if (!strcmp(argv[i], "--multigrid") && i + 3 < argc) {
             multigrid = true;
             for (int k = 0; k < 3; ++k) mg_dims[k] = atoi(argv[++i]);
@@ -54,6 +56,10 @@ int main(int argc, char *argv[]) {
     }
     if (multigrid && mixed) {
         fprintf(stderr, "--multigrid does not go with --mixed (the mixed solve replaces residuals, which the multigrid loop does not serve)\n");
+        return 1;
+    }
+    if (amg && (mixed || multigrid)) {
+        fprintf(stderr, "--amg goes with neither --mixed (the mixed solve replaces residuals, which the multigrid loop does not serve) nor --multigrid\n");
         return 1;
     }
     if (nRHS < 1 || nIterations < 0) { fprintf(stderr, "bad nRHS / nIterations\n"); return 1; }
@@ -98,14 +104,15 @@ int main(int argc, char *argv[]) {
                                                    m_status.data(), &m_repl);
         cgamd_mixed_destroy(m);
         if (ctx) cgamd_ctx_destroy(ctx);
-    } else if (!hermitian && !multigrid) rc = cgamd_cg(dtype, n, nnz, a.data(), b.data(), ptr, cols, x.data(), nRHS, nIterations, hist.data(), device);
+    } else if (!hermitian && !multigrid && !amg) rc = cgamd_cg(dtype, n, nnz, a.data(), b.data(), ptr, cols, x.data(), nRHS, nIterations, hist.data(), device);
     else {      // a handle of its own, created with the flag / given the preconditioner (cgamd_cg has neither): the same upload, solve and download
         cgamd_ctx *ctx = nullptr;
         cgamd_solver *s = nullptr;
         rc = cgamd_ctx_create(device, &ctx);
         if (rc == CGAMD_OK) rc = cgamd_solver_create(ctx, dtype, n, nnz, a.data(), ptr, cols, nRHS, hermitian ? CGAMD_HERMITIAN : 0, &s);
         if (rc == CGAMD_OK && multigrid) rc = cgamd_solver_set_preconditioner_multigrid(s, mg_dims[0], mg_dims[1], mg_dims[2], 0, 0., 0);
-        if (rc == CGAMD_OK && multigrid && !quiet) printf("multigrid: %d levels, %d launches per iteration\n", cgamd_solver_mg_levels(s), cgamd_solver_loop_launches(s));
+        if (rc == CGAMD_OK && amg) rc = cgamd_solver_set_preconditioner_amg(s, 0, 0., 0, 0., 0);
+        if (rc == CGAMD_OK && (multigrid || amg) && !quiet) printf("multigrid: %d levels, %d launches per iteration\n", cgamd_solver_mg_levels(s), cgamd_solver_loop_launches(s));
         if (rc == CGAMD_OK) rc = cgamd_solver_solve(s, b.data(), x.data(), nIterations, hist.data());
         cgamd_solver_destroy(s);
         if (ctx) cgamd_ctx_destroy(ctx);

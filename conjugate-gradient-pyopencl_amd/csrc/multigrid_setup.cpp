@@ -1,6 +1,8 @@
 // Aggregation multigrid preconditioner on grid systems: the hierarchy of a handle and its V-cycle as a chain of launches
 // (cgamd_solver_set_preconditioner_multigrid; kernels in multigrid.hip, the algorithm stated in include/cgamd.h and DESIGN.md).
 // The host reads back single words only: the coarse non-zero count, the error words and the Gershgorin bound of every level.
+// The algebraic entry (cgamd_solver_set_preconditioner_amg; kernels in amg.hip) builds the same hierarchy with aggregates matched
+// from the matrix: its levels carry a stored map and member lists, and the host also reads one word per matching round.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -15,6 +17,8 @@ struct MgLevel {
     int n = 0, nu = 0;          // rows the kernels work on (level 0: with the padding rows) / rows of the grid
     long long nnz = 0, ld = 0;
     MgGrid grid;                // this level's dims (nx, ny, nz) and its aggregates' (cnx, cny, cnz)
+    const int *agg = nullptr;   // algebraic hierarchy: row -> row of the next level (nu ints), and the members of every aggregate
+    const int *mem = nullptr;   // (kAmgWidth ints per row of the next level, ascending, -1 behind the last); nullptr: the box map
     const void *vals = nullptr;
     const int *ptr = nullptr, *cols = nullptr;
     SpmvPlan plan;
@@ -79,6 +83,126 @@ static int level_diagonal(MgHierarchy *h, MgLevel &L, int level, unsigned long l
     return CGAMD_OK;
 }
 
+namespace {
+// device memory of one level's setup: freed when the level is done, but for what the hierarchy keeps
+struct AmgTemps {
+    std::vector<void *> v;
+    ~AmgTemps() {
+        for (void *q : v)
+            if (q) (void)hipFree(q);
+    }
+    int get(void **q, size_t bytes, const char *what) {
+        const hipError_t e = hipMalloc(q, bytes ? bytes : 16);
+        if (e != hipSuccess)
+            return fail(CGAMD_ERR_ALLOC, std::string("hipMalloc(amg ") + what + ", " + std::to_string(bytes) + " B): " + hipGetErrorString(e));
+        v.push_back(*q);
+        return CGAMD_OK;
+    }
+    void drop(void *q) {
+        for (void *&t : v)
+            if (t && t == q) { (void)hipFree(t); t = nullptr; }
+    }
+    void keep(void *q, MgHierarchy *h) {
+        for (void *&t : v)
+            if (t && t == q) { h->owned.push_back(t); t = nullptr; }
+    }
+};
+}  // namespace
+
+// The next level of an algebraic hierarchy from its last level: up to p.passes passes of handshake matching, each on the Galerkin
+// product of the pass before; the passes kept give the composed map, the member lists and the coarse matrix (the last kept product).
+// *built = false: the level is not built (no pass kept, or the rows fall to more than 0.8 of the fine rows) and the hierarchy ends
+static int amg_coarsen(MgHierarchy *h, unsigned long long *word, int *flag, const std::string &who, hipStream_t st, MgLevel *C, bool *built) {
+    *built = false;
+    const int dt = h->dtype, level = (int)h->lv.size();
+    const size_t vs = dtype_size(dt);
+    MgLevel &F = h->lv.back();
+    const int nf = F.nu;
+    AmgTemps tmp;
+    void *smax = nullptr, *match = nullptr, *pick = nullptr, *rank = nullptr, *pmap = nullptr, *pairs = nullptr, *agg = nullptr, *formed = nullptr;
+    if (int rc = tmp.get(&smax, (size_t)nf * 8, "row maxima")) return rc;
+    if (int rc = tmp.get(&match, (size_t)nf * 4, "matching")) return rc;
+    if (int rc = tmp.get(&pick, (size_t)nf * 4, "picks")) return rc;
+    if (int rc = tmp.get(&rank, ((size_t)nf + 1) * 4, "ranks")) return rc;
+    if (int rc = tmp.get(&pmap, (size_t)nf * 4, "pass map")) return rc;
+    if (int rc = tmp.get(&pairs, (size_t)nf * 8, "pairs")) return rc;
+    if (int rc = tmp.get(&agg, (size_t)nf * 4, "map")) return rc;
+    if (int rc = tmp.get(&formed, 16, "round word")) return rc;
+
+    const void *vals = F.vals;
+    const int *ptr = F.ptr, *cols = F.cols;
+    int n = nf, kept = 0;
+    long long nnz = F.nnz;
+    void *mem = nullptr, *kp = nullptr, *kc = nullptr, *kv = nullptr;       // the member lists and the product of the passes kept
+    for (int pass = 0; pass < h->p.passes; ++pass) {
+        if (int rc = launch_amg_smax(dt, n, vals, ptr, cols, static_cast<double *>(smax), st)) return rc;
+        CG_HIP(hipMemsetAsync(match, 0xff, (size_t)n * 4, st));
+        for (int round = 0; round < kAmgMaxRounds; ++round) {
+            CG_HIP(hipMemsetAsync(formed, 0, 4, st));
+            if (int rc = launch_amg_pick(dt, n, h->p.theta, vals, ptr, cols, static_cast<const double *>(smax), static_cast<const int *>(match),
+                                         static_cast<int *>(pick), st)) return rc;
+            if (int rc = launch_amg_handshake(n, static_cast<const int *>(pick), static_cast<int *>(match), static_cast<int *>(formed), st)) return rc;
+            int any = 0;
+            CG_HIP(hipMemcpyAsync(&any, formed, 4, hipMemcpyDeviceToHost, st));
+            CG_HIP(hipStreamSynchronize(st));
+            if (!any) break;        // (a round that forms no pair leaves the state to the next one as it found it)
+        }
+        CG_HIP(hipMemsetAsync(flag, 0, 4, st));
+        if (int rc = launch_amg_roots(n, static_cast<const int *>(match), static_cast<int *>(rank), st)) return rc;
+        if (int rc = launch_mg_scan(n, static_cast<int *>(rank), flag, st)) return rc;
+        if (int rc = launch_amg_number(n, static_cast<const int *>(match), static_cast<const int *>(rank), static_cast<int *>(pmap),
+                                       static_cast<int *>(pairs), st)) return rc;
+        int nc = 0;
+        CG_HIP(hipMemcpyAsync(&nc, static_cast<int *>(rank) + n, 4, hipMemcpyDeviceToHost, st));
+        CG_HIP(hipStreamSynchronize(st));
+        if (nc < 1 || nc > n) return fail(CGAMD_ERR_HIP, who + ": level " + std::to_string(level) + ": the aggregate count is out of range");
+        // the product of the pass: rows from the pairs, columns through the pass map
+        void *ptrc = nullptr, *colsc = nullptr, *valsc = nullptr;
+        if (int rc = tmp.get(&ptrc, ((size_t)nc + 1 + 64) * 4, "row pointers")) return rc;
+        CG_HIP(hipMemsetAsync(word, 0xff, 8, st));
+        CG_HIP(hipMemsetAsync(flag, 0, 4, st));
+        if (int rc = launch_amg_count(nc, 2, static_cast<const int *>(pairs), static_cast<const int *>(pmap), ptr, cols, static_cast<int *>(ptrc),
+                                      word, st)) return rc;
+        if (int rc = launch_mg_scan(nc, static_cast<int *>(ptrc), flag, st)) return rc;
+        unsigned long long err_h = 0;
+        int back[2] = {0, 0};     // overflow flag, coarse nnz
+        CG_HIP(hipMemcpyAsync(&err_h, word, 8, hipMemcpyDeviceToHost, st));
+        CG_HIP(hipMemcpyAsync(&back[0], flag, 4, hipMemcpyDeviceToHost, st));
+        CG_HIP(hipMemcpyAsync(&back[1], static_cast<int *>(ptrc) + nc, 4, hipMemcpyDeviceToHost, st));
+        CG_HIP(hipStreamSynchronize(st));
+        if (err_h != ~0ull) break;      // a row of more than kMgMaxRow columns: this pass and the ones after it are dropped
+        if (back[0]) return fail(CGAMD_ERR_INVALID, who + ": level " + std::to_string(level) + ": the coarse matrix has more than 2^31 - 1 entries");
+        const long long nnzc = back[1];
+        if (int rc = tmp.get(&colsc, ((size_t)nnzc + 64) * 4, "columns")) return rc;
+        if (int rc = tmp.get(&valsc, ((size_t)nnzc + 64) * vs, "values")) return rc;
+        CG_HIP(hipMemsetAsync(colsc, 0, ((size_t)nnzc + 64) * 4, st));
+        CG_HIP(hipMemsetAsync(valsc, 0, ((size_t)nnzc + 64) * vs, st));
+        if (int rc = launch_amg_fill(dt, nc, 2, static_cast<const int *>(pairs), static_cast<const int *>(pmap), vals, ptr, cols,
+                                     static_cast<const int *>(ptrc), static_cast<int *>(colsc), valsc, st)) return rc;
+        // the pass is kept: the level's map and member lists take it in
+        void *mem_new = nullptr;
+        if (int rc = tmp.get(&mem_new, (size_t)nc * kAmgWidth * 4, "member lists")) return rc;
+        if (int rc = launch_amg_compose(nf, static_cast<const int *>(pmap), kept ? static_cast<const int *>(agg) : nullptr, static_cast<int *>(agg), st)) return rc;
+        if (int rc = launch_amg_members(nc, static_cast<const int *>(pairs), static_cast<const int *>(mem), static_cast<int *>(mem_new), st)) return rc;
+        CG_HIP(hipStreamSynchronize(st));
+        tmp.drop(mem); tmp.drop(kp); tmp.drop(kc); tmp.drop(kv);
+        mem = mem_new; kp = ptrc; kc = colsc; kv = valsc;
+        vals = valsc; ptr = static_cast<const int *>(ptrc); cols = static_cast<const int *>(colsc);
+        n = nc; nnz = nnzc;
+        ++kept;
+    }
+    CG_HIP(hipStreamSynchronize(st));
+    if (!kept || 5LL * n > 4LL * nf) return CGAMD_OK;
+    tmp.keep(agg, h); tmp.keep(mem, h); tmp.keep(kp, h); tmp.keep(kc, h); tmp.keep(kv, h);
+    F.agg = static_cast<const int *>(agg);
+    F.mem = static_cast<const int *>(mem);
+    C->n = C->nu = n;
+    C->nnz = nnz;
+    C->vals = kv; C->ptr = static_cast<const int *>(kp); C->cols = static_cast<const int *>(kc);
+    *built = true;
+    return CGAMD_OK;
+}
+
 int mg_build(hipStream_t st, int dt, int nu, int n, int nrhs, const SpmvPlan &plan0, long long nnz, const void *vals, const int *ptr,
              const int *cols, const MgParams &p, const std::string &who, MgHierarchy **out) {
     *out = nullptr;
@@ -99,7 +223,7 @@ int mg_build(hipStream_t st, int dt, int nu, int n, int nrhs, const SpmvPlan &pl
     h->lv.push_back(L0);
     if (int rc = level_diagonal(h, h->lv[0], 0, word, who, st)) return rc;
 
-    while (h->lv.back().nu > p.min_rows && (int)h->lv.size() < kMgMaxLevels) {
+    while (!p.algebraic && h->lv.back().nu > p.min_rows && (int)h->lv.size() < kMgMaxLevels) {
         const int level = (int)h->lv.size();
         MgGrid &g = h->lv.back().grid;
         g.cnx = (g.nx + 1) / 2; g.cny = (g.ny + 1) / 2; g.cnz = (g.nz + 1) / 2;
@@ -135,6 +259,20 @@ int mg_build(hipStream_t st, int dt, int nu, int n, int nrhs, const SpmvPlan &pl
         CG_HIP(hipMemsetAsync(valsc, 0, ((size_t)C.nnz + 64) * vs, st));
         if (int rc = launch_mg_fill(dt, g, nc, F.vals, F.ptr, F.cols, static_cast<int *>(ptrc), static_cast<int *>(colsc), valsc, st)) return rc;
         C.vals = valsc; C.ptr = static_cast<int *>(ptrc); C.cols = static_cast<int *>(colsc);
+        C.plan = make_spmv_plan(nc);
+        if (int rc = compute_spmv_plan(C.ptr, C.cols, nc, scratch, st, &C.plan)) return rc;
+        finalize_spmv_plan(&C.plan, dt, nrhs, nc, C.nnz, C.vals, C.cols);
+        h->lv.push_back(C);
+        if (int rc = level_diagonal(h, h->lv.back(), level, word, who, st)) return rc;
+    }
+    while (p.algebraic && h->lv.back().nu > p.min_rows && (int)h->lv.size() < kMgMaxLevels) {
+        const int level = (int)h->lv.size();
+        MgLevel C;
+        bool built = false;
+        if (int rc = amg_coarsen(h, word, flag, who, st, &C, &built)) return rc;
+        if (!built) break;
+        const int nc = C.nu;
+        C.ld = ((long long)nc + E - 1) / E * E;
         C.plan = make_spmv_plan(nc);
         if (int rc = compute_spmv_plan(C.ptr, C.cols, nc, scratch, st, &C.plan)) return rc;
         finalize_spmv_plan(&C.plan, dt, nrhs, nc, C.nnz, C.vals, C.cols);
@@ -208,15 +346,19 @@ static int mg_walk(const MgHierarchy *h, const void *r, void *z, hipStream_t st,
         if (l == nl - 1) break;
         const MgLevel &C = h->lv[(size_t)l + 1];
         if (int rc = spmv(L, l, x, L.w)) return rc;
-        if (cost) { ++cost->launches; cost->bytes += 2LL * nr * L.nu * V + ((2LL + (C.steps > 1)) * nr + 1) * C.n * V; }
-        else if (int rc = launch_mg_restrict(dt, L.grid, C.nu, L.ld, C.ld, nr, b, L.w, C.b, C.dinv, C.x, C.d, C.c1[0], C.steps > 1, st)) return rc;
+        if (cost) { ++cost->launches; cost->bytes += 2LL * nr * L.nu * V + ((2LL + (C.steps > 1)) * nr + 1) * C.n * V + (L.mem ? 4LL * kAmgWidth * C.n : 0); }
+        else if (L.mem) {
+            if (int rc = launch_amg_restrict(dt, C.nu, L.mem, L.ld, C.ld, nr, b, L.w, C.b, C.dinv, C.x, C.d, C.c1[0], C.steps > 1, st)) return rc;
+        } else if (int rc = launch_mg_restrict(dt, L.grid, C.nu, L.ld, C.ld, nr, b, L.w, C.b, C.dinv, C.x, C.d, C.c1[0], C.steps > 1, st)) return rc;
     }
     for (int l = nl - 2; l >= 0; --l) {
         const MgLevel &L = h->lv[(size_t)l], &C = h->lv[(size_t)l + 1];
         const void *b = l == 0 ? r : L.b;
         void *x = l == 0 ? z : L.x;
-        if (cost) { ++cost->launches; cost->bytes += 2LL * nr * L.nu * V + (long long)nr * C.n * V; }
-        else if (int rc = launch_mg_prolong(dt, L.grid, L.nu, L.ld, C.ld, nr, C.x, x, h->p.omega, st)) return rc;
+        if (cost) { ++cost->launches; cost->bytes += 2LL * nr * L.nu * V + (long long)nr * C.n * V + (L.agg ? 4LL * L.nu : 0); }
+        else if (L.agg) {
+            if (int rc = launch_amg_prolong(dt, L.nu, L.agg, L.ld, C.ld, nr, C.x, x, h->p.omega, st)) return rc;
+        } else if (int rc = launch_mg_prolong(dt, L.grid, L.nu, L.ld, C.ld, nr, C.x, x, h->p.omega, st)) return rc;
         if (int rc = spmv(L, l, x, L.w)) return rc;
         vec(L, 4 + (L.steps > 1), 1);
         if (!cost)
@@ -237,6 +379,7 @@ int mg_level_info(const MgHierarchy *h, int level, long long info[6]) {
     if (level < 0 || level >= (int)h->lv.size()) return fail(CGAMD_ERR_INVALID, "mg_level: no such level");
     const MgLevel &L = h->lv[(size_t)level];
     info[0] = L.nu; info[1] = L.nnz; info[2] = L.grid.nx; info[3] = L.grid.ny; info[4] = L.grid.nz;
+    if (h->p.algebraic) { info[2] = L.nu; info[3] = info[4] = 0; }
     std::memcpy(&info[5], &L.lmax, 8);
     return CGAMD_OK;
 }
@@ -247,6 +390,23 @@ int mg_level_matrix(const MgHierarchy *h, int level, int *ptr, int *cols, void *
     if (cols) CG_HIP(hipMemcpyAsync(cols, L.cols, (size_t)L.nnz * 4, hipMemcpyDeviceToHost, st));
     if (vals) CG_HIP(hipMemcpyAsync(vals, L.vals, (size_t)L.nnz * dtype_size(h->dtype), hipMemcpyDeviceToHost, st));
     CG_HIP(hipStreamSynchronize(st));
+    return CGAMD_OK;
+}
+int mg_aggregates(const MgHierarchy *h, int level, int *agg_host, int *n_coarse, hipStream_t st) {
+    if (level < 0 || level + 1 >= (int)h->lv.size()) return fail(CGAMD_ERR_INVALID, "mg_aggregates: no level below this one");
+    const MgLevel &L = h->lv[(size_t)level];
+    if (n_coarse) *n_coarse = h->lv[(size_t)level + 1].nu;
+    if (!agg_host) return CGAMD_OK;
+    if (L.agg) {
+        CG_HIP(hipMemcpyAsync(agg_host, L.agg, (size_t)L.nu * 4, hipMemcpyDeviceToHost, st));
+        CG_HIP(hipStreamSynchronize(st));
+        return CGAMD_OK;
+    }
+    const MgGrid &g = L.grid;       // the box map, as mg_agg computes it
+    for (int i = 0; i < L.nu; ++i) {
+        const int x = i % g.nx, t = i / g.nx, y = t % g.ny, z = t / g.ny;
+        agg_host[i] = (x >> 1) + g.cnx * ((y >> 1) + g.cny * (z >> 1));
+    }
     return CGAMD_OK;
 }
 

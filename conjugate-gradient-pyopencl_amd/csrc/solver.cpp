@@ -1190,6 +1190,29 @@ int cgamd_solver_set_preconditioner_multigrid(cgamd_solver *s, int nx, int ny, i
     TuneScope ts(&s->tune);
     return multigrid_from_matrix(s, who, p);
 }
+// the same hierarchy with aggregates matched from the matrix (amg.hip): everything downstream of mg_build is the grid entry's
+int cgamd_solver_set_preconditioner_amg(cgamd_solver *s, int passes, double strength, int smooth_steps, double over_correction, int min_rows) {
+    const std::string who = "set_preconditioner_amg";
+    if (!s) return fail(CGAMD_ERR_INVALID, who + ": solver is NULL");
+    if (s->nsys) return batched_refuses("set_preconditioner_amg");
+    if (s->herm) return herm_refuses("set_preconditioner_amg", "which the V-cycle does not serve");
+    if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, who + ": CGAMD_UNFUSED replays the reference's kernel sequence");
+    if (s->rm_ok) return fail(CGAMD_ERR_STATE, who + ": the handle keeps its right-hand sides interleaved (row-major layout)");
+    if (passes < 0 || passes > 3) return fail(CGAMD_ERR_INVALID, who + ": passes must be in 0 ... 3 (0 = the default, 3)");
+    if (!std::isfinite(strength) || strength < 0. || strength > 1.) return fail(CGAMD_ERR_INVALID, who + ": strength must be in (0, 1] (0 = the default, 0.25)");
+    if (smooth_steps < 0 || smooth_steps > 4) return fail(CGAMD_ERR_INVALID, who + ": smooth_steps must be in 0 ... 4 (0 = the default, 1)");
+    if (!std::isfinite(over_correction) || over_correction < 0.) return fail(CGAMD_ERR_INVALID, who + ": over_correction must be finite and not negative (0 = the default, 1.6)");
+    if (min_rows < 0) return fail(CGAMD_ERR_INVALID, who + ": min_rows must not be negative (0 = the default, 512)");
+    MgParams p;
+    p.algebraic = true;
+    if (passes) p.passes = passes;
+    if (strength != 0.) p.theta = strength;
+    if (smooth_steps) p.smooth_steps = smooth_steps;
+    if (over_correction != 0.) p.omega = over_correction;
+    if (min_rows) p.min_rows = min_rows;
+    TuneScope ts(&s->tune);
+    return multigrid_from_matrix(s, who, p);
+}
 int cgamd_solver_mg_levels(cgamd_solver *s) {
     if (!s) return -CGAMD_ERR_INVALID;
     return s->mg ? mg_levels(s->mg) : 0;
@@ -1208,6 +1231,11 @@ int cgamd_solver_mg_level_matrix(cgamd_solver *s, int level, int *ptr, int *cols
     if (int rc = mg_wanted(s, "mg_level_matrix")) return rc;
     CG_HIP(hipSetDevice(s->ctx->device));
     return mg_level_matrix(s->mg, level, ptr, cols, vals, s->ctx->stream);
+}
+int cgamd_solver_mg_aggregates(cgamd_solver *s, int level, int *agg_host, int *n_coarse) {
+    if (int rc = mg_wanted(s, "mg_aggregates")) return rc;
+    CG_HIP(hipSetDevice(s->ctx->device));
+    return mg_aggregates(s->mg, level, agg_host, n_coarse, s->ctx->stream);
 }
 // one V-cycle on caller vectors (nRHS * size values each, device memory, stride `size`), through buffers with the handle's padding
 int cgamd_solver_mg_apply(cgamd_solver *s, const void *r_dev, void *z_dev) {

@@ -432,6 +432,43 @@ int cgamd_solver_mg_level(cgamd_solver *s, int level, long long info[6]);
  * device pointers to nRHS * size values at stride `size`; synchronises. */
 int cgamd_solver_mg_level_matrix(cgamd_solver *s, int level, int *ptr, int *cols, void *vals);
 int cgamd_solver_mg_apply(cgamd_solver *s, const void *r_dev, void *z_dev);
+/* ---- Algebraic aggregation multigrid (csrc/amg.hip, csrc/multigrid_setup.cpp) ----
+ * The same V-cycle on a hierarchy whose aggregates are chosen FROM THE MATRIX, on the device: for a matrix that comes without a grid
+ * (a Matrix-Market file, a permuted or reordered grid matrix, a mesh or graph Laplacian) and for anisotropic or variable coefficients,
+ * where boxes coarsen across weak couplings.  Everything not said here is the contract of cgamd_solver_set_preconditioner_multigrid:
+ * the Galerkin sums, dinv and lmax, the smoother, V(l), when it takes effect, what it replaces and what removes it, the failure rule,
+ * cgamd_solver_preconditioner_source() reports 2, refresh_values / reload_matrix (the hierarchy is built again from the new values,
+ * aggregates included: the bits of a fresh handle), the handles served and refused, cgamd_solver_iterate_tol and
+ * cgamd_solver_replace_residual refused with it set, the launch count, the byte models (the cycle's vector passes now include the map
+ * reads: 32 bytes per coarse row in the restriction, 4 per fine row in the prolongation) and the 16 levels.
+ *   One PASS of deterministic handshake matching on a matrix B (n rows), strength threshold theta:
+ *     strength  s_ij = -Re(b_ij) in double for every stored entry with j != i (a column stored twice is judged entry by entry);
+ *       smax_i = the largest s_ij of row i that is > 0, else 0; entry (i, j) is strong when s_ij > 0 and s_ij >= theta * smax_i
+ *       (the product in double; a NaN is never strong).
+ *     rounds, at most 32, two launches each.  pick: every unmatched row i takes, among its strong entries whose column j was
+ *       unmatched when the round began, the one with the larger s_ij, then the larger h(i, j), then the smaller j: pick[i] = j, or -1.
+ *       handshake: i and j are matched when pick[i] == j and pick[j] == i.  h(i, j) in 32-bit unsigned arithmetic: lo = min(i, j),
+ *       hi = max(i, j), h = (lo * 0x9E3779B1) ^ hi; h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16
+ *       (not the index: by index a constant-coefficient stencil would match one pair per grid line per round).  A round that forms
+ *       no pair ends the matching (later rounds would change nothing).  Rows still unmatched stay single.
+ *     numbering  the root of an aggregate is its smaller member; coarse ids are the ranks of the roots in ascending order.  Then
+ *       B' = P^T B P by the Galerkin rules above (fine rows ascending, entries in stored order, double / complex double, rounded
+ *       once to the value type, columns ascending, structural zeros kept).  The next pass runs on B'.
+ *   One LEVEL from the matrix A_l of level l: up to `passes` passes; a pass whose product has a row of more than 64 distinct columns
+ *     is dropped together with the passes after it (the entry never returns that error: it stops coarsening instead); the passes
+ *     kept give the composed map agg (aggregates of at most 2^passes <= 8 rows) and A_{l+1} = the last kept product.  The level is
+ *     not built and the hierarchy ends at level l when no pass is kept or when 5 * rows(l + 1) > 4 * rows(l) (coarsening below 0.8:
+ *     a star, a diagonal matrix, positive off-diagonals only).  Coarsening repeats while a level has more than min_rows rows, at
+ *     most 16 levels.  Padding rows belong to no aggregate.  Errors about diagonals name the level and the row.
+ *   Restriction sums the members of an aggregate in ascending row order; prolongation reads e[agg[i]].
+ * passes 0 ... 3 (0 = 3), strength theta in (0, 1] (0 = 0.25), smooth_steps, over_correction, min_rows as in the grid entry.
+ * CGAMD_ERR_INVALID: passes outside 0 ... 3, strength negative, above 1 or not finite, and the grid entry's for the other three.
+ * cgamd_solver_mg_level reports nx = rows, ny = nz = 0 for the levels of an algebraic hierarchy. */
+int cgamd_solver_set_preconditioner_amg(cgamd_solver *s, int passes, double strength, int smooth_steps, double over_correction, int min_rows);
+/* Development entry, same standing as cgamd_solver_mg_level_matrix: the map level -> level + 1 of the hierarchy in force, `rows of the
+ * level` ints to the host, *n_coarse = rows of the next level (either pointer may be NULL); also serves a grid hierarchy (the box
+ * map).  CGAMD_ERR_INVALID on the coarsest level; synchronises. */
+int cgamd_solver_mg_aggregates(cgamd_solver *s, int level, int *agg_host, int *n_coarse);
 /* where the preconditioner in force came from -- 0: none; 1: the caller's arrays (the three array entries above, and
  * cgamd_solver_set_preconditioner_batched); 2: the matrix, built on the device; 3: the matrix, extracted on the device but factored by
  * the host route (long segments; never on a batched handle) */
