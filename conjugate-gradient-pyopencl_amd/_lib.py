@@ -121,6 +121,7 @@ def load():
         "cgamd_solver_joint_codes": (ci, [vp]),
         "cgamd_solver_row_codes": (ci, [vp]),
         "cgamd_solver_row_pipe": (ci, [vp]),
+        "cgamd_solver_row_pairs": (ci, [vp]),
         "cgamd_solver_iterate_tol": (ci, [vp, ci, ctypes.c_double, ctypes.POINTER(ci)]),
         "cgamd_solver_iterate_until": (ci, [vp, ci, ctypes.POINTER(ctypes.c_double), ci, ci, ctypes.POINTER(ci)]),
         "cgamd_solver_replace_residual": (ci, [vp, vp]),

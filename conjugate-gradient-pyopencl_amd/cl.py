@@ -564,7 +564,7 @@ class Solver:
         check(self._lib.cgamd_solver_spmv(self.handle, ptr(x), ptr(y), int(fused_dot)))
 
     SPMV_FAMILIES = ("stream", "rowblock", "vc", "vcp", "chunked", "spmm", "batched")
-    SPMV_FAMILIES_EXTRA = ("rowcode",)      # family numbers from len(SPMV_FAMILIES) on
+    SPMV_FAMILIES_EXTRA = ("rowcode", "rowpair")      # family numbers from len(SPMV_FAMILIES) on
     SPMV_FORM_FIELDS = ("family", "vec", "width", "index_bits", "value_codes", "nt", "fused", "wide", "grid", "partials")
 
     def last_spmv_form(self):
@@ -663,6 +663,12 @@ class Solver:
     def row_pipe(self):
         """row blocks whose gathers the row-coded SpMV keeps in flight per wave (1, 2 or 4); 0 when another form runs"""
         return self._lib.cgamd_solver_row_pipe(self.handle)
+
+    @property
+    def row_pairs(self):
+        """distinct row-pair patterns when the row-coded SpMV takes two rows per lane (one byte per pair of rows, one 16-byte gather
+        per slot), else 0"""
+        return self._lib.cgamd_solver_row_pairs(self.handle)
 
     def iter_bytes(self, fused=False):
         return self._lib.cgamd_solver_iter_bytes(self.handle, int(fused))

@@ -66,6 +66,11 @@ struct SpmvPlan {
     const void *rdict_val = nullptr;        // [256][8] values
     int n_patterns = 0;                     // patterns that occur (the kernel stages only these)
     const int *rcodes_for = nullptr;        // the aPointers array the codes were made from (with codes_for / vcodes_for: the matrix)
+    // one-byte ROW-PAIR codes on top of the row codes (build_row_pairs): rows 2p and 2p + 1 follow pair pattern pcodes[p] of pdict
+    const unsigned char *pcodes = nullptr;  // [ceil(n / 2) + pad]
+    const void *pdict = nullptr;            // pair_dict_* layout, n_pair_patterns entries
+    int n_pair_patterns = 0;
+    int pair_slots = 0;                     // the longest union of slots among the pair patterns (the kernel walks 7 or 8)
 };
 SpmvPlan make_spmv_plan(int n);
 // fills plan->max_span / chunk_span from the matrix structure; synchronises `st`; scratch_dev: >= 32 bytes
@@ -99,6 +104,27 @@ constexpr size_t row_dict_alloc_bytes(size_t value_size) { return row_dict_jmap_
 // the caller's rows
 int build_row_codes(int dtype, int n, int n_user, const int *ptr_dev, const unsigned char *jcodes, const int *joff, const void *jval, hipStream_t st,
                     unsigned char **rcodes_out, void **rdict_out, int *n_patterns, int *n_user_patterns);
+// ROW-PAIR patterns (index_codes.hip "ROW-PAIR codes", row_pairs.cpp): one byte per pair of rows (2p, 2p + 1) names the pair's union of
+// slots, so that the SpMV serves both rows of a slot from ONE 16-byte load.  The dictionary is ONE allocation holding np entries:
+// val0 [np][8] | val1 [np][8] | byte offsets [np][8] | masks [np] (bits 0..7: the slots row 2p uses, bits 8..15: row 2p + 1) -- what
+// the kernel stages, pair_dict_stage_bytes -- then, for refresh_pair_dict only, the index into rdict_val every value came from
+// (unsigned short [np][16]: row 2p's eight slots, then row 2p + 1's; 0xffff = slot not used by that row)
+constexpr size_t pair_dict_val1_at(int np, size_t value_size) { return (size_t)np * 8 * value_size; }
+constexpr size_t pair_dict_off_at(int np, size_t value_size) { return 2 * (size_t)np * 8 * value_size; }
+constexpr size_t pair_dict_mask_at(int np, size_t value_size) { return pair_dict_off_at(np, value_size) + (size_t)np * 8 * sizeof(int); }
+constexpr size_t pair_dict_stage_bytes(int np, size_t value_size) { return pair_dict_mask_at(np, value_size) + (size_t)np * sizeof(int); }
+constexpr size_t pair_dict_src_at(int np, size_t value_size) { return pair_dict_stage_bytes(np, value_size); }
+constexpr size_t pair_dict_alloc_bytes(int np, size_t value_size) { return pair_dict_src_at(np, value_size) + (size_t)np * 16 * sizeof(unsigned short); }
+// the LDS the staged pair dictionary may take: with it eight work-groups of the pair kernel still fit a CU (160 KB), the occupancy
+// the row form is measured at; a handle with more pair patterns than fit keeps the row form
+constexpr size_t kPairDictLdsCap = 16 * 1024;
+// *pcodes_out ((n + 1) / 2 + 64 bytes) and *pdict_out are device allocations the caller frees; both null (the handle keeps the row
+// form) beyond 256 pair patterns, beyond kPairDictLdsCap, or where a pair's union needs more than 8 slots.  With odd n the last row
+// pairs with an empty partner.  Synchronises `st`.
+int build_row_pairs(int dtype, int n, const unsigned char *rcodes, const void *rdict, int n_patterns, hipStream_t st,
+                    unsigned char **pcodes_out, void **pdict_out, int *n_pair_patterns, int *max_slots);
+// after refresh_value_dicts kept the codes: the pair dictionary's values from the rewritten rdict, IN PLACE
+int refresh_pair_dict(int dtype, int n_pair_patterns, const void *rdict, void *pdict, hipStream_t st);
 int build_value_codes(int dtype, long long nnz, const void *vals_dev, hipStream_t st, unsigned char **vcodes_out, void **vdict_out, int *n_values);
 // the values changed in place on the same pattern: one pass checks that every equal-value class of the codes is still one and, if so
 // (*kept), rewrites vdict and -- where given -- jval (behind joff) and the values of rdict IN PLACE; else nothing is written and the
@@ -147,6 +173,10 @@ struct Tuning {
     int dev_row_codes = 1;          // joint-coded SpMV: one byte per ROW naming its pattern where at most 256 row patterns occur (0 = joint codes: A/B)
     int dev_row_codes_min_mb = 32;  // ... for matrices above this size (its own threshold: index_codes_min_mb = 0 alone keeps the joint form)
     int dev_row_pipe = 0;           // row-coded SpMV: row blocks whose gathers are in flight per wave, 1, 2 or 4 (0 = the default rule, row_pipe_depth)
+    int dev_row_pairs = -1;         // row-coded SpMV: two rows per lane on one byte per PAIR of rows, one 16-byte gather per slot (1 / 0; -1 = the default rule, row_pairs_wanted)
+    int dev_row_pairs_min_mb = 256; // ... for matrices above this size (a threshold of its own, like dev_row_codes_min_mb).  256 MB: every system the
+                                    // form was measured on lies above it (300 MB, 840 MB, 8.4 GB: profiles/row_pairs/), and the handles of 85 to 151 MB
+                                    // whose CG steps are tested bit for bit (tests/test_gpu_cg_steps.py) keep recording the row form they assert
     int dev_vc_pipe = 1;            // value-coded SpMV: gathers pipelined across the row blocks of a work-group (0 = one block at a time: A/B)
     int dev_generic_spmv = 0;       // 1: the generic chunked CSR stream for every matrix (the row-block kernels' fallback, tested against them)
     int resident_lock = 1;          // 0: no per-GPU serialisation of resident launches (ranks of ONE job sharing a GPU in a rehearsal)
@@ -180,6 +210,9 @@ struct Tuning {
 // time (two measured 0.1 to 1.1 % faster in one process, but the plain benchmark did not separate it from the parent build by the
 // margin asked for, so the depth of 8-byte values stays at 1)
 inline int row_pipe_depth(int knob, size_t value_bytes) { return knob == 1 || knob == 2 || knob == 4 ? knob : value_bytes <= 4 ? 4 : 1; }
+// whether a handle builds and launches the row-pair form under dev.row_pairs = `knob`: 1 and 0 as given, anything else the default
+// rule -- by the size of a value, as measured (profiles/row_pairs/)
+inline bool row_pairs_wanted(int knob, size_t value_bytes) { return knob == 1 ? true : knob == 0 ? false : value_bytes >= 8; }
 extern Tuning g_tune;
 Tuning tune_snapshot();
 const Tuning &tune();

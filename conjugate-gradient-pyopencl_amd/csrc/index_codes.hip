@@ -5,6 +5,7 @@
 #include "spmv_device.h"
 #include "reduce_device.h"
 #include "launch_util.h"
+#include "row_pairs.h"
 
 #include <hip/hip_ext.h>
 
@@ -678,6 +679,139 @@ int refresh_value_dicts(int dtype, long long nnz, const void *vals_dev, const un
     if (dtype == CGAMD_F32) return refresh_value_dicts_impl<float>(nnz, vals_dev, vcodes, vdict, n_pairs, joff, jval, n_patterns, rdict, st, kept);
     if (dtype == CGAMD_F64) return refresh_value_dicts_impl<double>(nnz, vals_dev, vcodes, vdict, n_pairs, joff, jval, n_patterns, rdict, st, kept);
     return refresh_value_dicts_impl<float2>(nnz, vals_dev, vcodes, vdict, n_pairs, joff, jval, n_patterns, rdict, st, kept);
+}
+
+// -------------------------------------------------------------------------------------------------
+// ROW-PAIR codes: rows 2p and 2p + 1 of a stencil matrix almost always carry the same pattern, and for a slot of offset o row 2p needs
+// x[2p + o] and row 2p + 1 needs x[2p + 1 + o] -- the two halves of ONE 16-byte load.  One byte per pair names a PAIR pattern: the
+// union of the two rows' slots (merge_pair_slots, row_pairs.cpp), at most 8 of them, with the value either row multiplies and a mask
+// of the slots either row uses.  Passes: mark the (rcodes[2p], rcodes[2p + 1]) combinations that occur (the partner of a lone last
+// row is the empty pattern kPairEmpty, whether the dictionary holds one or not), read the marks and the row dictionary back, number
+// the combinations ascending and merge them on the HOST (at most 256 patterns of at most 7 slots), upload, encode.
+// -------------------------------------------------------------------------------------------------
+constexpr int kPairEmpty = 256;
+constexpr int kPairCombos = 256 * 257;
+__global__ __launch_bounds__(256) void rowpair_mark_kernel(int n, const unsigned char *__restrict__ rcodes, unsigned char *present) {
+    const long long npairs = ((long long)n + 1) / 2, stride = (long long)gridDim.x * 256;
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < npairs; p += stride) {
+        const int c0 = rcodes[2 * p], c1 = 2 * p + 1 < n ? (int)rcodes[2 * p + 1] : kPairEmpty;
+        if (!present[c0 * 257 + c1]) present[c0 * 257 + c1] = 1;
+    }
+}
+__global__ __launch_bounds__(256) void rowpair_encode_kernel(int n, const unsigned char *__restrict__ rcodes, const unsigned char *__restrict__ combo_code,
+                                                             unsigned char *__restrict__ pcodes) {
+    const long long npairs = ((long long)n + 1) / 2, stride = (long long)gridDim.x * 256;
+    for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < npairs; p += stride) {
+        const int c0 = rcodes[2 * p], c1 = 2 * p + 1 < n ? (int)rcodes[2 * p + 1] : kPairEmpty;
+        pcodes[p] = combo_code[c0 * 257 + c1];
+    }
+}
+// W: a value as bits (4 or 8 bytes).  src [np][16]: where in rval the value of (pair pattern, row of the pair, union slot) came from
+template <typename W>
+__global__ __launch_bounds__(256) void rowpair_values_kernel(int np, const W *__restrict__ rval, const unsigned short *__restrict__ src, W *val0, W *val1) {
+    for (int k = threadIdx.x; k < np * 16; k += 256) {
+        const int p = k >> 4, u = k & 7;
+        const unsigned s = src[k];
+        const W v = s == 0xffffu ? (W)0 : rval[s];
+        ((k & 8) ? val1 : val0)[p * 8 + u] = v;
+    }
+}
+static void launch_rowpair_values(size_t vs, int np, const void *rdict, char *pdict, hipStream_t st) {
+    const auto *src = reinterpret_cast<const unsigned short *>(pdict + pair_dict_src_at(np, vs));
+    if (vs == 4)
+        hipLaunchKernelGGL((rowpair_values_kernel<unsigned>), dim3(1), dim3(256), 0, st, np, static_cast<const unsigned *>(rdict), src,
+                           reinterpret_cast<unsigned *>(pdict), reinterpret_cast<unsigned *>(pdict + pair_dict_val1_at(np, vs)));
+    else
+        hipLaunchKernelGGL((rowpair_values_kernel<unsigned long long>), dim3(1), dim3(256), 0, st, np, static_cast<const unsigned long long *>(rdict), src,
+                           reinterpret_cast<unsigned long long *>(pdict), reinterpret_cast<unsigned long long *>(pdict + pair_dict_val1_at(np, vs)));
+}
+int build_row_pairs(int dtype, int n, const unsigned char *rcodes, const void *rdict, int n_patterns, hipStream_t st,
+                    unsigned char **pcodes_out, void **pdict_out, int *n_pair_patterns, int *max_slots) {
+    *pcodes_out = nullptr; *pdict_out = nullptr; *n_pair_patterns = 0; *max_slots = 0;
+    if (n < 2 || !rcodes || !rdict || n_patterns < 1 || dtype == CGAMD_C128) return CGAMD_OK;
+    const size_t vs = dtype_size(dtype);
+    unsigned char *marks = nullptr;         // present [kPairCombos], then the code of every combination [kPairCombos]
+    CG_HIP(hipMalloc((void **)&marks, 2 * (size_t)kPairCombos));
+    std::vector<unsigned char> present(kPairCombos), combo_code(kPairCombos, 0);
+    std::vector<int> roff(256 * 8), rlen(256);
+    const int grid = (int)std::min<long long>((((long long)n + 1) / 2 + 255) / 256, 4096);
+    hipError_t e = hipMemsetAsync(marks, 0, kPairCombos, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(rowpair_mark_kernel, dim3(grid), dim3(256), 0, st, n, rcodes, marks);
+        e = hipMemcpyAsync(present.data(), marks, kPairCombos, hipMemcpyDeviceToHost, st);
+    }
+    const char *rd = static_cast<const char *>(rdict);
+    if (e == hipSuccess) e = hipMemcpyAsync(roff.data(), rd + row_dict_off_at(vs), 256 * 8 * sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(rlen.data(), rd + row_dict_len_at(vs), 256 * sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    // number the combinations that occur, ascending, and merge each
+    std::vector<PairPattern> pats;
+    std::vector<int> combos;
+    bool fits = e == hipSuccess;
+    for (int c = 0; fits && c < kPairCombos; ++c) {
+        if (!present[c]) continue;
+        const int c0 = c / 257, c1 = c % 257;
+        if (pats.size() == 256 || c0 >= n_patterns || (c1 != kPairEmpty && c1 >= n_patterns)) { fits = false; break; }
+        const int len0 = rlen[c0], len1 = c1 == kPairEmpty ? 0 : rlen[c1];
+        PairPattern pp;
+        if (!merge_pair_slots(len0, &roff[c0 * 8], len1, c1 == kPairEmpty ? nullptr : &roff[c1 * 8], &pp)) { fits = false; break; }
+        combo_code[c] = (unsigned char)pats.size();
+        pats.push_back(pp);
+        combos.push_back(c);
+    }
+    const int np = (int)pats.size();
+    if (fits && (np < 1 || pair_dict_stage_bytes(np, vs) > kPairDictLdsCap)) fits = false;
+    unsigned char *pcodes = nullptr;
+    char *pdict = nullptr;
+    int slots = 0;
+    for (const PairPattern &pp : pats) slots = std::max(slots, pp.n);
+    if (fits) {
+        std::vector<char> img(pair_dict_alloc_bytes(np, vs), 0);
+        int *off = reinterpret_cast<int *>(img.data() + pair_dict_off_at(np, vs));
+        int *mask = reinterpret_cast<int *>(img.data() + pair_dict_mask_at(np, vs));
+        auto *src = reinterpret_cast<unsigned short *>(img.data() + pair_dict_src_at(np, vs));
+        for (int p = 0; p < np; ++p) {
+            const int c0 = combos[p] / 257, c1 = combos[p] % 257;
+            int m = 0;
+            for (int u = 0; u < kPairSlots; ++u) {
+                const PairPattern &pp = pats[p];
+                off[p * 8 + u] = u < pp.n ? pp.off[u] : 0;
+                const bool use0 = u < pp.n && pp.src0[u] >= 0, use1 = u < pp.n && pp.src1[u] >= 0;
+                src[p * 16 + u] = use0 ? (unsigned short)(c0 * 8 + pp.src0[u]) : (unsigned short)0xffffu;
+                src[p * 16 + 8 + u] = use1 ? (unsigned short)(c1 * 8 + pp.src1[u]) : (unsigned short)0xffffu;
+                m |= (use0 ? 1 << u : 0) | (use1 ? 256 << u : 0);
+            }
+            mask[p] = m;
+        }
+        e = hipMalloc((void **)&pcodes, ((size_t)n + 1) / 2 + 64);
+        if (e == hipSuccess) e = hipMalloc((void **)&pdict, img.size());
+        if (e == hipSuccess) e = hipMemsetAsync(pcodes + ((size_t)n + 1) / 2, 0, 64, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(pdict, img.data(), img.size(), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(marks + kPairCombos, combo_code.data(), kPairCombos, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) {
+            launch_rowpair_values(vs, np, rdict, pdict, st);
+            hipLaunchKernelGGL(rowpair_encode_kernel, dim3(grid), dim3(256), 0, st, n, rcodes, marks + kPairCombos, pcodes);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(st);      // (img and combo_code go away)
+    }
+    (void)hipFree(marks);
+    if (e != hipSuccess) {
+        if (pcodes) (void)hipFree(pcodes);
+        if (pdict) (void)hipFree(pdict);
+        return fail(CGAMD_ERR_HIP, std::string("build_row_pairs: ") + hipGetErrorString(e));
+    }
+    *pcodes_out = pcodes; *pdict_out = pdict; *n_pair_patterns = fits ? np : 0;
+    if (fits) *max_slots = slots;
+    return CGAMD_OK;
+}
+int refresh_pair_dict(int dtype, int n_pair_patterns, const void *rdict, void *pdict, hipStream_t st) {
+    if (!rdict || !pdict || n_pair_patterns < 1 || dtype == CGAMD_C128) return CGAMD_OK;
+    launch_rowpair_values(dtype_size(dtype), n_pair_patterns, rdict, static_cast<char *>(pdict), st);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(CGAMD_ERR_HIP, std::string("refresh_pair_dict: ") + hipGetErrorString(e));
+    return CGAMD_OK;
 }
 
 }  // namespace cgamd

@@ -116,6 +116,9 @@ struct cgamd_solver {
     int n_pairs = 0;
     unsigned char *rcodes = nullptr;  // one-byte row-pattern codes where at most 256 patterns of at most 7 entries occur (build_row_codes)
     void *rdict = nullptr;            // their dictionary: values, byte offsets, lengths (row_dict_bytes)
+    unsigned char *pcodes = nullptr;  // one byte per PAIR of rows on top of the row codes (build_row_pairs), and their dictionary
+    void *pdict = nullptr;
+    int n_pair_patterns = 0;
     int n_patterns = 0, n_user_patterns = 0;     // dictionary entries; patterns of the caller's rows (the appended empty rows may add one)
     // cgamd_solver_iterate_tol: tolerance of the device-side stop for the call in progress (0 = none), and what it reported
     double tol_req = 0.;
@@ -387,6 +390,10 @@ static void drop_value_codes(cgamd_solver *s) {
     s->plan.rcodes = nullptr; s->plan.rdict_len = nullptr; s->plan.rdict_off = nullptr; s->plan.rdict_val = nullptr; s->plan.n_patterns = 0;
     s->plan.rcodes_for = nullptr;
     s->n_patterns = 0; s->n_user_patterns = 0;
+    if (s->pcodes) { (void)hipFree(s->pcodes); s->pcodes = nullptr; }
+    if (s->pdict) { (void)hipFree(s->pdict); s->pdict = nullptr; }
+    s->plan.pcodes = nullptr; s->plan.pdict = nullptr; s->plan.n_pair_patterns = 0; s->plan.pair_slots = 0;
+    s->n_pair_patterns = 0;
 }
 // a handle whose SpMV reads one-byte column codes may carry codes of its values on top
 static bool value_codes_apply(const cgamd_solver *s) {
@@ -418,6 +425,13 @@ static int setup_value_codes(cgamd_solver *s) {
             s->plan.rdict_off = reinterpret_cast<const int *>(rd + row_dict_off_at(vsz));
             s->plan.rdict_len = reinterpret_cast<const int *>(rd + row_dict_len_at(vsz));
             s->plan.rcodes_for = s->ptr;
+            // ... and one byte per PAIR of rows (two rows per lane, one 16-byte gather per slot) above a threshold of its own
+            if (row_pairs_wanted(s->tune.dev_row_pairs, vsz) && s->tune.dev_row_pairs_min_mb >= 0 &&
+                matrix_bytes > ((size_t)s->tune.dev_row_pairs_min_mb << 20)) {
+                if (int rc = build_row_pairs(s->dtype, s->n, s->rcodes, s->rdict, s->n_patterns, s->ctx->stream, &s->pcodes, &s->pdict,
+                                             &s->n_pair_patterns, &s->plan.pair_slots)) return rc;
+                if (s->pcodes) { s->plan.pcodes = s->pcodes; s->plan.pdict = s->pdict; s->plan.n_pair_patterns = s->n_pair_patterns; }
+            }
         }
     }
     return CGAMD_OK;
@@ -814,6 +828,13 @@ static int refresh_codes(cgamd_solver *s) {
             drop_value_codes(s);
             return rc;
         }
+        if (kept && s->pdict) {     // the pair dictionary's values follow rdict's, in place too
+            if (int rc = refresh_pair_dict(s->dtype, s->n_pair_patterns, s->rdict, s->pdict, s->ctx->stream)) {
+                destroy_graphs(s);
+                drop_value_codes(s);
+                return rc;
+            }
+        }
         if (kept) { s->last_refresh = 1; return CGAMD_OK; }
     }
     const bool had = s->vcodes != nullptr;
@@ -886,7 +907,7 @@ int cgamd_solver_destroy(cgamd_solver *s) {
         if (s->cols) (void)hipFree(s->cols);
     }
     void *bufs[] = {s->slab, s->part_dq, s->part_rr, s->sc.alpha, s->sc.beta, s->sc.delta,
-                    s->sc.history, s->sc.iter, s->mdiag, s->part_rz, s->rho2, s->tri_coef, s->tri_part, s->tri_cstart, s->tri.maps, s->sc.stage, s->sc.ticket, s->res_sync, s->resw_sync, s->dlag, s->codes, s->dict, s->rm_pace, s->vcodes, s->vdict, s->jcodes, s->jdict_off, s->jdict_val, s->rcodes, s->rdict};
+                    s->sc.history, s->sc.iter, s->mdiag, s->part_rz, s->rho2, s->tri_coef, s->tri_part, s->tri_cstart, s->tri.maps, s->sc.stage, s->sc.ticket, s->res_sync, s->resw_sync, s->dlag, s->codes, s->dict, s->rm_pace, s->vcodes, s->vdict, s->jcodes, s->jdict_off, s->jdict_val, s->rcodes, s->rdict, s->pcodes, s->pdict};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     stop_run_free(s->stop);
@@ -1901,6 +1922,10 @@ long long cgamd_solver_spmv_moved_bytes(cgamd_solver *s) {
 int cgamd_solver_value_codes(cgamd_solver *s) { return s ? s->n_values : -CGAMD_ERR_INVALID; }
 int cgamd_solver_joint_codes(cgamd_solver *s) { return s ? (joint_form(s) ? s->n_pairs : 0) : -CGAMD_ERR_INVALID; }
 int cgamd_solver_row_codes(cgamd_solver *s) { return s ? (row_form(s) ? s->n_user_patterns : 0) : -CGAMD_ERR_INVALID; }
+int cgamd_solver_row_pairs(cgamd_solver *s) {
+    if (!s) return -CGAMD_ERR_INVALID;
+    return row_form(s) && s->plan.pcodes && row_pairs_wanted(s->tune.dev_row_pairs, dtype_size(s->dtype)) ? s->n_pair_patterns : 0;
+}
 int cgamd_solver_row_pipe(cgamd_solver *s) { return s ? (row_form(s) ? row_pipe_depth(s->tune.dev_row_pipe, dtype_size(s->dtype)) : 0) : -CGAMD_ERR_INVALID; }
 long long cgamd_solver_iter_moved_bytes(cgamd_solver *s) {
     if (!s) return 0;

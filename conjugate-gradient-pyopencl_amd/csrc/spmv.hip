@@ -715,6 +715,170 @@ __global__ __launch_bounds__(BLOCK) void spmv_rowcode_kernel(RowcodeArgs<T> a) {
 }
 
 // -------------------------------------------------------------------------------------------------
+// ROW-PAIR codes (build_row_pairs): TWO rows per lane.  For a slot of offset o row r needs x[r + o] and row r + 1 needs x[r + 1 + o]:
+// the two halves of ONE 16-byte load at byte (r + o) sizeof(T) (8 bytes for 4-byte values; raw buffer loads need dword alignment
+// only, so this holds for the +-1 slots too).  One byte per pair of rows (2p, 2p + 1) names the pair's pattern: the union of the two
+// rows' slots (at most 8; a common supersequence of the two stored sequences, so each row's own order survives), per slot the byte
+// offset, the value either row multiplies and a mask bit per row.  A lane owns rows 2t and 2t + 1 of a 512-row pass, a work-group
+// makes two passes over its four row blocks (same grid, same schedule as the row form), DEPTH passes' gathers in flight.
+// sum0 = vsel(mask0 bit u, vfma(val0_u, L_u.a, sum0), sum0), sum1 likewise on L_u.b: the products, the order and the bits of the row
+// form.  No load touches a byte outside x[0, n): the address is clamped per lane into [0, (n - 2) sizeof(T)] -- a slot row 2t + 1
+// alone uses can address element -1, one row 2t alone uses element n - 1 -- and the value a row needs (its column is valid) is taken
+// from the other half where the clamp moved the load.  y: one 16-byte store per lane (a lone last row stores its 8 bytes).
+// d.q partials, still one per 256-row block on the tree of block_sum<256>: the 64 rows of one wave of the row form sit in 32 lanes
+// x 2 components here, so v[l] += v[l + off] for off = 32 ... 2 is, per component, the lane steps 16, 8, 4, 2, 1 inside each 32-lane
+// half, and off = 1 is a + b inside the lane: a wave yields two of the old wave sums, in lanes 0 and 32.
+// -------------------------------------------------------------------------------------------------
+template <typename T> struct RowpairArgs {
+    int n, row_blocks, cycle, n_pair_patterns;
+    const T *x;
+    T *y;
+    const T *dvec;
+    typename VT<T>::acc *partials;
+    const unsigned char *pcodes;    // [(n + 1) / 2 + pad]
+    const void *pdict;              // val0 [np][8] | val1 [np][8] | byte offsets [np][8] | masks [np] (pair_dict_stage_bytes)
+};
+template <typename T> struct Two { T a, b; };
+template <typename T> CG_DEV Two<T> buf_gather2(__amdgpu_buffer_rsrc_t rs, unsigned byte_off) {
+    Two<T> r;
+    if constexpr (sizeof(T) == 4) {
+        const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(rs, byte_off, 0, 0);
+        __builtin_memcpy(&r, &w, 8);
+    } else {
+        const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(rs, byte_off, 0, 0);
+        __builtin_memcpy(&r, &w, 16);
+    }
+    return r;
+}
+// the lane steps 16, 8, 4, 2, 1 inside each 32-lane half of the wave: valid in lanes 0 and 32 (the guard of lanes_plus32 in front)
+CG_DEV double half_wave_sum(double v) {
+    const unsigned long long b0 = (unsigned long long)__double_as_longlong(v);
+    v = __longlong_as_double((long long)(((b0 >> 32) << 32) | exec_settle((unsigned)b0)));
+    v += lanes_plus16(v);
+    v += dpp_row_shl<8>(v);
+    v += dpp_row_shl<4>(v);
+    v += dpp_row_shl<2>(v);
+    v += dpp_row_shl<1>(v);
+    return v;
+}
+CG_DEV double2 half_wave_sum(double2 v) { return make_double2(half_wave_sum(v.x), half_wave_sum(v.y)); }
+constexpr int kPairPasses = kVcBlocks / 2;      // 512-row passes of a work-group
+// SLOTS: the longest union of the handle's pair patterns, 7 (the stencils whose x-runs are even) or 8
+template <typename T, int BLOCK, bool NT, bool FUSE_DOT, int DEPTH, int SLOTS>
+__global__ __launch_bounds__(BLOCK) void spmv_rowpair_kernel(RowpairArgs<T> a) {
+    using A = typename VT<T>::acc;
+    extern __shared__ __attribute__((aligned(16))) char dyn_smem[];
+    __shared__ A red[kVcBlocks][BLOCK / kWave];
+    static_assert(BLOCK == 256 && kVcBlocks == 4, "two passes of 512 rows");
+    static_assert(DEPTH == 1 || DEPTH == 2, "passes in flight");
+    static_assert(SLOTS == 7 || SLOTS == 8, "union slots");
+    const int t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
+    const int supers = (a.row_blocks + kVcBlocks - 1) / kVcBlocks;
+    const int srb = rowblock_of(blockIdx.x, supers, a.cycle);
+    if (srb < 0) return;
+    const int rb0 = srb * kVcBlocks, nb = min(kVcBlocks, a.row_blocks - rb0);
+    const int np = a.n_pair_patterns;
+    const T *sval0 = reinterpret_cast<const T *>(dyn_smem), *sval1 = sval0 + np * 8;
+    const int *soff = reinterpret_cast<const int *>(sval1 + np * 8), *smask = soff + np * 8;
+    const int npairs = (a.n + 1) / 2;
+    int code[kPairPasses];
+#pragma unroll
+    for (int p = 0; p < kPairPasses; ++p) {
+        const int q = min(rb0 * (BLOCK / 2) + p * BLOCK + t, npairs - 1);
+        code[p] = NT ? __builtin_nontemporal_load(a.pcodes + q) : a.pcodes[q];
+    }
+    {                                               // the staged part of the dictionary is one run of 4-byte words
+        const int words = np * (16 * (int)sizeof(T) + 8 * (int)sizeof(int) + (int)sizeof(int)) / 4;
+        const int *src = static_cast<const int *>(a.pdict);
+        int *dst = reinterpret_cast<int *>(dyn_smem);
+        for (int k = t; k < words; k += BLOCK) dst[k] = src[k];
+    }
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(a.x), 0, 0x7ffffffc, 0x00020000);
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t xrs_d = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(FUSE_DOT ? a.dvec : a.x), 0, 0x7ffffffc, 0x00020000);
+    __builtin_amdgcn_s_waitcnt(0);
+    __syncthreads();
+    const int top = (a.n - 2) * (int)sizeof(T);     // the last byte address a two-value load may have (n >= 2, n sizeof(T) < 2^30)
+    // one pass' gathers in flight.  lo / hi: bit u set where the clamp moved slot u's load up from element -1 / down from element
+    // n - 1 (or from further out: rows past the matrix and slots neither row uses, whose values are dropped)
+    struct Gath { Two<T> xv[SLOTS]; Two<T> dv; unsigned lo, hi; };
+    auto issue = [&](int p) -> Gath {
+        Gath g;
+        const int base = ((rb0 + 2 * p) * BLOCK + 2 * t) * (int)sizeof(T);
+        const int c = code[p];
+        const i32x4 o0 = *reinterpret_cast<const i32x4 *>(soff + c * 8), o1 = *reinterpret_cast<const i32x4 *>(soff + c * 8 + 4);
+        const int po[8] = {o0.x, o0.y, o0.z, o0.w, o1.x, o1.y, o1.z, o1.w};
+        g.lo = 0; g.hi = base > top ? 1u << 8 : 0u;     // (bit 8: the d load)
+        g.dv.a = vzero<T>(); g.dv.b = vzero<T>();
+        if (FUSE_DOT) g.dv = buf_gather2<T>(xrs_d, (unsigned)min(base, top));
+#pragma unroll
+        for (int u = 0; u < SLOTS; ++u) {
+            const int sb = base + po[u];
+            g.lo |= sb < 0 ? 1u << u : 0u;
+            g.hi |= sb > top ? 1u << u : 0u;
+            g.xv[u] = buf_gather2<T>(xrs, (unsigned)min(max(sb, 0), top));
+        }
+        return g;
+    };
+    [[maybe_unused]] A dotw[kPairPasses];
+    auto consume = [&](int p, const Gath &g) {
+        const int row0 = (rb0 + 2 * p) * BLOCK + 2 * t;
+        const int c = code[p];
+        const int mask = smask[c];
+        T v0[8], v1[8];                             // the pattern's values in 16-byte LDS reads
+        {
+            using V = typename Chunk16<T>::V;
+            constexpr int EPC = 16 / (int)sizeof(T);
+#pragma unroll
+            for (int k = 0; k < 8 / EPC; ++k) {
+                const V w0 = *reinterpret_cast<const V *>(sval0 + c * 8 + k * EPC), w1 = *reinterpret_cast<const V *>(sval1 + c * 8 + k * EPC);
+                __builtin_memcpy(&v0[k * EPC], &w0, 16);
+                __builtin_memcpy(&v1[k * EPC], &w1, 16);
+            }
+        }
+        T sum0 = vzero<T>(), sum1 = vzero<T>();
+#pragma unroll
+        for (int u = 0; u < SLOTS; ++u) {
+            const T x0 = vsel((g.hi >> u) & 1u, g.xv[u].b, g.xv[u].a);      // row 2t's value: the lower half, the upper one of a load moved down
+            const T x1 = vsel((g.lo >> u) & 1u, g.xv[u].a, g.xv[u].b);      // row 2t + 1's: the upper half, the lower one of a load moved up
+            const T n0 = vfma(v0[u], x0, sum0), n1 = vfma(v1[u], x1, sum1);
+            sum0 = vsel((mask >> u) & 1, n0, sum0);
+            sum1 = vsel((mask >> (8 + u)) & 1, n1, sum1);
+        }
+        A dot0 = vzero<A>(), dot1 = vzero<A>();
+        if (row0 + 1 < a.n) {
+            if constexpr (sizeof(T) == 4) { u32x2 w; __builtin_memcpy(&w, &sum0, 4); __builtin_memcpy(reinterpret_cast<char *>(&w) + 4, &sum1, 4); *reinterpret_cast<u32x2 *>(a.y + row0) = w; }
+            else { u32x4 w; __builtin_memcpy(&w, &sum0, 8); __builtin_memcpy(reinterpret_cast<char *>(&w) + 8, &sum1, 8); *reinterpret_cast<u32x4 *>(a.y + row0) = w; }
+            if (FUSE_DOT) { dot0 = to_acc(vmul(g.dv.a, sum0)); dot1 = to_acc(vmul(g.dv.b, sum1)); }
+        } else if (row0 < a.n) {                    // the lone last row of an odd n: its d came down with the clamp
+            a.y[row0] = sum0;
+            if (FUSE_DOT) dot0 = to_acc(vmul(vsel((g.hi >> 8) & 1u, g.dv.b, g.dv.a), sum0));
+        }
+        if (FUSE_DOT) dotw[p] = vadd(half_wave_sum(dot0), half_wave_sum(dot1));
+    };
+    Gath g[DEPTH];
+#pragma unroll
+    for (int p = 0; p < DEPTH; ++p) g[p] = issue(p);
+#pragma unroll
+    for (int p = 0; p < kPairPasses; ++p) {
+        consume(p, g[p % DEPTH]);
+        if (p + DEPTH < kPairPasses) g[p % DEPTH] = issue(p + DEPTH);
+    }
+    if (FUSE_DOT) {                         // block_sum<256> of every block behind one barrier, as in the row form
+        if ((lane & 31) == 0) {
+#pragma unroll
+            for (int p = 0; p < kPairPasses; ++p) red[2 * p + (wave >> 1)][2 * (wave & 1) + (lane >> 5)] = dotw[p];
+        }
+        __syncthreads();
+        if (t < nb) {
+            A v = red[t][0];
+#pragma unroll
+            for (int w = 1; w < BLOCK / kWave; ++w) v = vadd(v, red[t][w]);
+            a.partials[rb0 + t] = v;
+        }
+    }
+}
+
+// -------------------------------------------------------------------------------------------------
 // The same kernel for DENSER rows (a 256-row slice no longer fits LDS: > ~21 non-zeros per row in fp64).  The work-group
 // still owns 256 rows and writes one d.q partial, but stages and walks them in LPR chunks of 256/LPR rows, LPR = 2, 4 or
 // 8 lanes per row: lane l of a row takes entries s+l, s+l+LPR, ... (consecutive lanes -> consecutive entries -> for
@@ -1172,7 +1336,35 @@ static int spmv_impl(const SpmvPlan &plan, int n, long long nnz, const void *val
                 // ... and where at most 256 (offset, value) pairs occur: one joint code byte per non-zero
                 const bool joint = pipe && plan.jcodes && tune().dev_joint_codes != 0;
                 // ... and where the rows follow at most 256 patterns: one byte per ROW (build_row_codes), no row pointers and no code staging
-                if (joint && plan.rcodes && plan.rcodes_for == ptr && tune().dev_row_codes != 0) {
+                const bool rowform = joint && plan.rcodes && plan.rcodes_for == ptr && tune().dev_row_codes != 0;
+                // ... and two rows per lane on one byte per PAIR of rows (build_row_pairs) where the vectors allow 16-byte accesses
+                // (a caller's Solver.spmv vectors may not: the row form takes those)
+                if (rowform && plan.pcodes && plan.pdict && plan.n_pair_patterns > 0 && row_pairs_wanted(tune().dev_row_pairs, sizeof(T)) && n >= 2 &&
+                    aligned16(a.x) && aligned16(a.y) && (!fuse || aligned16(a.dvec))) {
+                    RowpairArgs<T> pa;
+                    pa.n = n; pa.row_blocks = plan.row_blocks; pa.cycle = cyc; pa.n_pair_patterns = plan.n_pair_patterns;
+                    pa.x = a.x; pa.y = a.y; pa.dvec = a.dvec; pa.partials = a.partials;
+                    pa.pcodes = plan.pcodes; pa.pdict = plan.pdict;
+                    const size_t ldsp = pair_dict_stage_bytes(plan.n_pair_patterns, sizeof(T));
+                    record_form(8, true, unroll, 8, 3, nt, fuse, false, gvc.x, plan.row_blocks);
+#define CG_RP(DEPTH, SLOTS)                                                                                             \
+    do {                                                                                                                \
+        if (nt) {                                                                                                \
+            if (fuse) CG_LAUNCH_EV((spmv_rowpair_kernel<T, kBlock, true, true, DEPTH, SLOTS>), gvc, block, ldsp, st, pa);   \
+            else CG_LAUNCH_EV((spmv_rowpair_kernel<T, kBlock, true, false, DEPTH, SLOTS>), gvc, block, ldsp, st, pa);       \
+        } else {                                                                                                        \
+            if (fuse) CG_LAUNCH_EV((spmv_rowpair_kernel<T, kBlock, false, true, DEPTH, SLOTS>), gvc, block, ldsp, st, pa);  \
+            else CG_LAUNCH_EV((spmv_rowpair_kernel<T, kBlock, false, false, DEPTH, SLOTS>), gvc, block, ldsp, st, pa);      \
+        }                                                                                                               \
+    } while (0)
+                    // passes whose gathers are in flight per wave: dev.row_pipe's depth, 4 meaning 2 here
+                    const int depth = std::min(2, row_pipe_depth(tune().dev_row_pipe, sizeof(T)));
+                    if (plan.pair_slots <= 7) { if (depth == 1) CG_RP(1, 7); else CG_RP(2, 7); }
+                    else { if (depth == 1) CG_RP(1, 8); else CG_RP(2, 8); }
+#undef CG_RP
+                    return check_launch("spmv_rowpair");
+                }
+                if (rowform) {
                     RowcodeArgs<T> ra;
                     ra.n = n; ra.row_blocks = plan.row_blocks; ra.cycle = cyc; ra.n_patterns = plan.n_patterns;
                     ra.x = a.x; ra.y = a.y; ra.dvec = a.dvec; ra.partials = a.partials;

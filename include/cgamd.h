@@ -560,6 +560,12 @@ int cgamd_solver_row_codes(cgamd_solver *s);
  * the default, or what cgamd_tune("dev.row_pipe") forced when the handle was created.  Every depth forms the same bits.  0: the handle
  * does not run the row-coded form. */
 int cgamd_solver_row_pipe(cgamd_solver *s);
+/* the number of row-PAIR patterns of a handle whose row-coded SpMV takes two rows per lane: one byte per pair of rows (2p, 2p + 1)
+ * names the union of the two rows' slots, and one 16-byte load per slot serves both rows.  Same products in the same order per row:
+ * same bits.  0: the row form (or another) runs -- cgamd_tune("dev.row_pairs", 0), a matrix below dev.row_pairs_min_mb, more than
+ * 256 pair patterns, or a pair whose union needs more than 8 slots.  cgamd_last_spmv_form reports the pair form as family 8; a
+ * launch whose vectors are not 16-byte aligned runs the row form (family 7). */
+int cgamd_solver_row_pairs(cgamd_solver *s);
 int cgamd_transpose(cgamd_ctx *ctx, int dtype, int rows, int cols, const void *in, void *out);
 /* algorithmic HBM bytes of one SpMV / one CG iteration of this solver (SURVEY §8d formulae: 14 vector passes for the
  * reference's op structure, 11 for its "fused minimum"; the default loop here moves 10) */
