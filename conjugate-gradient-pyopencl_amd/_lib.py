@@ -132,6 +132,11 @@ def load():
         "cgamd_mixed_solve": (ci, [vp, vp, vp, ci, ctypes.POINTER(ctypes.c_double), ci, ci, ctypes.c_double, ci, ci, ctypes.POINTER(ci),
                                    ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci), ctypes.POINTER(ci)]),
         "cgamd_mixed_scales": (ci, [vp, ctypes.POINTER(ctypes.c_double)]),
+        "cgamd_mixed_accumulate": (ci, [vp, ci, ci, vp, ll, vp, ll, vp, vp, ci]),
+        "cgamd_mixed_round_down": (ci, [vp, ci, ci, vp, ll, vp, ll, vp, ci]),
+        "cgamd_mixed_norm2_grid": (ci, [ci, ci]),
+        "cgamd_mixed_norm2": (ci, [vp, ci, ci, vp, ll, ci, vp, vp]),
+        "cgamd_mixed_round_values": (ci, [vp, ci, ll, vp, vp]),
         "cgamd_transpose": (ci, [vp, ci, ci, ci, vp, vp]),
         "cgamd_solver_spmv_bytes": (ll, [vp]),
         "cgamd_solver_iter_bytes": (ll, [vp, ci]),

@@ -100,6 +100,52 @@ int cgamd_mixed_scales(cgamd_mixed *m, double *scales) {
     return CGAMD_OK;
 }
 
+// ---- the four streaming kernels as stateless entries (include/cgamd.h "Mixed precision: the kernels"): thin wrappers over the
+// launch_mixed_* the solve calls, with leading dimensions and pointers left to the caller.  What can be judged without a device is
+// judged first, the context last.
+static int mixed_op(cgamd_ctx *ctx, int dtype_hi, long long size, int nRHS, const char *what) {
+    if (dtype_hi != CGAMD_F64 && dtype_hi != CGAMD_C128) return fail(CGAMD_ERR_INVALID, std::string(what) + ": dtype_hi must be CGAMD_F64 or CGAMD_C128");
+    if (size < 0 || nRHS < 1) return fail(CGAMD_ERR_INVALID, std::string(what) + ": bad size/nRHS");
+    if (!ctx) return fail(CGAMD_ERR_INVALID, std::string(what) + ": ctx is NULL");
+    thread_hip_setup();
+    CG_HIP(hipSetDevice(ctx->device));
+    return CGAMD_OK;
+}
+
+int cgamd_mixed_accumulate(cgamd_ctx *ctx, int dtype_hi, int size, void *x_hi, long long ld_hi, const void *x_lo, long long ld_lo,
+                           const double *scale, const int *mask, int nRHS) {
+    if (!x_hi || !x_lo || !scale || !mask) return fail(CGAMD_ERR_INVALID, "mixed_accumulate: null pointer");
+    if (ld_hi < size || ld_lo < size) return fail(CGAMD_ERR_INVALID, "mixed_accumulate: leading dimension below size");
+    if (int rc = mixed_op(ctx, dtype_hi, size, nRHS, "mixed_accumulate")) return rc;
+    return launch_mixed_accumulate(dtype_hi, size, x_hi, ld_hi, x_lo, ld_lo, scale, mask, nRHS, ctx->stream);
+}
+
+int cgamd_mixed_round_down(cgamd_ctx *ctx, int dtype_hi, int size, const void *r_hi, long long ld_hi, void *r_lo, long long ld_lo,
+                           const double *inv_scale, int nRHS) {
+    if (!r_hi || !r_lo || !inv_scale) return fail(CGAMD_ERR_INVALID, "mixed_round_down: null pointer");
+    if (ld_hi < size || ld_lo < size) return fail(CGAMD_ERR_INVALID, "mixed_round_down: leading dimension below size");
+    if (int rc = mixed_op(ctx, dtype_hi, size, nRHS, "mixed_round_down")) return rc;
+    return launch_mixed_round_down(dtype_hi, size, r_hi, ld_hi, r_lo, ld_lo, inv_scale, nRHS, ctx->stream);
+}
+
+int cgamd_mixed_norm2_grid(int dtype_hi, int size) {
+    if ((dtype_hi != CGAMD_F64 && dtype_hi != CGAMD_C128) || size < 1) return 0;
+    return mixed_norm2_grid(dtype_hi, size);
+}
+
+int cgamd_mixed_norm2(cgamd_ctx *ctx, int dtype_hi, int size, const void *v, long long ld, int nRHS, double *partials, double *out) {
+    if (!v || !partials || !out) return fail(CGAMD_ERR_INVALID, "mixed_norm2: null pointer");
+    if (ld < size) return fail(CGAMD_ERR_INVALID, "mixed_norm2: leading dimension below size");
+    if (int rc = mixed_op(ctx, dtype_hi, size, nRHS, "mixed_norm2")) return rc;
+    return launch_mixed_norm2(dtype_hi, size, v, ld, nRHS, partials, out, ctx->stream);
+}
+
+int cgamd_mixed_round_values(cgamd_ctx *ctx, int dtype_hi, long long count, const void *hi, void *lo) {
+    if (!hi || !lo) return fail(CGAMD_ERR_INVALID, "mixed_round_values: null pointer");
+    if (int rc = mixed_op(ctx, dtype_hi, count, 1, "mixed_round_values")) return rc;
+    return launch_mixed_round_values(dtype_hi, count, hi, lo, ctx->stream);
+}
+
 int cgamd_mixed_solve(cgamd_mixed *m, const void *b, void *x, int on_device, const double *tol, int nTol, int maxIterations, double delta,
                       int maxSegment, int checkEvery, int *iterations, double *resnorm, int *status, int *replacements) {
     if (!m || !b || !x || !tol || !iterations || !resnorm || !status || !replacements)

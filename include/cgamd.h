@@ -620,6 +620,41 @@ cgamd_solver *cgamd_mixed_inner(cgamd_mixed *m);
 int cgamd_mixed_solve(cgamd_mixed *m, const void *b, void *x, int on_device, const double *tol, int nTol, int maxIterations, double delta,
                       int maxSegment, int checkEvery, int *iterations, double *resnorm, int *status, int *replacements);
 int cgamd_mixed_scales(cgamd_mixed *m, double *scales);
+/* ---- Mixed precision: the kernels (csrc/mixed.hip).  The four streaming kernels between the hi and the lo side as stateless
+ * entries, the launches cgamd_mixed_solve itself makes.  All pointers are DEVICE pointers; a call is enqueued on the ctx stream and
+ * does not synchronise.  dtype_hi: CGAMD_F64 (lo: float) or CGAMD_C128 (lo: complex64).  Every operation is real and component-wise:
+ * a column of `size` values is m = size * R real lanes, R = 1 (CGAMD_F64) or 2 (CGAMD_C128).  Column r of an array starts r * ld
+ * VALUES (not lanes) after its pointer; ld >= size.  The library is built with -ffp-contract=off: every product and every sum below
+ * is one IEEE operation in double, every conversion to float one rounding to nearest-even with gradual underflow (a result below
+ * 2^-126 is a float subnormal, not zero), overflow to +-inf, NaN to NaN, -0 to -0.
+ * THE TWO FORMS.  A kernel runs its 16-byte form -- lanes 4 q .. 4 q + 3 of a column as one float4 and two double2 accesses, q <
+ * m / 4, and the m % 4 lanes left as a scalar tail -- when every array pointer of the call is 16-byte aligned and, where nRHS > 1,
+ * every leading dimension is a whole number of 16-byte packs (ld_hi * 8 R and ld_lo * 4 R both multiples of 16).  Otherwise the scalar
+ * form runs, lane by lane.  The element-wise results are the same bits in both forms; the order of the norm's sum is not.
+ * cgamd_mixed_accumulate: x_hi[i] = x_hi[i] + scale[r] * (double)x_lo[i] per lane, i < m, for the columns with mask[r] != 0: two
+ * roundings at most -- the product, exact when scale[r] is a power of two and the product neither overflows nor underflows, and the
+ * sum.  A column with mask[r] == 0 is NEITHER READ NOR WRITTEN, on either side.  Nothing beyond lane m of a column is touched.
+ * cgamd_mixed_round_down: r_lo[i] = (float)(r_hi[i] * inv_scale[r]), i < m: the product rounds once in double (not at all for a power
+ * of two in range), the conversion once.  The lo side's padding, values size <= i < ld_lo of EVERY column (the last one too: r_lo
+ * holds nRHS * ld_lo values), is written as +0.  The hi side is only read.
+ * cgamd_mixed_norm2: out[r] = sum of v[i]^2 over the m lanes of column r (the conjugated norm, re^2 + im^2), in double, in a fixed
+ * order: G = cgamd_mixed_norm2_grid(dtype_hi, size) = min(1024, ceil(m / 4096)) work-groups of 256 threads per column.  Thread t of
+ * work-group g starts from +0 and adds, with T = 256 g + t and S = 256 G: 16-byte form -- the quads q = T, T + S, ... < m / 4, the
+ * four squares of a quad in lane order, then the tail lanes 4 (m / 4) + T (T < m % 4); scalar form -- the lanes T, T + S, ... < m.
+ * Then the work-group's 256 values are added by the wave tree v[l] += v[l + off], off = 32 .. 1, per 64 lanes, and the four wave sums
+ * as ((w0 + w1) + w2) + w3: partials[r * G + g].  One thread then adds the G partials of a column from +0 in index order: out[r].
+ * No atomics: the same bits on every run.  partials: nRHS * G doubles, written in full.  cgamd_mixed_norm2_grid: 0 for a dtype_hi
+ * that is not served or size < 1 (no device is touched).
+ * cgamd_mixed_round_values: lo[j] = (float)hi[j] over count * R lanes, one rounding each; 16-byte form when both pointers are aligned.
+ * size (count) == 0: CGAMD_OK, nothing is launched.  CGAMD_ERR_INVALID, judged in this order and before a device is touched: a NULL
+ * array pointer, a leading dimension below size, a dtype_hi other than the two, size < 0 or nRHS < 1, ctx == NULL. */
+int cgamd_mixed_accumulate(cgamd_ctx *ctx, int dtype_hi, int size, void *x_hi, long long ld_hi, const void *x_lo, long long ld_lo,
+                           const double *scale, const int *mask, int nRHS);
+int cgamd_mixed_round_down(cgamd_ctx *ctx, int dtype_hi, int size, const void *r_hi, long long ld_hi, void *r_lo, long long ld_lo,
+                           const double *inv_scale, int nRHS);
+int cgamd_mixed_norm2_grid(int dtype_hi, int size);
+int cgamd_mixed_norm2(cgamd_ctx *ctx, int dtype_hi, int size, const void *v, long long ld, int nRHS, double *partials, double *out);
+int cgamd_mixed_round_values(cgamd_ctx *ctx, int dtype_hi, long long count, const void *hi, void *lo);
 
 /* one-call typed solve on host arrays: cg() generalised to all four dtypes, with history and status */
 int cgamd_cg(int dtype, int size, long long nnz, const void *aValues, const void *b, const int *aPointers,

@@ -7,7 +7,11 @@ each product and each sum within eps: derived here, not chosen.
 
 The iteration caps (1.3 x the fp64 handle's count; 2.0 x for the complex Helmholtz system) are conditions, not measurements: they keep a
 broken replacement -- one that loses the direction and so restarts the Krylov space -- from passing as "converged eventually".  The
-numpy restatement (tests/mixed_ref.py) gives 1.00 - 1.17 and 1.53 - 1.61 on these inputs."""
+numpy restatement (tests/mixed_ref.py) gives 1.00 - 1.17 and 1.53 - 1.61 on these inputs.
+
+The second half pins the solve's bookkeeping, which a self-correcting scheme hides from a residual check: the mask and the freeze
+(columns that finish segments apart), columns done at the start, a non-finite column, one segment against the accumulate rule, and
+the segment cap with the budget.  The kernels themselves are held bit for bit in tests/test_gpu_mixed_kernels.py."""
 import os
 import subprocess
 
@@ -15,6 +19,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import mixed_kernel_ref
 import mixed_ref
 
 pytestmark = pytest.mark.gpu
@@ -217,6 +222,150 @@ def test_budget(pkg, gpu):
     res, slack = host_residual(csr, b, x)
     assert info.status.tolist() == [1] and int(info.iterations[0]) <= 20
     assert np.all(np.isfinite(x)) and abs(info.resnorm[0] - res) <= slack
+
+
+# ---- the solve's bookkeeping: masks, frozen columns, segments and the budget (33 x 29, b of seed 3) -------------------------------------
+def check_column(csr, b, x, tol, info, k):
+    """the host residual check of this file on column k"""
+    res, slack = host_residual(csr, b, x)
+    assert info.status[k] == 0 and res <= tol + slack and abs(info.resnorm[k] - res) <= slack, (k, info, res, tol, slack)
+
+
+def test_columns_that_finish_segments_apart_keep_the_bits_of_their_own_solve(pkg, gpu):
+    """V: the same b in three columns with tolerances 1e-10, 1e-4, 1e-7 ||b||; U_k: tolerance k in all three.  A stopped column is
+    frozen at its stopping iteration, a finished one is masked out of the accumulation, and a segment's threshold depends on the
+    column's own history only: column k of V is column k of U_k, in every bit"""
+    ctx = gpu[0]
+    csr = system("33x29")
+    n = len(csr[0]) - 1
+    b = rhs(n)
+    B = np.tile(b, 3)
+    tols = np.array([1e-10, 1e-4, 1e-7]) * udot_norm(b)
+    m = mixed(pkg, ctx, csr, nrhs=3)
+    xv, V = m.solve(B, tol=tols, maxit=4000)
+    # the header's step 4 on V's last segment, read from the inner handle (maxit 0: the counts as they stand): the two columns that
+    # were finished before it stopped after one iteration, the open one ran on
+    last = m.inner.iterate_until(1.0, 0)
+    print(f"  the inner handle's counts of V's last segment: {last.tolist()}")
+    assert last[1] == 1 and last[2] == 1 and last[0] > 1 and last[0] == m.inner.iterations_done()
+    U = [m.solve(B, tol=np.full(3, t), maxit=4000) for t in tols]
+    m.close()
+    print(f"  V: {V}")
+    for k, (_, u) in enumerate(U):
+        print(f"  U_{k}: {u}")
+    # not vacuous: the columns of V finish in different segments, so the mask of its later accumulations is partly clear
+    assert len(set(V.iterations.tolist())) == 3, V
+    assert V.replacements > U[1][1].replacements, (V, U[1][1])
+    xv = xv.reshape(3, n)
+    for k, (xu, u) in enumerate(U):
+        xu = xu.reshape(3, n)
+        assert xv[k].tobytes() == xu[k].tobytes(), k
+        assert V.iterations[k] == u.iterations[k] and V.status[k] == u.status[k] == 0 and V.scales[k] == u.scales[k], (k, V, u)
+        assert V.resnorm[k:k + 1].tobytes() == u.resnorm[k:k + 1].tobytes(), (k, V, u)
+        check_column(csr, b, xv[k], tols[k], V, k)
+
+
+def test_columns_done_at_the_start_beside_an_open_one(pkg, gpu):
+    ctx = gpu[0]
+    csr = system("33x29")
+    n = len(csr[0]) - 1
+    b = rhs(n)
+    tol = 1e-10 * udot_norm(b)
+    m1 = mixed(pkg, ctx, csr)
+    solved_x, info1 = m1.solve(b, tol=tol, maxit=4000)
+    m1.close()
+    _, slack = host_residual(csr, b, solved_x)
+    assert info1.status.tolist() == [0]
+    B = np.stack([b, np.zeros(n), b])
+    X0 = np.stack([np.zeros(n), np.zeros(n), solved_x])
+    tols = np.array([tol, tol, 2 * (tol + slack)])
+    m = mixed(pkg, ctx, csr, nrhs=3)
+    x, info = m.solve(B.reshape(-1), x0=X0.reshape(-1), tol=tols, maxit=4000)
+    m.close()
+    print(f"  {info}")
+    x = x.reshape(3, n)
+    assert info.status.tolist() == [0, 0, 0] and info.iterations[1] == 0 and info.iterations[2] == 0 and info.iterations[0] > 0
+    assert x[1].tobytes() == X0[1].tobytes() and x[2].tobytes() == X0[2].tobytes()
+    assert info.resnorm[1] == 0.0
+    check_column(csr, b, x[0], tol, info, 0)
+
+
+def test_a_non_finite_column_beside_converging_ones(pkg, gpu):
+    ctx = gpu[0]
+    csr = system("33x29")
+    n = len(csr[0]) - 1
+    B = np.stack([rhs(n), rhs(n), rhs(n, 4)])
+    B[1, 311] = np.inf
+    X0 = np.stack([np.zeros(n), np.random.default_rng(8).standard_normal(n), np.zeros(n)])
+    tols = np.array([1e-10 * udot_norm(B[0]), 1e-10 * udot_norm(B[0]), 1e-10 * udot_norm(B[2])])
+    m = mixed(pkg, ctx, csr, nrhs=3)
+    x, info = m.solve(B.reshape(-1), x0=X0.reshape(-1), tol=tols, maxit=4000)
+    m.close()
+    print(f"  {info}")
+    x = x.reshape(3, n)
+    assert info.status.tolist() == [0, 2, 0] and info.iterations[1] == 0 and not np.isfinite(info.resnorm[1])
+    assert x[1].tobytes() == X0[1].tobytes()
+    for k in (0, 2):
+        check_column(csr, B[k], x[k], tols[k], info, k)
+
+
+def one_segment(pkg, m, n, nrhs, b, x0, tol):
+    """maxit = 5 and delta = 1e-30: one segment, which ends at its cap.  What the solve returns is then x0 with the inner handle's x
+    added by the rule of the accumulate kernel (tests/mixed_kernel_ref.py), on the real lanes, in every bit"""
+    x, info = m.solve(b, x0=x0, tol=tol, maxit=5, delta=1e-30)
+    assert info.replacements == 1 and info.iterations.tolist() == [5] * nrhs and info.status.tolist() == [1] * nrhs, info
+    x_lo = m.inner.x()
+    assert x_lo.dtype == (np.complex64 if x.dtype.kind == "c" else np.float32) and np.all(np.isfinite(x_lo.view(np.float32))) and np.any(x_lo != 0)
+    lanes = lambda a, t: np.ascontiguousarray(a).view(t).reshape(nrhs, -1)
+    want = mixed_kernel_ref.accumulate(lanes(np.asarray(x0, dtype=x.dtype), np.float64), lanes(x_lo, np.float32), info.scales, [1] * nrhs)
+    assert lanes(x, np.float64).tobytes() == want.tobytes(), info
+    assert x.tobytes() != np.asarray(x0, dtype=x.dtype).tobytes()
+
+
+@pytest.mark.parametrize("nrhs", [1, 3])
+def test_one_segment_is_x0_plus_the_scaled_inner_x(pkg, gpu, nrhs):
+    ctx = gpu[0]
+    csr = system("33x29")
+    n = len(csr[0]) - 1
+    b = rhs(n)
+    B = np.concatenate([b * f for f in (1.0, 2.0 ** 11 * 1.1, 2.0 ** -9 * 0.9)[:nrhs]])
+    x0 = np.random.default_rng(11).standard_normal(n * nrhs)
+    m = mixed(pkg, ctx, csr, nrhs=nrhs)
+    one_segment(pkg, m, n, nrhs, B, x0, 1e-10 * udot_norm(b) * 2.0 ** -9)
+    m.close()
+
+
+def test_one_segment_complex(pkg, gpu):
+    """the same on helm_fe_var(16) in complex128"""
+    ctx, L = gpu[0], pkg._lib
+    N = 16
+    indptr, indices, data = pkg.generators.helm_fe_var(ctx, N, 12.0, None, 0.15, dtype=np.complex128)
+    b = pkg.generators.rhsA(ctx, N, 12.0, dtype=np.complex128).cpu().numpy()
+    rng = np.random.default_rng(12)
+    x0 = 1e-3 * (rng.standard_normal(N * N) + 1j * rng.standard_normal(N * N))
+    m = pkg.MixedSolver(ctx, N * N, int(data.numel()), data, indptr, indices, 1, flags=L.MATRIX_ON_DEVICE, dtype=np.complex128)
+    one_segment(pkg, m, N * N, 1, b, x0, 1e-12 * udot_norm(b))
+    m.close()
+
+
+def test_segments_and_the_budget(pkg, gpu):
+    """delta = 1e-30 and a tolerance out of reach: a segment ends only at its cap.  max_segment = 7 and maxit = 40: segments of
+    7, 7, 7, 7, 7 and 5 iterations -- the budget is the sum of the inner handle's counts"""
+    ctx = gpu[0]
+    csr = system("33x29")
+    n = len(csr[0]) - 1
+    b = rhs(n)
+    m = mixed(pkg, ctx, csr)
+    runs = [m.solve(b, tol=1e-30 * udot_norm(b), maxit=40, delta=1e-30, max_segment=7, check_every=ce) for ce in (1, 3, 8)]
+    m.close()
+    x, info = runs[0]
+    print(f"  {info}")
+    assert info.status.tolist() == [1] and info.iterations.tolist() == [40] and info.replacements == -(-40 // 7)
+    res, slack = host_residual(csr, b, x)
+    assert abs(info.resnorm[0] - res) <= slack, (info, res, slack)
+    for x2, i2 in runs[1:]:
+        assert x2.tobytes() == x.tobytes() and i2.resnorm.tobytes() == info.resnorm.tobytes()
+        assert i2.iterations.tolist() == [40] and i2.replacements == info.replacements and i2.status.tolist() == [1]
 
 
 def test_a_line_preconditioner_on_the_inner_handle_is_refused(pkg, gpu):
