@@ -149,6 +149,15 @@ def load():
         "cgamd_solver_refresh_values": (ci, [vp, vp, ci]),
         "cgamd_solver_last_refresh": (ci, [vp]),
         "cgamd_solver_graph_captures": (ci, [vp]),
+        "cgamd_solver_projection_enable": (ci, [vp, ci, ctypes.c_double]),
+        "cgamd_solver_projection_count": (ci, [vp]),
+        "cgamd_solver_projection_clear": (ci, [vp]),
+        "cgamd_solver_set_rhs_projected": (ci, [vp, vp, ci]),
+        "cgamd_solver_projection_update": (ci, [vp, ctypes.POINTER(ci)]),
+        "cgamd_solver_projection_state": (ci, [vp, ci, ci, vp]),
+        "cgamd_projection_dots": (ci, [vp, ci, ci, ll, ci, ctypes.c_uint, vp, ll, vp, ci, vp]),
+        "cgamd_projection_combine": (ci, [vp, ci, ci, ll, ci, ctypes.c_uint, vp, ll, vp, vp, ci, vp, ci]),
+        "cgamd_projection_dots_grid": (ci, [ci, ci]),
         "cgamd_gen_laplace3d": (ci, [vp, ci, ci, ci, ci, ll, ll, vp, vp, vp, ctypes.POINTER(ll)]),
         "cgamd_gen_poisson2d": (ci, [vp, ci, ci, vp, vp, vp, ctypes.POINTER(ll)]),
         "cgamd_gen_helm_fe_var": (ci, [vp, ci, ci, ctypes.c_double, vp, ctypes.c_double, ci, ci, vp, vp, vp, ctypes.POINTER(ll)]),

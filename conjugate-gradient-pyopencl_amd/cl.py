@@ -369,6 +369,54 @@ class Solver:
                 x0 = np.ascontiguousarray(np.asarray(x0).reshape(-1), dtype=self.dtype)
         check(self._lib.cgamd_solver_set_rhs(self.handle, ptr(b), ptr(x0), int(on_device)))
 
+    # ---- solution projection (include/cgamd.h "Solution projection"): start each solve from the span of the earlier ones
+    def enable_projection(self, capacity, drop_tol=0.0):
+        """Keep up to `capacity` (1 ... 32) A-orthonormal vectors per right-hand-side column spanning the recent solutions
+        (cgamd_solver_projection_enable); 0 disables the feature and frees the storage.  A vector whose A-norm squared is not above
+        drop_tol^2 |<x, A x>| is not stored.  refresh_values and reload_matrix clear the basis."""
+        check(self._lib.cgamd_solver_projection_enable(self.handle, int(capacity), float(drop_tol)))
+        self._projection_capacity = int(capacity)
+
+    def projection_count(self):
+        """slots held, 0 ... capacity"""
+        got = self._lib.cgamd_solver_projection_count(self.handle)
+        if got < 0:
+            check(-got)
+        return got
+
+    def projection_clear(self):
+        check(self._lib.cgamd_solver_projection_clear(self.handle))
+
+    def set_rhs_projected(self, b, on_device=False):
+        """set_rhs(b, x0) with x0 the A-projection of the solution onto the span of the vectors held (x0 = 0 with none)"""
+        if not on_device:
+            b = np.ascontiguousarray(np.asarray(b).reshape(-1), dtype=self.dtype)
+        check(self._lib.cgamd_solver_set_rhs_projected(self.handle, ptr(b), int(on_device)))
+
+    def projection_update(self):
+        """Add what the solve found beyond the span (after iterate / iterate_until of a right-hand side set by set_rhs_projected);
+        returns the `added` flags, one bool per right-hand side.  The next call on the handle must be a set_rhs of either kind."""
+        added = np.zeros(self.n_rhs, dtype=np.intc)
+        check(self._lib.cgamd_solver_projection_update(self.handle, added.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return added != 0
+
+    PROJECTION_STATES = ("slot", "x0", "alpha", "c", "nu_s")
+
+    def projection_state(self, which, slot=0):
+        """development entry (cgamd_solver_projection_state).  which 0 / "slot": vector `slot`, (n_rhs, size); 1 / "x0": the last guess,
+        (n_rhs, size); 2 / "alpha", 3 / "c": (capacity, n_rhs) of the handle's type; 4 / "nu_s": (2, n_rhs) float64 / complex128"""
+        idx = self.PROJECTION_STATES.index(which) if isinstance(which, str) else int(which)
+        cap = getattr(self, "_projection_capacity", 0)
+        acc = np.complex128 if self.dtype.kind == "c" else np.float64
+        if idx in (0, 1):
+            out = np.empty((self.n_rhs, self.size), dtype=self.dtype)
+        elif idx in (2, 3):
+            out = np.empty((max(cap, 1), self.n_rhs), dtype=self.dtype)
+        else:
+            out = np.empty((2, self.n_rhs), dtype=acc)
+        check(self._lib.cgamd_solver_projection_state(self.handle, idx, int(slot), ptr(out)))
+        return out
+
     def set_preconditioner(self, m):
         """The reference's PCG preconditioner `M` (helmFE_var.py:546-586), chosen by the reference's own rule:
         * None: plain CG again.
@@ -771,27 +819,47 @@ class Solver:
                                                    int(check_every), its.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return its
 
-    def solve_until(self, b, x0=None, tol=1e-5, maxit=1000, check_every=8):
+    def solve_until(self, b, x0=None, tol=1e-5, maxit=1000, check_every=8, project=False):
         """The reference's tolerance-stopping sub-solver (p_h-PY_C-CL.py:1338-1369; with a preconditioner set, PCG's stop,
         helmFE_var.py:580-584) for ALL right-hand sides of the handle in one solve, batched handles included: each stops on its own
         tolerance (`tol`: a scalar or n_rhs values) in the iteration the reference stops in, and its x is the iterate of that
         iteration.  Returns (x, iterations per right-hand side, history); the history column of a right-hand side that stopped
-        early repeats its last entry down to the last row."""
+        early repeats its last entry down to the last row.
+        project=True (enable_projection first): the solve starts from the projection onto the span of the earlier solutions instead
+        of x0, which must be None, and the basis is updated from its result (set_rhs_projected, iterate_until, projection_update)."""
         self._tolerances(tol)
+        if project:
+            if x0 is not None:
+                raise ValueError("project=True chooses the initial guess: x0 must be None")
+            self.set_rhs_projected(b)
+            its = self.iterate_until(tol, maxit, check_every)
+            out = self.x(), its, self.history()
+            self.projection_update()
+            return out
         self.set_rhs(b, x0)
         its = self.iterate_until(tol, maxit, check_every)
         return self.x(), its, self.history()
 
-    def pcg(self, b, M=None, x0=None, tol=1e-6, maxit=1000, check_every=8):
+    def pcg(self, b, M=None, x0=None, tol=1e-6, maxit=1000, check_every=8, project=False):
         """`PCG(A, b, M, x, tol, maxit)` of the reference (helmFE_var.py:546-586) for M = None, a diagonal M, a tridiagonal
         sparse M along any grid axis (the spsolve branch) or "jacobi" / ("line", stride) / ("multigrid", dims) / "amg" built from the matrix (see set_preconditioner): stops when sqrt(|r.r|) < tol, returns (x, i) with i the 0-based
         index of the last iteration run, like the reference.  The residual history stays on the device and is read back every
         `check_every` iterations; x is taken at the first iteration that met the tolerance by re-running exactly that many
-        iterations when the check overshot it."""
+        iterations when the check overshot it.
+        project=True (enable_projection first): the solve starts from the projection onto the span of the earlier solutions instead
+        of x0, which must be None, stops on the device (iterate_until), and the basis is updated from its result."""
         if self.n_rhs != 1:
             raise ValueError("pcg handles one right-hand side")
+        if project and x0 is not None:
+            raise ValueError("project=True chooses the initial guess: x0 must be None")
         self.set_preconditioner(M)
         try:
+            if project:
+                self.set_rhs_projected(b)
+                its = self.iterate_until(tol, int(maxit), check_every) if int(maxit) > 0 else np.zeros(1, np.intc)
+                x = self.x()
+                self.projection_update()
+                return x, int(its[0]) - 1
             if int(maxit) > 0 and self._lib.cgamd_solver_loop_launches(self.handle) < 2:
                 self.set_rhs(b, x0)             # resident loop (with a diagonal M: the chip-wide groups): the stop happens on the device
                 run_ = ctypes.c_int(0)
@@ -910,7 +978,7 @@ def _shared_pattern(P):
 
 
 def solve_subdomains(ctx, P0, residuals, n_iterations, dtype=np.csingle, solver=None, preconditioner=None, tol=None,
-                     return_iterations=False):
+                     return_iterations=False, project=False):
     """The batched sub-domain solve of the reference's Additive-Schwarz preconditioner `as_prec`.
 
     * UseCG in {2, 3} (p_h-PY_C-CL.py:1918-1937, 1938-1953): all n_my sub-domains share ONE matrix P[0] -- P0: scipy CSR (or
@@ -930,9 +998,14 @@ def solve_subdomains(ctx, P0, residuals, n_iterations, dtype=np.csingle, solver=
     sqrt(|r.r|) is below its tolerance -- the reference's `CG(P[0], z[p].ravel(), tol=CGtol, maxit=CGMaxIT)` per sub-domain
     (p_h-PY_C-CL.py:1916-1921) in one batched solve (Solver.iterate_until); n_iterations is then the cap.  tol=None: exactly
     n_iterations iterations for all, as before.  ValueError for a tol of another length, before anything touches the device.
+    project=True: the persistent `solver=` (required; Solver.enable_projection first) starts every sub-domain from the projection onto
+    the span of its earlier solutions and updates its basis afterwards.  (A list of matrices is reloaded on every call, which clears
+    the basis: the option pays for one shared matrix.)
     Returns a list of complex arrays shaped like the inputs (`x[p*size:(p+1)*size].astype(complex)`); with return_iterations=True
     the pair (that list, the iterations of every sub-domain as an int array)."""
     n_my = len(residuals)
+    if project and solver is None:
+        raise ValueError("solve_subdomains: project=True needs a persistent solver= (the basis lives in the handle)")
     if tol is not None:
         tol = np.ascontiguousarray(np.asarray(tol, dtype=np.float64).reshape(-1))
         if tol.size not in (1, n_my):
@@ -965,13 +1038,18 @@ def solve_subdomains(ctx, P0, residuals, n_iterations, dtype=np.csingle, solver=
     try:
         if preconditioner is not None:
             solver.set_preconditioner(preconditioner)
-        solver.set_rhs(b_values, None)
+        if project:
+            solver.set_rhs_projected(b_values)
+        else:
+            solver.set_rhs(b_values, None)
         if tol is None:
             solver.iterate(n_iterations)
             its = np.full(n_my, int(n_iterations), dtype=np.intc)
         else:
             its = solver.iterate_until(tol, n_iterations)
         x = solver.x()
+        if project:
+            solver.projection_update()
     finally:
         if own:
             solver.close()

@@ -758,6 +758,24 @@ int launch_mixed_norm2(int dtype_hi, int n, const void *v, long long ld, int nrh
 // lo[j] = LO(hi[j]), count values: the inner handle's copy of the matrix
 int launch_mixed_round_values(int dtype_hi, long long count, const void *hi, void *lo, hipStream_t st);
 
+// ---- solution projection (projection.hip): W holds `slots` vectors per right-hand side, slot j of right-hand side r at
+// W + j * slot_pitch + r * ld; live_mask names the slots that take part.  Scalars per (slot, right-hand side) live at [slot * nrhs + r]
+// in the value type
+constexpr int kProjMaxSlots = 32;
+int proj_dots_grid(int dtype, long long n);     // work-groups (= partials per slot and right-hand side) of the dots pass
+// out[slot * nrhs + r] = <w_slot, v_r> for the live slots (the others are not written); partials: slots * nrhs * grid accumulators
+int launch_proj_dots(int dtype, int n, long long ld, int slots, unsigned live_mask, const void *W, long long slot_pitch, const void *v, int nrhs,
+                     void *partials, int grid, void *out, hipStream_t st);
+// y = base + sign * sum_j c_j w_j over the live slots, ascending; base = v - u, v (u == nullptr) or 0 (v == nullptr); y may be v
+int launch_proj_combine(int dtype, int n, long long ld, int slots, unsigned live_mask, const void *W, long long slot_pitch, const void *v,
+                        const void *u, const void *c, int sign, void *y, int nrhs, hipStream_t st);
+// the scalar step of the update: s = sum alpha_j^2 + 2 sum alpha_j c_j + eq, acceptance, t = 1 / sqrt(nu) or 0, the flags;
+// held: the slots of alpha, live: the slots of c; eq, nu: accumulators [nrhs]; out_nus: nu [nrhs], then s [nrhs]
+int launch_proj_decide(int dtype, int nrhs, int slots, unsigned held, unsigned live, const void *alpha, const void *c, const void *eq,
+                       const void *nu, double drop_tol, void *out_nus, void *t, int *added, hipStream_t st);
+// w_r = e_r * t[r] where added[r], else zeros
+int launch_proj_store(int dtype, int n, const void *e, long long ld, const void *t, const int *added, void *w, int nrhs, hipStream_t st);
+
 }  // namespace cgamd
 
 // ---- what mixed.cpp needs of its two handles beyond the C ABI (solver.cpp) ----

@@ -133,6 +133,18 @@ struct cgamd_solver {
     hipGraph_t gTg = nullptr;
     int gT_len = 0;
     int last_refresh = 0;           // what the last cgamd_solver_refresh_values did (cgamd_solver_last_refresh)
+    // solution projection (cgamd_solver_projection_enable; projection.hip): `cap` slots of nrhs vectors at stride n each, `m` of them
+    // held; once m == cap the slots form a ring and `head` is the oldest.  One allocation `scal` holds alpha and c (cap x nrhs values
+    // each), t (nrhs values), <e, q>, nu and the (nu, s) record (accumulators) and the added flags.  projected: the right-hand side in
+    // force came through cgamd_solver_set_rhs_projected; spent: its update has run (q and d hold the update's vectors: set_rhs is next)
+    struct Projection {
+        int cap = 0, m = 0, head = 0, grid = 0;
+        double drop_tol = 0.;
+        void *W = nullptr, *x0 = nullptr, *scal = nullptr, *partials = nullptr;
+        void *alpha = nullptr, *c = nullptr, *t = nullptr, *eq = nullptr, *nu = nullptr, *nus = nullptr;
+        int *added = nullptr;
+        bool projected = false, spent = false;
+    } proj;
     int captures = 0;               // graphs captured since creation (cgamd_solver_graph_captures)
 };
 
@@ -149,6 +161,15 @@ static void destroy_graphs(cgamd_solver *s) {
     if (s->gTg) (void)hipGraphDestroy(s->gTg);
     s->gT = nullptr; s->gTg = nullptr; s->gT_len = 0;
 }
+
+static void proj_free(cgamd_solver *s) {
+    for (void *p : {s->proj.W, s->proj.x0, s->proj.scal, s->proj.partials})
+        if (p) (void)hipFree(p);
+    s->proj = cgamd_solver::Projection();
+}
+// the vectors held were A-orthonormal for the matrix that has just been replaced
+static void proj_clear(cgamd_solver *s) { s->proj.m = s->proj.head = 0; s->proj.projected = s->proj.spent = false; }
+static const char *kProjSpent = ": cgamd_solver_projection_update has used the handle's q and d storage: call set_rhs (of either kind) first";
 
 static void drop_multigrid(cgamd_solver *s) {
     if (s->mg) mg_free(s->mg);
@@ -764,6 +785,7 @@ int cgamd_solver_reload_matrix(cgamd_solver *s, const void *aValues, const int *
     hipStream_t st = s->ctx->stream;
     const size_t vs = dtype_size(s->dtype);
     s->rhs_set = false;
+    proj_clear(s);
     if (s->nnz) {
         CG_HIP(hipMemcpyAsync(s->vals, aValues, (size_t)s->nnz * (s->nsys ? (size_t)s->nsys : 1) * vs, hipMemcpyHostToDevice, st));
         CG_HIP(hipMemcpyAsync(s->cols, aCols, (size_t)s->nnz * 4, hipMemcpyHostToDevice, st));
@@ -863,6 +885,7 @@ int cgamd_solver_refresh_values(cgamd_solver *s, const void *aValues, int on_dev
     }
     s->rhs_set = false;
     s->last_refresh = 0;
+    proj_clear(s);
     CG_HIP(hipStreamSynchronize(st));       // nothing of the handle's still reads the old values
     if (s->own_matrix && s->nnz) {
         const size_t bytes = (size_t)s->nnz * (s->nsys ? (size_t)s->nsys : 1) * dtype_size(s->dtype);
@@ -900,6 +923,7 @@ int cgamd_solver_destroy(cgamd_solver *s) {
     (void)hipStreamSynchronize(s->ctx->stream);
     destroy_graphs(s);
     drop_multigrid(s);
+    proj_free(s);
     if (s->own_ptr && s->ptr) (void)hipFree(s->ptr);
     if (s->own_matrix) {
         if (s->vals) (void)hipFree(s->vals);
@@ -929,6 +953,7 @@ static int set_rhs_impl(cgamd_solver *s, const void *b, const void *x0, int on_d
     if (rm != s->rm) destroy_graphs(s);         // captured launch sequences belong to one layout
     if (s->until_mode && s->fused2) destroy_graphs(s);      // (captured while the two-launch loop was set aside: iterate_until)
     s->until_mode = s->until_stopped = s->stop.armed = false;
+    s->proj.projected = s->proj.spent = false;      // (cgamd_solver_set_rhs_projected sets its mark after this call)
     s->rm = rm;
     int rc;
     if (rm) {
@@ -1344,6 +1369,7 @@ int cgamd_solver_iterate(cgamd_solver *s, int nIterations) {
     if (!s->rhs_set) return fail(CGAMD_ERR_STATE, "iterate: call set_rhs first");
     if (nIterations < 0) return fail(CGAMD_ERR_INVALID, "iterate: negative iteration count");
     if (s->until_stopped) return fail(CGAMD_ERR_STATE, "iterate: iterate_until has stopped a right-hand side (the columns are at different iterations): go on with iterate_until, or call set_rhs");
+    if (s->proj.spent) return fail(CGAMD_ERR_STATE, std::string("iterate") + kProjSpent);
     CG_HIP(hipSetDevice(s->ctx->device));
     if (int rc = ensure_history(s, s->iters + nIterations + 1)) return rc;
     hipStream_t st = s->ctx->stream;
@@ -1463,6 +1489,7 @@ int cgamd_solver_iterate_tol(cgamd_solver *s, int maxIterations, double tol, int
     if (!s->rhs_set) return fail(CGAMD_ERR_STATE, "iterate_tol: call set_rhs first");
     if (s->nrhs != 1) return fail(CGAMD_ERR_STATE, "iterate_tol: one right-hand side");
     if (s->until_mode) return fail(CGAMD_ERR_STATE, "iterate_tol: iterate_until runs this right-hand side on the launched loop until the next set_rhs");
+    if (s->proj.spent) return fail(CGAMD_ERR_STATE, std::string("iterate_tol") + kProjSpent);
     {
         TuneScope ts(&s->tune);
         const bool local = fused2_now(s) && s->res_ok, wide = s->resw.ok && !s->tri_on && !s->mg && !s->rm && !(s->res_ok && !precond_set(s));
@@ -1518,6 +1545,7 @@ static int replace_refuses(const cgamd_solver *s, bool planned) {
 static int replace_residual_impl(cgamd_solver *s, const void *r_new, long long ldr) {
     TuneScope ts(&s->tune);
     if (int rc = replace_refuses(s, false)) return rc;
+    if (s->proj.spent) return fail(CGAMD_ERR_STATE, std::string("replace_residual") + kProjSpent);
     CG_HIP(hipSetDevice(s->ctx->device));
     if (int rc = step_not_capturing(s, "replace_residual")) return rc;
     hipStream_t st = s->ctx->stream;
@@ -1568,6 +1596,7 @@ int cgamd_solver_iterate_until(cgamd_solver *s, int maxIterations, const double 
     if (!s->rhs_set) return fail(CGAMD_ERR_STATE, "iterate_until: call set_rhs first");
     if (s->rm) return fail(CGAMD_ERR_STATE, "iterate_until: the handle keeps its right-hand sides interleaved (row-major layout)");
     if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, "iterate_until: CGAMD_UNFUSED replays the reference's kernel sequence, which has no guarded form");
+    if (s->proj.spent) return fail(CGAMD_ERR_STATE, std::string("iterate_until") + kProjSpent);
     const int nr = s->nrhs;
     if (maxIterations == 0) {
         for (int r = 0; r < nr; ++r) iterations_run[r] = (s->stop.armed && s->stop.stopped[r]) ? s->stop.stopped[r] : s->iters;
@@ -1627,6 +1656,7 @@ int cgamd_solver_iterate_timed(cgamd_solver *s, int nIterations, float *spmv_ms_
     if (!s->rhs_set) return fail(CGAMD_ERR_STATE, "iterate_timed: call set_rhs first");
     if (nIterations < 1) return fail(CGAMD_ERR_INVALID, "iterate_timed: needs >= 1 iteration");
     if (s->until_stopped) return fail(CGAMD_ERR_STATE, "iterate_timed: iterate_until has stopped a right-hand side: go on with iterate_until, or call set_rhs");
+    if (s->proj.spent) return fail(CGAMD_ERR_STATE, std::string("iterate_timed") + kProjSpent);
     CG_HIP(hipSetDevice(s->ctx->device));
     if (int rc = ensure_history(s, s->iters + nIterations + 1)) return rc;
     hipStream_t st = s->ctx->stream;
@@ -1940,6 +1970,181 @@ long long cgamd_solver_iter_moved_bytes(cgamd_solver *s) {
     // handle iterated in multiples of U: (9 L + 1) / L passes per iteration
     if (lag >= 2) return matrix + (9 * lag + 1) * s->n_user * V * s->nrhs / lag;
     return matrix + passes * s->n_user * V * s->nrhs;
+}
+
+
+// ---- solution projection (include/cgamd.h "Solution projection"; kernels: projection.hip) -----------------------------------------
+static unsigned proj_held_mask(const cgamd_solver *s) { return s->proj.m >= 32 ? 0xffffffffu : ((1u << s->proj.m) - 1u); }
+// what every entry checks first: the handle, no capture in progress
+static int proj_entry(cgamd_solver *s, const char *who) {
+    if (!s) return fail(CGAMD_ERR_INVALID, std::string(who) + ": solver is NULL");
+    CG_HIP(hipSetDevice(s->ctx->device));
+    return step_not_capturing(s, who);
+}
+static int proj_refuses(const cgamd_solver *s, const char *who) {
+    if (s->rm || (s->rm_ok && !precond_set(s)))
+        return fail(CGAMD_ERR_STATE, std::string(who) + ": the handle keeps its right-hand sides interleaved (row-major layout)");
+    if (s->herm) return herm_refuses(who, "whose conjugated projection is a later change");
+    return CGAMD_OK;
+}
+
+int cgamd_solver_projection_enable(cgamd_solver *s, int capacity, double drop_tol) {
+    if (!s) return fail(CGAMD_ERR_INVALID, "projection_enable: solver is NULL");
+    if (capacity < 0 || capacity > kProjMaxSlots) return fail(CGAMD_ERR_INVALID, "projection_enable: capacity runs 0 ... 32");
+    if (!(drop_tol >= 0.) || !std::isfinite(drop_tol)) return fail(CGAMD_ERR_INVALID, "projection_enable: drop_tol must be finite and >= 0");
+    TuneScope ts(&s->tune);
+    if (int rc = proj_entry(s, "projection_enable")) return rc;
+    if (capacity == 0) {
+        CG_HIP(hipStreamSynchronize(s->ctx->stream));
+        proj_free(s);
+        return CGAMD_OK;
+    }
+    if (int rc = proj_refuses(s, "projection_enable")) return rc;
+    const int nr = s->nrhs;
+    const size_t vs = dtype_size(s->dtype), as = acc_size(s->dtype), block = (size_t)s->n * nr * vs;
+    cgamd_solver::Projection p;
+    p.cap = capacity;
+    p.drop_tol = drop_tol;
+    p.grid = proj_dots_grid(s->dtype, s->n);
+    // alpha | c | t (values), then eq | nu | nus (accumulators, 16-byte aligned), then the flags
+    const size_t n_val = ((size_t)2 * capacity * nr + nr) * vs, at_acc = (n_val + 15) & ~(size_t)15, n_acc = (size_t)4 * nr * as;
+    const size_t scal_bytes = at_acc + n_acc + (size_t)nr * sizeof(int);
+    const size_t part_bytes = as * (size_t)capacity * nr * p.grid;
+    int rc = dmalloc(&p.W, block * capacity, "projection basis");
+    if (!rc) rc = dmalloc(&p.x0, block, "projection guess");
+    if (!rc) rc = dmalloc(&p.scal, scal_bytes, "projection scalars");
+    if (!rc) rc = dmalloc(&p.partials, part_bytes, "projection partials");
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemsetAsync(p.W, 0, block * capacity, s->ctx->stream);
+    if (!rc && e == hipSuccess) e = hipMemsetAsync(p.x0, 0, block, s->ctx->stream);
+    if (!rc && e == hipSuccess) e = hipMemsetAsync(p.scal, 0, scal_bytes, s->ctx->stream);
+    if (!rc && e == hipSuccess) e = hipStreamSynchronize(s->ctx->stream);
+    if (rc || e != hipSuccess) {        // the handle keeps what it had
+        for (void *q : {p.W, p.x0, p.scal, p.partials})
+            if (q) (void)hipFree(q);
+        return rc ? rc : fail(CGAMD_ERR_HIP, std::string("projection_enable: ") + hipGetErrorString(e));
+    }
+    char *base = static_cast<char *>(p.scal);
+    p.alpha = base;
+    p.c = base + (size_t)capacity * nr * vs;
+    p.t = base + (size_t)2 * capacity * nr * vs;
+    p.eq = base + at_acc;
+    p.nu = base + at_acc + (size_t)nr * as;
+    p.nus = base + at_acc + (size_t)2 * nr * as;
+    p.added = reinterpret_cast<int *>(base + at_acc + n_acc);
+    proj_free(s);
+    s->proj = p;
+    return CGAMD_OK;
+}
+
+int cgamd_solver_projection_count(cgamd_solver *s) { return s ? (s->proj.cap ? s->proj.m : 0) : -CGAMD_ERR_INVALID; }
+
+int cgamd_solver_projection_clear(cgamd_solver *s) {
+    if (int rc = proj_entry(s, "projection_clear")) return rc;
+    proj_clear(s);
+    return CGAMD_OK;
+}
+
+int cgamd_solver_set_rhs_projected(cgamd_solver *s, const void *b, int on_device) {
+    if (!s || !b) return fail(CGAMD_ERR_INVALID, "set_rhs_projected: null argument");
+    TuneScope ts(&s->tune);
+    if (int rc = proj_entry(s, "set_rhs_projected")) return rc;
+    if (!s->proj.cap) return fail(CGAMD_ERR_STATE, "set_rhs_projected: call cgamd_solver_projection_enable first");
+    if (int rc = proj_refuses(s, "set_rhs_projected")) return rc;
+    hipStream_t st = s->ctx->stream;
+    const int dt = s->dtype, n = s->n, nr = s->nrhs;
+    const size_t vs = dtype_size(dt), vbytes = (size_t)n * nr * vs;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    s->rhs_set = false;         // b changes under the handle: only a completed set_rhs makes it usable again
+    s->proj.projected = s->proj.spent = false;
+    // b as cgamd_solver_set_rhs places it (the padding rows stay 0)
+    if (n != s->n_user) CG_HIP(hipMemcpy2DAsync(s->b, (size_t)n * vs, b, (size_t)s->n_user * vs, (size_t)s->n_user * vs, (size_t)nr, kind, st));
+    else CG_HIP(hipMemcpyAsync(s->b, b, vbytes, kind, st));
+    // the guess: alpha_j = <w_j, b>, x0 = sum_j alpha_j w_j
+    const unsigned held = proj_held_mask(s);
+    const long long pitch = (long long)n * nr;
+    if (s->proj.m > 0) {
+        if (int rc = launch_proj_dots(dt, n, n, s->proj.cap, held, s->proj.W, pitch, s->b, nr, s->proj.partials, s->proj.grid, s->proj.alpha, st)) return rc;
+        if (int rc = launch_proj_combine(dt, n, n, s->proj.cap, held, s->proj.W, pitch, nullptr, nullptr, s->proj.alpha, +1, s->proj.x0, nr, st)) return rc;
+    } else {
+        CG_HIP(hipMemsetAsync(s->proj.x0, 0, vbytes, st));
+    }
+    CG_HIP(hipMemcpyAsync(s->x, s->proj.x0, vbytes, hipMemcpyDeviceToDevice, st));
+    // everything after the guess is cgamd_solver_set_rhs(b, x0): b and x are in place
+    if (int rc = set_rhs_impl(s, nullptr, nullptr, on_device, s->n_user)) return rc;
+    s->proj.projected = true;
+    return CGAMD_OK;
+}
+
+int cgamd_solver_projection_update(cgamd_solver *s, int *added) {
+    if (!s) return fail(CGAMD_ERR_INVALID, "projection_update: solver is NULL");
+    TuneScope ts(&s->tune);
+    if (int rc = proj_entry(s, "projection_update")) return rc;
+    if (!s->proj.cap) return fail(CGAMD_ERR_STATE, "projection_update: call cgamd_solver_projection_enable first");
+    if (!s->rhs_set || !s->proj.projected)
+        return fail(CGAMD_ERR_STATE, "projection_update: the right-hand side in force did not come through cgamd_solver_set_rhs_projected");
+    if (s->proj.spent) return fail(CGAMD_ERR_STATE, "projection_update: already updated from this solve");
+    hipStream_t st = s->ctx->stream;
+    cgamd_solver::Projection &p = s->proj;
+    const int dt = s->dtype, n = s->n, nr = s->nrhs, cap = p.cap;
+    const long long pitch = (long long)n * nr;
+    const int retired = p.m == cap ? p.head : -1;       // a full ring: the oldest slot takes no part and receives the new vector
+    const unsigned held = proj_held_mask(s), live = retired >= 0 ? held & ~(1u << retired) : held;
+    void *e = s->d;             // the direction is dead from here on: iterate* refuse until the next set_rhs
+    p.spent = true;
+    int rc;
+    // e = x - x0, plus what the retired slot carried of the guess (alpha_ret w_ret), so that the vector that takes its place keeps it:
+    // e is what the solve found beyond the span of the slots that STAY.  Then q = A e ; c_j = <w_j, q> ; <e, q>
+    if ((rc = launch_proj_combine(dt, n, n, cap, retired >= 0 ? 1u << retired : 0u, p.W, pitch, s->x, p.x0, p.alpha, +1, e, nr, st))) return rc;
+    if ((rc = handle_spmv(s, n, e, n, s->q, n, nullptr, nullptr, st))) return rc;
+    if ((rc = launch_proj_dots(dt, n, n, cap, live, p.W, pitch, s->q, nr, p.partials, p.grid, p.c, st))) return rc;
+    if ((rc = launch_dot_partials(dt, n, e, s->q, n, nr, p.partials, p.grid, st))) return rc;
+    if ((rc = launch_reduce_to_acc(dt, p.partials, p.grid, nr, p.eq, st))) return rc;
+    // e' = e - sum_j c_j w_j ; q' = A e' ; nu = <e', q'>
+    if (live && (rc = launch_proj_combine(dt, n, n, cap, live, p.W, pitch, e, nullptr, p.c, -1, e, nr, st))) return rc;
+    if ((rc = handle_spmv(s, n, e, n, s->q, n, nullptr, nullptr, st))) return rc;
+    if ((rc = launch_dot_partials(dt, n, e, s->q, n, nr, p.partials, p.grid, st))) return rc;
+    if ((rc = launch_reduce_to_acc(dt, p.partials, p.grid, nr, p.nu, st))) return rc;
+    if ((rc = launch_proj_decide(dt, nr, cap, live, live, p.alpha, p.c, p.eq, p.nu, p.drop_tol, p.nus, p.t, p.added, st))) return rc;
+    std::vector<int> flags((size_t)nr, 0);
+    CG_HIP(hipMemcpyAsync(flags.data(), p.added, sizeof(int) * (size_t)nr, hipMemcpyDeviceToHost, st));
+    CG_HIP(hipStreamSynchronize(st));
+    bool any = false;
+    for (int f : flags) any = any || f != 0;
+    if (any) {          // one slot for all columns: a refused column stores zeros
+        const int slot = retired >= 0 ? retired : p.m;
+        void *w = static_cast<char *>(p.W) + (size_t)slot * pitch * dtype_size(dt);
+        if ((rc = launch_proj_store(dt, n, e, n, p.t, p.added, w, nr, st))) return rc;
+        if (retired >= 0) p.head = (p.head + 1) % cap;
+        else ++p.m;
+    }
+    if (added)
+        for (int r = 0; r < nr; ++r) added[r] = flags[(size_t)r];
+    return CGAMD_OK;
+}
+
+int cgamd_solver_projection_state(cgamd_solver *s, int which, int slot, void *out_host) {
+    if (!s || !out_host) return fail(CGAMD_ERR_INVALID, "projection_state: null argument");
+    if (int rc = proj_entry(s, "projection_state")) return rc;
+    const cgamd_solver::Projection &p = s->proj;
+    if (!p.cap) return fail(CGAMD_ERR_STATE, "projection_state: call cgamd_solver_projection_enable first");
+    hipStream_t st = s->ctx->stream;
+    const int nr = s->nrhs;
+    const size_t vs = dtype_size(s->dtype), row = (size_t)s->n_user * vs;
+    switch (which) {
+    case 0:
+        if (slot < 0 || slot >= p.cap) return fail(CGAMD_ERR_INVALID, "projection_state: slot runs 0 ... capacity - 1");
+        CG_HIP(hipMemcpy2DAsync(out_host, row, static_cast<const char *>(p.W) + (size_t)slot * s->n * nr * vs, (size_t)s->n * vs, row, (size_t)nr,
+                                hipMemcpyDeviceToHost, st));
+        break;
+    case 1: CG_HIP(hipMemcpy2DAsync(out_host, row, p.x0, (size_t)s->n * vs, row, (size_t)nr, hipMemcpyDeviceToHost, st)); break;
+    case 2: CG_HIP(hipMemcpyAsync(out_host, p.alpha, (size_t)p.cap * nr * vs, hipMemcpyDeviceToHost, st)); break;
+    case 3: CG_HIP(hipMemcpyAsync(out_host, p.c, (size_t)p.cap * nr * vs, hipMemcpyDeviceToHost, st)); break;
+    case 4: CG_HIP(hipMemcpyAsync(out_host, p.nus, (size_t)2 * nr * acc_size(s->dtype), hipMemcpyDeviceToHost, st)); break;
+    default: return fail(CGAMD_ERR_INVALID, "projection_state: which is 0 .. 4");
+    }
+    CG_HIP(hipStreamSynchronize(st));
+    return CGAMD_OK;
 }
 
 }  // extern "C"

@@ -811,6 +811,83 @@ int cgamd_dist_loop_launches(cgamd_dist *d);
  * 0 when the handle has no communicator (peer-to-peer backend, or one rank without peers) */
 int cgamd_dist_comm_ranks(cgamd_dist *d);
 
+/* ---- Solution projection: start each solve from the span of earlier ones (csrc/projection.hip; Fischer, "Projection techniques
+ * for iterative solution of Ax = b with successive right-hand sides", 1998).  A handle that serves a sequence of right-hand sides
+ * keeps up to `capacity` vectors w_j per right-hand-side column, A-orthonormal in the handle's unconjugated inner product:
+ * <w_i, A w_j> = delta_ij with <a, b> = sum a_i b_i.  Every column keeps a basis of its own (on a batched handle column r uses matrix r).
+ * It only chooses x0, so it composes with every loop and every preconditioner of the handle.
+ *   GUESS (cgamd_solver_set_rhs_projected): alpha_j = <w_j, b> for the held slots; x0 = sum_j alpha_j w_j, slots ascending from +0,
+ *     one rounding per operation in the value type (x0 = 0 with no slot held); then cgamd_solver_set_rhs(s, b, x0), unchanged: the
+ *     result is, bit for bit, what the caller gets by reading the guess (cgamd_solver_projection_state, which 1) and calling
+ *     cgamd_solver_set_rhs with it.
+ *   UPDATE (cgamd_solver_projection_update), from the x that cgamd_solver_get_x would return: e = x - x0 (with a full ring:
+ *     e = (x - x0) + alpha_ret w_ret, see RING), q = A e (the handle's own SpMV), c_j = <w_j, q>; e' = e - sum_j c_j w_j, one classical Gram-Schmidt pass, slots ascending, all c_j from the same q;
+ *     q' = A e', nu = <e', q'> (a second SpMV, not <e, q> - sum c_j^2, which cancels); s = sum alpha_j^2 + 2 sum alpha_j c_j + <e, q>
+ *     over the slots that take part (<x, A x> in exact arithmetic; formed in the accumulation type).  A column's vector is accepted when nu is finite and
+ *     |nu| > drop_tol^2 |s|, for the real types also nu > 0.  An accepted column stores w_new = e' * (1 / sqrt nu) -- the principal
+ *     square root for the complex types, 1 / sqrt nu formed in the accumulation type and rounded once -- and a refused column stores
+ *     a column of zeros, so that all columns keep one common slot count.  If every column is refused, nothing is retired and nothing
+ *     is stored.
+ *   RING: slots fill in order 0, 1, ...; with count == capacity the oldest slot is retired before the update -- its c_j is not formed
+ *     and it takes no part in e' -- and w_new takes its place (dropping a member of an A-orthonormal set leaves the rest
+ *     A-orthonormal: no restart).  What the retired vector carried of the guess stays in what is added: e = (x - x0) + alpha_ret w_ret,
+ *     that is x minus the guess of the slots that stay.  (The oldest vector of a sequence of similar solutions is the direction they
+ *     share -- every later one was orthogonalised against it -- so dropping it without this would leave a basis of differences: the
+ *     first solve after the ring wraps then takes as many iterations as from zero.)
+ *   Padding rows (cgamd_solver_ld) of every stored vector are 0.  The caller's arrays keep stride `size`.
+ * Scalars: alpha_j and c_j are summed in double / complex double and rounded once to the value type, stored at [slot * nRHS + r];
+ * nu, s and <e, q> stay in the accumulation type.
+ * ORDER OF THE SUMS (fixed: two calls return the same bits).  <w_j, v> over `size` values with G = cgamd_projection_dots_grid(dtype,
+ * size) work-groups of 256 threads and E = 16 / sizeof(value) values per 16-byte pack: thread t of work-group g starts from +0 and
+ * adds the products (rounded in the value type, then widened) of packs g 256 + t + k G 256, k = 0, 1, ..., the E values of a pack in
+ * order, then value E floor(size / E) + g 256 + t of the scalar tail; the 256 thread sums of a work-group are added by the wave tree
+ * v[l] += v[l + off], off = 32 ... 1, and the four wave sums in order; the G work-group sums by one 1024-thread work-group: thread t
+ * adds p[t], p[t + 1024], ..., then the wave tree and the 16 wave sums in order.  (With a pointer that is not 16-byte aligned, or
+ * nRHS > 1 and ld or slot_pitch not whole packs, E = 1.)  <e, q> and nu: the order of cgamd_vdot's partials on the same G.
+ * BYTES, V = sizeof(value), n = cgamd_solver_ld, m slots held (the basis is read once; v once per group of at most 8 slots):
+ *   guess   (m + ceil(m / 8) + 1) n V nRHS          the dots pass m + ceil(m / 8), the combine pass m read + 1 written
+ *   update  two SpMVs, then (3 + m + ceil(m / 8) + 4 + m + 2 + 2) n V nRHS: e = x - x0 (3), the dots pass (m + ceil(m / 8)), <e, q>
+ *           and nu (2 + 2), the combine pass (m + 2), the store pass (2); with a full ring m - 1 for m in the dots and combine passes
+ *           and 4 for e (it reads the retired vector)
+ * cgamd_solver_projection_enable: capacity 1 ... 32 allocates capacity * nRHS * ld values plus one x0 block (CGAMD_ERR_ALLOC on
+ *   failure, the handle unchanged) and starts with no slot held; capacity 0 disables the feature and frees the storage.  drop_tol >= 0
+ *   and finite; 0 accepts every finite vector (nu > 0 for the real types).
+ * cgamd_solver_projection_count: slots held, 0 ... capacity; 0 when disabled; negative on error.
+ * cgamd_solver_projection_clear: count = 0, the storage is kept.
+ * cgamd_solver_set_rhs_projected: CGAMD_ERR_STATE when the feature is not enabled.
+ * cgamd_solver_projection_update: CGAMD_ERR_STATE unless the last right-hand side came through cgamd_solver_set_rhs_projected; may
+ *   follow cgamd_solver_iterate, _iterate_until (frozen columns: their stopping iterate) and _iterate_tol.  x stays readable with
+ *   cgamd_solver_get_x.  Afterwards the next call must be a set_rhs of either kind: the update uses the handle's q and d storage, so
+ *   cgamd_solver_iterate, _iterate_until, _iterate_tol, _iterate_timed and _replace_residual return CGAMD_ERR_STATE, and so does a
+ *   second update without a new solve.  added: nRHS ints (1 = the column's vector was accepted), may be NULL.  Synchronises once, to
+ *   read the flags; nothing else crosses to the host.
+ * cgamd_solver_refresh_values and cgamd_solver_reload_matrix clear the basis (the vectors were orthonormal for the old matrix);
+ * changing or removing a preconditioner does not.
+ * Served: every handle with RHS-major vectors (cgamd_solver_layout() == 0), all four value types, any nRHS, batched handles, every
+ * preconditioner and loop, CGAMD_NO_GRAPH, CGAMD_UNFUSED, CGAMD_MATRIX_ON_DEVICE.  CGAMD_ERR_STATE, the handle untouched: row-major
+ * layout; CGAMD_HERMITIAN on a complex type (the conjugated form is a later change).  CGAMD_ERR_INVALID: NULL handle, capacity
+ * outside 0 ... 32, drop_tol negative or not finite, any of these calls while the stream is being captured. */
+int cgamd_solver_projection_enable(cgamd_solver *s, int capacity, double drop_tol);
+int cgamd_solver_projection_count(cgamd_solver *s);
+int cgamd_solver_projection_clear(cgamd_solver *s);
+int cgamd_solver_set_rhs_projected(cgamd_solver *s, const void *b, int on_device);
+int cgamd_solver_projection_update(cgamd_solver *s, int *added /* nRHS ints, may be NULL */);
+/* Development entries (tests; same standing as cgamd_solver_step_state).  _projection_state waits for the handle's stream and copies
+ * to the host -- which 0: slot vector `slot`, nRHS x size values at stride size; 1: the guess x0, likewise; 2: alpha of the last guess,
+ * capacity x nRHS values at [slot * nRHS + r]; 3: c of the last update, likewise (slots that took no part hold what they held);
+ * 4: nu [nRHS], then s [nRHS] of the last update, in the accumulation type.
+ * cgamd_projection_dots / _combine: the two basis kernels on DEVICE arrays of the caller, enqueued on the ctx stream.  Slot j of
+ * column r starts at W + j * slot_pitch + r * ld values, column r of v and y at r * ld; bit j of live_mask says that slot j takes
+ * part.  _dots: out[j * nRHS + r] = <w_j, v_r> for the live slots (the entry of a masked slot is untouched).  _combine:
+ * y = v + sign * sum_j c_j w_j over the live slots, ascending, c at [j * nRHS + r], sign +1 or -1, v == NULL: y starts from +0; one
+ * multiplication and one addition (subtraction) per slot per element; y may be v.  cgamd_projection_dots_grid: G above. */
+int cgamd_solver_projection_state(cgamd_solver *s, int which, int slot, void *out_host);
+int cgamd_projection_dots(cgamd_ctx *ctx, int dtype, int size, long long ld, int slots, unsigned live_mask,
+                          const void *W, long long slot_pitch, const void *v, int nRHS, void *out /* device */);
+int cgamd_projection_combine(cgamd_ctx *ctx, int dtype, int size, long long ld, int slots, unsigned live_mask,
+                             const void *W, long long slot_pitch, const void *v, const void *c, int sign, void *y, int nRHS);
+int cgamd_projection_dots_grid(int dtype, int size);
+
 #ifdef __cplusplus
 }
 #endif
