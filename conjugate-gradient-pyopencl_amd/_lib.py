@@ -122,6 +122,7 @@ def load():
         "cgamd_solver_row_codes": (ci, [vp]),
         "cgamd_solver_row_pipe": (ci, [vp]),
         "cgamd_solver_row_pairs": (ci, [vp]),
+        "cgamd_solver_spmv_schedule": (ci, [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ll)]),
         "cgamd_solver_iterate_tol": (ci, [vp, ci, ctypes.c_double, ctypes.POINTER(ci)]),
         "cgamd_solver_iterate_until": (ci, [vp, ci, ctypes.POINTER(ctypes.c_double), ci, ci, ctypes.POINTER(ci)]),
         "cgamd_solver_replace_residual": (ci, [vp, vp]),

@@ -718,6 +718,15 @@ class Solver:
         per slot), else 0"""
         return self._lib.cgamd_solver_row_pairs(self.handle)
 
+    @property
+    def spmv_schedule(self):
+        """how the row- or pair-coded SpMV deals its 1024-row super blocks to the XCDs: {"kind": "plane" (the plane-matched table) or
+        "cycle" (block-cyclic, tuning key spmv_cycle), "grid": work-groups per launch, "unit_rows": the handle's largest stride in rows};
+        grid and unit_rows are 0 when another SpMV form runs"""
+        kind, grid, unit = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_longlong(0)
+        check(self._lib.cgamd_solver_spmv_schedule(self.handle, ctypes.byref(kind), ctypes.byref(grid), ctypes.byref(unit)))
+        return {"kind": "plane" if kind.value == 1 else "cycle", "grid": grid.value, "unit_rows": unit.value}
+
     def iter_bytes(self, fused=False):
         return self._lib.cgamd_solver_iter_bytes(self.handle, int(fused))
 

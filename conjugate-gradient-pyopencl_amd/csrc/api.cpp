@@ -42,6 +42,8 @@ int cgamd_tune(const char *key, int value) {
         return fail(CGAMD_ERR_INVALID, "tune: dev.row_pipe takes 0 (default rule), 1, 2 or 4");
     if (k == "dev.row_pairs" && value != -1 && value != 0 && value != 1)
         return fail(CGAMD_ERR_INVALID, "tune: dev.row_pairs takes -1 (default rule), 0 or 1");
+    if (k == "dev.spmv_plane" && value != -1 && value != 0 && value != 1)
+        return fail(CGAMD_ERR_INVALID, "tune: dev.spmv_plane takes -1 (default rule), 0 or 1");
     g_tune_generation.fetch_add(1, std::memory_order_relaxed);     // cached cg() handles were created under the old configuration
     tune_set([&](Tuning &g_tune) {
     // public keys (include/cgamd.h)
@@ -73,6 +75,7 @@ int cgamd_tune(const char *key, int value) {
     else if (k == "dev.row_pipe") g_tune.dev_row_pipe = value;
     else if (k == "dev.row_pairs") g_tune.dev_row_pairs = value;
     else if (k == "dev.row_pairs_min_mb") g_tune.dev_row_pairs_min_mb = value;
+    else if (k == "dev.spmv_plane") g_tune.dev_spmv_plane = value;
     else if (k == "dev.resident_lock") g_tune.resident_lock = value;
     else if (k == "dev.slab_cus") g_tune.slab_cus = value;
     else if (k == "dev.slab_trim") g_tune.slab_trim = value;

@@ -32,6 +32,8 @@ constexpr int kBlock = 256;          // threads per work-group (4 waves)
 constexpr int kMaxGrid = 2048;       // 256 CUs x 8 resident work-groups
 constexpr int kQuadsPerThread = 2;   // SpMV: 2 x 4 non-zeros per thread per chunk -> 2048 nnz / chunk
 
+constexpr int kSuperRows = 4 * kBlock;   // rows of a SUPER block: the kVcBlocks row blocks one work-group of the coded SpMV forms takes (spmv.hip)
+
 struct SpmvPlan {
     int grid = 0;        // work-groups launched (multiple of 8 when >= 8)
     int row_blocks = 0;  // ceil(n / kBlock)
@@ -71,6 +73,10 @@ struct SpmvPlan {
     const void *pdict = nullptr;            // pair_dict_* layout, n_pair_patterns entries
     int n_pair_patterns = 0;
     int pair_slots = 0;                     // the longest union of slots among the pair patterns (the kernel walks 7 or 8)
+    // PLANE-MATCHED schedule of the row- and pair-coded kernels (build_xcd_schedule, xcd_schedule.h): work-group b takes super block
+    // sched[b] (-1: none); null = the block-cyclic schedule of rowblock_of
+    const int *sched = nullptr;             // [sched_grid]
+    int sched_grid = 0;
 };
 SpmvPlan make_spmv_plan(int n);
 // fills plan->max_span / chunk_span from the matrix structure; synchronises `st`; scratch_dev: >= 32 bytes
@@ -177,6 +183,8 @@ struct Tuning {
     int dev_row_pairs_min_mb = 256; // ... for matrices above this size (a threshold of its own, like dev_row_codes_min_mb).  256 MB: every system the
                                     // form was measured on lies above it (300 MB, 840 MB, 8.4 GB: profiles/row_pairs/), and the handles of 85 to 151 MB
                                     // whose CG steps are tested bit for bit (tests/test_gpu_cg_steps.py) keep recording the row form they assert
+    int dev_spmv_plane = -1;        // row- and pair-coded SpMV: super blocks dealt to the XCDs by their place inside the handle's largest stride, from a
+                                    // table per handle (1: every such handle; 0: the block-cyclic schedule; -1 = the default rule, spmv_plane_wanted)
     int dev_vc_pipe = 1;            // value-coded SpMV: gathers pipelined across the row blocks of a work-group (0 = one block at a time: A/B)
     int dev_generic_spmv = 0;       // 1: the generic chunked CSR stream for every matrix (the row-block kernels' fallback, tested against them)
     int resident_lock = 1;          // 0: no per-GPU serialisation of resident launches (ranks of ONE job sharing a GPU in a rehearsal)
@@ -213,6 +221,20 @@ inline int row_pipe_depth(int knob, size_t value_bytes) { return knob == 1 || kn
 // whether a handle builds and launches the row-pair form under dev.row_pairs = `knob`: 1 and 0 as given, anything else the default
 // rule -- by the size of a value, as measured (profiles/row_pairs/)
 inline bool row_pairs_wanted(int knob, size_t value_bytes) { return knob == 1 ? true : knob == 0 ? false : value_bytes >= 8; }
+// whether a row- or pair-coded handle whose largest stride is unit_rows rows runs the plane-matched schedule under dev.spmv_plane =
+// `knob`: 1 whenever it has a stride at all, a stride of one row included, and whatever the table looks like (below 8 super blocks per
+// stride some XCDs sit out parts of a plane, below one the blocks are scattered, at exactly one super block EVERY block lands on one
+// XCD and the grid is 8 x the super blocks: correct and slow, a development knob and what the tests run), 0 never, anything else the
+// default rule, as measured (profiles/xcd_plane/): strides of at least 8 super blocks -- every XCD busy in every
+// eighth of a plane: 3-D grids -- on matrices above 256 MB, the smallest size measured (the threshold of the pair form), for 4- and
+// 8-byte values alike, AND only where the table built loads the XCDs evenly (xcd_schedule_balanced, checked by setup_xcd_schedule).
+// The gain is 0.8 to 1.7 % of an iteration, not the third of the SpMV its saved traffic would be
+constexpr size_t kPlaneMinMatrixBytes = (size_t)256 << 20;
+inline bool spmv_plane_wanted(int knob, long long unit_rows, int rows_per_super, size_t matrix_bytes) {
+    if (knob == 0 || unit_rows < 1) return false;
+    if (knob == 1) return true;
+    return unit_rows >= 8LL * rows_per_super && matrix_bytes > kPlaneMinMatrixBytes;
+}
 extern Tuning g_tune;
 Tuning tune_snapshot();
 const Tuning &tune();

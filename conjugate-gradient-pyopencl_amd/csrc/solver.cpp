@@ -19,6 +19,8 @@
 
 #include "cgamd_internal.h"
 #include "launch_util.h"
+#include "spmv_device.h"
+#include "xcd_schedule.h"
 
 using namespace cgamd;
 
@@ -120,6 +122,8 @@ struct cgamd_solver {
     void *pdict = nullptr;
     int n_pair_patterns = 0;
     int n_patterns = 0, n_user_patterns = 0;     // dictionary entries; patterns of the caller's rows (the appended empty rows may add one)
+    int *sched = nullptr;             // plane-matched XCD schedule of the row- / pair-coded SpMV (setup_xcd_schedule): plan.sched_grid ints
+    long long sched_unit = 0;         // the largest |column - row| among the row dictionary's entries, in rows (0: no row codes)
     // cgamd_solver_iterate_tol: tolerance of the device-side stop for the call in progress (0 = none), and what it reported
     double tol_req = 0.;
     bool tol_served = false, tol_stopped = false;
@@ -415,6 +419,39 @@ static void drop_value_codes(cgamd_solver *s) {
     if (s->pdict) { (void)hipFree(s->pdict); s->pdict = nullptr; }
     s->plan.pcodes = nullptr; s->plan.pdict = nullptr; s->plan.n_pair_patterns = 0; s->plan.pair_slots = 0;
     s->n_pair_patterns = 0;
+    if (s->sched) { (void)hipFree(s->sched); s->sched = nullptr; }
+    s->plan.sched = nullptr; s->plan.sched_grid = 0;
+    s->sched_unit = 0;
+}
+// The plane-matched XCD schedule of a handle that has just got its row codes.  The unit is the handle's largest
+// stride, read from the row dictionary (9 KB to the host, once per pattern); where spmv_plane_wanted, the table of build_xcd_schedule
+// goes to the device and the row- and pair-coded launches take it and its grid.  Built and dropped with the row codes, so captured
+// graphs are destroyed wherever its pointer changes.
+static int setup_xcd_schedule(cgamd_solver *s) {
+    const size_t vsz = dtype_size(s->dtype);
+    hipStream_t st = s->ctx->stream;
+    std::vector<int> off(256 * 8), len(256);
+    const char *rd = static_cast<const char *>(s->rdict);
+    CG_HIP(hipMemcpyAsync(off.data(), rd + row_dict_off_at(vsz), off.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    CG_HIP(hipMemcpyAsync(len.data(), rd + row_dict_len_at(vsz), len.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    CG_HIP(hipStreamSynchronize(st));
+    long long unit = 0;
+    for (int c = 0; c < s->n_patterns && c < 256; ++c)
+        for (int j = 0; j < len[c] && j < 8; ++j) unit = std::max(unit, std::llabs((long long)off[c * 8 + j]) / (long long)vsz);
+    s->sched_unit = unit;
+    if (!spmv_plane_wanted(s->tune.dev_spmv_plane, unit, kSuperRows, (size_t)s->nnz * (vsz + 4))) return CGAMD_OK;
+    std::vector<int> table;
+    const int supers = (s->plan.row_blocks + kSuperRows / kBlock - 1) / (kSuperRows / kBlock);
+    const int grid = build_xcd_schedule(supers, kSuperRows, unit, table);
+    if (grid <= 0) return CGAMD_OK;
+    // the default rule takes only a table that loads the XCDs evenly (the launch lasts as long as the longest list); asked for by
+    // name (dev.spmv_plane = 1) any table runs
+    if (s->tune.dev_spmv_plane != 1 && !xcd_schedule_balanced(supers, grid)) return CGAMD_OK;
+    CG_HIP(hipMalloc(&s->sched, table.size() * sizeof(int)));
+    CG_HIP(hipMemcpyAsync(s->sched, table.data(), table.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    CG_HIP(hipStreamSynchronize(st));       // (the host table goes away)
+    s->plan.sched = s->sched; s->plan.sched_grid = grid;
+    return CGAMD_OK;
 }
 // a handle whose SpMV reads one-byte column codes may carry codes of its values on top
 static bool value_codes_apply(const cgamd_solver *s) {
@@ -453,6 +490,8 @@ static int setup_value_codes(cgamd_solver *s) {
                                              &s->n_pair_patterns, &s->plan.pair_slots)) return rc;
                 if (s->pcodes) { s->plan.pcodes = s->pcodes; s->plan.pdict = s->pdict; s->plan.n_pair_patterns = s->n_pair_patterns; }
             }
+            // ... and both forms' super blocks dealt to the XCDs by their place inside the largest stride
+            if (int rc = setup_xcd_schedule(s)) return rc;
         }
     }
     return CGAMD_OK;
@@ -931,7 +970,7 @@ int cgamd_solver_destroy(cgamd_solver *s) {
         if (s->cols) (void)hipFree(s->cols);
     }
     void *bufs[] = {s->slab, s->part_dq, s->part_rr, s->sc.alpha, s->sc.beta, s->sc.delta,
-                    s->sc.history, s->sc.iter, s->mdiag, s->part_rz, s->rho2, s->tri_coef, s->tri_part, s->tri_cstart, s->tri.maps, s->sc.stage, s->sc.ticket, s->res_sync, s->resw_sync, s->dlag, s->codes, s->dict, s->rm_pace, s->vcodes, s->vdict, s->jcodes, s->jdict_off, s->jdict_val, s->rcodes, s->rdict, s->pcodes, s->pdict};
+                    s->sc.history, s->sc.iter, s->mdiag, s->part_rz, s->rho2, s->tri_coef, s->tri_part, s->tri_cstart, s->tri.maps, s->sc.stage, s->sc.ticket, s->res_sync, s->resw_sync, s->dlag, s->codes, s->dict, s->rm_pace, s->vcodes, s->vdict, s->jcodes, s->jdict_off, s->jdict_val, s->rcodes, s->rdict, s->pcodes, s->pdict, s->sched};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     stop_run_free(s->stop);
@@ -1955,6 +1994,20 @@ int cgamd_solver_row_codes(cgamd_solver *s) { return s ? (row_form(s) ? s->n_use
 int cgamd_solver_row_pairs(cgamd_solver *s) {
     if (!s) return -CGAMD_ERR_INVALID;
     return row_form(s) && s->plan.pcodes && row_pairs_wanted(s->tune.dev_row_pairs, dtype_size(s->dtype)) ? s->n_pair_patterns : 0;
+}
+int cgamd_solver_spmv_schedule(cgamd_solver *s, int *kind, int *grid, long long *unit_rows) {
+    if (!s) return fail(CGAMD_ERR_INVALID, "spmv_schedule: solver is NULL");
+    const bool rf = row_form(s);
+    const bool table = rf && s->plan.sched != nullptr;
+    if (kind) *kind = table ? 1 : 0;
+    if (unit_rows) *unit_rows = rf ? s->sched_unit : 0;
+    if (grid) {
+        const int supers = (s->plan.row_blocks + kSuperRows / kBlock - 1) / (kSuperRows / kBlock);
+        // the launch site's own arithmetic (spmv.hip: a.cycle from tune(), which is s->tune inside every call of this handle)
+        const int cyc = std::max(1, (s->tune.spmv_cycle > 0 ? s->tune.spmv_cycle : 1) / (kSuperRows / kBlock));
+        *grid = table ? s->plan.sched_grid : rf ? rowblock_grid(supers, cyc) : 0;
+    }
+    return CGAMD_OK;
 }
 int cgamd_solver_row_pipe(cgamd_solver *s) { return s ? (row_form(s) ? row_pipe_depth(s->tune.dev_row_pipe, dtype_size(s->dtype)) : 0) : -CGAMD_ERR_INVALID; }
 long long cgamd_solver_iter_moved_bytes(cgamd_solver *s) {

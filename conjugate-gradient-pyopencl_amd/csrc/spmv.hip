@@ -246,6 +246,7 @@ __global__ __launch_bounds__(BLOCK) void spmv_rowblock_kernel(SpmvArgs<T> a) {
 // LDS (two LDS buffers; the row pointers of the pair after that are loaded a step earlier still).  One d.q partial per 256-row
 // block, formed exactly as block_sum<256> forms it, as everywhere.
 constexpr int kVcBlocks = 4;      // row blocks per work-group
+static_assert(kVcBlocks * kBlock == kSuperRows, "the plane-matched schedule (solver.cpp) counts super blocks of kSuperRows rows");
 constexpr int kVcRows = 1;        // of which a thread walks this many at a time (one row of each): 2 were measured slower (108 VGPRs)
 template <typename T> CG_DEV T buf_gather(__amdgpu_buffer_rsrc_t rs, unsigned byte_off) {
     if constexpr (sizeof(T) == 4) {
@@ -599,6 +600,7 @@ template <typename T> struct RowcodeArgs {
     const int *rdict_len;           // [256]
     const int *rdict_off;           // [256][8] byte offsets
     const T *rdict_val;             // [256][8]
+    const int *sched;               // plane-matched schedule: the super block of every work-group, [grid] (null: rowblock_of on `cycle`)
 };
 constexpr int kRowSlots = 7;      // longest coded row
 // PIPELINED like the vcp kernel, and cheaper to have: all four blocks' gather addresses follow from four code bytes that sit in registers
@@ -624,7 +626,8 @@ __global__ __launch_bounds__(BLOCK) void spmv_rowcode_kernel(RowcodeArgs<T> a) {
     static_assert(DEPTH == 1 || DEPTH == 2 || DEPTH == 4, "blocks in flight");
     const int t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
     const int supers = (a.row_blocks + kVcBlocks - 1) / kVcBlocks;
-    const int srb = rowblock_of(blockIdx.x, supers, a.cycle);
+    // (a uniform load, once per work-group; which work-group computes a super block enters neither y nor the partials)
+    const int srb = a.sched ? a.sched[blockIdx.x] : rowblock_of(blockIdx.x, supers, a.cycle);
     if (srb < 0) return;
     const int rb0 = srb * kVcBlocks, nb = min(kVcBlocks, a.row_blocks - rb0);
     const int np = a.n_patterns;
@@ -737,6 +740,7 @@ template <typename T> struct RowpairArgs {
     typename VT<T>::acc *partials;
     const unsigned char *pcodes;    // [(n + 1) / 2 + pad]
     const void *pdict;              // val0 [np][8] | val1 [np][8] | byte offsets [np][8] | masks [np] (pair_dict_stage_bytes)
+    const int *sched;               // plane-matched schedule, as in RowcodeArgs
 };
 template <typename T> struct Two { T a, b; };
 template <typename T> CG_DEV Two<T> buf_gather2(__amdgpu_buffer_rsrc_t rs, unsigned byte_off) {
@@ -774,7 +778,7 @@ __global__ __launch_bounds__(BLOCK) void spmv_rowpair_kernel(RowpairArgs<T> a) {
     static_assert(SLOTS == 7 || SLOTS == 8, "union slots");
     const int t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
     const int supers = (a.row_blocks + kVcBlocks - 1) / kVcBlocks;
-    const int srb = rowblock_of(blockIdx.x, supers, a.cycle);
+    const int srb = a.sched ? a.sched[blockIdx.x] : rowblock_of(blockIdx.x, supers, a.cycle);
     if (srb < 0) return;
     const int rb0 = srb * kVcBlocks, nb = min(kVcBlocks, a.row_blocks - rb0);
     const int np = a.n_pair_patterns;
@@ -1337,6 +1341,9 @@ static int spmv_impl(const SpmvPlan &plan, int n, long long nnz, const void *val
                 const bool joint = pipe && plan.jcodes && tune().dev_joint_codes != 0;
                 // ... and where the rows follow at most 256 patterns: one byte per ROW (build_row_codes), no row pointers and no code staging
                 const bool rowform = joint && plan.rcodes && plan.rcodes_for == ptr && tune().dev_row_codes != 0;
+                // ... whose super blocks the handle's plane-matched table deals to the XCDs where it has one (solver.cpp setup_xcd_schedule);
+                // the grid is the table's
+                const dim3 grc(plan.sched ? (unsigned)plan.sched_grid : gvc.x);
                 // ... and two rows per lane on one byte per PAIR of rows (build_row_pairs) where the vectors allow 16-byte accesses
                 // (a caller's Solver.spmv vectors may not: the row form takes those)
                 if (rowform && plan.pcodes && plan.pdict && plan.n_pair_patterns > 0 && row_pairs_wanted(tune().dev_row_pairs, sizeof(T)) && n >= 2 &&
@@ -1344,17 +1351,17 @@ static int spmv_impl(const SpmvPlan &plan, int n, long long nnz, const void *val
                     RowpairArgs<T> pa;
                     pa.n = n; pa.row_blocks = plan.row_blocks; pa.cycle = cyc; pa.n_pair_patterns = plan.n_pair_patterns;
                     pa.x = a.x; pa.y = a.y; pa.dvec = a.dvec; pa.partials = a.partials;
-                    pa.pcodes = plan.pcodes; pa.pdict = plan.pdict;
+                    pa.pcodes = plan.pcodes; pa.pdict = plan.pdict; pa.sched = plan.sched;
                     const size_t ldsp = pair_dict_stage_bytes(plan.n_pair_patterns, sizeof(T));
-                    record_form(8, true, unroll, 8, 3, nt, fuse, false, gvc.x, plan.row_blocks);
+                    record_form(8, true, unroll, 8, 3, nt, fuse, false, grc.x, plan.row_blocks);
 #define CG_RP(DEPTH, SLOTS)                                                                                             \
     do {                                                                                                                \
         if (nt) {                                                                                                \
-            if (fuse) CG_LAUNCH_EV((spmv_rowpair_kernel<T, kBlock, true, true, DEPTH, SLOTS>), gvc, block, ldsp, st, pa);   \
-            else CG_LAUNCH_EV((spmv_rowpair_kernel<T, kBlock, true, false, DEPTH, SLOTS>), gvc, block, ldsp, st, pa);       \
+            if (fuse) CG_LAUNCH_EV((spmv_rowpair_kernel<T, kBlock, true, true, DEPTH, SLOTS>), grc, block, ldsp, st, pa);   \
+            else CG_LAUNCH_EV((spmv_rowpair_kernel<T, kBlock, true, false, DEPTH, SLOTS>), grc, block, ldsp, st, pa);       \
         } else {                                                                                                        \
-            if (fuse) CG_LAUNCH_EV((spmv_rowpair_kernel<T, kBlock, false, true, DEPTH, SLOTS>), gvc, block, ldsp, st, pa);  \
-            else CG_LAUNCH_EV((spmv_rowpair_kernel<T, kBlock, false, false, DEPTH, SLOTS>), gvc, block, ldsp, st, pa);      \
+            if (fuse) CG_LAUNCH_EV((spmv_rowpair_kernel<T, kBlock, false, true, DEPTH, SLOTS>), grc, block, ldsp, st, pa);  \
+            else CG_LAUNCH_EV((spmv_rowpair_kernel<T, kBlock, false, false, DEPTH, SLOTS>), grc, block, ldsp, st, pa);      \
         }                                                                                                               \
     } while (0)
                     // passes whose gathers are in flight per wave: dev.row_pipe's depth, 4 meaning 2 here
@@ -1369,17 +1376,17 @@ static int spmv_impl(const SpmvPlan &plan, int n, long long nnz, const void *val
                     ra.n = n; ra.row_blocks = plan.row_blocks; ra.cycle = cyc; ra.n_patterns = plan.n_patterns;
                     ra.x = a.x; ra.y = a.y; ra.dvec = a.dvec; ra.partials = a.partials;
                     ra.rcodes = plan.rcodes; ra.rdict_len = plan.rdict_len; ra.rdict_off = plan.rdict_off;
-                    ra.rdict_val = static_cast<const T *>(plan.rdict_val);
+                    ra.rdict_val = static_cast<const T *>(plan.rdict_val); ra.sched = plan.sched;
                     const size_t ldsr = (size_t)plan.n_patterns * (8 * sizeof(T) + 8 * sizeof(int) + sizeof(int));
-                    record_form(7, true, unroll, 8, 3, nt, fuse, false, gvc.x, plan.row_blocks);
+                    record_form(7, true, unroll, 8, 3, nt, fuse, false, grc.x, plan.row_blocks);
 #define CG_RC(DEPTH)                                                                                                    \
     do {                                                                                                                \
         if (nt) {                                                                                                       \
-            if (fuse) CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, true, true, DEPTH>), gvc, block, ldsr, st, ra);      \
-            else CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, true, false, DEPTH>), gvc, block, ldsr, st, ra);          \
+            if (fuse) CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, true, true, DEPTH>), grc, block, ldsr, st, ra);      \
+            else CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, true, false, DEPTH>), grc, block, ldsr, st, ra);          \
         } else {                                                                                                        \
-            if (fuse) CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, false, true, DEPTH>), gvc, block, ldsr, st, ra);     \
-            else CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, false, false, DEPTH>), gvc, block, ldsr, st, ra);         \
+            if (fuse) CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, false, true, DEPTH>), grc, block, ldsr, st, ra);     \
+            else CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, false, false, DEPTH>), grc, block, ldsr, st, ra);         \
         }                                                                                                               \
     } while (0)
                     // row blocks whose gathers are in flight per wave (dev.row_pipe; 0 = the default rule)

@@ -566,6 +566,17 @@ int cgamd_solver_row_pipe(cgamd_solver *s);
  * 256 pair patterns, or a pair whose union needs more than 8 slots.  cgamd_last_spmv_form reports the pair form as family 8; a
  * launch whose vectors are not 16-byte aligned runs the row form (family 7). */
 int cgamd_solver_row_pairs(cgamd_solver *s);
+/* how the handle's row- or pair-coded SpMV deals its super blocks (1024 rows, one work-group each) to the eight XCDs.  *kind 1: the
+ * PLANE-MATCHED table -- super block s runs on XCD floor(8 frac(centre(s) / unit)), every XCD's blocks in ascending order, so rows r and
+ * r + unit (the neighbours across the largest stride: a z plane of a 3-D grid) meet in one XCD's L2 and their line of x is fetched
+ * once; *kind 0: the block-cyclic schedule of the tuning key "spmv_cycle".  *grid: the work-groups of a launch (0: the handle runs
+ * neither form); *unit_rows: the largest |column - row| among the handle's row patterns (0 likewise).  Which work-group computes a
+ * row enters no result: same bits under either kind.  cgamd_tune("dev.spmv_plane", 1 / 0) forces the table or the cycle for handles
+ * created afterwards (1: for any unit of at least one row, however unevenly the table loads the XCDs -- a unit of exactly one super
+ * block puts every block on one XCD; a development setting); -1 restores the default rule: the table where the unit is at least 8
+ * super blocks (3-D grids), the matrix above 256 MB and the longest XCD list at most 2 % above an eighth of the super blocks, else the
+ * cycle (a third less read traffic, 1 to 2 % of an iteration).  Any out pointer may be NULL. */
+int cgamd_solver_spmv_schedule(cgamd_solver *s, int *kind, int *grid, long long *unit_rows);
 int cgamd_transpose(cgamd_ctx *ctx, int dtype, int rows, int cols, const void *in, void *out);
 /* algorithmic HBM bytes of one SpMV / one CG iteration of this solver (SURVEY §8d formulae: 14 vector passes for the
  * reference's op structure, 11 for its "fused minimum"; the default loop here moves 10) */
