@@ -98,6 +98,12 @@ def load():
         "cgamd_solver_mg_apply": (ci, [vp, vp, vp]),
         "cgamd_solver_set_preconditioner_amg": (ci, [vp, ci, ctypes.c_double, ci, ctypes.c_double, ci]),
         "cgamd_solver_mg_aggregates": (ci, [vp, ci, vp, ctypes.POINTER(ci)]),
+        "cgamd_mg_smooth_step": (ci, [vp, ci, ci, ci, ll, ci, vp, vp, vp, vp, vp, ctypes.c_double, ctypes.c_double, ci]),
+        "cgamd_mg_restrict": (ci, [vp, ci, ci, ci, ci, vp, ci, ll, ll, ci, vp, vp, vp, vp, vp, vp, ctypes.c_double, ci]),
+        "cgamd_mg_prolong": (ci, [vp, ci, ci, ci, ci, vp, ci, ll, ll, ci, vp, vp, ctypes.c_double]),
+        "cgamd_mg_scan": (ci, [vp, ci, vp, vp]),
+        "cgamd_solver_mg_level_state": (ci, [vp, ci, ci, vp, ll, ctypes.POINTER(ll)]),
+        "cgamd_solver_mg_level_spmv": (ci, [vp, ci, vp, vp]),
         "cgamd_solver_preconditioner_source": (ci, [vp]),
         "cgamd_solver_iterate": (ci, [vp, ci]),
         "cgamd_solver_iterate_timed": (ci, [vp, ci, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),

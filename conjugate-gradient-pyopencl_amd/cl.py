@@ -533,6 +533,27 @@ class Solver:
             rd.release()
             zd.release()
 
+    def mg_level_state(self, level, which):
+        """one piece of what a level of the hierarchy in force holds (include/cgamd.h cgamd_solver_mg_level_state; development
+        accessor: tests).  which 0: a dict (n, nu, ld, steps, algebraic); 1: dinv, n values; 2 / 3: c0 / c1, doubles; 4: the member
+        lists, (rows of the next level, 8) ints"""
+        dtype = {1: self.dtype, 2: np.float64, 3: np.float64}.get(which, np.intc)
+        count = ctypes.c_longlong(0)
+        probe = np.empty(1, dtype)
+        rc = self._lib.cgamd_solver_mg_level_state(self.handle, int(level), int(which), ptr(probe), 0, ctypes.byref(count))
+        if rc != 0 and count.value == 0:
+            check(rc)
+        out = np.empty(count.value, dtype)
+        check(self._lib.cgamd_solver_mg_level_state(self.handle, int(level), int(which), ptr(out), out.size, ctypes.byref(count)))
+        if which == 0:
+            return dict(zip(("n", "nu", "ld", "steps", "algebraic"), (int(v) for v in out)))
+        return out.reshape(-1, 8) if which == 4 else out
+
+    def mg_level_spmv(self, level, x_dev, w_dev):
+        """w = A_level x as the V-cycle launches it, on device vectors of n_rhs * ld values at the level's leading dimension
+        (development accessor: tests); last_spmv_form() then reports what ran"""
+        check(self._lib.cgamd_solver_mg_level_spmv(self.handle, int(level), ptr(x_dev), ptr(w_dev)))
+
     def _set_tridiag(self, m):
         """the three diagonals of a sparse M with nnz > size into cgamd_solver_set_preconditioner_tridiag, or, when they lie at
         distance s > 1, into cgamd_solver_set_preconditioner_tridiag_strided"""

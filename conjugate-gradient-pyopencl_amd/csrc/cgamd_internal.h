@@ -688,6 +688,11 @@ int mg_level_info(const MgHierarchy *h, int level, long long info[6]);
 int mg_level_matrix(const MgHierarchy *h, int level, int *ptr, int *cols, void *vals, hipStream_t st);
 // the map level -> level + 1 to the host (rows of the level ints; the box map of a grid hierarchy), *n_coarse = rows of level + 1
 int mg_aggregates(const MgHierarchy *h, int level, int *agg_host, int *n_coarse, hipStream_t st);
+// which: 0 five ints (n, nu, ld, steps, algebraic), 1 dinv (n values), 2 / 3 c0 / c1 (steps doubles), 4 the member lists (kAmgWidth
+// ints per row of level + 1); *count is set even when cap_values is too small.  Synchronises
+int mg_level_state(const MgHierarchy *h, int level, int which, void *out_host, long long cap_values, long long *count, hipStream_t st);
+// w = A_level x as the cycle launches it (the level's plan and leading dimension, the hierarchy's nrhs); synchronises
+int mg_level_spmv(const MgHierarchy *h, int level, const void *x, void *w, hipStream_t st);
 // ---- PCG of the row-partitioned loop (vector.hip, p2p.hip): z lives in q's storage for every preconditioner; part = [2][P] partials
 // (r.z, then r.r); rho2 = two-entry parity buffer of rho = r.z (entry iter & 1), delta holds rho for cg_alpha
 // r -= alpha q ; z = m .* r (stored over q) ; partials of r.z and r.r

@@ -410,4 +410,116 @@ int mg_aggregates(const MgHierarchy *h, int level, int *agg_host, int *n_coarse,
     return CGAMD_OK;
 }
 
+// ---- development entries (tests): what a level holds, and one level's product as the cycle launches it ----------------------------
+int mg_level_state(const MgHierarchy *h, int level, int which, void *out_host, long long cap_values, long long *count, hipStream_t st) {
+    if (level < 0 || level >= (int)h->lv.size()) return fail(CGAMD_ERR_INVALID, "mg_level_state: no such level");
+    const MgLevel &L = h->lv[(size_t)level];
+    int five[5] = {L.n, L.nu, (int)L.ld, L.steps, h->p.algebraic ? 1 : 0};
+    const void *host = nullptr, *dev = nullptr;
+    size_t each = 0;
+    long long values = 0;
+    switch (which) {
+    case 0: host = five; each = sizeof(int); values = 5; break;
+    case 1: dev = L.dinv; each = dtype_size(h->dtype); values = L.n; break;
+    case 2: host = L.c0.data(); each = sizeof(double); values = L.steps; break;
+    case 3: host = L.c1.data(); each = sizeof(double); values = L.steps; break;
+    case 4:
+        if (!L.mem || level + 1 >= (int)h->lv.size())
+            return fail(CGAMD_ERR_INVALID, "mg_level_state: the level has no member lists (a grid hierarchy, or the coarsest level)");
+        dev = L.mem; each = sizeof(int); values = (long long)kAmgWidth * h->lv[(size_t)level + 1].nu;
+        break;
+    default: return fail(CGAMD_ERR_INVALID, "mg_level_state: which is 0 .. 4");
+    }
+    *count = values;
+    if (cap_values < values) return fail(CGAMD_ERR_INVALID, "mg_level_state: output holds fewer values than the state has");
+    if (host) std::memcpy(out_host, host, each * (size_t)values);
+    else CG_HIP(hipMemcpyAsync(out_host, dev, each * (size_t)values, hipMemcpyDeviceToHost, st));
+    CG_HIP(hipStreamSynchronize(st));
+    return CGAMD_OK;
+}
+int mg_level_spmv(const MgHierarchy *h, int level, const void *x, void *w, hipStream_t st) {
+    if (level < 0 || level >= (int)h->lv.size()) return fail(CGAMD_ERR_INVALID, "mg_level_spmv: no such level");
+    const MgLevel &L = h->lv[(size_t)level];
+    if (int rc = launch_spmv(h->dtype, L.plan, L.n, L.nnz, L.vals, L.ptr, L.cols, x, L.ld, w, L.ld, h->nrhs, nullptr, nullptr, st)) return rc;
+    CG_HIP(hipStreamSynchronize(st));
+    return CGAMD_OK;
+}
+
 }  // namespace cgamd
+
+// ---- the cycle kernels and the scan as stateless entries (include/cgamd.h "Multigrid: the kernels"): thin wrappers over the launch_*
+// the cycle and the setup call, with pointers and leading dimensions left to the caller.  What can be judged without a device is
+// judged first, the context last.
+using namespace cgamd;
+
+static int mg_op(cgamd_ctx *ctx, int dtype, const char *what) {
+    if (dtype < 0 || dtype > 3) return fail(CGAMD_ERR_INVALID, std::string(what) + ": dtype must be one of the four value types");
+    if (!ctx) return fail(CGAMD_ERR_INVALID, std::string(what) + ": ctx is NULL");
+    thread_hip_setup();
+    CG_HIP(hipSetDevice(ctx->device));
+    return CGAMD_OK;
+}
+static int mg_done(cgamd_ctx *ctx, int rc) {
+    if (rc) return rc;
+    CG_HIP(hipStreamSynchronize(ctx->stream));
+    return CGAMD_OK;
+}
+// the grid of a box map; false when a dimension is below 1 or the rows do not fit an int
+static bool mg_box(int nx, int ny, int nz, MgGrid *g, long long *nf, long long *nc) {
+    if (nx < 1 || ny < 1 || nz < 1) return false;
+    g->nx = nx; g->ny = ny; g->nz = nz;
+    g->cnx = (nx + 1) / 2; g->cny = (ny + 1) / 2; g->cnz = (nz + 1) / 2;
+    *nf = (long long)nx * ny * nz;
+    *nc = (long long)g->cnx * g->cny * g->cnz;
+    return *nf <= 2147483647LL;
+}
+
+extern "C" {
+
+int cgamd_mg_smooth_step(cgamd_ctx *ctx, int dtype, int mode, int size, long long ld, int nRHS, const void *dinv, const void *b, const void *w,
+                         void *d, void *x, double c0, double c1, int store_d) {
+    if (mode < 0 || mode > 2) return fail(CGAMD_ERR_INVALID, "mg_smooth_step: mode is 0, 1 or 2");
+    if (!dinv || !b || !x || (mode != 0 && !w) || ((mode == 2 || store_d) && !d)) return fail(CGAMD_ERR_INVALID, "mg_smooth_step: null pointer");
+    if (size < 0 || nRHS < 1) return fail(CGAMD_ERR_INVALID, "mg_smooth_step: bad size/nRHS");
+    if (ld < size) return fail(CGAMD_ERR_INVALID, "mg_smooth_step: leading dimension below size");
+    if (int rc = mg_op(ctx, dtype, "mg_smooth_step")) return rc;
+    return mg_done(ctx, launch_mg_cheb(dtype, mode, size, ld, nRHS, dinv, b, w, d, x, c0, c1, store_d != 0, ctx->stream));
+}
+
+int cgamd_mg_restrict(cgamd_ctx *ctx, int dtype, int nx, int ny, int nz, const int *members, int n_coarse, long long ld_f, long long ld_c,
+                      int nRHS, const void *b, const void *w, void *bc, const void *dinv_c, void *xc, void *dc, double c1, int store_d) {
+    if (!b || !w || !bc || !dinv_c || !xc || (store_d && !dc)) return fail(CGAMD_ERR_INVALID, "mg_restrict: null pointer");
+    if (n_coarse < 0 || nRHS < 1) return fail(CGAMD_ERR_INVALID, "mg_restrict: bad size/nRHS");
+    MgGrid g;
+    long long nf = nx, nc = n_coarse;
+    if (members ? nx < 1 : !mg_box(nx, ny, nz, &g, &nf, &nc)) return fail(CGAMD_ERR_INVALID, "mg_restrict: bad size/nRHS");
+    if (nc != n_coarse) return fail(CGAMD_ERR_INVALID, "mg_restrict: n_coarse is not the number of boxes of the grid");
+    if (ld_f < nf || ld_c < n_coarse) return fail(CGAMD_ERR_INVALID, "mg_restrict: leading dimension below size");
+    if (int rc = mg_op(ctx, dtype, "mg_restrict")) return rc;
+    if (n_coarse == 0) return CGAMD_OK;
+    if (members) return mg_done(ctx, launch_amg_restrict(dtype, n_coarse, members, ld_f, ld_c, nRHS, b, w, bc, dinv_c, xc, dc, c1, store_d != 0, ctx->stream));
+    return mg_done(ctx, launch_mg_restrict(dtype, g, n_coarse, ld_f, ld_c, nRHS, b, w, bc, dinv_c, xc, dc, c1, store_d != 0, ctx->stream));
+}
+
+int cgamd_mg_prolong(cgamd_ctx *ctx, int dtype, int nx, int ny, int nz, const int *agg, int n_fine, long long ld_f, long long ld_c, int nRHS,
+                     const void *e, void *x, double omega) {
+    if (!e || !x) return fail(CGAMD_ERR_INVALID, "mg_prolong: null pointer");
+    if (n_fine < 0 || nRHS < 1) return fail(CGAMD_ERR_INVALID, "mg_prolong: bad size/nRHS");
+    MgGrid g;
+    long long nf = n_fine, nc = 1;
+    if (!agg && (!mg_box(nx, ny, nz, &g, &nf, &nc) || n_fine > nf)) return fail(CGAMD_ERR_INVALID, "mg_prolong: bad size/nRHS");
+    if (ld_f < n_fine || ld_c < nc) return fail(CGAMD_ERR_INVALID, "mg_prolong: leading dimension below size");
+    if (int rc = mg_op(ctx, dtype, "mg_prolong")) return rc;
+    if (n_fine == 0) return CGAMD_OK;
+    if (agg) return mg_done(ctx, launch_amg_prolong(dtype, n_fine, agg, ld_f, ld_c, nRHS, e, x, omega, ctx->stream));
+    return mg_done(ctx, launch_mg_prolong(dtype, g, n_fine, ld_f, ld_c, nRHS, e, x, omega, ctx->stream));
+}
+
+int cgamd_mg_scan(cgamd_ctx *ctx, int n, int *counts_to_ptr, int *overflow) {
+    if (!counts_to_ptr || !overflow) return fail(CGAMD_ERR_INVALID, "mg_scan: null pointer");
+    if (n < 0) return fail(CGAMD_ERR_INVALID, "mg_scan: bad size");
+    if (int rc = mg_op(ctx, CGAMD_F64, "mg_scan")) return rc;
+    return mg_done(ctx, launch_mg_scan(n, counts_to_ptr, overflow, ctx->stream));
+}
+
+}  // extern "C"

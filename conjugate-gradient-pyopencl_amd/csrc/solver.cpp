@@ -1345,6 +1345,21 @@ int cgamd_solver_mg_apply(cgamd_solver *s, const void *r_dev, void *z_dev) {
     if (e != hipSuccess || e2 != hipSuccess) return fail(CGAMD_ERR_HIP, std::string("mg_apply: ") + hipGetErrorString(e != hipSuccess ? e : e2));
     return CGAMD_OK;
 }
+int cgamd_solver_mg_level_state(cgamd_solver *s, int level, int which, void *out_host, long long cap_values, long long *count) {
+    if (!s || !out_host || !count) return fail(CGAMD_ERR_INVALID, "mg_level_state: null argument");
+    if (int rc = mg_wanted(s, "mg_level_state")) return rc;
+    CG_HIP(hipSetDevice(s->ctx->device));
+    if (int rc = step_not_capturing(s, "mg_level_state")) return rc;
+    return mg_level_state(s->mg, level, which, out_host, cap_values, count, s->ctx->stream);
+}
+int cgamd_solver_mg_level_spmv(cgamd_solver *s, int level, const void *x_dev, void *w_dev) {
+    if (!s || !x_dev || !w_dev) return fail(CGAMD_ERR_INVALID, "mg_level_spmv: null argument");
+    if (int rc = mg_wanted(s, "mg_level_spmv")) return rc;
+    TuneScope ts(&s->tune);
+    CG_HIP(hipSetDevice(s->ctx->device));
+    if (int rc = step_not_capturing(s, "mg_level_spmv")) return rc;
+    return mg_level_spmv(s->mg, level, x_dev, w_dev, s->ctx->stream);
+}
 
 // ---- a batched handle: one M per system (M_r for right-hand side r), never one shared by all ------------------------------------------
 static int not_batched(const char *who, const char *shared) {

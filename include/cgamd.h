@@ -469,6 +469,68 @@ int cgamd_solver_set_preconditioner_amg(cgamd_solver *s, int passes, double stre
  * level` ints to the host, *n_coarse = rows of the next level (either pointer may be NULL); also serves a grid hierarchy (the box
  * map).  CGAMD_ERR_INVALID on the coarsest level; synchronises. */
 int cgamd_solver_mg_aggregates(cgamd_solver *s, int level, int *agg_host, int *n_coarse);
+/* ---- Multigrid: the kernels (csrc/multigrid.hip, csrc/amg.hip) ----
+ * Development entries (tests; same standing as the cgamd_mixed_* and cgamd_projection_* kernel entries): the three kernels of the
+ * V-cycle and the scan of the setup as the hierarchy launches them, thin wrappers over the same launch functions, and what a handle's
+ * hierarchy holds per level.  All pointers of the stateless entries are DEVICE pointers and free, as are the leading dimensions; a
+ * call runs on the ctx stream and is synchronised.  CGAMD_ERR_INVALID, judged in this order and before the context is looked at: a
+ * mode outside 0 .. 2, a null pointer that the call needs, a bad size / nRHS (negative size, nRHS < 1, a grid dimension < 1, n_coarse
+ * that is not the number of boxes), a leading dimension below the size, a dtype outside the four value types, then ctx == NULL.  A
+ * size of 0 launches nothing.
+ * ARITHMETIC of all three: every operation is ONE IEEE operation in the value type T (no contraction into a multiply-add); complex
+ * values go by components, vmul(a, b) = (ar br - ai bi, ar bi + ai br), a scale by c0, c1 or omega multiplies both components by the
+ * coefficient ROUNDED TO THE REAL TYPE of T first.  No reductions across threads: every output element is one thread's own sequence,
+ * so the bits do not depend on the launch geometry.  Column r of a vector starts at r * ld; dinv is shared by the columns.
+ * NO LANE AT OR BEYOND `size` of any column is read or written (padding lanes between size and ld keep their bytes).
+ * cgamd_mg_smooth_step: one Chebyshev step per lane i < size of every column, in this order:
+ *     res = b[i]                      mode 0 (x = 0 on entry; w is NOT READ and may be NULL, x is NOT READ)
+ *     res = b[i] - w[i]               modes 1 and 2 (w = A x)
+ *     t   = vmul(dinv[i], res)        the complex product by components
+ *     t   = c1 * t                    by components
+ *     t   = c0 * d[i] + t             mode 2 only: the scaled d is the LEFT operand; d is NOT READ in modes 0 and 1
+ *     d[i] = t                        only when store_d != 0: with store_d == 0, d is NOT WRITTEN (and may be NULL unless mode is 2)
+ *     x[i] = t (mode 0) or x[i] + t   (modes 1 and 2)
+ *   b, w and dinv are only read.  c0 is ignored in modes 0 and 1.
+ * cgamd_mg_restrict: per coarse row I < n_coarse of every column: s = +0; for every fine row i of aggregate I, ASCENDING,
+ *   s = s + (b[i] - w[i]); bc[I] = s; t = c1 * vmul(dinv_c[I], s); xc[I] = t; dc[I] = t only when store_d != 0 (else dc is NOT WRITTEN
+ *   and may be NULL).  members == NULL: the box map of the nx x ny x nz grid (n_coarse = ceil(nx / 2) ceil(ny / 2) ceil(nz / 2); the
+ *   rows of a box ascend as x fastest, then y, then z).  Otherwise members holds 8 ints per coarse row, fine rows ascending, -1 behind
+ *   the last (a list of exactly 8 has no -1), read as two 16-byte loads: the pointer must be 16-byte aligned; nx names the number of
+ *   fine rows (ny, nz unused) and every member must lie in [0, nx).  Fine rows in no aggregate are not read; b, w, dinv_c, members are
+ *   only read.  ld_f >= fine rows, ld_c >= n_coarse.
+ * cgamd_mg_prolong: x[i] = x[i] + omega * e[agg(i)] (by components) for i < n_fine of every column; nothing at or beyond n_fine.
+ *   agg == NULL: the box map of the grid (n_fine <= nx ny nz, ld_c >= the number of boxes).  Otherwise agg holds n_fine ints, the
+ *   coarse row of every fine row (nx, ny, nz unused; ld_c >= 1 is all that can be judged).  e and agg are only read.
+ * cgamd_mg_scan: a[0 .. n - 1] counts (non-negative ints) -> exclusive prefix sums in place, a[n] = the total; integer sums, exact.
+ *   One work-group of 1024 threads, thread t takes the chunk [t ceil(n / 1024), (t + 1) ceil(n / 1024)) cut at n.  A total above
+ *   2^31 - 1: *overflow = 1, a[n] = 2^31 - 1 and every prefix is clamped to 2^31 - 1; otherwise *overflow is NOT WRITTEN (the caller
+ *   presets it to 0).  Nothing behind a[n] is touched. */
+int cgamd_mg_smooth_step(cgamd_ctx *ctx, int dtype, int mode, int size, long long ld, int nRHS, const void *dinv, const void *b,
+                         const void *w, void *d, void *x, double c0, double c1, int store_d);
+int cgamd_mg_restrict(cgamd_ctx *ctx, int dtype, int nx, int ny, int nz, const int *members, int n_coarse, long long ld_f, long long ld_c,
+                      int nRHS, const void *b, const void *w, void *bc, const void *dinv_c, void *xc, void *dc, double c1, int store_d);
+int cgamd_mg_prolong(cgamd_ctx *ctx, int dtype, int nx, int ny, int nz, const int *agg, int n_fine, long long ld_f, long long ld_c, int nRHS,
+                     const void *e, void *x, double omega);
+int cgamd_mg_scan(cgamd_ctx *ctx, int n, int *counts_to_ptr, int *overflow);
+/* On a handle with a hierarchy in force (CGAMD_ERR_STATE without one, CGAMD_ERR_INVALID for a NULL handle or pointer, a level that does
+ * not exist, or while the handle's stream is being captured); both synchronise.
+ * cgamd_solver_mg_level_state, shaped like cgamd_solver_step_state (cap_values = values out_host holds; *count is set even when the
+ *   capacity is too small, CGAMD_ERR_INVALID then).  which: 0 five ints -- n, the rows the level's kernels work on (level 0: with the
+ *   padding rows), nu, the rows of the level, the leading dimension of its vectors, its smoothing steps (8 on the coarsest), 1 for an
+ *   algebraic hierarchy; 1 dinv, n values of the handle's type (the padding rows of level 0 are +0); 2 / 3 c0[k] / c1[k], k <
+ *   steps, as the doubles the launches are given (they round them to the real type; c0[0] = 0 is never read); 4 the member lists of the
+ *   level's aggregates, 8 ints per row of the next level (CGAMD_ERR_INVALID for a grid hierarchy and for the coarsest level).
+ * cgamd_solver_mg_level_spmv: w = A_level x exactly as the cycle launches it -- the level's own plan, n rows, the level's leading
+ *   dimension ld for x and w -- on caller vectors of nRHS * ld values (device pointers).  cgamd_last_spmv_form afterwards reports
+ *   what ran on that level.
+ * The launch chain of one cycle, L = the last level, s_l = steps of level l (every smoothing step works on n rows, restriction on the
+ * nu rows of level l + 1, prolongation on the nu rows of level l):
+ *   down, l = 0 .. L:  l == 0: smooth_step mode 0 (x = z, b = r, store_d = s_0 > 1);  for k = 1 .. s_l - 1: w = A_l x, smooth_step mode 2
+ *     (c0[k], c1[k], store_d = 1);  l < L: w = A_l x, restrict into level l + 1 (c1[0] of level l + 1, store_d = s_{l+1} > 1);
+ *   up, l = L - 1 .. 0:  prolong (omega = over_correction), w = A_l x, smooth_step mode 1 (c1[0], store_d = s_l > 1), then the
+ *     steps k = 1 .. s_l - 1 as above. */
+int cgamd_solver_mg_level_state(cgamd_solver *s, int level, int which, void *out_host, long long cap_values, long long *count);
+int cgamd_solver_mg_level_spmv(cgamd_solver *s, int level, const void *x_dev, void *w_dev);
 /* where the preconditioner in force came from -- 0: none; 1: the caller's arrays (the three array entries above, and
  * cgamd_solver_set_preconditioner_batched); 2: the matrix, built on the device; 3: the matrix, extracted on the device but factored by
  * the host route (long segments; never on a batched handle) */
