@@ -92,6 +92,8 @@ def load():
         "cgamd_solver_set_preconditioner_batched_jacobi": (ci, [vp]),
         "cgamd_solver_set_preconditioner_batched_line": (ci, [vp, ci]),
         "cgamd_solver_set_preconditioner_multigrid": (ci, [vp, ci, ci, ci, ci, ctypes.c_double, ci]),
+        "cgamd_solver_set_preconditioner_batched_multigrid": (ci, [vp, ci, ci, ci, ci, ctypes.c_double, ci]),
+        "cgamd_solver_mg_level_bounds": (ci, [vp, ci, ctypes.POINTER(ctypes.c_double), ci]),
         "cgamd_solver_mg_levels": (ci, [vp]),
         "cgamd_solver_mg_level": (ci, [vp, ci, ctypes.POINTER(ll)]),
         "cgamd_solver_mg_level_matrix": (ci, [vp, ci, vp, vp, vp]),

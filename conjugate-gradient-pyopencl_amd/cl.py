@@ -218,6 +218,17 @@ def _set_preconditioner_batched(self, m):
     if isinstance(m, tuple) and len(m) == 2 and isinstance(m[0], str) and m[0] == "line":
         check(self._lib.cgamd_solver_set_preconditioner_batched_line(self.handle, int(m[1])))
         return
+    if isinstance(m, tuple) and len(m) in (2, 3) and isinstance(m[0], str) and m[0] == "multigrid":
+        dims = tuple(int(d) for d in m[1]) + (1,) * (3 - len(m[1]))
+        opts = dict(m[2]) if len(m) == 3 else {}
+        unknown = set(opts) - {"smooth_steps", "over_correction", "min_rows"}
+        if len(dims) != 3 or unknown:
+            raise ValueError('("multigrid", (nx, ny, nz)[, {"smooth_steps": 1, "over_correction": 1.6, "min_rows": 512}])')
+        check(self._lib.cgamd_solver_set_preconditioner_batched_multigrid(self.handle, dims[0], dims[1], dims[2],
+                                                                          int(opts.get("smooth_steps", 0)),
+                                                                          float(opts.get("over_correction", 0.0)),
+                                                                          int(opts.get("min_rows", 0))))
+        return
     if isinstance(m, (list, tuple)) and len(m) == self.n_rhs and all(hasattr(a, "diagonal") and hasattr(a, "nnz") for a in m):
         if any(a.shape != (self.size, self.size) or a.nnz > self.size for a in m):
             raise ValueError('a list of matrices on a batched handle gives their diagonals: n_rhs matrices of size x size with '
@@ -238,7 +249,7 @@ def _set_preconditioner_batched(self, m):
     if isinstance(m, int) or hasattr(m, "data_ptr") or hasattr(m, "ptr"):      # a device buffer of n_rhs * size values
         check(self._lib.cgamd_solver_set_preconditioner_batched(self.handle, ptr(m), 1))
         return
-    raise ValueError('a batched handle takes one preconditioner per system: None, "jacobi", ("line", stride), n_rhs * size '
+    raise ValueError('a batched handle takes one preconditioner per system: None, "jacobi", ("line", stride), ("multigrid", dims), n_rhs * size '
                      'diagonal entries (host array or device buffer) or a list of n_rhs diagonal matrices; for the tridiagonal '
                      'part of every system use ("line", stride)')
 
@@ -445,7 +456,8 @@ class Solver:
         Any other M raises ValueError.  Takes effect at the next set_rhs; history() keeps returning r.r.
 
         A batched handle takes one M per system (cgamd_solver_set_preconditioner_batched*): None, "jacobi" (1 / diag(A_r)),
-        ("line", stride) (the lines of every A_r, one segment plan for all), a host array of n_rhs * size entries (1-D, or
+        ("line", stride) (the lines of every A_r, one segment plan for all), ("multigrid", dims[, opts]) (one V-cycle per system on a
+        hierarchy of its own over shared aggregates, cgamd_solver_set_preconditioner_batched_multigrid), a host array of n_rhs * size entries (1-D, or
         (n_rhs, size): row r multiplies the residual of system r), a device buffer of that many, or a list of n_rhs scipy matrices
         with nnz <= size each (their diagonals)."""
         if self.batched:
@@ -495,20 +507,30 @@ class Solver:
         check(self._lib.cgamd_solver_set_preconditioner(self.handle, ptr(m), int(on_device)))
 
     def mg_levels(self):
-        """the multigrid hierarchy in force: a list of dicts (rows, nnz, nx, ny, nz, lmax), level 0 first; [] without one"""
+        """the multigrid hierarchy in force: a list of dicts (rows, nnz, nx, ny, nz, lmax), level 0 first; [] without one.  On a
+        batched handle lmax is the list of the n_rhs per-system bounds"""
         out = []
         for l in range(max(0, self._lib.cgamd_solver_mg_levels(self.handle))):
             info = (ctypes.c_longlong * 6)()
             check(self._lib.cgamd_solver_mg_level(self.handle, l, info))
             out.append({"rows": int(info[0]), "nnz": int(info[1]), "nx": int(info[2]), "ny": int(info[3]), "nz": int(info[4]),
                         "lmax": float(np.array([info[5]], dtype=np.int64).view(np.float64)[0])})
+            if self.batched:
+                out[-1]["lmax"] = [float(v) for v in self.mg_level_bounds(l)]
         return out
 
+    def mg_level_bounds(self, level):
+        """lmax of every system of a level of the hierarchy in force (one value on a handle that is not batched), doubles"""
+        out = (ctypes.c_double * (self.n_rhs if self.batched else 1))()
+        check(self._lib.cgamd_solver_mg_level_bounds(self.handle, int(level), out, len(out)))
+        return np.array(out[:], dtype=np.float64)
+
     def mg_level_matrix(self, level):
-        """(indptr, indices, data) of a level of the multigrid hierarchy, copied to the host (development accessor: tests)"""
+        """(indptr, indices, data) of a level of the multigrid hierarchy, copied to the host (development accessor: tests); on a
+        batched handle data has shape (n_rhs, nnz), row r the values of system r"""
         info = self.mg_levels()[level]
         ip, ix = np.empty(info["rows"] + 1, np.int32), np.empty(info["nnz"], np.int32)
-        da = np.empty(info["nnz"], self.dtype)
+        da = np.empty((self.n_rhs, info["nnz"]) if self.batched else info["nnz"], self.dtype)
         check(self._lib.cgamd_solver_mg_level_matrix(self.handle, int(level), ptr(ip), ptr(ix), ptr(da)))
         return ip, ix, da
 
@@ -1022,7 +1044,7 @@ def solve_subdomains(ctx, P0, residuals, n_iterations, dtype=np.csingle, solver=
     one, whose values are then reloaded from the list) to keep the allocations and the pattern resident across the outer GMRES
     iterations -- the reference re-uploads everything on every call (clcg.c:202-211).
     preconditioner (a list of matrices only): one M per sub-domain, as Solver.set_preconditioner takes it on a batched handle --
-    "jacobi", ("line", stride), n_my * size diagonal entries or a list of diagonal matrices.  It is set before the solve and removed
+    "jacobi", ("line", stride), ("multigrid", dims[, opts]), n_my * size diagonal entries or a list of diagonal matrices.  It is set before the solve and removed
     after it, also on the caller's `solver`.  ValueError for a shared matrix or a solver that is not batched.
     tol (a scalar or one value per sub-domain): every sub-domain stops on its own, on the device, in the first iteration whose
     sqrt(|r.r|) is below its tolerance -- the reference's `CG(P[0], z[p].ravel(), tol=CGtol, maxit=CGMaxIT)` per sub-domain

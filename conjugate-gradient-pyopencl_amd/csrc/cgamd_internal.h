@@ -611,9 +611,10 @@ int tri_build_from_matrix(hipStream_t st, int dt, int nu, int n, int route, cons
 // does in every system); errors name the system and the row.  A constant number of launches and synchronisations whatever nsys
 int tri_build_from_matrix_batched(hipStream_t st, int dt, int nu, int n, int nsys, long long nnz, const std::string &who, int stride,
                                   const void *vals, const int *ptr, const int *cols, TriBuilt *out);
-// m_r[i] = 1 / A_r[i][i] at m + r * pitch (m: nsys * pitch device values of the caller)
+// m_r[i] = 1 / A_r[i][i] at m + r * pitch (m: nsys * pitch device values of the caller); level >= 0: the matrices are a level of a
+// multigrid hierarchy and the error names "system R level L row I"
 int jacobi_build_from_matrix_batched(hipStream_t st, int dt, int nu, int nsys, long long nnz, const std::string &who, const void *vals,
-                                     const int *ptr, const int *cols, void *m, long long pitch);
+                                     const int *ptr, const int *cols, void *m, long long pitch, int level = -1);
 // m[i] = 1 / A[i][i] (m: nu device values of the caller); CGAMD_ERR_INVALID names the smallest bad row
 int jacobi_build_from_matrix(hipStream_t st, int dt, int nu, const std::string &who, const void *vals, const int *ptr, const int *cols,
                              void *m);
@@ -640,6 +641,18 @@ int launch_mg_restrict(int dtype, const MgGrid &g, int nc, long long ldf, long l
 // x += omega P e on the nf rows of the fine grid
 int launch_mg_prolong(int dtype, const MgGrid &g, int nf, long long ldf, long long ldc, int nrhs, const void *e, void *x, double omega,
                       hipStream_t st);
+// ---- the per-system forms for nsys systems on one pattern (multigrid_batched.hip): values of system r at vals + r * nnz, dinv at
+// dinv + r * ld, the Chebyshev coefficients of a step as device arrays of nsys values of the real type.  The prolongation is shared
+// the coarse columns once and every system's values (fine at vals + r * nnzf, coarse at valsc + r * nnzc), by the rules of launch_mg_fill
+int launch_mg_fill_batched(int dtype, const MgGrid &g, int nc, int nsys, long long nnzf, long long nnzc, const void *vals, const int *ptr,
+                           const int *cols, const int *ptrc, int *colsc, void *valsc, hipStream_t st);
+// out[r] (nsys words preset to 0) <- the bits of max_i |dinv_r[i]| sum_j |a_r[i][j]| (double)
+int launch_mg_gershgorin_batched(int dtype, int n, int nsys, long long nnz, long long pitch, const void *vals, const int *ptr,
+                                 const void *dinv, unsigned long long *out, hipStream_t st);
+int launch_mg_cheb_batched(int dtype, int mode, int n, long long ld, int nsys, const void *dinv, const void *b, const void *w, void *d,
+                           void *x, const void *c0, const void *c1, bool store_d, hipStream_t st);
+int launch_mg_restrict_batched(int dtype, const MgGrid &g, int nc, long long ldf, long long ldc, int nsys, const void *b, const void *w,
+                               void *bc, const void *dinvc, void *xc, void *dc, const void *c1, bool store_d, hipStream_t st);
 // The hierarchy of one handle.  Level 0 borrows the handle's matrix and the plan of its SpMV (codes included: build again whenever
 // they change); the coarse levels own theirs.  nu = the caller's rows, n = with the padding rows (z = 0 there)
 // ---- algebraic aggregates (amg.hip): handshake matching from the matrix, then the same Galerkin sums and V-cycle through stored maps
@@ -674,8 +687,9 @@ int launch_amg_prolong(int dtype, int nf, const int *agg, long long ldf, long lo
 struct MgHierarchy;
 // algebraic: aggregates by `passes` passes of matching at strength `theta` (cgamd_solver_set_preconditioner_amg), nx, ny, nz unused
 struct MgParams { int nx = 1, ny = 1, nz = 1, smooth_steps = 1, min_rows = 512; double omega = 1.6; bool algebraic = false; int passes = 3; double theta = 0.25; };
-int mg_build(hipStream_t st, int dt, int nu, int n, int nrhs, const SpmvPlan &plan0, long long nnz, const void *vals, const int *ptr,
-             const int *cols, const MgParams &p, const std::string &who, MgHierarchy **out);
+// nsys > 0 (a batched handle, nrhs == nsys): one hierarchy per system on shared aggregates and patterns, vals = nsys * nnz values
+int mg_build(hipStream_t st, int dt, int nu, int n, int nrhs, int nsys, const SpmvPlan &plan0, long long nnz, const void *vals,
+             const int *ptr, const int *cols, const MgParams &p, const std::string &who, MgHierarchy **out);
 void mg_free(MgHierarchy *h);
 // z = M^-1 r: nrhs vectors of n rows at stride n each, the padding rows of r zero; a linear chain of launches on st
 int mg_vcycle(const MgHierarchy *h, const void *r, void *z, hipStream_t st);
@@ -685,11 +699,15 @@ MgCost mg_cost(const MgHierarchy *h);
 int mg_levels(const MgHierarchy *h);
 // info: rows, nnz, nx, ny, nz, the bits of the double lmax
 int mg_level_info(const MgHierarchy *h, int level, long long info[6]);
+// lmax[r] of the level for r < count (count <= the systems of a batched hierarchy, else 1)
+int mg_level_bounds(const MgHierarchy *h, int level, double *lmax, int count);
+// (a batched hierarchy: vals takes nsys * nnz values, system-major)
 int mg_level_matrix(const MgHierarchy *h, int level, int *ptr, int *cols, void *vals, hipStream_t st);
 // the map level -> level + 1 to the host (rows of the level ints; the box map of a grid hierarchy), *n_coarse = rows of level + 1
 int mg_aggregates(const MgHierarchy *h, int level, int *agg_host, int *n_coarse, hipStream_t st);
 // which: 0 five ints (n, nu, ld, steps, algebraic), 1 dinv (n values), 2 / 3 c0 / c1 (steps doubles), 4 the member lists (kAmgWidth
-// ints per row of level + 1); *count is set even when cap_values is too small.  Synchronises
+// ints per row of level + 1); *count is set even when cap_values is too small.  Synchronises.  A batched hierarchy: dinv is nsys * ld
+// values (system r at r * ld), c0 / c1 steps * nsys doubles indexed (step, system)
 int mg_level_state(const MgHierarchy *h, int level, int which, void *out_host, long long cap_values, long long *count, hipStream_t st);
 // w = A_level x as the cycle launches it (the level's plan and leading dimension, the hierarchy's nrhs); synchronises
 int mg_level_spmv(const MgHierarchy *h, int level, const void *x, void *w, hipStream_t st);

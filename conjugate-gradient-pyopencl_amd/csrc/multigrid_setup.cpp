@@ -3,6 +3,9 @@
 // The host reads back single words only: the coarse non-zero count, the error words and the Gershgorin bound of every level.
 // The algebraic entry (cgamd_solver_set_preconditioner_amg; kernels in amg.hip) builds the same hierarchy with aggregates matched
 // from the matrix: its levels carry a stored map and member lists, and the host also reads one word per matching round.
+// The batched entry (cgamd_solver_set_preconditioner_batched_multigrid; kernels in multigrid_batched.hip) builds one hierarchy per
+// system of a batched handle in the same MgHierarchy (nsys > 0): aggregates, patterns and level vectors shared, values, dinv and
+// smoother coefficients per system; the host then reads nsys bound words per level.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -22,16 +25,23 @@ struct MgLevel {
     const void *vals = nullptr;
     const int *ptr = nullptr, *cols = nullptr;
     SpmvPlan plan;
-    void *dinv = nullptr;
-    double lmax = 0.;
+    void *dinv = nullptr;       // a batched hierarchy: nsys arrays, system r at r * ld
+    double lmax = 0.;           // (a batched hierarchy: the largest of lmaxs)
     void *x = nullptr, *b = nullptr, *w = nullptr, *d = nullptr;      // level 0: x and b are the caller's z and r
     int steps = 1;
-    std::vector<double> c0, c1; // Chebyshev coefficients of step k (c0[0] unused)
+    std::vector<double> c0, c1; // Chebyshev coefficients of step k (c0[0] unused); a batched hierarchy: of (step k, system r) at k * nsys + r
+    // a batched hierarchy: the bound of every system, and the coefficients rounded to the real type on the device: c0 of step k at
+    // coef + 2 k nsys, c1 at coef + (2 k + 1) nsys, nsys values each
+    std::vector<double> lmaxs;
+    void *coef = nullptr;
+    const void *coef0(int k, int nsys, size_t rs) const { return static_cast<const char *>(coef) + (size_t)2 * k * nsys * rs; }
+    const void *coef1(int k, int nsys, size_t rs) const { return static_cast<const char *>(coef) + ((size_t)2 * k + 1) * nsys * rs; }
 };
 }  // namespace
 
 struct MgHierarchy {
     int dtype = 0, nrhs = 1;
+    int nsys = 0;               // > 0: a batched handle's hierarchy (nrhs == nsys), one matrix, dinv and smoother per system on every level
     MgParams p;
     std::vector<MgLevel> lv;
     std::vector<void *> owned;
@@ -67,7 +77,9 @@ static void cheb_coefficients(double lmax, double kappa, int steps, std::vector<
 }
 
 // dinv and the Gershgorin bound of a level whose matrix is in place
+static int level_diagonal_batched(MgHierarchy *h, MgLevel &L, int level, const std::string &who, hipStream_t st);
 static int level_diagonal(MgHierarchy *h, MgLevel &L, int level, unsigned long long *word, const std::string &who, hipStream_t st) {
+    if (h->nsys) return level_diagonal_batched(h, L, level, who, st);
     const size_t vs = dtype_size(h->dtype);
     if (int rc = h->get(&L.dinv, (size_t)L.n * vs, "dinv")) return rc;
     CG_HIP(hipMemsetAsync(L.dinv, 0, (size_t)L.n * vs, st));
@@ -81,6 +93,39 @@ static int level_diagonal(MgHierarchy *h, MgLevel &L, int level, unsigned long l
     if (!std::isfinite(L.lmax) || !(L.lmax > 0.))
         return fail(CGAMD_ERR_INVALID, who + ": level " + std::to_string(level) + ": the Gershgorin bound of D^-1 A is not a positive finite number");
     return CGAMD_OK;
+}
+
+// the same for every system of a batched hierarchy: one launch each for the diagonals and the bounds, one word per system read back
+static int level_diagonal_batched(MgHierarchy *h, MgLevel &L, int level, const std::string &who, hipStream_t st) {
+    const size_t vs = dtype_size(h->dtype), ns = (size_t)h->nsys;
+    void *bounds = nullptr;
+    if (int rc = h->get(&L.dinv, (size_t)L.ld * ns * vs, "dinv")) return rc;
+    if (int rc = h->get(&bounds, ns * 8, "bound words")) return rc;
+    CG_HIP(hipMemsetAsync(L.dinv, 0, (size_t)L.ld * ns * vs, st));
+    if (int rc = jacobi_build_from_matrix_batched(st, h->dtype, L.nu, h->nsys, L.nnz, who, L.vals, L.ptr, L.cols, L.dinv, L.ld, level)) return rc;
+    CG_HIP(hipMemsetAsync(bounds, 0, ns * 8, st));
+    if (int rc = launch_mg_gershgorin_batched(h->dtype, L.nu, h->nsys, L.nnz, L.ld, L.vals, L.ptr, L.dinv,
+                                              static_cast<unsigned long long *>(bounds), st)) return rc;
+    L.lmaxs.assign(ns, 0.);
+    CG_HIP(hipMemcpyAsync(L.lmaxs.data(), bounds, ns * 8, hipMemcpyDeviceToHost, st));
+    CG_HIP(hipStreamSynchronize(st));
+    L.lmax = 0.;
+    for (size_t r = 0; r < ns; ++r) {
+        if (!std::isfinite(L.lmaxs[r]) || !(L.lmaxs[r] > 0.))
+            return fail(CGAMD_ERR_INVALID, who + ": system " + std::to_string(r) + " level " + std::to_string(level) +
+                                               ": the Gershgorin bound of D^-1 A is not a positive finite number");
+        L.lmax = std::max(L.lmax, L.lmaxs[r]);
+    }
+    return CGAMD_OK;
+}
+
+// the plan of a coarse level's batched product: what a batched handle's own plan holds (one d.q partial slot per 256-row block, the
+// cache policy priced on all value arrays)
+static void batched_level_plan(SpmvPlan *plan, int dt, int nsys, int n, long long nnz) {
+    plan->n_partials = plan->row_blocks;
+    const size_t V = dtype_size(dt), MB = (size_t)1 << 20;
+    const size_t matrix_bytes = (size_t)nnz * (V * (size_t)nsys + 4) + ((size_t)n + 1) * 4;
+    plan->nt = tune().spmv_nt >= 0 ? (tune().spmv_nt != 0) : (matrix_bytes > 256 * MB);
 }
 
 namespace {
@@ -203,14 +248,43 @@ static int amg_coarsen(MgHierarchy *h, unsigned long long *word, int *flag, cons
     return CGAMD_OK;
 }
 
-int mg_build(hipStream_t st, int dt, int nu, int n, int nrhs, const SpmvPlan &plan0, long long nnz, const void *vals, const int *ptr,
-             const int *cols, const MgParams &p, const std::string &who, MgHierarchy **out) {
+// the coefficients of every system of a level, in double from its own bound, and their table on the device, rounded to the real type
+static int batched_coefficients(MgHierarchy *h, MgLevel &L, double kappa, hipStream_t st) {
+    const size_t ns = (size_t)h->nsys, steps = (size_t)L.steps;
+    const bool dbl = h->dtype == CGAMD_F64 || h->dtype == CGAMD_C128;
+    const size_t rs = dbl ? 8 : 4;
+    L.c0.assign(steps * ns, 0.);
+    L.c1.assign(steps * ns, 0.);
+    std::vector<double> a, b;
+    for (size_t r = 0; r < ns; ++r) {
+        cheb_coefficients(L.lmaxs[r], kappa, L.steps, &a, &b);
+        for (size_t k = 0; k < steps; ++k) { L.c0[k * ns + r] = a[k]; L.c1[k * ns + r] = b[k]; }
+    }
+    std::vector<double> td(2 * steps * ns);
+    std::vector<float> tf(dbl ? 0 : 2 * steps * ns);
+    for (size_t k = 0; k < steps; ++k)
+        for (size_t r = 0; r < ns; ++r) {
+            td[2 * k * ns + r] = L.c0[k * ns + r];
+            td[(2 * k + 1) * ns + r] = L.c1[k * ns + r];
+        }
+    for (size_t i = 0; i < tf.size(); ++i) tf[i] = (float)td[i];
+    if (int rc = h->get(&L.coef, 2 * steps * ns * rs, "smoother coefficients")) return rc;
+    CG_HIP(hipMemcpyAsync(L.coef, dbl ? static_cast<const void *>(td.data()) : static_cast<const void *>(tf.data()), 2 * steps * ns * rs,
+                          hipMemcpyHostToDevice, st));
+    CG_HIP(hipStreamSynchronize(st));       // (the host table goes out of scope)
+    return CGAMD_OK;
+}
+
+int mg_build(hipStream_t st, int dt, int nu, int n, int nrhs, int nsys, const SpmvPlan &plan0, long long nnz, const void *vals,
+             const int *ptr, const int *cols, const MgParams &p, const std::string &who, MgHierarchy **out) {
     *out = nullptr;
     const size_t vs = dtype_size(dt);
     const int E = (int)(16 / vs);
     MgHierarchy *h = new MgHierarchy;
     struct Guard { MgHierarchy *h; ~Guard() { delete h; } } guard{h};
-    h->dtype = dt; h->nrhs = nrhs; h->p = p;
+    h->dtype = dt; h->nrhs = nrhs; h->nsys = nsys; h->p = p;
+    if (nsys && (p.algebraic || nrhs != nsys)) return fail(CGAMD_ERR_STATE, who + ": a batched hierarchy is a grid hierarchy with one right-hand side per system");
+    const size_t nmat = nsys ? (size_t)nsys : 1;      // value arrays of a level
     void *words = nullptr;      // [0] error word / Gershgorin bits, [1] scan overflow flag, [2..] scratch of compute_spmv_plan
     if (int rc = h->get(&words, 64, "setup words")) return rc;
     unsigned long long *word = static_cast<unsigned long long *>(words);
@@ -254,14 +328,18 @@ int mg_build(hipStream_t st, int dt, int nu, int n, int nrhs, const SpmvPlan &pl
         C.nnz = back[1];
         // (64 entries of zeroed padding behind both arrays, as the handle's own matrix carries for the row-block kernels)
         if (int rc = h->get(&colsc, ((size_t)C.nnz + 64) * 4, "columns")) return rc;
-        if (int rc = h->get(&valsc, ((size_t)C.nnz + 64) * vs, "values")) return rc;
+        if (int rc = h->get(&valsc, ((size_t)C.nnz * nmat + 64) * vs, "values")) return rc;
         CG_HIP(hipMemsetAsync(colsc, 0, ((size_t)C.nnz + 64) * 4, st));
-        CG_HIP(hipMemsetAsync(valsc, 0, ((size_t)C.nnz + 64) * vs, st));
-        if (int rc = launch_mg_fill(dt, g, nc, F.vals, F.ptr, F.cols, static_cast<int *>(ptrc), static_cast<int *>(colsc), valsc, st)) return rc;
+        CG_HIP(hipMemsetAsync(valsc, 0, ((size_t)C.nnz * nmat + 64) * vs, st));
+        if (nsys) {
+            if (int rc = launch_mg_fill_batched(dt, g, nc, nsys, F.nnz, C.nnz, F.vals, F.ptr, F.cols, static_cast<int *>(ptrc),
+                                                static_cast<int *>(colsc), valsc, st)) return rc;
+        } else if (int rc = launch_mg_fill(dt, g, nc, F.vals, F.ptr, F.cols, static_cast<int *>(ptrc), static_cast<int *>(colsc), valsc, st)) return rc;
         C.vals = valsc; C.ptr = static_cast<int *>(ptrc); C.cols = static_cast<int *>(colsc);
         C.plan = make_spmv_plan(nc);
         if (int rc = compute_spmv_plan(C.ptr, C.cols, nc, scratch, st, &C.plan)) return rc;
         finalize_spmv_plan(&C.plan, dt, nrhs, nc, C.nnz, C.vals, C.cols);
+        if (nsys) batched_level_plan(&C.plan, dt, nsys, nc, C.nnz);
         h->lv.push_back(C);
         if (int rc = level_diagonal(h, h->lv.back(), level, word, who, st)) return rc;
     }
@@ -285,7 +363,9 @@ int mg_build(hipStream_t st, int dt, int nu, int n, int nrhs, const SpmvPlan &pl
         MgLevel &L = h->lv[(size_t)l];
         const bool coarsest = l == nl - 1;
         L.steps = coarsest ? kMgCoarsestSteps : p.smooth_steps;
-        cheb_coefficients(L.lmax, coarsest ? kMgKappaCoarsest : kMgKappaSmooth, L.steps, &L.c0, &L.c1);
+        if (nsys) {
+            if (int rc = batched_coefficients(h, L, coarsest ? kMgKappaCoarsest : kMgKappaSmooth, st)) return rc;
+        } else cheb_coefficients(L.lmax, coarsest ? kMgKappaCoarsest : kMgKappaSmooth, L.steps, &L.c0, &L.c1);
         const size_t bytes = (size_t)L.ld * (size_t)nrhs * vs;
         if (int rc = h->get(&L.w, bytes, "w")) return rc;
         CG_HIP(hipMemsetAsync(L.w, 0, bytes, st));
@@ -312,23 +392,29 @@ void mg_free(MgHierarchy *h) { delete h; }
 static int mg_walk(const MgHierarchy *h, const void *r, void *z, hipStream_t st, MgCost *cost) {
     const int dt = h->dtype, nr = h->nrhs, nl = (int)h->lv.size();
     const long long V = (long long)dtype_size(dt);
+    const int ns = h->nsys;
+    const long long nm = ns ? ns : 1;                   // value arrays and dinv arrays of a level: one per system of a batched hierarchy
+    const size_t rs = (dt == CGAMD_F64 || dt == CGAMD_C128) ? 8 : 4;
     auto vec = [&](const MgLevel &L, int passes, int shared) {       // passes over nrhs-wide vectors, shared = over dinv
-        if (cost) { ++cost->launches; cost->bytes += ((long long)passes * nr + shared) * L.n * V; }
+        if (cost) { ++cost->launches; cost->bytes += ((long long)passes * nr + shared * nm) * L.n * V; }
     };
     auto spmv = [&](const MgLevel &L, int l, const void *x, void *w) -> int {
         if (cost) {
             ++cost->launches;
             if (l == 0) ++cost->spmv0;
-            else cost->bytes += L.nnz * (V + 4) + ((long long)L.n + 1) * 4 + 2LL * L.n * V * nr;
+            else cost->bytes += L.nnz * (nm * V + 4) + ((long long)L.n + 1) * 4 + 2LL * L.n * V * nr;
             return CGAMD_OK;
         }
+        if (ns) return launch_spmv_batched(dt, L.plan, L.n, L.nnz, ns, L.vals, L.ptr, L.cols, x, L.ld, w, L.ld, nullptr, nullptr, st);
         return launch_spmv(dt, L.plan, L.n, L.nnz, L.vals, L.ptr, L.cols, x, L.ld, w, L.ld, nr, nullptr, nullptr, st);
     };
     auto later_steps = [&](const MgLevel &L, int l, const void *b, void *x) -> int {       // steps 1 .. steps - 1 of a smoothing
         for (int k = 1; k < L.steps; ++k) {
             if (int rc = spmv(L, l, x, L.w)) return rc;
             vec(L, 7, 1);
-            if (!cost)
+            if (!cost && ns) {
+                if (int rc = launch_mg_cheb_batched(dt, 2, L.n, L.ld, ns, L.dinv, b, L.w, L.d, x, L.coef0(k, ns, rs), L.coef1(k, ns, rs), true, st)) return rc;
+            } else if (!cost)
                 if (int rc = launch_mg_cheb(dt, 2, L.n, L.ld, nr, L.dinv, b, L.w, L.d, x, L.c0[(size_t)k], L.c1[(size_t)k], true, st)) return rc;
         }
         return CGAMD_OK;
@@ -339,15 +425,19 @@ static int mg_walk(const MgHierarchy *h, const void *r, void *z, hipStream_t st,
         void *x = l == 0 ? z : L.x;
         if (l == 0) {       // (the first step of every coarse level rides in the restriction that makes its b)
             vec(L, 2 + (L.steps > 1), 1);
-            if (!cost)
+            if (!cost && ns) {
+                if (int rc = launch_mg_cheb_batched(dt, 0, L.n, L.ld, ns, L.dinv, b, nullptr, L.d, x, nullptr, L.coef1(0, ns, rs), L.steps > 1, st)) return rc;
+            } else if (!cost)
                 if (int rc = launch_mg_cheb(dt, 0, L.n, L.ld, nr, L.dinv, b, nullptr, L.d, x, 0., L.c1[0], L.steps > 1, st)) return rc;
         }
         if (int rc = later_steps(L, l, b, x)) return rc;
         if (l == nl - 1) break;
         const MgLevel &C = h->lv[(size_t)l + 1];
         if (int rc = spmv(L, l, x, L.w)) return rc;
-        if (cost) { ++cost->launches; cost->bytes += 2LL * nr * L.nu * V + ((2LL + (C.steps > 1)) * nr + 1) * C.n * V + (L.mem ? 4LL * kAmgWidth * C.n : 0); }
-        else if (L.mem) {
+        if (cost) { ++cost->launches; cost->bytes += 2LL * nr * L.nu * V + ((2LL + (C.steps > 1)) * nr + nm) * C.n * V + (L.mem ? 4LL * kAmgWidth * C.n : 0); }
+        else if (ns) {
+            if (int rc = launch_mg_restrict_batched(dt, L.grid, C.nu, L.ld, C.ld, ns, b, L.w, C.b, C.dinv, C.x, C.d, C.coef1(0, ns, rs), C.steps > 1, st)) return rc;
+        } else if (L.mem) {
             if (int rc = launch_amg_restrict(dt, C.nu, L.mem, L.ld, C.ld, nr, b, L.w, C.b, C.dinv, C.x, C.d, C.c1[0], C.steps > 1, st)) return rc;
         } else if (int rc = launch_mg_restrict(dt, L.grid, C.nu, L.ld, C.ld, nr, b, L.w, C.b, C.dinv, C.x, C.d, C.c1[0], C.steps > 1, st)) return rc;
     }
@@ -361,7 +451,9 @@ static int mg_walk(const MgHierarchy *h, const void *r, void *z, hipStream_t st,
         } else if (int rc = launch_mg_prolong(dt, L.grid, L.nu, L.ld, C.ld, nr, C.x, x, h->p.omega, st)) return rc;
         if (int rc = spmv(L, l, x, L.w)) return rc;
         vec(L, 4 + (L.steps > 1), 1);
-        if (!cost)
+        if (!cost && ns) {
+            if (int rc = launch_mg_cheb_batched(dt, 1, L.n, L.ld, ns, L.dinv, b, L.w, L.d, x, nullptr, L.coef1(0, ns, rs), L.steps > 1, st)) return rc;
+        } else if (!cost)
             if (int rc = launch_mg_cheb(dt, 1, L.n, L.ld, nr, L.dinv, b, L.w, L.d, x, 0., L.c1[0], L.steps > 1, st)) return rc;
         if (int rc = later_steps(L, l, b, x)) return rc;
     }
@@ -383,12 +475,19 @@ int mg_level_info(const MgHierarchy *h, int level, long long info[6]) {
     std::memcpy(&info[5], &L.lmax, 8);
     return CGAMD_OK;
 }
+int mg_level_bounds(const MgHierarchy *h, int level, double *lmax, int count) {
+    if (level < 0 || level >= (int)h->lv.size()) return fail(CGAMD_ERR_INVALID, "mg_level_bounds: no such level");
+    if (!lmax || count < 0 || count > (h->nsys ? h->nsys : 1)) return fail(CGAMD_ERR_INVALID, "mg_level_bounds: count is 0 ... the systems of the hierarchy (1 on a single-system handle)");
+    const MgLevel &L = h->lv[(size_t)level];
+    for (int r = 0; r < count; ++r) lmax[r] = h->nsys ? L.lmaxs[(size_t)r] : L.lmax;
+    return CGAMD_OK;
+}
 int mg_level_matrix(const MgHierarchy *h, int level, int *ptr, int *cols, void *vals, hipStream_t st) {
     if (level < 0 || level >= (int)h->lv.size()) return fail(CGAMD_ERR_INVALID, "mg_level_matrix: no such level");
     const MgLevel &L = h->lv[(size_t)level];
     if (ptr) CG_HIP(hipMemcpyAsync(ptr, L.ptr, ((size_t)L.nu + 1) * 4, hipMemcpyDeviceToHost, st));
     if (cols) CG_HIP(hipMemcpyAsync(cols, L.cols, (size_t)L.nnz * 4, hipMemcpyDeviceToHost, st));
-    if (vals) CG_HIP(hipMemcpyAsync(vals, L.vals, (size_t)L.nnz * dtype_size(h->dtype), hipMemcpyDeviceToHost, st));
+    if (vals) CG_HIP(hipMemcpyAsync(vals, L.vals, (size_t)L.nnz * (h->nsys ? (size_t)h->nsys : 1) * dtype_size(h->dtype), hipMemcpyDeviceToHost, st));
     CG_HIP(hipStreamSynchronize(st));
     return CGAMD_OK;
 }
@@ -420,9 +519,9 @@ int mg_level_state(const MgHierarchy *h, int level, int which, void *out_host, l
     long long values = 0;
     switch (which) {
     case 0: host = five; each = sizeof(int); values = 5; break;
-    case 1: dev = L.dinv; each = dtype_size(h->dtype); values = L.n; break;
-    case 2: host = L.c0.data(); each = sizeof(double); values = L.steps; break;
-    case 3: host = L.c1.data(); each = sizeof(double); values = L.steps; break;
+    case 1: dev = L.dinv; each = dtype_size(h->dtype); values = h->nsys ? L.ld * h->nsys : L.n; break;
+    case 2: host = L.c0.data(); each = sizeof(double); values = (long long)L.c0.size(); break;
+    case 3: host = L.c1.data(); each = sizeof(double); values = (long long)L.c1.size(); break;
     case 4:
         if (!L.mem || level + 1 >= (int)h->lv.size())
             return fail(CGAMD_ERR_INVALID, "mg_level_state: the level has no member lists (a grid hierarchy, or the coarsest level)");
@@ -440,7 +539,9 @@ int mg_level_state(const MgHierarchy *h, int level, int which, void *out_host, l
 int mg_level_spmv(const MgHierarchy *h, int level, const void *x, void *w, hipStream_t st) {
     if (level < 0 || level >= (int)h->lv.size()) return fail(CGAMD_ERR_INVALID, "mg_level_spmv: no such level");
     const MgLevel &L = h->lv[(size_t)level];
-    if (int rc = launch_spmv(h->dtype, L.plan, L.n, L.nnz, L.vals, L.ptr, L.cols, x, L.ld, w, L.ld, h->nrhs, nullptr, nullptr, st)) return rc;
+    if (h->nsys) {
+        if (int rc = launch_spmv_batched(h->dtype, L.plan, L.n, L.nnz, h->nsys, L.vals, L.ptr, L.cols, x, L.ld, w, L.ld, nullptr, nullptr, st)) return rc;
+    } else if (int rc = launch_spmv(h->dtype, L.plan, L.n, L.nnz, L.vals, L.ptr, L.cols, x, L.ld, w, L.ld, h->nrhs, nullptr, nullptr, st)) return rc;
     CG_HIP(hipStreamSynchronize(st));
     return CGAMD_OK;
 }

@@ -383,7 +383,7 @@ int tri_build_from_matrix_batched(hipStream_t st, int dt, int nu, int n, int nsy
 }
 
 int jacobi_build_from_matrix_batched(hipStream_t st, int dt, int nu, int nsys, long long nnz, const std::string &who, const void *vals,
-                                     const int *ptr, const int *cols, void *m, long long pitch) {
+                                     const int *ptr, const int *cols, void *m, long long pitch, int level) {
     DevScratch tmp;
     void *err = nullptr;
     int rc = tmp.get(&err, 8, "Jacobi preconditioner: error word");
@@ -394,7 +394,10 @@ int jacobi_build_from_matrix_batched(hipStream_t st, int dt, int nu, int nsys, l
     CG_HIP(hipMemcpyAsync(&err_h, err, 8, hipMemcpyDeviceToHost, st));
     CG_HIP(hipStreamSynchronize(st));
     if (err_h != ~0ull)
-        return fail(CGAMD_ERR_INVALID, who + ": zero, missing or non-finite diagonal in " + system_row(err_h >> 32, err_h & 0xffffffffull));
+        return fail(CGAMD_ERR_INVALID, who + ": zero, missing or non-finite diagonal in " +
+                                           (level < 0 ? system_row(err_h >> 32, err_h & 0xffffffffull)
+                                                      : "system " + std::to_string(err_h >> 32) + " level " + std::to_string(level) + " row " +
+                                                            std::to_string(err_h & 0xffffffffull)));
     return CGAMD_OK;
 }
 

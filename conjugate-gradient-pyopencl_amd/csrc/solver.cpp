@@ -69,7 +69,8 @@ struct cgamd_solver {
     // matrix) and, for one built from the matrix, what cgamd_solver_reload_matrix builds again: kind 1 = Jacobi, 2 = the lines at
     // pre_stride
     int pre_source = 0, pre_kind = 0, pre_stride = 0;
-    // aggregation multigrid preconditioner (cgamd_solver_set_preconditioner_multigrid; multigrid_setup.cpp): the hierarchy and what it
+    // aggregation multigrid preconditioner (cgamd_solver_set_preconditioner_multigrid, on a batched handle _batched_multigrid: one
+    // hierarchy per system inside the same MgHierarchy; multigrid_setup.cpp): the hierarchy and what it
     // was built with (pre_kind 3: refresh_values / reload_matrix build it again).  z lives in q's storage, like the line sweeps';
     // r.r partials in part_rr, r.z partials in part_rz, vgrid of each
     MgHierarchy *mg = nullptr;
@@ -806,6 +807,11 @@ static int batched_line_from_matrix(cgamd_solver *s, const std::string &who, int
 static int batched_jacobi_from_matrix(cgamd_solver *s, const std::string &who);
 static int multigrid_from_matrix(cgamd_solver *s, const std::string &who, const MgParams &p);
 static int step_not_capturing(cgamd_solver *s, const char *who);
+// the per-system preconditioner a batched handle built from its matrices, built again from the values as they are now
+static int rebuild_from_matrix_batched(cgamd_solver *s, const std::string &who) {
+    if (s->pre_kind == 3) return multigrid_from_matrix(s, who, s->mg_params);
+    return s->pre_kind == 1 ? batched_jacobi_from_matrix(s, who) : batched_line_from_matrix(s, who, s->pre_stride);
+}
 // the preconditioner a non-batched handle built from its matrix, built again from the matrix as it is now
 static int rebuild_from_matrix(cgamd_solver *s, const std::string &who) {
     if (s->pre_kind == 3) return multigrid_from_matrix(s, who, s->mg_params);
@@ -846,7 +852,7 @@ int cgamd_solver_reload_matrix(cgamd_solver *s, const void *aValues, const int *
     if (s->nsys) {                                  // no resident loop, no codes; a per-system preconditioner built from the matrices follows them
         CG_HIP(hipStreamSynchronize(st));
         if (s->pre_source >= 2) {
-            const int rc = s->pre_kind == 1 ? batched_jacobi_from_matrix(s, "reload_matrix") : batched_line_from_matrix(s, "reload_matrix", s->pre_stride);
+            const int rc = rebuild_from_matrix_batched(s, "reload_matrix");
             if (rc) {                               // the matrices are loaded; the old factors belong to the old ones
                 const std::string why = cgamd_last_error();
                 (void)diag_impl(s, nullptr, 0);
@@ -942,7 +948,7 @@ int cgamd_solver_refresh_values(cgamd_solver *s, const void *aValues, int on_dev
     }
     if (s->pre_source >= 2) {               // a preconditioner built from the matrix follows it (one from the caller's arrays is kept)
         int rc;
-        if (s->nsys) rc = s->pre_kind == 1 ? batched_jacobi_from_matrix(s, "refresh_values") : batched_line_from_matrix(s, "refresh_values", s->pre_stride);
+        if (s->nsys) rc = rebuild_from_matrix_batched(s, "refresh_values");
         else rc = rebuild_from_matrix(s, "refresh_values");
         if (rc) {                           // the values are in force; the old factors belong to the old ones
             const std::string why = cgamd_last_error();
@@ -1236,7 +1242,7 @@ static int multigrid_from_matrix(cgamd_solver *s, const std::string &who, const 
     hipStream_t st = s->ctx->stream;
     CG_HIP(hipStreamSynchronize(st));
     MgHierarchy *h = nullptr;
-    int rc = mg_build(st, s->dtype, s->n_user, s->n, s->nrhs, s->plan, s->nnz, s->vals, s->ptr, s->cols, p, who, &h);
+    int rc = mg_build(st, s->dtype, s->n_user, s->n, s->nrhs, s->nsys, s->plan, s->nnz, s->vals, s->ptr, s->cols, p, who, &h);
     if (rc) return rc;
     const size_t vs = dtype_size(s->dtype);
     if (!s->part_rz) rc = dmalloc(&s->part_rz, acc_size(s->dtype) * s->part_rr_cap * s->nrhs, "partials_rz");
@@ -1311,6 +1317,10 @@ int cgamd_solver_mg_level(cgamd_solver *s, int level, long long info[6]) {
     if (int rc = mg_wanted(s, "mg_level")) return rc;
     if (!info) return fail(CGAMD_ERR_INVALID, "mg_level: info is NULL");
     return mg_level_info(s->mg, level, info);
+}
+int cgamd_solver_mg_level_bounds(cgamd_solver *s, int level, double *lmax, int count) {
+    if (int rc = mg_wanted(s, "mg_level_bounds")) return rc;
+    return mg_level_bounds(s->mg, level, lmax, count);
 }
 int cgamd_solver_mg_level_matrix(cgamd_solver *s, int level, int *ptr, int *cols, void *vals) {
     if (int rc = mg_wanted(s, "mg_level_matrix")) return rc;
@@ -1413,6 +1423,31 @@ int cgamd_solver_set_preconditioner_batched_line(cgamd_solver *s, int stride) {
     if (stride < 1 || stride >= s->n_user) return fail(CGAMD_ERR_INVALID, "set_preconditioner_batched_line: stride must be in [1, size - 1]");
     TuneScope ts(&s->tune);
     return batched_line_from_matrix(s, "set_preconditioner_batched_line", stride);
+}
+
+// one hierarchy per system on shared box aggregates and patterns (multigrid_setup.cpp, multigrid_batched.hip); everything downstream
+// of mg_build is the single-system entry's: s->mg serves the loops, the accessors and the byte models of both
+int cgamd_solver_set_preconditioner_batched_multigrid(cgamd_solver *s, int nx, int ny, int nz, int smooth_steps, double over_correction,
+                                                      int min_rows) {
+    const std::string who = "set_preconditioner_batched_multigrid";
+    if (!s) return fail(CGAMD_ERR_INVALID, who + ": solver is NULL");
+    if (!s->nsys) return not_batched(who.c_str(), "cgamd_solver_set_preconditioner_multigrid");
+    if (s->herm) return herm_refuses(who.c_str(), "which the V-cycle does not serve");
+    if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, who + ": CGAMD_UNFUSED replays the reference's kernel sequence");
+    if (nx < 1 || ny < 1 || nz < 1) return fail(CGAMD_ERR_INVALID, who + ": every grid dimension must be at least 1");
+    const long long plane = (long long)nx * ny;
+    if (plane > 2147483647LL || plane * nz != (long long)s->n_user)
+        return fail(CGAMD_ERR_INVALID, who + ": nx * ny * nz must equal the size of the system");
+    if (smooth_steps < 0 || smooth_steps > 4) return fail(CGAMD_ERR_INVALID, who + ": smooth_steps must be in 0 ... 4 (0 = the default, 1)");
+    if (!std::isfinite(over_correction) || over_correction < 0.) return fail(CGAMD_ERR_INVALID, who + ": over_correction must be finite and not negative (0 = the default, 1.6)");
+    if (min_rows < 0) return fail(CGAMD_ERR_INVALID, who + ": min_rows must not be negative (0 = the default, 512)");
+    MgParams p;
+    p.nx = nx; p.ny = ny; p.nz = nz;
+    if (smooth_steps) p.smooth_steps = smooth_steps;
+    if (over_correction != 0.) p.omega = over_correction;
+    if (min_rows) p.min_rows = min_rows;
+    TuneScope ts(&s->tune);
+    return multigrid_from_matrix(s, who, p);
 }
 
 int cgamd_solver_preconditioner_source(cgamd_solver *s) { return s ? s->pre_source : 0; }
@@ -1975,7 +2010,7 @@ static long long tri_passes(const cgamd_solver *s) {
 long long cgamd_solver_iter_bytes(cgamd_solver *s, int fused) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
-    if (s->mg) return s->nnz * (V + 4) + ((long long)s->n_user + 1) * 4 + mg_bytes(s, cgamd_solver_spmv_bytes(s));
+    if (s->mg) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + mg_bytes(s, cgamd_solver_spmv_bytes(s));
     if (s->tri_on) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + tri_passes(s) * s->n_user * V;
     // the conjugated recurrence: the launched loop's 10 passes (12 with a diagonal M) and conj(d), written by the d step and read by the SpMV's dot
     if (s->herm) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + (s->mdiag ? 14LL : 12LL) * s->n_user * V * s->nrhs;

@@ -178,8 +178,8 @@ int cgamd_solver_destroy(cgamd_solver *s);
 /* new values / pattern of the SAME size (size, nnz, nRHS, dtype) into a handle that owns its matrix (created from host
  * arrays): keeps allocations, stream and -- when the row pointers are unchanged -- the plan and the captured graphs.
  * The next call must be cgamd_solver_set_rhs.  A preconditioner from the caller's arrays is kept; one built from the matrix
- * (cgamd_solver_set_preconditioner_line / _jacobi; on a batched handle _batched_line / _batched_jacobi) is built again from the new
- * matrix. */
+ * (cgamd_solver_set_preconditioner_line / _jacobi; on a batched handle _batched_line / _batched_jacobi / _batched_multigrid) is built
+ * again from the new matrix. */
 int cgamd_solver_reload_matrix(cgamd_solver *s, const void *aValues, const int *aPointers, const int *aCols);
 /* New VALUES on the SAME pattern.  Everything the handle made from the values follows them (the value, joint and row-pattern codes
  * of the SpMV, a preconditioner built from the matrix); nothing made from the pattern alone is touched: no CSR validation, no plan,
@@ -200,7 +200,7 @@ int cgamd_solver_reload_matrix(cgamd_solver *s, const void *aValues, const int *
  * the all-ones NaN pattern) run the form that reads aValues, and a handle that had no value codes gains them when the new values
  * qualify.  Results are, bit for bit, those of a fresh handle created from the new values.
  * Preconditioners: one from the caller's arrays is kept; one built from the matrix (cgamd_solver_set_preconditioner_jacobi / _line,
- * _batched_jacobi / _batched_line) is built again from the new values, same kind and stride.  If that fails the values are in force,
+ * _batched_jacobi / _batched_line / _batched_multigrid) is built again from the new values, same kind, stride and arguments.  If that fails the values are in force,
  * the preconditioner is removed and the error naming the row (batched: the system and the row) is returned. */
 int cgamd_solver_refresh_values(cgamd_solver *s, const void *aValues, int on_device);
 /* what the last cgamd_solver_refresh_values did: 0 no refresh yet, or the handle carries no codes of its values (multi-RHS, batched,
@@ -351,7 +351,8 @@ int cgamd_solver_set_preconditioner_line(cgamd_solver *s, int stride);
  * handle unchanged. */
 int cgamd_solver_set_preconditioner_jacobi(cgamd_solver *s);
 /* Preconditioned CG on a BATCHED handle (cgamd_solver_create_batched): one M per system, M_r for right-hand side r.  The three entries
- * are for batched handles only; on any other handle they return CGAMD_ERR_STATE naming the shared-M entry to use instead.
+ * (and cgamd_solver_set_preconditioner_batched_multigrid below) are for batched handles only; on any other handle they return
+ * CGAMD_ERR_STATE naming the shared-M entry to use instead.
  * Everything not said here is the contract of the one-matrix entries above: effective at the next cgamd_solver_set_rhs; history keeps
  * holding r.r; rho = r.z drives alpha and beta per system; cgamd_solver_set_preconditioner_batched(s, NULL, 0) or
  * cgamd_solver_set_preconditioner(s, NULL, 0) removes it and the handle then returns the bits of one that never had a
@@ -432,6 +433,46 @@ int cgamd_solver_mg_level(cgamd_solver *s, int level, long long info[6]);
  * device pointers to nRHS * size values at stride `size`; synchronises. */
 int cgamd_solver_mg_level_matrix(cgamd_solver *s, int level, int *ptr, int *cols, void *vals);
 int cgamd_solver_mg_apply(cgamd_solver *s, const void *r_dev, void *z_dev);
+/* ---- Aggregation multigrid on a BATCHED handle (csrc/multigrid_batched.hip, csrc/multigrid_setup.cpp) ----
+ * One hierarchy PER SYSTEM on a batched handle (cgamd_solver_create_batched): for right-hand side r, z_r is one V-cycle of r_r on the
+ * hierarchy that cgamd_solver_set_preconditioner_multigrid builds on a single-system handle made from A_r with the same arguments.
+ * For batched handles only: any other handle gets CGAMD_ERR_STATE naming cgamd_solver_set_preconditioner_multigrid (which, like
+ * cgamd_solver_set_preconditioner_amg, keeps refusing batched handles; there is no batched algebraic form: aggregates matched from
+ * the values would give every system a pattern of its own).  Everything not said here is the contract of the single-system entry,
+ * restated per system: aggregates, Galerkin sums and their order, dinv, lmax, the smoother, V(l), the defaults (0 = 1 step, 1.6, 512),
+ * the 16 levels, padding rows, the argument rules (CGAMD_ERR_INVALID).
+ *   Shared by the systems: the box aggregates; ptr / cols of every level (the coarse pattern comes from the pattern alone, structural
+ *     zeros kept, so it is the pattern every single-system handle would get); the level vectors, nSystems wide; over_correction.
+ *   Per system: the coarse values, nSystems * nnz_l per level, system r at r * nnz_l (the layout of aValues); dinv, system r at r * ld
+ *     of the level; lmax_r, hence the Chebyshev coefficients of every level -- computed on the host in double from each lmax_r, rounded
+ *     to the real type and kept in a small device array indexed by (step, system).
+ * The setup takes a constant number of launches and host synchronisations per level whatever nSystems is; the host reads the coarse
+ * non-zero count, the error words and nSystems bound words.  The coarse values and bounds have the BITS of the single-system handles'
+ * (the sums have a stated order).  Whether z_r has the bits of the single-system cycle depends on the summation order of the batched
+ * SpMV against the single-system one, which nothing promises.
+ * Takes effect at the next cgamd_solver_set_rhs; history keeps r.r, rho = r.z per system.  Replaces and is replaced by the other
+ * per-system preconditioners; cgamd_solver_set_preconditioner_batched(s, NULL, 0) or cgamd_solver_set_preconditioner(s, NULL, 0)
+ * removes it and the handle then returns the bits of one that never had it.  On failure the handle is unchanged and a preconditioner
+ * set before stays in force with the same bits.  cgamd_solver_preconditioner_source() reports 2.  cgamd_solver_refresh_values and
+ * cgamd_solver_reload_matrix build all hierarchies again from the nSystems * nnz new values; if that fails the preconditioner is
+ * removed and the error returned.
+ * Served: all four value types, any nSystems >= 1, CGAMD_MATRIX_ON_DEVICE, CGAMD_NO_GRAPH, cgamd_solver_iterate_until (the cycle runs
+ * unguarded, as on the single handle).  CGAMD_ERR_STATE, the handle untouched: CGAMD_HERMITIAN on a complex type, CGAMD_UNFUSED.
+ * cgamd_solver_iterate_tol and cgamd_solver_replace_residual keep refusing batched handles.
+ * Errors about diagonals and bounds name "system R level L row I" (bounds: system and level): the smallest failing system, then the
+ * smallest row.  The 64-column error names the level and the row: a property of the pattern, the same for all systems.
+ * Loop: SpMV (batched), cg_alpha, r update, the cycle, r.z, update -- cgamd_solver_loop_launches() = 5 + the cycle's launches by the
+ * single entry's formula: the launch count of ONE system whatever nSystems is.
+ * Byte models (cgamd_solver_iter_bytes / _iter_moved_bytes), V = sizeof(value): the single entry's model with every value array and
+ * dinv counted per system -- matrix nnz (nSystems V + 4) + 4 (size + 1), + 12 size V nSystems + m_0 SpMV_0 + sum over the coarse levels
+ * l of m_l (nnz_l (nSystems V + 4) + 4 (n_l + 1) + 2 n_l V nSystems) + the vector passes of the cycle's kernels, each pass nSystems wide
+ * and every dinv read nSystems n_l V.
+ * cgamd_solver_mg_levels, _mg_level (info[5] = the bits of the LARGEST lmax_r), _mg_aggregates and _mg_apply serve the batched
+ * hierarchy; _mg_level_matrix hands out nSystems * nnz_l values, system-major.
+ * cgamd_solver_mg_level_bounds (a development entry like _mg_level_matrix): lmax_r of the level for r < count, count <= nSystems; it
+ * also serves single-system handles (count <= 1). */
+int cgamd_solver_set_preconditioner_batched_multigrid(cgamd_solver *s, int nx, int ny, int nz, int smooth_steps, double over_correction, int min_rows);
+int cgamd_solver_mg_level_bounds(cgamd_solver *s, int level, double *lmax, int count);
 /* ---- Algebraic aggregation multigrid (csrc/amg.hip, csrc/multigrid_setup.cpp) ----
  * The same V-cycle on a hierarchy whose aggregates are chosen FROM THE MATRIX, on the device: for a matrix that comes without a grid
  * (a Matrix-Market file, a permuted or reordered grid matrix, a mesh or graph Laplacian) and for anisotropic or variable coefficients,
@@ -520,6 +561,8 @@ int cgamd_mg_scan(cgamd_ctx *ctx, int n, int *counts_to_ptr, int *overflow);
  *   algebraic hierarchy; 1 dinv, n values of the handle's type (the padding rows of level 0 are +0); 2 / 3 c0[k] / c1[k], k <
  *   steps, as the doubles the launches are given (they round them to the real type; c0[0] = 0 is never read); 4 the member lists of the
  *   level's aggregates, 8 ints per row of the next level (CGAMD_ERR_INVALID for a grid hierarchy and for the coarsest level).
+ *   The hierarchies of a batched handle: 1 is nSystems * ld values, system r at r * ld; 2 / 3 are steps * nSystems doubles, the
+ *   coefficient of (step k, system r) at k * nSystems + r.
  * cgamd_solver_mg_level_spmv: w = A_level x exactly as the cycle launches it -- the level's own plan, n rows, the level's leading
  *   dimension ld for x and w -- on caller vectors of nRHS * ld values (device pointers).  cgamd_last_spmv_form afterwards reports
  *   what ran on that level.

@@ -17,7 +17,14 @@ cgamd_solver_spmv_moved_bytes against 8 TB/s.
 (cgamd_solver_set_preconditioner_jacobi / _line), same method; (c) and the SpMV part are left out.  The driver starts one child
 process per size, each under its own time limit (--step-timeout), chained: a size that fails or runs out of time ends the run.  The
 lines are appended to --out (profiles/batched/pcg_ab.log: one log for both legs) and are echoed.
-usage: batched_ab.py [--sizes 128,500] [--systems 9] [--iters 400] [--warmup 50] [--reps 7] [--pcg jacobi|line [--stride 1]]"""
+--mg: the multigrid leg (profiles/batched/mg_ab.log).  Per case, solves to 1e-6 ||b_r|| per system through iterate_until, medians of
+--reps solves on the host clock (set_rhs from a device vector, iterate_until, synchronise): ONE batched handle with
+cgamd_solver_set_preconditioner_batched_multigrid against (a) nine single-system multigrid handles one after another and (b) the
+batched Jacobi handle.  Cases: 9 fp64 variable-coefficient 5-point systems (the 2-D form of the tests' variable7: D^(1/2) (Laplacian +
+shift) D^(1/2), seeds 3 + r) at 128^2 and 500^2 rows, and the local_rect shape of the other legs at 16 384 rows in complex64.  Logged
+per form: the iterations of every system, ms per solve (all systems), us per iteration (that time over the largest iteration count)
+and the setup time of the preconditioner.  One child process per case under --step-timeout, chained.
+usage: batched_ab.py [--sizes 128,500] [--systems 9] [--iters 400] [--warmup 50] [--reps 7] [--pcg jacobi|line [--stride 1]] [--mg]"""
 import argparse
 import importlib
 import json
@@ -44,8 +51,31 @@ ap.add_argument("--pcg", default="", choices=("", "jacobi", "line"), help="preco
 ap.add_argument("--stride", type=int, default=1, help="--pcg line: distance of the coupled rows (1: the x-lines of the grid)")
 ap.add_argument("--step-timeout", type=int, default=300, help="--pcg: time limit of one size, in seconds")
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "batched", "pcg_ab.log"))
+ap.add_argument("--mg", action="store_true", help="multigrid leg: batched multigrid PCG against nine single handles and batched Jacobi")
+ap.add_argument("--mg-case", default="", help=argparse.SUPPRESS)
 ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
 args = ap.parse_args()
+MG_OUT = os.path.join(ROOT, "profiles", "batched", "mg_ab.log")
+if args.mg and not args.child:          # the driver: opens no GPU itself
+    lines = [f"# scripts/batched_ab.py --mg --systems {args.systems} --reps {args.reps}"]
+    for case in ("var5:128", "var5:500", "local_rect:128"):
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", "--mg", "--mg-case", case, "--systems", str(args.systems),
+               "--reps", str(args.reps)]
+        try:
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.step_timeout)
+        except subprocess.TimeoutExpired:
+            lines.append(f"# case {case} ran into its time limit of {args.step_timeout} s; stopped here")
+            break
+        lines += [l for l in r.stdout.splitlines() if l.startswith("{")]
+        if r.returncode != 0:
+            lines.append(f"# case {case} failed with exit status {r.returncode}; stopped here\n" + r.stderr[-2000:])
+            break
+    out = MG_OUT if args.out == ap.get_default("out") else args.out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "a") as f:
+        f.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+    sys.exit(1 if lines[-1].startswith("# case") else 0)
 if args.pcg and not args.child:         # the driver: opens no GPU itself
     head = f"# scripts/batched_ab.py --pcg {args.pcg}" + (f" --stride {args.stride}" if args.pcg == "line" else "")
     lines = [head + f" --systems {args.systems} --iters {args.iters} --warmup {args.warmup} --reps {args.reps}"]
@@ -93,6 +123,100 @@ def window(fn):
 
 def summary(samples):
     return {"median": round(statistics.median(samples), 3), "min": round(min(samples), 3), "max": round(max(samples), 3)}
+
+
+def mg_case(case):
+    """one case of the multigrid leg: the three forms on the same systems, right-hand sides and tolerances"""
+    import scipy.sparse as sp
+    kind, side = case.split(":")
+    side = int(side)
+    nsys = args.systems
+    dims = (side, side, 1)
+    if kind == "var5":
+        dt = np.float64
+        t = sp.diags([-np.ones(side - 1), 2 * np.ones(side), -np.ones(side - 1)], [-1, 0, 1], format="csr")
+        eye = sp.identity(side, format="csr")
+        lap = sp.csr_matrix(sp.kron(eye, t) + sp.kron(t, eye))
+        mats = []
+        for r in range(nsys):
+            rng = np.random.default_rng(3 + r)
+            d = sp.diags(np.sqrt(rng.uniform(0.5, 2.0, side * side)))
+            A = sp.csr_matrix(d @ (lap + sp.diags(rng.uniform(0.0, 0.5, side * side))) @ d)
+            A.sort_indices()
+            mats.append(A)
+        ip, ix = mats[0].indptr.astype(np.int32), mats[0].indices.astype(np.int32)
+        vals = [A.data.astype(dt) for A in mats]
+    else:
+        dt = np.complex64
+        ipd, ixd, dad = pkg.generators.local_rect(ctx, side, 10.0, 10.0, 10.0, 1.0, side, side, dtype=dt)
+        ip, ix, da = ipd.cpu().numpy().astype(np.int32), ixd.cpu().numpy().astype(np.int32), dad.cpu().numpy()
+        rows = np.repeat(np.arange(len(ip) - 1), np.diff(ip))
+        vals = []
+        for r in range(nsys):
+            s_ = np.random.default_rng(100 + r).uniform(0.8, 1.25, len(ip) - 1).astype(np.float32)
+            vals.append((da * s_[rows] * s_[ix]).astype(dt))
+    n, nnz = len(ip) - 1, len(ix)
+    rng = np.random.default_rng(11)
+    B = rng.standard_normal((nsys, n)).astype(dt)
+    tol = 1e-6 * np.linalg.norm(B, axis=1)
+    bd = torch.from_numpy(B.reshape(-1)).to(dev)
+    b1 = [torch.from_numpy(B[r].copy()).to(dev) for r in range(nsys)]
+    M = ("multigrid", dims)
+    forms = {
+        "batched multigrid": ([pkg.Solver(ctx, n, nnz, np.concatenate(vals), ip, ix, nsys, batched=True)], M),
+        "nine multigrid handles": ([pkg.Solver(ctx, n, nnz, vals[r], ip, ix, 1) for r in range(nsys)], M),
+        "batched jacobi": ([pkg.Solver(ctx, n, nnz, np.concatenate(vals), ip, ix, nsys, batched=True)], "jacobi"),
+    }
+    maxit = 4000
+
+    def solve(hs):
+        its = []
+        for k, h in enumerate(hs):
+            h.set_rhs(bd if h.n_rhs == nsys else b1[k], None, on_device=True)
+            its += [int(v) for v in h.iterate_until(tol if h.n_rhs == nsys else tol[k:k + 1], maxit)]
+        ctx.synchronize()
+        return its
+
+    results = {}
+    for name, (hs, m) in forms.items():
+        setup = []
+        for _ in range(3):              # the setup: set_preconditioner on every handle of the form, synchronised
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            for h in hs:
+                h.set_preconditioner(m)
+            ctx.synchronize()
+            setup.append((time.perf_counter() - t0) * 1e3)
+        its = solve(hs)                 # warm-up: captures the graphs
+        solve(hs)
+        results[name] = {"its": its, "setup": setup, "ms": []}
+    for rep_ in range(args.reps):       # the forms alternate inside every repeat
+        for name, (hs, m) in forms.items():
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            solve(hs)
+            results[name]["ms"].append((time.perf_counter() - t0) * 1e3)
+    for name, (hs, m) in forms.items():
+        r = results[name]
+        med = statistics.median(r["ms"])
+        print(json.dumps({"case": case, "rows": n, "nnz": nnz, "systems": nsys, "dtype": np.dtype(dt).name, "form": name, "handles": len(hs),
+                          "levels": len(hs[0].mg_levels()), "loop_launches": lib.cgamd_solver_loop_launches(hs[0].handle),
+                          "iterations": r["its"], "converged": bool(max(r["its"]) < maxit), "reps": args.reps,
+                          "ms_per_solve_all_systems": summary(r["ms"]),
+                          "us_per_iteration": round(med * 1e3 / max(1, max(r["its"])), 3),
+                          "setup_ms": summary(r["setup"]), "iter_moved_bytes": sum(h.iter_moved_bytes for h in hs)}), flush=True)
+    ma, mb, mc = (statistics.median(results[k]["ms"]) for k in forms)
+    print(json.dumps({"case": case, "rows": n, "systems": nsys, "batched_multigrid_over_nine_handles_speedup": round(mb / ma, 3),
+                      "batched_multigrid_over_batched_jacobi_speedup": round(mc / ma, 3)}), flush=True)
+    for hs, _ in forms.values():
+        for h in hs:
+            h.close()
+
+
+if args.mg:
+    mg_case(args.mg_case)
+    ctx.close()
+    sys.exit(0)
 
 
 for side in (int(v) for v in args.sizes.split(",")):
