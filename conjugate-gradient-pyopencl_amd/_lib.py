@@ -190,6 +190,12 @@ def load():
         "cgamd_dist_set_preconditioner": (ci, [vp, vp]),
         "cgamd_dist_set_preconditioner_jacobi": (ci, [vp]),
         "cgamd_dist_set_preconditioner_line": (ci, [vp, ci]),
+        "cgamd_dist_set_preconditioner_multigrid": (ci, [vp, ci, ci, ci, ci, ctypes.c_double, ci]),
+        "cgamd_dist_set_preconditioner_amg": (ci, [vp, ci, ctypes.c_double, ci, ctypes.c_double, ci]),
+        "cgamd_dist_mg_levels": (ci, [vp]),
+        "cgamd_dist_mg_level": (ci, [vp, ci, ctypes.POINTER(ll)]),
+        "cgamd_dist_mg_level_matrix": (ci, [vp, ci, vp, vp, vp]),
+        "cgamd_dist_mg_apply": (ci, [vp, vp, vp]),
         "cgamd_dist_refresh_values": (ci, [vp]),
         "cgamd_dist_last_refresh": (ci, [vp]),
         "cgamd_p2p_mailbox_alloc": (ci, [vp, ll, ci, pvp, vp]),

@@ -711,6 +711,15 @@ int mg_aggregates(const MgHierarchy *h, int level, int *agg_host, int *n_coarse,
 int mg_level_state(const MgHierarchy *h, int level, int which, void *out_host, long long cap_values, long long *count, hipStream_t st);
 // w = A_level x as the cycle launches it (the level's plan and leading dimension, the hierarchy's nrhs); synchronises
 int mg_level_spmv(const MgHierarchy *h, int level, const void *x, void *w, hipStream_t st);
+// ---- the cut matrix of a rank of the row-partitioned handle (dist_cut.hip): its rows without the entries at columns >= col_limit
+// count[i] <- kept entries of row i < nu, 0 for the padding rows nu <= i < n (launch_mg_scan makes the row pointers)
+int launch_cut_count(int nu, int n, int col_limit, const int *ptr, const int *cols, int *count, hipStream_t st);
+// the kept columns and values of every row behind ptrc[row], in stored order
+int launch_cut_fill(int dtype, int nu, int col_limit, const void *vals, const int *ptr, const int *cols, const int *ptrc, int *colsc,
+                    void *valsc, hipStream_t st);
+// the values alone, on the pattern a launch_cut_fill left
+int launch_cut_refill(int dtype, int nu, int col_limit, const void *vals, const int *ptr, const int *cols, const int *ptrc, void *valsc,
+                      hipStream_t st);
 // ---- PCG of the row-partitioned loop (vector.hip, p2p.hip): z lives in q's storage for every preconditioner; part = [2][P] partials
 // (r.z, then r.r); rho2 = two-entry parity buffer of rho = r.z (entry iter & 1), delta holds rho for cg_alpha
 // r -= alpha q ; z = m .* r (stored over q) ; partials of r.z and r.r

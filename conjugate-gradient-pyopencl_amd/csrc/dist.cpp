@@ -19,6 +19,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -143,22 +144,48 @@ struct cgamd_dist {
     std::vector<int> xch_dst_off;      // where my entries land in each peer's halo numbering
     SlabComm slab_comm;
     int n_cus = 0;
-    // preconditioner (cgamd_dist_set_preconditioner*): 0 none, 1 diagonal (mdiag), 2 line (tri: factors cut at the rank's row range).
+    // preconditioner (cgamd_dist_set_preconditioner*): 0 none, 1 diagonal (mdiag), 2 line (tri: factors cut at the rank's row range),
+    // 3 multigrid (mg, below).
     // z = M^-1 r lives in q's storage; part_pcg = [2][pcg_P] partials of r.z and r.r; rho2 = parity buffer of rho = r.z (delta holds
     // rho for cg_alpha, history keeps r.r)
     int pre_kind = 0, pcg_P = 0;
     // a preconditioner built from the rank's matrix, which cgamd_dist_refresh_values builds again: 0 none (or the caller's values),
-    // 1 Jacobi, 2 the lines at pre_stride
+    // 1 Jacobi, 2 the lines at pre_stride, 3 / 4 the grid / algebraic multigrid of mg_params
     int pre_from_matrix = 0, pre_stride = 0;
     int last_refresh = 0;   // what the last cgamd_dist_refresh_values did (cgamd_dist_last_refresh)
     void *mdiag = nullptr, *tri_coef = nullptr, *part_pcg = nullptr, *rho2 = nullptr;
     int *tri_plan = nullptr;
     TriLaunch tri;
+    // multigrid (cgamd_dist_set_preconditioner_multigrid / _amg, pre_kind 3): one V-cycle of a hierarchy built from the CUT matrix,
+    // the rank's rows without their halo columns (dist_cut.hip) -- a second, uncoded copy of the rank's columns and values with
+    // n_pad - n_local empty rows behind them (n_pad: n_local rounded up to whole 16-byte packs, the rows mg_build's level 0 works
+    // on).  r and q are allocated to n_pad values, so the cycle runs on them in place; the padding of r is zeroed at set_rhs.
+    // pre_from_matrix 3 / 4: the grid / the algebraic form, with mg_params what cgamd_dist_refresh_values builds again
+    struct CutMatrix {
+        int *ptr = nullptr, *cols = nullptr;
+        void *vals = nullptr;
+        long long nnz = 0;
+        SpmvPlan plan;
+    } cut;
+    MgHierarchy *mg = nullptr;
+    MgParams mg_params;
+    int n_pad = 0;
     // cgamd_dist_iterate_until: the stop (StopRun with one right-hand side: allocated at the first call, armed once per set_rhs).
     // until_stopped: the handle is frozen until the next set_rhs
     StopRun stop;
     bool until_stopped = false;
 };
+
+static void free_cut(cgamd_dist::CutMatrix *c) {
+    for (void *p : {(void *)c->ptr, (void *)c->cols, c->vals})
+        if (p) (void)hipFree(p);
+    *c = cgamd_dist::CutMatrix();
+}
+static void drop_multigrid(cgamd_dist *d) {
+    if (d->mg) mg_free(d->mg);
+    d->mg = nullptr;
+    free_cut(&d->cut);
+}
 
 static int dalloc(void **p, size_t bytes, const char *what) {
     hipError_t e = hipMalloc(p, bytes ? bytes : 16);
@@ -263,6 +290,19 @@ static void *pcg_prr(const cgamd_dist *d) { return static_cast<char *>(d->part_p
 // update = true: r -= alpha q first (z over q); false: set_rhs, z0 of r0 into `z`
 static int pcg_sweep(cgamd_dist *d, bool update, void *z, hipStream_t st, const CgStop *g = nullptr) {
     const int dt = d->dtype, n = d->n_local;
+    if (d->pre_kind == 3) {
+        // multigrid M, the single handle's branch on the distributed launches: r -= alpha q with the r.r partials (guarded), then
+        // z = V-cycle(r) over q and the r.z partials -- both unguarded: z of a stopped handle is read by nothing that writes.  The
+        // cycle is a linear chain of launches on st and works on n_pad rows of r and q (the padding of r is zero, of z comes out zero)
+        int rc;
+        if (update && (rc = launch_axpy_dot(dt, n, d->q, d->r, n, d->sc.alpha, 1, pcg_prr(d), d->pcg_P, st, d->plan.vec_nt, g))) return rc;
+        if ((rc = mg_vcycle(d->mg, d->r, d->q, st))) return rc;
+        if (!update) {      // set_rhs: z0 goes to the local part of d_ext (whose halo part starts where the padding rows would lie)
+            CG_HIP(hipMemcpyAsync(z, d->q, (size_t)n * dtype_size(dt), hipMemcpyDeviceToDevice, st));
+            if ((rc = launch_dot_partials(dt, n, d->r, d->r, n, 1, pcg_prr(d), d->pcg_P, st))) return rc;
+        }
+        return launch_dot_partials(dt, n, d->r, z, n, 1, d->part_pcg, d->pcg_P, st);
+    }
     if (d->pre_kind == 1) {
         if (!update) return launch_pcg_axpy2_dot2(dt, true, n, z, d->x, d->q, d->r, d->mdiag, n, nullptr, 1, d->part_pcg, pcg_prr(d), d->pcg_P, st);
         return launch_pcg_jacobi_z(dt, n, d->q, d->r, d->mdiag, d->sc.alpha, d->part_pcg, pcg_prr(d), d->pcg_P, st, g);
@@ -491,8 +531,13 @@ int cgamd_dist_create(cgamd_ctx *ctx, const void *id128, int rank, int nranks, i
     const size_t vs = dtype_size(dtype);
     int rc = CGAMD_OK;
     if (!rc) rc = dalloc(&d->x, (size_t)n_local * vs, "x");
-    if (!rc) rc = dalloc(&d->r, (size_t)n_local * vs, "r");
-    if (!rc) rc = dalloc(&d->q, (size_t)n_local * vs, "q");
+    // (r and q to whole 16-byte packs: the multigrid cycle works on n_pad rows of them)
+    {
+        const int E = (int)(16 / vs);
+        d->n_pad = n_local < 2147483647 - 8 ? (n_local + E - 1) / E * E : n_local;
+    }
+    if (!rc) rc = dalloc(&d->r, (size_t)d->n_pad * vs, "r");
+    if (!rc) rc = dalloc(&d->q, (size_t)d->n_pad * vs, "q");
     if (!rc) rc = dalloc(&d->b, (size_t)n_local * vs, "b");
     if (!rc) rc = dalloc(&d->d_ext, ((size_t)n_local + n_halo) * vs, "d_ext");
     if (!rc) rc = dalloc(&d->sendbuf, (size_t)so * vs, "sendbuf");
@@ -589,6 +634,7 @@ int cgamd_dist_destroy(cgamd_dist *d) {
     if (d->vcodes) (void)hipFree(d->vcodes);
     if (d->vdict) (void)hipFree(d->vdict);
     if (d->dict) (void)hipFree(d->dict);
+    drop_multigrid(d);
     void *bufs[] = {d->x, d->r, d->q, d->b, d->d_ext, d->sendbuf, d->part_dq, d->part_rr, d->red, d->sc.alpha,
                     d->sc.beta, d->sc.delta, d->sc.history, d->sc.iter, d->s2, d->cg1_state, d->part_cg1, d->slab_sync, d->slab_map, d->ds_own[0], d->ds_own[1],
                     d->push_dst_dev, d->mdiag, d->tri_coef, d->part_pcg, d->rho2, d->tri_plan, d->tri.maps};
@@ -616,6 +662,8 @@ int cgamd_dist_set_rhs(cgamd_dist *d, const void *b_local, const void *x0_local)
                           nullptr, nullptr, st))) return rc;
     if ((rc = launch_sub(d->dtype, d->n_local, d->b, d->q, d->r, d->n_local, 1, st))) return rc;
     if (d->pre_kind) {      // z0 = M^-1 r0, d = z0, rho0 = all-reduced r0.z0, history[0] = r0.r0
+        if (d->pre_kind == 3 && d->n_pad > d->n_local)      // the cycle reads whole packs of r: nothing else ever writes the padding
+            CG_HIP(hipMemsetAsync(static_cast<char *>(d->r) + vb, 0, (size_t)(d->n_pad - d->n_local) * vs, st));
         if ((rc = pcg_sweep(d, false, d->d_ext, st))) return rc;
         if ((rc = pcg_reduce2(d, 1, st))) return rc;
     } else {
@@ -753,6 +801,7 @@ static void drop_preconditioner(cgamd_dist *d) {
     d->mdiag = d->tri_coef = d->part_pcg = nullptr;
     d->tri_plan = nullptr;
     d->tri = TriLaunch();
+    drop_multigrid(d);
     d->pre_kind = d->pcg_P = 0;
     d->pre_from_matrix = d->pre_stride = 0;
     drop_graph(d);
@@ -855,6 +904,164 @@ int cgamd_dist_set_preconditioner_line(cgamd_dist *d, int stride) {
     return CGAMD_OK;
 }
 
+// ---- multigrid on the cut matrix (include/cgamd.h).  The cut matrix: count, scan, fill (dist_cut.hip), its row pointers extended by
+// the empty padding rows, 64 zeroed entries behind columns and values as the coarse levels carry, and a plan made as theirs is.  It
+// runs the as-passed SpMV: the handle's column / value codes describe the uncut rows.
+static int build_cut(cgamd_dist *d, const std::string &who, cgamd_dist::CutMatrix *out) {
+    const int dt = d->dtype, nu = d->n_local, n = d->n_pad;
+    const size_t vs = dtype_size(dt);
+    hipStream_t st = d->ctx->stream;
+    cgamd_dist::CutMatrix c;
+    void *words = nullptr;      // ints: [0] scan overflow flag, [4 ...] scratch of compute_spmv_plan
+    int rc = dalloc(&words, 64, "cut matrix: setup words");
+    int *flag = static_cast<int *>(words), *scratch = flag + 4;
+    if (!rc) rc = dalloc((void **)&c.ptr, ((size_t)n + 1 + 64) * 4, "cut matrix: row pointers");
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemsetAsync(words, 0, 64, st);
+    if (!rc && e == hipSuccess) rc = launch_cut_count(nu, n, nu, d->ptr, d->cols, c.ptr, st);
+    if (!rc && e == hipSuccess) rc = launch_mg_scan(n, c.ptr, flag, st);
+    int back[2] = {0, 0};       // overflow flag, kept entries
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(&back[0], flag, 4, hipMemcpyDeviceToHost, st);
+    if (!rc && e == hipSuccess) e = hipMemcpyAsync(&back[1], c.ptr + n, 4, hipMemcpyDeviceToHost, st);
+    if (!rc && e == hipSuccess) e = hipStreamSynchronize(st);
+    if (!rc && e == hipSuccess && (back[0] || back[1] < 0 || back[1] > d->nnz)) rc = fail(CGAMD_ERR_HIP, who + ": the cut matrix's entry count is out of range");
+    if (!rc && e == hipSuccess) {
+        c.nnz = back[1];
+        rc = dalloc((void **)&c.cols, ((size_t)c.nnz + 64) * 4, "cut matrix: columns");
+        if (!rc) rc = dalloc(&c.vals, ((size_t)c.nnz + 64) * vs, "cut matrix: values");
+        if (!rc) e = hipMemsetAsync(c.cols, 0, ((size_t)c.nnz + 64) * 4, st);
+        if (!rc && e == hipSuccess) e = hipMemsetAsync(c.vals, 0, ((size_t)c.nnz + 64) * vs, st);
+        if (!rc && e == hipSuccess) rc = launch_cut_fill(dt, nu, nu, d->vals, d->ptr, d->cols, c.ptr, c.cols, c.vals, st);
+        if (!rc && e == hipSuccess) {
+            c.plan = make_spmv_plan(n);
+            rc = compute_spmv_plan(c.ptr, c.cols, n, scratch, st, &c.plan);
+            if (!rc) finalize_spmv_plan(&c.plan, dt, 1, n, c.nnz, c.vals, c.cols);
+        }
+        if (!rc && e == hipSuccess) e = hipStreamSynchronize(st);
+    }
+    if (words) (void)hipFree(words);
+    if (!rc && e != hipSuccess) rc = fail(CGAMD_ERR_HIP, who + ": cut matrix: " + hipGetErrorString(e));
+    if (rc) { free_cut(&c); return rc; }
+    *out = c;
+    return CGAMD_OK;
+}
+
+// refresh = false: a new cut matrix and hierarchy, installed when both stand (a failure leaves the handle as it was).  refresh = true
+// (cgamd_dist_refresh_values): the pattern in place, its values refilled from the rank's, the hierarchy built again on them
+static int multigrid_from_cut(cgamd_dist *d, const std::string &who, const MgParams &p, bool refresh) {
+    hipStream_t st = d->ctx->stream;
+    cgamd_dist::CutMatrix c;
+    int rc;
+    if (refresh) {
+        c = d->cut;
+        if ((rc = launch_cut_refill(d->dtype, d->n_local, d->n_local, d->vals, d->ptr, d->cols, c.ptr, c.vals, st))) return rc;
+    } else if ((rc = build_cut(d, who, &c))) return rc;
+    MgHierarchy *h = nullptr;
+    rc = mg_build(st, d->dtype, d->n_local, d->n_pad, 1, 0, c.plan, c.nnz, c.vals, c.ptr, c.cols, p, who, &h);
+    void *part = nullptr;
+    if (!rc && (rc = pre_buffers(d, d->vgrid, &part, nullptr, 0))) mg_free(h);
+    if (rc) {
+        if (part) (void)hipFree(part);
+        if (!refresh) free_cut(&c);
+        return rc;
+    }
+    if (refresh) d->cut = cgamd_dist::CutMatrix();      // (kept across the drop below)
+    drop_preconditioner(d);
+    d->cut = c; d->mg = h; d->mg_params = p;
+    d->part_pcg = part; d->pcg_P = d->vgrid; d->pre_kind = 3;
+    d->pre_from_matrix = p.algebraic ? 4 : 3;
+    return CGAMD_OK;
+}
+static int mg_begin(cgamd_dist *d, const std::string &who) {
+    if (int rc = pre_begin(d, who.c_str())) return rc;
+    if (d->n_pad % (int)(16 / dtype_size(d->dtype)) != 0) return fail(CGAMD_ERR_INVALID, who + ": the rank has too many rows for the padding to whole 16-byte packs");
+    return CGAMD_OK;
+}
+
+int cgamd_dist_set_preconditioner_multigrid(cgamd_dist *d, int nx, int ny, int nz, int smooth_steps, double over_correction, int min_rows) {
+    const std::string who = "dist_set_preconditioner_multigrid";
+    if (!d) return fail(CGAMD_ERR_INVALID, who + ": null handle");
+    TuneScope ts(&d->tune);
+    if (int rc = mg_begin(d, who)) return rc;
+    if (nx < 1 || ny < 1 || nz < 1) return fail(CGAMD_ERR_INVALID, who + ": every grid dimension must be at least 1");
+    const long long plane = (long long)nx * ny;
+    if (plane > 2147483647LL || plane * nz != (long long)d->n_local)
+        return fail(CGAMD_ERR_INVALID, who + ": nx * ny * nz must equal the size of the system (the rank's own box: n_local rows)");
+    if (smooth_steps < 0 || smooth_steps > 4) return fail(CGAMD_ERR_INVALID, who + ": smooth_steps must be in 0 ... 4 (0 = the default, 1)");
+    if (!std::isfinite(over_correction) || over_correction < 0.) return fail(CGAMD_ERR_INVALID, who + ": over_correction must be finite and not negative (0 = the default, 1.6)");
+    if (min_rows < 0) return fail(CGAMD_ERR_INVALID, who + ": min_rows must not be negative (0 = the default, 512)");
+    MgParams p;
+    p.nx = nx; p.ny = ny; p.nz = nz;
+    if (smooth_steps) p.smooth_steps = smooth_steps;
+    if (over_correction != 0.) p.omega = over_correction;
+    if (min_rows) p.min_rows = min_rows;
+    return multigrid_from_cut(d, who, p, false);
+}
+
+int cgamd_dist_set_preconditioner_amg(cgamd_dist *d, int passes, double strength, int smooth_steps, double over_correction, int min_rows) {
+    const std::string who = "dist_set_preconditioner_amg";
+    if (!d) return fail(CGAMD_ERR_INVALID, who + ": null handle");
+    TuneScope ts(&d->tune);
+    if (int rc = mg_begin(d, who)) return rc;
+    if (passes < 0 || passes > 3) return fail(CGAMD_ERR_INVALID, who + ": passes must be in 0 ... 3 (0 = the default, 3)");
+    if (!std::isfinite(strength) || strength < 0. || strength > 1.) return fail(CGAMD_ERR_INVALID, who + ": strength must be in (0, 1] (0 = the default, 0.25)");
+    if (smooth_steps < 0 || smooth_steps > 4) return fail(CGAMD_ERR_INVALID, who + ": smooth_steps must be in 0 ... 4 (0 = the default, 1)");
+    if (!std::isfinite(over_correction) || over_correction < 0.) return fail(CGAMD_ERR_INVALID, who + ": over_correction must be finite and not negative (0 = the default, 1.6)");
+    if (min_rows < 0) return fail(CGAMD_ERR_INVALID, who + ": min_rows must not be negative (0 = the default, 512)");
+    MgParams p;
+    p.algebraic = true;
+    if (passes) p.passes = passes;
+    if (strength != 0.) p.theta = strength;
+    if (smooth_steps) p.smooth_steps = smooth_steps;
+    if (over_correction != 0.) p.omega = over_correction;
+    if (min_rows) p.min_rows = min_rows;
+    return multigrid_from_cut(d, who, p, false);
+}
+
+int cgamd_dist_mg_levels(cgamd_dist *d) {
+    if (!d) return -CGAMD_ERR_INVALID;
+    return d->mg ? mg_levels(d->mg) : 0;
+}
+static int dist_mg_wanted(cgamd_dist *d, const char *who) {
+    if (!d) return fail(CGAMD_ERR_INVALID, std::string(who) + ": null handle");
+    if (!d->mg) return fail(CGAMD_ERR_STATE, std::string(who) + ": no multigrid preconditioner is set");
+    CG_HIP(hipSetDevice(d->ctx->device));
+    return CGAMD_OK;
+}
+int cgamd_dist_mg_level(cgamd_dist *d, int level, long long info[6]) {
+    if (int rc = dist_mg_wanted(d, "dist_mg_level")) return rc;
+    if (!info) return fail(CGAMD_ERR_INVALID, "dist_mg_level: info is NULL");
+    return mg_level_info(d->mg, level, info);
+}
+int cgamd_dist_mg_level_matrix(cgamd_dist *d, int level, int *ptr, int *cols, void *vals) {
+    if (int rc = dist_mg_wanted(d, "dist_mg_level_matrix")) return rc;
+    return mg_level_matrix(d->mg, level, ptr, cols, vals, d->ctx->stream);
+}
+// one V-cycle on caller vectors (n_local device values each), through buffers with the padding rows; synchronises
+int cgamd_dist_mg_apply(cgamd_dist *d, const void *r_dev, void *z_dev) {
+    if (int rc = dist_mg_wanted(d, "dist_mg_apply")) return rc;
+    if (!r_dev || !z_dev) return fail(CGAMD_ERR_INVALID, "dist_mg_apply: null argument");
+    TuneScope ts(&d->tune);
+    hipStream_t st = d->ctx->stream;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return fail(CGAMD_ERR_HIP, "dist_mg_apply: hipStreamIsCapturing failed"); }
+    if (cs != hipStreamCaptureStatusNone) return fail(CGAMD_ERR_INVALID, "dist_mg_apply: the handle's stream is being captured");
+    const size_t vs = dtype_size(d->dtype), bytes = (size_t)d->n_pad * vs, user = (size_t)d->n_local * vs;
+    void *buf = nullptr;
+    if (int rc = dalloc(&buf, 2 * bytes, "mg_apply vectors")) return rc;
+    void *r = buf, *z = static_cast<char *>(buf) + bytes;
+    int rc = CGAMD_OK;
+    hipError_t e = hipMemsetAsync(buf, 0, 2 * bytes, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(r, r_dev, user, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) rc = mg_vcycle(d->mg, r, z, st);
+    if (e == hipSuccess && !rc) e = hipMemcpyAsync(z_dev, z, user, hipMemcpyDeviceToDevice, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    if (rc) return rc;
+    if (e != hipSuccess || e2 != hipSuccess) return fail(CGAMD_ERR_HIP, std::string("dist_mg_apply: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+    return CGAMD_OK;
+}
+
 // The rank's matrix values changed in place on the same pattern (include/cgamd.h).  Rank-local: nothing here communicates; collective
 // in meaning: every rank calls it.  What was made from the values follows them: the value codes (dictionary rewritten in place where
 // the equal-value classes are intact, else rebuilt or dropped, with the captured graph) and a preconditioner built from the matrix.
@@ -894,7 +1101,10 @@ int cgamd_dist_refresh_values(cgamd_dist *d) {
     }
     if (d->pre_from_matrix) {
         const int stride = d->pre_stride;
-        const int rc = d->pre_from_matrix == 1 ? cgamd_dist_set_preconditioner_jacobi(d) : cgamd_dist_set_preconditioner_line(d, stride);
+        const MgParams p = d->mg_params;
+        const int rc = d->pre_from_matrix == 1   ? cgamd_dist_set_preconditioner_jacobi(d)
+                       : d->pre_from_matrix == 2 ? cgamd_dist_set_preconditioner_line(d, stride)
+                                                 : multigrid_from_cut(d, p.algebraic ? "dist_set_preconditioner_amg" : "dist_set_preconditioner_multigrid", p, true);
         if (rc) {           // the values are in force; the old factors belong to the old ones
             const std::string why = cgamd_last_error();
             drop_preconditioner(d);
@@ -1103,7 +1313,9 @@ int cgamd_dist_loop_launches(cgamd_dist *d) {
     if (d->slab.ok && !d->pre_kind) return 0;
     if (d->cg1) return d->p2p ? 2 : (d->peer.empty() ? 4 : 6);
     // the preconditioned loops replace launches one for one; the stride-1 line sweep in its long form is three launches, not one
-    const int extra = (d->pre_kind == 2 && d->tri.longform) ? 2 : 0;
+    // multigrid: the r update and the r.z partials are launches of their own around the cycle's chain (one more than the sweep they
+    // replace), plus every launch of the cycle
+    const int extra = d->pre_kind == 3 ? 1 + mg_cost(d->mg).launches : (d->pre_kind == 2 && d->tri.longform) ? 2 : 0;
     if (d->direct && d->p2p_attached) return 4 + extra;
     if (d->p2p) return (d->peer.empty() ? 5 : 7) + extra;
     return (d->peer.empty() ? 9 : 11) + extra;

@@ -55,6 +55,24 @@ def row_ranges(n, world, indptr=None):
     return [(cuts[g], cuts[g + 1]) for g in range(world)]
 
 
+def local_grid_dims(dims, ranges, rank):
+    """(nx, ny, nz) of the box a rank owns of a grid numbered x fastest, for DistSolver.set_preconditioner(("multigrid", ...)).
+    dims: the global (nx, ny, nz), or (nx, ny) for nz = 1; ranges: `row_ranges`' blocks.  The rank's rows must be whole planes of
+    nx * ny nodes (z-slabs), or whole x-lines of a grid with nz == 1; anything else is not a box and raises ValueError (the
+    algebraic form, "amg", takes any row range)."""
+    dims = tuple(int(v) for v in dims)
+    if len(dims) not in (2, 3) or any(v < 1 for v in dims):
+        raise ValueError(f"local_grid_dims: dims must be (nx, ny) or (nx, ny, nz) with positive entries, got {dims!r}")
+    nx, ny, nz = dims + (1,) * (3 - len(dims))
+    rb, re = (int(v) for v in ranges[rank])
+    if not 0 <= rb < re <= nx * ny * nz:
+        raise ValueError(f"local_grid_dims: rows [{rb}, {re}) of rank {rank} are not rows of a {nx} x {ny} x {nz} grid")
+    unit, what = (nx * ny, "planes") if nz > 1 else (nx, "x-lines")
+    if rb % unit or re % unit:
+        raise ValueError(f"local_grid_dims: rows [{rb}, {re}) of rank {rank} are not whole {what} of {unit} nodes")
+    return (nx, ny, (re - rb) // unit) if nz > 1 else (nx, (re - rb) // unit, 1)
+
+
 @dataclass
 class HaloPlan:
     rank: int
@@ -469,7 +487,10 @@ class DistSolver:
     def set_preconditioner(self, m, group=None):
         """Preconditioned CG from the next set_rhs on.  m: None (remove), "jacobi" (1 / diag of the rank's matrix, built on the
         device), ("line", stride) (the local entries at column - row in {-stride, 0, +stride}; halo columns never count, so lines end
-        at the rank's row range) or a device tensor / buffer of n_local values (z = m .* r).  Collective over `group`: the C calls
+        at the rank's row range), ("multigrid", local_dims[, opts]) (one V-cycle of a hierarchy built from the rank's CUT matrix, its
+        rows without their halo columns; local_dims is the rank's own box, `local_grid_dims`; opts as the single Solver's), "amg" or
+        ("amg", opts) (the same on aggregates matched from the cut matrix: any row range) or a device tensor / buffer of n_local
+        values (z = m .* r).  Collective over `group`: the C calls
         are local, so the ranks' statuses are all-gathered afterwards; if ANY rank failed, every rank removes its preconditioner and
         raises CgAmdError with the failing rank and its message -- ranks running different recurrences would wait for each
         other's sums until the peer-to-peer time-outs."""
@@ -481,6 +502,26 @@ class DistSolver:
         elif (isinstance(m, (tuple, list)) and len(m) == 2 and isinstance(m[0], str) and m[0] == "line"
               and isinstance(m[1], (int, np.integer)) and not isinstance(m[1], bool)):
             call = lambda: lib.cgamd_dist_set_preconditioner_line(self.handle, int(m[1]))
+        elif (isinstance(m, str) and m == "amg") or (isinstance(m, (tuple, list)) and len(m) == 2 and isinstance(m[0], str)
+                                                     and m[0] == "amg" and isinstance(m[1], dict)):
+            opts = {} if isinstance(m, str) else dict(m[1])
+            if set(opts) - {"passes", "strength", "smooth_steps", "over_correction", "min_rows"}:
+                raise ValueError('set_preconditioner: "amg" or ("amg", {"passes": 3, "strength": 0.25, "smooth_steps": 1, '
+                                 '"over_correction": 1.6, "min_rows": 512})')
+            args = (int(opts.get("passes", 0)), float(opts.get("strength", 0.0)), int(opts.get("smooth_steps", 0)),
+                    float(opts.get("over_correction", 0.0)), int(opts.get("min_rows", 0)))
+            call = lambda: lib.cgamd_dist_set_preconditioner_amg(self.handle, *args)
+        elif (isinstance(m, (tuple, list)) and len(m) in (2, 3) and isinstance(m[0], str) and m[0] == "multigrid"
+              and isinstance(m[1], (tuple, list)) and 1 <= len(m[1]) <= 3
+              and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in m[1])
+              and (len(m) == 2 or isinstance(m[2], dict))):
+            dims = tuple(int(v) for v in m[1]) + (1,) * (3 - len(m[1]))
+            opts = dict(m[2]) if len(m) == 3 else {}
+            if set(opts) - {"smooth_steps", "over_correction", "min_rows"}:
+                raise ValueError('set_preconditioner: ("multigrid", (nx, ny, nz)[, {"smooth_steps": 1, "over_correction": 1.6, '
+                                 '"min_rows": 512}]) with the dims of the rank\'s own box (local_grid_dims)')
+            args = dims + (int(opts.get("smooth_steps", 0)), float(opts.get("over_correction", 0.0)), int(opts.get("min_rows", 0)))
+            call = lambda: lib.cgamd_dist_set_preconditioner_multigrid(self.handle, *args)
         elif not isinstance(m, (str, tuple, list)) and (hasattr(m, "data_ptr") or hasattr(m, "ptr")):
             count = m.numel() if hasattr(m, "numel") else getattr(m, "size", self.plan.n_local)
             if int(count) != self.plan.n_local:
@@ -494,7 +535,8 @@ class DistSolver:
                 torch.cuda.synchronize()        # torch filled the tensor on ITS stream; the library copies it on the context's
             call = lambda: lib.cgamd_dist_set_preconditioner(self.handle, ptr(m))
         else:
-            raise ValueError('set_preconditioner: expected None, "jacobi", ("line", stride) or n_local device values')
+            raise ValueError('set_preconditioner: expected None, "jacobi", ("line", stride), ("multigrid", local_dims[, opts]), "amg", '
+                             '("amg", opts) or n_local device values')
         status = call()
         mine = (int(status), lib.cgamd_last_error().decode(errors="replace") if status else "")
         if self.plan.world > 1:
@@ -509,9 +551,39 @@ class DistSolver:
             r, (code, text) = bad[0]
             raise _lib.CgAmdError(code, f"set_preconditioner failed on rank {r}: {text}")
 
+    def mg_levels(self):
+        """this rank's multigrid hierarchy in force: a list of dicts (rows, nnz, nx, ny, nz, lmax), level 0 (the cut matrix) first; []
+        without one"""
+        out = []
+        for l in range(max(0, self._lib.cgamd_dist_mg_levels(self.handle))):
+            info = (ctypes.c_longlong * 6)()
+            check(self._lib.cgamd_dist_mg_level(self.handle, l, info))
+            out.append({"rows": int(info[0]), "nnz": int(info[1]), "nx": int(info[2]), "ny": int(info[3]), "nz": int(info[4]),
+                        "lmax": float(np.array([info[5]], dtype=np.int64).view(np.float64)[0])})
+        return out
+
+    def mg_level_matrix(self, level):
+        """(indptr, indices, data) of a level of this rank's hierarchy, copied to the host (development accessor: tests)"""
+        info = self.mg_levels()[level]
+        ip, ix, da = np.empty(info["rows"] + 1, np.int32), np.empty(info["nnz"], np.int32), np.empty(info["nnz"], self.dtype)
+        check(self._lib.cgamd_dist_mg_level_matrix(self.handle, int(level), ptr(ip), ptr(ix), ptr(da)))
+        return ip, ix, da
+
+    def mg_apply(self, r):
+        """z = one V-cycle of this rank's hierarchy on r: a device tensor of n_local values in, a new one out (development
+        accessor: tests)"""
+        import torch
+        if int(r.numel()) != self.plan.n_local or not r.is_cuda or np.dtype(str(r.dtype).replace("torch.", "")) != self.dtype:
+            raise ValueError("mg_apply takes n_local device values of the solver's type")
+        r = r.contiguous()
+        z = torch.empty_like(r)
+        torch.cuda.synchronize()        # torch filled r on ITS stream; the library reads it on the context's
+        check(self._lib.cgamd_dist_mg_apply(self.handle, ptr(r), ptr(z)))
+        return z
+
     def refresh_values(self, group=None):
         """The rank's matrix values (the borrowed tensor) were changed in place on the same pattern: the value codes and a "jacobi"
-        / ("line", stride) preconditioner follow them (cgamd_dist_refresh_values); the next call must be set_rhs.  Collective over
+        / ("line", stride) / multigrid preconditioner follow them (cgamd_dist_refresh_values); the next call must be set_rhs.  Collective over
         `group` like set_preconditioner: the C call is local, the statuses are all-gathered; if ANY rank failed (a zero diagonal
         under the new values), every rank removes its preconditioner and raises CgAmdError with the failing rank and its message."""
         lib = self._lib

@@ -895,11 +895,35 @@ int cgamd_dist_synchronize(cgamd_dist *d);
 int cgamd_dist_set_preconditioner(cgamd_dist *d, const void *m_local);
 int cgamd_dist_set_preconditioner_jacobi(cgamd_dist *d);
 int cgamd_dist_set_preconditioner_line(cgamd_dist *d, int stride);
+/* Multigrid on the row-partitioned handle: block-Jacobi over the ranks with a LOCAL hierarchy.  M^-1 on a rank is one V-cycle
+ * (cgamd_solver_set_preconditioner_multigrid / _amg: same algorithm, defaults with 0, argument checks, error wording and level naming)
+ * of a hierarchy built from the rank's CUT MATRIX: its rows with every entry at a halo column (>= n_local) removed, stored order kept --
+ * the rank's diagonal block of A, symmetric positive definite whenever A is; the rule of the line preconditioner ("halo columns are
+ * never line neighbours") for a whole matrix.  The cut matrix is a second copy of the rank's columns and values kept by the handle
+ * (nnz_local entries at most) and runs the as-passed SpMV, not the coded one.  Errors name the LOCAL row.
+ *   _multigrid  (nx, ny, nz) is the rank's OWN box, x fastest: nx * ny * nz != n_local is CGAMD_ERR_INVALID.  The caller vouches
+ *               that its row range is that box (z-slabs of whole planes are).
+ *   _amg        aggregates matched from the cut matrix: any row range, one that falls mid-line included.
+ * Contracts of the three entries above: collective in meaning and local in execution, in force from the next cgamd_dist_set_rhs, a
+ * failed call leaves the handle as it was, cgamd_dist_set_preconditioner(d, NULL) removes the hierarchy, CGAMD_DIST_SINGLE_REDUCTION
+ * gets CGAMD_ERR_STATE, a CGAMD_DIST_RESIDENT handle runs its launched loop meanwhile.  Every launched loop is served, captured or
+ * not, and cgamd_dist_iterate_until (the r update guarded; the cycle and the r.z partials unguarded; communication unchanged).  An
+ * iteration: [SpMV + halo] [all-reduce d.q, alpha] [r -= alpha q, r.r] [the cycle's chain of launches, z over q] [r.z] [all-reduce
+ * of both, beta, x += alpha d, d = z + beta d]: cgamd_dist_loop_launches is the preconditioned loop's count plus one plus the
+ * cycle's launches.  cgamd_dist_refresh_values refills the cut values and builds the hierarchy again (removed if that fails).
+ * cgamd_dist_mg_levels / _mg_level / _mg_level_matrix: as the cgamd_solver_mg_* accessors, level 0 the cut matrix.
+ * cgamd_dist_mg_apply: z = one V-cycle of r, n_local device values each; synchronises (development accessor, like the two before). */
+int cgamd_dist_set_preconditioner_multigrid(cgamd_dist *d, int nx, int ny, int nz, int smooth_steps, double over_correction, int min_rows);
+int cgamd_dist_set_preconditioner_amg(cgamd_dist *d, int passes, double strength, int smooth_steps, double over_correction, int min_rows);
+int cgamd_dist_mg_levels(cgamd_dist *d);
+int cgamd_dist_mg_level(cgamd_dist *d, int level, long long info[6]);
+int cgamd_dist_mg_level_matrix(cgamd_dist *d, int level, int *ptr, int *cols, void *vals);
+int cgamd_dist_mg_apply(cgamd_dist *d, const void *r_dev, void *z_dev);   /* n_local values each */
 /* The rank's matrix values (always borrowed) were changed in place on the same pattern: as cgamd_solver_refresh_values(s, NULL, 0).
  * Same contract: change the values only between solves, call this on EVERY rank before the next cgamd_dist_set_rhs.  Rank-local (it
  * does not communicate; DistSolver.refresh_values all-gathers the status).  The value codes follow on every loop (RCCL, both
- * peer-to-peer forms, single-reduction, slab); a captured graph is dropped when the code array was replaced; a Jacobi or line
- * preconditioner built from the matrix is built again, and removed if that fails.  cgamd_dist_last_refresh: as
+ * peer-to-peer forms, single-reduction, slab); a captured graph is dropped when the code array was replaced; a Jacobi, line
+ * or multigrid preconditioner built from the matrix is built again, and removed if that fails.  cgamd_dist_last_refresh: as
  * cgamd_solver_last_refresh (the outcome may differ from rank to rank). */
 int cgamd_dist_refresh_values(cgamd_dist *d);
 int cgamd_dist_last_refresh(cgamd_dist *d);
@@ -921,7 +945,8 @@ int cgamd_dist_enable_resident(cgamd_dist *d, long long mailbox_values, const in
 /* as cgamd_solver_index_codes, for this rank's local matrix (the halo columns of a slab partition sit at constant offsets) */
 int cgamd_dist_index_codes(cgamd_dist *d);
 /* stream operations per iteration of the loop this handle runs (kernel launches, plus RCCL calls with that backend); with a
- * preconditioner set, of the preconditioned loop (the same counts; two more where a stride-1 line sweep takes its long form) */
+ * preconditioner set, of the preconditioned loop (the same counts; two more where a stride-1 line sweep takes its long form; with multigrid
+ * one more and the launches of the V-cycle) */
 int cgamd_dist_loop_launches(cgamd_dist *d);
 /* number of ranks of the RCCL communicator behind this handle as RCCL itself reports it (ncclCommCount);
  * 0 when the handle has no communicator (peer-to-peer backend, or one rank without peers) */
