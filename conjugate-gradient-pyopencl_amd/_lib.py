@@ -19,6 +19,7 @@ CODE_DTYPE = {v: k for k, v in DTYPE_CODE.items()}
 
 MATRIX_ON_DEVICE, NO_GRAPH, UNFUSED, DIST_GRAPH, DIST_NO_OVERLAP, DIST_P2P, DIST_P2P_STAGED, DIST_SINGLE_REDUCTION, DIST_RESIDENT = 1, 2, 4, 8, 32, 64, 128, 256, 512
 HERMITIAN = 16      # CGAMD_HERMITIAN: Solver(..., hermitian=True), the conjugated recurrence for complex Hermitian positive-definite matrices
+SPLIT_LONG_ROWS = 1024      # CGAMD_SPLIT_LONG_ROWS: Solver(..., long_rows=True), very long rows cut across work-groups (csrc/long_rows.hip)
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC, ERR_IO, ERR_COMM, ERR_STATE = range(8)      # cgamd_status (include/cgamd.h)
 
 
@@ -118,6 +119,7 @@ def load():
         "cgamd_solver_spmv": (ci, [vp, vp, vp, ci]),
         "cgamd_solver_spmm_rowmajor": (ci, [vp, vp, vp, ci]),
         "cgamd_last_spmv_form": (ci, [ctypes.POINTER(ci), ci]),
+        "cgamd_solver_long_rows": (ci, [vp, ctypes.POINTER(ci), ci]),
         "cgamd_solver_dot_partials": (ci, [vp, vp, ll, ctypes.POINTER(ci)]),
         "cgamd_solver_step_plan": (ci, [vp, ctypes.POINTER(ci), ci]),
         "cgamd_solver_step_state": (ci, [vp, ci, vp, ll, ctypes.POINTER(ll)]),

@@ -258,13 +258,18 @@ class Solver:
     """Matrix-resident CG handle: the reference re-uploads the matrix and re-JITs
     its kernels on every call (clcg.c:142-214, cl.py:45-46,73-84); here only b goes up and x comes down."""
 
-    def __init__(self, ctx, size, non_zeros, a_values, a_pointers, a_cols, n_rhs=1, flags=0, dtype=None, batched=False, hermitian=False):
+    def __init__(self, ctx, size, non_zeros, a_values, a_pointers, a_cols, n_rhs=1, flags=0, dtype=None, batched=False, hermitian=False, long_rows=False):
         """batched=True: n_rhs systems on one pattern (cgamd_solver_create_batched) -- a_values holds n_rhs * non_zeros entries,
         the values of system r at a_values[r * non_zeros:(r + 1) * non_zeros] in the order of a_cols, and right-hand side r
         belongs to system r.
         hermitian=True (flag HERMITIAN): the matrix is complex Hermitian positive definite -- CG with the conjugated inner product
         <a, b> = sum conj(a_i) b_i instead of the reference's unconjugated recurrence, which does not converge on such a matrix.
-        history() is then r^H r (real, >= 0).  Real value types: accepted, changes nothing."""
+        history() is then r^H r (real, >= 0).  Real value types: accepted, changes nothing.
+        long_rows=True (flag SPLIT_LONG_ROWS): rows too long for the block SpMV forms (hubs of a graph Laplacian) are cut across
+        work-groups and every other row keeps those forms; accepted everywhere, without effect where the split does not apply (the
+        property `long_rows` tells)."""
+        if long_rows:
+            flags = int(flags) | _lib.SPLIT_LONG_ROWS
         if hermitian:
             flags = int(flags) | _lib.HERMITIAN
         self.ctx = ctx
@@ -309,6 +314,19 @@ class Solver:
     def hermitian(self):
         """1 when the handle runs the conjugated recurrence (created with hermitian=True / HERMITIAN on a complex type), else 0"""
         return self._lib.cgamd_solver_hermitian(self.handle)
+
+    LONG_ROWS_FIELDS = ("heavy_blocks", "segments", "segment", "body_kind", "body_lanes", "scratch_bytes")
+
+    @property
+    def long_rows(self):
+        """what the SPLIT_LONG_ROWS form of this handle runs on (cgamd_solver_long_rows), as a dict: heavy 256-row blocks, segments,
+        entries per segment, the body's kind (5 row-block, 7 chunked) and lanes per row, bytes of piece scratch; all 0 where the flag
+        is not set or does not apply"""
+        out = (ctypes.c_int * len(self.LONG_ROWS_FIELDS))()
+        got = self._lib.cgamd_solver_long_rows(self.handle, out, len(out))
+        if got < 0:
+            check(-got)
+        return dict(zip(self.LONG_ROWS_FIELDS, (int(v) for v in out)))
 
     def hermitian_scalars(self):
         """(alpha, beta) of the last iteration of a hermitian handle, n_rhs values each (development accessor: step_state describes
@@ -656,6 +674,7 @@ class Solver:
 
     SPMV_FAMILIES = ("stream", "rowblock", "vc", "vcp", "chunked", "spmm", "batched")
     SPMV_FAMILIES_EXTRA = ("rowcode", "rowpair")      # family numbers from len(SPMV_FAMILIES) on
+    SPMV_FAMILIES_SPLIT = ("split",)                  # family 9, SPLIT_LONG_ROWS (a tuple of its own: the two above are pinned by tests)
     SPMV_FORM_FIELDS = ("family", "vec", "width", "index_bits", "value_codes", "nt", "fused", "wide", "grid", "partials")
 
     def last_spmv_form(self):
@@ -667,7 +686,7 @@ class Solver:
         if got < 0:
             check(-got)
         form = dict(zip(self.SPMV_FORM_FIELDS, (int(v) for v in out)))
-        names = self.SPMV_FAMILIES + self.SPMV_FAMILIES_EXTRA
+        names = self.SPMV_FAMILIES + self.SPMV_FAMILIES_EXTRA + self.SPMV_FAMILIES_SPLIT
         form["family"] = names[form["family"]] if form["family"] >= 0 else None
         return form
 

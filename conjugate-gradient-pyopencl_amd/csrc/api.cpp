@@ -42,6 +42,9 @@ int cgamd_tune(const char *key, int value) {
         return fail(CGAMD_ERR_INVALID, "tune: dev.row_pipe takes 0 (default rule), 1, 2 or 4");
     if (k == "dev.row_pairs" && value != -1 && value != 0 && value != 1)
         return fail(CGAMD_ERR_INVALID, "tune: dev.row_pairs takes -1 (default rule), 0 or 1");
+    if (k == "dev.long_row_bytes" && value < 0) return fail(CGAMD_ERR_INVALID, "tune: dev.long_row_bytes takes 0 (the rule) or a byte count");
+    if (k == "dev.long_row_segment" && (value < 0 || (value & 3)))
+        return fail(CGAMD_ERR_INVALID, "tune: dev.long_row_segment takes 0 (default) or a multiple of 4 entries");
     if (k == "dev.spmv_plane" && value != -1 && value != 0 && value != 1)
         return fail(CGAMD_ERR_INVALID, "tune: dev.spmv_plane takes -1 (default rule), 0 or 1");
     g_tune_generation.fetch_add(1, std::memory_order_relaxed);     // cached cg() handles were created under the old configuration
@@ -67,6 +70,8 @@ int cgamd_tune(const char *key, int value) {
     else if (k == "dev.x_lag") g_tune.dev_x_lag = value;
     else if (k == "dev.x_lag_dnt") g_tune.dev_x_lag_dnt = value;
     else if (k == "dev.generic_spmv") g_tune.dev_generic_spmv = value;
+    else if (k == "dev.long_row_bytes") g_tune.dev_long_row_bytes = value;
+    else if (k == "dev.long_row_segment") g_tune.dev_long_row_segment = value;
     else if (k == "dev.value_codes") g_tune.value_codes = value;
     else if (k == "dev.vc_pipe") g_tune.dev_vc_pipe = value;
     else if (k == "dev.joint_codes") g_tune.dev_joint_codes = value;

@@ -34,7 +34,23 @@ constexpr int kQuadsPerThread = 2;   // SpMV: 2 x 4 non-zeros per thread per chu
 
 constexpr int kSuperRows = 4 * kBlock;   // rows of a SUPER block: the kVcBlocks row blocks one work-group of the coded SpMV forms takes (spmv.hip)
 
+// CGAMD_SPLIT_LONG_ROWS (long_rows.hip): the 256-row blocks no block form can hold ("heavy") run a segmented kernel pair, every other
+// block the row-block or chunked kernel through a block list.  Device lists, built once from the row pointers and owned by the handle
+struct LongRows {
+    int on = 0;                     // the handle's single-RHS SpMV takes the split form
+    int n_heavy = 0, n_seg = 0, n_regular = 0;
+    int seg_len = 0;                // entries per segment (a multiple of 4)
+    int body_kind = 0, body_lpr = 1;                // the regular blocks' kernel (5 or 7) and its lanes per row, from THEIR spans:
+    int body_max_span = 0, body_max_row = 0, body_chunk_span[5] = {0, 0, 0, 0, 0};
+    int *regular = nullptr;         // [n_regular] regular row blocks in the order rowblock_of deals them
+    int *heavy = nullptr;           // [n_heavy] heavy row blocks, ascending
+    int *seg0 = nullptr;            // [n_heavy + 1] first segment of every heavy block
+    int *segtab = nullptr;          // [n_seg][2]: heavy block (index into heavy[]), first entry (4-aligned)
+    void *scratch = nullptr;        // [n_seg][2] values: the pieces of the (at most two) rows that cross a segment's edges
+    size_t scratch_bytes = 0;
+};
 struct SpmvPlan {
+    LongRows lr;
     int grid = 0;        // work-groups launched (multiple of 8 when >= 8)
     int row_blocks = 0;  // ceil(n / kBlock)
     int max_span = 0;    // largest 4-aligned nnz span of a kBlock-row slice (0 = unknown -> generic kernel)
@@ -79,6 +95,19 @@ struct SpmvPlan {
     int sched_grid = 0;
 };
 SpmvPlan make_spmv_plan(int n);
+// ---- CGAMD_SPLIT_LONG_ROWS (long_rows.hip) ----
+constexpr int kLongRowSegment = 4 * kQuadsPerThread * kBlock;     // default segment: the stream kernel's chunk, 2048 entries
+constexpr int kLongRowPiece = 64;             // a row's piece inside a segment of up to this many entries is summed by one lane, a longer one by a wave
+constexpr size_t kLongRowMaxLds = 128 * 1024; // a segment's values and columns in LDS: the segment length is clamped to fit
+// Marks the heavy row blocks (an 8-row slice spanning more than heavy_entries entries, measured 4-aligned as spmv_span_kernel does),
+// builds the lists of `out` (count, scan, fill; no atomics) and the spans of the REGULAR blocks (spans[0..5]: 256 ... 8-row slices,
+// spans[7]: longest row).  cycle: the row-block schedule's.  Synchronises `st`.  out->n_heavy == 0: no list was allocated
+int build_long_rows(int n, const int *ptr_dev, int row_blocks, int heavy_entries, int seg_len, size_t value_bytes, int cycle, hipStream_t st,
+                    LongRows *out, int spans[8]);
+void free_long_rows(LongRows *lr);
+// the heavy blocks of y = A x (and their d.q partials, partials[rb], when partials != nullptr): segment launch, then combine launch
+int launch_long_rows(int dtype, const LongRows &lr, bool nt, int n, long long nnz, const void *vals, const int *ptr, const int *cols,
+                     const void *x, void *y, const void *dvec, void *partials, hipStream_t st);
 // fills plan->max_span / chunk_span from the matrix structure; synchronises `st`; scratch_dev: >= 32 bytes
 int compute_spmv_plan(const int *ptr_dev, const int *cols_dev, int n, int *scratch_dev, hipStream_t st, SpmvPlan *plan);
 // device-resident CSR (and an optional device index list with entries in [0, index_bound)): CGAMD_ERR_INVALID on a bad
@@ -187,6 +216,9 @@ struct Tuning {
                                     // table per handle (1: every such handle; 0: the block-cyclic schedule; -1 = the default rule, spmv_plane_wanted)
     int dev_vc_pipe = 1;            // value-coded SpMV: gathers pipelined across the row blocks of a work-group (0 = one block at a time: A/B)
     int dev_generic_spmv = 0;       // 1: the generic chunked CSR stream for every matrix (the row-block kernels' fallback, tested against them)
+    int dev_long_row_bytes = 0;     // CGAMD_SPLIT_LONG_ROWS: an 8-row slice of more than this many bytes makes its row block heavy (0 = kMaxChunkBytes;
+                                    // larger values count as that: the threshold can only be lowered, so that tests reach the form at small shapes)
+    int dev_long_row_segment = 0;   // ... entries per segment, a multiple of 4 (0 = kLongRowSegment)
     int resident_lock = 1;          // 0: no per-GPU serialisation of resident launches (ranks of ONE job sharing a GPU in a rehearsal)
     int slab_trim = -1;             // slab loop: 1024-row granules a member that pushes to a peer owns fewer than the others (-1 = 2, 0 = equal members)
     int slab_cus = 0;               // slab loop: CUs (= members at most) a handle may use; 0 = all (ranks that share a GPU must fit side by side)

@@ -1,6 +1,8 @@
 // oclcgex -- command-line front end with the reference's argv (reference main.c:13-61):
 //     oclcgex <matrix.mtx> <nRHS> <isComplex> <nIterations> [--double] [--device N] [--quiet] [--history <file>] [--hermitian]
-//             [--mixed --tol T] [--multigrid NX NY NZ] [--amg]
+//             [--mixed --tol T] [--multigrid NX NY NZ] [--amg] [--long-rows]
+// --long-rows: the handle is created with CGAMD_SPLIT_LONG_ROWS (nRHS 1: rows too long for the block SpMV forms are cut across
+// work-groups and every other row keeps those forms; without effect where the split does not apply).  Not with --mixed.
 // Matrix-Market file -> symmetric storage expanded -> CSR; b[r*n+i] = (r+1)*5, x0 = 0 (main.c:41-46).
 // --hermitian: the matrix is complex Hermitian positive definite (a `hermitian` file): CG with conjugated inner products
 // (CGAMD_HERMITIAN), the history then being r_k^H r_k.  Never chosen from the file's symmetry field: the default is the reference's
@@ -26,12 +28,12 @@
 
 int main(int argc, char *argv[]) {
     if (argc < 5) {
-        fprintf(stderr, "Usage: %s <input matrix file> <number of RHS> <is complex> <number of iterations> [--double] [--device N] [--quiet] [--history <file>] [--hermitian] [--mixed --tol T] [--multigrid NX NY NZ] [--amg]\n", argv[0]);
+        fprintf(stderr, "Usage: %s <input matrix file> <number of RHS> <is complex> <number of iterations> [--double] [--device N] [--quiet] [--history <file>] [--hermitian] [--mixed --tol T] [--multigrid NX NY NZ] [--amg] [--long-rows]\n", argv[0]);
         return 1;
     }
     const char *path = argv[1];
     const int nRHS = atoi(argv[2]), isComplex = atoi(argv[3]), nIterations = atoi(argv[4]);
-    bool dbl = false, quiet = false, hermitian = false, mixed = false, multigrid = false, amg = false;
+    bool dbl = false, quiet = false, hermitian = false, mixed = false, multigrid = false, amg = false, long_rows = false;
     int mg_dims[3] = {0, 0, 0};
     double rel_tol = 0.;
     int device = 0;
@@ -45,6 +47,7 @@ int main(int argc, char *argv[]) {
         else if (!strcmp(argv[i], "--mixed")) mixed = true;
         else if (!strcmp(argv[i], "--tol") && i + 1 < argc) rel_tol = atof(argv[++i]);
         else if (!strcmp(argv[i], "--amg")) amg = true;
+        else if (!strcmp(argv[i], "--long-rows")) long_rows = true;
         else if (!strcmp(argv[i], "--multigrid") && i + 3 < argc) {
             multigrid = true;
             for (int k = 0; k < 3; ++k) mg_dims[k] = atoi(argv[++i]);
@@ -60,6 +63,10 @@ int main(int argc, char *argv[]) {
     }
     if (amg && (mixed || multigrid)) {
         fprintf(stderr, "--amg goes with neither --mixed (the mixed solve replaces residuals, which the multigrid loop does not serve) nor --multigrid\n");
+        return 1;
+    }
+    if (long_rows && mixed) {
+        fprintf(stderr, "--long-rows does not go with --mixed (cgamd_mixed_create does not take the flag)\n");
         return 1;
     }
     if (nRHS < 1 || nIterations < 0) { fprintf(stderr, "bad nRHS / nIterations\n"); return 1; }
@@ -104,12 +111,12 @@ int main(int argc, char *argv[]) {
                                                    m_status.data(), &m_repl);
         cgamd_mixed_destroy(m);
         if (ctx) cgamd_ctx_destroy(ctx);
-    } else if (!hermitian && !multigrid && !amg) rc = cgamd_cg(dtype, n, nnz, a.data(), b.data(), ptr, cols, x.data(), nRHS, nIterations, hist.data(), device);
+    } else if (!hermitian && !multigrid && !amg && !long_rows) rc = cgamd_cg(dtype, n, nnz, a.data(), b.data(), ptr, cols, x.data(), nRHS, nIterations, hist.data(), device);
     else {      // a handle of its own, created with the flag / given the preconditioner (cgamd_cg has neither): the same upload, solve and download
         cgamd_ctx *ctx = nullptr;
         cgamd_solver *s = nullptr;
         rc = cgamd_ctx_create(device, &ctx);
-        if (rc == CGAMD_OK) rc = cgamd_solver_create(ctx, dtype, n, nnz, a.data(), ptr, cols, nRHS, hermitian ? CGAMD_HERMITIAN : 0, &s);
+        if (rc == CGAMD_OK) rc = cgamd_solver_create(ctx, dtype, n, nnz, a.data(), ptr, cols, nRHS, (hermitian ? CGAMD_HERMITIAN : 0) | (long_rows ? CGAMD_SPLIT_LONG_ROWS : 0), &s);
         if (rc == CGAMD_OK && multigrid) rc = cgamd_solver_set_preconditioner_multigrid(s, mg_dims[0], mg_dims[1], mg_dims[2], 0, 0., 0);
         if (rc == CGAMD_OK && amg) rc = cgamd_solver_set_preconditioner_amg(s, 0, 0., 0, 0., 0);
         if (rc == CGAMD_OK && (multigrid || amg) && !quiet) printf("multigrid: %d levels, %d launches per iteration\n", cgamd_solver_mg_levels(s), cgamd_solver_loop_launches(s));

@@ -590,6 +590,45 @@ static void setup_x_lag(cgamd_solver *s) {
     s->x_lag = lag;
 }
 
+// CGAMD_SPLIT_LONG_ROWS (include/cgamd.h, long_rows.hip): after finalize_spmv_plan.  The flag applies where the plan ended at kind 0
+// on a single system with one right-hand side and 16-byte-aligned aValues / aCols for no other reason than its spans; everywhere else
+// it changes nothing.  The lists live in s->plan.lr (copies of the plan, the multigrid's finest level among them, borrow them)
+static int setup_long_rows(cgamd_solver *s) {
+    const bool had = s->plan.lr.on != 0;
+    free_long_rows(&s->plan.lr);
+    if (had) destroy_graphs(s);
+    if (!(s->flags & CGAMD_SPLIT_LONG_ROWS) || s->nsys || s->nrhs != 1 || s->plan.max_span <= 0) return CGAMD_OK;
+    if (!aligned16(s->vals) || !aligned16(s->cols) || tune().dev_generic_spmv) return CGAMD_OK;
+    const size_t ebytes = dtype_size(s->dtype) + 4;
+    const int knob = tune().dev_long_row_bytes;
+    // dev.long_row_bytes below the chunked form's cap: the handle is planned as if that cap were the knob -- a block form that could
+    // stage the heavy blocks is set aside, so that small test matrices reach the split
+    const bool lowered = knob > 0 && knob < kMaxChunkBytes;
+    if (s->plan.kind != 0 && !(lowered && (s->plan.kind == 5 || s->plan.kind == 7))) return CGAMD_OK;
+    const int heavy_entries = (int)((size_t)(lowered ? knob : kMaxChunkBytes) / ebytes);
+    int seg = tune().dev_long_row_segment > 0 ? tune().dev_long_row_segment : kLongRowSegment;
+    seg = std::min(seg, (int)(kLongRowMaxLds / ebytes));
+    seg = std::max(seg & ~3, 4);
+    LongRows lr;
+    int spans[8];
+    const int cycle = tune().spmv_cycle > 0 ? tune().spmv_cycle : 1;
+    if (int rc = build_long_rows(s->n, s->ptr, s->plan.row_blocks, heavy_entries, seg, dtype_size(s->dtype), cycle, s->ctx->stream, &lr, spans)) return rc;
+    if (lr.n_heavy == 0) return CGAMD_OK;
+    // the body's kernel, chosen from the regular blocks' spans by the rules of every other handle
+    SpmvPlan body = s->plan;
+    body.max_span = spans[0]; body.max_row = spans[7];
+    for (int lv = 0; lv < 5; ++lv) body.chunk_span[lv] = spans[lv + 1];
+    finalize_spmv_plan(&body, s->dtype, 1, s->n, s->nnz, s->vals, s->cols);
+    if (lr.n_regular > 0 && body.kind != 5 && body.kind != 7) { free_long_rows(&lr); return CGAMD_OK; }      // (dev.spmv_chunked = 0: no form for the body)
+    lr.body_kind = lr.n_regular > 0 ? body.kind : 0; lr.body_lpr = body.lpr; lr.body_max_span = body.max_span; lr.body_max_row = body.max_row;
+    for (int lv = 0; lv < 5; ++lv) lr.body_chunk_span[lv] = body.chunk_span[lv];
+    lr.on = 1;
+    s->plan.lr = lr;
+    s->plan.kind = 0; s->plan.lpr = 1; s->plan.wide = false;      // (already so unless dev.long_row_bytes lowered the threshold)
+    s->plan.n_partials = s->plan.row_blocks;      // one d.q partial per 256-row block, from the body and from the combine launch alike
+    return CGAMD_OK;
+}
+
 static int capture(cgamd_solver *s, int k0, int iters, hipGraph_t *g, hipGraphExec_t *ge, bool guarded = false) {
     hipStream_t st = s->ctx->stream;
     hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
@@ -751,6 +790,7 @@ static int create_impl(const std::string &who, cgamd_ctx *ctx, int dtype, int si
         rc = validate_csr_device(size, nnz, size, aPointers, s->cols, nullptr, 0, 0, s->sc.iter, ctx->stream);     // the caller's arrays, as passed
     if (!rc) rc = compute_spmv_plan(s->ptr, s->cols, n_int, s->sc.iter, ctx->stream, &s->plan);
     if (!rc) finalize_spmv_plan(&s->plan, dtype, nRHS, n_int, nnz, s->vals, s->cols);
+    if (!rc && (flags & CGAMD_SPLIT_LONG_ROWS)) rc = setup_long_rows(s);
     if (!rc && s->rm_ok) s->rm_nwg = spmm_rm_grid(dtype, nRHS, size, s->plan.max_quad, true);
     if (!rc && s->rm_ok) rc = dmalloc((void **)&s->rm_pace, sizeof(int) * kSpmmPaceInts, "spmm pace counters");
     if (!rc && s->rm_ok && hipMemsetAsync(s->rm_pace, 0, sizeof(int) * kSpmmPaceInts, ctx->stream) != hipSuccess) rc = fail(CGAMD_ERR_HIP, "hipMemsetAsync(spmm pace counters)");
@@ -841,9 +881,13 @@ int cgamd_solver_reload_matrix(cgamd_solver *s, const void *aValues, const int *
         CG_HIP(hipMemcpyAsync(s->ptr, aPointers, ((size_t)s->n_user + 1) * 4, hipMemcpyHostToDevice, st));
         std::copy(aPointers, aPointers + s->n_user + 1, s->ptr_host.begin());
         destroy_graphs(s);          // kernel choice, LDS size and partial counts are baked into the captured launches
+        const LongRows old_lists = s->plan.lr;      // (the handle's: setup_long_rows frees them and builds the new pattern's)
         s->plan = make_spmv_plan(s->n);
+        s->plan.lr = old_lists;
         if (int rc = compute_spmv_plan(s->ptr, s->cols, s->n, s->sc.iter, st, &s->plan)) return rc;
         finalize_spmv_plan(&s->plan, s->dtype, s->nrhs, s->n, s->nnz, s->vals, s->cols);
+        if (s->flags & CGAMD_SPLIT_LONG_ROWS)
+            if (int rc = setup_long_rows(s)) return rc;
         if ((size_t)std::max(s->plan.grid, s->plan.row_blocks) > s->part_dq_cap) return fail(CGAMD_ERR_STATE, "reload_matrix: partial buffer too small");
         if (s->rm_ok) s->rm_nwg = spmm_rm_grid(s->dtype, s->nrhs, s->n, s->plan.max_quad, true);
         s->fused2 = !s->herm && fused2_ok(s->plan, s->dtype, s->nrhs, s->vals, s->cols);
@@ -969,6 +1013,7 @@ int cgamd_solver_destroy(cgamd_solver *s) {
     destroy_graphs(s);
     drop_multigrid(s);
     proj_free(s);
+    free_long_rows(&s->plan.lr);
     if (s->own_ptr && s->ptr) (void)hipFree(s->ptr);
     if (s->own_matrix) {
         if (s->vals) (void)hipFree(s->vals);
@@ -2023,6 +2068,7 @@ long long cgamd_solver_iter_bytes(cgamd_solver *s, int fused) {
 // passes of the launched loop the handle runs (10 with the deferred x update, 11 without, 12 preconditioned, 14 for the
 // reference's op structure; the tridiagonal M: tri_passes).  Handles whose iterate() runs a resident loop report the launched loop
 // they fall back to.
+static long long long_rows_scratch_traffic(const cgamd_solver *s) { return s->plan.lr.on ? 2LL * (long long)s->plan.lr.scratch_bytes : 0; }
 static long long index_bytes_per_nnz(const cgamd_solver *s) { return s->plan.codes ? (s->plan.codes16 ? 2 : 1) : 4; }
 // the single-RHS SpMV of this handle runs on joint codes (launch condition of spmv_impl: rows that fit one batch of the walk)
 static bool joint_form(const cgamd_solver *s) {
@@ -2036,7 +2082,16 @@ long long cgamd_solver_spmv_moved_bytes(cgamd_solver *s) {
     const long long V = (long long)dtype_size(s->dtype);
     if (row_form(s)) return (long long)s->n_user + 2LL * s->n_user * V;       // one code byte per row, x read, y written: no per-non-zero bytes, no row pointers
     const long long value_bytes = joint_form(s) ? 0 : s->plan.vcodes ? 1 : V * value_arrays(s);      // value codes: one byte per entry instead of the value; joint codes: one byte for both
-    return s->nnz * (value_bytes + index_bytes_per_nnz(s)) + ((long long)s->n_user + 1) * 4 + 2LL * s->n_user * V * s->nrhs;
+    // (CGAMD_SPLIT_LONG_ROWS: the body's bytes and the heavy blocks' entries once are the matrix once; the piece scratch is written and read)
+    return s->nnz * (value_bytes + index_bytes_per_nnz(s)) + ((long long)s->n_user + 1) * 4 + 2LL * s->n_user * V * s->nrhs + long_rows_scratch_traffic(s);
+}
+int cgamd_solver_long_rows(cgamd_solver *s, int *out, int n_out) {
+    if (!s || !out || n_out < 1) return -fail(CGAMD_ERR_INVALID, "solver_long_rows: null or empty output");
+    const LongRows &lr = s->plan.lr;
+    const int f[6] = {lr.on ? lr.n_heavy : 0, lr.on ? lr.n_seg : 0, lr.on ? lr.seg_len : 0, lr.on ? lr.body_kind : 0,
+                      lr.on ? (lr.body_kind == 7 ? lr.body_lpr : lr.body_kind == 5 ? 1 : 0) : 0, lr.on ? (int)lr.scratch_bytes : 0};
+    for (int i = 0; i < n_out && i < 6; ++i) out[i] = f[i];
+    return n_out < 6 ? n_out : 6;
 }
 int cgamd_solver_value_codes(cgamd_solver *s) { return s ? s->n_values : -CGAMD_ERR_INVALID; }
 int cgamd_solver_joint_codes(cgamd_solver *s) { return s ? (joint_form(s) ? s->n_pairs : 0) : -CGAMD_ERR_INVALID; }
@@ -2066,7 +2121,7 @@ long long cgamd_solver_iter_moved_bytes(cgamd_solver *s) {
     const long long passes = s->herm ? (s->mdiag ? 14 : 12) : (s->nsys && s->mdiag) ? 12 : (s->flags & CGAMD_UNFUSED) ? 14 : s->mdiag ? 12 : 10;
     const long long lag = x_lag_now(s);
     const long long value_bytes = joint_form(s) ? 0 : s->plan.vcodes ? 1 : V * value_arrays(s);
-    const long long matrix = row_form(s) ? (long long)s->n_user : s->nnz * (value_bytes + index_bytes_per_nnz(s)) + ((long long)s->n_user + 1) * 4;
+    const long long matrix = (row_form(s) ? (long long)s->n_user : s->nnz * (value_bytes + index_bytes_per_nnz(s)) + ((long long)s->n_user + 1) * 4) + long_rows_scratch_traffic(s);
     if (s->mg) return matrix + mg_bytes(s, cgamd_solver_spmv_moved_bytes(s));
     if (s->tri_on) return matrix + tri_passes(s) * s->n_user * V;
     // the deferred x update: the d steps of a group of L iterations move 4 L + 1 vectors instead of 5 L, the steady state of a

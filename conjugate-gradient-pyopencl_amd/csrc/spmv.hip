@@ -900,8 +900,14 @@ __global__ __launch_bounds__(BLOCK) void spmv_rowblock_chunked_kernel(SpmvArgs<T
     constexpr int RC = BLOCK / LPR;                 // rows per chunk
     const int t = threadIdx.x, j = t / LPR, l = t % LPR;
     if constexpr (CODED == 1) sdict[t] = a.dict[t];      // visible after the first staging barrier
-    const int rb = rowblock_of(blockIdx.x, a.row_blocks, a.cycle);
-    if (rb < 0) return;
+    int rb;
+    if (a.rb_list) {                       // explicit subset (the regular row blocks of a CGAMD_SPLIT_LONG_ROWS handle)
+        if ((int)blockIdx.x >= a.rb_count) return;
+        rb = a.rb_list[blockIdx.x];
+    } else {
+        rb = rowblock_of(blockIdx.x, a.row_blocks, a.cycle);
+        if (rb < 0) return;
+    }
     [[maybe_unused]] const int cbase = CODED == 2 ? a.dict[rb] : 0;
     A dot1 = vzero<A>();
     for (int c = 0; c < LPR; ++c) {
@@ -1241,7 +1247,7 @@ void set_kernel_event_pair(hipEvent_t *pair) { t_kernel_events = pair; }
 
 // cgamd_last_spmv_form: what the calling thread's most recent launch_spmv launched, stored AT the launch sites of spmv_impl (the
 // template arguments of the instance that goes out, not a second reading of the plan), so that a test can assert the form it was
-// written for.  [0] family (0 stream, 1 row-block, 2 vc, 3 vcp, 4 chunked, 5 grouped SpMM, 7 row-pattern codes; -1: nothing launched yet), [1] VEC,
+// written for.  [0] family (0 stream, 1 row-block, 2 vc, 3 vcp, 4 chunked, 5 grouped SpMM, 7 row-pattern codes, 9 split long rows; -1: nothing launched yet), [1] VEC,
 // [2] batch length / lanes per row / group width, [3] index encoding (0 aCols, 8, 16), [4] value encoding (0 aValues, 1 two
 // code streams, 2 joint, 3 one pattern byte per row), [5] NT, [6] fused d.q, [7] wide, [8] grid.x, [9] d.q partials per right-hand side (0 when not fused).
 static thread_local int t_form[kSpmvFormFields] = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -1287,6 +1293,24 @@ static int spmv_impl(const SpmvPlan &plan, int n, long long nnz, const void *val
     const bool fuse = partials != nullptr;
     const size_t dyn = (fuse && nrhs > 1) ? sizeof(typename VT<T>::acc) * nrhs * (kBlock / kWave) : 0;
     dim3 grid(plan.grid), block(kBlock);
+    // CGAMD_SPLIT_LONG_ROWS: the regular blocks by their own kernel on the block list, then the heavy blocks' two launches (long_rows.hip);
+    // a linear chain on `st`.  The form recorded is the split's, with the body's width, index encoding and grid
+    if (plan.lr.on && vec && nrhs == 1 && !rb_list) {
+        const LongRows &lr = plan.lr;
+        int width = 0, ienc = 0;
+        unsigned gx = 0;
+        if (lr.n_regular > 0) {
+            SpmvPlan body = plan;
+            body.lr = LongRows();
+            body.kind = lr.body_kind; body.lpr = lr.body_lpr; body.max_span = lr.body_max_span; body.max_row = lr.body_max_row;
+            for (int lv = 0; lv < 5; ++lv) body.chunk_span[lv] = lr.body_chunk_span[lv];
+            if (int rc = spmv_impl<T>(body, n, nnz, vals, ptr, cols, x, ldx, y, ldy, nrhs, dvec, partials, lr.regular, lr.n_regular, st)) return rc;
+            width = t_form[2]; ienc = t_form[3]; gx = (unsigned)t_form[8];
+        }
+        const bool nt = tune().spmv_nt >= 0 ? (tune().spmv_nt != 0) : (plan.nt != 0);
+        record_form(9, true, width, ienc, 0, nt, fuse, false, gx, plan.row_blocks);
+        return launch_long_rows(VT<T>::dtype, lr, nt, n, nnz, vals, ptr, cols, x, y, dvec, partials, st);
+    }
     const int variant = (vec && ((nrhs == 1 && plan.kind == 5) || (nrhs > 1 && plan.kind == 6 && plan.wide))) ? 5 : 0;
     if (variant == 5) {
         a.cap = (plan.max_span + 3) & ~3;
@@ -1429,7 +1453,8 @@ static int spmv_impl(const SpmvPlan &plan, int n, long long nnz, const void *val
 #undef CG_RB
         return check_launch("spmv_rowblock");
     }
-    if (vec && nrhs == 1 && plan.kind == 7 && !rb_list) {
+    if (vec && nrhs == 1 && plan.kind == 7) {
+        if (rb_list && rb_count <= 0) return CGAMD_OK;
         const int span = plan.chunk_span[plan.lpr == 2 ? 0 : plan.lpr == 4 ? 1 : plan.lpr == 8 ? 2 : plan.lpr == 16 ? 3 : 4];
         a.cap = (span + 3) & ~3;
         a.cycle = tune().spmv_cycle > 0 ? tune().spmv_cycle : 1;
@@ -1439,7 +1464,7 @@ static int spmv_impl(const SpmvPlan &plan, int n, long long nnz, const void *val
         a.dict = coded_any ? plan.dict : nullptr;
         const size_t lds = coded ? (((size_t)a.cap * (sizeof(T) + 1) + 15) & ~(size_t)15)
                                  : coded16 ? (((size_t)a.cap * (sizeof(T) + 2) + 15) & ~(size_t)15) : (size_t)a.cap * (sizeof(T) + 4);
-        const dim3 g7(rowblock_grid(plan.row_blocks, a.cycle));
+        const dim3 g7(rb_list ? rb_count : rowblock_grid(plan.row_blocks, a.cycle));
         const bool nt = tune().spmv_nt >= 0 ? (tune().spmv_nt != 0) : (plan.nt != 0);
         constexpr int U = sizeof(T) > 8 ? 4 : 8;
 #define CG_CH(NT, L)                                                                                                     \
@@ -1623,7 +1648,7 @@ int launch_spmv(int dtype, const SpmvPlan &plan, int n, long long nnz, const voi
                 const int *cols, const void *x, long long ldx, void *y, long long ldy, int nrhs, const void *dvec,
                 void *partials, hipStream_t st, const int *rb_list, int rb_count) {
     if (n <= 0) return CGAMD_OK;
-    if (rb_list && !(plan.kind == 5 && nrhs == 1)) return fail(CGAMD_ERR_INVALID, "spmv: row-block lists need the row-block kernel");
+    if (rb_list && !((plan.kind == 5 || plan.kind == 7) && nrhs == 1)) return fail(CGAMD_ERR_INVALID, "spmv: row-block lists need the row-block kernel");
     CG_DISPATCH(dtype, spmv_impl, plan, n, nnz, vals, ptr, cols, x, ldx, y, ldy, nrhs, dvec, partials, rb_list, rb_count, st);
 }
 

@@ -108,6 +108,10 @@ int cgamd_sub(cgamd_ctx *ctx, int dtype, int size, const void *a, const void *b,
                                     * matrix -- every inner product of the recurrence conjugated, <a, b> = sum conj(a_i) b_i -- in place of
                                     * the reference's unconjugated recurrence (COCG, for complex-symmetric matrices).  See "Hermitian
                                     * systems" below cgamd_solver_hermitian.  Accepted and without effect on the real value types */
+#define CGAMD_SPLIT_LONG_ROWS 1024  /* cgamd_solver_create: cut very long rows across work-groups and keep the block SpMV forms for every
+                                    * other row (csrc/long_rows.hip).  Without it ONE hub row sends the whole matrix to the generic
+                                    * stream kernel.  See "Long rows" below cgamd_solver_long_rows.  Accepted by every create entry and
+                                    * without effect where the split does not apply */
 #define CGAMD_DIST_NO_OVERLAP 32    /* cgamd_dist_create: exchange first, then one SpMV (no interior/boundary overlap) */
 #define CGAMD_DIST_P2P 64            /* cgamd_dist_create: no RCCL; peers write each other's IPC mailboxes (attach_p2p) */
 #define CGAMD_DIST_GRAPH 8         /* cgamd_dist_create: replay each iteration (incl. RCCL ops) from a hipGraph */
@@ -586,7 +590,8 @@ int cgamd_solver_spmv(cgamd_solver *s, const void *x, void *y, int fused_dot);
  * cgamd_last_spmv_form: what the CALLING THREAD's most recent SpMV launch (cgamd_solver_spmv, cgamd_spmv, an iteration's SpMV) really
  * launched, recorded where the kernel is launched.  Writes min(n_out, 10) ints and returns that count (negative: error):
  * [0] family: 0 generic stream, 1 row-block, 2 value-coded (vc), 3 value-coded pipelined (vcp), 4 chunked, 5 grouped SpMM, 6 batched (a matrix per right-hand side:
- * [2] batch length of the row walk, [7] 1 = the any-CSR form that reads the matrix per row), -1 none yet;
+ * [2] batch length of the row walk, [7] 1 = the any-CSR form that reads the matrix per row), 9 split long rows (CGAMD_SPLIT_LONG_ROWS:
+ * [2], [3] and [8] are the body's), -1 none yet;
  * [1] 16-byte loads (VEC); [2] batch length of the row walk / lanes per row (chunked) / right-hand sides per register group (SpMM);
  * [3] index encoding: 0 aCols, 8, 16 bits; [4] value encoding: 0 aValues, 1 code stream of its own, 2 joint (offset, value) codes;
  * [5] non-temporal matrix loads; [6] fused d.q; [7] wide (one work-group per row block AND right-hand side); [8] grid.x;
@@ -693,6 +698,38 @@ long long cgamd_solver_iter_bytes(cgamd_solver *s, int fused);
  * reference's CSR byte model (an "effective" rate). */
 long long cgamd_solver_spmv_moved_bytes(cgamd_solver *s);
 long long cgamd_solver_iter_moved_bytes(cgamd_solver *s);
+
+/* ---- Long rows (CGAMD_SPLIT_LONG_ROWS; csrc/long_rows.hip).  Graph Laplacians with a few high-degree vertices, circuit matrices with
+ * supply nets and grid systems with one coupled unknown have a few rows of thousands to millions of entries.  The plan chooses ONE
+ * kernel per matrix from the largest slice span of any 256-row block, so one such row costs every row the block forms, and the row
+ * itself is walked by one work-group.  With the flag the handle's single-right-hand-side SpMV takes a fourth way:
+ *   HEAVY RULE.  A 256-row block is heavy when any of its 8-row slices (rows 8 k .. 8 k + 7 of the block) spans more than
+ *   48 KB / (sizeof(value) + 4) entries, the span measured from aPointers[first row] rounded down to a multiple of 4 to
+ *   aPointers[last row + 1] -- exactly the blocks that even the chunked form with 32 lanes per row cannot stage.  The rule reads the
+ *   row pointers only.  (cgamd_tune "dev.long_row_bytes" lowers the 48 KB for tests.)
+ *   Every other block runs the row-block or chunked kernel, chosen from THEIR spans by the rules of an unflagged handle, on aCols;
+ *   the rows of those blocks have the bits an unflagged handle of the matrix without the heavy blocks would give them.
+ *   A heavy block's span is cut into segments of 2048 entries ("dev.long_row_segment": another multiple of 4; clamped so that a
+ *   segment's values and columns fit 128 KB), one work-group each; a second launch of one work-group per heavy block completes the
+ *   rows and forms the block's d.q partial.  Nothing of the matrix is copied; no atomics, no spins.
+ *   SUMMATION ORDER of a row of a heavy block: inside each segment the row's entries ("piece") are summed from +0 in stored order by
+ *   one lane when the piece has at most 64 entries (a row that lies inside one segment and is that short has the bits of every
+ *   one-lane form), else by 64 lanes -- lane l adds entries l, l + 64, ... from +0, then v[l] += v[l + off], off = 32, 16, 8, 4, 2, 1,
+ *   lane 0; a row that crosses segment edges is the sum of its pieces in ascending segment order from +0.  All in the value type.
+ *   Results are the same from run to run, with and without hipGraph replay, and however a solve is cut into iterate() calls.
+ * The flag applies to cgamd_solver_create handles with nRHS == 1 whose aValues and aCols are 16-byte aligned and whose plan would
+ * otherwise end at the generic stream kernel because of its spans.  Everywhere else -- batched handles, several right-hand sides,
+ * "dev.generic_spmv" = 1, misaligned borrowed arrays, a matrix without heavy blocks -- it changes nothing, by a bit or by a launch,
+ * and the query reports zeros.  CGAMD_HERMITIAN handles are served.  cgamd_dist_* and cgamd_mixed_* do not take the flag.  Such a
+ * handle runs the launched loops (plain, iterate_until, diagonal / line / multigrid PCG, CGAMD_NO_GRAPH); the resident, chip-wide
+ * and two-launch loops need the one-kernel row-block plan and do not take it, and it builds no column or value codes.
+ * cgamd_solver_refresh_values: the kernels read the values live, the lists depend on the row pointers only and stay.
+ * cgamd_last_spmv_form reports family 9 with [2] the body's batch length or lanes per row, [3] its index encoding, [8] its grid and
+ * [9] one partial per 256-row block.  The byte model prices the matrix once plus the piece scratch written and read.
+ * cgamd_solver_long_rows: writes min(n_out, 6) ints and returns that count (negative: error): [0] heavy blocks, [1] segments,
+ * [2] entries per segment, [3] the body's kind (5 row-block, 7 chunked, 0 no regular block), [4] its lanes per row, [5] scratch bytes;
+ * all 0 where the flag is not set or does not apply. */
+int cgamd_solver_long_rows(cgamd_solver *s, int *out, int n_out);
 
 /* ---- Mixed precision (csrc/mixed.cpp, csrc/mixed.hip): an fp64 / complex128 answer at close to the fp32 / complex64 loop's byte rate.
  * The loops are bound by bytes and most of them are vectors; fp32 alone stalls near 1e-6 ||b||.  Here the recurrence runs in the lo
