@@ -207,6 +207,7 @@ def load():
         "cgamd_dist_enable_resident": (ci, [vp, ll, vp, vp]),
         "cgamd_dist_index_codes": (ci, [vp]),
         "cgamd_dist_loop_launches": (ci, [vp]),
+        "cgamd_dist_slab_plan": (ci, [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ci]),
         "cgamd_dist_comm_ranks": (ci, [vp]),
         # legacy entry, reference clcg.h:3-5
         "cg": (vp, [ci, ci, vp, vp, vp, vp, vp, ci, ci, ci]),

@@ -137,6 +137,7 @@ struct cgamd_dist {
     // slab loop (CGAMD_DIST_RESIDENT, slab.hip): every iteration of an iterate() call in one launch, vectors in registers
     SlabPlan slab, slab_plan_;         // slab: in use (ok); slab_plan_: what create found, waiting for its buffers (peer-to-peer handles)
     int *slab_map = nullptr;            // member starts [G + 1] and granule owners of a non-uniform slab partition
+    std::vector<int> slab_mstart;       // host copy of those member starts (cgamd_dist_slab_plan); empty = uniform members
     void *slab_sync = nullptr, *ds_own[2] = {nullptr, nullptr};     // ds_own: plain buffers of a handle without peers
     void *ds[2] = {nullptr, nullptr};  // where the slab loop publishes d: ds_own, or inside the rank's mailbox allocation
     void **push_dst_dev = nullptr;     // device [2][n_peers]
@@ -1283,6 +1284,7 @@ int cgamd_dist_enable_resident(cgamd_dist *d, long long mailbox_values, const in
             CG_HIP(hipMemcpy(d->slab_map, mstart.data(), mstart.size() * sizeof(int), hipMemcpyHostToDevice));
             CG_HIP(hipMemcpy(d->slab_map + mstart.size(), gmember.data(), gmember.size() * sizeof(int), hipMemcpyHostToDevice));
             sp.mstart = d->slab_map; sp.gmember = d->slab_map + mstart.size(); sp.G = members;
+            d->slab_mstart = mstart;
             if (slab_sync_bytes(members) > sp.sync_bytes) {
                 if (d->slab_sync) { (void)hipFree(d->slab_sync); d->slab_sync = nullptr; }
                 sp.sync_bytes = slab_sync_bytes(members);
@@ -1319,6 +1321,23 @@ int cgamd_dist_loop_launches(cgamd_dist *d) {
     if (d->direct && d->p2p_attached) return 4 + extra;
     if (d->p2p) return (d->peer.empty() ? 5 : 7) + extra;
     return (d->peer.empty() ? 9 : 11) + extra;
+}
+
+// what the slab loop of this handle runs on: reads the plan in force, launches nothing, changes nothing
+int cgamd_dist_slab_plan(cgamd_dist *d, int info[8], int *member_start, int cap) {
+    if (!d || !info) return -CGAMD_ERR_INVALID;
+    for (int i = 0; i < 8; ++i) info[i] = 0;
+    const SlabPlan &sp = d->slab;
+    if (!sp.ok || d->pre_kind) return 0;
+    const bool uniform = sp.mstart == nullptr;
+    info[0] = 1; info[1] = sp.G; info[2] = sp.rows_m; info[3] = sp.nsteps; info[4] = sp.unroll; info[5] = sp.nsteps <= 10 ? 10 : 12;
+    info[6] = (sp.vcodes && sp.vdict && d->tune.value_codes != 0) ? 1 : 0;
+    info[7] = uniform ? 1 : 0;
+    if (member_start && cap >= sp.G + 1) {
+        for (int m = 0; m <= sp.G; ++m)
+            member_start[m] = uniform ? (int)std::min<long long>((long long)m * sp.rows_m, d->n_local) : d->slab_mstart[(size_t)m];
+    }
+    return sp.G + 1;
 }
 
 int cgamd_dist_p2p_error(cgamd_dist *d) {

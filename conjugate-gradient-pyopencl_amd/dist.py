@@ -480,6 +480,22 @@ class DistSolver:
         """stream operations per iteration of the loop this handle runs; 0 = the slab loop (whole calls in one launch)"""
         return int(self._lib.cgamd_dist_loop_launches(self.handle))
 
+    def slab_plan(self):
+        """what the slab loop of this handle runs on (cgamd_dist_slab_plan), as a dict: in_use, members, rows_m and steps of the largest
+        member, unroll (5 / 7 / 8), budget (10 / 12 steps), value_coded, uniform, member_start (the members + 1 starts; [] when the
+        loop is not in use)"""
+        info = (ctypes.c_int * 8)()
+        need = self._lib.cgamd_dist_slab_plan(self.handle, info, None, 0)
+        if need < 0:
+            raise _lib.CgAmdError(-need, "cgamd_dist_slab_plan")
+        starts = (ctypes.c_int * max(need, 1))()
+        if need > 0:
+            assert self._lib.cgamd_dist_slab_plan(self.handle, info, starts, need) == need
+        keys = ("in_use", "members", "rows_m", "steps", "unroll", "budget", "value_coded", "uniform")
+        out = {k: int(v) for k, v in zip(keys, info)}
+        out["member_start"] = [int(v) for v in starts[:need]]
+        return out
+
     def comm_ranks(self):
         """ranks of the RCCL communicator, as RCCL reports them (0: no communicator)"""
         return int(self._lib.cgamd_dist_comm_ranks(self.handle))

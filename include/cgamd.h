@@ -985,6 +985,13 @@ int cgamd_dist_index_codes(cgamd_dist *d);
  * preconditioner set, of the preconditioned loop (the same counts; two more where a stride-1 line sweep takes its long form; with multigrid
  * one more and the launches of the V-cycle) */
 int cgamd_dist_loop_launches(cgamd_dist *d);
+/* What the slab loop (CGAMD_DIST_RESIDENT, csrc/slab.hip) of this handle runs on; reads the plan, launches nothing, changes nothing.
+ * info = {in use (0/1: as cgamd_dist_loop_launches() == 0), members G, rows of the largest member, 512-row steps of the largest member,
+ * row unroll (5 / 7 / 8), register budget in steps (10 / 12), values from one-byte value codes (1) or streamed (0), uniform members
+ * (1) or the unequal ones of a rank with peers (0)}; all zeros when the loop is not in use.  member_start receives the G + 1 member
+ * starts (m * rows_m clipped to n_local when uniform; multiples of 1024, the last one rounded up, otherwise) when cap >= G + 1 and is left
+ * alone otherwise.  Returns G + 1 (the count needed), 0 when the loop is not in use, negative on a null handle or null info. */
+int cgamd_dist_slab_plan(cgamd_dist *d, int info[8], int *member_start, int cap);
 /* number of ranks of the RCCL communicator behind this handle as RCCL itself reports it (ncclCommCount);
  * 0 when the handle has no communicator (peer-to-peer backend, or one rank without peers) */
 int cgamd_dist_comm_ranks(cgamd_dist *d);
