@@ -169,6 +169,12 @@ def load():
         "cgamd_projection_dots": (ci, [vp, ci, ci, ll, ci, ctypes.c_uint, vp, ll, vp, ci, vp]),
         "cgamd_projection_combine": (ci, [vp, ci, ci, ll, ci, ctypes.c_uint, vp, ll, vp, vp, ci, vp, ci]),
         "cgamd_projection_dots_grid": (ci, [ci, ci]),
+        "cgamd_solver_set_shifts": (ci, [vp, vp, ci]),
+        "cgamd_solver_shifts": (ci, [vp]),
+        "cgamd_solver_get_x_shifted": (ci, [vp, ci, vp, ci]),
+        "cgamd_solver_shift_history": (ci, [vp, vp, ci]),
+        "cgamd_solver_shift_scalars": (ci, [vp, ci, vp]),
+        "cgamd_shift_update": (ci, [vp, ci, ci, ll, ci, ci, vp, vp, vp, vp, vp, vp]),
         "cgamd_gen_laplace3d": (ci, [vp, ci, ci, ci, ci, ll, ll, vp, vp, vp, ctypes.POINTER(ll)]),
         "cgamd_gen_poisson2d": (ci, [vp, ci, ci, vp, vp, vp, ctypes.POINTER(ll)]),
         "cgamd_gen_helm_fe_var": (ci, [vp, ci, ci, ctypes.c_double, vp, ctypes.c_double, ci, ci, vp, vp, vp, ctypes.POINTER(ll)]),

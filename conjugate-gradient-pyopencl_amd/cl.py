@@ -398,6 +398,88 @@ class Solver:
                 x0 = np.ascontiguousarray(np.asarray(x0).reshape(-1), dtype=self.dtype)
         check(self._lib.cgamd_solver_set_rhs(self.handle, ptr(b), ptr(x0), int(on_device)))
 
+    # ---- multi-shift CG (include/cgamd.h "Multi-shift CG"): all (A + sigma_j I) x_j = b on the one SpMV of A x = b
+    MAX_SHIFTS = 16
+
+    def _shift_values(self, sigmas):
+        """`sigmas` as the array cgamd_solver_set_shifts takes: 1 ... 16 finite values of the handle's type.  ValueError otherwise,
+        before anything touches the device."""
+        s = np.asarray(sigmas).reshape(-1)
+        if s.size < 1 or s.size > self.MAX_SHIFTS:
+            raise ValueError(f"1 ... {self.MAX_SHIFTS} shifts, got {s.size}")
+        if self.dtype.kind != "c" and np.iscomplexobj(s) and np.any(s.imag != 0):
+            raise ValueError("complex shifts need a complex handle")
+        s = np.ascontiguousarray(s.real if self.dtype.kind != "c" else s, dtype=self.dtype)
+        if not np.all(np.isfinite(s)):
+            raise ValueError("every shift must be finite")
+        return s
+
+    def set_shifts(self, sigmas):
+        """From the next set_rhs on the handle also solves (A + sigma_j I) x_j = b for every sigma_j (cgamd_solver_set_shifts), with
+        the SpMV of the seed system alone; the seed's x and history keep their bits.  None or an empty list removes the shifts.
+        Needs x0 = None and no preconditioner; the shifts are shared by all right-hand sides."""
+        if sigmas is None or np.size(sigmas) == 0:
+            check(self._lib.cgamd_solver_set_shifts(self.handle, None, 0))
+            return
+        s = self._shift_values(sigmas)
+        check(self._lib.cgamd_solver_set_shifts(self.handle, ptr(s), int(s.size)))
+
+    def shifts(self):
+        """number of shifts in force"""
+        got = self._lib.cgamd_solver_shifts(self.handle)
+        if got < 0:
+            check(-got)
+        return got
+
+    def x_shifted(self):
+        """the shifted solutions, shape (shifts, n_rhs, size)"""
+        out = np.empty((max(self.shifts(), 1), self.n_rhs, self.size), dtype=self.dtype)
+        for j in range(self.shifts()):
+            check(self._lib.cgamd_solver_get_x_shifted(self.handle, j, ptr(out[j]), 0))
+        return out[:self.shifts()]
+
+    def shift_history(self):
+        """zeta_k^j, the factor between the residual of shifted system j and the seed's, r_k^j = zeta_k^j r_k, for k = 0..iterations:
+        shape (iterations + 1, shifts, n_rhs).  delta_k^j = zeta_k^j ** 2 * history()[k] (unconjugated, like the history)."""
+        n, S = self.iterations_done() + 1, self.shifts()
+        out = np.empty((n, max(S, 1), self.n_rhs), dtype=self.dtype)
+        got = self._lib.cgamd_solver_shift_history(self.handle, ptr(out), n)
+        if got < 0:
+            check(-got)
+        return out[:got, :S]
+
+    SHIFT_SCALARS = ("theta", "zeta", "alpha", "beta")
+
+    def shift_scalars(self, which):
+        """development entry (cgamd_solver_shift_scalars): the last iteration's theta / zeta (float64 / complex128) or alpha_j / beta_j
+        (the handle's type), shape (shifts, n_rhs)"""
+        idx = self.SHIFT_SCALARS.index(which) if isinstance(which, str) else int(which)
+        acc = np.complex128 if self.dtype.kind == "c" else np.float64
+        out = np.empty((max(self.shifts(), 1), self.n_rhs), dtype=acc if idx < 2 else self.dtype)
+        check(self._lib.cgamd_solver_shift_scalars(self.handle, idx, ptr(out)))
+        return out[:self.shifts()]
+
+    def solve_shifted(self, b, sigmas, iterations=None, tol=None, maxit=1000, check_every=8):
+        """A x = b and (A + sigma_j I) x_j = b in one solve: `iterations` iterations, or with `tol` (a scalar or n_rhs values) until
+        the SEED's sqrt(|r.r|) falls below it, per right-hand side (iterate_until).  For positive shifts of a positive-definite matrix
+        the shifted systems have then converged too; otherwise read shift_history().  Returns (x, xs, its): xs of shape
+        (shifts, n_rhs, size), its the iterations of every right-hand side.  The shifts stay in force."""
+        if (iterations is None) == (tol is None):
+            raise ValueError("give either iterations or tol")
+        if iterations is not None and int(iterations) < 0:
+            raise ValueError("iterations must not be negative")
+        if tol is not None:
+            self._tolerances(tol)
+        sigmas = self._shift_values(sigmas)
+        self.set_shifts(sigmas)
+        self.set_rhs(b, None)
+        if tol is None:
+            self.iterate(int(iterations))
+            its = np.full(self.n_rhs, int(iterations), dtype=np.intc)
+        else:
+            its = self.iterate_until(tol, maxit, check_every)
+        return self.x(), self.x_shifted(), its
+
     # ---- solution projection (include/cgamd.h "Solution projection"): start each solve from the span of the earlier ones
     def enable_projection(self, capacity, drop_tol=0.0):
         """Keep up to `capacity` (1 ... 32) A-orthonormal vectors per right-hand-side column spanning the recent solutions

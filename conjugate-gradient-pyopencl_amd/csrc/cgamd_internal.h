@@ -862,6 +862,26 @@ int launch_proj_decide(int dtype, int nrhs, int slots, unsigned held, unsigned l
 // w_r = e_r * t[r] where added[r], else zeros
 int launch_proj_store(int dtype, int n, const void *e, long long ld, const void *t, const int *added, void *w, int nrhs, hipStream_t st);
 
+// ---- multi-shift CG (shifts.hip): S shifted systems on the seed recurrence.  Scalars per (shift, right-hand side) live at
+// [j * nrhs + r]: the state in the accumulator type, the coefficients of the vector pass and the history in the value type
+constexpr int kShiftMax = 16;
+struct ShiftScalars {
+    int S = 0;
+    const void *sigma = nullptr;                                // acc[S]
+    void *theta = nullptr, *zeta = nullptr;                     // acc[S][nrhs]: zeta_k / zeta_{k-1} and zeta_k
+    void *aprev = nullptr, *bprev = nullptr;                    // acc[S][nrhs]: alpha_{k-1}, beta_{k-1}, a copy per pair (no thread reads another's word)
+    void *alpha_s = nullptr, *beta_s = nullptr, *zeta_s = nullptr;      // T[S][nrhs]: what the vector pass multiplies by
+    void *history = nullptr;                                    // T[cap][S][nrhs]: zeta_k, row 0 all ones
+    int history_cap = 0;
+};
+// theta = zeta = alpha_{-1} = 1, beta_{-1} = 0, history row 0
+int launch_shift_init(int dtype, int nrhs, const ShiftScalars &sh, hipStream_t st);
+// the scalar step of an iteration, from sc.alpha (slot 0), sc.beta and *sc.iter as the d step left them (stop: leaves on live[])
+int launch_shift_scalars(int dtype, int nrhs, const ShiftScalars &sh, const CgScalars &sc, hipStream_t st, const CgStop *stop = nullptr);
+// x_j += alpha_j d_j ; d_j = zeta_j r + beta_j d_j for all S shifts in ONE launch; r: [nrhs][ld], xs / ds: [S][nrhs][ld]
+int launch_shift_update(int dtype, int n, long long ld, int nrhs, int S, const void *r, void *xs, void *ds, const void *alpha_s, const void *beta_s,
+                        const void *zeta_s, hipStream_t st, int vec_nt = 0, const CgStop *stop = nullptr);
+
 }  // namespace cgamd
 
 // ---- what mixed.cpp needs of its two handles beyond the C ABI (solver.cpp) ----

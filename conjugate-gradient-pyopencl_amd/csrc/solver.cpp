@@ -151,7 +151,23 @@ struct cgamd_solver {
         bool projected = false, spent = false;
     } proj;
     int captures = 0;               // graphs captured since creation (cgamd_solver_graph_captures)
+    // multi-shift CG (cgamd_solver_set_shifts; shifts.hip): view.S shifted systems ride on the seed recurrence.  vec = x_j then d_j,
+    // [2][S][nrhs][n] values; scal = sigma, the state and the coefficients behind `view`; view.history = zeta_k, grown with the seed's
+    // history (ensure_history).  While view.S > 0 every set_rhs puts the handle into until_mode: the three / four-launch loop alone,
+    // d in one buffer, x updated in every iteration, and behind its d step the two launches of shifts.hip
+    struct Shifts {
+        ShiftScalars view;
+        void *vec = nullptr, *scal = nullptr;
+    } sh;
 };
+static int nshifts(const cgamd_solver *s) { return s->sh.view.S; }
+static void *shift_xs(const cgamd_solver *s) { return s->sh.vec; }
+static void *shift_ds(const cgamd_solver *s) { return static_cast<char *>(s->sh.vec) + dtype_size(s->dtype) * (size_t)nshifts(s) * s->nrhs * s->n; }
+static void shifts_free(cgamd_solver *s) {
+    for (void *p : {s->sh.vec, s->sh.scal, s->sh.view.history})
+        if (p) (void)hipFree(p);
+    s->sh = cgamd_solver::Shifts();
+}
 
 static void destroy_graphs(cgamd_solver *s) {
     for (int p = 0; p < 2; ++p) {
@@ -256,7 +272,7 @@ static int enqueue_tri_sweep(cgamd_solver *s, bool update, const void *q, void *
 // Deferred x update: the lag the captured U-iteration graphs of this handle run with NOW (1 = none).  s->x_lag is what creation
 // decided and allocated for; the loop family may have changed since (a preconditioner, the row-major layout)
 static int x_lag_now(const cgamd_solver *s) {
-    if (s->x_lag < 2 || s->nsys || s->rm || precond_set(s) || (s->flags & (CGAMD_UNFUSED | CGAMD_NO_GRAPH)) || fused2_now(s)) return 1;
+    if (s->x_lag < 2 || s->nsys || s->rm || precond_set(s) || (s->flags & (CGAMD_UNFUSED | CGAMD_NO_GRAPH)) || fused2_now(s) || nshifts(s)) return 1;
     return s->U % s->x_lag == 0 ? s->x_lag : 1;
 }
 static void *lag_dir(const cgamd_solver *s, int j) {
@@ -293,6 +309,9 @@ static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st, int lag = 1
     int rc;
     if (g && (lag >= 2 || fused2_now(s) || s->rm || (s->flags & CGAMD_UNFUSED)))
         return fail(CGAMD_ERR_STATE, "iterate_until: the loop this handle runs now has no guarded form");
+    // (cgamd_solver_set_shifts and set_rhs see to it; any other loop with shifts in force is an error, never a run without them)
+    if (nshifts(s) && (lag >= 2 || fused2_now(s) || s->rm || s->herm || precond_set(s) || (s->flags & CGAMD_UNFUSED)))
+        return fail(CGAMD_ERR_STATE, "iterate: the loop this handle runs now does not carry the shifted systems");
     if (lag >= 2) return enqueue_lag_iteration(s, k, lag, k % lag, st);
     if (fused2_now(s)) {   // two launches: [beta, d = beta d + r, q = A d, d.q] and [alpha, x += alpha d, r -= alpha q, r.r]
         if ((rc = enqueue_spmv(s, k, st))) return rc;
@@ -344,7 +363,12 @@ static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st, int lag = 1
         if (fold) rc = launch_axpy_dot_alpha(dt, n, s->q, s->r, n, s->part_dq, s->plan.n_partials, s->sc, nr, s->part_rr, s->vgrid, st, g);
         else rc = launch_axpy_dot(dt, n, s->q, s->r, n, s->sc.alpha, nr, s->part_rr, s->vgrid, st, s->plan.vec_nt, g);
         if (rc) return rc;
-        return launch_aypx_beta_x(dt, n, s->r, s->d, s->x, n, s->part_rr, s->vgrid, nr, s->sc, st, s->plan.vec_nt, g);
+        if ((rc = launch_aypx_beta_x(dt, n, s->r, s->d, s->x, n, s->part_rr, s->vgrid, nr, s->sc, st, s->plan.vec_nt, g))) return rc;
+        if (!nshifts(s)) return CGAMD_OK;
+        // the shifted systems, from alpha, beta and r_{k+1} as the seed's launches left them: the scalar step, then ONE vector launch
+        const ShiftScalars &sh = s->sh.view;
+        if ((rc = launch_shift_scalars(dt, nr, sh, s->sc, st, g))) return rc;
+        return launch_shift_update(dt, n, n, nr, sh.S, s->r, shift_xs(s), shift_ds(s), sh.alpha_s, sh.beta_s, sh.zeta_s, st, s->plan.vec_nt, g);
     }
     if ((rc = enqueue_spmv(s, k, st))) return rc;
     if ((rc = launch_dot_partials(dt, n, s->d, s->q, n, nr, s->part_rr, s->vgrid, st))) return rc;
@@ -646,8 +670,27 @@ static int capture(cgamd_solver *s, int k0, int iters, hipGraph_t *g, hipGraphEx
     return CGAMD_OK;
 }
 
+// the shift history (zeta_k per shift and right-hand side) holds as many rows as the seed's history
+static int ensure_shift_history(cgamd_solver *s, int cap) {
+    ShiftScalars &sh = s->sh.view;
+    if (!sh.S || cap <= sh.history_cap) return CGAMD_OK;
+    const size_t row = dtype_size(s->dtype) * (size_t)sh.S * s->nrhs;
+    void *nh = nullptr;
+    if (int rc = dmalloc(&nh, (size_t)cap * row, "shift history")) return rc;
+    if (sh.history) {
+        CG_HIP(hipStreamSynchronize(s->ctx->stream));
+        CG_HIP(hipMemcpyAsync(nh, sh.history, (size_t)sh.history_cap * row, hipMemcpyDeviceToDevice, s->ctx->stream));
+        CG_HIP(hipStreamSynchronize(s->ctx->stream));
+        CG_HIP(hipFree(sh.history));
+    }
+    sh.history = nh;
+    sh.history_cap = cap;
+    destroy_graphs(s);  // (as below)
+    return CGAMD_OK;
+}
+
 static int ensure_history(cgamd_solver *s, int entries) {
-    if (entries <= s->sc.history_cap) return CGAMD_OK;
+    if (entries <= s->sc.history_cap) return ensure_shift_history(s, s->sc.history_cap);
     int cap = std::max(entries, std::max(1024, s->sc.history_cap * 2));
     const size_t vs = dtype_size(s->dtype);
     void *nh = nullptr;
@@ -663,7 +706,7 @@ static int ensure_history(cgamd_solver *s, int entries) {
     s->sc.history = nh;
     s->sc.history_cap = cap;
     destroy_graphs(s);  // history pointer / capacity are baked into captured kernel arguments
-    return CGAMD_OK;
+    return ensure_shift_history(s, cap);
 }
 
 // What a batched handle's plan holds once the pattern is known: one d.q partial per 256-row block whichever kernel of batched.hip
@@ -840,6 +883,12 @@ static int batched_refuses(const char *who) {
 static int herm_refuses(const char *who, const char *why) {
     return fail(CGAMD_ERR_STATE, std::string(who) + ": the handle runs the conjugated recurrence (CGAMD_HERMITIAN), " + why);
 }
+// with shifts in force (cgamd_solver_set_shifts) the handle serves the unpreconditioned recurrence from x0 = 0 alone: a preconditioned
+// operator is not a shift of anything.  Refused before anything on the handle changes
+static int shifts_refuse(const cgamd_solver *s, const char *who) {
+    if (!s->sh.view.S) return CGAMD_OK;
+    return fail(CGAMD_ERR_STATE, std::string(who) + ": shifts are in force (cgamd_solver_set_shifts), which this entry does not serve; remove them first");
+}
 constexpr const char *kHermNoLines = "whose preconditioner is diagonal: the line sweeps form the unconjugated r.z and r.r";
 static int line_from_matrix(cgamd_solver *s, const std::string &who, int stride);
 static int jacobi_from_matrix(cgamd_solver *s, const std::string &who);
@@ -1013,6 +1062,7 @@ int cgamd_solver_destroy(cgamd_solver *s) {
     destroy_graphs(s);
     drop_multigrid(s);
     proj_free(s);
+    shifts_free(s);
     free_long_rows(&s->plan.lr);
     if (s->own_ptr && s->ptr) (void)hipFree(s->ptr);
     if (s->own_matrix) {
@@ -1041,8 +1091,10 @@ static int set_rhs_impl(cgamd_solver *s, const void *b, const void *x0, int on_d
     const bool rm = s->rm_ok && !precond_set(s);      // the preconditioned recurrence keeps the RHS-major kernels
     if (rm && (!b || ldb != s->n_user)) return fail(CGAMD_ERR_STATE, "the handle keeps its right-hand sides interleaved (row-major layout)");
     if (rm != s->rm) destroy_graphs(s);         // captured launch sequences belong to one layout
-    if (s->until_mode && s->fused2) destroy_graphs(s);      // (captured while the two-launch loop was set aside: iterate_until)
-    s->until_mode = s->until_stopped = s->stop.armed = false;
+    // (captured while the two-launch loop was set aside: iterate_until; with shifts in force it stays set aside)
+    if (s->until_mode && s->fused2 && !nshifts(s)) destroy_graphs(s);
+    s->until_mode = nshifts(s) > 0;
+    s->until_stopped = s->stop.armed = false;
     s->proj.projected = s->proj.spent = false;      // (cgamd_solver_set_rhs_projected sets its mark after this call)
     s->rm = rm;
     int rc;
@@ -1101,6 +1153,13 @@ static int set_rhs_impl(cgamd_solver *s, const void *b, const void *x0, int on_d
         CG_HIP(hipMemcpyAsync(s->d, s->r, vbytes, hipMemcpyDeviceToDevice, st));
         if ((rc = launch_dot_partials(s->dtype, s->n, s->r, s->r, s->n, s->nrhs, s->part_rr, s->vgrid, st))) return rc;
         if ((rc = launch_cg_delta0(s->dtype, s->part_rr, s->vgrid, s->nrhs, s->sc, st))) return rc;
+        if (nshifts(s)) {   // x_j = 0, d_j = r_0 = b (x0 = 0), theta = zeta = 1: every shifted system starts where the seed does
+            const size_t sbytes = vbytes * (size_t)nshifts(s);
+            CG_HIP(hipMemsetAsync(shift_xs(s), 0, sbytes, st));
+            for (int j = 0; j < nshifts(s); ++j)
+                CG_HIP(hipMemcpyAsync(static_cast<char *>(shift_ds(s)) + (size_t)j * vbytes, s->r, vbytes, hipMemcpyDeviceToDevice, st));
+            if ((rc = launch_shift_init(s->dtype, s->nrhs, s->sh.view, st))) return rc;
+        }
     }
     if (!on_device) CG_HIP(hipStreamSynchronize(st));  // host buffers may be released by the caller
     s->rhs_set = true;
@@ -1109,6 +1168,7 @@ static int set_rhs_impl(cgamd_solver *s, const void *b, const void *x0, int on_d
 }
 int cgamd_solver_set_rhs(cgamd_solver *s, const void *b, const void *x0, int on_device) {
     if (!s || !b) return fail(CGAMD_ERR_INVALID, "set_rhs: null argument");
+    if (nshifts(s) && x0) return fail(CGAMD_ERR_INVALID, "set_rhs: shifts are in force (cgamd_solver_set_shifts), and the shifted systems share a Krylov space with the seed only from x0 = 0: pass x0 = NULL");
     return set_rhs_impl(s, b, x0, on_device, s->n_user);
 }
 
@@ -1127,6 +1187,8 @@ static void drop_tridiag(cgamd_solver *s) {
 int cgamd_solver_set_preconditioner(cgamd_solver *s, const void *m, int on_device) {
     if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner: solver is NULL");
     if (s->nsys && m) return batched_refuses("set_preconditioner");
+    if (m)      // (removal stays served)
+        if (int rc = shifts_refuse(s, "set_preconditioner")) return rc;
     if (s->nsys && !precond_set(s)) return CGAMD_OK;      // there is none to remove
     TuneScope ts(&s->tune);       // (m == NULL also removes the per-system preconditioner of a batched handle)
     return diag_impl(s, m, on_device);
@@ -1219,6 +1281,7 @@ int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, 
     if (!s || !lower || !diag || !upper) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag: null argument");
     if (s->nsys) return batched_refuses("set_preconditioner_tridiag");
     if (s->herm) return herm_refuses("set_preconditioner_tridiag", kHermNoLines);
+    if (int rc = shifts_refuse(s, "set_preconditioner_tridiag")) return rc;
     TuneScope ts(&s->tune);
     return tridiag_strided_impl(s, "set_preconditioner_tridiag", 1, lower, diag, upper, on_device);
 }
@@ -1228,6 +1291,7 @@ int cgamd_solver_set_preconditioner_tridiag_strided(cgamd_solver *s, int stride,
     if (!s || !lower || !diag || !upper) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag_strided: null argument");
     if (s->nsys) return batched_refuses("set_preconditioner_tridiag_strided");
     if (s->herm) return herm_refuses("set_preconditioner_tridiag_strided", kHermNoLines);
+    if (int rc = shifts_refuse(s, "set_preconditioner_tridiag_strided")) return rc;
     if (stride < 1 || stride >= s->n_user)
         return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag_strided: stride must be in [1, size - 1]");
     TuneScope ts(&s->tune);
@@ -1254,6 +1318,7 @@ int cgamd_solver_set_preconditioner_line(cgamd_solver *s, int stride) {
     if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner_line: solver is NULL");
     if (s->nsys) return batched_refuses("set_preconditioner_line");
     if (s->herm) return herm_refuses("set_preconditioner_line", kHermNoLines);
+    if (int rc = shifts_refuse(s, "set_preconditioner_line")) return rc;
     if (stride < 1 || stride >= s->n_user) return fail(CGAMD_ERR_INVALID, "set_preconditioner_line: stride must be in [1, size - 1]");
     TuneScope ts(&s->tune);
     return line_from_matrix(s, "set_preconditioner_line", stride);
@@ -1276,6 +1341,7 @@ static int jacobi_from_matrix(cgamd_solver *s, const std::string &who) {
 int cgamd_solver_set_preconditioner_jacobi(cgamd_solver *s) {
     if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner_jacobi: solver is NULL");
     if (s->nsys) return batched_refuses("set_preconditioner_jacobi");
+    if (int rc = shifts_refuse(s, "set_preconditioner_jacobi")) return rc;
     TuneScope ts(&s->tune);
     return jacobi_from_matrix(s, "set_preconditioner_jacobi");
 }
@@ -1309,6 +1375,7 @@ int cgamd_solver_set_preconditioner_multigrid(cgamd_solver *s, int nx, int ny, i
     if (!s) return fail(CGAMD_ERR_INVALID, who + ": solver is NULL");
     if (s->nsys) return batched_refuses("set_preconditioner_multigrid");
     if (s->herm) return herm_refuses("set_preconditioner_multigrid", "which the V-cycle does not serve");
+    if (int rc = shifts_refuse(s, "set_preconditioner_multigrid")) return rc;
     if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, who + ": CGAMD_UNFUSED replays the reference's kernel sequence");
     if (s->rm_ok) return fail(CGAMD_ERR_STATE, who + ": the handle keeps its right-hand sides interleaved (row-major layout)");
     if (nx < 1 || ny < 1 || nz < 1) return fail(CGAMD_ERR_INVALID, who + ": every grid dimension must be at least 1");
@@ -1332,6 +1399,7 @@ int cgamd_solver_set_preconditioner_amg(cgamd_solver *s, int passes, double stre
     if (!s) return fail(CGAMD_ERR_INVALID, who + ": solver is NULL");
     if (s->nsys) return batched_refuses("set_preconditioner_amg");
     if (s->herm) return herm_refuses("set_preconditioner_amg", "which the V-cycle does not serve");
+    if (int rc = shifts_refuse(s, "set_preconditioner_amg")) return rc;
     if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, who + ": CGAMD_UNFUSED replays the reference's kernel sequence");
     if (s->rm_ok) return fail(CGAMD_ERR_STATE, who + ": the handle keeps its right-hand sides interleaved (row-major layout)");
     if (passes < 0 || passes > 3) return fail(CGAMD_ERR_INVALID, who + ": passes must be in 0 ... 3 (0 = the default, 3)");
@@ -1620,6 +1688,7 @@ int cgamd_solver_iterate_tol(cgamd_solver *s, int maxIterations, double tol, int
     if (!(tol > 0.) || maxIterations < 0) return fail(CGAMD_ERR_INVALID, "iterate_tol: tol must be positive, maxIterations >= 0");
     if (s->nsys) return fail(CGAMD_ERR_STATE, "iterate_tol: a batched handle runs a launched loop (check the history from the host)");
     if (s->herm) return herm_refuses("iterate_tol", "which has no resident loop: use cgamd_solver_iterate_until");
+    if (int rc = shifts_refuse(s, "iterate_tol")) return rc;
     if (!s->rhs_set) return fail(CGAMD_ERR_STATE, "iterate_tol: call set_rhs first");
     if (s->nrhs != 1) return fail(CGAMD_ERR_STATE, "iterate_tol: one right-hand side");
     if (s->until_mode) return fail(CGAMD_ERR_STATE, "iterate_tol: iterate_until runs this right-hand side on the launched loop until the next set_rhs");
@@ -1679,6 +1748,7 @@ static int replace_refuses(const cgamd_solver *s, bool planned) {
 static int replace_residual_impl(cgamd_solver *s, const void *r_new, long long ldr) {
     TuneScope ts(&s->tune);
     if (int rc = replace_refuses(s, false)) return rc;
+    if (int rc = shifts_refuse(s, "replace_residual")) return rc;
     if (s->proj.spent) return fail(CGAMD_ERR_STATE, std::string("replace_residual") + kProjSpent);
     CG_HIP(hipSetDevice(s->ctx->device));
     if (int rc = step_not_capturing(s, "replace_residual")) return rc;
@@ -2015,6 +2085,8 @@ int cgamd_solver_loop_launches(cgamd_solver *s) {
     if (s->flags & CGAMD_UNFUSED) return 8;
     if (s->rm) return 5;
     if (s->mdiag) return (s->resw.ok && !s->rm && !(s->flags & (CGAMD_NO_GRAPH | CGAMD_UNFUSED))) ? 1 : 4;
+    // shifts in force: the three / four-launch loop, then the shift scalar step and ONE vector launch whatever the number of shifts
+    if (nshifts(s)) return (fold_alpha_ok(s->plan.n_partials, s->plan.fold_max) ? 3 : 4) + 2;
     if (fused2_now(s) && s->res_ok && !(s->flags & CGAMD_NO_GRAPH)) return 0;
     if (s->resw.ok && !(s->flags & CGAMD_NO_GRAPH)) return 1;       // chip-wide resident group (same bits as the launched loops of this handle)
     if (fused2_now(s)) return 2;
@@ -2047,6 +2119,8 @@ static long long mg_bytes(const cgamd_solver *s, long long spmv_bytes) {
     const MgCost c = mg_cost(s->mg);
     return 12LL * s->n_user * (long long)dtype_size(s->dtype) * s->nrhs + c.spmv0 * spmv_bytes + c.bytes;
 }
+// the shift vector launch: r read once, x_j and d_j of every shift read and written
+static long long shift_bytes(const cgamd_solver *s) { return nshifts(s) ? (4LL * nshifts(s) + 1) * s->n_user * (long long)dtype_size(s->dtype) * s->nrhs : 0; }
 static long long tri_passes(const cgamd_solver *s) {
     const long long f = value_arrays(s);
     if (s->tri.stride > 1) return 14LL * s->nrhs + 3 * f;
@@ -2060,7 +2134,7 @@ long long cgamd_solver_iter_bytes(cgamd_solver *s, int fused) {
     // the conjugated recurrence: the launched loop's 10 passes (12 with a diagonal M) and conj(d), written by the d step and read by the SpMV's dot
     if (s->herm) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + (s->mdiag ? 14LL : 12LL) * s->n_user * V * s->nrhs;
     if (s->nsys && s->mdiag) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + 12LL * s->n_user * V * s->nrhs;
-    return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + (fused ? 11LL : 14LL) * s->n_user * V * s->nrhs;
+    return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + (fused ? 11LL : 14LL) * s->n_user * V * s->nrhs + shift_bytes(s);
 }
 
 // What the handle's own kernels MOVE (the physical byte model the roofline fraction is priced on): index bytes per non-zero as
@@ -2127,7 +2201,7 @@ long long cgamd_solver_iter_moved_bytes(cgamd_solver *s) {
     // the deferred x update: the d steps of a group of L iterations move 4 L + 1 vectors instead of 5 L, the steady state of a
     // handle iterated in multiples of U: (9 L + 1) / L passes per iteration
     if (lag >= 2) return matrix + (9 * lag + 1) * s->n_user * V * s->nrhs / lag;
-    return matrix + passes * s->n_user * V * s->nrhs;
+    return matrix + passes * s->n_user * V * s->nrhs + shift_bytes(s);
 }
 
 
@@ -2207,6 +2281,7 @@ int cgamd_solver_set_rhs_projected(cgamd_solver *s, const void *b, int on_device
     if (!s || !b) return fail(CGAMD_ERR_INVALID, "set_rhs_projected: null argument");
     TuneScope ts(&s->tune);
     if (int rc = proj_entry(s, "set_rhs_projected")) return rc;
+    if (int rc = shifts_refuse(s, "set_rhs_projected")) return rc;      // (the shifted systems start from x0 = 0)
     if (!s->proj.cap) return fail(CGAMD_ERR_STATE, "set_rhs_projected: call cgamd_solver_projection_enable first");
     if (int rc = proj_refuses(s, "set_rhs_projected")) return rc;
     hipStream_t st = s->ctx->stream;
@@ -2302,6 +2377,127 @@ int cgamd_solver_projection_state(cgamd_solver *s, int which, int slot, void *ou
     default: return fail(CGAMD_ERR_INVALID, "projection_state: which is 0 .. 4");
     }
     CG_HIP(hipStreamSynchronize(st));
+    return CGAMD_OK;
+}
+
+// ---- multi-shift CG (include/cgamd.h "Multi-shift CG"; kernels: shifts.hip) ------------------------------------------------------
+// what every entry checks first: the handle, no capture in progress
+static int shift_entry(cgamd_solver *s, const char *who) {
+    if (!s) return fail(CGAMD_ERR_INVALID, std::string(who) + ": solver is NULL");
+    thread_hip_setup();
+    CG_HIP(hipSetDevice(s->ctx->device));
+    return step_not_capturing(s, who);
+}
+
+int cgamd_solver_set_shifts(cgamd_solver *s, const void *sigma, int nShifts) {
+    const std::string who = "set_shifts";
+    if (int rc = shift_entry(s, "set_shifts")) return rc;
+    if (nShifts < 0 || nShifts > kShiftMax) return fail(CGAMD_ERR_INVALID, who + ": nShifts runs 0 ... 16");
+    TuneScope ts(&s->tune);
+    hipStream_t st = s->ctx->stream;
+    if (!sigma || nShifts == 0) {       // removal: the next set_rhs starts a handle that never had shifts
+        if (!nshifts(s)) return CGAMD_OK;
+        CG_HIP(hipStreamSynchronize(st));
+        shifts_free(s);
+        destroy_graphs(s);
+        s->rhs_set = false;
+        s->until_mode = s->until_stopped = false;       // (the loop the shifts asked for; set_rhs decides anew)
+        return CGAMD_OK;
+    }
+    if (s->nsys) return fail(CGAMD_ERR_STATE, who + ": the handle is batched (a matrix of its own per right-hand side)");
+    if (s->herm) return herm_refuses("set_shifts", "which the shifted recurrence does not serve yet");
+    if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, who + ": CGAMD_UNFUSED replays the reference's kernel sequence");
+    if (s->rm_ok) return fail(CGAMD_ERR_STATE, who + ": the handle keeps its right-hand sides interleaved (row-major layout)");
+    if (precond_set(s)) return fail(CGAMD_ERR_STATE, who + ": a preconditioner is in force, and a preconditioned operator is not a shift of anything; remove it first");
+    // sigma in the accumulator type, as the scalar step reads it
+    const bool cplx = s->dtype == CGAMD_C64 || s->dtype == CGAMD_C128, single = s->dtype == CGAMD_F32 || s->dtype == CGAMD_C64;
+    const int parts = cplx ? 2 : 1;
+    std::vector<double> sig((size_t)nShifts * parts);
+    for (size_t i = 0; i < sig.size(); ++i) {
+        sig[i] = single ? (double)static_cast<const float *>(sigma)[i] : static_cast<const double *>(sigma)[i];
+        if (!std::isfinite(sig[i])) return fail(CGAMD_ERR_INVALID, who + ": shift " + std::to_string(i / parts) + " is not finite");
+    }
+    // everything is allocated before the handle changes
+    const int nr = s->nrhs;
+    const size_t vs = dtype_size(s->dtype), as = acc_size(s->dtype), pairs = (size_t)nShifts * nr;
+    const size_t scal_bytes = as * (size_t)nShifts + 4 * as * pairs + 3 * vs * pairs;
+    cgamd_solver::Shifts nw;
+    int rc = dmalloc(&nw.vec, 2 * pairs * (size_t)s->n * vs, "shifted solutions and directions");
+    if (!rc) rc = dmalloc(&nw.scal, scal_bytes, "shift scalars");
+    if (!rc) rc = dmalloc(&nw.view.history, (size_t)s->sc.history_cap * pairs * vs, "shift history");
+    hipError_t e = hipSuccess;
+    if (!rc) e = hipMemcpyAsync(nw.scal, sig.data(), as * (size_t)nShifts, hipMemcpyHostToDevice, st);
+    if (!rc && e == hipSuccess) e = hipStreamSynchronize(st);       // (sig goes away; work of the old shifts has drained)
+    if (!rc && e != hipSuccess) rc = fail(CGAMD_ERR_HIP, who + ": " + hipGetErrorString(e));
+    if (rc) {
+        for (void *p : {nw.vec, nw.scal, nw.view.history})
+            if (p) (void)hipFree(p);
+        return rc;
+    }
+    char *p = static_cast<char *>(nw.scal);
+    ShiftScalars &v = nw.view;
+    v.S = nShifts;
+    v.history_cap = s->sc.history_cap;
+    v.sigma = p; p += as * (size_t)nShifts;
+    v.theta = p; p += as * pairs;
+    v.zeta = p; p += as * pairs;
+    v.aprev = p; p += as * pairs;
+    v.bprev = p; p += as * pairs;
+    v.alpha_s = p; p += vs * pairs;
+    v.beta_s = p; p += vs * pairs;
+    v.zeta_s = p;
+    shifts_free(s);
+    s->sh = nw;
+    destroy_graphs(s);      // another loop from the next set_rhs on
+    s->rhs_set = false;
+    return CGAMD_OK;
+}
+
+int cgamd_solver_shifts(cgamd_solver *s) { return s ? nshifts(s) : -CGAMD_ERR_INVALID; }
+
+// what the entries below ask for: shifts in force and a right-hand side they have started from
+static int shifts_running(cgamd_solver *s, const std::string &who) {
+    if (!nshifts(s)) return fail(CGAMD_ERR_STATE, who + ": no shifts are in force (cgamd_solver_set_shifts)");
+    if (!s->rhs_set) return fail(CGAMD_ERR_STATE, who + ": call set_rhs first");
+    return CGAMD_OK;
+}
+
+int cgamd_solver_get_x_shifted(cgamd_solver *s, int j, void *x, int on_device) {
+    if (int rc = shift_entry(s, "get_x_shifted")) return rc;
+    if (!x) return fail(CGAMD_ERR_INVALID, "get_x_shifted: x is NULL");
+    if (int rc = shifts_running(s, "get_x_shifted")) return rc;
+    if (j < 0 || j >= nshifts(s)) return fail(CGAMD_ERR_INVALID, "get_x_shifted: j runs 0 ... shifts - 1");
+    const size_t vs = dtype_size(s->dtype), row = (size_t)s->n_user * vs;
+    const char *src = static_cast<const char *>(shift_xs(s)) + (size_t)j * s->nrhs * s->n * vs;
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    CG_HIP(hipMemcpy2DAsync(x, row, src, (size_t)s->n * vs, row, (size_t)s->nrhs, kind, s->ctx->stream));
+    if (!on_device) CG_HIP(hipStreamSynchronize(s->ctx->stream));
+    return CGAMD_OK;
+}
+
+int cgamd_solver_shift_history(cgamd_solver *s, void *out, int max_entries) {
+    if (int rc = shift_entry(s, "shift_history")) return -rc;
+    if (!out) return -fail(CGAMD_ERR_INVALID, "shift_history: out is NULL");
+    if (int rc = shifts_running(s, "shift_history")) return -rc;
+    const ShiftScalars &v = s->sh.view;
+    const int entries = std::max(0, std::min(std::min(s->iters + 1, v.history_cap), max_entries));
+    hipError_t e = hipMemcpyAsync(out, v.history, (size_t)entries * v.S * s->nrhs * dtype_size(s->dtype), hipMemcpyDeviceToHost, s->ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->ctx->stream);
+    if (e != hipSuccess) return -fail(CGAMD_ERR_HIP, std::string("shift_history: ") + hipGetErrorString(e));
+    return entries;
+}
+
+// which: 0 theta, 1 zeta (double / complex double), 2 alpha_j, 3 beta_j (value type); shifts x nRHS values at [j * nRHS + r]
+int cgamd_solver_shift_scalars(cgamd_solver *s, int which, void *out_host) {
+    if (int rc = shift_entry(s, "shift_scalars")) return rc;
+    if (!out_host) return fail(CGAMD_ERR_INVALID, "shift_scalars: out_host is NULL");
+    if (int rc = shifts_running(s, "shift_scalars")) return rc;
+    const ShiftScalars &v = s->sh.view;
+    if (which < 0 || which > 3) return fail(CGAMD_ERR_INVALID, "shift_scalars: which is 0 .. 3");
+    const void *src = which == 0 ? v.theta : which == 1 ? v.zeta : which == 2 ? v.alpha_s : v.beta_s;
+    const size_t each = which < 2 ? acc_size(s->dtype) : dtype_size(s->dtype);
+    CG_HIP(hipMemcpyAsync(out_host, src, each * (size_t)v.S * s->nrhs, hipMemcpyDeviceToHost, s->ctx->stream));
+    CG_HIP(hipStreamSynchronize(s->ctx->stream));
     return CGAMD_OK;
 }
 

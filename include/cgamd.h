@@ -1073,6 +1073,65 @@ int cgamd_projection_combine(cgamd_ctx *ctx, int dtype, int size, long long ld, 
                              const void *W, long long slot_pitch, const void *v, const void *c, int sign, void *y, int nRHS);
 int cgamd_projection_dots_grid(int dtype, int size);
 
+/* ---- Multi-shift CG: all (A + sigma_j I) x_j = b, j < S, on ONE SpMV per iteration (csrc/shifts.hip; Frommer and Maass, "Fast
+ * CG-based methods for Tikhonov-Phillips regularization", 1999; Jegerlehner, "Krylov space solvers for shifted linear systems", 1996).
+ * The Krylov spaces of the shifted systems are the seed's, and from x0 = 0 their residuals are multiples of the seed's residual,
+ * r_k^j = zeta_k^j r_k.  So the handle runs its recurrence for A x = b unchanged -- the seed's x and history keep their bits -- and
+ * every shift costs a few scalar operations and one pass over its own x_j and d_j.  The recurrence is algebraic in alpha_k and
+ * beta_k: it serves the unconjugated recurrence on complex-symmetric matrices, with complex shifts.
+ *   State per (shift j, right-hand side r): theta (= zeta_k / zeta_{k-1}), zeta, x_j, d_j.  At cgamd_solver_set_rhs: theta = zeta = 1,
+ *   x_j = 0, d_j = r_0 = b; alpha_{-1} = 1, beta_{-1} = 0.  In iteration k, once alpha_k, beta_k and r_{k+1} exist:
+ *     theta' = alpha_{k-1} / (alpha_k beta_{k-1} (1 - theta) + alpha_{k-1} (1 + sigma_j alpha_k))
+ *     zeta'  = zeta theta' ;  alpha_j = alpha_k theta' ;  beta_j = beta_k theta' theta'
+ *     x_j = x_j + alpha_j d_j ;  d_j = zeta' r_{k+1} + beta_j d_j
+ *   This is the RATIO form: zeta underflows to 0 for a well-shifted system (sigma = 6 on a 200 x 200 Laplacian: exactly 0 after 900
+ *   iterations), where the three-zeta form of the literature divides 0 / 0; here zeta = 0 only switches the r term off.
+ *   Scalars: theta, zeta and the products in double / complex double (complex division by Smith's algorithm), from alpha_k and beta_k
+ *   as the loop stores them in the value type; alpha_j, beta_j and zeta' are each rounded once to the value type.  Vectors: in the
+ *   value type, one rounding per operation, x_j = x_j + (alpha_j * d_j), d_j = (zeta' * r) + (beta_j * d_j).
+ *   LOOP: from set_rhs on, a handle with shifts in force runs the three / four-launch loop cgamd_solver_iterate_until runs (d in one
+ *   buffer, x updated in every iteration; no two-launch, resident or deferred-x loop -- their bits are the same), and behind its d
+ *   step the shift scalar step and ONE vector launch for all shifts: cgamd_solver_loop_launches() is that loop's count plus 2,
+ *   whatever nShifts.  Captured graphs and CGAMD_NO_GRAPH give the same bits.
+ *   cgamd_solver_iterate_until is served: the stop rule is unchanged (the SEED's delta_k per right-hand side), and a frozen
+ *   right-hand side keeps, for every shift, the bits of cgamd_solver_iterate(its_r).  For positive shifts of a positive-definite
+ *   matrix |zeta| <= 1 and the shifted systems have converged whenever the seed has; for other shifts read the shift history.
+ * cgamd_solver_set_shifts: sigma = nShifts values of the handle's type in HOST memory, shared by all right-hand sides; nShifts
+ *   1 ... 16; sigma == NULL or nShifts == 0 removes the shifts, and the handle then returns the bits of one that never had any.  Takes
+ *   effect at the next cgamd_solver_set_rhs (which the next solve must start with).  Allocates 2 nShifts nRHS ld values
+ *   (ld = cgamd_solver_ld), freed on removal and destroy.  A failed call leaves the handle unchanged.
+ * cgamd_solver_shifts: shifts in force, 0 = none, negative on error.
+ * cgamd_solver_get_x_shifted: x_j like cgamd_solver_get_x, nRHS x size values at the caller's stride `size`.
+ * cgamd_solver_shift_history: entry k = zeta_k^j of every (j, r) in the value type, layout [k][j][r], k = 0 ... iterations done, row 0
+ *   all ones; synchronises and returns the entries written (negative on error).  The residual of shifted system j is zeta_k^j r_k, so
+ *   its delta_k^j = (zeta_k^j)^2 delta_k with delta_k of cgamd_solver_history -- unconjugated, like it.  A right-hand side frozen by
+ *   cgamd_solver_iterate_until repeats its last entry.
+ * Contract.  Served: single-system handles with RHS-major vectors, all four value types, any nRHS, CGAMD_NO_GRAPH,
+ *   CGAMD_MATRIX_ON_DEVICE, CGAMD_SPLIT_LONG_ROWS, every SpMV form.  cgamd_solver_refresh_values and cgamd_solver_reload_matrix keep
+ *   the shifts.  cgamd_solver_set_shifts returns CGAMD_ERR_STATE, the handle untouched, on batched handles, CGAMD_HERMITIAN on a complex
+ *   type, CGAMD_UNFUSED, the row-major layout, and with a preconditioner in force (a preconditioned operator is not a shift of
+ *   anything); CGAMD_ERR_INVALID for nShifts outside 0 ... 16 or a sigma that is not finite.  With shifts in force: CGAMD_ERR_STATE from
+ *   every cgamd_solver_set_preconditioner* entry (except removal with NULL), cgamd_solver_iterate_tol, cgamd_solver_replace_residual and
+ *   cgamd_solver_set_rhs_projected; CGAMD_ERR_INVALID from cgamd_solver_set_rhs with x0 != NULL.
+ * Byte models: cgamd_solver_iter_bytes and cgamd_solver_iter_moved_bytes grow by (4 nShifts + 1) size V nRHS, V = sizeof(value): r
+ *   read once for all shifts, x_j and d_j of every shift read and written (on top of the ten vector passes of the loop such a handle
+ *   runs: x is updated in every iteration). */
+int cgamd_solver_set_shifts(cgamd_solver *s, const void *sigma, int nShifts);
+int cgamd_solver_shifts(cgamd_solver *s);
+int cgamd_solver_get_x_shifted(cgamd_solver *s, int j, void *x, int on_device);
+int cgamd_solver_shift_history(cgamd_solver *s, void *out, int max_entries);
+/* Development entries (tests; same standing as cgamd_solver_step_state).  _shift_scalars waits for the handle's stream and copies the
+ * last iteration's scalars to the host, nShifts x nRHS values at [j * nRHS + r] -- which 0: theta, 1: zeta, in double / complex
+ * double; 2: alpha_j, 3: beta_j, in the value type.
+ * cgamd_shift_update: the vector kernel alone on DEVICE arrays of the caller, enqueued on the ctx stream: r holds nRHS vectors at
+ * stride ld, xs and ds nShifts x nRHS vectors, (j, r) at (j * nRHS + r) * ld; alpha_s, beta_s, zeta_s nShifts x nRHS values at
+ * [j * nRHS + r].  xs_j = xs_j + alpha_j ds_j ; ds_j = zeta_j r + beta_j ds_j on the first `size` values of every vector; the rows
+ * between size and ld are neither read nor written.  16-byte packs when r, xs, ds are 16-byte aligned and ld is whole packs, else
+ * value by value: the same bits. */
+int cgamd_solver_shift_scalars(cgamd_solver *s, int which, void *out_host);
+int cgamd_shift_update(cgamd_ctx *ctx, int dtype, int size, long long ld, int nRHS, int nShifts, const void *r, void *xs, void *ds,
+                       const void *alpha_s, const void *beta_s, const void *zeta_s);
+
 #ifdef __cplusplus
 }
 #endif
