@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/cgamd.h"
+#include "mg_params.h"
 
 namespace cgamd {
 
@@ -23,6 +24,8 @@ int fail(int status, const std::string &msg);
                                  std::string(#expr) + ": " + hipGetErrorString(e__));        \
     } while (0)
 
+// hipMalloc (16 bytes at least) with the library's error text (precond_state.cpp)
+int dmalloc(void **p, size_t bytes, const char *what);
 inline size_t dtype_size(int dt) { return dt == 0 ? 4 : dt == 1 ? 8 : dt == 2 ? 8 : dt == 3 ? 16 : 0; }
 inline size_t acc_size(int dt) { return (dt == 0 || dt == 1) ? 8 : 16; }
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -717,14 +720,15 @@ int launch_amg_restrict(int dtype, int nc, const int *mem, long long ldf, long l
 int launch_amg_prolong(int dtype, int nf, const int *agg, long long ldf, long long ldc, int nrhs, const void *e, void *x, double omega,
                        hipStream_t st);
 struct MgHierarchy;
-// algebraic: aggregates by `passes` passes of matching at strength `theta` (cgamd_solver_set_preconditioner_amg), nx, ny, nz unused
-struct MgParams { int nx = 1, ny = 1, nz = 1, smooth_steps = 1, min_rows = 512; double omega = 1.6; bool algebraic = false; int passes = 3; double theta = 0.25; };
+// (struct MgParams and the range checks of the entries that fill it: mg_params.h)
 // nsys > 0 (a batched handle, nrhs == nsys): one hierarchy per system on shared aggregates and patterns, vals = nsys * nnz values
 int mg_build(hipStream_t st, int dt, int nu, int n, int nrhs, int nsys, const SpmvPlan &plan0, long long nnz, const void *vals,
              const int *ptr, const int *cols, const MgParams &p, const std::string &who, MgHierarchy **out);
 void mg_free(MgHierarchy *h);
 // z = M^-1 r: nrhs vectors of n rows at stride n each, the padding rows of r zero; a linear chain of launches on st
 int mg_vcycle(const MgHierarchy *h, const void *r, void *z, hipStream_t st);
+// the same on caller vectors without the padding rows (nrhs * n_user device values each), through padded buffers; synchronises
+int mg_apply_padded(MgHierarchy *h, hipStream_t st, int dtype, int n, int n_user, int nrhs, const void *r_dev, void *z_dev, const char *who);
 // what one V-cycle launches and moves: kernels, fine-level SpMVs (priced by the handle), and the bytes of everything else
 struct MgCost { int launches = 0, spmv0 = 0; long long bytes = 0; };
 MgCost mg_cost(const MgHierarchy *h);

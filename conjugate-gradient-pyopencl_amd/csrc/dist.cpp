@@ -25,6 +25,8 @@
 #include <vector>
 
 #include "cgamd_internal.h"
+#include "launch_util.h"
+#include "precond_state.h"
 
 using namespace cgamd;
 
@@ -145,31 +147,25 @@ struct cgamd_dist {
     std::vector<int> xch_dst_off;      // where my entries land in each peer's halo numbering
     SlabComm slab_comm;
     int n_cus = 0;
-    // preconditioner (cgamd_dist_set_preconditioner*): 0 none, 1 diagonal (mdiag), 2 line (tri: factors cut at the rank's row range),
-    // 3 multigrid (mg, below).
-    // z = M^-1 r lives in q's storage; part_pcg = [2][pcg_P] partials of r.z and r.r; rho2 = parity buffer of rho = r.z (delta holds
-    // rho for cg_alpha, history keeps r.r)
-    int pre_kind = 0, pcg_P = 0;
-    // a preconditioner built from the rank's matrix, which cgamd_dist_refresh_values builds again: 0 none (or the caller's values),
-    // 1 Jacobi, 2 the lines at pre_stride, 3 / 4 the grid / algebraic multigrid of mg_params
-    int pre_from_matrix = 0, pre_stride = 0;
+    // the preconditioner in force (precond_state.h; cgamd_dist_set_preconditioner*): pre.kind decides the loop -- a diagonal, lines
+    // (factors cut at the rank's row range) or multigrid (below) -- and pre.built what cgamd_dist_refresh_values builds again.
+    // z = M^-1 r lives in q's storage; the partials of r.z and r.r are [2][P] accumulators: part_pcg with P = vgrid for the diagonal
+    // and multigrid loops (allocated at the first such M and kept), pre.tri_part with P = the sweeps' grid for the lines (pcg_prz,
+    // pcg_prr, pcg_P); pre.rho2 = parity buffer of rho = r.z (delta holds rho for cg_alpha, history keeps r.r)
+    Precond pre;
+    void *part_pcg = nullptr;
     int last_refresh = 0;   // what the last cgamd_dist_refresh_values did (cgamd_dist_last_refresh)
-    void *mdiag = nullptr, *tri_coef = nullptr, *part_pcg = nullptr, *rho2 = nullptr;
-    int *tri_plan = nullptr;
-    TriLaunch tri;
-    // multigrid (cgamd_dist_set_preconditioner_multigrid / _amg, pre_kind 3): one V-cycle of a hierarchy built from the CUT matrix,
+    // multigrid (cgamd_dist_set_preconditioner_multigrid / _amg): one V-cycle of a hierarchy built from the CUT matrix,
     // the rank's rows without their halo columns (dist_cut.hip) -- a second, uncoded copy of the rank's columns and values with
     // n_pad - n_local empty rows behind them (n_pad: n_local rounded up to whole 16-byte packs, the rows mg_build's level 0 works
     // on).  r and q are allocated to n_pad values, so the cycle runs on them in place; the padding of r is zeroed at set_rhs.
-    // pre_from_matrix 3 / 4: the grid / the algebraic form, with mg_params what cgamd_dist_refresh_values builds again
+    // The cut matrix lives and dies with pre.mg (pre_replaced)
     struct CutMatrix {
         int *ptr = nullptr, *cols = nullptr;
         void *vals = nullptr;
         long long nnz = 0;
         SpmvPlan plan;
     } cut;
-    MgHierarchy *mg = nullptr;
-    MgParams mg_params;
     int n_pad = 0;
     // cgamd_dist_iterate_until: the stop (StopRun with one right-hand side: allocated at the first call, armed once per set_rhs).
     // until_stopped: the handle is frozen until the next set_rhs
@@ -181,17 +177,6 @@ static void free_cut(cgamd_dist::CutMatrix *c) {
     for (void *p : {(void *)c->ptr, (void *)c->cols, c->vals})
         if (p) (void)hipFree(p);
     *c = cgamd_dist::CutMatrix();
-}
-static void drop_multigrid(cgamd_dist *d) {
-    if (d->mg) mg_free(d->mg);
-    d->mg = nullptr;
-    free_cut(&d->cut);
-}
-
-static int dalloc(void **p, size_t bytes, const char *what) {
-    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-    if (e != hipSuccess) return fail(CGAMD_ERR_ALLOC, std::string("hipMalloc(") + what + "): " + hipGetErrorString(e));
-    return CGAMD_OK;
 }
 
 static ncclDataType_t elem_type(int dtype) { return (dtype == CGAMD_F32 || dtype == CGAMD_C64) ? ncclFloat : ncclDouble; }
@@ -287,42 +272,47 @@ static int enqueue_tail_cg1(cgamd_dist *d, hipStream_t st) {
 // delta = rho = r.z; then r -= alpha q and z = M^-1 r over q's storage with partials of r.z and r.r, ONE global round for the two
 // sums, beta = rho / rho_old, x += alpha d, d = z + beta d.  M is rank-local (a diagonal, or lines cut at the row range): the
 // sweep needs no communication.
-static void *pcg_prr(const cgamd_dist *d) { return static_cast<char *>(d->part_pcg) + acc_size(d->dtype) * (size_t)d->pcg_P; }
+static int pcg_P(const cgamd_dist *d) { return d->pre.kind == Precond::kTri ? d->pre.tri.grid : d->vgrid; }
+static PcgPartials pcg_part(const cgamd_dist *d) {
+    return pcg_partials(d->pre.kind == Precond::kTri ? d->pre.tri_part : d->part_pcg, d->dtype, pcg_P(d), 1);
+}
+static void *pcg_prz(const cgamd_dist *d) { return pcg_part(d).rz; }
+static void *pcg_prr(const cgamd_dist *d) { return pcg_part(d).rr; }
 // update = true: r -= alpha q first (z over q); false: set_rhs, z0 of r0 into `z`
 static int pcg_sweep(cgamd_dist *d, bool update, void *z, hipStream_t st, const CgStop *g = nullptr) {
     const int dt = d->dtype, n = d->n_local;
-    if (d->pre_kind == 3) {
+    if (d->pre.kind == Precond::kMg) {
         // multigrid M, the single handle's branch on the distributed launches: r -= alpha q with the r.r partials (guarded), then
         // z = V-cycle(r) over q and the r.z partials -- both unguarded: z of a stopped handle is read by nothing that writes.  The
         // cycle is a linear chain of launches on st and works on n_pad rows of r and q (the padding of r is zero, of z comes out zero)
         int rc;
-        if (update && (rc = launch_axpy_dot(dt, n, d->q, d->r, n, d->sc.alpha, 1, pcg_prr(d), d->pcg_P, st, d->plan.vec_nt, g))) return rc;
-        if ((rc = mg_vcycle(d->mg, d->r, d->q, st))) return rc;
+        if (update && (rc = launch_axpy_dot(dt, n, d->q, d->r, n, d->sc.alpha, 1, pcg_prr(d), pcg_P(d), st, d->plan.vec_nt, g))) return rc;
+        if ((rc = mg_vcycle(d->pre.mg, d->r, d->q, st))) return rc;
         if (!update) {      // set_rhs: z0 goes to the local part of d_ext (whose halo part starts where the padding rows would lie)
             CG_HIP(hipMemcpyAsync(z, d->q, (size_t)n * dtype_size(dt), hipMemcpyDeviceToDevice, st));
-            if ((rc = launch_dot_partials(dt, n, d->r, d->r, n, 1, pcg_prr(d), d->pcg_P, st))) return rc;
+            if ((rc = launch_dot_partials(dt, n, d->r, d->r, n, 1, pcg_prr(d), pcg_P(d), st))) return rc;
         }
-        return launch_dot_partials(dt, n, d->r, z, n, 1, d->part_pcg, d->pcg_P, st);
+        return launch_dot_partials(dt, n, d->r, z, n, 1, pcg_prz(d), pcg_P(d), st);
     }
-    if (d->pre_kind == 1) {
-        if (!update) return launch_pcg_axpy2_dot2(dt, true, n, z, d->x, d->q, d->r, d->mdiag, n, nullptr, 1, d->part_pcg, pcg_prr(d), d->pcg_P, st);
-        return launch_pcg_jacobi_z(dt, n, d->q, d->r, d->mdiag, d->sc.alpha, d->part_pcg, pcg_prr(d), d->pcg_P, st, g);
+    if (d->pre.kind == Precond::kDiag) {
+        if (!update) return launch_pcg_axpy2_dot2(dt, true, n, z, d->x, d->q, d->r, d->pre.mdiag, n, nullptr, 1, pcg_prz(d), pcg_prr(d), pcg_P(d), st);
+        return launch_pcg_jacobi_z(dt, n, d->q, d->r, d->pre.mdiag, d->sc.alpha, pcg_prz(d), pcg_prr(d), pcg_P(d), st, g);
     }
     const void *q = update ? d->q : nullptr, *alpha = update ? d->sc.alpha : nullptr;
-    if (d->tri.stride > 1) return launch_pcg_tri_strided(dt, d->tri, update, q, d->r, z, n, alpha, 1, d->part_pcg, pcg_prr(d), st, g);
-    return launch_pcg_tri(dt, d->tri, update, q, d->r, z, n, alpha, 1, d->part_pcg, pcg_prr(d), st, g);
+    if (d->pre.tri.stride > 1) return launch_pcg_tri_strided(dt, d->pre.tri, update, q, d->r, z, n, alpha, 1, pcg_prz(d), pcg_prr(d), st, g);
+    return launch_pcg_tri(dt, d->pre.tri, update, q, d->r, z, n, alpha, 1, pcg_prz(d), pcg_prr(d), st, g);
 }
 // {r.z, r.r} partials -> global sums -> the scalar step (mode 1 set_rhs, 3 beta).  RCCL: local reduce of two values, ONE ncclAllReduce
 // of count 2, scalar kernel; peer-to-peer: one launch
 static int pcg_reduce2(cgamd_dist *d, int mode, hipStream_t st, const CgStop *g = nullptr) {
     if (d->p2p) {
         if (!d->p2p_attached) return fail(CGAMD_ERR_STATE, "p2p backend: call cgamd_dist_attach_p2p first");
-        return launch_pcg_allreduce2_p2p(d->dtype, mode, d->part_pcg, pcg_prr(d), d->pcg_P, d->mailbox_dev, d->rank, d->nranks, d->epochs + 2,
-                                         d->sc, d->rho2, st, g);
+        return launch_pcg_allreduce2_p2p(d->dtype, mode, pcg_prz(d), pcg_prr(d), pcg_P(d), d->mailbox_dev, d->rank, d->nranks, d->epochs + 2,
+                                         d->sc, d->pre.rho2, st, g);
     }
-    if (int rc = launch_reduce_to_acc(d->dtype, d->part_pcg, d->pcg_P, 2, d->red, st)) return rc;
+    if (int rc = launch_reduce_to_acc(d->dtype, pcg_prz(d), pcg_P(d), 2, d->red, st)) return rc;
     if (int rc = allreduce_scalar(d, d->red, st, 2)) return rc;
-    return launch_pcg_scalars(d->dtype, mode, d->red, d->sc, d->rho2, st, g);
+    return launch_pcg_scalars(d->dtype, mode, d->red, d->sc, d->pre.rho2, st, g);
 }
 
 // One iteration of the handle's launched loop and preconditioner.  g (cgamd_dist_iterate_until): the same launches with the guarded
@@ -342,10 +332,10 @@ static int enqueue_iteration(cgamd_dist *d, hipStream_t st, const CgStop *g = nu
                                   d->rotate, d->xch, st))) return rc;
         if ((rc = launch_p2p_allreduce(dt, 2, d->part_dq, d->plan.n_partials, d->mailbox_dev, d->rank, d->nranks, 0, d->epochs + 1,
                                        d->sc, st, d->epochs, d->epochs + 2, g))) return rc;
-        if (d->pre_kind) {      // [r -= alpha q, z = M^-1 r, r.z, r.r], [all-reduce of both, beta, x += alpha d, d = z + beta d]
+        if (d->pre.kind != Precond::kNone) {      // [r -= alpha q, z = M^-1 r, r.z, r.r], [all-reduce of both, beta, x += alpha d, d = z + beta d]
             if ((rc = pcg_sweep(d, true, d->q, st, g))) return rc;
-            return launch_pcg_aypx_beta_p2p(dt, n, d->q, d->d_ext, d->x, d->part_pcg, pcg_prr(d), d->pcg_P, d->mailbox_dev, d->rank, d->nranks,
-                                            d->epochs + 2, d->sc, d->rho2, st, d->plan.vec_nt, g);
+            return launch_pcg_aypx_beta_p2p(dt, n, d->q, d->d_ext, d->x, pcg_prz(d), pcg_prr(d), pcg_P(d), d->mailbox_dev, d->rank, d->nranks,
+                                            d->epochs + 2, d->sc, d->pre.rho2, st, d->plan.vec_nt, g);
         }
         if ((rc = launch_axpy_dot(dt, n, d->q, d->r, n, d->sc.alpha, 1, d->part_rr, d->vgrid, st, d->plan.vec_nt, g))) return rc;
         return launch_aypx_beta_p2p(dt, n, d->r, d->d_ext, d->x, d->part_rr, d->vgrid, d->mailbox_dev, d->rank, d->nranks, 1,
@@ -369,7 +359,7 @@ static int enqueue_iteration(cgamd_dist *d, hipStream_t st, const CgStop *g = nu
         if ((rc = launch_spmv(dt, d->plan, n, d->nnz, d->vals, d->ptr, d->cols, d->d_ext, ldx, d->q, n, 1, d->d_ext, d->part_dq, st))) return rc;
     }
     if ((rc = reduce_all(d, d->part_dq, d->plan.n_partials, 0, 2, st, g))) return rc;
-    if (d->pre_kind) {      // (guarded: x += alpha d rides in the last launch, which leaves on live[]: the stopping iteration still gets it)
+    if (d->pre.kind != Precond::kNone) {      // (guarded: x += alpha d rides in the last launch, which leaves on live[]: the stopping iteration still gets it)
         if ((rc = pcg_sweep(d, true, d->q, st, g))) return rc;
         if ((rc = pcg_reduce2(d, 3, st, g))) return rc;
         return launch_pcg_xd_update(dt, n, d->q, d->d_ext, d->x, d->sc, st, g);
@@ -405,7 +395,7 @@ static int setup_value_codes(cgamd_dist *d) {
 static int classify_row_blocks(cgamd_dist *d, std::vector<int> *interior, std::vector<int> *boundary) {
     const int nb = d->plan.row_blocks;
     int *flags_dev = nullptr;
-    if (int rc = dalloc((void **)&flags_dev, sizeof(int) * (size_t)nb, "halo flags")) return rc;
+    if (int rc = dmalloc((void **)&flags_dev, sizeof(int) * (size_t)nb, "halo flags")) return rc;
     int rc = launch_halo_flags(d->n_local, d->ptr, d->cols, d->n_local, nb, flags_dev, d->ctx->stream);
     std::vector<int> flags((size_t)nb);
     hipError_t e = rc ? hipSuccess : hipMemcpyAsync(flags.data(), flags_dev, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, d->ctx->stream);
@@ -418,7 +408,7 @@ static int classify_row_blocks(cgamd_dist *d, std::vector<int> *interior, std::v
 }
 
 static int upload_ints(int **dev, const std::vector<int> &v, const char *what) {
-    if (int rc = dalloc((void **)dev, sizeof(int) * v.size(), what)) return rc;
+    if (int rc = dmalloc((void **)dev, sizeof(int) * v.size(), what)) return rc;
     if (!v.empty()) CG_HIP(hipMemcpy(*dev, v.data(), sizeof(int) * v.size(), hipMemcpyHostToDevice));
     return CGAMD_OK;
 }
@@ -456,7 +446,7 @@ static int ensure_history(cgamd_dist *d, int entries) {
     const int cap = std::max(entries, std::max(1024, d->sc.history_cap * 2));
     const size_t vs = dtype_size(d->dtype);
     void *nh = nullptr;
-    if (int rc = dalloc(&nh, (size_t)cap * vs, "history")) return rc;
+    if (int rc = dmalloc(&nh, (size_t)cap * vs, "history")) return rc;
     if (d->sc.history) {
         CG_HIP(hipStreamSynchronize(d->ctx->stream));
         CG_HIP(hipMemcpy(nh, d->sc.history, (size_t)d->sc.history_cap * vs, hipMemcpyDeviceToDevice));
@@ -531,24 +521,24 @@ int cgamd_dist_create(cgamd_ctx *ctx, const void *id128, int rank, int nranks, i
 
     const size_t vs = dtype_size(dtype);
     int rc = CGAMD_OK;
-    if (!rc) rc = dalloc(&d->x, (size_t)n_local * vs, "x");
+    if (!rc) rc = dmalloc(&d->x, (size_t)n_local * vs, "x");
     // (r and q to whole 16-byte packs: the multigrid cycle works on n_pad rows of them)
     {
         const int E = (int)(16 / vs);
         d->n_pad = n_local < 2147483647 - 8 ? (n_local + E - 1) / E * E : n_local;
     }
-    if (!rc) rc = dalloc(&d->r, (size_t)d->n_pad * vs, "r");
-    if (!rc) rc = dalloc(&d->q, (size_t)d->n_pad * vs, "q");
-    if (!rc) rc = dalloc(&d->b, (size_t)n_local * vs, "b");
-    if (!rc) rc = dalloc(&d->d_ext, ((size_t)n_local + n_halo) * vs, "d_ext");
-    if (!rc) rc = dalloc(&d->sendbuf, (size_t)so * vs, "sendbuf");
-    if (!rc) rc = dalloc(&d->part_dq, acc_size(dtype) * (size_t)std::max(d->plan.grid, d->plan.row_blocks), "partials_dq");
-    if (!rc) rc = dalloc(&d->part_rr, acc_size(dtype) * (size_t)d->vgrid, "partials_rr");
-    if (!rc) rc = dalloc(&d->red, 64, "red");
-    if (!rc) rc = dalloc(&d->sc.alpha, vs, "alpha");
-    if (!rc) rc = dalloc(&d->sc.beta, vs, "beta");
-    if (!rc) rc = dalloc(&d->sc.delta, vs, "delta");
-    if (!rc) rc = dalloc((void **)&d->sc.iter, 64, "iter");
+    if (!rc) rc = dmalloc(&d->r, (size_t)d->n_pad * vs, "r");
+    if (!rc) rc = dmalloc(&d->q, (size_t)d->n_pad * vs, "q");
+    if (!rc) rc = dmalloc(&d->b, (size_t)n_local * vs, "b");
+    if (!rc) rc = dmalloc(&d->d_ext, ((size_t)n_local + n_halo) * vs, "d_ext");
+    if (!rc) rc = dmalloc(&d->sendbuf, (size_t)so * vs, "sendbuf");
+    if (!rc) rc = dmalloc(&d->part_dq, acc_size(dtype) * (size_t)std::max(d->plan.grid, d->plan.row_blocks), "partials_dq");
+    if (!rc) rc = dmalloc(&d->part_rr, acc_size(dtype) * (size_t)d->vgrid, "partials_rr");
+    if (!rc) rc = dmalloc(&d->red, 64, "red");
+    if (!rc) rc = dmalloc(&d->sc.alpha, vs, "alpha");
+    if (!rc) rc = dmalloc(&d->sc.beta, vs, "beta");
+    if (!rc) rc = dmalloc(&d->sc.delta, vs, "delta");
+    if (!rc) rc = dmalloc((void **)&d->sc.iter, 64, "iter");
     if (!rc) rc = ensure_history(d, 1024);
     if (!rc) rc = validate_csr_device(n_local, nnz_local, n_local + n_halo, d->ptr, d->cols, d->send_index, d->total_send, n_local, d->sc.iter,
                                       ctx->stream);
@@ -564,9 +554,9 @@ int cgamd_dist_create(cgamd_ctx *ctx, const void *id128, int rank, int nranks, i
         if (!cg1_supported(d->plan, d->vals, d->cols))
             rc = fail(CGAMD_ERR_INVALID, "dist_create: the single-reduction loop needs the row-block SpMV (16-byte aligned matrix arrays, rows "
                                          "whose 256-row slices fit LDS)");
-        if (!rc) rc = dalloc(&d->s2, (size_t)n_local * vs, "s");
-        if (!rc) rc = dalloc(&d->cg1_state, 64, "single-reduction state");
-        if (!rc) rc = dalloc(&d->part_cg1, acc_size(dtype) * 2 * (size_t)d->plan.row_blocks, "partials (r.w, r.r)");
+        if (!rc) rc = dmalloc(&d->s2, (size_t)n_local * vs, "s");
+        if (!rc) rc = dmalloc(&d->cg1_state, 64, "single-reduction state");
+        if (!rc) rc = dmalloc(&d->part_cg1, acc_size(dtype) * 2 * (size_t)d->plan.row_blocks, "partials (r.w, r.r)");
     }
     if (!rc && (flags & CGAMD_DIST_RESIDENT) && !d->cg1) {
         if (hipDeviceGetAttribute(&d->n_cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess) d->n_cus = 0;
@@ -574,9 +564,9 @@ int cgamd_dist_create(cgamd_ctx *ctx, const void *id128, int rank, int nranks, i
         SlabPlan sp;
         if (slab_plan(dtype, n_local, d->n_cus, d->plan, d->codes != nullptr, &sp)) {
             sp.vcodes = d->vcodes; sp.vdict = d->vdict;      // (publish_value_codes keeps both copies current)
-            rc = dalloc(&d->slab_sync, sp.sync_bytes, "slab sync words");
+            rc = dmalloc(&d->slab_sync, sp.sync_bytes, "slab sync words");
             if (!rc && d->peer.empty() && nranks == 1) {     // nothing to exchange: plain buffers, usable at once
-                for (int b = 0; b < 2 && !rc; ++b) rc = dalloc(&d->ds_own[b], (size_t)n_local * vs, "published d");
+                for (int b = 0; b < 2 && !rc; ++b) rc = dmalloc(&d->ds_own[b], (size_t)n_local * vs, "published d");
                 if (!rc) { d->ds[0] = d->ds_own[0]; d->ds[1] = d->ds_own[1]; d->slab = sp; }
             } else if (!rc && d->p2p) {
                 d->slab_plan_ = sp;              // cgamd_dist_enable_resident finds the buffers inside the mailbox allocation
@@ -635,10 +625,11 @@ int cgamd_dist_destroy(cgamd_dist *d) {
     if (d->vcodes) (void)hipFree(d->vcodes);
     if (d->vdict) (void)hipFree(d->vdict);
     if (d->dict) (void)hipFree(d->dict);
-    drop_multigrid(d);
+    free_cut(&d->cut);
+    precond_drop(&d->pre);
     void *bufs[] = {d->x, d->r, d->q, d->b, d->d_ext, d->sendbuf, d->part_dq, d->part_rr, d->red, d->sc.alpha,
                     d->sc.beta, d->sc.delta, d->sc.history, d->sc.iter, d->s2, d->cg1_state, d->part_cg1, d->slab_sync, d->slab_map, d->ds_own[0], d->ds_own[1],
-                    d->push_dst_dev, d->mdiag, d->tri_coef, d->part_pcg, d->rho2, d->tri_plan, d->tri.maps};
+                    d->push_dst_dev, d->part_pcg, d->pre.rho2};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     delete d;
@@ -662,8 +653,8 @@ int cgamd_dist_set_rhs(cgamd_dist *d, const void *b_local, const void *x0_local)
     if ((rc = launch_spmv(d->dtype, d->plan, d->n_local, d->nnz, d->vals, d->ptr, d->cols, d->d_ext, ldx, d->q, d->n_local, 1,
                           nullptr, nullptr, st))) return rc;
     if ((rc = launch_sub(d->dtype, d->n_local, d->b, d->q, d->r, d->n_local, 1, st))) return rc;
-    if (d->pre_kind) {      // z0 = M^-1 r0, d = z0, rho0 = all-reduced r0.z0, history[0] = r0.r0
-        if (d->pre_kind == 3 && d->n_pad > d->n_local)      // the cycle reads whole packs of r: nothing else ever writes the padding
+    if (d->pre.kind != Precond::kNone) {      // z0 = M^-1 r0, d = z0, rho0 = all-reduced r0.z0, history[0] = r0.r0
+        if (d->pre.kind == Precond::kMg && d->n_pad > d->n_local)      // the cycle reads whole packs of r: nothing else ever writes the padding
             CG_HIP(hipMemsetAsync(static_cast<char *>(d->r) + vb, 0, (size_t)(d->n_pad - d->n_local) * vs, st));
         if ((rc = pcg_sweep(d, false, d->d_ext, st))) return rc;
         if ((rc = pcg_reduce2(d, 1, st))) return rc;
@@ -693,7 +684,7 @@ int cgamd_dist_iterate(cgamd_dist *d, int nIterations) {
     hipStream_t st = d->ctx->stream;
     int left = nIterations;
     // (the slab loop has no preconditioned form: such a handle runs its launched loop while a preconditioner is set)
-    if (d->slab.ok && !d->pre_kind && nIterations >= std::max(1, d->tune.resident_wide_min)) {
+    if (d->slab.ok && d->pre.kind == Precond::kNone && nIterations >= std::max(1, d->tune.resident_wide_min)) {
         // the whole call in one launch per 2^15 iterations (slab.hip); same state in and out as the launched loop below
         while (left > 0) {
             const int K = std::min(left, 1 << 15);
@@ -796,17 +787,16 @@ static void drop_graph(cgamd_dist *d) {
     if (d->gexec) { (void)hipGraphExecDestroy(d->gexec); d->gexec = nullptr; }
     if (d->graph) { (void)hipGraphDestroy(d->graph); d->graph = nullptr; }
 }
-static void drop_preconditioner(cgamd_dist *d) {
-    for (void *p : {d->mdiag, d->tri_coef, (void *)d->tri_plan, d->tri.maps, d->part_pcg})
-        if (p) (void)hipFree(p);
-    d->mdiag = d->tri_coef = d->part_pcg = nullptr;
-    d->tri_plan = nullptr;
-    d->tri = TriLaunch();
-    drop_multigrid(d);
-    d->pre_kind = d->pcg_P = 0;
-    d->pre_from_matrix = d->pre_stride = 0;
+// M has just been replaced or removed: the captured graph replays the old loop, the recurrence starts again at set_rhs, and a cut
+// matrix whose hierarchy is gone goes too
+static void pre_replaced(cgamd_dist *d) {
+    if (!d->pre.mg) free_cut(&d->cut);
     drop_graph(d);
     d->rhs_set = false;
+}
+static void drop_preconditioner(cgamd_dist *d) {
+    precond_drop(&d->pre);
+    pre_replaced(d);
 }
 static int pre_begin(cgamd_dist *d, const char *who) {
     if (d->cg1)
@@ -815,23 +805,20 @@ static int pre_begin(cgamd_dist *d, const char *who) {
     CG_HIP(hipStreamSynchronize(d->ctx->stream));
     return CGAMD_OK;
 }
-// what every preconditioned loop needs besides M: P pairs of partials and the rho parity buffer
-static int pre_buffers(cgamd_dist *d, int P, void **part, void **maps, int map_values) {
-    int rc = dalloc(part, 2 * acc_size(d->dtype) * (size_t)P, "partials_rz/rr");
-    if (!rc && map_values) rc = dalloc(maps, (size_t)map_values * dtype_size(d->dtype), "tridiagonal chunk maps");
-    if (!rc && !d->rho2) rc = dalloc(&d->rho2, 2 * dtype_size(d->dtype), "rho");
-    return rc;
+// what the diagonal and multigrid loops need besides M: vgrid pairs of partials and the rho parity buffer
+static int pre_buffers(cgamd_dist *d) {
+    if (!d->part_pcg)
+        if (int rc = dmalloc(&d->part_pcg, 2 * acc_size(d->dtype) * (size_t)d->vgrid, "partials_rz/rr")) return rc;
+    return precond_ensure_rho(&d->pre, d->dtype, 1);
 }
 // the handle takes m (n_local device values, its own allocation from here on) over
-static int install_diag(cgamd_dist *d, void *m) {
-    void *part = nullptr;
-    if (int rc = pre_buffers(d, d->vgrid, &part, nullptr, 0)) {
-        if (part) (void)hipFree(part);
+static int install_diag(cgamd_dist *d, void *m, Precond::Built built) {
+    if (int rc = pre_buffers(d)) {
         (void)hipFree(m);
         return rc;
     }
-    drop_preconditioner(d);
-    d->mdiag = m; d->part_pcg = part; d->pcg_P = d->vgrid; d->pre_kind = 1;
+    precond_take_diag(&d->pre, m, built);
+    pre_replaced(d);
     return CGAMD_OK;
 }
 
@@ -847,11 +834,11 @@ int cgamd_dist_set_preconditioner(cgamd_dist *d, const void *m_local) {
     if (int rc = pre_begin(d, "dist_set_preconditioner")) return rc;
     const size_t vb = (size_t)d->n_local * dtype_size(d->dtype);
     void *m = nullptr;
-    if (int rc = dalloc(&m, vb, "preconditioner")) return rc;
+    if (int rc = dmalloc(&m, vb, "preconditioner")) return rc;
     hipError_t e = hipMemcpyAsync(m, m_local, vb, hipMemcpyDeviceToDevice, d->ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(d->ctx->stream);
     if (e != hipSuccess) { (void)hipFree(m); return fail(CGAMD_ERR_HIP, std::string("dist_set_preconditioner: ") + hipGetErrorString(e)); }
-    return install_diag(d, m);
+    return install_diag(d, m, Precond::kCaller);
 }
 
 int cgamd_dist_set_preconditioner_jacobi(cgamd_dist *d) {
@@ -859,15 +846,13 @@ int cgamd_dist_set_preconditioner_jacobi(cgamd_dist *d) {
     TuneScope ts(&d->tune);
     if (int rc = pre_begin(d, "dist_set_preconditioner_jacobi")) return rc;
     void *m = nullptr;
-    if (int rc = dalloc(&m, (size_t)d->n_local * dtype_size(d->dtype), "Jacobi preconditioner")) return rc;
+    if (int rc = dmalloc(&m, (size_t)d->n_local * dtype_size(d->dtype), "Jacobi preconditioner")) return rc;
     // the diagonal of local row i is local column i: the halo columns (>= n_local) never match a row
     if (int rc = jacobi_build_from_matrix(d->ctx->stream, d->dtype, d->n_local, "dist_set_preconditioner_jacobi", d->vals, d->ptr, d->cols, m)) {
         (void)hipFree(m);
         return rc;
     }
-    const int rc = install_diag(d, m);
-    if (!rc) d->pre_from_matrix = 1;
-    return rc;
+    return install_diag(d, m, Precond::kJacobi);
 }
 
 int cgamd_dist_set_preconditioner_line(cgamd_dist *d, int stride) {
@@ -881,27 +866,8 @@ int cgamd_dist_set_preconditioner_line(cgamd_dist *d, int stride) {
     int rc = tri_build_from_matrix(d->ctx->stream, d->dtype, d->n_local, d->n_local, d->tune.dev_line_host_route, "dist_set_preconditioner_line",
                                    stride, d->vals, d->ptr, d->cols, d->n_local, &b);
     if (rc) return rc;
-    const int P = b.stride == 1 ? std::min(b.count, 1024) : tri_strided_grid(b.count);
-    void *part = nullptr, *maps = nullptr;
-    if ((rc = pre_buffers(d, P, &part, &maps, b.longform ? tri_maps_values(b.count, 1) : 0))) {
-        if (part) (void)hipFree(part);
-        if (maps) (void)hipFree(maps);
-        tri_built_free(&b);
-        return rc;
-    }
-    drop_preconditioner(d);
-    const size_t vs = dtype_size(d->dtype);
-    char *cb = static_cast<char *>(b.coef);
-    d->tri_coef = b.coef; d->tri_plan = b.plan; d->part_pcg = part; d->pcg_P = P;
-    d->tri.nl = cb; d->tri.ne = cb + b.pitch * vs; d->tri.w = cb + 2 * b.pitch * vs;
-    d->tri.grid = P; d->tri.maps = maps;
-    if (b.stride == 1) {
-        d->tri.cstart = b.plan; d->tri.nchunks = b.count; d->tri.longform = b.longform;
-    } else {
-        d->tri.stride = b.stride; d->tri.segs = b.plan; d->tri.nsegs = b.count;
-    }
-    d->pre_kind = 2;
-    d->pre_from_matrix = 2; d->pre_stride = stride;
+    if ((rc = precond_take_tri(&d->pre, &b, d->dtype, 1, 0, stride))) return rc;
+    pre_replaced(d);
     return CGAMD_OK;
 }
 
@@ -914,9 +880,9 @@ static int build_cut(cgamd_dist *d, const std::string &who, cgamd_dist::CutMatri
     hipStream_t st = d->ctx->stream;
     cgamd_dist::CutMatrix c;
     void *words = nullptr;      // ints: [0] scan overflow flag, [4 ...] scratch of compute_spmv_plan
-    int rc = dalloc(&words, 64, "cut matrix: setup words");
+    int rc = dmalloc(&words, 64, "cut matrix: setup words");
     int *flag = static_cast<int *>(words), *scratch = flag + 4;
-    if (!rc) rc = dalloc((void **)&c.ptr, ((size_t)n + 1 + 64) * 4, "cut matrix: row pointers");
+    if (!rc) rc = dmalloc((void **)&c.ptr, ((size_t)n + 1 + 64) * 4, "cut matrix: row pointers");
     hipError_t e = hipSuccess;
     if (!rc) e = hipMemsetAsync(words, 0, 64, st);
     if (!rc && e == hipSuccess) rc = launch_cut_count(nu, n, nu, d->ptr, d->cols, c.ptr, st);
@@ -928,8 +894,8 @@ static int build_cut(cgamd_dist *d, const std::string &who, cgamd_dist::CutMatri
     if (!rc && e == hipSuccess && (back[0] || back[1] < 0 || back[1] > d->nnz)) rc = fail(CGAMD_ERR_HIP, who + ": the cut matrix's entry count is out of range");
     if (!rc && e == hipSuccess) {
         c.nnz = back[1];
-        rc = dalloc((void **)&c.cols, ((size_t)c.nnz + 64) * 4, "cut matrix: columns");
-        if (!rc) rc = dalloc(&c.vals, ((size_t)c.nnz + 64) * vs, "cut matrix: values");
+        rc = dmalloc((void **)&c.cols, ((size_t)c.nnz + 64) * 4, "cut matrix: columns");
+        if (!rc) rc = dmalloc(&c.vals, ((size_t)c.nnz + 64) * vs, "cut matrix: values");
         if (!rc) e = hipMemsetAsync(c.cols, 0, ((size_t)c.nnz + 64) * 4, st);
         if (!rc && e == hipSuccess) e = hipMemsetAsync(c.vals, 0, ((size_t)c.nnz + 64) * vs, st);
         if (!rc && e == hipSuccess) rc = launch_cut_fill(dt, nu, nu, d->vals, d->ptr, d->cols, c.ptr, c.cols, c.vals, st);
@@ -959,18 +925,15 @@ static int multigrid_from_cut(cgamd_dist *d, const std::string &who, const MgPar
     } else if ((rc = build_cut(d, who, &c))) return rc;
     MgHierarchy *h = nullptr;
     rc = mg_build(st, d->dtype, d->n_local, d->n_pad, 1, 0, c.plan, c.nnz, c.vals, c.ptr, c.cols, p, who, &h);
-    void *part = nullptr;
-    if (!rc && (rc = pre_buffers(d, d->vgrid, &part, nullptr, 0))) mg_free(h);
+    if (!rc && (rc = pre_buffers(d))) mg_free(h);
     if (rc) {
-        if (part) (void)hipFree(part);
         if (!refresh) free_cut(&c);
         return rc;
     }
-    if (refresh) d->cut = cgamd_dist::CutMatrix();      // (kept across the drop below)
-    drop_preconditioner(d);
-    d->cut = c; d->mg = h; d->mg_params = p;
-    d->part_pcg = part; d->pcg_P = d->vgrid; d->pre_kind = 3;
-    d->pre_from_matrix = p.algebraic ? 4 : 3;
+    if (!refresh) free_cut(&d->cut);        // (the cut matrix of the hierarchy that goes, if any)
+    precond_take_mg(&d->pre, h, p);
+    d->cut = c;
+    pre_replaced(d);
     return CGAMD_OK;
 }
 static int mg_begin(cgamd_dist *d, const std::string &who) {
@@ -984,18 +947,8 @@ int cgamd_dist_set_preconditioner_multigrid(cgamd_dist *d, int nx, int ny, int n
     if (!d) return fail(CGAMD_ERR_INVALID, who + ": null handle");
     TuneScope ts(&d->tune);
     if (int rc = mg_begin(d, who)) return rc;
-    if (nx < 1 || ny < 1 || nz < 1) return fail(CGAMD_ERR_INVALID, who + ": every grid dimension must be at least 1");
-    const long long plane = (long long)nx * ny;
-    if (plane > 2147483647LL || plane * nz != (long long)d->n_local)
-        return fail(CGAMD_ERR_INVALID, who + ": nx * ny * nz must equal the size of the system (the rank's own box: n_local rows)");
-    if (smooth_steps < 0 || smooth_steps > 4) return fail(CGAMD_ERR_INVALID, who + ": smooth_steps must be in 0 ... 4 (0 = the default, 1)");
-    if (!std::isfinite(over_correction) || over_correction < 0.) return fail(CGAMD_ERR_INVALID, who + ": over_correction must be finite and not negative (0 = the default, 1.6)");
-    if (min_rows < 0) return fail(CGAMD_ERR_INVALID, who + ": min_rows must not be negative (0 = the default, 512)");
     MgParams p;
-    p.nx = nx; p.ny = ny; p.nz = nz;
-    if (smooth_steps) p.smooth_steps = smooth_steps;
-    if (over_correction != 0.) p.omega = over_correction;
-    if (min_rows) p.min_rows = min_rows;
+    if (int rc = mg_params_grid(who, d->n_local, " (the rank's own box: n_local rows)", nx, ny, nz, smooth_steps, over_correction, min_rows, &p)) return rc;
     return multigrid_from_cut(d, who, p, false);
 }
 
@@ -1004,63 +957,61 @@ int cgamd_dist_set_preconditioner_amg(cgamd_dist *d, int passes, double strength
     if (!d) return fail(CGAMD_ERR_INVALID, who + ": null handle");
     TuneScope ts(&d->tune);
     if (int rc = mg_begin(d, who)) return rc;
-    if (passes < 0 || passes > 3) return fail(CGAMD_ERR_INVALID, who + ": passes must be in 0 ... 3 (0 = the default, 3)");
-    if (!std::isfinite(strength) || strength < 0. || strength > 1.) return fail(CGAMD_ERR_INVALID, who + ": strength must be in (0, 1] (0 = the default, 0.25)");
-    if (smooth_steps < 0 || smooth_steps > 4) return fail(CGAMD_ERR_INVALID, who + ": smooth_steps must be in 0 ... 4 (0 = the default, 1)");
-    if (!std::isfinite(over_correction) || over_correction < 0.) return fail(CGAMD_ERR_INVALID, who + ": over_correction must be finite and not negative (0 = the default, 1.6)");
-    if (min_rows < 0) return fail(CGAMD_ERR_INVALID, who + ": min_rows must not be negative (0 = the default, 512)");
     MgParams p;
-    p.algebraic = true;
-    if (passes) p.passes = passes;
-    if (strength != 0.) p.theta = strength;
-    if (smooth_steps) p.smooth_steps = smooth_steps;
-    if (over_correction != 0.) p.omega = over_correction;
-    if (min_rows) p.min_rows = min_rows;
+    if (int rc = mg_params_amg(who, passes, strength, smooth_steps, over_correction, min_rows, &p)) return rc;
     return multigrid_from_cut(d, who, p, false);
 }
 
 int cgamd_dist_mg_levels(cgamd_dist *d) {
     if (!d) return -CGAMD_ERR_INVALID;
-    return d->mg ? mg_levels(d->mg) : 0;
+    return d->pre.mg ? mg_levels(d->pre.mg) : 0;
 }
 static int dist_mg_wanted(cgamd_dist *d, const char *who) {
     if (!d) return fail(CGAMD_ERR_INVALID, std::string(who) + ": null handle");
-    if (!d->mg) return fail(CGAMD_ERR_STATE, std::string(who) + ": no multigrid preconditioner is set");
+    if (!d->pre.mg) return fail(CGAMD_ERR_STATE, std::string(who) + ": no multigrid preconditioner is set");
     CG_HIP(hipSetDevice(d->ctx->device));
     return CGAMD_OK;
 }
 int cgamd_dist_mg_level(cgamd_dist *d, int level, long long info[6]) {
     if (int rc = dist_mg_wanted(d, "dist_mg_level")) return rc;
     if (!info) return fail(CGAMD_ERR_INVALID, "dist_mg_level: info is NULL");
-    return mg_level_info(d->mg, level, info);
+    return mg_level_info(d->pre.mg, level, info);
 }
 int cgamd_dist_mg_level_matrix(cgamd_dist *d, int level, int *ptr, int *cols, void *vals) {
     if (int rc = dist_mg_wanted(d, "dist_mg_level_matrix")) return rc;
-    return mg_level_matrix(d->mg, level, ptr, cols, vals, d->ctx->stream);
+    return mg_level_matrix(d->pre.mg, level, ptr, cols, vals, d->ctx->stream);
 }
 // one V-cycle on caller vectors (n_local device values each), through buffers with the padding rows; synchronises
 int cgamd_dist_mg_apply(cgamd_dist *d, const void *r_dev, void *z_dev) {
     if (int rc = dist_mg_wanted(d, "dist_mg_apply")) return rc;
     if (!r_dev || !z_dev) return fail(CGAMD_ERR_INVALID, "dist_mg_apply: null argument");
     TuneScope ts(&d->tune);
-    hipStream_t st = d->ctx->stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return fail(CGAMD_ERR_HIP, "dist_mg_apply: hipStreamIsCapturing failed"); }
-    if (cs != hipStreamCaptureStatusNone) return fail(CGAMD_ERR_INVALID, "dist_mg_apply: the handle's stream is being captured");
-    const size_t vs = dtype_size(d->dtype), bytes = (size_t)d->n_pad * vs, user = (size_t)d->n_local * vs;
-    void *buf = nullptr;
-    if (int rc = dalloc(&buf, 2 * bytes, "mg_apply vectors")) return rc;
-    void *r = buf, *z = static_cast<char *>(buf) + bytes;
+    if (int rc = stream_not_capturing(d->ctx->stream, "dist_mg_apply")) return rc;
+    return mg_apply_padded(d->pre.mg, d->ctx->stream, d->dtype, d->n_pad, d->n_local, 1, r_dev, z_dev, "dist_mg_apply");
+}
+
+// a preconditioner built from the rank's matrix follows its values: removed where the values' own follow-up failed with status rc
+// (text in cgamd_last_error()) -- they are in force, read as they are, and factors of the old ones must not stay --
+static int remove_and_fail(cgamd_dist *d, int rc) {
+    if (d->pre.built == Precond::kCaller) return rc;
+    const std::string why = cgamd_last_error();
+    drop_preconditioner(d);
+    return fail(rc, why);
+}
+// -- and built again from the values as they are now, or removed where that fails
+static int rebuild_or_remove(cgamd_dist *d) {
     int rc = CGAMD_OK;
-    hipError_t e = hipMemsetAsync(buf, 0, 2 * bytes, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(r, r_dev, user, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) rc = mg_vcycle(d->mg, r, z, st);
-    if (e == hipSuccess && !rc) e = hipMemcpyAsync(z_dev, z, user, hipMemcpyDeviceToDevice, st);
-    const hipError_t e2 = hipStreamSynchronize(st);
-    (void)hipFree(buf);
-    if (rc) return rc;
-    if (e != hipSuccess || e2 != hipSuccess) return fail(CGAMD_ERR_HIP, std::string("dist_mg_apply: ") + hipGetErrorString(e != hipSuccess ? e : e2));
-    return CGAMD_OK;
+    switch (d->pre.built) {
+    case Precond::kCaller: return CGAMD_OK;
+    case Precond::kJacobi: rc = cgamd_dist_set_preconditioner_jacobi(d); break;
+    case Precond::kLine: rc = cgamd_dist_set_preconditioner_line(d, d->pre.stride); break;
+    case Precond::kGridMg:
+    case Precond::kAmg: {
+        const MgParams p = d->pre.mg_params;
+        rc = multigrid_from_cut(d, p.algebraic ? "dist_set_preconditioner_amg" : "dist_set_preconditioner_multigrid", p, true);
+    } break;
+    }
+    return rc ? remove_and_fail(d, rc) : CGAMD_OK;
 }
 
 // The rank's matrix values changed in place on the same pattern (include/cgamd.h).  Rank-local: nothing here communicates; collective
@@ -1071,9 +1022,7 @@ int cgamd_dist_refresh_values(cgamd_dist *d) {
     TuneScope ts(&d->tune);
     CG_HIP(hipSetDevice(d->ctx->device));
     hipStream_t st = d->ctx->stream;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return fail(CGAMD_ERR_HIP, "dist_refresh_values: hipStreamIsCapturing failed"); }
-    if (cs != hipStreamCaptureStatusNone) return fail(CGAMD_ERR_INVALID, "dist_refresh_values: the handle's stream is being captured");
+    if (int rc = stream_not_capturing(st, "dist_refresh_values")) return rc;
     CG_HIP(hipStreamSynchronize(st));
     d->rhs_set = false;
     d->last_refresh = 0;
@@ -1090,29 +1039,12 @@ int cgamd_dist_refresh_values(cgamd_dist *d) {
             if (had || d->vcodes) drop_graph(d);        // the captured launches hold the old array, or read aValues
             if (rc) {       // the values are in force, read as they are; factors of the old ones must not stay
                 d->last_refresh = -rc;
-                if (d->pre_from_matrix) {
-                    const std::string why = cgamd_last_error();
-                    drop_preconditioner(d);
-                    return fail(rc, why);
-                }
-                return rc;
+                return remove_and_fail(d, rc);
             }
             d->last_refresh = d->vcodes ? 2 : 3;
         }
     }
-    if (d->pre_from_matrix) {
-        const int stride = d->pre_stride;
-        const MgParams p = d->mg_params;
-        const int rc = d->pre_from_matrix == 1   ? cgamd_dist_set_preconditioner_jacobi(d)
-                       : d->pre_from_matrix == 2 ? cgamd_dist_set_preconditioner_line(d, stride)
-                                                 : multigrid_from_cut(d, p.algebraic ? "dist_set_preconditioner_amg" : "dist_set_preconditioner_multigrid", p, true);
-        if (rc) {           // the values are in force; the old factors belong to the old ones
-            const std::string why = cgamd_last_error();
-            drop_preconditioner(d);
-            return fail(rc, why);
-        }
-    }
-    return CGAMD_OK;
+    return rebuild_or_remove(d);
 }
 int cgamd_dist_last_refresh(cgamd_dist *d) { return d ? d->last_refresh : -CGAMD_ERR_INVALID; }
 
@@ -1187,11 +1119,11 @@ int cgamd_dist_attach_p2p(cgamd_dist *d, void *my_mailbox, const void *handles, 
         base[(size_t)r] = static_cast<char *>(m);
     }
     int rc;
-    if ((rc = dalloc((void **)&d->mailbox_dev, sizeof(char *) * (size_t)d->nranks, "mailbox table"))) return rc;
+    if ((rc = dmalloc((void **)&d->mailbox_dev, sizeof(char *) * (size_t)d->nranks, "mailbox table"))) return rc;
     CG_HIP(hipMemcpy(d->mailbox_dev, base.data(), sizeof(char *) * (size_t)d->nranks, hipMemcpyHostToDevice));
     d->mailbox_host = base;
     const size_t epoch_bytes = 64 + sizeof(unsigned) * (size_t)(1 + np);   // 3 epochs, then the work-group counters
-    if ((rc = dalloc((void **)&d->epochs, epoch_bytes, "epochs"))) return rc;
+    if ((rc = dmalloc((void **)&d->epochs, epoch_bytes, "epochs"))) return rc;
     CG_HIP(hipMemset(d->epochs, 0, epoch_bytes));
     std::vector<int> plan((size_t)np * 6 + 1, 0);
     for (int p = 0; p < np; ++p) {
@@ -1202,7 +1134,7 @@ int cgamd_dist_attach_p2p(cgamd_dist *d, void *my_mailbox, const void *handles, 
         plan[(size_t)4 * np + p] = d->recv_off[(size_t)p];
         plan[(size_t)5 * np + p] = d->recv_count[(size_t)p];
     }
-    if ((rc = dalloc((void **)&d->plan_dev, sizeof(int) * plan.size(), "p2p plan"))) return rc;
+    if ((rc = dmalloc((void **)&d->plan_dev, sizeof(int) * plan.size(), "p2p plan"))) return rc;
     CG_HIP(hipMemcpy(d->plan_dev, plan.data(), sizeof(int) * plan.size(), hipMemcpyHostToDevice));
     d->xch_dst_off.assign(dst_offset, dst_offset + np);
     P2pExchange &x = d->xch;
@@ -1249,7 +1181,7 @@ int cgamd_dist_enable_resident(cgamd_dist *d, long long mailbox_values, const in
             dst[(size_t)which * np + p] = d->mailbox_host[(size_t)q] + ds_off(q, which) + ((size_t)rank_n_local[q] + d->xch_dst_off[(size_t)p]) * vs;
         }
     int rc;
-    if (!d->push_dst_dev && (rc = dalloc((void **)&d->push_dst_dev, sizeof(void *) * dst.size(), "slab push table"))) return rc;
+    if (!d->push_dst_dev && (rc = dmalloc((void **)&d->push_dst_dev, sizeof(void *) * dst.size(), "slab push table"))) return rc;
     CG_HIP(hipMemcpy(d->push_dst_dev, dst.data(), sizeof(void *) * dst.size(), hipMemcpyHostToDevice));
     d->ds[0] = d->my_mailbox + ds_off(d->rank, 0);
     d->ds[1] = d->my_mailbox + ds_off(d->rank, 1);
@@ -1280,7 +1212,7 @@ int cgamd_dist_enable_resident(cgamd_dist *d, long long mailbox_values, const in
             if (members < 2) continue;
             const size_t bytes = (mstart.size() + gmember.size()) * sizeof(int);
             if (d->slab_map) { (void)hipFree(d->slab_map); d->slab_map = nullptr; }
-            if ((rc = dalloc((void **)&d->slab_map, bytes, "slab member map"))) return rc;
+            if ((rc = dmalloc((void **)&d->slab_map, bytes, "slab member map"))) return rc;
             CG_HIP(hipMemcpy(d->slab_map, mstart.data(), mstart.size() * sizeof(int), hipMemcpyHostToDevice));
             CG_HIP(hipMemcpy(d->slab_map + mstart.size(), gmember.data(), gmember.size() * sizeof(int), hipMemcpyHostToDevice));
             sp.mstart = d->slab_map; sp.gmember = d->slab_map + mstart.size(); sp.G = members;
@@ -1288,7 +1220,7 @@ int cgamd_dist_enable_resident(cgamd_dist *d, long long mailbox_values, const in
             if (slab_sync_bytes(members) > sp.sync_bytes) {
                 if (d->slab_sync) { (void)hipFree(d->slab_sync); d->slab_sync = nullptr; }
                 sp.sync_bytes = slab_sync_bytes(members);
-                if ((rc = dalloc(&d->slab_sync, sp.sync_bytes, "slab sync words"))) return rc;
+                if ((rc = dmalloc(&d->slab_sync, sp.sync_bytes, "slab sync words"))) return rc;
             }
             break;
         }
@@ -1312,12 +1244,12 @@ int cgamd_dist_index_codes(cgamd_dist *d) { return d ? d->n_offsets : -CGAMD_ERR
 // stream operations per iteration of the loop this handle runs (kernel launches, plus RCCL calls with that backend)
 int cgamd_dist_loop_launches(cgamd_dist *d) {
     if (!d) return -CGAMD_ERR_INVALID;
-    if (d->slab.ok && !d->pre_kind) return 0;
+    if (d->slab.ok && d->pre.kind == Precond::kNone) return 0;
     if (d->cg1) return d->p2p ? 2 : (d->peer.empty() ? 4 : 6);
     // the preconditioned loops replace launches one for one; the stride-1 line sweep in its long form is three launches, not one
     // multigrid: the r update and the r.z partials are launches of their own around the cycle's chain (one more than the sweep they
     // replace), plus every launch of the cycle
-    const int extra = d->pre_kind == 3 ? 1 + mg_cost(d->mg).launches : (d->pre_kind == 2 && d->tri.longform) ? 2 : 0;
+    const int extra = d->pre.kind == Precond::kMg ? 1 + mg_cost(d->pre.mg).launches : (d->pre.kind == Precond::kTri && d->pre.tri.longform) ? 2 : 0;
     if (d->direct && d->p2p_attached) return 4 + extra;
     if (d->p2p) return (d->peer.empty() ? 5 : 7) + extra;
     return (d->peer.empty() ? 9 : 11) + extra;
@@ -1328,7 +1260,7 @@ int cgamd_dist_slab_plan(cgamd_dist *d, int info[8], int *member_start, int cap)
     if (!d || !info) return -CGAMD_ERR_INVALID;
     for (int i = 0; i < 8; ++i) info[i] = 0;
     const SlabPlan &sp = d->slab;
-    if (!sp.ok || d->pre_kind) return 0;
+    if (!sp.ok || d->pre.kind != Precond::kNone) return 0;
     const bool uniform = sp.mstart == nullptr;
     info[0] = 1; info[1] = sp.G; info[2] = sp.rows_m; info[3] = sp.nsteps; info[4] = sp.unroll; info[5] = sp.nsteps <= 10 ? 10 : 12;
     info[6] = (sp.vcodes && sp.vdict && d->tune.value_codes != 0) ? 1 : 0;

@@ -22,6 +22,15 @@ inline int check_launch(const char *what) {
     return CGAMD_OK;
 }
 
+// an entry that copies or synchronises must not run while its stream is being captured: that would end the capture with an error
+inline int stream_not_capturing(hipStream_t st, const char *who) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const hipError_t e = hipStreamIsCapturing(st, &cs);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(CGAMD_ERR_HIP, std::string(who) + ": hipStreamIsCapturing: " + hipGetErrorString(e)); }
+    if (cs != hipStreamCaptureStatusNone) return fail(CGAMD_ERR_INVALID, std::string(who) + ": the handle's stream is being captured");
+    return CGAMD_OK;
+}
+
 // 16-byte vector path of the streaming kernels: every pointer aligned, and with several right-hand sides a leading dimension
 // that keeps each of them aligned
 inline bool vec_ok(int dtype, long long ld, int nrhs, std::initializer_list<const void *> ptrs) {

@@ -536,6 +536,24 @@ int mg_level_state(const MgHierarchy *h, int level, int which, void *out_host, l
     CG_HIP(hipStreamSynchronize(st));
     return CGAMD_OK;
 }
+// one V-cycle on caller vectors (nrhs * n_user device values each, stride n_user), through buffers with the handle's padding rows
+// (n >= n_user rows, the padding zero); synchronises
+int mg_apply_padded(MgHierarchy *h, hipStream_t st, int dtype, int n, int n_user, int nrhs, const void *r_dev, void *z_dev, const char *who) {
+    const size_t vs = dtype_size(dtype), row = (size_t)n * vs, user = (size_t)n_user * vs, bytes = row * (size_t)nrhs;
+    void *buf = nullptr;
+    if (int rc = dmalloc(&buf, 2 * bytes, "mg_apply vectors")) return rc;
+    void *r = buf, *z = static_cast<char *>(buf) + bytes;
+    int rc = CGAMD_OK;
+    hipError_t e = hipMemsetAsync(buf, 0, 2 * bytes, st);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(r, row, r_dev, user, user, (size_t)nrhs, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) rc = mg_vcycle(h, r, z, st);
+    if (e == hipSuccess && !rc) e = hipMemcpy2DAsync(z_dev, user, z, row, user, (size_t)nrhs, hipMemcpyDeviceToDevice, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    (void)hipFree(buf);
+    if (rc) return rc;
+    if (e != hipSuccess || e2 != hipSuccess) return fail(CGAMD_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e != hipSuccess ? e : e2));
+    return CGAMD_OK;
+}
 int mg_level_spmv(const MgHierarchy *h, int level, const void *x, void *w, hipStream_t st) {
     if (level < 0 || level >= (int)h->lv.size()) return fail(CGAMD_ERR_INVALID, "mg_level_spmv: no such level");
     const MgLevel &L = h->lv[(size_t)level];

@@ -12,12 +12,6 @@
 
 namespace cgamd {
 
-static int dmalloc(void **p, size_t bytes, const char *what) {
-    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-    if (e != hipSuccess)
-        return fail(CGAMD_ERR_ALLOC, std::string("hipMalloc(") + what + ", " + std::to_string(bytes) + " B): " + hipGetErrorString(e));
-    return CGAMD_OK;
-}
 
 void tri_built_free(TriBuilt *b) {
     if (b->coef) (void)hipFree(b->coef);

@@ -346,11 +346,7 @@ static int proj_op_check(cgamd_ctx *c, int dtype, int size, long long ld, int sl
     if (slots < 0 || slots > kProjMaxSlots) return fail(CGAMD_ERR_INVALID, std::string(who) + ": slots runs 0 ... 32");
     thread_hip_setup();
     CG_HIP(hipSetDevice(c->device));
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const hipError_t e = hipStreamIsCapturing(c->stream, &cs);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(CGAMD_ERR_HIP, std::string(who) + ": hipStreamIsCapturing: " + hipGetErrorString(e)); }
-    if (cs != hipStreamCaptureStatusNone) return fail(CGAMD_ERR_INVALID, std::string(who) + ": the context's stream is being captured");
-    return CGAMD_OK;
+    return stream_not_capturing(c->stream, who);
 }
 
 extern "C" {

@@ -224,9 +224,6 @@ extern "C" int cgamd_shift_update(cgamd_ctx *ctx, int dtype, int size, long long
     if (!r || !xs || !ds || !alpha_s || !beta_s || !zeta_s) return fail(CGAMD_ERR_INVALID, "shift_update: null pointer");
     thread_hip_setup();
     CG_HIP(hipSetDevice(ctx->device));
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const hipError_t e = hipStreamIsCapturing(ctx->stream, &cs);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(CGAMD_ERR_HIP, std::string("shift_update: hipStreamIsCapturing: ") + hipGetErrorString(e)); }
-    if (cs != hipStreamCaptureStatusNone) return fail(CGAMD_ERR_INVALID, "shift_update: the context's stream is being captured");
+    if (int rc = stream_not_capturing(ctx->stream, "shift_update")) return rc;
     return launch_shift_update(dtype, size, ld, nRHS, nShifts, r, xs, ds, alpha_s, beta_s, zeta_s, ctx->stream, 0);
 }

@@ -19,147 +19,12 @@
 
 #include "cgamd_internal.h"
 #include "launch_util.h"
+#include "solver_handle.h"
 #include "spmv_device.h"
 #include "xcd_schedule.h"
 
 using namespace cgamd;
 
-struct cgamd_solver {
-    Tuning tune;            // configuration this handle was created under (installed per call: TuneScope)
-    cgamd_ctx *ctx = nullptr;
-    int dtype = 0, n = 0, nrhs = 1, flags = 0;
-    // n is the size every kernel of the handle works on; n_user the caller's.  They differ when `size` is not a whole number of
-    // 16-byte packs (odd sizes in fp64 / complex64, not a multiple of 4 in fp32): the system is then carried with 1-3 EMPTY rows
-    // appended (row pointers repeated, b = x0 = 0 there, so r, d, q and x stay exactly 0 in them and every sum gains exact zeros),
-    // which keeps every right-hand side's vectors 16-byte aligned: the vectorised multi-RHS kernels and the resident loops apply
-    // to any size.  The caller's arrays keep their own stride (strided copies in set_rhs / get_x).
-    int n_user = 0;
-    // cgamd_solver_create_batched: nsys systems on one pattern, the values of system r at vals + r * nnz and right-hand side r its
-    // own; 0 = every other handle (one matrix for all right-hand sides).  A batched handle has nrhs == nsys, runs the launched loops
-    // only (no resident loop, no row-major layout, no codes) and launches its SpMV through launch_spmv_batched.  Its preconditioner is
-    // one M per system (cgamd_solver_set_preconditioner_batched*): mdiag holds nsys diagonals at stride n, tri the factors of every
-    // system at tri.fpitch on one segment plan.
-    int nsys = 0;
-    // CGAMD_HERMITIAN on a complex value type (hermitian.hip): the conjugated recurrence, on a four-launch loop of its own -- no
-    // resident, chip-wide or two-launch loop, no row-major layout, no deferred x update.  dc = conj(d), the vector of the SpMV's fused
-    // dot, lives in the d2 slot, which those loops alone use.  Never set for the real types: the flag changes nothing there.
-    bool herm = false;
-    bool own_ptr = false;   // a borrowed device matrix whose row pointers were copied to append the padding rows
-    long long nnz = 0;
-    void *vals = nullptr;
-    int *ptr = nullptr, *cols = nullptr;
-    bool own_matrix = false;
-    std::vector<int> ptr_host;   // own_matrix: the row pointers as uploaded (cgamd_solver_reload_matrix compares against them)
-    SpmvPlan plan;
-    int vgrid = 1;
-    void *x = nullptr, *r = nullptr, *d = nullptr, *q = nullptr, *b = nullptr;
-    void *slab = nullptr;   // backing store of x, r, d, q, b
-    void *part_dq = nullptr, *part_rr = nullptr;
-    size_t part_dq_cap = 0;      // entries per RHS
-    // diagonal preconditioner (cgamd_solver_set_preconditioner): z = mdiag .* r; r.z partials; rho parity buffer
-    void *mdiag = nullptr, *part_rz = nullptr, *rho2 = nullptr;
-    // tridiagonal preconditioner (cgamd_solver_set_preconditioner_tridiag and its strided form): factors, chunk plan (strided: the
-    // segment list, in tri_cstart as well), r.z / r.r partials [2][nrhs][grid]; z lives in q's storage (q is dead between the r
-    // update and the next SpMV)
-    bool tri_on = false;
-    TriLaunch tri;
-    void *tri_coef = nullptr, *tri_part = nullptr;
-    int *tri_cstart = nullptr;
-    // where the preconditioner in force came from (cgamd_solver_preconditioner_source: 0 none, 1 the caller's arrays, 2 / 3 the
-    // matrix) and, for one built from the matrix, what cgamd_solver_reload_matrix builds again: kind 1 = Jacobi, 2 = the lines at
-    // pre_stride
-    int pre_source = 0, pre_kind = 0, pre_stride = 0;
-    // aggregation multigrid preconditioner (cgamd_solver_set_preconditioner_multigrid, on a batched handle _batched_multigrid: one
-    // hierarchy per system inside the same MgHierarchy; multigrid_setup.cpp): the hierarchy and what it
-    // was built with (pre_kind 3: refresh_values / reload_matrix build it again).  z lives in q's storage, like the line sweeps';
-    // r.r partials in part_rr, r.z partials in part_rz, vgrid of each
-    MgHierarchy *mg = nullptr;
-    MgParams mg_params;
-    CgScalars sc;
-    bool rhs_set = false;
-    int iters = 0;  // iterations enqueued since set_rhs
-    // captured iteration sequences, per parity of the iteration count they start at (the two-launch loop ping-pongs d)
-    hipGraphExec_t g1[2] = {nullptr, nullptr}, gU[2] = {nullptr, nullptr};
-    hipGraph_t g1g[2] = {nullptr, nullptr}, gUg[2] = {nullptr, nullptr};
-    int U = 8;
-    bool graph_failed = false;
-    // row-major multi-RHS path (rowmajor.hip): x, r, d, q, b hold [n][nrhs]; rm_ok is decided at creation, `rm` per set_rhs
-    bool rm_ok = false, rm = false;
-    int rm_nwg = 0, rm_vgrid = 0;
-    size_t part_rr_cap = 0;
-    int *rm_pace = nullptr;     // progress counters of the paced SpMM sweep (kSpmmPaceInts, zero between launches)
-    // event hooks around the SpMV launch of enqueue_iteration (cgamd_solver_iterate_timed)
-    hipEvent_t *ev_pair = nullptr;
-    // two-launch loop (small systems): d of iteration k lives in dbuf[k & 1] (dbuf[0] = d, the initial r); decided at creation
-    bool fused2 = false;
-    void *d2 = nullptr;
-    // x brought up to date once per x_lag iterations inside a captured U-iteration graph of the three / four-launch loop (vector.hip):
-    // direction buffer 0 = d, 1 = d2, 2 .. x_lag - 1 in dlag.  Decided by setup_x_lag; 1 = x updated in every iteration
-    int x_lag = 1;
-    void *dlag = nullptr;
-    size_t dlag_pitch = 0;
-    int dlag_bufs = 0;
-    // resident loop (resident.hip): iterate() calls of a small system in ONE launch; decided with fused2
-    bool res_ok = false;
-    ResidentPlan res;
-    void *res_sync = nullptr;
-    int n_cus = 0;
-    // wide resident loop: one chip-wide group for a single right-hand side (resident.hip)
-    ResidentWidePlan resw;
-    void *resw_sync = nullptr;
-    unsigned char *codes = nullptr;   // one-byte column codes of the single-RHS SpMV (build_index_codes), with their dictionary
-    int *dict = nullptr;
-    int n_offsets = 0;                // distinct (column - row) offsets behind the codes; 0 = the SpMV reads aCols
-    unsigned char *vcodes = nullptr;  // one-byte value codes on top of the one-byte column codes (build_value_codes), with their dictionary
-    void *vdict = nullptr;
-    int n_values = 0;                 // distinct matrix entries behind the value codes; 0 = the SpMV reads aValues
-    unsigned char *jcodes = nullptr;  // one-byte joint (offset, value) codes where at most 256 pairs occur (build_joint_codes)
-    int *jdict_off = nullptr;
-    void *jdict_val = nullptr;
-    int n_pairs = 0;
-    unsigned char *rcodes = nullptr;  // one-byte row-pattern codes where at most 256 patterns of at most 7 entries occur (build_row_codes)
-    void *rdict = nullptr;            // their dictionary: values, byte offsets, lengths (row_dict_bytes)
-    unsigned char *pcodes = nullptr;  // one byte per PAIR of rows on top of the row codes (build_row_pairs), and their dictionary
-    void *pdict = nullptr;
-    int n_pair_patterns = 0;
-    int n_patterns = 0, n_user_patterns = 0;     // dictionary entries; patterns of the caller's rows (the appended empty rows may add one)
-    int *sched = nullptr;             // plane-matched XCD schedule of the row- / pair-coded SpMV (setup_xcd_schedule): plan.sched_grid ints
-    long long sched_unit = 0;         // the largest |column - row| among the row dictionary's entries, in rows (0: no row codes)
-    // cgamd_solver_iterate_tol: tolerance of the device-side stop for the call in progress (0 = none), and what it reported
-    double tol_req = 0.;
-    bool tol_served = false, tol_stopped = false;
-    // cgamd_solver_iterate_until: the per-right-hand-side stop (StopRun: allocated at the first call, armed once per set_rhs) and the
-    // captured chunk of guarded iterations.  until_mode: since the first call after set_rhs the handle runs its three / four-launch
-    // loop only (d in one buffer, updated at the end of every iteration); until_stopped: a right-hand side has stopped, so the columns
-    // are at different iterations and only iterate_until goes on.
-    StopRun stop;
-    bool until_mode = false, until_stopped = false;
-    hipGraphExec_t gT = nullptr;
-    hipGraph_t gTg = nullptr;
-    int gT_len = 0;
-    int last_refresh = 0;           // what the last cgamd_solver_refresh_values did (cgamd_solver_last_refresh)
-    // solution projection (cgamd_solver_projection_enable; projection.hip): `cap` slots of nrhs vectors at stride n each, `m` of them
-    // held; once m == cap the slots form a ring and `head` is the oldest.  One allocation `scal` holds alpha and c (cap x nrhs values
-    // each), t (nrhs values), <e, q>, nu and the (nu, s) record (accumulators) and the added flags.  projected: the right-hand side in
-    // force came through cgamd_solver_set_rhs_projected; spent: its update has run (q and d hold the update's vectors: set_rhs is next)
-    struct Projection {
-        int cap = 0, m = 0, head = 0, grid = 0;
-        double drop_tol = 0.;
-        void *W = nullptr, *x0 = nullptr, *scal = nullptr, *partials = nullptr;
-        void *alpha = nullptr, *c = nullptr, *t = nullptr, *eq = nullptr, *nu = nullptr, *nus = nullptr;
-        int *added = nullptr;
-        bool projected = false, spent = false;
-    } proj;
-    int captures = 0;               // graphs captured since creation (cgamd_solver_graph_captures)
-    // multi-shift CG (cgamd_solver_set_shifts; shifts.hip): view.S shifted systems ride on the seed recurrence.  vec = x_j then d_j,
-    // [2][S][nrhs][n] values; scal = sigma, the state and the coefficients behind `view`; view.history = zeta_k, grown with the seed's
-    // history (ensure_history).  While view.S > 0 every set_rhs puts the handle into until_mode: the three / four-launch loop alone,
-    // d in one buffer, x updated in every iteration, and behind its d step the two launches of shifts.hip
-    struct Shifts {
-        ShiftScalars view;
-        void *vec = nullptr, *scal = nullptr;
-    } sh;
-};
 static int nshifts(const cgamd_solver *s) { return s->sh.view.S; }
 static void *shift_xs(const cgamd_solver *s) { return s->sh.vec; }
 static void *shift_ds(const cgamd_solver *s) { return static_cast<char *>(s->sh.vec) + dtype_size(s->dtype) * (size_t)nshifts(s) * s->nrhs * s->n; }
@@ -169,7 +34,7 @@ static void shifts_free(cgamd_solver *s) {
     s->sh = cgamd_solver::Shifts();
 }
 
-static void destroy_graphs(cgamd_solver *s) {
+void cgamd::destroy_graphs(cgamd_solver *s) {
     for (int p = 0; p < 2; ++p) {
         if (s->g1[p]) (void)hipGraphExecDestroy(s->g1[p]);
         if (s->gU[p]) (void)hipGraphExecDestroy(s->gU[p]);
@@ -192,18 +57,6 @@ static void proj_free(cgamd_solver *s) {
 static void proj_clear(cgamd_solver *s) { s->proj.m = s->proj.head = 0; s->proj.projected = s->proj.spent = false; }
 static const char *kProjSpent = ": cgamd_solver_projection_update has used the handle's q and d storage: call set_rhs (of either kind) first";
 
-static void drop_multigrid(cgamd_solver *s) {
-    if (s->mg) mg_free(s->mg);
-    s->mg = nullptr;
-}
-
-static int dmalloc(void **p, size_t bytes, const char *what) {
-    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-    if (e != hipSuccess)
-        return fail(CGAMD_ERR_ALLOC, std::string("hipMalloc(") + what + ", " + std::to_string(bytes) + " B): " + hipGetErrorString(e));
-    return CGAMD_OK;
-}
-
 static int validate_csr_host(int n, long long nnz, const int *ptr, const int *cols) {
     if (ptr[0] != 0) return fail(CGAMD_ERR_INVALID, "CSR: aPointers[0] != 0");
     for (int i = 0; i < n; ++i)
@@ -216,9 +69,7 @@ static int validate_csr_host(int n, long long nnz, const int *ptr, const int *co
 
 // the SpMV (SpMM) launch of the iteration, bracketed by the caller's event pair when one is installed
 static void *dbuf(cgamd_solver *s, int k) { return (s->fused2 && !s->until_mode && (k & 1)) ? s->d2 : s->d; }
-// a preconditioner (diagonal or tridiagonal) is set: what decides the loop family; s->mdiag is read where the diagonal is used
-static bool precond_set(const cgamd_solver *s) { return s->mdiag != nullptr || s->tri_on || s->mg != nullptr; }
-// values between the diagonals of consecutive right-hand sides in s->mdiag: a batched handle keeps one per system, else one for all
+// values between the diagonals of consecutive right-hand sides in s->pre.mdiag: a batched handle keeps one per system, else one for all
 static long long m_pitch(const cgamd_solver *s) { return s->nsys ? s->n : 0; }
 static bool fused2_now(const cgamd_solver *s) { return s->fused2 && !s->rm && !precond_set(s) && !(s->flags & CGAMD_UNFUSED) && !s->until_mode; }
 
@@ -246,7 +97,7 @@ static int enqueue_spmv(cgamd_solver *s, int k, hipStream_t st, void *dvec = nul
                                s->part_rr, s->vgrid, s->sc, st);
     else if (s->rm) rc = launch_spmm_rm(dt, n, s->nnz, s->vals, s->ptr, s->cols, s->d, s->q, nr, s->part_dq, s->plan.max_quad, s->rm_pace, st);
     // (the preconditioned loops of a batched handle take alpha from the d.q partials whatever the flags)
-    else if ((s->flags & CGAMD_UNFUSED) && !s->tri_on && !(s->nsys && s->mdiag)) rc = handle_spmv(s, n, s->d, n, s->q, n, nullptr, nullptr, st);
+    else if ((s->flags & CGAMD_UNFUSED) && !tri_on(s) && !(s->nsys && s->pre.mdiag)) rc = handle_spmv(s, n, s->d, n, s->q, n, nullptr, nullptr, st);
     else if (s->herm) rc = handle_spmv(s, n, s->d, n, s->q, n, s->d2, s->part_dq, st);       // the dot against dc = conj(d): d^H q
     else rc = handle_spmv(s, n, dvec ? dvec : s->d, n, s->q, n, dvec ? dvec : s->d, s->part_dq, st);
     set_kernel_event_pair(nullptr);
@@ -257,16 +108,13 @@ static int enqueue_spmv(cgamd_solver *s, int k, hipStream_t st, void *dvec = nul
 
 // r -= alpha q (update) and z = M^-1 r of a tridiagonal M, by the kernel of its form: the scan sweep of rows i +- 1 (precond.hip) or
 // one thread per segment of rows i +- stride (precond_strided.hip)
-struct TriPartials { void *rz, *rr; };
-// the r.z and r.r partials of the sweeps: the two halves of s->tri_part, [nrhs][grid] each
-static TriPartials tri_partials(const cgamd_solver *s) {
-    return {s->tri_part, static_cast<char *>(s->tri_part) + acc_size(s->dtype) * (size_t)s->tri.grid * s->nrhs};
-}
+// the r.z and r.r partials of the sweeps: the two halves of s->pre.tri_part, [nrhs][grid] each
+static PcgPartials tri_partials(const cgamd_solver *s) { return pcg_partials(s->pre.tri_part, s->dtype, s->pre.tri.grid, s->nrhs); }
 static int enqueue_tri_sweep(cgamd_solver *s, bool update, const void *q, void *z, hipStream_t st, const CgStop *g = nullptr) {
     const void *alpha = update ? s->sc.alpha : nullptr;
-    const TriPartials p = tri_partials(s);
-    if (s->tri.stride > 1) return launch_pcg_tri_strided(s->dtype, s->tri, update, q, s->r, z, s->n, alpha, s->nrhs, p.rz, p.rr, st, g);
-    return launch_pcg_tri(s->dtype, s->tri, update, q, s->r, z, s->n, alpha, s->nrhs, p.rz, p.rr, st, g);
+    const PcgPartials p = tri_partials(s);
+    if (s->pre.tri.stride > 1) return launch_pcg_tri_strided(s->dtype, s->pre.tri, update, q, s->r, z, s->n, alpha, s->nrhs, p.rz, p.rr, st, g);
+    return launch_pcg_tri(s->dtype, s->pre.tri, update, q, s->r, z, s->n, alpha, s->nrhs, p.rz, p.rr, st, g);
 }
 
 // Deferred x update: the lag the captured U-iteration graphs of this handle run with NOW (1 = none).  s->x_lag is what creation
@@ -327,32 +175,32 @@ static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st, int lag = 1
     if (s->herm) {    // conjugated recurrence (hermitian.hip), with or without a diagonal M; delta holds rho
         if ((rc = enqueue_spmv(s, k, st))) return rc;
         if ((rc = launch_herm_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st, g))) return rc;
-        if ((rc = launch_herm_axpy_dot(dt, n, s->q, s->r, s->mdiag, m_pitch(s), n, s->sc.alpha, nr, s->part_rz, s->part_rr, s->vgrid, st, g))) return rc;
-        return launch_herm_aypx_beta_x(dt, n, s->r, s->d, s->d2, s->x, s->mdiag, m_pitch(s), n, s->part_rz, s->part_rr, s->vgrid, nr, s->sc,
-                                       s->rho2, st, g);
+        if ((rc = launch_herm_axpy_dot(dt, n, s->q, s->r, s->pre.mdiag, m_pitch(s), n, s->sc.alpha, nr, s->part_rz, s->part_rr, s->vgrid, st, g))) return rc;
+        return launch_herm_aypx_beta_x(dt, n, s->r, s->d, s->d2, s->x, s->pre.mdiag, m_pitch(s), n, s->part_rz, s->part_rr, s->vgrid, nr, s->sc,
+                                       s->pre.rho2, st, g);
     }
-    if (s->mg) {      // multigrid M: r -= alpha q (+ r.r), z = V-cycle(r) in q's storage, r.z, then the tridiagonal loop's last launch
+    if (s->pre.mg) {      // multigrid M: r -= alpha q (+ r.r), z = V-cycle(r) in q's storage, r.z, then the tridiagonal loop's last launch
         if ((rc = enqueue_spmv(s, k, st))) return rc;
         if ((rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st, g))) return rc;
         if ((rc = launch_axpy_dot(dt, n, s->q, s->r, n, s->sc.alpha, nr, s->part_rr, s->vgrid, st, s->plan.vec_nt, g))) return rc;
         // (unguarded under iterate_until: z of a frozen right-hand side is read by nothing that writes)
-        if ((rc = mg_vcycle(s->mg, s->r, s->q, st))) return rc;
+        if ((rc = mg_vcycle(s->pre.mg, s->r, s->q, st))) return rc;
         if ((rc = launch_dot_partials(dt, n, s->r, s->q, n, nr, s->part_rz, s->vgrid, st))) return rc;
-        return launch_pcg_aypx_beta_z(dt, n, s->d, s->q, n, s->part_rz, s->part_rr, s->vgrid, nr, s->sc, s->rho2, s->x, st, g);
+        return launch_pcg_aypx_beta_z(dt, n, s->d, s->q, n, s->part_rz, s->part_rr, s->vgrid, nr, s->sc, s->pre.rho2, s->x, st, g);
     }
-    if (s->tri_on) {  // tridiagonal M (helmFE_var.py:561-562): z = M^-1 r by the line sweeps, in q's storage
+    if (tri_on(s)) {  // tridiagonal M (helmFE_var.py:561-562): z = M^-1 r by the line sweeps, in q's storage
         if ((rc = enqueue_spmv(s, k, st))) return rc;
         if ((rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st, g))) return rc;
         if ((rc = enqueue_tri_sweep(s, true, s->q, s->q, st, g))) return rc;
-        const TriPartials p = tri_partials(s);
-        return launch_pcg_aypx_beta_z(dt, n, s->d, s->q, n, p.rz, p.rr, s->tri.grid, nr, s->sc, s->rho2, s->x, st, g);
+        const PcgPartials p = tri_partials(s);
+        return launch_pcg_aypx_beta_z(dt, n, s->d, s->q, n, p.rz, p.rr, s->pre.tri.grid, nr, s->sc, s->pre.rho2, s->x, st, g);
     }
-    if (s->mdiag) {   // preconditioned recurrence (helmFE_var.py:560-585); delta holds rho = r.z
+    if (s->pre.mdiag) {   // preconditioned recurrence (helmFE_var.py:560-585); delta holds rho = r.z
         if ((rc = enqueue_spmv(s, k, st))) return rc;
         if ((rc = launch_cg_alpha(dt, s->part_dq, s->plan.n_partials, nr, s->sc, st, g))) return rc;
-        if ((rc = launch_pcg_axpy2_dot2(dt, false, n, s->d, s->x, s->q, s->r, s->mdiag, n, s->sc.alpha, nr, s->part_rz, s->part_rr,
+        if ((rc = launch_pcg_axpy2_dot2(dt, false, n, s->d, s->x, s->q, s->r, s->pre.mdiag, n, s->sc.alpha, nr, s->part_rz, s->part_rr,
                                         s->vgrid, st, m_pitch(s), g))) return rc;
-        return launch_pcg_aypx_beta(dt, n, s->r, s->d, s->mdiag, n, s->part_rz, s->part_rr, s->vgrid, nr, s->sc, s->rho2, s->x, st, m_pitch(s), g);
+        return launch_pcg_aypx_beta(dt, n, s->r, s->d, s->pre.mdiag, n, s->part_rz, s->part_rr, s->vgrid, nr, s->sc, s->pre.rho2, s->x, st, m_pitch(s), g);
     }
     if (!(s->flags & CGAMD_UNFUSED)) {
         if ((rc = enqueue_spmv(s, k, st))) return rc;
@@ -386,12 +234,12 @@ static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st, int lag = 1
 // the size, and every prologue sum in the member-blocked order (reduce_device.h thread_partials; K = the blocks of one member).
 // So iterate(15) twice and iterate(30) return the same bits although the first takes the launched loop and the second the
 // resident one.  Called whenever the wide plan may have changed; captured graphs hold grids and orders, so they go when it did.
-static void apply_wide_order(cgamd_solver *s) {
+void cgamd::apply_wide_order(cgamd_solver *s) {
     if (s->nsys) return;        // a batched handle has no resident loop to match
     const int E = (int)(16 / dtype_size(s->dtype));
     // (where the one-XCD resident loop applies it runs, with the strided order -- unless a preconditioner is set: that recurrence only
     // has the chip-wide form; the tridiagonal one has none)
-    const bool wide = s->resw.ok && !s->tri_on && !s->mg && (!s->res_ok || precond_set(s));
+    const bool wide = s->resw.ok && !tri_on(s) && !s->pre.mg && (!s->res_ok || precond_set(s));
     const int kdq = wide ? kResWideBlocksPerRpt * s->resw.rpt : 0, krr = wide ? kdq / E : 0;
     const int vgrid = wide ? (s->n / E + kBlock - 1) / kBlock : vec_grid(s->n, s->dtype, s->nrhs);
     const int fold_max = 0;      // (alpha folded beyond 2048 partials was tried for these handles: every work-group summing 3907 partials, 1M rows 30 -> 52 us)
@@ -402,7 +250,7 @@ static void apply_wide_order(cgamd_solver *s) {
 }
 
 // the resident loop applies where the two-launch loop does and the matrix slices fit LDS (needs the row pointers on the host)
-static int setup_resident_wide_plan(cgamd_solver *s) {
+int cgamd::setup_resident_wide_plan(cgamd_solver *s) {
     s->resw.ok = false;
     if (tune().resident_wide == 0 || tune().resident == 0 || (s->flags & CGAMD_UNFUSED)) return CGAMD_OK;
     if (s->rm_ok && tune().spmm_rowmajor >= 2) return CGAMD_OK;      // the row-major loop was asked for
@@ -563,7 +411,7 @@ static int setup_resident_local(cgamd_solver *s) {
     if (int rc = setup_resident_one_xcd(s)) return rc;
     // where the one-XCD loop applies the chip-wide plan is only needed once a preconditioner is set (that recurrence has no one-XCD
     // form): cgamd_solver_set_preconditioner asks for it then -- the stateless cg() entry reloads per call and would pay the scan
-    if (s->res_ok && !s->mdiag) return CGAMD_OK;
+    if (s->res_ok && !s->pre.mdiag) return CGAMD_OK;
     return setup_resident_wide_plan(s);
 }
 static int setup_resident_one_xcd(cgamd_solver *s) {
@@ -856,6 +704,21 @@ static int create_impl(const std::string &who, cgamd_ctx *ctx, int dtype, int si
     return CGAMD_OK;
 }
 
+// a batched handle (cgamd_solver_create_batched) has a matrix per right-hand side: one M shared by all of them preconditions none
+int cgamd::batched_refuses(const char *who) {
+    return fail(CGAMD_ERR_STATE, std::string(who) + ": the handle is batched (a matrix of its own per right-hand side); a preconditioner "
+                                                    "shared by all right-hand sides has no meaning for different systems");
+}
+// what a CGAMD_HERMITIAN handle does not serve: refused before anything on the handle changes
+int cgamd::herm_refuses(const char *who, const char *why) {
+    return fail(CGAMD_ERR_STATE, std::string(who) + ": the handle runs the conjugated recurrence (CGAMD_HERMITIAN), " + why);
+}
+// with shifts in force (cgamd_solver_set_shifts) the handle serves the unpreconditioned recurrence from x0 = 0 alone: a preconditioned
+// operator is not a shift of anything.  Refused before anything on the handle changes
+int cgamd::shifts_refuse(const cgamd_solver *s, const char *who) {
+    if (!s->sh.view.S) return CGAMD_OK;
+    return fail(CGAMD_ERR_STATE, std::string(who) + ": shifts are in force (cgamd_solver_set_shifts), which this entry does not serve; remove them first");
+}
 extern "C" {
 
 int cgamd_solver_create(cgamd_ctx *ctx, int dtype, int size, long long nnz, const void *aValues, const int *aPointers,
@@ -873,39 +736,7 @@ int cgamd_solver_create_batched(cgamd_ctx *ctx, int dtype, int size, long long n
 int cgamd_solver_systems(cgamd_solver *s) { return s ? s->nsys : -CGAMD_ERR_INVALID; }
 int cgamd_solver_hermitian(cgamd_solver *s) { return s ? (s->herm ? 1 : 0) : -CGAMD_ERR_INVALID; }
 
-static int diag_impl(cgamd_solver *s, const void *m, int on_device);
-// a batched handle (cgamd_solver_create_batched) has a matrix per right-hand side: one M shared by all of them preconditions none
-static int batched_refuses(const char *who) {
-    return fail(CGAMD_ERR_STATE, std::string(who) + ": the handle is batched (a matrix of its own per right-hand side); a preconditioner "
-                                                    "shared by all right-hand sides has no meaning for different systems");
-}
-// what a CGAMD_HERMITIAN handle does not serve: refused before anything on the handle changes
-static int herm_refuses(const char *who, const char *why) {
-    return fail(CGAMD_ERR_STATE, std::string(who) + ": the handle runs the conjugated recurrence (CGAMD_HERMITIAN), " + why);
-}
-// with shifts in force (cgamd_solver_set_shifts) the handle serves the unpreconditioned recurrence from x0 = 0 alone: a preconditioned
-// operator is not a shift of anything.  Refused before anything on the handle changes
-static int shifts_refuse(const cgamd_solver *s, const char *who) {
-    if (!s->sh.view.S) return CGAMD_OK;
-    return fail(CGAMD_ERR_STATE, std::string(who) + ": shifts are in force (cgamd_solver_set_shifts), which this entry does not serve; remove them first");
-}
-constexpr const char *kHermNoLines = "whose preconditioner is diagonal: the line sweeps form the unconjugated r.z and r.r";
-static int line_from_matrix(cgamd_solver *s, const std::string &who, int stride);
-static int jacobi_from_matrix(cgamd_solver *s, const std::string &who);
-static int batched_line_from_matrix(cgamd_solver *s, const std::string &who, int stride);
-static int batched_jacobi_from_matrix(cgamd_solver *s, const std::string &who);
-static int multigrid_from_matrix(cgamd_solver *s, const std::string &who, const MgParams &p);
-static int step_not_capturing(cgamd_solver *s, const char *who);
-// the per-system preconditioner a batched handle built from its matrices, built again from the values as they are now
-static int rebuild_from_matrix_batched(cgamd_solver *s, const std::string &who) {
-    if (s->pre_kind == 3) return multigrid_from_matrix(s, who, s->mg_params);
-    return s->pre_kind == 1 ? batched_jacobi_from_matrix(s, who) : batched_line_from_matrix(s, who, s->pre_stride);
-}
-// the preconditioner a non-batched handle built from its matrix, built again from the matrix as it is now
-static int rebuild_from_matrix(cgamd_solver *s, const std::string &who) {
-    if (s->pre_kind == 3) return multigrid_from_matrix(s, who, s->mg_params);
-    return s->pre_kind == 1 ? jacobi_from_matrix(s, who) : line_from_matrix(s, who, s->pre_stride);
-}
+static int step_not_capturing(cgamd_solver *s, const char *who) { return stream_not_capturing(s->ctx->stream, who); }
 
 // New matrix VALUES / PATTERN of the same size into an existing handle (host arrays; the handle must own its matrix):
 // what the stateless cg() needs to reuse its cached device state -- allocations, stream, captured graphs -- from one call
@@ -944,15 +775,7 @@ int cgamd_solver_reload_matrix(cgamd_solver *s, const void *aValues, const int *
     }
     if (s->nsys) {                                  // no resident loop, no codes; a per-system preconditioner built from the matrices follows them
         CG_HIP(hipStreamSynchronize(st));
-        if (s->pre_source >= 2) {
-            const int rc = rebuild_from_matrix_batched(s, "reload_matrix");
-            if (rc) {                               // the matrices are loaded; the old factors belong to the old ones
-                const std::string why = cgamd_last_error();
-                (void)diag_impl(s, nullptr, 0);
-                return fail(rc, why);
-            }
-        }
-        return CGAMD_OK;
+        return rebuild_or_remove(s, "reload_matrix");
     }
     if (int rc = setup_resident(s)) return rc;      // also with unchanged row pointers: the column range of a row slice may have moved
     {                                               // the columns were replaced: their codes go with them
@@ -963,15 +786,7 @@ int cgamd_solver_reload_matrix(cgamd_solver *s, const void *aValues, const int *
     }
     setup_x_lag(s);                     // (the default rule follows the number of d.q partials and the resident plan)
     CG_HIP(hipStreamSynchronize(st));   // the host arrays may go away after return
-    if (s->pre_source >= 2) {           // a preconditioner built from the matrix follows it (one from the caller's arrays is kept)
-        const int rc = rebuild_from_matrix(s, "reload_matrix");
-        if (rc) {                       // the matrix is loaded; the old factors belong to the old one
-            const std::string why = cgamd_last_error();
-            (void)diag_impl(s, nullptr, 0);
-            return fail(rc, why);
-        }
-    }
-    return CGAMD_OK;
+    return rebuild_or_remove(s, "reload_matrix");       // a preconditioner built from the matrix follows it
 }
 
 // New VALUES on the SAME pattern (include/cgamd.h): everything made from the values follows them -- the value, joint and row-pattern
@@ -1015,12 +830,7 @@ int cgamd_solver_refresh_values(cgamd_solver *s, const void *aValues, int on_dev
     TuneScope ts(&s->tune);
     CG_HIP(hipSetDevice(s->ctx->device));
     hipStream_t st = s->ctx->stream;
-    {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        const hipError_t e = hipStreamIsCapturing(st, &cs);
-        if (e != hipSuccess) { (void)hipGetLastError(); return fail(CGAMD_ERR_HIP, std::string("refresh_values: hipStreamIsCapturing: ") + hipGetErrorString(e)); }
-        if (cs != hipStreamCaptureStatusNone) return fail(CGAMD_ERR_INVALID, "refresh_values: the handle's stream is being captured");
-    }
+    if (int rc = stream_not_capturing(st, "refresh_values")) return rc;
     s->rhs_set = false;
     s->last_refresh = 0;
     proj_clear(s);
@@ -1032,24 +842,9 @@ int cgamd_solver_refresh_values(cgamd_solver *s, const void *aValues, int on_dev
     }
     if (int rc = refresh_codes(s)) {        // the values are in force, read as they are; factors of the old ones must not stay
         s->last_refresh = -rc;
-        if (s->pre_source >= 2) {
-            const std::string why = cgamd_last_error();
-            (void)diag_impl(s, nullptr, 0);
-            return fail(rc, why);
-        }
-        return rc;
+        return remove_and_fail(s, rc);
     }
-    if (s->pre_source >= 2) {               // a preconditioner built from the matrix follows it (one from the caller's arrays is kept)
-        int rc;
-        if (s->nsys) rc = rebuild_from_matrix_batched(s, "refresh_values");
-        else rc = rebuild_from_matrix(s, "refresh_values");
-        if (rc) {                           // the values are in force; the old factors belong to the old ones
-            const std::string why = cgamd_last_error();
-            (void)diag_impl(s, nullptr, 0);
-            return fail(rc, why);
-        }
-    }
-    return CGAMD_OK;
+    return rebuild_or_remove(s, "refresh_values");      // a preconditioner built from the matrix follows it
 }
 int cgamd_solver_last_refresh(cgamd_solver *s) { return s ? s->last_refresh : -CGAMD_ERR_INVALID; }
 int cgamd_solver_graph_captures(cgamd_solver *s) { return s ? s->captures : -CGAMD_ERR_INVALID; }
@@ -1060,7 +855,7 @@ int cgamd_solver_destroy(cgamd_solver *s) {
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
     destroy_graphs(s);
-    drop_multigrid(s);
+    precond_drop(&s->pre);
     proj_free(s);
     shifts_free(s);
     free_long_rows(&s->plan.lr);
@@ -1071,7 +866,7 @@ int cgamd_solver_destroy(cgamd_solver *s) {
         if (s->cols) (void)hipFree(s->cols);
     }
     void *bufs[] = {s->slab, s->part_dq, s->part_rr, s->sc.alpha, s->sc.beta, s->sc.delta,
-                    s->sc.history, s->sc.iter, s->mdiag, s->part_rz, s->rho2, s->tri_coef, s->tri_part, s->tri_cstart, s->tri.maps, s->sc.stage, s->sc.ticket, s->res_sync, s->resw_sync, s->dlag, s->codes, s->dict, s->rm_pace, s->vcodes, s->vdict, s->jcodes, s->jdict_off, s->jdict_val, s->rcodes, s->rdict, s->pcodes, s->pdict, s->sched};
+                    s->sc.history, s->sc.iter, s->part_rz, s->pre.rho2, s->sc.stage, s->sc.ticket, s->res_sync, s->resw_sync, s->dlag, s->codes, s->dict, s->rm_pace, s->vcodes, s->vdict, s->jcodes, s->jdict_off, s->jdict_val, s->rcodes, s->rdict, s->pcodes, s->pdict, s->sched};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     stop_run_free(s->stop);
@@ -1134,21 +929,21 @@ static int set_rhs_impl(cgamd_solver *s, const void *b, const void *x0, int on_d
     if ((rc = handle_spmv(s, s->n, s->x, s->n, s->q, s->n, nullptr, nullptr, st))) return rc;
     if ((rc = launch_sub(s->dtype, s->n, s->b, s->q, s->r, s->n, s->nrhs, st))) return rc;
     if (s->herm) {    // d0 = r0 (d0 = m .* r0), dc = conj(d0), delta0 = r0^H r0, rho0 (hermitian.hip)
-        if ((rc = launch_herm_init(s->dtype, s->n, s->r, s->d, s->d2, s->mdiag, m_pitch(s), s->n, s->nrhs, s->part_rz, s->part_rr, s->vgrid, st))) return rc;
-        if ((rc = launch_herm_delta0(s->dtype, s->mdiag != nullptr, s->part_rz, s->part_rr, s->vgrid, s->nrhs, s->sc, s->rho2, st))) return rc;
-    } else if (s->mg) {      // z0 = V-cycle(r0), p0 = z0, rho0 = r0.z0; the partials by the launches of an iteration
-        if ((rc = mg_vcycle(s->mg, s->r, s->d, st))) return rc;
+        if ((rc = launch_herm_init(s->dtype, s->n, s->r, s->d, s->d2, s->pre.mdiag, m_pitch(s), s->n, s->nrhs, s->part_rz, s->part_rr, s->vgrid, st))) return rc;
+        if ((rc = launch_herm_delta0(s->dtype, s->pre.mdiag != nullptr, s->part_rz, s->part_rr, s->vgrid, s->nrhs, s->sc, s->pre.rho2, st))) return rc;
+    } else if (s->pre.mg) {      // z0 = V-cycle(r0), p0 = z0, rho0 = r0.z0; the partials by the launches of an iteration
+        if ((rc = mg_vcycle(s->pre.mg, s->r, s->d, st))) return rc;
         if ((rc = launch_dot_partials(s->dtype, s->n, s->r, s->r, s->n, s->nrhs, s->part_rr, s->vgrid, st))) return rc;
         if ((rc = launch_dot_partials(s->dtype, s->n, s->r, s->d, s->n, s->nrhs, s->part_rz, s->vgrid, st))) return rc;
-        if ((rc = launch_pcg_delta0(s->dtype, s->part_rz, s->part_rr, s->vgrid, s->nrhs, s->sc, s->rho2, st))) return rc;
-    } else if (s->tri_on) {  // z0 = M^-1 r0 (the line sweeps), p0 = z0, rho0 = r0.z0
+        if ((rc = launch_pcg_delta0(s->dtype, s->part_rz, s->part_rr, s->vgrid, s->nrhs, s->sc, s->pre.rho2, st))) return rc;
+    } else if (tri_on(s)) {  // z0 = M^-1 r0 (the line sweeps), p0 = z0, rho0 = r0.z0
         if ((rc = enqueue_tri_sweep(s, false, nullptr, s->d, st))) return rc;
-        const TriPartials p = tri_partials(s);
-        if ((rc = launch_pcg_delta0(s->dtype, p.rz, p.rr, s->tri.grid, s->nrhs, s->sc, s->rho2, st))) return rc;
-    } else if (s->mdiag) {   // z0 = M r0, p0 = z0, rho0 = r0.z0 (helmFE_var.py:562-573)
-        if ((rc = launch_pcg_axpy2_dot2(s->dtype, true, s->n, s->d, s->x, s->q, s->r, s->mdiag, s->n, nullptr, s->nrhs, s->part_rz,
+        const PcgPartials p = tri_partials(s);
+        if ((rc = launch_pcg_delta0(s->dtype, p.rz, p.rr, s->pre.tri.grid, s->nrhs, s->sc, s->pre.rho2, st))) return rc;
+    } else if (s->pre.mdiag) {   // z0 = M r0, p0 = z0, rho0 = r0.z0 (helmFE_var.py:562-573)
+        if ((rc = launch_pcg_axpy2_dot2(s->dtype, true, s->n, s->d, s->x, s->q, s->r, s->pre.mdiag, s->n, nullptr, s->nrhs, s->part_rz,
                                         s->part_rr, s->vgrid, st, m_pitch(s)))) return rc;
-        if ((rc = launch_pcg_delta0(s->dtype, s->part_rz, s->part_rr, s->vgrid, s->nrhs, s->sc, s->rho2, st))) return rc;
+        if ((rc = launch_pcg_delta0(s->dtype, s->part_rz, s->part_rr, s->vgrid, s->nrhs, s->sc, s->pre.rho2, st))) return rc;
     } else {
         CG_HIP(hipMemcpyAsync(s->d, s->r, vbytes, hipMemcpyDeviceToDevice, st));
         if ((rc = launch_dot_partials(s->dtype, s->n, s->r, s->r, s->n, s->nrhs, s->part_rr, s->vgrid, st))) return rc;
@@ -1172,398 +967,6 @@ int cgamd_solver_set_rhs(cgamd_solver *s, const void *b, const void *x0, int on_
     return set_rhs_impl(s, b, x0, on_device, s->n_user);
 }
 
-static void drop_tridiag(cgamd_solver *s) {
-    for (void *p : {s->tri_coef, s->tri_part, (void *)s->tri_cstart, s->tri.maps})
-        if (p) (void)hipFree(p);
-    s->tri_coef = s->tri_part = nullptr;
-    s->tri_cstart = nullptr;
-    s->tri = TriLaunch();
-    s->tri_on = false;
-}
-
-// z = m .* r between residual and search direction: the reference's PCG with a diagonal CSR M (helmFE_var.py:546-586;
-// pass 1/diag(A) for Jacobi).  m: `size` values of the solver's type, shared by all right-hand sides; NULL removes the
-// preconditioner.  The next cgamd_solver_set_rhs starts the preconditioned recurrence; history then holds r.r as before.
-int cgamd_solver_set_preconditioner(cgamd_solver *s, const void *m, int on_device) {
-    if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner: solver is NULL");
-    if (s->nsys && m) return batched_refuses("set_preconditioner");
-    if (m)      // (removal stays served)
-        if (int rc = shifts_refuse(s, "set_preconditioner")) return rc;
-    if (s->nsys && !precond_set(s)) return CGAMD_OK;      // there is none to remove
-    TuneScope ts(&s->tune);       // (m == NULL also removes the per-system preconditioner of a batched handle)
-    return diag_impl(s, m, on_device);
-}
-static int diag_impl(cgamd_solver *s, const void *m, int on_device) {
-    CG_HIP(hipSetDevice(s->ctx->device));
-    CG_HIP(hipStreamSynchronize(s->ctx->stream));
-    destroy_graphs(s);
-    s->rhs_set = false;
-    drop_tridiag(s);
-    drop_multigrid(s);
-    s->pre_source = s->pre_kind = s->pre_stride = 0;
-    if (!m) {
-        if (s->mdiag) { (void)hipFree(s->mdiag); s->mdiag = nullptr; }
-        apply_wide_order(s);
-        return CGAMD_OK;
-    }
-    const size_t vs = dtype_size(s->dtype);
-    const size_t nm = s->nsys ? (size_t)s->nsys : 1;      // diagonals behind m: one per system of a batched handle, at the caller's stride
-    int rc = CGAMD_OK;
-    if (!s->mdiag) rc = dmalloc(&s->mdiag, (size_t)s->n * nm * vs, "preconditioner");
-    if (!rc && !s->part_rz) rc = dmalloc(&s->part_rz, acc_size(s->dtype) * s->part_rr_cap * s->nrhs, "partials_rz");
-    if (!rc && !s->rho2) rc = dmalloc(&s->rho2, 2 * vs * (size_t)s->nrhs, "rho");
-    if (rc) return rc;
-    if (s->n != s->n_user) CG_HIP(hipMemsetAsync(s->mdiag, 0, (size_t)s->n * nm * vs, s->ctx->stream));
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (nm == 1 || s->n == s->n_user) CG_HIP(hipMemcpyAsync(s->mdiag, m, (size_t)s->n_user * nm * vs, kind, s->ctx->stream));
-    else CG_HIP(hipMemcpy2DAsync(s->mdiag, (size_t)s->n * vs, m, (size_t)s->n_user * vs, (size_t)s->n_user * vs, nm, kind, s->ctx->stream));
-    CG_HIP(hipStreamSynchronize(s->ctx->stream));
-    s->pre_source = 1;
-    if (!s->resw.ok && !s->nsys && !s->herm)
-        if (int rc2 = setup_resident_wide_plan(s)) return rc2;      // (skipped at creation where the one-XCD loop runs the plain recurrence)
-    apply_wide_order(s);
-    return CGAMD_OK;
-}
-
-// The handle takes a factored tridiagonal M over.  coef (3 x pitch values: -l, -w c, w) and plan (stride 1: count + 1 chunk
-// boundaries; stride > 1: count (first row, length) pairs) are device allocations, filled, that belong to the handle from here on
-// -- also when this fails.  Everything that can be wrong with M was checked before.
-static int tri_install(cgamd_solver *s, void *coef, size_t pitch, int *plan, int stride, int count, bool longform, int nsys = 0) {
-    const int dt = s->dtype;
-    const size_t vs = dtype_size(dt);
-    const int grid = stride == 1 ? std::min(count, 1024) : tri_strided_grid(count);
-    destroy_graphs(s);
-    s->rhs_set = false;
-    drop_tridiag(s);
-    drop_multigrid(s);
-    s->pre_source = s->pre_kind = s->pre_stride = 0;
-    if (s->mdiag) { (void)hipFree(s->mdiag); s->mdiag = nullptr; }
-    s->tri_coef = coef;
-    s->tri_cstart = plan;
-    int rc = dmalloc(&s->tri_part, 2 * acc_size(dt) * (size_t)grid * s->nrhs, "partials_rz/rr (tridiagonal)");
-    if (!rc && longform) rc = dmalloc(&s->tri.maps, (size_t)tri_maps_values(count, s->nrhs) * vs, "tridiagonal chunk maps");
-    if (!rc && !s->rho2) rc = dmalloc(&s->rho2, 2 * vs * (size_t)s->nrhs, "rho");
-    if (rc) {
-        drop_tridiag(s);
-        apply_wide_order(s);
-        return rc;
-    }
-    char *cb = static_cast<char *>(s->tri_coef);
-    const size_t arr = pitch * vs * (nsys ? (size_t)nsys : 1);      // nsys > 0: every array holds the factors of all systems, `pitch` apart
-    s->tri.nl = cb; s->tri.ne = cb + arr; s->tri.w = cb + 2 * arr;
-    s->tri.fpitch = nsys ? (long long)pitch : 0;
-    if (stride == 1) {
-        s->tri.cstart = s->tri_cstart;
-        s->tri.nchunks = count; s->tri.longform = longform;
-    } else {
-        s->tri.stride = stride;
-        s->tri.segs = s->tri_cstart;
-        s->tri.nsegs = count;
-    }
-    s->tri.grid = grid;
-    s->tri_on = true;
-    s->pre_source = 1;
-    apply_wide_order(s);
-    return CGAMD_OK;
-}
-
-// Tridiagonal M from its three arrays (precond_setup.cpp: factored on the host, planned, uploaded), at stride 1 or at a distance:
-// lower[i] = M[i][i-stride], upper[i] = M[i][i+stride].  Everything is checked before the handle changes.
-static int tridiag_strided_impl(cgamd_solver *s, const std::string &who, int stride, const void *lower, const void *diag,
-                                const void *upper, int on_device) {
-    CG_HIP(hipSetDevice(s->ctx->device));
-    CG_HIP(hipStreamSynchronize(s->ctx->stream));
-    TriBuilt b;
-    if (int rc = tri_build_host(s->ctx->stream, s->dtype, s->n_user, s->n, who, stride, lower, diag, upper, on_device, &b)) return rc;
-    return tri_install(s, b.coef, b.pitch, b.plan, b.stride, b.count, b.longform);
-}
-int cgamd_solver_set_preconditioner_tridiag(cgamd_solver *s, const void *lower, const void *diag, const void *upper, int on_device) {
-    if (!s || !lower || !diag || !upper) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag: null argument");
-    if (s->nsys) return batched_refuses("set_preconditioner_tridiag");
-    if (s->herm) return herm_refuses("set_preconditioner_tridiag", kHermNoLines);
-    if (int rc = shifts_refuse(s, "set_preconditioner_tridiag")) return rc;
-    TuneScope ts(&s->tune);
-    return tridiag_strided_impl(s, "set_preconditioner_tridiag", 1, lower, diag, upper, on_device);
-}
-
-int cgamd_solver_set_preconditioner_tridiag_strided(cgamd_solver *s, int stride, const void *lower, const void *diag, const void *upper,
-                                                    int on_device) {
-    if (!s || !lower || !diag || !upper) return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag_strided: null argument");
-    if (s->nsys) return batched_refuses("set_preconditioner_tridiag_strided");
-    if (s->herm) return herm_refuses("set_preconditioner_tridiag_strided", kHermNoLines);
-    if (int rc = shifts_refuse(s, "set_preconditioner_tridiag_strided")) return rc;
-    if (stride < 1 || stride >= s->n_user)
-        return fail(CGAMD_ERR_INVALID, "set_preconditioner_tridiag_strided: stride must be in [1, size - 1]");
-    TuneScope ts(&s->tune);
-    return tridiag_strided_impl(s, stride == 1 ? "set_preconditioner_tridiag" : "set_preconditioner_tridiag_strided", stride, lower,
-                                diag, upper, on_device);
-}
-
-// ---- preconditioners built from the handle's own matrix, on the device (precond_setup.cpp, precond_build.hip) ---------------------
-// M = the matrix entries at column - row in {-stride, 0, +stride}: extracted, factored and planned on the device.  Nothing on the
-// handle changes before tri_install.
-static int line_from_matrix(cgamd_solver *s, const std::string &who, int stride) {
-    CG_HIP(hipSetDevice(s->ctx->device));
-    hipStream_t st = s->ctx->stream;
-    CG_HIP(hipStreamSynchronize(st));
-    TriBuilt b;
-    int rc = tri_build_from_matrix(st, s->dtype, s->n_user, s->n, s->tune.dev_line_host_route, who, stride, s->vals, s->ptr, s->cols,
-                                   s->n_user, &b);
-    if (rc) return rc;
-    rc = tri_install(s, b.coef, b.pitch, b.plan, b.stride, b.count, b.longform);
-    if (!rc) { s->pre_source = b.source; s->pre_kind = 2; s->pre_stride = stride; }
-    return rc;
-}
-int cgamd_solver_set_preconditioner_line(cgamd_solver *s, int stride) {
-    if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner_line: solver is NULL");
-    if (s->nsys) return batched_refuses("set_preconditioner_line");
-    if (s->herm) return herm_refuses("set_preconditioner_line", kHermNoLines);
-    if (int rc = shifts_refuse(s, "set_preconditioner_line")) return rc;
-    if (stride < 1 || stride >= s->n_user) return fail(CGAMD_ERR_INVALID, "set_preconditioner_line: stride must be in [1, size - 1]");
-    TuneScope ts(&s->tune);
-    return line_from_matrix(s, "set_preconditioner_line", stride);
-}
-
-// m = 1 / diag(A) on the device, then the diagonal form itself
-static int jacobi_from_matrix(cgamd_solver *s, const std::string &who) {
-    CG_HIP(hipSetDevice(s->ctx->device));
-    hipStream_t st = s->ctx->stream;
-    CG_HIP(hipStreamSynchronize(st));
-    void *m = nullptr;
-    int rc = dmalloc(&m, (size_t)s->n_user * dtype_size(s->dtype), "Jacobi preconditioner");
-    if (rc) return rc;
-    rc = jacobi_build_from_matrix(st, s->dtype, s->n_user, who, s->vals, s->ptr, s->cols, m);
-    if (!rc) rc = diag_impl(s, m, 1);
-    (void)hipFree(m);
-    if (!rc) { s->pre_source = 2; s->pre_kind = 1; }
-    return rc;
-}
-int cgamd_solver_set_preconditioner_jacobi(cgamd_solver *s) {
-    if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner_jacobi: solver is NULL");
-    if (s->nsys) return batched_refuses("set_preconditioner_jacobi");
-    if (int rc = shifts_refuse(s, "set_preconditioner_jacobi")) return rc;
-    TuneScope ts(&s->tune);
-    return jacobi_from_matrix(s, "set_preconditioner_jacobi");
-}
-
-// ---- aggregation multigrid on a grid system (multigrid_setup.cpp): the hierarchy is built from the matrix as it is now, on the
-// device; nothing on the handle changes before it stands
-static int multigrid_from_matrix(cgamd_solver *s, const std::string &who, const MgParams &p) {
-    CG_HIP(hipSetDevice(s->ctx->device));
-    hipStream_t st = s->ctx->stream;
-    CG_HIP(hipStreamSynchronize(st));
-    MgHierarchy *h = nullptr;
-    int rc = mg_build(st, s->dtype, s->n_user, s->n, s->nrhs, s->nsys, s->plan, s->nnz, s->vals, s->ptr, s->cols, p, who, &h);
-    if (rc) return rc;
-    const size_t vs = dtype_size(s->dtype);
-    if (!s->part_rz) rc = dmalloc(&s->part_rz, acc_size(s->dtype) * s->part_rr_cap * s->nrhs, "partials_rz");
-    if (!rc && !s->rho2) rc = dmalloc(&s->rho2, 2 * vs * (size_t)s->nrhs, "rho");
-    if (rc) { mg_free(h); return rc; }
-    destroy_graphs(s);
-    s->rhs_set = false;
-    drop_tridiag(s);
-    drop_multigrid(s);
-    if (s->mdiag) { (void)hipFree(s->mdiag); s->mdiag = nullptr; }
-    s->mg = h;
-    s->mg_params = p;
-    s->pre_source = 2; s->pre_kind = 3; s->pre_stride = 0;
-    apply_wide_order(s);
-    return CGAMD_OK;
-}
-int cgamd_solver_set_preconditioner_multigrid(cgamd_solver *s, int nx, int ny, int nz, int smooth_steps, double over_correction, int min_rows) {
-    const std::string who = "set_preconditioner_multigrid";
-    if (!s) return fail(CGAMD_ERR_INVALID, who + ": solver is NULL");
-    if (s->nsys) return batched_refuses("set_preconditioner_multigrid");
-    if (s->herm) return herm_refuses("set_preconditioner_multigrid", "which the V-cycle does not serve");
-    if (int rc = shifts_refuse(s, "set_preconditioner_multigrid")) return rc;
-    if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, who + ": CGAMD_UNFUSED replays the reference's kernel sequence");
-    if (s->rm_ok) return fail(CGAMD_ERR_STATE, who + ": the handle keeps its right-hand sides interleaved (row-major layout)");
-    if (nx < 1 || ny < 1 || nz < 1) return fail(CGAMD_ERR_INVALID, who + ": every grid dimension must be at least 1");
-    const long long plane = (long long)nx * ny;
-    if (plane > 2147483647LL || plane * nz != (long long)s->n_user)
-        return fail(CGAMD_ERR_INVALID, who + ": nx * ny * nz must equal the size of the system");
-    if (smooth_steps < 0 || smooth_steps > 4) return fail(CGAMD_ERR_INVALID, who + ": smooth_steps must be in 0 ... 4 (0 = the default, 1)");
-    if (!std::isfinite(over_correction) || over_correction < 0.) return fail(CGAMD_ERR_INVALID, who + ": over_correction must be finite and not negative (0 = the default, 1.6)");
-    if (min_rows < 0) return fail(CGAMD_ERR_INVALID, who + ": min_rows must not be negative (0 = the default, 512)");
-    MgParams p;
-    p.nx = nx; p.ny = ny; p.nz = nz;
-    if (smooth_steps) p.smooth_steps = smooth_steps;
-    if (over_correction != 0.) p.omega = over_correction;
-    if (min_rows) p.min_rows = min_rows;
-    TuneScope ts(&s->tune);
-    return multigrid_from_matrix(s, who, p);
-}
-// the same hierarchy with aggregates matched from the matrix (amg.hip): everything downstream of mg_build is the grid entry's
-int cgamd_solver_set_preconditioner_amg(cgamd_solver *s, int passes, double strength, int smooth_steps, double over_correction, int min_rows) {
-    const std::string who = "set_preconditioner_amg";
-    if (!s) return fail(CGAMD_ERR_INVALID, who + ": solver is NULL");
-    if (s->nsys) return batched_refuses("set_preconditioner_amg");
-    if (s->herm) return herm_refuses("set_preconditioner_amg", "which the V-cycle does not serve");
-    if (int rc = shifts_refuse(s, "set_preconditioner_amg")) return rc;
-    if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, who + ": CGAMD_UNFUSED replays the reference's kernel sequence");
-    if (s->rm_ok) return fail(CGAMD_ERR_STATE, who + ": the handle keeps its right-hand sides interleaved (row-major layout)");
-    if (passes < 0 || passes > 3) return fail(CGAMD_ERR_INVALID, who + ": passes must be in 0 ... 3 (0 = the default, 3)");
-    if (!std::isfinite(strength) || strength < 0. || strength > 1.) return fail(CGAMD_ERR_INVALID, who + ": strength must be in (0, 1] (0 = the default, 0.25)");
-    if (smooth_steps < 0 || smooth_steps > 4) return fail(CGAMD_ERR_INVALID, who + ": smooth_steps must be in 0 ... 4 (0 = the default, 1)");
-    if (!std::isfinite(over_correction) || over_correction < 0.) return fail(CGAMD_ERR_INVALID, who + ": over_correction must be finite and not negative (0 = the default, 1.6)");
-    if (min_rows < 0) return fail(CGAMD_ERR_INVALID, who + ": min_rows must not be negative (0 = the default, 512)");
-    MgParams p;
-    p.algebraic = true;
-    if (passes) p.passes = passes;
-    if (strength != 0.) p.theta = strength;
-    if (smooth_steps) p.smooth_steps = smooth_steps;
-    if (over_correction != 0.) p.omega = over_correction;
-    if (min_rows) p.min_rows = min_rows;
-    TuneScope ts(&s->tune);
-    return multigrid_from_matrix(s, who, p);
-}
-int cgamd_solver_mg_levels(cgamd_solver *s) {
-    if (!s) return -CGAMD_ERR_INVALID;
-    return s->mg ? mg_levels(s->mg) : 0;
-}
-static int mg_wanted(cgamd_solver *s, const char *who) {
-    if (!s) return fail(CGAMD_ERR_INVALID, std::string(who) + ": solver is NULL");
-    if (!s->mg) return fail(CGAMD_ERR_STATE, std::string(who) + ": no multigrid preconditioner is set");
-    return CGAMD_OK;
-}
-int cgamd_solver_mg_level(cgamd_solver *s, int level, long long info[6]) {
-    if (int rc = mg_wanted(s, "mg_level")) return rc;
-    if (!info) return fail(CGAMD_ERR_INVALID, "mg_level: info is NULL");
-    return mg_level_info(s->mg, level, info);
-}
-int cgamd_solver_mg_level_bounds(cgamd_solver *s, int level, double *lmax, int count) {
-    if (int rc = mg_wanted(s, "mg_level_bounds")) return rc;
-    return mg_level_bounds(s->mg, level, lmax, count);
-}
-int cgamd_solver_mg_level_matrix(cgamd_solver *s, int level, int *ptr, int *cols, void *vals) {
-    if (int rc = mg_wanted(s, "mg_level_matrix")) return rc;
-    CG_HIP(hipSetDevice(s->ctx->device));
-    return mg_level_matrix(s->mg, level, ptr, cols, vals, s->ctx->stream);
-}
-int cgamd_solver_mg_aggregates(cgamd_solver *s, int level, int *agg_host, int *n_coarse) {
-    if (int rc = mg_wanted(s, "mg_aggregates")) return rc;
-    CG_HIP(hipSetDevice(s->ctx->device));
-    return mg_aggregates(s->mg, level, agg_host, n_coarse, s->ctx->stream);
-}
-// one V-cycle on caller vectors (nRHS * size values each, device memory, stride `size`), through buffers with the handle's padding
-int cgamd_solver_mg_apply(cgamd_solver *s, const void *r_dev, void *z_dev) {
-    if (int rc = mg_wanted(s, "mg_apply")) return rc;
-    if (!r_dev || !z_dev) return fail(CGAMD_ERR_INVALID, "mg_apply: null argument");
-    TuneScope ts(&s->tune);
-    CG_HIP(hipSetDevice(s->ctx->device));
-    if (int rc = step_not_capturing(s, "mg_apply")) return rc;
-    hipStream_t st = s->ctx->stream;
-    const size_t vs = dtype_size(s->dtype), row = (size_t)s->n * vs, bytes = row * (size_t)s->nrhs;
-    void *buf = nullptr;
-    if (int rc = dmalloc(&buf, 2 * bytes, "mg_apply vectors")) return rc;
-    void *r = buf, *z = static_cast<char *>(buf) + bytes;
-    int rc = CGAMD_OK;
-    hipError_t e = hipMemsetAsync(buf, 0, 2 * bytes, st);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(r, row, r_dev, (size_t)s->n_user * vs, (size_t)s->n_user * vs, (size_t)s->nrhs, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) rc = mg_vcycle(s->mg, r, z, st);
-    if (e == hipSuccess && !rc) e = hipMemcpy2DAsync(z_dev, (size_t)s->n_user * vs, z, row, (size_t)s->n_user * vs, (size_t)s->nrhs, hipMemcpyDeviceToDevice, st);
-    const hipError_t e2 = hipStreamSynchronize(st);
-    (void)hipFree(buf);
-    if (rc) return rc;
-    if (e != hipSuccess || e2 != hipSuccess) return fail(CGAMD_ERR_HIP, std::string("mg_apply: ") + hipGetErrorString(e != hipSuccess ? e : e2));
-    return CGAMD_OK;
-}
-int cgamd_solver_mg_level_state(cgamd_solver *s, int level, int which, void *out_host, long long cap_values, long long *count) {
-    if (!s || !out_host || !count) return fail(CGAMD_ERR_INVALID, "mg_level_state: null argument");
-    if (int rc = mg_wanted(s, "mg_level_state")) return rc;
-    CG_HIP(hipSetDevice(s->ctx->device));
-    if (int rc = step_not_capturing(s, "mg_level_state")) return rc;
-    return mg_level_state(s->mg, level, which, out_host, cap_values, count, s->ctx->stream);
-}
-int cgamd_solver_mg_level_spmv(cgamd_solver *s, int level, const void *x_dev, void *w_dev) {
-    if (!s || !x_dev || !w_dev) return fail(CGAMD_ERR_INVALID, "mg_level_spmv: null argument");
-    if (int rc = mg_wanted(s, "mg_level_spmv")) return rc;
-    TuneScope ts(&s->tune);
-    CG_HIP(hipSetDevice(s->ctx->device));
-    if (int rc = step_not_capturing(s, "mg_level_spmv")) return rc;
-    return mg_level_spmv(s->mg, level, x_dev, w_dev, s->ctx->stream);
-}
-
-// ---- a batched handle: one M per system (M_r for right-hand side r), never one shared by all ------------------------------------------
-static int not_batched(const char *who, const char *shared) {
-    return fail(CGAMD_ERR_STATE, std::string(who) + ": the handle is not batched (one matrix for all right-hand sides); use " + shared);
-}
-// m: nSystems * size values, the diagonal of system r at m + r * size; NULL removes any preconditioner
-int cgamd_solver_set_preconditioner_batched(cgamd_solver *s, const void *m, int on_device) {
-    if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner_batched: solver is NULL");
-    if (!s->nsys) return not_batched("set_preconditioner_batched", "cgamd_solver_set_preconditioner");
-    if (!m && !precond_set(s)) return CGAMD_OK;
-    TuneScope ts(&s->tune);
-    return diag_impl(s, m, on_device);
-}
-// m_r = 1 / diag(A_r) of every system on the device, then the diagonal form itself
-static int batched_jacobi_from_matrix(cgamd_solver *s, const std::string &who) {
-    CG_HIP(hipSetDevice(s->ctx->device));
-    hipStream_t st = s->ctx->stream;
-    CG_HIP(hipStreamSynchronize(st));
-    void *m = nullptr;
-    int rc = dmalloc(&m, (size_t)s->n_user * s->nsys * dtype_size(s->dtype), "Jacobi preconditioner");
-    if (rc) return rc;
-    rc = jacobi_build_from_matrix_batched(st, s->dtype, s->n_user, s->nsys, s->nnz, who, s->vals, s->ptr, s->cols, m, s->n_user);
-    if (!rc) rc = diag_impl(s, m, 1);
-    (void)hipFree(m);
-    if (!rc) { s->pre_source = 2; s->pre_kind = 1; }
-    return rc;
-}
-int cgamd_solver_set_preconditioner_batched_jacobi(cgamd_solver *s) {
-    if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner_batched_jacobi: solver is NULL");
-    if (!s->nsys) return not_batched("set_preconditioner_batched_jacobi", "cgamd_solver_set_preconditioner_jacobi");
-    TuneScope ts(&s->tune);
-    return batched_jacobi_from_matrix(s, "set_preconditioner_batched_jacobi");
-}
-// M_r = the lines of A_r at `stride`: every system extracted and factored on the device, one segment plan for all of them.  Nothing on
-// the handle changes before tri_install.
-static int batched_line_from_matrix(cgamd_solver *s, const std::string &who, int stride) {
-    CG_HIP(hipSetDevice(s->ctx->device));
-    hipStream_t st = s->ctx->stream;
-    CG_HIP(hipStreamSynchronize(st));
-    TriBuilt b;
-    int rc = tri_build_from_matrix_batched(st, s->dtype, s->n_user, s->n, s->nsys, s->nnz, who, stride, s->vals, s->ptr, s->cols, &b);
-    if (rc) return rc;
-    rc = tri_install(s, b.coef, b.pitch, b.plan, b.stride, b.count, b.longform, b.nsys);
-    if (!rc) { s->pre_source = 2; s->pre_kind = 2; s->pre_stride = stride; }
-    return rc;
-}
-int cgamd_solver_set_preconditioner_batched_line(cgamd_solver *s, int stride) {
-    if (!s) return fail(CGAMD_ERR_INVALID, "set_preconditioner_batched_line: solver is NULL");
-    if (!s->nsys) return not_batched("set_preconditioner_batched_line", "cgamd_solver_set_preconditioner_line");
-    if (s->herm) return herm_refuses("set_preconditioner_batched_line", kHermNoLines);
-    if (stride < 1 || stride >= s->n_user) return fail(CGAMD_ERR_INVALID, "set_preconditioner_batched_line: stride must be in [1, size - 1]");
-    TuneScope ts(&s->tune);
-    return batched_line_from_matrix(s, "set_preconditioner_batched_line", stride);
-}
-
-// one hierarchy per system on shared box aggregates and patterns (multigrid_setup.cpp, multigrid_batched.hip); everything downstream
-// of mg_build is the single-system entry's: s->mg serves the loops, the accessors and the byte models of both
-int cgamd_solver_set_preconditioner_batched_multigrid(cgamd_solver *s, int nx, int ny, int nz, int smooth_steps, double over_correction,
-                                                      int min_rows) {
-    const std::string who = "set_preconditioner_batched_multigrid";
-    if (!s) return fail(CGAMD_ERR_INVALID, who + ": solver is NULL");
-    if (!s->nsys) return not_batched(who.c_str(), "cgamd_solver_set_preconditioner_multigrid");
-    if (s->herm) return herm_refuses(who.c_str(), "which the V-cycle does not serve");
-    if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, who + ": CGAMD_UNFUSED replays the reference's kernel sequence");
-    if (nx < 1 || ny < 1 || nz < 1) return fail(CGAMD_ERR_INVALID, who + ": every grid dimension must be at least 1");
-    const long long plane = (long long)nx * ny;
-    if (plane > 2147483647LL || plane * nz != (long long)s->n_user)
-        return fail(CGAMD_ERR_INVALID, who + ": nx * ny * nz must equal the size of the system");
-    if (smooth_steps < 0 || smooth_steps > 4) return fail(CGAMD_ERR_INVALID, who + ": smooth_steps must be in 0 ... 4 (0 = the default, 1)");
-    if (!std::isfinite(over_correction) || over_correction < 0.) return fail(CGAMD_ERR_INVALID, who + ": over_correction must be finite and not negative (0 = the default, 1.6)");
-    if (min_rows < 0) return fail(CGAMD_ERR_INVALID, who + ": min_rows must not be negative (0 = the default, 512)");
-    MgParams p;
-    p.nx = nx; p.ny = ny; p.nz = nz;
-    if (smooth_steps) p.smooth_steps = smooth_steps;
-    if (over_correction != 0.) p.omega = over_correction;
-    if (min_rows) p.min_rows = min_rows;
-    TuneScope ts(&s->tune);
-    return multigrid_from_matrix(s, who, p);
-}
-
-int cgamd_solver_preconditioner_source(cgamd_solver *s) { return s ? s->pre_source : 0; }
 
 int cgamd_solver_iterate(cgamd_solver *s, int nIterations) {
     if (!s) return fail(CGAMD_ERR_INVALID, "iterate: solver is NULL");
@@ -1578,7 +981,7 @@ int cgamd_solver_iterate(cgamd_solver *s, int nIterations) {
     int left = nIterations, k = s->iters;
     const bool use_graph = !(s->flags & CGAMD_NO_GRAPH) && !s->graph_failed;
     const bool two = fused2_now(s);
-    if (s->resw.ok && !s->until_mode && !s->tri_on && !s->mg && !(two && s->res_ok) && !s->rm && !(s->flags & (CGAMD_NO_GRAPH | CGAMD_UNFUSED)) &&
+    if (s->resw.ok && !s->until_mode && !tri_on(s) && !s->pre.mg && !(two && s->res_ok) && !s->rm && !(s->flags & (CGAMD_NO_GRAPH | CGAMD_UNFUSED)) &&
         (nIterations >= std::max(1, tune().resident_wide_min) || s->tol_req > 0.)) {
         // one chip-wide resident group (single right-hand side, matrix rows in registers).  d ping-pongs inside the launch; handles
         // of the launched loops that keep d in one buffer get it back there, and the launched loops' r.r partials are rebuilt.
@@ -1593,7 +996,7 @@ int cgamd_solver_iterate(cgamd_solver *s, int nIterations) {
             int stop = -1;
             s->tol_served = s->tol_req > 0.;
             CgScalars scw = s->sc;           // the Jacobi-preconditioned recurrence runs in the same loop (rho for delta, z = m r)
-            if (s->mdiag) { scw.pcg_m = s->mdiag; scw.pcg_rho2 = s->rho2; }
+            if (s->pre.mdiag) { scw.pcg_m = s->pre.mdiag; scw.pcg_rho2 = s->pre.rho2; }
             if (int rc = run_cg_resident_wide(s->dtype, s->resw, s->n, s->nrhs, s->vals, s->ptr, s->cols, s->x, s->r, d0, d1,
                                               keeps_new_d && s->iters > 0, scw, s->iters, K, s->resw_sync, s->n_cus, st, &untouched, s->tol_req,
                                               &stop)) {
@@ -1615,8 +1018,8 @@ int cgamd_solver_iterate(cgamd_solver *s, int nIterations) {
             if (done > 0) {                  // (a stop before the first iteration leaves d as the caller had it)
                 if (fin != dbuf(s, s->iters))
                     CG_HIP(hipMemcpyAsync(dbuf(s, s->iters), fin, (size_t)s->n * s->nrhs * dtype_size(s->dtype), hipMemcpyDeviceToDevice, st));
-                if (s->mdiag) {              // p = beta p + m r (helmFE_var.py:583-585)
-                    if (int rc = launch_pcg_p_update(s->dtype, s->n, s->r, dbuf(s, s->iters), s->mdiag, s->n, s->sc.beta, s->nrhs, st)) return rc;
+                if (s->pre.mdiag) {              // p = beta p + m r (helmFE_var.py:583-585)
+                    if (int rc = launch_pcg_p_update(s->dtype, s->n, s->r, dbuf(s, s->iters), s->pre.mdiag, s->n, s->sc.beta, s->nrhs, st)) return rc;
                 } else if (keeps_new_d)      // d = beta d + r with the beta the launch recorded last (clcg.c:415)
                     if (int rc = launch_aypx(s->dtype, s->n, s->r, dbuf(s, s->iters), s->n, s->sc.beta, s->nrhs, st)) return rc;
             }
@@ -1695,7 +1098,7 @@ int cgamd_solver_iterate_tol(cgamd_solver *s, int maxIterations, double tol, int
     if (s->proj.spent) return fail(CGAMD_ERR_STATE, std::string("iterate_tol") + kProjSpent);
     {
         TuneScope ts(&s->tune);
-        const bool local = fused2_now(s) && s->res_ok, wide = s->resw.ok && !s->tri_on && !s->mg && !s->rm && !(s->res_ok && !precond_set(s));
+        const bool local = fused2_now(s) && s->res_ok, wide = s->resw.ok && !tri_on(s) && !s->pre.mg && !s->rm && !(s->res_ok && !precond_set(s));
         if ((!local && !wide) || (s->flags & (CGAMD_NO_GRAPH | CGAMD_UNFUSED)))
             return fail(CGAMD_ERR_STATE, "iterate_tol: this handle runs a launched loop (check the history from the host)");
     }
@@ -1731,14 +1134,13 @@ static int enter_until_mode(cgamd_solver *s, hipStream_t st) {
 // Residual replacement (include/cgamd.h; the "reliable updates" of van der Vorst and Ye): the recurrence goes on from (0, r_new, d).
 // What the entry does not serve is refused before anything on the handle changes.  planned: the question is asked BEFORE the set_rhs
 // that will precede the call (the mixed solve, mixed.cpp), so the layout is the one that set_rhs will decide
-static int step_not_capturing(cgamd_solver *s, const char *who);
 static int replace_refuses(const cgamd_solver *s, bool planned) {
     const std::string who = "replace_residual: ";
     if (!planned && !s->rhs_set) return fail(CGAMD_ERR_STATE, who + "call set_rhs first");
     if (planned ? (s->rm_ok && !precond_set(s)) : s->rm)
         return fail(CGAMD_ERR_STATE, who + "the handle keeps its right-hand sides interleaved (row-major layout)");
-    if (s->tri_on) return fail(CGAMD_ERR_STATE, who + "a tridiagonal / line preconditioner is set; the entry serves no preconditioner or a diagonal one");
-    if (s->mg) return fail(CGAMD_ERR_STATE, who + "a multigrid preconditioner is set; the entry serves no preconditioner or a diagonal one");
+    if (tri_on(s)) return fail(CGAMD_ERR_STATE, who + "a tridiagonal / line preconditioner is set; the entry serves no preconditioner or a diagonal one");
+    if (s->pre.mg) return fail(CGAMD_ERR_STATE, who + "a multigrid preconditioner is set; the entry serves no preconditioner or a diagonal one");
     if (s->herm) return herm_refuses("replace_residual", "which the entry does not serve");
     if (s->nsys) return fail(CGAMD_ERR_STATE, who + "the handle is batched");
     if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, who + "CGAMD_UNFUSED replays the reference's kernel sequence");
@@ -1764,10 +1166,10 @@ static int replace_residual_impl(cgamd_solver *s, const void *r_new, long long l
     CG_HIP(hipMemsetAsync(s->x, 0, vbytes, st));
     // delta0 (rho0) by the launches of set_rhs, in their order; d is read and written by none of them
     int rc;
-    if (s->mdiag) {     // z = m .* r lands in q, which is dead between iterations
-        if ((rc = launch_pcg_axpy2_dot2(s->dtype, true, s->n, s->q, s->x, s->q, s->r, s->mdiag, s->n, nullptr, s->nrhs, s->part_rz, s->part_rr,
+    if (s->pre.mdiag) {     // z = m .* r lands in q, which is dead between iterations
+        if ((rc = launch_pcg_axpy2_dot2(s->dtype, true, s->n, s->q, s->x, s->q, s->r, s->pre.mdiag, s->n, nullptr, s->nrhs, s->part_rz, s->part_rr,
                                         s->vgrid, st, m_pitch(s)))) return rc;
-        if ((rc = launch_pcg_delta0(s->dtype, s->part_rz, s->part_rr, s->vgrid, s->nrhs, s->sc, s->rho2, st))) return rc;
+        if ((rc = launch_pcg_delta0(s->dtype, s->part_rz, s->part_rr, s->vgrid, s->nrhs, s->sc, s->pre.rho2, st))) return rc;
     } else {
         if ((rc = launch_dot_partials(s->dtype, s->n, s->r, s->r, s->n, s->nrhs, s->part_rr, s->vgrid, st))) return rc;
         if ((rc = launch_cg_delta0(s->dtype, s->part_rr, s->vgrid, s->nrhs, s->sc, st))) return rc;
@@ -1982,17 +1384,10 @@ int cgamd_solver_dot_partials(cgamd_solver *s, void *out_host, long long cap_val
 // ---- test-facing record of the vector and scalar steps (tests/test_gpu_cg_steps.py) ------------------------------------------------
 // Neither entry launches a kernel or changes the handle.  Both refuse a handle whose stream is being captured: a copy or a
 // synchronisation there would end the capture with an error.
-static int step_not_capturing(cgamd_solver *s, const char *who) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const hipError_t e = hipStreamIsCapturing(s->ctx->stream, &cs);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(CGAMD_ERR_HIP, std::string(who) + ": hipStreamIsCapturing: " + hipGetErrorString(e)); }
-    if (cs != hipStreamCaptureStatusNone) return fail(CGAMD_ERR_INVALID, std::string(who) + ": the handle's stream is being captured");
-    return CGAMD_OK;
-}
 // Row-major and tridiagonal handles launch their vector and scalar steps with grids of their own (rm_nwg / rm_vgrid, tri.grid) and keep
 // their partials elsewhere (tri_part): neither entry describes them, both refuse them
 static int step_launched_rhs_major(cgamd_solver *s, const char *who) {
-    if (s->rm || (s->rm_ok && !precond_set(s)) || s->tri_on || s->mg)
+    if (s->rm || (s->rm_ok && !precond_set(s)) || tri_on(s) || s->pre.mg)
         return fail(CGAMD_ERR_INVALID, std::string(who) + ": not recorded for row-major and tridiagonal handles");
     if (s->herm) return fail(CGAMD_ERR_INVALID, std::string(who) + ": not recorded for CGAMD_HERMITIAN handles (steps of their own, hermitian.hip)");
     return CGAMD_OK;
@@ -2012,11 +1407,11 @@ int cgamd_solver_step_plan(cgamd_solver *s, int *out, int n_out) {
     if (int rc = step_launched_rhs_major(s, "step_plan")) return -rc;
     // the branches of enqueue_iteration that are left: the diagonal preconditioner first, then the UNFUSED flag (eight launches, alpha
     // from the vgrid partials of dot_partials), else the folded or the separate alpha on the SpMV's d.q partials
-    const bool unfused = (s->flags & CGAMD_UNFUSED) && !s->mdiag;
+    const bool unfused = (s->flags & CGAMD_UNFUSED) && !s->pre.mdiag;
     const int alpha_grid = unfused ? s->vgrid : s->plan.n_partials;
-    const bool fold = !unfused && !s->mdiag && fold_alpha_ok(s->plan.n_partials, s->plan.fold_max);
+    const bool fold = !unfused && !s->pre.mdiag && fold_alpha_ok(s->plan.n_partials, s->plan.fold_max);
     bool vec = vec_ok(s->dtype, s->n, s->nrhs, {s->x, s->r, s->d, s->q});
-    if (s->mdiag) vec = vec && aligned16(s->mdiag) && ((m_pitch(s) * (long long)dtype_size(s->dtype)) & 15) == 0;
+    if (s->pre.mdiag) vec = vec && aligned16(s->pre.mdiag) && ((m_pitch(s) * (long long)dtype_size(s->dtype)) & 15) == 0;
     const int f[kStepPlanFields] = {s->n, s->n, s->vgrid, s->plan.n_partials, s->sc.kdq, s->sc.krr, fold ? 1 : 0,
                                     (!fold && s->sc.stage && s->sc.ticket && alpha_grid >= 16384) ? 1 : 0, vec ? 1 : 0,
                                     tune().vec_nt >= 0 ? tune().vec_nt : s->plan.vec_nt, x_lag_now(s)};
@@ -2040,7 +1435,7 @@ int cgamd_solver_step_state(cgamd_solver *s, int which, void *out_host, long lon
     case 2: src = s->sc.alpha; break;
     case 3: src = s->sc.beta; break;
     case 4: src = s->sc.delta; break;
-    case 5: src = s->rho2; values = 2LL * s->nrhs; break;
+    case 5: src = s->pre.rho2; values = 2LL * s->nrhs; break;
     case 6: src = s->sc.iter; each = sizeof(int); values = 1; break;
     default: return fail(CGAMD_ERR_INVALID, "step_state: which is 0 .. 6");
     }
@@ -2079,12 +1474,12 @@ int cgamd_solver_loop_launches(cgamd_solver *s) {
     if (!s) return -CGAMD_ERR_INVALID;
     TuneScope ts(&s->tune);
     if (s->herm) return 4;                               // SpMV, herm_alpha, herm_axpy_dot, herm_aypx_beta_x under every flag
-    if (s->mg) return 5 + mg_cost(s->mg).launches;       // SpMV, cg_alpha, r update, the V-cycle's chain, r.z, update
-    if (s->tri_on) return s->tri.longform ? 6 : 4;      // launched loop only: SpMV, cg_alpha, the sweep (3 launches in the long form), update
-    if (s->nsys && s->mdiag) return 4;                   // a batched handle's PCG loop is the same four launches under every flag
+    if (s->pre.mg) return 5 + mg_cost(s->pre.mg).launches;       // SpMV, cg_alpha, r update, the V-cycle's chain, r.z, update
+    if (tri_on(s)) return s->pre.tri.longform ? 6 : 4;      // launched loop only: SpMV, cg_alpha, the sweep (3 launches in the long form), update
+    if (s->nsys && s->pre.mdiag) return 4;                   // a batched handle's PCG loop is the same four launches under every flag
     if (s->flags & CGAMD_UNFUSED) return 8;
     if (s->rm) return 5;
-    if (s->mdiag) return (s->resw.ok && !s->rm && !(s->flags & (CGAMD_NO_GRAPH | CGAMD_UNFUSED))) ? 1 : 4;
+    if (s->pre.mdiag) return (s->resw.ok && !s->rm && !(s->flags & (CGAMD_NO_GRAPH | CGAMD_UNFUSED))) ? 1 : 4;
     // shifts in force: the three / four-launch loop, then the shift scalar step and ONE vector launch whatever the number of shifts
     if (nshifts(s)) return (fold_alpha_ok(s->plan.n_partials, s->plan.fold_max) ? 3 : 4) + 2;
     if (fused2_now(s) && s->res_ok && !(s->flags & CGAMD_NO_GRAPH)) return 0;
@@ -2116,24 +1511,24 @@ long long cgamd_solver_spmv_bytes(cgamd_solver *s) {
 // the multigrid loop: SpMV (p, q) 2 + r update (q, r in; r out) 3 + r.z (r, z) 2 + update (z, p, x in; x, p out) 5 = 12 passes per RHS,
 // and the V-cycle: its fine-level SpMVs at the price of this handle's SpMV, everything else as multigrid_setup.cpp counts it
 static long long mg_bytes(const cgamd_solver *s, long long spmv_bytes) {
-    const MgCost c = mg_cost(s->mg);
+    const MgCost c = mg_cost(s->pre.mg);
     return 12LL * s->n_user * (long long)dtype_size(s->dtype) * s->nrhs + c.spmv0 * spmv_bytes + c.bytes;
 }
 // the shift vector launch: r read once, x_j and d_j of every shift read and written
 static long long shift_bytes(const cgamd_solver *s) { return nshifts(s) ? (4LL * nshifts(s) + 1) * s->n_user * (long long)dtype_size(s->dtype) * s->nrhs : 0; }
 static long long tri_passes(const cgamd_solver *s) {
     const long long f = value_arrays(s);
-    if (s->tri.stride > 1) return 14LL * s->nrhs + 3 * f;
-    return s->tri.longform ? 13LL * s->nrhs + 6 * f : 11LL * s->nrhs + 3 * f;
+    if (s->pre.tri.stride > 1) return 14LL * s->nrhs + 3 * f;
+    return s->pre.tri.longform ? 13LL * s->nrhs + 6 * f : 11LL * s->nrhs + 3 * f;
 }
 long long cgamd_solver_iter_bytes(cgamd_solver *s, int fused) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
-    if (s->mg) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + mg_bytes(s, cgamd_solver_spmv_bytes(s));
-    if (s->tri_on) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + tri_passes(s) * s->n_user * V;
+    if (s->pre.mg) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + mg_bytes(s, cgamd_solver_spmv_bytes(s));
+    if (tri_on(s)) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + tri_passes(s) * s->n_user * V;
     // the conjugated recurrence: the launched loop's 10 passes (12 with a diagonal M) and conj(d), written by the d step and read by the SpMV's dot
-    if (s->herm) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + (s->mdiag ? 14LL : 12LL) * s->n_user * V * s->nrhs;
-    if (s->nsys && s->mdiag) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + 12LL * s->n_user * V * s->nrhs;
+    if (s->herm) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + (s->pre.mdiag ? 14LL : 12LL) * s->n_user * V * s->nrhs;
+    if (s->nsys && s->pre.mdiag) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + 12LL * s->n_user * V * s->nrhs;
     return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + (fused ? 11LL : 14LL) * s->n_user * V * s->nrhs + shift_bytes(s);
 }
 
@@ -2192,12 +1587,12 @@ int cgamd_solver_row_pipe(cgamd_solver *s) { return s ? (row_form(s) ? row_pipe_
 long long cgamd_solver_iter_moved_bytes(cgamd_solver *s) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
-    const long long passes = s->herm ? (s->mdiag ? 14 : 12) : (s->nsys && s->mdiag) ? 12 : (s->flags & CGAMD_UNFUSED) ? 14 : s->mdiag ? 12 : 10;
+    const long long passes = s->herm ? (s->pre.mdiag ? 14 : 12) : (s->nsys && s->pre.mdiag) ? 12 : (s->flags & CGAMD_UNFUSED) ? 14 : s->pre.mdiag ? 12 : 10;
     const long long lag = x_lag_now(s);
     const long long value_bytes = joint_form(s) ? 0 : s->plan.vcodes ? 1 : V * value_arrays(s);
     const long long matrix = (row_form(s) ? (long long)s->n_user : s->nnz * (value_bytes + index_bytes_per_nnz(s)) + ((long long)s->n_user + 1) * 4) + long_rows_scratch_traffic(s);
-    if (s->mg) return matrix + mg_bytes(s, cgamd_solver_spmv_moved_bytes(s));
-    if (s->tri_on) return matrix + tri_passes(s) * s->n_user * V;
+    if (s->pre.mg) return matrix + mg_bytes(s, cgamd_solver_spmv_moved_bytes(s));
+    if (tri_on(s)) return matrix + tri_passes(s) * s->n_user * V;
     // the deferred x update: the d steps of a group of L iterations move 4 L + 1 vectors instead of 5 L, the steady state of a
     // handle iterated in multiples of U: (9 L + 1) / L passes per iteration
     if (lag >= 2) return matrix + (9 * lag + 1) * s->n_user * V * s->nrhs / lag;
