@@ -122,6 +122,7 @@ def load():
         "cgamd_solver_long_rows": (ci, [vp, ctypes.POINTER(ci), ci]),
         "cgamd_solver_dot_partials": (ci, [vp, vp, ll, ctypes.POINTER(ci)]),
         "cgamd_solver_step_plan": (ci, [vp, ctypes.POINTER(ci), ci]),
+        "cgamd_solver_spmv_form": (ci, [vp, ci, ctypes.POINTER(ci), ci, ctypes.POINTER(ci), ci]),
         "cgamd_solver_step_state": (ci, [vp, ci, vp, ll, ctypes.POINTER(ll)]),
         "cgamd_solver_layout": (ci, [vp]),
         "cgamd_solver_loop_launches": (ci, [vp]),

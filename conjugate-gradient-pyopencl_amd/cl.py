@@ -767,10 +767,26 @@ class Solver:
         got = self._lib.cgamd_last_spmv_form(out, len(out))
         if got < 0:
             check(-got)
-        form = dict(zip(self.SPMV_FORM_FIELDS, (int(v) for v in out)))
+        return self._named_form(out)
+
+    def _named_form(self, fields):
+        form = dict(zip(self.SPMV_FORM_FIELDS, (int(v) for v in fields)))
         names = self.SPMV_FAMILIES + self.SPMV_FAMILIES_EXTRA + self.SPMV_FAMILIES_SPLIT
         form["family"] = names[form["family"]] if form["family"] >= 0 else None
         return form
+
+    SPMV_FORM_INPUTS = 62
+
+    def spmv_form(self, fused=True, with_inputs=False):
+        """the form the SpMV of this handle's launched loop will take (include/cgamd.h cgamd_solver_spmv_form), in the layout of
+        last_spmv_form(); nothing is launched.  with_inputs: (form, the ints of the call, plan and tuning the decision read)"""
+        out = (ctypes.c_int * len(self.SPMV_FORM_FIELDS))()
+        inputs = (ctypes.c_int * self.SPMV_FORM_INPUTS)()
+        got = self._lib.cgamd_solver_spmv_form(self.handle, 1 if fused else 0, inputs, len(inputs), out, len(out))
+        if got < 0:
+            check(-got)
+        form = self._named_form(out)
+        return (form, [int(v) for v in inputs]) if with_inputs else form
 
     def dot_partials(self):
         """the d.q partials of the last spmv(..., fused_dot=True): (n_rhs, partials per right-hand side), float64 / complex128"""

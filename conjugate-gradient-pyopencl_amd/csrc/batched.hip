@@ -194,7 +194,7 @@ static int spmv_batched_impl(const SpmvPlan &plan, int n, long long nnz, int nsy
     a.partials = static_cast<typename VT<T>::acc *>(partials);
     a.P = plan.n_partials;
     a.row_blocks = plan.row_blocks;
-    a.cycle = tune().spmv_cycle > 0 ? tune().spmv_cycle : 1;
+    a.cycle = spmv_cycle_now(tune());
     a.capc = a.capv = 0; a.vbufs = 1; a.spw = 1;
     const bool fuse = partials != nullptr;
     const dim3 block(kBlock);
@@ -205,7 +205,7 @@ static int spmv_batched_impl(const SpmvPlan &plan, int n, long long nnz, int nsy
     a.capv = ((span + 2 * EPC) + 3) & ~3;
     const size_t fixed = 64 + (size_t)a.capc * 4;   // the block sum's wave slots, then the columns
     const bool elem_aligned = (reinterpret_cast<uintptr_t>(vals) % sizeof(T)) == 0 && (reinterpret_cast<uintptr_t>(cols) % 4) == 0;
-    const bool nt = tune().spmv_nt >= 0 ? (tune().spmv_nt != 0) : (plan.nt != 0);
+    const bool nt = spmv_nt_now(tune(), plan);
     if (nsys > 65535) return fail(CGAMD_ERR_INVALID, "batched spmv: more than 65535 systems");
     // the limit holds for the slice as it is staged: one system's values and the columns, with their alignment slack
     if (plan.max_span <= 0 || !elem_aligned || fixed + (size_t)a.capv * sizeof(T) > (size_t)kMaxSpmmSliceBytes) {
@@ -222,7 +222,7 @@ static int spmv_batched_impl(const SpmvPlan &plan, int n, long long nnz, int nsy
     for (int w = nsys; w > 1; --w)
         if ((long long)plan.row_blocks * ((nsys + w - 1) / w) >= 1024) { a.spw = w; break; }
     const dim3 grid(gx, (nsys + a.spw - 1) / a.spw);
-    const int fit = plan.max_row <= 0 ? 8 : plan.max_row <= 4 ? 4 : plan.max_row == 5 ? 5 : plan.max_row <= 7 ? 7 : 8;
+    const int fit = batch_fit(plan.max_row);
     const int unroll = sizeof(T) > 8 ? 4 : fit;
     const int form[kSpmvFormFields] = {6, 1, unroll, 0, 0, nt, fuse, 0, (int)gx, fuse ? a.P : 0};
     record_spmv_form(form);

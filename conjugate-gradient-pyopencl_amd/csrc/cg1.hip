@@ -361,7 +361,7 @@ static int spmv_cg1_impl(const SpmvPlan &plan, int n, long long nnz, const void 
     a.partials = static_cast<typename VT<T>::acc *>(partials);
     a.row_blocks = plan.row_blocks; a.rb_list = nullptr; a.rb_count = 0;
     a.cap = (plan.max_span + 3) & ~3;
-    a.cycle = tune().spmv_cycle > 0 ? tune().spmv_cycle : 1;
+    a.cycle = spmv_cycle_now(tune());
     const bool p2p = e != nullptr;
     g.halo = nullptr; g.halo_flag = halo_flag; g.n_local = n; g.rotate = 0; g.push_chunks = 1;
     g.iter = iter; g.slot_epoch = slot_epoch;
@@ -385,7 +385,7 @@ static int spmv_cg1_impl(const SpmvPlan &plan, int n, long long nnz, const void 
     const int grid = rowblock_grid(plan.row_blocks, a.cycle);
     if (p2p && grid < e->n_peers * g.push_chunks) return fail(CGAMD_ERR_STATE, "spmv_cg1: fewer work-groups than push chunks");
     const dim3 gd(grid), block(kBlock);
-    const bool nt = tune().spmv_nt >= 0 ? (tune().spmv_nt != 0) : (plan.nt != 0);
+    const bool nt = spmv_nt_now(tune(), plan);
     constexpr int U = sizeof(T) > 8 ? 4 : 8;
     const int fit = (sizeof(T) > 8 || tune().spmv_unroll) ? U : plan.max_row == 5 ? 5 : (plan.max_row == 6 || plan.max_row == 7) ? 7 : U;
 #define CG1_L(UU, CO, PP)                                                                                              \

@@ -504,7 +504,7 @@ static int spmv_p2p_impl(const SpmvPlan &plan, int n, long long nnz, const void 
     a.partials = static_cast<typename VT<T>::acc *>(partials);
     a.row_blocks = plan.row_blocks; a.rb_list = halo_flag; a.rb_count = plan.row_blocks;
     a.cap = (plan.max_span + 3) & ~3;
-    a.cycle = tune().spmv_cycle > 0 ? tune().spmv_cycle : 1;
+    a.cycle = spmv_cycle_now(tune());
     g.x = p2p_args(e);
     g.halo = static_cast<const T *>(e.my_halo);
     g.n_local = e.n_local; g.rotate = rotate; g.push_chunks = p2p_push_chunks(e);
@@ -519,9 +519,11 @@ static int spmv_p2p_impl(const SpmvPlan &plan, int n, long long nnz, const void 
     const int grid = rowblock_grid(plan.row_blocks, a.cycle);
     if (grid < e.n_peers * g.push_chunks) return fail(CGAMD_ERR_STATE, "spmv_p2p: fewer work-groups than push chunks");
     const dim3 gd(grid), block(kBlock);
-    const bool nt = tune().spmv_nt >= 0 ? (tune().spmv_nt != 0) : (plan.nt != 0);
+    const bool nt = spmv_nt_now(tune(), plan);
     constexpr int U = sizeof(T) > 8 ? 4 : 8;
-    // batch length of the row walk follows the longest row, as in spmv_impl (5 / 7: one batch per row of a 5- / 7-point stencil)
+    // batch length of the row walk follows the longest row (5 / 7: one batch per row of a 5- / 7-point stencil).  NOT batch_fit
+    // (spmv_plan.h): this rule has no batch of 4, and dev.spmv_unroll forces U here -- this launcher instantiates the batches 5, 7
+    // and U of its own kernel only, and stays as it is
     const int fit = (sizeof(T) > 8 || tune().spmv_unroll) ? U : plan.max_row == 5 ? 5 : (plan.max_row == 6 || plan.max_row == 7) ? 7 : U;
 #define CG_P2P(UU)                                                                                                      \
     do {                                                                                                                \
@@ -547,7 +549,7 @@ int launch_spmv_p2p(int dtype, const SpmvPlan &plan, int n, long long nnz, const
     CG_DISPATCH(dtype, spmv_p2p_impl, plan, n, nnz, vals, ptr, cols, d_ext, q, partials, halo_flag, rotate, e, st);
 }
 // work-groups the four-launch SpMV runs (they carry the push chunks)
-int spmv_p2p_grid(const SpmvPlan &plan) { return rowblock_grid(plan.row_blocks, tune().spmv_cycle > 0 ? tune().spmv_cycle : 1); }
+int spmv_p2p_grid(const SpmvPlan &plan) { return rowblock_grid(plan.row_blocks, spmv_cycle_now(tune())); }
 
 // Every work-group of aypx_beta_p2p_kernel spins until all ranks' r.r slots have arrived, and this rank's own slot is
 // published by work-group 0 of the same launch: the launch is only safe if the whole grid is resident at once (a queued

@@ -483,7 +483,7 @@ static int setup_long_rows(cgamd_solver *s) {
     seg = std::max(seg & ~3, 4);
     LongRows lr;
     int spans[8];
-    const int cycle = tune().spmv_cycle > 0 ? tune().spmv_cycle : 1;
+    const int cycle = spmv_cycle_now(tune());
     if (int rc = build_long_rows(s->n, s->ptr, s->plan.row_blocks, heavy_entries, seg, dtype_size(s->dtype), cycle, s->ctx->stream, &lr, spans)) return rc;
     if (lr.n_heavy == 0) return CGAMD_OK;
     // the body's kernel, chosen from the regular blocks' spans by the rules of every other handle
@@ -1538,21 +1538,47 @@ long long cgamd_solver_iter_bytes(cgamd_solver *s, int fused) {
 // reference's op structure; the tridiagonal M: tri_passes).  Handles whose iterate() runs a resident loop report the launched loop
 // they fall back to.
 static long long long_rows_scratch_traffic(const cgamd_solver *s) { return s->plan.lr.on ? 2LL * (long long)s->plan.lr.scratch_bytes : 0; }
-static long long index_bytes_per_nnz(const cgamd_solver *s) { return s->plan.codes ? (s->plan.codes16 ? 2 : 1) : 4; }
-// the single-RHS SpMV of this handle runs on joint codes (launch condition of spmv_impl: rows that fit one batch of the walk)
-static bool joint_form(const cgamd_solver *s) {
-    const int fit = s->plan.max_row <= 0 ? 8 : s->plan.max_row <= 4 ? 4 : s->plan.max_row == 5 ? 5 : s->plan.max_row <= 7 ? 7 : 8;
-    return s->plan.jcodes && s->nrhs == 1 && s->plan.max_row > 0 && s->plan.max_row <= fit && dtype_size(s->dtype) <= 8;
+// The form the SpMV of the handle's launched loop takes: the decision of the launcher itself (spmv_form.cpp), asked with the call
+// enqueue_spmv makes through launch_spmv -- the handle's own arrays, the direction d in, q out, the d.q partials unless the handle
+// sums them in a launch of its own.  Every accessor and byte model below is read off this form.  (Handles whose loop SpMV is another
+// launcher's -- launch_spmv_batched, the row-major SpMM, the two-launch loop -- have none of the codes, and are priced on aValues
+// and aCols as before.)
+static bool loop_fused(const cgamd_solver *s) { return !((s->flags & CGAMD_UNFUSED) && !tri_on(s) && !(s->nsys && s->pre.mdiag)); }
+static SpmvCall loop_call(const cgamd_solver *s, bool fused) {
+    SpmvCall c;
+    c.value_bytes = (int)dtype_size(s->dtype); c.acc_bytes = (int)acc_size(s->dtype); c.n = s->n; c.nrhs = s->nrhs;
+    c.vec = aligned16(s->vals) && aligned16(s->cols);
+    c.codes_for = s->plan.codes_for == s->cols; c.vcodes_for = s->plan.vcodes_for == s->vals; c.rcodes_for = s->plan.rcodes_for == s->ptr;
+    c.fuse = fused;
+    c.x16 = aligned16(s->d); c.y16 = aligned16(s->q); c.d16 = aligned16(s->herm ? s->d2 : s->d);
+    return c;
 }
-// ... on row-pattern codes (spmv_impl takes that form before the joint one)
-static bool row_form(const cgamd_solver *s) { return joint_form(s) && s->plan.rcodes && s->plan.rcodes_for == s->ptr && s->tune.dev_row_codes != 0 && s->tune.dev_vc_pipe != 0; }
+static SpmvForm loop_form(const cgamd_solver *s) { return choose_spmv_form(s->plan, s->tune, loop_call(s, loop_fused(s))); }
+static bool row_coded(const SpmvForm &f) { return f.family == 7 || f.family == 8; }
+// bytes of the matrix one SpMV of that form reads: one code byte per row (no per-non-zero bytes, no row pointers), or per non-zero
+// the index as encoded (aCols 4, 8-bit codes 1, 16-bit codes 2) and the value (joint and row codes: none beside the index byte; value
+// codes: 1; else aValues of every system) and the row pointers
+static long long matrix_moved_bytes(const cgamd_solver *s, const SpmvForm &f) {
+    if (row_coded(f)) return (long long)s->n_user;
+    const long long value_bytes = f.venc >= 2 ? 0 : f.venc == 1 ? 1 : (long long)dtype_size(s->dtype) * value_arrays(s);
+    return s->nnz * (value_bytes + (f.ienc == 8 ? 1 : f.ienc == 16 ? 2 : 4)) + ((long long)s->n_user + 1) * 4;
+}
 long long cgamd_solver_spmv_moved_bytes(cgamd_solver *s) {
     if (!s) return 0;
-    const long long V = (long long)dtype_size(s->dtype);
-    if (row_form(s)) return (long long)s->n_user + 2LL * s->n_user * V;       // one code byte per row, x read, y written: no per-non-zero bytes, no row pointers
-    const long long value_bytes = joint_form(s) ? 0 : s->plan.vcodes ? 1 : V * value_arrays(s);      // value codes: one byte per entry instead of the value; joint codes: one byte for both
+    // the matrix, x read, y written
     // (CGAMD_SPLIT_LONG_ROWS: the body's bytes and the heavy blocks' entries once are the matrix once; the piece scratch is written and read)
-    return s->nnz * (value_bytes + index_bytes_per_nnz(s)) + ((long long)s->n_user + 1) * 4 + 2LL * s->n_user * V * s->nrhs + long_rows_scratch_traffic(s);
+    return matrix_moved_bytes(s, loop_form(s)) + 2LL * s->n_user * (long long)dtype_size(s->dtype) * s->nrhs + long_rows_scratch_traffic(s);
+}
+int cgamd_solver_spmv_form(cgamd_solver *s, int fused, int *inputs, int n_inputs, int *form, int n_form) {
+    if (!s || !form || n_form < 1) return -fail(CGAMD_ERR_INVALID, "spmv_form: null or empty output");
+    const SpmvCall c = loop_call(s, fused != 0);
+    int in[kSpmvFormInputs], out[kSpmvFormFields];
+    spmv_form_pack(s->plan, s->tune, c, in);
+    choose_spmv_form(s->plan, s->tune, c).record(out);
+    for (int i = 0; inputs && i < n_inputs && i < kSpmvFormInputs; ++i) inputs[i] = in[i];
+    const int k = n_form < kSpmvFormFields ? n_form : kSpmvFormFields;
+    for (int i = 0; i < k; ++i) form[i] = out[i];
+    return k;
 }
 int cgamd_solver_long_rows(cgamd_solver *s, int *out, int n_out) {
     if (!s || !out || n_out < 1) return -fail(CGAMD_ERR_INVALID, "solver_long_rows: null or empty output");
@@ -1563,34 +1589,28 @@ int cgamd_solver_long_rows(cgamd_solver *s, int *out, int n_out) {
     return n_out < 6 ? n_out : 6;
 }
 int cgamd_solver_value_codes(cgamd_solver *s) { return s ? s->n_values : -CGAMD_ERR_INVALID; }
-int cgamd_solver_joint_codes(cgamd_solver *s) { return s ? (joint_form(s) ? s->n_pairs : 0) : -CGAMD_ERR_INVALID; }
-int cgamd_solver_row_codes(cgamd_solver *s) { return s ? (row_form(s) ? s->n_user_patterns : 0) : -CGAMD_ERR_INVALID; }
-int cgamd_solver_row_pairs(cgamd_solver *s) {
-    if (!s) return -CGAMD_ERR_INVALID;
-    return row_form(s) && s->plan.pcodes && row_pairs_wanted(s->tune.dev_row_pairs, dtype_size(s->dtype)) ? s->n_pair_patterns : 0;
-}
+int cgamd_solver_joint_codes(cgamd_solver *s) { return s ? (loop_form(s).venc >= 2 ? s->n_pairs : 0) : -CGAMD_ERR_INVALID; }
+int cgamd_solver_row_codes(cgamd_solver *s) { return s ? (row_coded(loop_form(s)) ? s->n_user_patterns : 0) : -CGAMD_ERR_INVALID; }
+int cgamd_solver_row_pairs(cgamd_solver *s) { return s ? (loop_form(s).family == 8 ? s->n_pair_patterns : 0) : -CGAMD_ERR_INVALID; }
 int cgamd_solver_spmv_schedule(cgamd_solver *s, int *kind, int *grid, long long *unit_rows) {
     if (!s) return fail(CGAMD_ERR_INVALID, "spmv_schedule: solver is NULL");
-    const bool rf = row_form(s);
-    const bool table = rf && s->plan.sched != nullptr;
-    if (kind) *kind = table ? 1 : 0;
-    if (unit_rows) *unit_rows = rf ? s->sched_unit : 0;
-    if (grid) {
-        const int supers = (s->plan.row_blocks + kSuperRows / kBlock - 1) / (kSuperRows / kBlock);
-        // the launch site's own arithmetic (spmv.hip: a.cycle from tune(), which is s->tune inside every call of this handle)
-        const int cyc = std::max(1, (s->tune.spmv_cycle > 0 ? s->tune.spmv_cycle : 1) / (kSuperRows / kBlock));
-        *grid = table ? s->plan.sched_grid : rf ? rowblock_grid(supers, cyc) : 0;
-    }
+    const SpmvForm f = loop_form(s);
+    if (kind) *kind = row_coded(f) && f.table ? 1 : 0;
+    if (unit_rows) *unit_rows = row_coded(f) ? s->sched_unit : 0;
+    if (grid) *grid = row_coded(f) ? f.grid : 0;
     return CGAMD_OK;
 }
-int cgamd_solver_row_pipe(cgamd_solver *s) { return s ? (row_form(s) ? row_pipe_depth(s->tune.dev_row_pipe, dtype_size(s->dtype)) : 0) : -CGAMD_ERR_INVALID; }
+int cgamd_solver_row_pipe(cgamd_solver *s) {
+    if (!s) return -CGAMD_ERR_INVALID;
+    const SpmvForm f = loop_form(s);
+    return row_coded(f) ? f.depth : 0;
+}
 long long cgamd_solver_iter_moved_bytes(cgamd_solver *s) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
     const long long passes = s->herm ? (s->pre.mdiag ? 14 : 12) : (s->nsys && s->pre.mdiag) ? 12 : (s->flags & CGAMD_UNFUSED) ? 14 : s->pre.mdiag ? 12 : 10;
     const long long lag = x_lag_now(s);
-    const long long value_bytes = joint_form(s) ? 0 : s->plan.vcodes ? 1 : V * value_arrays(s);
-    const long long matrix = (row_form(s) ? (long long)s->n_user : s->nnz * (value_bytes + index_bytes_per_nnz(s)) + ((long long)s->n_user + 1) * 4) + long_rows_scratch_traffic(s);
+    const long long matrix = matrix_moved_bytes(s, loop_form(s)) + long_rows_scratch_traffic(s);
     if (s->pre.mg) return matrix + mg_bytes(s, cgamd_solver_spmv_moved_bytes(s));
     if (tri_on(s)) return matrix + tri_passes(s) * s->n_user * V;
     // the deferred x update: the d steps of a group of L iterations move 4 L + 1 vectors instead of 5 L, the steady state of a

@@ -245,9 +245,6 @@ __global__ __launch_bounds__(BLOCK) void spmv_rowblock_kernel(SpmvArgs<T> a) {
 // per thread: 92.9 -> see DESIGN.md), and the next pair's code dwords travel (registers) while the current pair is multiplied out of
 // LDS (two LDS buffers; the row pointers of the pair after that are loaded a step earlier still).  One d.q partial per 256-row
 // block, formed exactly as block_sum<256> forms it, as everywhere.
-constexpr int kVcBlocks = 4;      // row blocks per work-group
-static_assert(kVcBlocks * kBlock == kSuperRows, "the plane-matched schedule (solver.cpp) counts super blocks of kSuperRows rows");
-constexpr int kVcRows = 1;        // of which a thread walks this many at a time (one row of each): 2 were measured slower (108 VGPRs)
 template <typename T> CG_DEV T buf_gather(__amdgpu_buffer_rsrc_t rs, unsigned byte_off) {
     if constexpr (sizeof(T) == 4) {
         const unsigned w = __builtin_amdgcn_raw_buffer_load_b32(rs, byte_off, 0, 0);
@@ -1245,16 +1242,12 @@ void set_kernel_event_pair(hipEvent_t *pair) { t_kernel_events = pair; }
         }                                                                                                                      \
     } while (0)
 
-// cgamd_last_spmv_form: what the calling thread's most recent launch_spmv launched, stored AT the launch sites of spmv_impl (the
-// template arguments of the instance that goes out, not a second reading of the plan), so that a test can assert the form it was
-// written for.  [0] family (0 stream, 1 row-block, 2 vc, 3 vcp, 4 chunked, 5 grouped SpMM, 7 row-pattern codes, 9 split long rows; -1: nothing launched yet), [1] VEC,
+// cgamd_last_spmv_form: what the calling thread's most recent launch_spmv launched: the SpmvForm spmv_impl launched from, whose fields
+// are the template arguments of the instance that goes out (not a second reading of the plan), so that a test can assert the form it
+// was written for.  [0] family (numbered in spmv_form.h beside struct SpmvForm, row pairs = 8 included; -1: nothing launched yet), [1] VEC,
 // [2] batch length / lanes per row / group width, [3] index encoding (0 aCols, 8, 16), [4] value encoding (0 aValues, 1 two
 // code streams, 2 joint, 3 one pattern byte per row), [5] NT, [6] fused d.q, [7] wide, [8] grid.x, [9] d.q partials per right-hand side (0 when not fused).
 static thread_local int t_form[kSpmvFormFields] = {-1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-static inline void record_form(int family, bool vec, int width, int ienc, int venc, bool nt, bool fused, bool wide, unsigned gx, int parts) {
-    t_form[0] = family; t_form[1] = vec; t_form[2] = width; t_form[3] = ienc; t_form[4] = venc;
-    t_form[5] = nt; t_form[6] = fused; t_form[7] = wide; t_form[8] = (int)gx; t_form[9] = fused ? parts : 0;
-}
 void last_spmv_form(int *out, int n_out) {
     for (int i = 0; i < n_out && i < kSpmvFormFields; ++i) out[i] = t_form[i];
 }
@@ -1275,279 +1268,154 @@ SpmvPlan make_spmv_plan(int n) {
     return p;
 }
 
+// A runtime bool, or a runtime value out of a closed list, handed to a generic lambda as a compile-time constant (std::bool_constant,
+// std::integral_constant): the template arguments of a launch are read from the SpmvForm through these.  The LAST value of the list
+// stands for any other, so no call returns without a launch
+template <typename F> static void with_bool(bool b, F &&f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <int V, int... Vs, typename F> static void with_int(int v, F &&f) {
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V>{});
+    else if (v == V) f(std::integral_constant<int, V>{});
+    else with_int<Vs...>(v, f);
+}
+#define CG_V(x) decltype(x)::value
+
+template <typename T>
+static int spmv_impl(const SpmvPlan &plan, int n, long long nnz, const void *vals, const int *ptr, const int *cols, const void *x, long long ldx,
+                     void *y, long long ldy, int nrhs, const void *dvec, void *partials, const int *rb_list, int rb_count, hipStream_t st);
+// CGAMD_SPLIT_LONG_ROWS: the regular blocks by the form of the body plan on the block list, then the heavy blocks' two launches
+// (long_rows.hip); a linear chain on `st`.  The form recorded is the split's
+template <typename T>
+static int spmv_split(const SpmvPlan &plan, const SpmvForm &form, int n, long long nnz, const void *vals, const int *ptr, const int *cols,
+                      const void *x, long long ldx, void *y, long long ldy, const void *dvec, void *partials, hipStream_t st) {
+    const LongRows &lr = plan.lr;
+    if (form.body)
+        if (int rc = spmv_impl<T>(long_rows_body(plan), n, nnz, vals, ptr, cols, x, ldx, y, ldy, 1, dvec, partials, lr.regular, lr.n_regular, st)) return rc;
+    form.record(t_form);
+    return launch_long_rows(VT<T>::dtype, lr, form.nt != 0, n, nnz, vals, ptr, cols, x, y, dvec, partials, st);
+}
+
+// Fills the arguments, asks choose_spmv_form (spmv_form.cpp) which form the call gets, records it, launches it.  The switch and what
+// is under it read the form and the arguments only -- never the plan or the tuning: what is recorded and what goes out come from the
+// same fields
 template <typename T>
 static int spmv_impl(const SpmvPlan &plan, int n, long long nnz, const void *vals, const int *ptr, const int *cols,
                      const void *x, long long ldx, void *y, long long ldy, int nrhs, const void *dvec, void *partials,
                      const int *rb_list, int rb_count, hipStream_t st) {
+    using A = typename VT<T>::acc;
+    SpmvCall c;
+    c.value_bytes = sizeof(T); c.acc_bytes = sizeof(A); c.n = n; c.nrhs = nrhs;
+    c.vec = aligned16(vals) && aligned16(cols);
+    c.codes_for = plan.codes_for == cols; c.vcodes_for = plan.vcodes_for == vals; c.rcodes_for = plan.rcodes_for == ptr;
+    c.fuse = partials != nullptr;
+    c.rb_list = rb_list != nullptr; c.rb_count = rb_count;
+    c.x16 = aligned16(x); c.y16 = aligned16(y); c.d16 = aligned16(dvec);
+    const SpmvForm form = choose_spmv_form(plan, tune(), c);
+    if (form.family < 0) return CGAMD_OK;      // an empty row-block list
+    if (form.family == 9) return spmv_split<T>(plan, form, n, nnz, vals, ptr, cols, x, ldx, y, ldy, dvec, partials, st);
     SpmvArgs<T> a;
     a.n = n; a.nrhs = nrhs; a.nnz = nnz;
     a.vals = static_cast<const T *>(vals); a.ptr = ptr; a.cols = cols;
     a.x = static_cast<const T *>(x); a.ldx = ldx;
     a.y = static_cast<T *>(y); a.ldy = ldy;
     a.dvec = static_cast<const T *>(dvec);
-    a.partials = static_cast<typename VT<T>::acc *>(partials);
+    a.partials = static_cast<A *>(partials);
     a.row_blocks = plan.row_blocks;
     a.rb_list = rb_list; a.rb_count = rb_count;
-    a.codes = nullptr; a.dict = nullptr; a.vcodes = nullptr; a.vdict = nullptr;
-    const bool vec = aligned16(vals) && aligned16(cols);
-    const bool fuse = partials != nullptr;
-    const size_t dyn = (fuse && nrhs > 1) ? sizeof(typename VT<T>::acc) * nrhs * (kBlock / kWave) : 0;
-    dim3 grid(plan.grid), block(kBlock);
-    // CGAMD_SPLIT_LONG_ROWS: the regular blocks by their own kernel on the block list, then the heavy blocks' two launches (long_rows.hip);
-    // a linear chain on `st`.  The form recorded is the split's, with the body's width, index encoding and grid
-    if (plan.lr.on && vec && nrhs == 1 && !rb_list) {
-        const LongRows &lr = plan.lr;
-        int width = 0, ienc = 0;
-        unsigned gx = 0;
-        if (lr.n_regular > 0) {
-            SpmvPlan body = plan;
-            body.lr = LongRows();
-            body.kind = lr.body_kind; body.lpr = lr.body_lpr; body.max_span = lr.body_max_span; body.max_row = lr.body_max_row;
-            for (int lv = 0; lv < 5; ++lv) body.chunk_span[lv] = lr.body_chunk_span[lv];
-            if (int rc = spmv_impl<T>(body, n, nnz, vals, ptr, cols, x, ldx, y, ldy, nrhs, dvec, partials, lr.regular, lr.n_regular, st)) return rc;
-            width = t_form[2]; ienc = t_form[3]; gx = (unsigned)t_form[8];
-        }
-        const bool nt = tune().spmv_nt >= 0 ? (tune().spmv_nt != 0) : (plan.nt != 0);
-        record_form(9, true, width, ienc, 0, nt, fuse, false, gx, plan.row_blocks);
-        return launch_long_rows(VT<T>::dtype, lr, nt, n, nnz, vals, ptr, cols, x, y, dvec, partials, st);
+    a.cap = form.cap; a.cycle = form.cycle;
+    // the code streams of the form: joint codes (one byte for offset and value), or column codes (8-bit: offsets in dict; 16-bit: the
+    // first column of every row block) with or without value codes
+    const bool joint = form.venc == 2;
+    a.codes = joint ? plan.jcodes : form.ienc ? plan.codes : nullptr;
+    a.dict = joint ? plan.jdict_off : form.ienc ? plan.dict : nullptr;
+    a.vcodes = form.venc == 1 ? plan.vcodes : nullptr;
+    a.vdict = static_cast<const T *>(joint ? plan.jdict_val : form.venc == 1 ? plan.vdict : nullptr);
+    RowcodeArgs<T> ra{};
+    if (form.family == 7) {
+        ra.n = n; ra.row_blocks = plan.row_blocks; ra.cycle = form.cycle; ra.n_patterns = plan.n_patterns;
+        ra.x = a.x; ra.y = a.y; ra.dvec = a.dvec; ra.partials = a.partials;
+        ra.rcodes = plan.rcodes; ra.rdict_len = plan.rdict_len; ra.rdict_off = plan.rdict_off;
+        ra.rdict_val = static_cast<const T *>(plan.rdict_val); ra.sched = plan.sched;
     }
-    const int variant = (vec && ((nrhs == 1 && plan.kind == 5) || (nrhs > 1 && plan.kind == 6 && plan.wide))) ? 5 : 0;
-    if (variant == 5) {
-        a.cap = (plan.max_span + 3) & ~3;
-        a.cycle = tune().spmv_cycle > 0 ? tune().spmv_cycle : 1;
-        dim3 g5(rb_list ? (rb_count > 0 ? rb_count : 1) : rowblock_grid(plan.row_blocks, a.cycle), nrhs);
-        if (rb_list && rb_count <= 0) return CGAMD_OK;
-        const bool nt = tune().spmv_nt >= 0 ? (tune().spmv_nt != 0) : (plan.nt != 0);
+    RowpairArgs<T> pa{};
+    if (form.family == 8) {
+        pa.n = n; pa.row_blocks = plan.row_blocks; pa.cycle = form.cycle; pa.n_pair_patterns = plan.n_pair_patterns;
+        pa.x = a.x; pa.y = a.y; pa.dvec = a.dvec; pa.partials = a.partials;
+        pa.pcodes = plan.pcodes; pa.pdict = plan.pdict; pa.sched = plan.sched;
+    }
+    const dim3 grid(form.grid, form.grid_y), block(kBlock);
+    const size_t lds = form.lds;
+    form.record(t_form);
+    switch (form.family) {
+    case 1:
         // (the value stream is staged interleaved across the lanes in 16-byte chunks, stage_slice_ilv: N=10M SpMV f64 186 -> 165 us,
         // c64 186 -> 166, c128 435 -> 314, f32 109 -> 105; the plain staging has no instance any more)
-        // one-byte column codes instead of aCols (build_index_codes; the codes belong to THIS cols array)
-        const bool coded_any = nrhs == 1 && plan.codes && plan.codes_for == cols && tune().index_codes != 0;
-        const bool coded = coded_any && !plan.codes16, coded16 = coded_any && plan.codes16;
-        // ... and one-byte value codes on top (matrices of at most 256 distinct entries; complex128 has none)
-        // (its staging covers slices of at most 8 x 256 entries: rows of 8 entries on average)
-        const bool vcoded = coded && !rb_list && plan.vcodes && plan.vcodes_for == vals && tune().value_codes != 0 && a.cap <= 8 * kBlock && (unsigned long long)n * sizeof(T) < (1ULL << 30);
-        a.codes = coded_any ? plan.codes : nullptr;
-        a.dict = coded_any ? plan.dict : nullptr;      // (16-bit form: the first column of every row block)
-        const size_t lds = coded ? (((size_t)a.cap * (sizeof(T) + 1) + 15) & ~(size_t)15)
-                                 : coded16 ? (((size_t)a.cap * (sizeof(T) + 2) + 15) & ~(size_t)15) : (size_t)a.cap * (sizeof(T) + 4);
-#define CG_RB(NT, UNR)                                                                                                  \
-    do {                                                                                                                \
-        if (coded16) {                                                                                                  \
-            record_form(1, true, UNR, 16, 0, NT, fuse, g5.y > 1, g5.x, plan.row_blocks);                                \
-            if (fuse) CG_LAUNCH_EV((spmv_rowblock_kernel<T, kBlock, NT, true, UNR, -4>), g5, block, lds, st, a);        \
-            else CG_LAUNCH_EV((spmv_rowblock_kernel<T, kBlock, NT, false, UNR, -4>), g5, block, lds, st, a);            \
-        } else if (coded) {                                                                                             \
-            record_form(1, true, UNR, 8, 0, NT, fuse, g5.y > 1, g5.x, plan.row_blocks);                                 \
-            if (fuse) CG_LAUNCH_EV((spmv_rowblock_kernel<T, kBlock, NT, true, UNR, -3>), g5, block, lds, st, a);        \
-            else CG_LAUNCH_EV((spmv_rowblock_kernel<T, kBlock, NT, false, UNR, -3>), g5, block, lds, st, a);            \
-        } else {                                                                                                        \
-            record_form(1, true, UNR, 0, 0, NT, fuse, g5.y > 1, g5.x, plan.row_blocks);                                 \
-            if (fuse) CG_LAUNCH_EV((spmv_rowblock_kernel<T, kBlock, NT, true, UNR, -2>), g5, block, lds, st, a);        \
-            else CG_LAUNCH_EV((spmv_rowblock_kernel<T, kBlock, NT, false, UNR, -2>), g5, block, lds, st, a);            \
-        }                                                                                                               \
-    } while (0)
-        // up to 8 gathers in flight per lane for 4/8-byte values; 4 for complex128 (8 would cost 3 waves/SIMD of occupancy).  A row is
-        // walked in batches of `unroll` slots (slots past the row's end re-read its last entry and are dropped): when no row of the
-        // matrix is longer than 5 or 7 entries (5-point, 7-point and P1-FE stencils) the batch is exactly that long -- one batch per
-        // row and no idle slot (N = 10M 7-point fp64: SpMV 134.7 -> 131.2 us, CG 4 215 -> 4 292 it/s; same sums, same bits)
-        const int fit = plan.max_row <= 0 ? 8 : plan.max_row <= 4 ? 4 : plan.max_row == 5 ? 5 : plan.max_row <= 7 ? 7 : 8;
-        const int unroll = tune().spmv_unroll ? tune().spmv_unroll : (sizeof(T) > 8 ? 4 : fit);
-        if constexpr (sizeof(T) <= 8) {
-            if (vcoded) {
-                a.vcodes = plan.vcodes; a.vdict = static_cast<const T *>(plan.vdict);
-                const size_t lds2 = (((size_t)a.cap * 4 * kVcRows + 15) & ~(size_t)15) + 16;      // two buffers x kVcRows blocks x two code streams (+ the unclamped reads' slack)
-                const int supers = (plan.row_blocks + kVcBlocks - 1) / kVcBlocks, cyc = std::max(1, a.cycle / kVcBlocks);
-                a.cycle = cyc;
-                const dim3 gvc(rowblock_grid(supers, cyc));
-                // rows that fit one batch (max_row <= unroll): the form with the gathers pipelined across the row blocks
-                const bool pipe = plan.max_row > 0 && plan.max_row <= unroll && tune().dev_vc_pipe != 0;
-                // ... and where at most 256 (offset, value) pairs occur: one joint code byte per non-zero
-                const bool joint = pipe && plan.jcodes && tune().dev_joint_codes != 0;
-                // ... and where the rows follow at most 256 patterns: one byte per ROW (build_row_codes), no row pointers and no code staging
-                const bool rowform = joint && plan.rcodes && plan.rcodes_for == ptr && tune().dev_row_codes != 0;
-                // ... whose super blocks the handle's plane-matched table deals to the XCDs where it has one (solver.cpp setup_xcd_schedule);
-                // the grid is the table's
-                const dim3 grc(plan.sched ? (unsigned)plan.sched_grid : gvc.x);
-                // ... and two rows per lane on one byte per PAIR of rows (build_row_pairs) where the vectors allow 16-byte accesses
-                // (a caller's Solver.spmv vectors may not: the row form takes those)
-                if (rowform && plan.pcodes && plan.pdict && plan.n_pair_patterns > 0 && row_pairs_wanted(tune().dev_row_pairs, sizeof(T)) && n >= 2 &&
-                    aligned16(a.x) && aligned16(a.y) && (!fuse || aligned16(a.dvec))) {
-                    RowpairArgs<T> pa;
-                    pa.n = n; pa.row_blocks = plan.row_blocks; pa.cycle = cyc; pa.n_pair_patterns = plan.n_pair_patterns;
-                    pa.x = a.x; pa.y = a.y; pa.dvec = a.dvec; pa.partials = a.partials;
-                    pa.pcodes = plan.pcodes; pa.pdict = plan.pdict; pa.sched = plan.sched;
-                    const size_t ldsp = pair_dict_stage_bytes(plan.n_pair_patterns, sizeof(T));
-                    record_form(8, true, unroll, 8, 3, nt, fuse, false, grc.x, plan.row_blocks);
-#define CG_RP(DEPTH, SLOTS)                                                                                             \
-    do {                                                                                                                \
-        if (nt) {                                                                                                \
-            if (fuse) CG_LAUNCH_EV((spmv_rowpair_kernel<T, kBlock, true, true, DEPTH, SLOTS>), grc, block, ldsp, st, pa);   \
-            else CG_LAUNCH_EV((spmv_rowpair_kernel<T, kBlock, true, false, DEPTH, SLOTS>), grc, block, ldsp, st, pa);       \
-        } else {                                                                                                        \
-            if (fuse) CG_LAUNCH_EV((spmv_rowpair_kernel<T, kBlock, false, true, DEPTH, SLOTS>), grc, block, ldsp, st, pa);  \
-            else CG_LAUNCH_EV((spmv_rowpair_kernel<T, kBlock, false, false, DEPTH, SLOTS>), grc, block, ldsp, st, pa);      \
-        }                                                                                                               \
-    } while (0)
-                    // passes whose gathers are in flight per wave: dev.row_pipe's depth, 4 meaning 2 here
-                    const int depth = std::min(2, row_pipe_depth(tune().dev_row_pipe, sizeof(T)));
-                    if (plan.pair_slots <= 7) { if (depth == 1) CG_RP(1, 7); else CG_RP(2, 7); }
-                    else { if (depth == 1) CG_RP(1, 8); else CG_RP(2, 8); }
-#undef CG_RP
-                    return check_launch("spmv_rowpair");
-                }
-                if (rowform) {
-                    RowcodeArgs<T> ra;
-                    ra.n = n; ra.row_blocks = plan.row_blocks; ra.cycle = cyc; ra.n_patterns = plan.n_patterns;
-                    ra.x = a.x; ra.y = a.y; ra.dvec = a.dvec; ra.partials = a.partials;
-                    ra.rcodes = plan.rcodes; ra.rdict_len = plan.rdict_len; ra.rdict_off = plan.rdict_off;
-                    ra.rdict_val = static_cast<const T *>(plan.rdict_val); ra.sched = plan.sched;
-                    const size_t ldsr = (size_t)plan.n_patterns * (8 * sizeof(T) + 8 * sizeof(int) + sizeof(int));
-                    record_form(7, true, unroll, 8, 3, nt, fuse, false, grc.x, plan.row_blocks);
-#define CG_RC(DEPTH)                                                                                                    \
-    do {                                                                                                                \
-        if (nt) {                                                                                                       \
-            if (fuse) CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, true, true, DEPTH>), grc, block, ldsr, st, ra);      \
-            else CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, true, false, DEPTH>), grc, block, ldsr, st, ra);          \
-        } else {                                                                                                        \
-            if (fuse) CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, false, true, DEPTH>), grc, block, ldsr, st, ra);     \
-            else CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, false, false, DEPTH>), grc, block, ldsr, st, ra);         \
-        }                                                                                                               \
-    } while (0)
-                    // row blocks whose gathers are in flight per wave (dev.row_pipe; 0 = the default rule)
-                    const int depth = row_pipe_depth(tune().dev_row_pipe, sizeof(T));
-                    if (depth == 1) CG_RC(1);
-                    else if (depth == 2) CG_RC(2);
-                    else CG_RC(4);
-#undef CG_RC
-                    return check_launch("spmv_rowcode");
-                }
-                if (joint) { a.codes = plan.jcodes; a.dict = plan.jdict_off; a.vdict = static_cast<const T *>(plan.jdict_val); a.vcodes = nullptr; }
-#define CG_VC(NT, UNR)                                                                                                  \
-    do {                                                                                                                \
-        if (joint) {                                                                                                    \
-            record_form(3, true, UNR, 8, 2, NT, fuse, false, gvc.x, plan.row_blocks);                                   \
-            if (fuse) CG_LAUNCH_EV((spmv_rowblock_vcp_kernel<T, kBlock, NT, true, UNR, true>), gvc, block, lds2, st, a); \
-            else CG_LAUNCH_EV((spmv_rowblock_vcp_kernel<T, kBlock, NT, false, UNR, true>), gvc, block, lds2, st, a);     \
-        } else if (pipe) {                                                                                              \
-            record_form(3, true, UNR, 8, 1, NT, fuse, false, gvc.x, plan.row_blocks);                                   \
-            if (fuse) CG_LAUNCH_EV((spmv_rowblock_vcp_kernel<T, kBlock, NT, true, UNR, false>), gvc, block, lds2, st, a); \
-            else CG_LAUNCH_EV((spmv_rowblock_vcp_kernel<T, kBlock, NT, false, UNR, false>), gvc, block, lds2, st, a);    \
-        } else {                                                                                                        \
-            record_form(2, true, UNR, 8, 1, NT, fuse, false, gvc.x, plan.row_blocks);                                   \
-            if (fuse) CG_LAUNCH_EV((spmv_rowblock_vc_kernel<T, kBlock, NT, true, UNR>), gvc, block, lds2, st, a);       \
-            else CG_LAUNCH_EV((spmv_rowblock_vc_kernel<T, kBlock, NT, false, UNR>), gvc, block, lds2, st, a);           \
-        }                                                                                                               \
-    } while (0)
-                if (unroll == 4) { if (nt) CG_VC(true, 4); else CG_VC(false, 4); }
-                else if (unroll == 5) { if (nt) CG_VC(true, 5); else CG_VC(false, 5); }
-                else if (unroll == 7) { if (nt) CG_VC(true, 7); else CG_VC(false, 7); }
-                else { if (nt) CG_VC(true, 8); else CG_VC(false, 8); }
-#undef CG_VC
-                return check_launch("spmv_rowblock_vc");
-            }
-        }
-        if (unroll == 4) { if (nt) CG_RB(true, 4); else CG_RB(false, 4); }
-        else if (unroll == 5) { if (nt) CG_RB(true, 5); else CG_RB(false, 5); }
-        else if (unroll == 7) { if (nt) CG_RB(true, 7); else CG_RB(false, 7); }
-        else { if (nt) CG_RB(true, 8); else CG_RB(false, 8); }
-#undef CG_RB
+        with_int<4, 5, 7, 8>(form.width, [&](auto U) { with_int<16, 8, 0>(form.ienc, [&](auto I) { with_bool(form.nt, [&](auto NT) { with_bool(form.fused, [&](auto F) {
+            constexpr int CODED = CG_V(I) == 16 ? -4 : CG_V(I) == 8 ? -3 : -2;
+            CG_LAUNCH_EV((spmv_rowblock_kernel<T, kBlock, CG_V(NT), CG_V(F), CG_V(U), CODED>), grid, block, lds, st, a);
+        }); }); }); });
         return check_launch("spmv_rowblock");
-    }
-    if (vec && nrhs == 1 && plan.kind == 7) {
-        if (rb_list && rb_count <= 0) return CGAMD_OK;
-        const int span = plan.chunk_span[plan.lpr == 2 ? 0 : plan.lpr == 4 ? 1 : plan.lpr == 8 ? 2 : plan.lpr == 16 ? 3 : 4];
-        a.cap = (span + 3) & ~3;
-        a.cycle = tune().spmv_cycle > 0 ? tune().spmv_cycle : 1;
-        const bool coded_any = plan.codes && plan.codes_for == cols && tune().index_codes != 0;
-        const bool coded = coded_any && !plan.codes16, coded16 = coded_any && plan.codes16;
-        a.codes = coded_any ? plan.codes : nullptr;
-        a.dict = coded_any ? plan.dict : nullptr;
-        const size_t lds = coded ? (((size_t)a.cap * (sizeof(T) + 1) + 15) & ~(size_t)15)
-                                 : coded16 ? (((size_t)a.cap * (sizeof(T) + 2) + 15) & ~(size_t)15) : (size_t)a.cap * (sizeof(T) + 4);
-        const dim3 g7(rb_list ? rb_count : rowblock_grid(plan.row_blocks, a.cycle));
-        const bool nt = tune().spmv_nt >= 0 ? (tune().spmv_nt != 0) : (plan.nt != 0);
+    case 2:
+    case 3:
+        if constexpr (sizeof(T) <= 8) {
+            with_int<4, 5, 7, 8>(form.width, [&](auto U) { with_bool(form.nt, [&](auto NT) { with_bool(form.fused, [&](auto F) {
+                if (form.family == 2) CG_LAUNCH_EV((spmv_rowblock_vc_kernel<T, kBlock, CG_V(NT), CG_V(F), CG_V(U)>), grid, block, lds, st, a);
+                else with_bool(joint, [&](auto J) { CG_LAUNCH_EV((spmv_rowblock_vcp_kernel<T, kBlock, CG_V(NT), CG_V(F), CG_V(U), CG_V(J)>), grid, block, lds, st, a); });
+            }); }); });
+        }
+        return check_launch("spmv_rowblock_vc");
+    case 7:
+        if constexpr (sizeof(T) <= 8) {
+            with_int<1, 2, 4>(form.depth, [&](auto D) { with_bool(form.nt, [&](auto NT) { with_bool(form.fused, [&](auto F) {
+                CG_LAUNCH_EV((spmv_rowcode_kernel<T, kBlock, CG_V(NT), CG_V(F), CG_V(D)>), grid, block, lds, st, ra);
+            }); }); });
+        }
+        return check_launch("spmv_rowcode");
+    case 8:
+        if constexpr (sizeof(T) <= 8) {
+            with_int<1, 2>(form.depth, [&](auto D) { with_int<7, 8>(form.pair_slots, [&](auto S) { with_bool(form.nt, [&](auto NT) { with_bool(form.fused, [&](auto F) {
+                CG_LAUNCH_EV((spmv_rowpair_kernel<T, kBlock, CG_V(NT), CG_V(F), CG_V(D), CG_V(S)>), grid, block, lds, st, pa);
+            }); }); }); });
+        }
+        return check_launch("spmv_rowpair");
+    case 4: {
         constexpr int U = sizeof(T) > 8 ? 4 : 8;
-#define CG_CH(NT, L)                                                                                                     \
-    do {                                                                                                                  \
-        if (coded16) {                                                                                                    \
-            record_form(4, true, L, 16, 0, NT, fuse, false, g7.x, plan.row_blocks);                                       \
-            if (fuse) hipLaunchKernelGGL((spmv_rowblock_chunked_kernel<T, kBlock, NT, true, L, U, 2>), g7, block, lds, st, a);      \
-            else hipLaunchKernelGGL((spmv_rowblock_chunked_kernel<T, kBlock, NT, false, L, U, 2>), g7, block, lds, st, a);          \
-        } else if (coded) {                                                                                               \
-            record_form(4, true, L, 8, 0, NT, fuse, false, g7.x, plan.row_blocks);                                        \
-            if (fuse) hipLaunchKernelGGL((spmv_rowblock_chunked_kernel<T, kBlock, NT, true, L, U, 1>), g7, block, lds, st, a);      \
-            else hipLaunchKernelGGL((spmv_rowblock_chunked_kernel<T, kBlock, NT, false, L, U, 1>), g7, block, lds, st, a);          \
-        } else {                                                                                                          \
-            record_form(4, true, L, 0, 0, NT, fuse, false, g7.x, plan.row_blocks);                                        \
-            if (fuse) hipLaunchKernelGGL((spmv_rowblock_chunked_kernel<T, kBlock, NT, true, L, U>), g7, block, lds, st, a); \
-            else hipLaunchKernelGGL((spmv_rowblock_chunked_kernel<T, kBlock, NT, false, L, U>), g7, block, lds, st, a);   \
-        }                                                                                                                 \
-    } while (0)
-        if (plan.lpr == 2) { if (nt) CG_CH(true, 2); else CG_CH(false, 2); }
-        else if (plan.lpr == 4) { if (nt) CG_CH(true, 4); else CG_CH(false, 4); }
-        else if (plan.lpr == 8) { if (nt) CG_CH(true, 8); else CG_CH(false, 8); }
-        else if (plan.lpr == 16) { if (nt) CG_CH(true, 16); else CG_CH(false, 16); }
-        else { if (nt) CG_CH(true, 32); else CG_CH(false, 32); }
-#undef CG_CH
+        with_int<2, 4, 8, 16, 32>(form.width, [&](auto L) { with_int<16, 8, 0>(form.ienc, [&](auto I) { with_bool(form.nt, [&](auto NT) { with_bool(form.fused, [&](auto F) {
+            constexpr int CODED = CG_V(I) == 16 ? 2 : CG_V(I) == 8 ? 1 : 0;
+            hipLaunchKernelGGL((spmv_rowblock_chunked_kernel<T, kBlock, CG_V(NT), CG_V(F), CG_V(L), U, CODED>), grid, block, lds, st, a);
+        }); }); }); });
         return check_launch("spmv_rowblock_chunked");
     }
-    if (vec && nrhs > 1 && plan.kind == 6) {
-        a.cap = (plan.max_span + 3) & ~3;
-        a.cycle = tune().spmv_cycle > 0 ? tune().spmv_cycle : 1;
-        const size_t lds = (size_t)a.cap * (sizeof(T) + 4) + sizeof(typename VT<T>::acc) * nrhs * (kBlock / kWave);
-        dim3 g6(rowblock_grid(plan.row_blocks, a.cycle));
+    case 5: {
         constexpr int RBMAX = sizeof(T) <= 8 ? 8 : 4;
-        // One launch covers all right-hand sides (groups of RB inside the kernel).  Splitting into one launch per
-        // group (cgamd_tune "spmm_rb") re-reads the matrix per group and shrinks the x window per XCD; measured
-        // slower at nRHS = 32 (253 vs 220 us) and at nRHS = 9 -- kept as an experiment knob only.
-        const int chunk = (tune().spmm_rb > 0 && tune().spmm_rb < nrhs) ? tune().spmm_rb : nrhs;
-        const bool nt6 = tune().spmv_nt >= 0 ? (tune().spmv_nt != 0) : (plan.nt != 0);
-        // group width: the right-hand sides are cut into ceil(n / RBMAX) groups of (nearly) equal width, so that the last
-        // group is not mostly padding -- the reference's own shape, 9 sub-domains, runs as 5 + 4 instead of 8 + 1
-        const int ngroups = (chunk + RBMAX - 1) / RBMAX;
-        int rbw = tune().spmm_group > 0 ? tune().spmm_group : (chunk + ngroups - 1) / ngroups;
-        if (rbw > RBMAX) rbw = RBMAX;
-#define CG_MM(RBW)                                                                                                         \
-    do {                                                                                                                    \
-        record_form(5, true, RBW, 0, 0, nt6, fuse, false, g6.x, plan.row_blocks);                                           \
-        if (fuse) {                                                                                                         \
-            if (nt6) hipLaunchKernelGGL((spmm_rowblock_kernel<T, kBlock, true, true, RBW>), g6, block, lds, st, b);         \
-            else hipLaunchKernelGGL((spmm_rowblock_kernel<T, kBlock, false, true, RBW>), g6, block, lds, st, b);            \
-        } else {                                                                                                            \
-            if (nt6) hipLaunchKernelGGL((spmm_rowblock_kernel<T, kBlock, true, false, RBW>), g6, block, lds, st, b);        \
-            else hipLaunchKernelGGL((spmm_rowblock_kernel<T, kBlock, false, false, RBW>), g6, block, lds, st, b);           \
-        }                                                                                                                   \
-    } while (0)
-        for (int g0 = 0; g0 < nrhs; g0 += chunk) {
+        // (one launch per `chunk` right-hand sides: all of them in one launch unless the experiment knob cuts them)
+        for (int g0 = 0; g0 < nrhs; g0 += form.chunk) {
             SpmvArgs<T> b = a;
-            b.nrhs = (nrhs - g0 < chunk) ? nrhs - g0 : chunk;
+            b.nrhs = (nrhs - g0 < form.chunk) ? nrhs - g0 : form.chunk;
             b.x = a.x + (long long)g0 * ldx;
             b.y = a.y + (long long)g0 * ldy;
-            if (fuse) {
+            if (form.fused) {
                 b.dvec = a.dvec + (long long)g0 * ldx;
-                b.partials = a.partials + (long long)g0 * plan.row_blocks;
+                b.partials = a.partials + (long long)g0 * a.row_blocks;
             }
-            if (RBMAX == 8 && rbw > 6) CG_MM(RBMAX);
-            else if (RBMAX == 8 && rbw == 6) CG_MM(6);
-            else if (RBMAX == 8 && rbw == 5) CG_MM(5);
-            else if (rbw == 4 || (RBMAX == 4 && rbw > 3)) CG_MM(4);
-            else if (rbw == 3) CG_MM(3);
-            else CG_MM(2);
+            auto go = [&](auto W) { with_bool(form.nt, [&](auto NT) { with_bool(form.fused, [&](auto F) {
+                hipLaunchKernelGGL((spmm_rowblock_kernel<T, kBlock, CG_V(NT), CG_V(F), CG_V(W)>), grid, block, lds, st, b);
+            }); }); };
+            if constexpr (RBMAX == 8) with_int<8, 6, 5, 4, 3, 2>(form.width, go);       // (complex128: groups of at most 4)
+            else with_int<4, 3, 2>(form.width, go);
         }
-#undef CG_MM
         return check_launch("spmm_rowblock");
     }
-    if (vec) {
-        record_form(0, true, 0, 0, 0, false, fuse, false, grid.x, plan.grid);      // (the stream kernel has no NT parameter)
-        if (fuse) hipLaunchKernelGGL((spmv_stream_kernel<T, kBlock, kQuadsPerThread, true, true>), grid, block, dyn, st, a);
-        else hipLaunchKernelGGL((spmv_stream_kernel<T, kBlock, kQuadsPerThread, true, false>), grid, block, dyn, st, a);
-    } else {
-        record_form(0, false, 0, 0, 0, false, fuse, false, grid.x, plan.grid);
-        if (fuse) hipLaunchKernelGGL((spmv_stream_kernel<T, kBlock, kQuadsPerThread, false, true>), grid, block, dyn, st, a);
-        else hipLaunchKernelGGL((spmv_stream_kernel<T, kBlock, kQuadsPerThread, false, false>), grid, block, dyn, st, a);
+    default:
+        with_bool(form.vec, [&](auto VEC) { with_bool(form.fused, [&](auto F) {
+            hipLaunchKernelGGL((spmv_stream_kernel<T, kBlock, kQuadsPerThread, CG_V(VEC), CG_V(F)>), grid, block, lds, st, a);
+        }); });
+        return check_launch("spmv");
     }
-    return check_launch("spmv");
 }
+#undef CG_V
 
 int validate_csr_device(int n, long long nnz, int ncols, const int *ptr_dev, const int *cols_dev, const int *index_dev, int n_index,
                         int index_bound, int *scratch_dev, hipStream_t st) {
@@ -1684,13 +1552,13 @@ static int spmv_fused_impl(const SpmvPlan &plan, int n, long long nnz, const voi
     a.dvec = nullptr; a.partials = static_cast<A *>(part_dq);
     a.row_blocks = plan.row_blocks; a.rb_list = nullptr; a.rb_count = 0;
     a.cap = (plan.max_span + 3) & ~3;
-    a.cycle = tune().spmv_cycle > 0 ? tune().spmv_cycle : 1;
+    a.cycle = spmv_cycle_now(tune());
     FusedArgs<T> f;
     f.r = static_cast<const T *>(r); f.dnew = static_cast<T *>(d_new);
     f.part_rr = static_cast<const A *>(part_rr); f.P = P; f.K = sc.krr;
     f.delta = (T *)sc.delta; f.beta = (T *)sc.beta; f.history = (T *)sc.history; f.history_cap = sc.history_cap; f.iter = sc.iter;
     const dim3 g(rowblock_grid(plan.row_blocks, a.cycle), nrhs), b(kBlock);
-    const bool nt = tune().spmv_nt >= 0 ? (tune().spmv_nt != 0) : (plan.nt != 0);
+    const bool nt = spmv_nt_now(tune(), plan);
     const size_t lds = (size_t)a.cap * (sizeof(T) + 4);
     constexpr int U = sizeof(T) > 8 ? 4 : 8;
     if (nt) hipLaunchKernelGGL((spmv_fused_kernel<T, kBlock, true, U>), g, b, lds, st, a, f);

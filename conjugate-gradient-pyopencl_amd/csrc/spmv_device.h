@@ -56,15 +56,7 @@ __host__ __device__ __forceinline__ int rowblock_of(int b, int row_blocks, int c
     const int xb = (int)((long long)xcd * row_blocks / 8), xe = (int)((long long)(xcd + 1) * row_blocks / 8);
     return i < xe - xb ? xb + i : -1;
 }
-inline int rowblock_grid(int row_blocks, int cycle) {
-    if (cycle > 1) return 8 * ((cycle + 7) / 8) * ((row_blocks + cycle - 1) / cycle);
-    int per_xcd = 0;
-    for (int x = 0; x < 8; ++x) {
-        const int m = (int)((long long)(x + 1) * row_blocks / 8) - (int)((long long)x * row_blocks / 8);
-        per_xcd = m > per_xcd ? m : per_xcd;
-    }
-    return per_xcd * 8;
-}
+// (rowblock_grid, the padded grid of this schedule: spmv_plan.h)
 
 // Park the slice [cfirst, p1) of aValues/aCols in LDS with the VALUE stream interleaved across the lanes in 16-byte chunks:
 // chunk k of a lane is chunk k*64 + lane of

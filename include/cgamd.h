@@ -619,6 +619,14 @@ int cgamd_solver_dot_partials(cgamd_solver *s, void *out_host, long long cap_val
  * (CGAMD_ERR_INVALID then). */
 int cgamd_solver_step_plan(cgamd_solver *s, int *out, int n_out);
 int cgamd_solver_step_state(cgamd_solver *s, int which, void *out_host, long long cap_values, long long *count);
+/* Of the same standing: the form the SpMV of this handle's launched loop WILL take -- the launcher's own decision, asked without a
+ * launch -- in the layout of cgamd_last_spmv_form.  fused: with the d.q partials (what every loop but CGAMD_UNFUSED launches) or
+ * without.  Writes min(n_form, 10) ints to `form` and returns that count (negative: error).  inputs (may be NULL): min(n_inputs, 62)
+ * ints, everything the decision read -- the call (value and accumulator size, n, nRHS, alignments, whether the codes belong to the
+ * handle's arrays, fused, row-block list), the plan (pointers as 0 / 1) and the tuning keys, in the order of kSpmvFormInputNames
+ * (csrc/spmv_form.cpp).  cgamd_solver_joint_codes, _row_codes, _row_pairs, _row_pipe, _spmv_schedule, _spmv_moved_bytes and
+ * _iter_moved_bytes are read off this form. */
+int cgamd_solver_spmv_form(cgamd_solver *s, int fused, int *inputs, int n_inputs, int *form, int n_form);
 /* SpMM on the matrix cores (BASELINE config 4, "MFMA tall-B tile path"): Y[size][nRHS] = A * X[size][nRHS] with
  * the right-hand-side block in ROW-MAJOR layout (element i of RHS r at [i*nRHS + r]); f64 with nRHS = 16 or 32, f32 with 16, 32
  * or 64, complex64 with 16 or 32; any CSR matrix.  Solvers created with such a width keep their vectors in this layout
@@ -667,7 +675,8 @@ int cgamd_solver_joint_codes(cgamd_solver *s);
  * cgamd_last_spmv_form reports it as family 7, [2] batch length, [3] 8, [4] 3. */
 int cgamd_solver_row_codes(cgamd_solver *s);
 /* the number of row blocks (1, 2 or 4 of the 4 a work-group takes) whose gathers the handle's row-coded SpMV keeps in flight per wave:
- * the default, or what cgamd_tune("dev.row_pipe") forced when the handle was created.  Every depth forms the same bits.  0: the handle
+ * the default, or what cgamd_tune("dev.row_pipe") forced when the handle was created -- the depth the launch goes out with: a handle on
+ * the row-PAIR form keeps at most 2 of its two passes in flight and reports that.  Every depth forms the same bits.  0: the handle
  * does not run the row-coded form. */
 int cgamd_solver_row_pipe(cgamd_solver *s);
 /* the number of row-PAIR patterns of a handle whose row-coded SpMV takes two rows per lane: one byte per pair of rows (2p, 2p + 1)

@@ -209,6 +209,28 @@ def test_step_plan_and_step_state_entries_without_gpu(pkg):
     assert len(pkg.Solver.STEP_PLAN_FIELDS) == 11 and len(pkg.Solver.STEP_STATES) == 7
 
 
+def test_spmv_form_entry_without_gpu(pkg):
+    """the development entry behind Solver.spmv_form(): declared, exported by both libraries, bound with the header's signature, loud
+    about a null handle or output (nothing is written then); its inputs have the names and the count csrc/spmv_form.cpp lists"""
+    lib = pkg._lib.load()
+    assert "cgamd_solver_spmv_form" in _declared_functions("cgamd.h")
+    header = open(os.path.join(INCLUDE, "cgamd.h")).read()
+    assert "int cgamd_solver_spmv_form(cgamd_solver *s, int fused, int *inputs, int n_inputs, int *form, int n_form);" in header
+    assert "cgamd_solver_spmv_form" in _exports(pkg.LIB_PATH) and "cgamd_solver_spmv_form" in _exports(pkg.LEGACY_LIB_PATH)
+    pi = ctypes.POINTER(ctypes.c_int)
+    assert lib.cgamd_solver_spmv_form.argtypes == [ctypes.c_void_p, ctypes.c_int, pi, ctypes.c_int, pi, ctypes.c_int]
+    form, inputs = (ctypes.c_int * 10)(*([77] * 10)), (ctypes.c_int * 62)(*([77] * 62))
+    assert lib.cgamd_solver_spmv_form(None, 1, inputs, 62, form, 10) == -1 and b"spmv_form" in lib.cgamd_last_error()      # -CGAMD_ERR_INVALID
+    assert list(form) == [77] * 10 and list(inputs) == [77] * 62
+    assert "spmv_form" in dir(pkg.Solver) and pkg.Solver.SPMV_FORM_INPUTS == 62
+    src = open(os.path.join(os.path.dirname(pkg.LIB_PATH), "csrc", "spmv_form.h")).read()
+    assert "constexpr int kSpmvFormInputs = 62;" in src and "constexpr int kSpmvFormFields = 10;" in src
+    # the decision's files stay free of HIP: they are what the CPU test compiles alone
+    for name in ("spmv_form.h", "spmv_form.cpp", "spmv_plan.h"):
+        text = open(os.path.join(os.path.dirname(pkg.LIB_PATH), "csrc", name)).read()
+        assert "#include <hip" not in text and '#include "cgamd_internal.h"' not in text, name
+
+
 def test_python_module_mirrors_reference_names(pkg):
     """names and arity of the reference's cl.py (cl.py:16-44,203)"""
     import inspect
