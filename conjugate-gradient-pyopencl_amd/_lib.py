@@ -176,6 +176,13 @@ def load():
         "cgamd_solver_shift_history": (ci, [vp, vp, ci]),
         "cgamd_solver_shift_scalars": (ci, [vp, ci, vp]),
         "cgamd_shift_update": (ci, [vp, ci, ci, ll, ci, ci, vp, vp, vp, vp, vp, vp]),
+        "cgamd_solver_set_block": (ci, [vp, ci]),
+        "cgamd_solver_block_status": (ci, [vp, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_double)]),
+        "cgamd_solver_block_state": (ci, [vp, ci, vp]),
+        "cgamd_block_gram_grid": (ci, [ci]),
+        "cgamd_block_gram": (ci, [vp, ci, ci, ll, ci, vp, vp, vp]),
+        "cgamd_block_update_xw": (ci, [vp, ci, ci, ll, ci, vp, vp, vp, vp, vp, vp, vp]),
+        "cgamd_block_update_qp": (ci, [vp, ci, ci, ll, ci, vp, vp, vp, vp, ci]),
         "cgamd_gen_laplace3d": (ci, [vp, ci, ci, ci, ci, ll, ll, vp, vp, vp, ctypes.POINTER(ll)]),
         "cgamd_gen_poisson2d": (ci, [vp, ci, ci, vp, vp, vp, ctypes.POINTER(ll)]),
         "cgamd_gen_helm_fe_var": (ci, [vp, ci, ci, ctypes.c_double, vp, ctypes.c_double, ci, ci, vp, vp, vp, ctypes.POINTER(ll)]),

@@ -480,6 +480,80 @@ class Solver:
             its = self.iterate_until(tol, maxit, check_every)
         return self.x(), self.x_shifted(), its
 
+    # ---- block CG (include/cgamd.h "Block CG"): the n_rhs right-hand sides of one real SPD matrix share one Krylov space
+    MAX_BLOCK = 16
+
+    def _block_check(self):
+        """what block CG asks of the handle that Python can see: a real type and 2 ... 16 right-hand sides.  ValueError otherwise,
+        before anything touches the device"""
+        if np.dtype(self.dtype).kind == "c":
+            raise ValueError("block CG serves the real value types")
+        if not 2 <= self.n_rhs <= self.MAX_BLOCK:
+            raise ValueError(f"block CG takes the handle's n_rhs = 2 ... {self.MAX_BLOCK} right-hand sides as its block, got {self.n_rhs}")
+
+    def _block_tolerances(self, b, tol):
+        """(b as the handle takes it, the absolute tolerance of every column): tol is relative to |b_j|, a scalar or n_rhs values"""
+        t = self._tolerances(tol)
+        b = np.ascontiguousarray(np.asarray(b).reshape(-1), dtype=self.dtype)
+        if b.size != self.n_rhs * self.size:
+            raise ValueError(f"b must hold n_rhs x size = {self.n_rhs} x {self.size} values, got {b.size}")
+        nb = np.linalg.norm(b.reshape(self.n_rhs, self.size).astype(np.float64), axis=1)
+        return b, np.maximum(np.broadcast_to(t, (self.n_rhs,)) * nb, np.finfo(np.float64).tiny)
+
+    def set_block(self, on=True):
+        """From the next set_rhs on the handle runs block CG on its n_rhs right-hand sides (cgamd_solver_set_block): one Krylov space
+        for all columns, fewer iterations than any single solve, six launches per iteration.  Real types, 2 ... 16 right-hand sides,
+        no preconditioner and no shifts.  on=False returns the handle to the bits of one that never had it."""
+        if on:
+            self._block_check()
+        check(self._lib.cgamd_solver_set_block(self.handle, 1 if on else 0))
+
+    def block_status(self):
+        """{"on", "status" (0 running or stopped, 1 G failed, 2 W^T W failed, 3 NaN), "iteration" (of that event), "s",
+        "min_pivot_ratio"} (cgamd_solver_block_status; waits for the handle's stream)"""
+        info = (ctypes.c_int * 4)()
+        ratio = ctypes.c_double(0.0)
+        check(self._lib.cgamd_solver_block_status(self.handle, info, ctypes.byref(ratio)))
+        return {"on": bool(info[0]), "status": int(info[1]), "iteration": int(info[2]), "s": int(info[3]), "min_pivot_ratio": float(ratio.value)}
+
+    def block_state(self, which):
+        """development entry (cgamd_solver_block_state): one s x s matrix in float64 -- "xi", "G", "alpha", "tau", "C" (W^T W as summed),
+        "tau_inv" (tau^-1) or "M" (alpha xi)"""
+        idx = {"xi": 0, "G": 1, "alpha": 2, "tau": 3, "C": 4, "tau_inv": 5, "M": 6}[which]
+        out = np.empty((self.n_rhs, self.n_rhs), dtype=np.float64)
+        check(self._lib.cgamd_solver_block_state(self.handle, idx, ptr(out)))
+        return out
+
+    def solve_block(self, b, x0=None, tol=1e-6, maxit=1000, check_every=8):
+        """A X = B by block CG to |r_j| <= tol |b_j| for every column (tol: a scalar or n_rhs values): all columns stop in the first
+        iteration in which each satisfies its own tolerance.  Where the block breaks down -- duplicate or linearly dependent
+        right-hand sides -- the solve finishes on the same handle with the ordinary per-column loop from the X reached, each column's
+        tolerance still relative to the ORIGINAL |b_j|, so the answer is a converged one either way.  Returns (x, info): info["path"]
+        is "block" or "block+columns", with the iterations of each part, the breakdown record and the smallest pivot ratio.
+        Block CG stays on."""
+        self._block_check()
+        if int(maxit) < 0 or int(check_every) < 0:
+            raise ValueError("maxit and check_every must not be negative")
+        b, tol_abs = self._block_tolerances(b, tol)
+        self.set_block(True)
+        self.set_rhs(b, x0)
+        its = self.iterate_until(tol_abs, maxit, check_every)
+        st = self.block_status()
+        info = {"path": "block", "block_iterations": int(its[0]), "column_iterations": None, "status": st["status"],
+                "breakdown_iteration": st["iteration"], "min_pivot_ratio": st["min_pivot_ratio"]}
+        if st["status"] == 0:
+            return self.x(), info
+        x = self.x()
+        self.set_block(False)
+        try:
+            self.set_rhs(b, x)
+            info["column_iterations"] = self.iterate_until(tol_abs, max(int(maxit) - int(its[0]), 0), check_every)
+            info["path"] = "block+columns"
+            x = self.x()
+        finally:
+            self.set_block(True)
+        return x, info
+
     # ---- solution projection (include/cgamd.h "Solution projection"): start each solve from the span of the earlier ones
     def enable_projection(self, capacity, drop_tol=0.0):
         """Keep up to `capacity` (1 ... 32) A-orthonormal vectors per right-hand-side column spanning the recent solutions

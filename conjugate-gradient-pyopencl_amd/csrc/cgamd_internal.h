@@ -745,6 +745,33 @@ int launch_shift_scalars(int dtype, int nrhs, const ShiftScalars &sh, const CgSc
 int launch_shift_update(int dtype, int n, long long ld, int nrhs, int S, const void *r, void *xs, void *ds, const void *alpha_s, const void *beta_s,
                         const void *zeta_s, hipStream_t st, int vec_nt = 0, const CgStop *stop = nullptr);
 
+// ---- block CG (block_cg.hip): the s = nRHS right-hand sides of one real SPD matrix share one Krylov space.  The s x s matrices are
+// row-major at pitch s
+constexpr int kBlockMax = 16;
+struct BlockDev {
+    int *rec = nullptr;             // [0] status (0 fine, 1 G failed, 2 W^T W failed, 3 NaN), [1] the iteration of the event, [2] frozen
+    double *min_ratio = nullptr;    // the smallest pivot ratio since set_rhs
+    double *xi = nullptr, *G = nullptr, *alpha = nullptr, *tau = nullptr, *C = nullptr, *tau_inv = nullptr, *M = nullptr;
+    void *M_T = nullptr, *alpha_T = nullptr, *tinv_T = nullptr, *tau_T = nullptr;      // what the vector launches multiply by, in the value type
+    double *partials = nullptr;     // [s (s + 1) / 2][grid]
+};
+struct BlockState {
+    int S = 0;                      // 0: off
+    int grid = 0;                   // work-groups of the two launches that leave Gram partials
+    void *mem = nullptr;
+    BlockDev dev;
+};
+int block_gram_grid(long long n);
+int block_alloc(BlockState *b, int S, long long n);
+void block_free(BlockState *b);
+// frozen: the record's word every launch behind a breakdown or the stop leaves on (NULL: none)
+int launch_block_gram(int dtype, int n, long long ld, int S, const void *a, const void *b, double *part, int grid, const int *frozen, hipStream_t st);
+int launch_block_xw(int dtype, int n, long long ld, int S, const void *P, const void *AP, void *X, void *Q, const void *M, const void *AL, double *part,
+                    int grid, const int *frozen, hipStream_t st);
+int launch_block_qp(int dtype, int n, long long ld, int S, void *Q, void *P, const void *TI, const void *TA, bool init, const int *frozen, hipStream_t st);
+// mode 0: set_rhs, 1: the G step, 2: the W step (stop: iterate_until's tolerances and words)
+int launch_block_small(int dtype, int mode, const BlockState &b, const CgScalars &sc, const CgStop *stop, hipStream_t st);
+
 }  // namespace cgamd
 
 // ---- what mixed.cpp needs of its two handles beyond the C ABI (solver.cpp) ----
@@ -754,6 +781,7 @@ const void *solver_matrix(cgamd_solver *s, const int **ptr, const int **cols);  
 int solver_restart(cgamd_solver *s);        // set_rhs again from the b and the x the handle holds (x as written through cgamd_solver_vector)
 int solver_set_rhs_ld(cgamd_solver *s, const void *b, long long ldb);                // set_rhs(b, NULL, on_device) with b at stride ldb
 int solver_replace_residual_ld(cgamd_solver *s, const void *r_new, long long ldr);  // cgamd_solver_replace_residual, r_new at stride ldr
+bool solver_block_on(const cgamd_solver *s);      // cgamd_solver_set_block is in force: the mixed solve does not serve it
 int solver_replace_planned(cgamd_solver *s);        // would replace_residual refuse this handle after its next set_rhs?  (changes nothing)
 }  // namespace cgamd
 #pragma GCC visibility pop

@@ -158,6 +158,8 @@ int cgamd_mixed_solve(cgamd_mixed *m, const void *b, void *x, int on_device, con
     if (!(delta >= 0.) || !(delta < 1.)) return fail(CGAMD_ERR_INVALID, "mixed_solve: delta must be in [0, 1) (0 = 0.1)");
     if (delta == 0.) delta = 0.1;
     // what the inner handle cannot do (a line preconditioner, a row-major width) is its own refusal, before anything is touched
+    if (solver_block_on(m->outer) || solver_block_on(m->inner))
+        return fail(CGAMD_ERR_STATE, "mixed_solve: block CG is on (cgamd_solver_set_block) on one of the two handles, which this entry does not serve; turn it off first");
     if (int rc = solver_replace_planned(m->inner)) return rc;
     CG_HIP(hipSetDevice(m->ctx->device));
     hipStream_t st = m->ctx->stream;

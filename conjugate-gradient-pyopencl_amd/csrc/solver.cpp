@@ -120,7 +120,7 @@ static int enqueue_tri_sweep(cgamd_solver *s, bool update, const void *q, void *
 // Deferred x update: the lag the captured U-iteration graphs of this handle run with NOW (1 = none).  s->x_lag is what creation
 // decided and allocated for; the loop family may have changed since (a preconditioner, the row-major layout)
 static int x_lag_now(const cgamd_solver *s) {
-    if (s->x_lag < 2 || s->nsys || s->rm || precond_set(s) || (s->flags & (CGAMD_UNFUSED | CGAMD_NO_GRAPH)) || fused2_now(s) || nshifts(s)) return 1;
+    if (s->x_lag < 2 || s->nsys || s->rm || precond_set(s) || (s->flags & (CGAMD_UNFUSED | CGAMD_NO_GRAPH)) || fused2_now(s) || nshifts(s) || s->blk_on) return 1;
     return s->U % s->x_lag == 0 ? s->x_lag : 1;
 }
 static void *lag_dir(const cgamd_solver *s, int j) {
@@ -147,6 +147,27 @@ static int enqueue_lag_iteration(cgamd_solver *s, int k, int lag, int j, hipStre
     return launch_aypx_beta_xlag(dt, n, lag, s->r, dirs, s->x, n, s->part_rr, s->vgrid, nr, s->sc, st, s->plan.vec_nt);
 }
 
+// One block CG iteration (include/cgamd.h "Block CG"): the handle's SpMV as it is, without its dot, and the five launches of
+// block_cg.hip -- a linear chain.  Every launch behind a breakdown or the stop leaves on the record's frozen word, under
+// cgamd_solver_iterate as under cgamd_solver_iterate_until (g: the tolerances and the host's word); the SpMV is the unguarded one,
+// its q is read by nothing that writes then
+static int enqueue_block_iteration(cgamd_solver *s, int k, hipStream_t st, const CgStop *g) {
+    const int dt = s->dtype, n = s->n, S = s->nrhs;
+    const BlockState &b = s->blk;
+    const int *frozen = b.dev.rec + 2;
+    int rc;
+    if (b.S != S || precond_set(s) || nshifts(s) || s->rm || s->herm || s->nsys || (s->flags & CGAMD_UNFUSED))
+        return fail(CGAMD_ERR_STATE, "iterate: the handle is not in the state block CG was set up for");
+    if (s->ev_pair) CG_HIP(hipEventRecord(s->ev_pair[0], st));
+    if ((rc = handle_spmv(s, n, s->d, n, s->q, n, nullptr, nullptr, st))) return rc;
+    if (s->ev_pair) CG_HIP(hipEventRecord(s->ev_pair[1], st));
+    if ((rc = launch_block_gram(dt, n, n, S, s->d, s->q, b.dev.partials, b.grid, frozen, st))) return rc;
+    if ((rc = launch_block_small(dt, 1, b, s->sc, g, st))) return rc;
+    if ((rc = launch_block_xw(dt, n, n, S, s->d, s->q, s->x, s->r, b.dev.M_T, b.dev.alpha_T, b.dev.partials, b.grid, frozen, st))) return rc;
+    if ((rc = launch_block_small(dt, 2, b, s->sc, g, st))) return rc;
+    return launch_block_qp(dt, n, n, S, s->r, s->d, b.dev.tinv_T, b.dev.tau_T, false, frozen, st);
+}
+
 // lag >= 2 (capture of a U-iteration graph only): this is iteration k % lag of a group of the deferred x update
 // g (cgamd_solver_iterate_until): the same launches with the guarded instantiation of every kernel that writes x, r, d, a scalar, the
 // history or the counter (stop_device.h).  The SpMV is the unguarded one: q of a frozen right-hand side is recomputed from its frozen
@@ -155,6 +176,7 @@ static int enqueue_lag_iteration(cgamd_solver *s, int k, int lag, int j, hipStre
 static int enqueue_iteration(cgamd_solver *s, int k, hipStream_t st, int lag = 1, const CgStop *g = nullptr) {
     const int dt = s->dtype, n = s->n, nr = s->nrhs;
     int rc;
+    if (s->blk_on) return lag >= 2 ? fail(CGAMD_ERR_STATE, "iterate: block CG has no deferred x update") : enqueue_block_iteration(s, k, st, g);
     if (g && (lag >= 2 || fused2_now(s) || s->rm || (s->flags & CGAMD_UNFUSED)))
         return fail(CGAMD_ERR_STATE, "iterate_until: the loop this handle runs now has no guarded form");
     // (cgamd_solver_set_shifts and set_rhs see to it; any other loop with shifts in force is an error, never a run without them)
@@ -715,8 +737,12 @@ int cgamd::herm_refuses(const char *who, const char *why) {
 }
 // with shifts in force (cgamd_solver_set_shifts) the handle serves the unpreconditioned recurrence from x0 = 0 alone: a preconditioned
 // operator is not a shift of anything.  Refused before anything on the handle changes
-int cgamd::shifts_refuse(const cgamd_solver *s, const char *who) {
-    if (!s->sh.view.S) return CGAMD_OK;
+int cgamd::block_refuses(const cgamd_solver *s, const char *who) {
+    if (!s->blk_want) return CGAMD_OK;
+    return fail(CGAMD_ERR_STATE, std::string(who) + ": block CG is on (cgamd_solver_set_block), which this entry does not serve; turn it off first");
+}
+int cgamd::shifts_refuse(const cgamd_solver *s, const char *who, bool block_too) {
+    if (!s->sh.view.S) return block_too ? block_refuses(s, who) : CGAMD_OK;
     return fail(CGAMD_ERR_STATE, std::string(who) + ": shifts are in force (cgamd_solver_set_shifts), which this entry does not serve; remove them first");
 }
 extern "C" {
@@ -858,6 +884,7 @@ int cgamd_solver_destroy(cgamd_solver *s) {
     precond_drop(&s->pre);
     proj_free(s);
     shifts_free(s);
+    block_free(&s->blk);
     free_long_rows(&s->plan.lr);
     if (s->own_ptr && s->ptr) (void)hipFree(s->ptr);
     if (s->own_matrix) {
@@ -886,9 +913,13 @@ static int set_rhs_impl(cgamd_solver *s, const void *b, const void *x0, int on_d
     const bool rm = s->rm_ok && !precond_set(s);      // the preconditioned recurrence keeps the RHS-major kernels
     if (rm && (!b || ldb != s->n_user)) return fail(CGAMD_ERR_STATE, "the handle keeps its right-hand sides interleaved (row-major layout)");
     if (rm != s->rm) destroy_graphs(s);         // captured launch sequences belong to one layout
-    // (captured while the two-launch loop was set aside: iterate_until; with shifts in force it stays set aside)
-    if (s->until_mode && s->fused2 && !nshifts(s)) destroy_graphs(s);
-    s->until_mode = nshifts(s) > 0;
+    const bool blk = s->blk_want;               // block CG takes effect here, and goes here
+    if (blk && rm) return fail(CGAMD_ERR_STATE, "set_rhs: block CG is on (cgamd_solver_set_block), which the row-major layout does not serve");
+    if (blk != s->blk_on) destroy_graphs(s);
+    s->blk_on = blk;
+    // (captured while the two-launch loop was set aside: iterate_until; with shifts in force or block CG on it stays set aside)
+    if (s->until_mode && s->fused2 && !nshifts(s) && !blk) destroy_graphs(s);
+    s->until_mode = nshifts(s) > 0 || blk;
     s->until_stopped = s->stop.armed = false;
     s->proj.projected = s->proj.spent = false;      // (cgamd_solver_set_rhs_projected sets its mark after this call)
     s->rm = rm;
@@ -928,7 +959,12 @@ static int set_rhs_impl(cgamd_solver *s, const void *b, const void *x0, int on_d
     // r = b - A x0 ; d = r ; delta0 = r.r   (clcg.c:255-292)
     if ((rc = handle_spmv(s, s->n, s->x, s->n, s->q, s->n, nullptr, nullptr, st))) return rc;
     if ((rc = launch_sub(s->dtype, s->n, s->b, s->q, s->r, s->n, s->nrhs, st))) return rc;
-    if (s->herm) {    // d0 = r0 (d0 = m .* r0), dc = conj(d0), delta0 = r0^H r0, rho0 (hermitian.hip)
+    if (s->blk_on) {   // C = R0^T R0 = L L^T, xi = L^T, Q = R0 xi^-1 over r, P = Q, delta_0[j] = |xi e_j|^2; a dependent block freezes here
+        const BlockState &bk = s->blk;
+        if ((rc = launch_block_gram(s->dtype, s->n, s->n, s->nrhs, s->r, s->r, bk.dev.partials, bk.grid, nullptr, st))) return rc;
+        if ((rc = launch_block_small(s->dtype, 0, bk, s->sc, nullptr, st))) return rc;
+        if ((rc = launch_block_qp(s->dtype, s->n, s->n, s->nrhs, s->r, s->d, bk.dev.tinv_T, bk.dev.tau_T, true, bk.dev.rec + 2, st))) return rc;
+    } else if (s->herm) {    // d0 = r0 (d0 = m .* r0), dc = conj(d0), delta0 = r0^H r0, rho0 (hermitian.hip)
         if ((rc = launch_herm_init(s->dtype, s->n, s->r, s->d, s->d2, s->pre.mdiag, m_pitch(s), s->n, s->nrhs, s->part_rz, s->part_rr, s->vgrid, st))) return rc;
         if ((rc = launch_herm_delta0(s->dtype, s->pre.mdiag != nullptr, s->part_rz, s->part_rr, s->vgrid, s->nrhs, s->sc, s->pre.rho2, st))) return rc;
     } else if (s->pre.mg) {      // z0 = V-cycle(r0), p0 = z0, rho0 = r0.z0; the partials by the launches of an iteration
@@ -1142,6 +1178,7 @@ static int replace_refuses(const cgamd_solver *s, bool planned) {
     if (tri_on(s)) return fail(CGAMD_ERR_STATE, who + "a tridiagonal / line preconditioner is set; the entry serves no preconditioner or a diagonal one");
     if (s->pre.mg) return fail(CGAMD_ERR_STATE, who + "a multigrid preconditioner is set; the entry serves no preconditioner or a diagonal one");
     if (s->herm) return herm_refuses("replace_residual", "which the entry does not serve");
+    if (int rc = block_refuses(s, "replace_residual")) return rc;
     if (s->nsys) return fail(CGAMD_ERR_STATE, who + "the handle is batched");
     if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, who + "CGAMD_UNFUSED replays the reference's kernel sequence");
     return CGAMD_OK;
@@ -1473,6 +1510,7 @@ int cgamd_solver_layout(cgamd_solver *s) { return s ? (s->rm ? 1 : 0) : -CGAMD_E
 int cgamd_solver_loop_launches(cgamd_solver *s) {
     if (!s) return -CGAMD_ERR_INVALID;
     TuneScope ts(&s->tune);
+    if (s->blk_want) return 6;                           // block CG: SpMV, Gram, the G step, x / w update, the W step, q / p update, whatever s
     if (s->herm) return 4;                               // SpMV, herm_alpha, herm_axpy_dot, herm_aypx_beta_x under every flag
     if (s->pre.mg) return 5 + mg_cost(s->pre.mg).launches;       // SpMV, cg_alpha, r update, the V-cycle's chain, r.z, update
     if (tri_on(s)) return s->pre.tri.longform ? 6 : 4;      // launched loop only: SpMV, cg_alpha, the sweep (3 launches in the long form), update
@@ -1516,6 +1554,8 @@ static long long mg_bytes(const cgamd_solver *s, long long spmv_bytes) {
 }
 // the shift vector launch: r read once, x_j and d_j of every shift read and written
 static long long shift_bytes(const cgamd_solver *s) { return nshifts(s) ? (4LL * nshifts(s) + 1) * s->n_user * (long long)dtype_size(s->dtype) * s->nrhs : 0; }
+// the block loop: SpMV (P in, AP out) 2 + Gram (P, AP) 2 + x / w update (P, AP, X, Q in; X, Q out) 6 + q / p update (Q, P in and out) 4
+constexpr long long kBlockPasses = 14;
 static long long tri_passes(const cgamd_solver *s) {
     const long long f = value_arrays(s);
     if (s->pre.tri.stride > 1) return 14LL * s->nrhs + 3 * f;
@@ -1524,6 +1564,7 @@ static long long tri_passes(const cgamd_solver *s) {
 long long cgamd_solver_iter_bytes(cgamd_solver *s, int fused) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
+    if (s->blk_want) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + kBlockPasses * s->n_user * V * s->nrhs;
     if (s->pre.mg) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + mg_bytes(s, cgamd_solver_spmv_bytes(s));
     if (tri_on(s)) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + tri_passes(s) * s->n_user * V;
     // the conjugated recurrence: the launched loop's 10 passes (12 with a diagonal M) and conj(d), written by the d step and read by the SpMV's dot
@@ -1543,7 +1584,8 @@ static long long long_rows_scratch_traffic(const cgamd_solver *s) { return s->pl
 // sums them in a launch of its own.  Every accessor and byte model below is read off this form.  (Handles whose loop SpMV is another
 // launcher's -- launch_spmv_batched, the row-major SpMM, the two-launch loop -- have none of the codes, and are priced on aValues
 // and aCols as before.)
-static bool loop_fused(const cgamd_solver *s) { return !((s->flags & CGAMD_UNFUSED) && !tri_on(s) && !(s->nsys && s->pre.mdiag)); }
+// (the block loop forms its Gram matrix in a launch of its own: its SpMV carries no dot)
+static bool loop_fused(const cgamd_solver *s) { return !s->blk_want && !((s->flags & CGAMD_UNFUSED) && !tri_on(s) && !(s->nsys && s->pre.mdiag)); }
 static SpmvCall loop_call(const cgamd_solver *s, bool fused) {
     SpmvCall c;
     c.value_bytes = (int)dtype_size(s->dtype); c.acc_bytes = (int)acc_size(s->dtype); c.n = s->n; c.nrhs = s->nrhs;
@@ -1611,6 +1653,7 @@ long long cgamd_solver_iter_moved_bytes(cgamd_solver *s) {
     const long long passes = s->herm ? (s->pre.mdiag ? 14 : 12) : (s->nsys && s->pre.mdiag) ? 12 : (s->flags & CGAMD_UNFUSED) ? 14 : s->pre.mdiag ? 12 : 10;
     const long long lag = x_lag_now(s);
     const long long matrix = matrix_moved_bytes(s, loop_form(s)) + long_rows_scratch_traffic(s);
+    if (s->blk_want) return matrix + kBlockPasses * s->n_user * V * s->nrhs;
     if (s->pre.mg) return matrix + mg_bytes(s, cgamd_solver_spmv_moved_bytes(s));
     if (tri_on(s)) return matrix + tri_passes(s) * s->n_user * V;
     // the deferred x update: the d steps of a group of L iterations move 4 L + 1 vectors instead of 5 L, the steady state of a
@@ -1696,7 +1739,7 @@ int cgamd_solver_set_rhs_projected(cgamd_solver *s, const void *b, int on_device
     if (!s || !b) return fail(CGAMD_ERR_INVALID, "set_rhs_projected: null argument");
     TuneScope ts(&s->tune);
     if (int rc = proj_entry(s, "set_rhs_projected")) return rc;
-    if (int rc = shifts_refuse(s, "set_rhs_projected")) return rc;      // (the shifted systems start from x0 = 0)
+    if (int rc = shifts_refuse(s, "set_rhs_projected", false)) return rc;      // (the shifted systems start from x0 = 0; block CG takes any x0)
     if (!s->proj.cap) return fail(CGAMD_ERR_STATE, "set_rhs_projected: call cgamd_solver_projection_enable first");
     if (int rc = proj_refuses(s, "set_rhs_projected")) return rc;
     hipStream_t st = s->ctx->stream;
@@ -1819,6 +1862,7 @@ int cgamd_solver_set_shifts(cgamd_solver *s, const void *sigma, int nShifts) {
         s->until_mode = s->until_stopped = false;       // (the loop the shifts asked for; set_rhs decides anew)
         return CGAMD_OK;
     }
+    if (int rc = block_refuses(s, "set_shifts")) return rc;
     if (s->nsys) return fail(CGAMD_ERR_STATE, who + ": the handle is batched (a matrix of its own per right-hand side)");
     if (s->herm) return herm_refuses("set_shifts", "which the shifted recurrence does not serve yet");
     if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, who + ": CGAMD_UNFUSED replays the reference's kernel sequence");
@@ -1916,6 +1960,66 @@ int cgamd_solver_shift_scalars(cgamd_solver *s, int which, void *out_host) {
     return CGAMD_OK;
 }
 
+// ---- block CG (include/cgamd.h "Block CG"; kernels: block_cg.hip) -----------------------------------------------------------------
+int cgamd_solver_set_block(cgamd_solver *s, int on) {
+    const std::string who = "set_block";
+    if (int rc = shift_entry(s, "set_block")) return rc;
+    TuneScope ts(&s->tune);
+    if (!on) {          // the next set_rhs starts a handle that never had it
+        if (!s->blk_want && !s->blk_on) return CGAMD_OK;
+        CG_HIP(hipStreamSynchronize(s->ctx->stream));
+        block_free(&s->blk);
+        destroy_graphs(s);
+        s->blk_want = s->blk_on = false;
+        s->rhs_set = false;     // (r and d hold Q and P)
+        s->until_mode = s->until_stopped = false;
+        return CGAMD_OK;
+    }
+    if (s->dtype != CGAMD_F32 && s->dtype != CGAMD_F64)
+        return fail(CGAMD_ERR_STATE, who + ": block CG serves the real value types (the unconjugated block recurrence diverged on complex symmetric operators; the Hermitian form is a later piece of work)");
+    if (s->nsys) return fail(CGAMD_ERR_STATE, who + ": the handle is batched (a matrix of its own per right-hand side: no common Krylov space)");
+    if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, who + ": CGAMD_UNFUSED replays the reference's kernel sequence");
+    if (s->rm_ok) return fail(CGAMD_ERR_STATE, who + ": the handle keeps its right-hand sides interleaved (row-major layout)");
+    if (s->nrhs < 2 || s->nrhs > kBlockMax) return fail(CGAMD_ERR_STATE, who + ": the block is the handle's nRHS right-hand sides, 2 ... 16 of them");
+    if (precond_set(s)) return fail(CGAMD_ERR_STATE, who + ": a preconditioner is in force; remove it first");
+    if (nshifts(s)) return fail(CGAMD_ERR_STATE, who + ": shifts are in force (cgamd_solver_set_shifts); remove them first");
+    if (s->blk_want) return CGAMD_OK;
+    if (int rc = block_alloc(&s->blk, s->nrhs, s->n)) return rc;
+    s->blk_want = true;     // (blk_on, and with it the loop, changes at the next set_rhs)
+    return CGAMD_OK;
+}
+
+int cgamd_solver_block_status(cgamd_solver *s, int *info, double *min_pivot_ratio) {
+    if (int rc = shift_entry(s, "block_status")) return rc;
+    if (!info) return fail(CGAMD_ERR_INVALID, "block_status: info is NULL");
+    info[0] = s->blk_want ? 1 : 0; info[1] = 0; info[2] = 0; info[3] = s->nrhs;
+    if (min_pivot_ratio) *min_pivot_ratio = INFINITY;
+    if (!s->blk_on || !s->rhs_set) return CGAMD_OK;
+    struct { int rec[4]; double ratio; } img;
+    int it = 0;
+    hipStream_t st = s->ctx->stream;
+    CG_HIP(hipMemcpyAsync(&img, s->blk.dev.rec, sizeof(img), hipMemcpyDeviceToHost, st));
+    CG_HIP(hipMemcpyAsync(&it, s->sc.iter, sizeof(int), hipMemcpyDeviceToHost, st));
+    CG_HIP(hipStreamSynchronize(st));
+    info[1] = img.rec[0]; info[2] = img.rec[1];
+    if (min_pivot_ratio) *min_pivot_ratio = img.ratio;
+    if (img.rec[0]) s->iters = it;      // a breakdown froze the loop there, whatever was enqueued behind it
+    return CGAMD_OK;
+}
+
+// which: 0 xi, 1 G = P^T A P, 2 alpha = G^-1, 3 tau, 4 W^T W (R0^T R0 after set_rhs), 5 tau^-1, 6 M = alpha xi; s x s doubles, row-major
+int cgamd_solver_block_state(cgamd_solver *s, int which, void *out_host) {
+    if (int rc = shift_entry(s, "block_state")) return rc;
+    if (!out_host) return fail(CGAMD_ERR_INVALID, "block_state: out_host is NULL");
+    if (!s->blk_on || !s->rhs_set) return fail(CGAMD_ERR_STATE, "block_state: block CG is not running (cgamd_solver_set_block, then set_rhs)");
+    if (which < 0 || which > 6) return fail(CGAMD_ERR_INVALID, "block_state: which is 0 .. 6");
+    const BlockDev &d = s->blk.dev;
+    const double *src[] = {d.xi, d.G, d.alpha, d.tau, d.C, d.tau_inv, d.M};
+    CG_HIP(hipMemcpyAsync(out_host, src[which], sizeof(double) * (size_t)s->nrhs * s->nrhs, hipMemcpyDeviceToHost, s->ctx->stream));
+    CG_HIP(hipStreamSynchronize(s->ctx->stream));
+    return CGAMD_OK;
+}
+
 }  // extern "C"
 
 // ---- what the mixed-precision solve (mixed.cpp) needs of its two handles beyond the C ABI (cgamd_internal.h) ----
@@ -1930,6 +2034,7 @@ int solver_restart(cgamd_solver *s) {
 }
 int solver_set_rhs_ld(cgamd_solver *s, const void *b, long long ldb) { return set_rhs_impl(s, b, nullptr, 1, ldb); }
 int solver_replace_residual_ld(cgamd_solver *s, const void *r_new, long long ldr) { return replace_residual_impl(s, r_new, ldr); }
+bool solver_block_on(const cgamd_solver *s) { return s->blk_want; }
 int solver_replace_planned(cgamd_solver *s) {
     TuneScope ts(&s->tune);
     return replace_refuses(s, true);

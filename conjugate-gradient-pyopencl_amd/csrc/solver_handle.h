@@ -130,6 +130,12 @@ struct cgamd_solver {
         cgamd::ShiftScalars view;
         void *vec = nullptr, *scal = nullptr;
     } sh;
+    // block CG (cgamd_solver_set_block; block_cg.hip): the nrhs right-hand sides share one Krylov space.  blk_want: what the caller
+    // asked for, in force from the next set_rhs; blk_on: the right-hand side in force runs the block loop -- x = X, r = Q, d = P,
+    // q = A P, the SpMV and five launches per iteration, until_mode like every loop with d in one buffer.  blk: the small matrices,
+    // the record and the Gram partials (allocated by set_block, no n-sized buffer)
+    cgamd::BlockState blk;
+    bool blk_want = false, blk_on = false;
 };
 
 namespace cgamd {
@@ -143,7 +149,9 @@ int setup_resident_wide_plan(cgamd_solver *s);
 // refusals made before anything on the handle changes
 int batched_refuses(const char *who);
 int herm_refuses(const char *who, const char *why);
-int shifts_refuse(const cgamd_solver *s, const char *who);
+// block_too: the entry does not serve block CG either (cgamd_solver_set_block), which is every caller but set_rhs_projected
+int shifts_refuse(const cgamd_solver *s, const char *who, bool block_too = true);
+int block_refuses(const cgamd_solver *s, const char *who);
 // (solver_precond.cpp) the matrix behind a preconditioner built from it has changed: build it again -- or, where that fails, remove
 // it (the new values are in force, the old factors belong to the old ones) and fail with the build's status and text
 int rebuild_or_remove(cgamd_solver *s, const char *who);

@@ -1141,6 +1141,69 @@ int cgamd_solver_shift_scalars(cgamd_solver *s, int which, void *out_host);
 int cgamd_shift_update(cgamd_ctx *ctx, int dtype, int size, long long ld, int nRHS, int nShifts, const void *r, void *xs, void *ds,
                        const void *alpha_s, const void *beta_s, const void *zeta_s);
 
+/* ---- Block CG: the s = nRHS right-hand sides of one real SPD matrix share one Krylov space (csrc/block_cg.hip; O'Leary, "The block
+ * conjugate gradient algorithm and related methods", 1980, in the residual-orthonormalised form of Dubrulle, "Retooling the method of
+ * block conjugate gradients", 2001, "BCGrQ").  Every column searches the sum of all s Krylov spaces, so the block needs fewer
+ * iterations than any single solve (5-point Laplacians, independent random right-hand sides: two to three times fewer at s = 16).  The
+ * textbook recurrence is not built: its Gram matrices lose rank as the residuals shrink; here the residual block is kept as
+ * R = Q xi with Q orthonormal, and the matrices factored stay well conditioned (pivot ratios of 0.4 and above on those systems).
+ *   The handle's own vectors carry the block: x = X, r = Q, d = P, q = A P.  No n-sized buffer is allocated.
+ *   At cgamd_solver_set_rhs: R0 = B - A X0 as ever; C = R0^T R0 = L L^T; xi = L^T; Q = R0 xi^-1; P = Q; history row 0 is
+ *   delta_0[j] = |xi e_j|^2.  Iteration k, SIX launches whatever s, a linear chain:
+ *     1  A P                                  the handle's multi-RHS SpMV in whatever form it has, its fused dot unused
+ *     2  G = P^T (A P)                        per-work-group partials of the s (s + 1) / 2 distinct entries
+ *     3  G = L L^T, alpha = G^-1, M = alpha xi        one work-group, in double, the partials summed in fixed order
+ *     4  X += P M ; W = Q - (A P) alpha over Q        and the partials of W^T W; P, AP, X, Q read once, X and Q written once
+ *     5  W^T W = L L^T, tau = L^T, tau^-1, xi <- tau xi, delta_k[j] = |xi e_j|^2 into the history; the stop word and the breakdown record
+ *     6  Q <- W tau^-1 ; P <- Q + P tau^T      both in place
+ *   Small matrices in double, left-looking Cholesky by columns, every inner sum in index order; alpha, M, tau^-1 and tau are each rounded
+ *   once to the value type.  Vectors in the value type, one rounding per operation (tests/block_ref.py restates every order).
+ *   Captured graphs and CGAMD_NO_GRAPH give the same bits; iterate(a); iterate(b) gives the bits of iterate(a + b).
+ *   BREAKDOWN: a pivot v of either Cholesky counts as rank-deficient when not v > s eps_value max_j C_jj, C the matrix factored,
+ *   eps_value = 2^-23 (float) or 2^-52 (double) -- a condition, not a tuned number: exact or linearly dependent columns give pivot
+ *   ratios v / max_j C_jj of 5e-16 and below at set_rhs, healthy runs 0.4 and above.  The small step records which factorisation
+ *   failed and the iteration, and freezes the loop: every later launch of the chain leaves at once and writes nothing.  X stays the
+ *   last complete iterate: a failed G freezes before step 4, a failed W^T W after X is updated.  NaN freezes the same way.
+ * cgamd_solver_set_block: on != 0 turns block CG on, on == 0 off.  Takes effect at the next cgamd_solver_set_rhs (x0 is allowed), which
+ *   the next solve must start with; on = 0 returns the handle to the bits of one that never had it.  Returns CGAMD_ERR_STATE, the handle
+ *   untouched, on complex types (the unconjugated block recurrence diverged on complex symmetric operators; the Hermitian block form
+ *   is a later piece of work), batched handles, CGAMD_UNFUSED, the row-major layout, nRHS outside 2 ... 16, a preconditioner in force,
+ *   shifts in force.  With block CG on: CGAMD_ERR_STATE from every cgamd_solver_set_preconditioner* entry (except removal with NULL),
+ *   cgamd_solver_set_shifts, cgamd_solver_iterate_tol, cgamd_solver_replace_residual and cgamd_mixed_solve.
+ *   cgamd_solver_set_rhs_projected stays served: projection only chooses x0.  cgamd_solver_refresh_values and
+ *   cgamd_solver_reload_matrix keep the setting.
+ * cgamd_solver_iterate(k) runs k block iterations.  cgamd_solver_iterate_until stops ALL columns in the first iteration in which
+ *   every column satisfies its own tolerance -- the test of the plain loop, sqrt|delta_k[j]| >= tol[j] evaluated in double, on the
+ *   history entry -- so iterations_run[r] are all equal; a breakdown ends the call with the count reached.  The host reads one device
+ *   word per chunk as before, and the result does not depend on checkEvery.  cgamd_solver_history, cgamd_solver_get_x and
+ *   cgamd_solver_iterations_done behave as ever; after a breakdown inside cgamd_solver_iterate, cgamd_solver_block_status brings
+ *   cgamd_solver_iterations_done to the count reached.
+ * cgamd_solver_block_status: waits for the handle's stream; info[0] on or off, info[1] status (0 running or stopped, 1 G failed,
+ *   2 W^T W failed -- at iteration 0: R0^T R0 in set_rhs --, 3 NaN), info[2] the iteration of the event, info[3] s;
+ *   *min_pivot_ratio (may be NULL) the smallest v / max_j C_jj since set_rhs.
+ * Byte models: cgamd_solver_iter_bytes and cgamd_solver_iter_moved_bytes count the block loop's 14 vector passes per right-hand side
+ *   (SpMV 2, Gram 2, step 4: 6, step 6: 4) beside the matrix; cgamd_solver_loop_launches is 6. */
+int cgamd_solver_set_block(cgamd_solver *s, int on);
+int cgamd_solver_block_status(cgamd_solver *s, int *info, double *min_pivot_ratio);
+/* Development entries (tests; same standing as cgamd_shift_update).  _block_state waits for the handle's stream and copies one s x s
+ * matrix to the host in double, row-major -- which 0: xi, 1: G, 2: alpha, 3: tau, 4: W^T W as summed (after set_rhs: R0^T R0),
+ * 5: tau^-1, 6: M = alpha xi.
+ * The vector kernels alone on DEVICE arrays of the caller, enqueued on the ctx stream; blocks hold s vectors at stride ld, the rows
+ * between size and ld are neither read nor written; s x s factors in the value type, row-major, in device memory.  One thread owns a
+ * row, so there is one path whatever the alignment of ld.
+ * cgamd_block_gram: partials[p * grid + g], p = j (j + 1) / 2 + i, of a_i . b_j for i <= j, in double, grid = cgamd_block_gram_grid(size)
+ *   work-groups (negative on error).  cgamd_block_update_xw: x_j = (..(x_j + p_0 m_0j) + ..) + p_s-1 m_s-1,j ; q_j = (..(q_j - ap_0
+ *   alpha_0j) - ..) - ap_s-1 alpha_s-1,j, and the Gram partials of the new q with itself.  cgamd_block_update_qp: q_j = (..(q_0 ti_0j +
+ *   q_1 ti_1j) + ..) + q_j ti_jj ; p_j = (..(q_j + p_j tau_jj) + ..) + p_s-1 tau_j,s-1 in place (init != 0: p_j = q_j), tau_inv and tau
+ *   upper triangular. */
+int cgamd_solver_block_state(cgamd_solver *s, int which, void *out_host);
+int cgamd_block_gram_grid(int size);
+int cgamd_block_gram(cgamd_ctx *ctx, int dtype, int size, long long ld, int s, const void *a, const void *b, void *partials);
+int cgamd_block_update_xw(cgamd_ctx *ctx, int dtype, int size, long long ld, int s, const void *p, const void *ap, void *x, void *q,
+                          const void *m, const void *alpha, void *partials);
+int cgamd_block_update_qp(cgamd_ctx *ctx, int dtype, int size, long long ld, int s, void *q, void *p, const void *tau_inv, const void *tau,
+                          int init);
+
 #ifdef __cplusplus
 }
 #endif
