@@ -124,6 +124,7 @@ def load():
         "cgamd_solver_step_plan": (ci, [vp, ctypes.POINTER(ci), ci]),
         "cgamd_solver_spmv_form": (ci, [vp, ci, ctypes.POINTER(ci), ci, ctypes.POINTER(ci), ci]),
         "cgamd_solver_step_state": (ci, [vp, ci, vp, ll, ctypes.POINTER(ll)]),
+        "cgamd_solver_rowmajor_plan": (ci, [vp, ctypes.POINTER(ci), ci]),
         "cgamd_solver_layout": (ci, [vp]),
         "cgamd_solver_loop_launches": (ci, [vp]),
         "cgamd_solver_x_lag": (ci, [vp]),

@@ -899,6 +899,17 @@ class Solver:
             return int(out[0])
         return out.reshape((self.n_rhs, -1) if idx < 2 else (2, self.n_rhs) if idx == 5 else (self.n_rhs,))
 
+    ROWMAJOR_PLAN_FIELDS = ("n", "rc", "nh", "tq_fused", "tq_plain", "strips", "nwg_fused", "nwg_plain", "vgrid", "nt_axpy_dot", "nt_aypx_x",
+                            "kdq", "krr", "paced_fused", "paced_plain", "lead", "n_partials")
+
+    def rowmajor_plan(self):
+        """what the launches of this handle's row-major loop use now (include/cgamd.h cgamd_solver_rowmajor_plan), as a dict of ints"""
+        out = (ctypes.c_int * len(self.ROWMAJOR_PLAN_FIELDS))()
+        got = self._lib.cgamd_solver_rowmajor_plan(self.handle, out, len(out))
+        if got < 0:
+            check(-got)
+        return dict(zip(self.ROWMAJOR_PLAN_FIELDS, (int(v) for v in out)))
+
     def spmm_rowmajor(self, x, y, n_rhs):
         """Y[size][n_rhs] = A X on the matrix cores; x, y ROW-MAJOR device arrays, n_rhs in {16, 32}, f32/f64"""
         check(self._lib.cgamd_solver_spmm_rowmajor(self.handle, ptr(x), ptr(y), int(n_rhs)))

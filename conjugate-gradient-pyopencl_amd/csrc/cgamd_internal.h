@@ -293,6 +293,11 @@ int spmm_rm_grid(int dtype, int nrhs, int n, int max_quad, bool dot);
 int launch_spmm_rm(int dtype, int n, long long nnz, const void *vals, const int *ptr, const int *cols, const void *x, void *y,
                    int nrhs, void *partials, int max_quad, int *pace, hipStream_t st);
 constexpr int kSpmmPaceInts = 2 * 8 * 256 / 4;
+// what launch_spmm_rm will launch for this problem, from the functions it launches through: out = real columns, values per lane (NH),
+// K-steps per quad and round (TQ), strips, work-groups, XCDs whose sweep paces itself (have_pace: the caller passes progress words)
+int spmm_rm_plan(int dtype, int nrhs, int n, int max_quad, bool dot, bool have_pace, int out[6], int *lead);
+// the streaming form of rm_axpy_dot (mask 2) / rm_aypx_x (mask 1) on a block of `total` values
+bool rm_vec_nt(int mask, long long total, int dtype);
 // vector kernels with per-column scalars; partials[r * grid + wg]
 int rm_vec_grid(long long total_elems, int dtype);
 int launch_rm_dot(int dtype, int n, int nrhs, const void *a, const void *b, void *partials, int grid, hipStream_t st);

@@ -77,6 +77,10 @@ template <typename T> struct SpmmRmArgs {
     int lead;               // a wave gathers step g only when every wave of its XCD has finished g - lead steps
 };
 constexpr int kPaceWaves = 256;
+// the strips [first, second) XCD `xcd` sweeps, and whether a sweep of S strips by W waves paces itself once it has the progress bytes:
+// the kernel and the launch record (spmm_rm_plan) read both rules here
+__host__ __device__ inline int rm_xcd_strip(int xcd, int strips) { return (int)((long long)xcd * strips / 8); }
+__host__ __device__ inline bool rm_xcd_paces(int S, int W) { return W <= kPaceWaves && S >= W; }
 
 template <typename T, int NH, int TQ, int NQ, bool CPLX>
 struct RmGeom {
@@ -105,7 +109,7 @@ __global__ __launch_bounds__(256, (RmGeom<T, NH, TQ, NQ, CPLX>::WAVES)) void spm
 
     const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6), m = lane & 15, kq = lane >> 4;
     const int xcd = blockIdx.x & 7, W = ((int)gridDim.x >> 3) * 4, wl = ((int)blockIdx.x >> 3) * 4 + wave;
-    const int sb = (int)((long long)xcd * a.strips / 8), se = (int)((long long)(xcd + 1) * a.strips / 8);
+    const int sb = rm_xcd_strip(xcd, a.strips), se = rm_xcd_strip(xcd + 1, a.strips);
 
     // Paced sweep.  The strips are handed out statically (the fused d.q partial of a work-group must not depend on the schedule),
     // so nothing but the L2's patience keeps a fast wave from running steps ahead of a slow one, and an X row that three strips
@@ -121,7 +125,7 @@ __global__ __launch_bounds__(256, (RmGeom<T, NH, TQ, NQ, CPLX>::WAVES)) void spm
     constexpr int kPacePolls = 256;
     const int S = se - sb, MX = (S + W - 1) / W;
     unsigned char *const pw = a.pace ? reinterpret_cast<unsigned char *>(a.pace) + kPaceWaves * xcd : nullptr;     // one BYTE per wave (mod 256)
-    bool paced = pw != nullptr && W <= kPaceWaves && S >= W;
+    bool paced = pw != nullptr && rm_xcd_paces(S, W);
     const int base = pw && wl < kPaceWaves ? __builtin_amdgcn_readfirstlane((int)pw[wl]) : 0;
     const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(pw, 0, pw ? kPaceWaves : 0, 0x00020000);
     int stepno = 0;                                         // step of s_cur
@@ -591,19 +595,33 @@ int spmm_rm_grid(int dtype, int nrhs, int n, int max_quad, bool dot) {
 #undef CG_GRID
 }
 
+// everything of a launch that does not depend on the caller's arrays: the launcher and the launch record read it here
+struct RmSweep { int tq, strips, nwg, lead, ynt; bool pace; };
+template <typename T, int NH, bool CPLX> static RmSweep rm_sweep(int n, int max_quad, bool dot, bool have_pace) {
+    RmSweep w;
+    const RmInstance inst = rm_instance<T, NH, CPLX>(max_quad, dot);
+    w.tq = inst.tq;
+    w.strips = (n + inst.rows - 1) / inst.rows;
+    w.nwg = rm_grid_for(n, inst.rows, inst.per_cu);
+    w.lead = tune().spmm_lead > 0 ? tune().spmm_lead : 3;
+    w.pace = !(tune().spmm_lead < 0 || !have_pace);
+    w.ynt = tune().spmm_ynt >= 0 ? tune().spmm_ynt : 2;      // Y stores write-through (sc1): the lines do not displace X in L2
+    return w;
+}
+
 template <typename T, int NH, bool CPLX>
 static int spmm_rm_launch(int n, long long nnz, const void *vals, const int *ptr, const int *cols, const void *x, void *y,
                           void *partials, int max_quad, int *pace, hipStream_t st) {
     SpmmRmArgs<T> a;
+    const RmSweep inst = rm_sweep<T, NH, CPLX>(n, max_quad, partials != nullptr, pace != nullptr);
     a.n = n; a.nnz = nnz;
-    a.lead = tune().spmm_lead > 0 ? tune().spmm_lead : 3;
-    a.pace = (tune().spmm_lead < 0 || !pace) ? nullptr : pace + (partials ? 0 : 8 * kPaceWaves / 4);
-    a.ynt = tune().spmm_ynt >= 0 ? tune().spmm_ynt : 2;      // Y stores write-through (sc1): the lines do not displace X in L2
+    a.lead = inst.lead;
+    a.pace = !inst.pace ? nullptr : pace + (partials ? 0 : 8 * kPaceWaves / 4);
+    a.ynt = inst.ynt;
     a.vals = static_cast<const T *>(vals); a.ptr = ptr; a.cols = cols;
     a.x = static_cast<const T *>(x); a.y = static_cast<T *>(y); a.partials = static_cast<double *>(partials);
-    const RmInstance inst = rm_instance<T, NH, CPLX>(max_quad, partials != nullptr);
-    a.strips = (n + inst.rows - 1) / inst.rows;
-    a.nwg = rm_grid_for(n, inst.rows, inst.per_cu);
+    a.strips = inst.strips;
+    a.nwg = inst.nwg;
     const dim3 g(a.nwg), b(256);
 #define CG_SPMM(TQ, NQ)                                                                                       \
     do {                                                                                                       \
@@ -624,6 +642,26 @@ int launch_spmm_rm(int dtype, int n, long long nnz, const void *vals, const int 
 #define CG_RM(T, NH, C) return spmm_rm_launch<T, NH, C>(n, nnz, vals, ptr, cols, x, y, partials, max_quad, pace, st)
     CG_RM_TYPES(dtype, rc, CG_RM);
 #undef CG_RM
+}
+
+// the record of a launch (cgamd_solver_rowmajor_plan): out[0..5] = real columns, values per lane (NH), K-steps per quad and round (TQ),
+// strips, work-groups, XCDs whose sweep paces itself; *lead = the lead of a paced sweep
+int spmm_rm_plan(int dtype, int nrhs, int n, int max_quad, bool dot, bool have_pace, int out[6], int *lead) {
+    const int rc = rm_real_columns(dtype, nrhs);
+    if (!rc) return fail(CGAMD_ERR_INVALID, "rowmajor_plan: this type and width have no row-major loop");
+#define CG_PLAN(T, NH, C)                                                                                 \
+    do {                                                                                                  \
+        const RmSweep w = rm_sweep<T, NH, C>(n, max_quad, dot, have_pace);                                \
+        int paced = 0;                                                                                    \
+        for (int xcd = 0; xcd < 8; ++xcd)                                                                 \
+            paced += w.pace && rm_xcd_paces(rm_xcd_strip(xcd + 1, w.strips) - rm_xcd_strip(xcd, w.strips), (w.nwg >> 3) * 4); \
+        const int f[6] = {rc, NH, w.tq, w.strips, w.nwg, paced};                                          \
+        for (int i = 0; i < 6; ++i) out[i] = f[i];                                                        \
+        *lead = w.lead;                                                                                   \
+        return CGAMD_OK;                                                                                  \
+    } while (0)
+    CG_RM_TYPES(dtype, rc, CG_PLAN);
+#undef CG_PLAN
 }
 
 // grid of the row-major vector kernels: ~4 packs per thread.  NOT capped at the resident 2048 work-groups like the
@@ -664,9 +702,13 @@ int launch_rm_dot(int dtype, int n, int nrhs, const void *a, const void *b, void
     if (!rm_vec_ok(dtype, nrhs, {a, b})) return fail(CGAMD_ERR_INVALID, "rm_dot: unsupported width or misaligned vectors");
     CG_RM_DISPATCH(dtype, rm_dot_impl, (long long)n * nrhs, nrhs, a, b, partials, grid, st);
 }
+// streaming hints once the block is far beyond the 256 MB Infinity Cache (as the single-vector kernels do: Tuning::vec_nt); mask 2: the
+// q loads of rm_axpy_dot, mask 1: x of rm_aypx_x
+bool rm_vec_nt(int mask, long long total, int dtype) {
+    return tune().vec_nt >= 0 ? (tune().vec_nt & mask) != 0 : (size_t)total * dtype_size(dtype) > ((size_t)96 << 20);
+}
 template <typename T> static int rm_axpy_dot_impl(long long total, int R, const void *q, void *r, const void *alpha, void *partials, int grid, hipStream_t st) {
-    // streaming hints once the block is far beyond the 256 MB Infinity Cache (as the single-vector kernels do: Tuning::vec_nt)
-    const bool nt = tune().vec_nt >= 0 ? (tune().vec_nt & 2) != 0 : (size_t)total * sizeof(T) > ((size_t)96 << 20);
+    const bool nt = rm_vec_nt(2, total, VT<T>::dtype);
     if (nt) hipLaunchKernelGGL((rm_axpy_dot_kernel<T, kBlock, true>), dim3(grid), dim3(kBlock), 0, st, total, R, (const T *)q, (T *)r, (const T *)alpha,
                                (typename VT<T>::acc *)partials);
     else hipLaunchKernelGGL((rm_axpy_dot_kernel<T, kBlock, false>), dim3(grid), dim3(kBlock), 0, st, total, R, (const T *)q, (T *)r, (const T *)alpha,
@@ -678,7 +720,7 @@ int launch_rm_axpy_dot(int dtype, int n, int nrhs, const void *q, void *r, const
     CG_RM_DISPATCH(dtype, rm_axpy_dot_impl, (long long)n * nrhs, nrhs, q, r, alpha, partials, grid, st);
 }
 template <typename T> static int rm_aypx_x_impl(long long total, int R, const void *r, void *d, void *x, const void *alpha, const void *beta, int grid, hipStream_t st) {
-    const bool nt = tune().vec_nt >= 0 ? (tune().vec_nt & 1) != 0 : (size_t)total * sizeof(T) > ((size_t)96 << 20);
+    const bool nt = rm_vec_nt(1, total, VT<T>::dtype);
     if (nt) hipLaunchKernelGGL((rm_aypx_x_kernel<T, kBlock, true>), dim3(grid), dim3(kBlock), 0, st, total, R, (const T *)r, (T *)d, (T *)x, (const T *)alpha,
                                (const T *)beta);
     else hipLaunchKernelGGL((rm_aypx_x_kernel<T, kBlock, false>), dim3(grid), dim3(kBlock), 0, st, total, R, (const T *)r, (T *)d, (T *)x, (const T *)alpha,

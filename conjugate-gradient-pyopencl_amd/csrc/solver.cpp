@@ -1409,7 +1409,7 @@ int cgamd_last_spmv_form(int *out, int n_out) {
 
 int cgamd_solver_dot_partials(cgamd_solver *s, void *out_host, long long cap_values, int *per_rhs) {
     if (!s || !out_host || !per_rhs) return fail(CGAMD_ERR_INVALID, "dot_partials: null argument");
-    const int P = s->plan.n_partials;
+    const int P = s->rm ? s->rm_nwg : s->plan.n_partials;      // a row-major handle: one partial per work-group of the SpMM sweep
     *per_rhs = P;
     if (cap_values < (long long)P * s->nrhs) return fail(CGAMD_ERR_INVALID, "dot_partials: output holds fewer than nRHS * partials values");
     CG_HIP(hipSetDevice(s->ctx->device));
@@ -1421,9 +1421,11 @@ int cgamd_solver_dot_partials(cgamd_solver *s, void *out_host, long long cap_val
 // ---- test-facing record of the vector and scalar steps (tests/test_gpu_cg_steps.py) ------------------------------------------------
 // Neither entry launches a kernel or changes the handle.  Both refuse a handle whose stream is being captured: a copy or a
 // synchronisation there would end the capture with an error.
-// Row-major and tridiagonal handles launch their vector and scalar steps with grids of their own (rm_nwg / rm_vgrid, tri.grid) and keep
-// their partials elsewhere (tri_part): neither entry describes them, both refuse them
-static int step_launched_rhs_major(cgamd_solver *s, const char *who) {
+// Row-major and tridiagonal handles launch their vector and scalar steps with grids of their own (rm_nwg / rm_vgrid, tri.grid); the
+// tridiagonal ones keep their partials elsewhere (tri_part).  step_plan describes neither and refuses both; step_state serves a handle
+// that is row-major now (rm_ok: the state of a handle that will be row-major after its next set_rhs is nobody's) and refuses the rest
+static int step_launched_rhs_major(cgamd_solver *s, const char *who, bool serve_rm = false) {
+    if (serve_rm && s->rm) return CGAMD_OK;
     if (s->rm || (s->rm_ok && !precond_set(s)) || tri_on(s) || s->pre.mg)
         return fail(CGAMD_ERR_INVALID, std::string(who) + ": not recorded for row-major and tridiagonal handles");
     if (s->herm) return fail(CGAMD_ERR_INVALID, std::string(who) + ": not recorded for CGAMD_HERMITIAN handles (steps of their own, hermitian.hip)");
@@ -1462,17 +1464,18 @@ int cgamd_solver_step_plan(cgamd_solver *s, int *out, int n_out) {
 int cgamd_solver_step_state(cgamd_solver *s, int which, void *out_host, long long cap_values, long long *count) {
     if (!s || !out_host || !count) return fail(CGAMD_ERR_INVALID, "step_state: null argument");
     if (int rc = step_not_capturing(s, "step_state")) return rc;
-    if (int rc = step_launched_rhs_major(s, "step_state")) return rc;
+    if (int rc = step_launched_rhs_major(s, "step_state", true)) return rc;
     const void *src = nullptr;
     size_t each = dtype_size(s->dtype);
     long long values = s->nrhs;
+    const int vgrid = s->rm ? s->rm_vgrid : s->vgrid;      // the grid of the rm_* vector launches; they form no r.z partials, no rho
     switch (which) {
-    case 0: src = s->part_rr; each = acc_size(s->dtype); values = (long long)s->vgrid * s->nrhs; break;
-    case 1: src = s->part_rz; each = acc_size(s->dtype); values = (long long)s->vgrid * s->nrhs; break;
+    case 0: src = s->part_rr; each = acc_size(s->dtype); values = (long long)vgrid * s->nrhs; break;
+    case 1: src = s->rm ? nullptr : s->part_rz; each = acc_size(s->dtype); values = (long long)vgrid * s->nrhs; break;
     case 2: src = s->sc.alpha; break;
     case 3: src = s->sc.beta; break;
     case 4: src = s->sc.delta; break;
-    case 5: src = s->pre.rho2; values = 2LL * s->nrhs; break;
+    case 5: src = s->rm ? nullptr : s->pre.rho2; values = 2LL * s->nrhs; break;
     case 6: src = s->sc.iter; each = sizeof(int); values = 1; break;
     default: return fail(CGAMD_ERR_INVALID, "step_state: which is 0 .. 6");
     }
@@ -1483,6 +1486,26 @@ int cgamd_solver_step_state(cgamd_solver *s, int which, void *out_host, long lon
     CG_HIP(hipMemcpyAsync(out_host, src, each * (size_t)values, hipMemcpyDeviceToHost, s->ctx->stream));
     CG_HIP(hipStreamSynchronize(s->ctx->stream));
     return CGAMD_OK;
+}
+
+// What enqueue_iteration / set_rhs_impl pass to the launchers of rowmajor.hip NOW (include/cgamd.h), through the functions they launch
+// through: spmm_rm_plan is rm_instance + rm_grid_for as launch_spmm_rm calls them (fused: with s->part_dq; unfused: set_rhs and
+// cgamd_solver_spmm_rowmajor), rm_vec_nt the rule of rm_axpy_dot_impl / rm_aypx_x_impl; s->rm_vgrid, sc.kdq / sc.krr are the fields
+constexpr int kRowmajorPlanFields = 17;
+int cgamd_solver_rowmajor_plan(cgamd_solver *s, int *out, int n_out) {
+    if (!s || !out || n_out < 1) return -fail(CGAMD_ERR_INVALID, "rowmajor_plan: null or empty output");
+    TuneScope ts(&s->tune);
+    if (int rc = step_not_capturing(s, "rowmajor_plan")) return -rc;
+    if (!s->rm) return -fail(CGAMD_ERR_INVALID, "rowmajor_plan: the handle does not keep its right-hand sides row-major now (cgamd_solver_layout)");
+    int fu[6], un[6], lead = 0;
+    if (int rc = spmm_rm_plan(s->dtype, s->nrhs, s->n, s->plan.max_quad, true, s->rm_pace != nullptr, fu, &lead)) return -rc;
+    if (int rc = spmm_rm_plan(s->dtype, s->nrhs, s->n, s->plan.max_quad, false, s->rm_pace != nullptr, un, &lead)) return -rc;
+    const long long total = (long long)s->n * s->nrhs;
+    const int f[kRowmajorPlanFields] = {s->n, fu[0], fu[1], fu[2], un[2], fu[3], fu[4], un[4], s->rm_vgrid, rm_vec_nt(2, total, s->dtype) ? 1 : 0,
+                                        rm_vec_nt(1, total, s->dtype) ? 1 : 0, s->sc.kdq, s->sc.krr, fu[5], un[5], lead, s->rm_nwg};
+    const int k = n_out < kRowmajorPlanFields ? n_out : kRowmajorPlanFields;
+    for (int i = 0; i < k; ++i) out[i] = f[i];
+    return k;
 }
 
 // alpha and beta of a CGAMD_HERMITIAN handle (step_state describes the other loops' steps and refuses these handles)

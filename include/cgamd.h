@@ -603,7 +603,10 @@ int cgamd_last_spmv_form(int *out, int n_out);
 int cgamd_solver_dot_partials(cgamd_solver *s, void *out_host, long long cap_values, int *per_rhs);
 /* Development entries of the same standing (tests of the vector and scalar steps of an iteration; not part of the interface).  Neither
  * launches a kernel or changes the handle; both return CGAMD_ERR_INVALID while the handle's stream is being captured, and for handles
- * that keep their block row-major or run the tridiagonal preconditioner (their steps launch with grids of their own, not recorded).
+ * that run the tridiagonal preconditioner (their steps launch with grids of their own, not recorded).  A handle that keeps its block
+ * row-major is refused by cgamd_solver_step_plan (cgamd_solver_rowmajor_plan describes its launches) and served by
+ * cgamd_solver_step_state once cgamd_solver_layout() is 1: the r.r partials are [nRHS][rowmajor plan 8], there are no r.z partials and
+ * no rho buffer (which 1 and 5: CGAMD_ERR_INVALID); cgamd_solver_dot_partials reports [nRHS][rowmajor plan 6] for it.
  * cgamd_solver_step_plan: what the vector and scalar launches of this handle use NOW, read from the fields the launch sites read.
  * Writes min(n_out, 11) ints and returns that count (negative: error): [0] working size n (rows including appended ones), [1] leading
  * dimension of the handle's vectors, [2] r.r / r.z partials per right-hand side (grid.x of the vector launches), [3] d.q partials per
@@ -619,6 +622,16 @@ int cgamd_solver_dot_partials(cgamd_solver *s, void *out_host, long long cap_val
  * (CGAMD_ERR_INVALID then). */
 int cgamd_solver_step_plan(cgamd_solver *s, int *out, int n_out);
 int cgamd_solver_step_state(cgamd_solver *s, int which, void *out_host, long long cap_values, long long *count);
+/* Of the same standing: what the launches of the row-major loop use NOW (cgamd_solver_layout() == 1; any other handle:
+ * CGAMD_ERR_INVALID), read from the functions and fields the launch sites read.  Writes min(n_out, 17) ints and returns that count
+ * (negative: error): [0] working size n, [1] real columns of the block (complex64: 2 nRHS), [2] values a lane loads per non-zero (NH),
+ * [3] / [4] K-steps per quad and round (TQ: 5 or 8) of the SpMM instance with / without the fused d.q, [5] strips of 16 rows,
+ * [6] / [7] work-groups of the SpMM launch with / without the fused d.q ([6] = d.q partials per right-hand side as the kernel lays them
+ * out), [8] grid of the rm_dot / rm_axpy_dot / rm_aypx_x launches (r.r partials per right-hand side), [9] / [10] rm_axpy_dot / rm_aypx_x
+ * launch their streaming (NT) form, [11] / [12] order of the sums over the d.q / r.r partials as in step_plan [4] / [5], [13] / [14] XCDs
+ * (of 8) whose sweep paces itself in the launch with / without the fused d.q (0: unpaced), [15] steps a paced wave may lead by,
+ * [16] d.q partials per right-hand side the alpha launch sums (the handle's field; equals [6]). */
+int cgamd_solver_rowmajor_plan(cgamd_solver *s, int *out, int n_out);
 /* Of the same standing: the form the SpMV of this handle's launched loop WILL take -- the launcher's own decision, asked without a
  * launch -- in the layout of cgamd_last_spmv_form.  fused: with the d.q partials (what every loop but CGAMD_UNFUSED launches) or
  * without.  Writes min(n_form, 10) ints to `form` and returns that count (negative: error).  inputs (may be NULL): min(n_inputs, 62)

@@ -24,7 +24,7 @@ The two-launch loop is restated too (cg_step_ref.Steps._two_launch: beta and d =
 
 NOT covered here: the tridiagonal ZV form (its
 partials come from the sweep kernels of precond.hip); the GUARD instantiations (tied to the unguarded bits by test_gpu_until.py); the
-row-major rm_* kernels; the resident and distributed loops (tied to the launched loops form against form by their own modules)."""
+row-major rm_* kernels (test_gpu_rowmajor_steps.py restates them); the resident and distributed loops (tied to the launched loops form against form by their own modules)."""
 import ctypes
 import time
 
