@@ -184,6 +184,9 @@ def load():
         "cgamd_block_gram": (ci, [vp, ci, ci, ll, ci, vp, vp, vp]),
         "cgamd_block_update_xw": (ci, [vp, ci, ci, ll, ci, vp, vp, vp, vp, vp, vp, vp]),
         "cgamd_block_update_qp": (ci, [vp, ci, ci, ll, ci, vp, vp, vp, vp, ci]),
+        "cgamd_solver_set_block_pcg": (ci, [vp, ci]),
+        "cgamd_block_gram_weighted": (ci, [vp, ci, ci, ll, ci, vp, vp, vp]),
+        "cgamd_block_update_qp_z": (ci, [vp, ci, ci, ll, ci, vp, vp, vp, vp, vp, vp, ci]),
         "cgamd_gen_laplace3d": (ci, [vp, ci, ci, ci, ci, ll, ll, vp, vp, vp, ctypes.POINTER(ll)]),
         "cgamd_gen_poisson2d": (ci, [vp, ci, ci, vp, vp, vp, ctypes.POINTER(ll)]),
         "cgamd_gen_helm_fe_var": (ci, [vp, ci, ci, ctypes.c_double, vp, ctypes.c_double, ci, ci, vp, vp, vp, ctypes.POINTER(ll)]),

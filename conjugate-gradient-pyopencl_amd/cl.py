@@ -510,16 +510,18 @@ class Solver:
 
     def block_status(self):
         """{"on", "status" (0 running or stopped, 1 G failed, 2 W^T W failed, 3 NaN), "iteration" (of that event), "s",
-        "min_pivot_ratio"} (cgamd_solver_block_status; waits for the handle's stream)"""
+        "min_pivot_ratio", "preconditioned"} (cgamd_solver_block_status; waits for the handle's stream).  With set_block_pcg on,
+        "preconditioned" is True and status 2 means W^T Z failed"""
         info = (ctypes.c_int * 4)()
         ratio = ctypes.c_double(0.0)
         check(self._lib.cgamd_solver_block_status(self.handle, info, ctypes.byref(ratio)))
-        return {"on": bool(info[0]), "status": int(info[1]), "iteration": int(info[2]), "s": int(info[3]), "min_pivot_ratio": float(ratio.value)}
+        return {"on": bool(info[0]), "status": int(info[1]), "iteration": int(info[2]), "s": int(info[3]), "min_pivot_ratio": float(ratio.value),
+                "preconditioned": info[0] == 2}
 
     def block_state(self, which):
         """development entry (cgamd_solver_block_state): one s x s matrix in float64 -- "xi", "G", "alpha", "tau", "C" (W^T W as summed),
-        "tau_inv" (tau^-1) or "M" (alpha xi)"""
-        idx = {"xi": 0, "G": 1, "alpha": 2, "tau": 3, "C": 4, "tau_inv": 5, "M": 6}[which]
+        "tau_inv" (tau^-1), "M" (alpha xi) or, with set_block_pcg on, "CZ" (W^T Z as summed)"""
+        idx = {"xi": 0, "G": 1, "alpha": 2, "tau": 3, "C": 4, "tau_inv": 5, "M": 6, "CZ": 7}[which]
         out = np.empty((self.n_rhs, self.n_rhs), dtype=np.float64)
         check(self._lib.cgamd_solver_block_state(self.handle, idx, ptr(out)))
         return out
@@ -552,6 +554,57 @@ class Solver:
             x = self.x()
         finally:
             self.set_block(True)
+        return x, info
+
+    # ---- preconditioned block CG (include/cgamd.h "Preconditioned block CG"): the shared Krylov space with the M in force inside
+    def set_block_pcg(self, on=True):
+        """From the next set_rhs on the handle runs block CG on its n_rhs right-hand sides WITH the preconditioner in force inside the
+        recurrence (cgamd_solver_set_block_pcg): install M first (set_preconditioner), then turn this on; while it is on M cannot
+        be replaced or removed.  Real types, 2 ... 16 right-hand sides, no shifts; set_block and set_block_pcg exclude each other.
+        on=False returns the handle to the bits of the scalar PCG handle it was."""
+        if on:
+            self._block_check()
+        check(self._lib.cgamd_solver_set_block_pcg(self.handle, 1 if on else 0))
+
+    def solve_block_pcg(self, b, M, x0=None, tol=1e-6, maxit=1000, check_every=8):
+        """A X = B by preconditioned block CG to |r_j| <= tol |b_j| for every column (tol: a scalar or n_rhs values).  M as in
+        set_preconditioner / pcg; None keeps the M already in force, and raises ValueError when there is none.  All columns stop in the
+        first iteration in which each satisfies its own tolerance.  Where the block breaks down -- dependent right-hand sides, or an M
+        that is not positive definite on the block -- the block is turned off and the solve finishes column by column on the same
+        handle with the scalar PCG loop (solve_until's) from the X reached, M still in force, each column's tolerance relative to the
+        ORIGINAL |b_j|.  Returns (x, info) like solve_block: info["path"] is "block" or "block+columns".  The mode and M stay on."""
+        self._block_check()
+        if int(maxit) < 0 or int(check_every) < 0:
+            raise ValueError("maxit and check_every must not be negative")
+        b, tol_abs = self._block_tolerances(b, tol)
+        if M is not None:
+            was_on = self.block_status()["preconditioned"]
+            self.set_block_pcg(False)       # (M is part of the block's state: it is replaced with the mode off)
+            try:
+                self.set_preconditioner(M)
+            except Exception:               # an M that is refused: the mode comes back over the M that is still in force
+                if was_on and self._lib.cgamd_solver_preconditioner_source(self.handle) != 0:
+                    self.set_block_pcg(True)
+                raise
+        elif self._lib.cgamd_solver_preconditioner_source(self.handle) == 0:
+            raise ValueError("solve_block_pcg: M is None and no preconditioner is in force")
+        self.set_block_pcg(True)
+        self.set_rhs(b, x0)
+        its = self.iterate_until(tol_abs, maxit, check_every)
+        st = self.block_status()
+        info = {"path": "block", "block_iterations": int(its[0]), "column_iterations": None, "status": st["status"],
+                "breakdown_iteration": st["iteration"], "min_pivot_ratio": st["min_pivot_ratio"]}
+        if st["status"] == 0:
+            return self.x(), info
+        x = self.x()
+        self.set_block_pcg(False)
+        try:
+            self.set_rhs(b, x)
+            info["column_iterations"] = self.iterate_until(tol_abs, max(int(maxit) - int(its[0]), 0), check_every)
+            info["path"] = "block+columns"
+            x = self.x()
+        finally:
+            self.set_block_pcg(True)
         return x, info
 
     # ---- solution projection (include/cgamd.h "Solution projection"): start each solve from the span of the earlier ones

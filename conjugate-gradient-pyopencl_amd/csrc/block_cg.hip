@@ -16,6 +16,7 @@
 // FREEZE: a breakdown (a pivot v of either Cholesky with not v > s eps max_j C_jj, or NaN) and the stop of iterate_until set
 // rec.frozen.  It is written by the small steps only (one work-group) and is the exit of every launch BEHIND the one that wrote it;
 // no launch reads a word that one of its own work-groups writes.
+#include "block_device.h"
 #include "cgamd_internal.h"
 #include "device_types.h"
 #include "launch_util.h"
@@ -27,38 +28,8 @@
 namespace cgamd {
 
 constexpr int kGramGridMax = 512;       // one work-group per CU holds the accumulators; two passes over the chip at the most
-constexpr int kBlockLd = kBlockMax + 1; // row pitch of the small matrices in LDS
 
 int block_gram_grid(long long n) { return (int)std::max(1LL, std::min((n + kBlock - 1) / kBlock, (long long)kGramGridMax)); }
-
-// The factors in LDS are the same for every row, and the compiler would lift all 2 s^2 of them out of the row loop into registers
-// (s = 16 in double: 1024 of them, spilled to scratch).  A compiler-level memory barrier at the head of the loop body keeps them
-// where they are: broadcast reads of LDS, row after row.  No instruction is emitted
-CG_DEV void lds_stays() { asm volatile("" ::: "memory"); }
-
-// the block_sum<256> of NP values per thread: the wave trees, then thread p adds entry p's four wave sums in order.  sm: NP x 4
-template <int NP> CG_DEV void gram_store(const double (&acc)[NP], double *sm, double *__restrict__ part) {
-    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        const double v = wave_sum(acc[p]);
-        if (lane == 0) sm[p * 4 + w] = v;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < NP) {
-        double v = sm[threadIdx.x * 4];
-        for (int i = 1; i < kBlock / kWave; ++i) v = v + sm[threadIdx.x * 4 + i];
-        part[(long long)threadIdx.x * gridDim.x + blockIdx.x] = v;
-    }
-}
-template <typename T, int S> CG_DEV void gram_add(const T (&a)[S], const T (&b)[S], double (&acc)[S * (S + 1) / 2]) {
-#pragma unroll
-    for (int j = 0; j < S; ++j) {
-        const double bj = (double)b[j];
-#pragma unroll
-        for (int i = 0; i <= j; ++i) acc[j * (j + 1) / 2 + i] = acc[j * (j + 1) / 2 + i] + (double)a[i] * bj;
-    }
-}
 
 // a, b: [S][ld]; part: [S (S + 1) / 2][grid], entry j (j + 1) / 2 + i = a_i . b_j (i <= j)
 template <typename T, int S>
@@ -172,18 +143,7 @@ __global__ __launch_bounds__(kScalarBlock) void block_small_kernel(int mode, int
     }
     // the entries, each by one wave: lane-strided over the partials, then the wave tree
     const int NP = S * (S + 1) / 2;
-    for (int p = wv; p < NP; p += kScalarBlock / kWave) {
-        double acc = 0.;
-        for (int k = lane; k < grid; k += kWave) acc = acc + part[(long long)p * grid + k];
-        acc = wave_sum(acc);
-        if (lane == 0) {
-            int j = 0;
-            while ((j + 1) * (j + 2) / 2 <= p) ++j;
-            const int i = p - j * (j + 1) / 2;
-            C[i * kBlockLd + j] = acc;
-            C[j * kBlockLd + i] = acc;
-        }
-    }
+    for (int p = wv; p < NP; p += kScalarBlock / kWave) small_sum_entry(part, grid, p, lane, C);
     if (tid < S * S) {
         const int i = tid / S, j = tid - i * S;
         XI[i * kBlockLd + j] = mode == 0 ? (i == j ? 1. : 0.) : bd.xi[tid];
@@ -191,28 +151,8 @@ __global__ __launch_bounds__(kScalarBlock) void block_small_kernel(int mode, int
     __syncthreads();
     if (tid < S * S) (mode == 1 ? bd.G : bd.C)[tid] = C[(tid / S) * kBlockLd + tid % S];
     if (tid == 0) {         // Cholesky, left-looking by columns, with the pivot rule
-        int status = 0;
         double ratio = mode == 0 ? (double)INFINITY : *bd.min_ratio;
-        double maxd = C[0];
-        for (int k = 1; k < S; ++k) maxd = C[k * kBlockLd + k] > maxd ? C[k * kBlockLd + k] : maxd;
-        for (int k = 0; k < S; ++k)
-            if (C[k * kBlockLd + k] != C[k * kBlockLd + k]) status = 3;
-        const double thr = (double)S * eps * maxd;
-        for (int k = 0; k < S && !status; ++k) {
-            double v = C[k * kBlockLd + k];
-            for (int m = 0; m < k; ++m) v = v - L[k * kBlockLd + m] * L[k * kBlockLd + m];
-            if (v != v) { status = 3; break; }
-            const double rk = v / maxd;
-            if (rk < ratio) ratio = rk;
-            if (!(v > thr)) { status = mode == 1 ? 1 : 2; break; }
-            const double d = sqrt(v);
-            L[k * kBlockLd + k] = d;
-            for (int i = k + 1; i < S; ++i) {
-                double w = C[i * kBlockLd + k];
-                for (int m = 0; m < k; ++m) w = w - L[i * kBlockLd + m] * L[k * kBlockLd + m];
-                L[i * kBlockLd + k] = w / d;
-            }
-        }
+        const int status = small_cholesky(C, L, S, eps, mode == 1 ? 1 : 2, ratio);
         sh_status = status;
         sh_ratio = ratio;
     }
@@ -232,16 +172,7 @@ __global__ __launch_bounds__(kScalarBlock) void block_small_kernel(int mode, int
             history[(long long)it * S + tid] = mode == 0 ? (T)C[tid * kBlockLd + tid] : history[(long long)(it - 1) * S + tid];
         return;
     }
-    if (tid < S) {          // column tid of X = L^-1
-        const int j = tid;
-        X[j * kBlockLd + j] = 1. / L[j * kBlockLd + j];
-        for (int i = j + 1; i < S; ++i) {
-            double acc = L[i * kBlockLd + j] * X[j * kBlockLd + j];
-            for (int m = j + 1; m < i; ++m) acc = acc + L[i * kBlockLd + m] * X[m * kBlockLd + j];
-            X[i * kBlockLd + j] = -acc / L[i * kBlockLd + i];
-        }
-        for (int i = 0; i < j; ++i) X[i * kBlockLd + j] = 0.;
-    }
+    if (tid < S) small_linv_column(L, X, S, tid);
     __syncthreads();
     const int i = tid / S, j = tid - (tid / S) * S;
     if (mode == 1) {
@@ -302,15 +233,6 @@ __global__ __launch_bounds__(kScalarBlock) void block_small_kernel(int mode, int
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------------
-#define CG_BLOCK_S(S, CALL)                                                                             \
-    switch (S) {                                                                                        \
-    case 2: CALL(2); break; case 3: CALL(3); break; case 4: CALL(4); break; case 5: CALL(5); break;     \
-    case 6: CALL(6); break; case 7: CALL(7); break; case 8: CALL(8); break; case 9: CALL(9); break;     \
-    case 10: CALL(10); break; case 11: CALL(11); break; case 12: CALL(12); break; case 13: CALL(13); break; \
-    case 14: CALL(14); break; case 15: CALL(15); break; case 16: CALL(16); break;                       \
-    default: return fail(CGAMD_ERR_INVALID, "block CG: the block size runs 2 ... 16");                  \
-    }
-
 template <typename T>
 static int block_gram_impl(int n, long long ld, int S, const void *a, const void *b, double *part, int grid, const int *frozen, hipStream_t st) {
 #define CG_BG(N) hipLaunchKernelGGL((block_gram_kernel<T, N>), dim3(grid), dim3(kBlock), 0, st, n, ld, (const T *)a, (const T *)b, part, frozen)
@@ -342,12 +264,6 @@ static int block_small_impl(int mode, int S, int grid, const double *part, const
                        stop ? *stop : none, stop ? 1 : 0);
     return check_launch("block small step");
 }
-#define CG_BLOCK_REAL(dtype, FN, ...)                                                       \
-    switch (dtype) {                                                                        \
-    case CGAMD_F32: return FN<float>(__VA_ARGS__);                                          \
-    case CGAMD_F64: return FN<double>(__VA_ARGS__);                                         \
-    default: return fail(CGAMD_ERR_INVALID, "block CG serves the real value types");        \
-    }
 
 int launch_block_gram(int dtype, int n, long long ld, int S, const void *a, const void *b, double *part, int grid, const int *frozen, hipStream_t st) {
     CG_BLOCK_REAL(dtype, block_gram_impl, n, ld, S, a, b, part, grid, frozen, st);
@@ -387,6 +303,7 @@ int block_alloc(BlockState *b, int S, long long n) {
 }
 void block_free(BlockState *b) {
     if (b->mem) (void)hipFree(b->mem);
+    if (b->mem_pcg) (void)hipFree(b->mem_pcg);
     *b = BlockState();
 }
 

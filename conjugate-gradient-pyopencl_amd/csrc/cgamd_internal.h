@@ -759,11 +759,13 @@ struct BlockDev {
     double *xi = nullptr, *G = nullptr, *alpha = nullptr, *tau = nullptr, *C = nullptr, *tau_inv = nullptr, *M = nullptr;
     void *M_T = nullptr, *alpha_T = nullptr, *tinv_T = nullptr, *tau_T = nullptr;      // what the vector launches multiply by, in the value type
     double *partials = nullptr;     // [s (s + 1) / 2][grid]
+    // the preconditioned form (block_pcg.hip) alone: W^T Z as summed, and its partials beside those of W^T W
+    double *CZ = nullptr, *partials_z = nullptr;
 };
 struct BlockState {
     int S = 0;                      // 0: off
     int grid = 0;                   // work-groups of the two launches that leave Gram partials
-    void *mem = nullptr;
+    void *mem = nullptr, *mem_pcg = nullptr;
     BlockDev dev;
 };
 int block_gram_grid(long long n);
@@ -776,6 +778,17 @@ int launch_block_xw(int dtype, int n, long long ld, int S, const void *P, const 
 int launch_block_qp(int dtype, int n, long long ld, int S, void *Q, void *P, const void *TI, const void *TA, bool init, const int *frozen, hipStream_t st);
 // mode 0: set_rhs, 1: the G step, 2: the W step (stop: iterate_until's tolerances and words)
 int launch_block_small(int dtype, int mode, const BlockState &b, const CgScalars &sc, const CgStop *stop, hipStream_t st);
+// ---- block CG with a preconditioner inside the recurrence (block_pcg.hip): R = Q xi with Q^T M^-1 Q = I, Z = M^-1 W in q's storage
+// the second allocation of a handle in that mode: W^T Z and its partials (b: allocated by block_alloc)
+int block_pcg_alloc(BlockState *b);
+// the partials of w^T diag(m) w: entry j (j + 1) / 2 + i = w_i . (m w_j), m w_j rounded once in the value type; m: n values, shared
+int launch_block_gram_weighted(int dtype, int n, long long ld, int S, const void *w, const void *m, double *part, int grid, const int *frozen,
+                               hipStream_t st);
+// Q <- W tau^-1 ; P <- Z tau^-1 + P tau^T (init: P <- Z tau^-1).  Z: the block itself, or NULL and z_k = m w_k rounded once
+int launch_block_qp_z(int dtype, int n, long long ld, int S, void *Q, void *P, const void *Z, const void *m, const void *TI, const void *TA, bool init,
+                      const int *frozen, hipStream_t st);
+// mode 0: set_rhs (partials: R0^T R0, partials_z: R0^T Z0), 2: the W step (W^T W, W^T Z)
+int launch_block_pcg_small(int dtype, int mode, const BlockState &b, const CgScalars &sc, const CgStop *stop, hipStream_t st);
 
 }  // namespace cgamd
 

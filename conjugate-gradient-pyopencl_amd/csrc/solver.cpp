@@ -151,11 +151,13 @@ static int enqueue_lag_iteration(cgamd_solver *s, int k, int lag, int j, hipStre
 // block_cg.hip -- a linear chain.  Every launch behind a breakdown or the stop leaves on the record's frozen word, under
 // cgamd_solver_iterate as under cgamd_solver_iterate_until (g: the tolerances and the host's word); the SpMV is the unguarded one,
 // its q is read by nothing that writes then
+static int enqueue_block_pcg_iteration(cgamd_solver *s, int k, hipStream_t st, const CgStop *g);
 static int enqueue_block_iteration(cgamd_solver *s, int k, hipStream_t st, const CgStop *g) {
     const int dt = s->dtype, n = s->n, S = s->nrhs;
     const BlockState &b = s->blk;
     const int *frozen = b.dev.rec + 2;
     int rc;
+    if (s->blk_pcg) return enqueue_block_pcg_iteration(s, k, st, g);
     if (b.S != S || precond_set(s) || nshifts(s) || s->rm || s->herm || s->nsys || (s->flags & CGAMD_UNFUSED))
         return fail(CGAMD_ERR_STATE, "iterate: the handle is not in the state block CG was set up for");
     if (s->ev_pair) CG_HIP(hipEventRecord(s->ev_pair[0], st));
@@ -166,6 +168,50 @@ static int enqueue_block_iteration(cgamd_solver *s, int k, hipStream_t st, const
     if ((rc = launch_block_xw(dt, n, n, S, s->d, s->q, s->x, s->r, b.dev.M_T, b.dev.alpha_T, b.dev.partials, b.grid, frozen, st))) return rc;
     if ((rc = launch_block_small(dt, 2, b, s->sc, g, st))) return rc;
     return launch_block_qp(dt, n, n, S, s->r, s->d, b.dev.tinv_T, b.dev.tau_T, false, frozen, st);
+}
+
+// The M^-1 side of preconditioned block CG (include/cgamd.h "Preconditioned block CG"; block_pcg.hip), shared by set_rhs and the
+// iteration: Z = M^-1 W from r into q -- the V-cycle or the line sweeps, unguarded like the scalar multigrid loop's (what they write is
+// read by nothing that writes once the loop is frozen), and nothing at all for a diagonal M -- then the partials of W^T Z beside those
+// of W^T W: the Gram launch on (W, Z), or for a diagonal M the weighted one, which reads W and m and no Z
+static int enqueue_block_pcg_wz(cgamd_solver *s, const int *frozen, hipStream_t st) {
+    const int dt = s->dtype, n = s->n, S = s->nrhs;
+    const BlockState &b = s->blk;
+    int rc;
+    if (s->pre.mdiag) return launch_block_gram_weighted(dt, n, n, S, s->r, s->pre.mdiag, b.dev.partials_z, b.grid, frozen, st);
+    if (s->pre.mg) rc = mg_vcycle(s->pre.mg, s->r, s->q, st);
+    else rc = enqueue_tri_sweep(s, false, nullptr, s->q, st);
+    if (rc) return rc;
+    return launch_block_gram(dt, n, n, S, s->r, s->q, b.dev.partials_z, b.grid, frozen, st);
+}
+// Q <- W tau^-1 ; P <- Z tau^-1 + P tau^T with Z in q, or z = m w formed in the launch
+static int enqueue_block_pcg_qp(cgamd_solver *s, bool init, const int *frozen, hipStream_t st) {
+    const BlockState &b = s->blk;
+    return launch_block_qp_z(s->dtype, s->n, s->n, s->nrhs, s->r, s->d, s->pre.mdiag ? nullptr : s->q, s->pre.mdiag, b.dev.tinv_T, b.dev.tau_T, init,
+                             frozen, st);
+}
+static bool block_pcg_state_ok(const cgamd_solver *s) {
+    return s->blk.S == s->nrhs && s->blk.dev.CZ && precond_set(s) && (s->pre.mdiag || s->pre.mg || tri_on(s)) && !nshifts(s) && !s->rm && !s->herm &&
+           !s->nsys && !(s->flags & CGAMD_UNFUSED);
+}
+// One preconditioned block iteration: the SpMV, the Gram launch and the G step and the x / w update of block CG as they are, then
+// z = M^-1 w, the partials of W^T Z, the W step of block_pcg.hip and the q / p update with Z -- a linear chain, frozen like the
+// unpreconditioned one
+static int enqueue_block_pcg_iteration(cgamd_solver *s, int k, hipStream_t st, const CgStop *g) {
+    const int dt = s->dtype, n = s->n, S = s->nrhs;
+    const BlockState &b = s->blk;
+    const int *frozen = b.dev.rec + 2;
+    int rc;
+    if (!block_pcg_state_ok(s)) return fail(CGAMD_ERR_STATE, "iterate: the handle is not in the state preconditioned block CG was set up for");
+    if (s->ev_pair) CG_HIP(hipEventRecord(s->ev_pair[0], st));
+    if ((rc = handle_spmv(s, n, s->d, n, s->q, n, nullptr, nullptr, st))) return rc;
+    if (s->ev_pair) CG_HIP(hipEventRecord(s->ev_pair[1], st));
+    if ((rc = launch_block_gram(dt, n, n, S, s->d, s->q, b.dev.partials, b.grid, frozen, st))) return rc;
+    if ((rc = launch_block_small(dt, 1, b, s->sc, g, st))) return rc;
+    if ((rc = launch_block_xw(dt, n, n, S, s->d, s->q, s->x, s->r, b.dev.M_T, b.dev.alpha_T, b.dev.partials, b.grid, frozen, st))) return rc;
+    if ((rc = enqueue_block_pcg_wz(s, frozen, st))) return rc;
+    if ((rc = launch_block_pcg_small(dt, 2, b, s->sc, g, st))) return rc;
+    return enqueue_block_pcg_qp(s, false, frozen, st);
 }
 
 // lag >= 2 (capture of a U-iteration graph only): this is iteration k % lag of a group of the deferred x update
@@ -739,7 +785,17 @@ int cgamd::herm_refuses(const char *who, const char *why) {
 // operator is not a shift of anything.  Refused before anything on the handle changes
 int cgamd::block_refuses(const cgamd_solver *s, const char *who) {
     if (!s->blk_want) return CGAMD_OK;
+    if (s->blk_pcg)
+        return fail(CGAMD_ERR_STATE, std::string(who) + ": preconditioned block CG is on (cgamd_solver_set_block_pcg), which this entry does not serve -- M is part of its state; turn it off first");
     return fail(CGAMD_ERR_STATE, std::string(who) + ": block CG is on (cgamd_solver_set_block), which this entry does not serve; turn it off first");
+}
+// block CG goes, in either mode: the next set_rhs starts a handle that never had it.  The caller has waited for the stream
+void cgamd::block_drop(cgamd_solver *s) {
+    block_free(&s->blk);
+    destroy_graphs(s);
+    s->blk_want = s->blk_on = s->blk_pcg = false;
+    s->rhs_set = false;     // (r and d hold Q and P)
+    s->until_mode = s->until_stopped = false;
 }
 int cgamd::shifts_refuse(const cgamd_solver *s, const char *who, bool block_too) {
     if (!s->sh.view.S) return block_too ? block_refuses(s, who) : CGAMD_OK;
@@ -959,7 +1015,14 @@ static int set_rhs_impl(cgamd_solver *s, const void *b, const void *x0, int on_d
     // r = b - A x0 ; d = r ; delta0 = r.r   (clcg.c:255-292)
     if ((rc = handle_spmv(s, s->n, s->x, s->n, s->q, s->n, nullptr, nullptr, st))) return rc;
     if ((rc = launch_sub(s->dtype, s->n, s->b, s->q, s->r, s->n, s->nrhs, st))) return rc;
-    if (s->blk_on) {   // C = R0^T R0 = L L^T, xi = L^T, Q = R0 xi^-1 over r, P = Q, delta_0[j] = |xi e_j|^2; a dependent block freezes here
+    if (s->blk_on && s->blk_pcg) {     // Z0 = M^-1 R0 into q; C = R0^T Z0 = L L^T, xi = L^T, Q = R0 xi^-1 over r, P = Z0 xi^-1, delta_0[j] = (R0^T R0)_jj
+        const BlockState &bk = s->blk;
+        if (!block_pcg_state_ok(s)) return fail(CGAMD_ERR_STATE, "set_rhs: the handle is not in the state preconditioned block CG was set up for");
+        if ((rc = launch_block_gram(s->dtype, s->n, s->n, s->nrhs, s->r, s->r, bk.dev.partials, bk.grid, nullptr, st))) return rc;
+        if ((rc = enqueue_block_pcg_wz(s, nullptr, st))) return rc;
+        if ((rc = launch_block_pcg_small(s->dtype, 0, bk, s->sc, nullptr, st))) return rc;
+        if ((rc = enqueue_block_pcg_qp(s, true, bk.dev.rec + 2, st))) return rc;
+    } else if (s->blk_on) {   // C = R0^T R0 = L L^T, xi = L^T, Q = R0 xi^-1 over r, P = Q, delta_0[j] = |xi e_j|^2; a dependent block freezes here
         const BlockState &bk = s->blk;
         if ((rc = launch_block_gram(s->dtype, s->n, s->n, s->nrhs, s->r, s->r, bk.dev.partials, bk.grid, nullptr, st))) return rc;
         if ((rc = launch_block_small(s->dtype, 0, bk, s->sc, nullptr, st))) return rc;
@@ -1533,6 +1596,8 @@ int cgamd_solver_layout(cgamd_solver *s) { return s ? (s->rm ? 1 : 0) : -CGAMD_E
 int cgamd_solver_loop_launches(cgamd_solver *s) {
     if (!s) return -CGAMD_ERR_INVALID;
     TuneScope ts(&s->tune);
+    // preconditioned block CG: the six below, the partials of W^T Z, and what z = M^-1 w launches (a diagonal M: nothing)
+    if (s->blk_want && s->blk_pcg) return 7 + (s->pre.mg ? mg_cost(s->pre.mg).launches : tri_on(s) ? (s->pre.tri.longform ? 3 : 1) : 0);
     if (s->blk_want) return 6;                           // block CG: SpMV, Gram, the G step, x / w update, the W step, q / p update, whatever s
     if (s->herm) return 4;                               // SpMV, herm_alpha, herm_axpy_dot, herm_aypx_beta_x under every flag
     if (s->pre.mg) return 5 + mg_cost(s->pre.mg).launches;       // SpMV, cg_alpha, r update, the V-cycle's chain, r.z, update
@@ -1584,9 +1649,26 @@ static long long tri_passes(const cgamd_solver *s) {
     if (s->pre.tri.stride > 1) return 14LL * s->nrhs + 3 * f;
     return s->pre.tri.longform ? 13LL * s->nrhs + 6 * f : 11LL * s->nrhs + 3 * f;
 }
+// the preconditioned block loop, beside the matrix: the block loop's SpMV 2 + Gram 2 + x / w update 6, then
+//   a diagonal M    the weighted Gram (W) 1 + the q / p update (Q, P in and out; z formed in registers) 4 = 15 per right-hand side, and m
+//                   read by both launches
+//   a line M or a   Gram (W, Z) 2 + the q / p update (Q, Z, P in; Q, P out) 5 = 17 per right-hand side, and z = M^-1 w at the price the
+//   V-cycle         scalar loops' models give it: the V-cycle as mg_bytes counts it; the sweep without the r update (r in, z out: 2,
+//                   the long form reads r twice: 3, the strided form stores and reads back w y: 5) and the factors it reads
+static long long block_pcg_bytes(const cgamd_solver *s, long long spmv_bytes) {
+    const long long V = (long long)dtype_size(s->dtype), col = (long long)s->n_user * V;
+    if (s->pre.mdiag) return 15 * col * s->nrhs + 2 * col;
+    if (s->pre.mg) {
+        const MgCost c = mg_cost(s->pre.mg);
+        return 17 * col * s->nrhs + c.spmv0 * spmv_bytes + c.bytes;
+    }
+    const long long sweep = s->pre.tri.stride > 1 ? 5LL * s->nrhs + 3 : s->pre.tri.longform ? 3LL * s->nrhs + 6 : 2LL * s->nrhs + 3;
+    return (17LL * s->nrhs + sweep) * col;
+}
 long long cgamd_solver_iter_bytes(cgamd_solver *s, int fused) {
     if (!s) return 0;
     const long long V = (long long)dtype_size(s->dtype);
+    if (s->blk_want && s->blk_pcg) return s->nnz * (V + 4) + ((long long)s->n_user + 1) * 4 + block_pcg_bytes(s, cgamd_solver_spmv_bytes(s));
     if (s->blk_want) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + kBlockPasses * s->n_user * V * s->nrhs;
     if (s->pre.mg) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + mg_bytes(s, cgamd_solver_spmv_bytes(s));
     if (tri_on(s)) return s->nnz * (value_arrays(s) * V + 4) + ((long long)s->n_user + 1) * 4 + tri_passes(s) * s->n_user * V;
@@ -1676,6 +1758,7 @@ long long cgamd_solver_iter_moved_bytes(cgamd_solver *s) {
     const long long passes = s->herm ? (s->pre.mdiag ? 14 : 12) : (s->nsys && s->pre.mdiag) ? 12 : (s->flags & CGAMD_UNFUSED) ? 14 : s->pre.mdiag ? 12 : 10;
     const long long lag = x_lag_now(s);
     const long long matrix = matrix_moved_bytes(s, loop_form(s)) + long_rows_scratch_traffic(s);
+    if (s->blk_want && s->blk_pcg) return matrix + block_pcg_bytes(s, cgamd_solver_spmv_moved_bytes(s));
     if (s->blk_want) return matrix + kBlockPasses * s->n_user * V * s->nrhs;
     if (s->pre.mg) return matrix + mg_bytes(s, cgamd_solver_spmv_moved_bytes(s));
     if (tri_on(s)) return matrix + tri_passes(s) * s->n_user * V;
@@ -1988,14 +2071,11 @@ int cgamd_solver_set_block(cgamd_solver *s, int on) {
     const std::string who = "set_block";
     if (int rc = shift_entry(s, "set_block")) return rc;
     TuneScope ts(&s->tune);
+    if (s->blk_pcg) return fail(CGAMD_ERR_STATE, who + ": preconditioned block CG is on (cgamd_solver_set_block_pcg); the two modes exclude each other: turn it off there");
     if (!on) {          // the next set_rhs starts a handle that never had it
         if (!s->blk_want && !s->blk_on) return CGAMD_OK;
         CG_HIP(hipStreamSynchronize(s->ctx->stream));
-        block_free(&s->blk);
-        destroy_graphs(s);
-        s->blk_want = s->blk_on = false;
-        s->rhs_set = false;     // (r and d hold Q and P)
-        s->until_mode = s->until_stopped = false;
+        block_drop(s);
         return CGAMD_OK;
     }
     if (s->dtype != CGAMD_F32 && s->dtype != CGAMD_F64)
@@ -2012,10 +2092,39 @@ int cgamd_solver_set_block(cgamd_solver *s, int on) {
     return CGAMD_OK;
 }
 
+// Preconditioned block CG (include/cgamd.h "Preconditioned block CG"; block_pcg.hip): legal only WITH a preconditioner in force, which
+// becomes part of the block's state -- every set_preconditioner* entry refuses the handle while the mode is on
+int cgamd_solver_set_block_pcg(cgamd_solver *s, int on) {
+    const std::string who = "set_block_pcg";
+    if (int rc = shift_entry(s, "set_block_pcg")) return rc;
+    TuneScope ts(&s->tune);
+    if (s->blk_want && !s->blk_pcg) return fail(CGAMD_ERR_STATE, who + ": block CG is on (cgamd_solver_set_block); the two modes exclude each other: turn it off there");
+    if (!on) {          // the next set_rhs starts the scalar PCG handle it was
+        if (!s->blk_pcg) return CGAMD_OK;
+        CG_HIP(hipStreamSynchronize(s->ctx->stream));
+        block_drop(s);
+        return CGAMD_OK;
+    }
+    if (s->dtype != CGAMD_F32 && s->dtype != CGAMD_F64)
+        return fail(CGAMD_ERR_STATE, who + ": block CG serves the real value types");
+    if (s->nsys) return fail(CGAMD_ERR_STATE, who + ": the handle is batched (a matrix of its own per right-hand side: no common Krylov space)");
+    if (s->herm) return herm_refuses("set_block_pcg", "which the block recurrence does not serve");
+    if (s->flags & CGAMD_UNFUSED) return fail(CGAMD_ERR_STATE, who + ": CGAMD_UNFUSED replays the reference's kernel sequence");
+    if (s->rm_ok) return fail(CGAMD_ERR_STATE, who + ": the handle keeps its right-hand sides interleaved (row-major layout)");
+    if (s->nrhs < 2 || s->nrhs > kBlockMax) return fail(CGAMD_ERR_STATE, who + ": the block is the handle's nRHS right-hand sides, 2 ... 16 of them");
+    if (nshifts(s)) return fail(CGAMD_ERR_STATE, who + ": shifts are in force (cgamd_solver_set_shifts); remove them first");
+    if (!precond_set(s)) return fail(CGAMD_ERR_STATE, who + ": no preconditioner is in force; install one first (cgamd_solver_set_block runs the unpreconditioned block)");
+    if (s->blk_pcg) return CGAMD_OK;
+    if (int rc = block_alloc(&s->blk, s->nrhs, s->n)) return rc;
+    if (int rc = block_pcg_alloc(&s->blk)) { block_free(&s->blk); return rc; }
+    s->blk_want = s->blk_pcg = true;    // (blk_on, and with it the loop, changes at the next set_rhs)
+    return CGAMD_OK;
+}
+
 int cgamd_solver_block_status(cgamd_solver *s, int *info, double *min_pivot_ratio) {
     if (int rc = shift_entry(s, "block_status")) return rc;
     if (!info) return fail(CGAMD_ERR_INVALID, "block_status: info is NULL");
-    info[0] = s->blk_want ? 1 : 0; info[1] = 0; info[2] = 0; info[3] = s->nrhs;
+    info[0] = s->blk_want ? (s->blk_pcg ? 2 : 1) : 0; info[1] = 0; info[2] = 0; info[3] = s->nrhs;
     if (min_pivot_ratio) *min_pivot_ratio = INFINITY;
     if (!s->blk_on || !s->rhs_set) return CGAMD_OK;
     struct { int rec[4]; double ratio; } img;
@@ -2031,13 +2140,14 @@ int cgamd_solver_block_status(cgamd_solver *s, int *info, double *min_pivot_rati
 }
 
 // which: 0 xi, 1 G = P^T A P, 2 alpha = G^-1, 3 tau, 4 W^T W (R0^T R0 after set_rhs), 5 tau^-1, 6 M = alpha xi; s x s doubles, row-major
+// the preconditioned mode alone: 7 W^T Z (R0^T Z0 after set_rhs) as summed
 int cgamd_solver_block_state(cgamd_solver *s, int which, void *out_host) {
     if (int rc = shift_entry(s, "block_state")) return rc;
     if (!out_host) return fail(CGAMD_ERR_INVALID, "block_state: out_host is NULL");
     if (!s->blk_on || !s->rhs_set) return fail(CGAMD_ERR_STATE, "block_state: block CG is not running (cgamd_solver_set_block, then set_rhs)");
-    if (which < 0 || which > 6) return fail(CGAMD_ERR_INVALID, "block_state: which is 0 .. 6");
+    if (which < 0 || which > (s->blk_pcg ? 7 : 6)) return fail(CGAMD_ERR_INVALID, s->blk_pcg ? "block_state: which is 0 .. 7" : "block_state: which is 0 .. 6");
     const BlockDev &d = s->blk.dev;
-    const double *src[] = {d.xi, d.G, d.alpha, d.tau, d.C, d.tau_inv, d.M};
+    const double *src[] = {d.xi, d.G, d.alpha, d.tau, d.C, d.tau_inv, d.M, d.CZ};
     CG_HIP(hipMemcpyAsync(out_host, src[which], sizeof(double) * (size_t)s->nrhs * s->nrhs, hipMemcpyDeviceToHost, s->ctx->stream));
     CG_HIP(hipStreamSynchronize(s->ctx->stream));
     return CGAMD_OK;

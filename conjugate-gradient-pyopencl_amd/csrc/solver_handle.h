@@ -135,7 +135,9 @@ struct cgamd_solver {
     // q = A P, the SpMV and five launches per iteration, until_mode like every loop with d in one buffer.  blk: the small matrices,
     // the record and the Gram partials (allocated by set_block, no n-sized buffer)
     cgamd::BlockState blk;
-    bool blk_want = false, blk_on = false;
+    // blk_pcg (cgamd_solver_set_block_pcg; block_pcg.hip): the block loop is the preconditioned one -- the M in force sits inside the
+    // recurrence, q also holds Z = M^-1 W, and blk carries W^T Z and its partials; set and cleared with blk_want
+    bool blk_want = false, blk_on = false, blk_pcg = false;
 };
 
 namespace cgamd {
@@ -152,6 +154,8 @@ int herm_refuses(const char *who, const char *why);
 // block_too: the entry does not serve block CG either (cgamd_solver_set_block), which is every caller but set_rhs_projected
 int shifts_refuse(const cgamd_solver *s, const char *who, bool block_too = true);
 int block_refuses(const cgamd_solver *s, const char *who);
+// block CG off, plain or preconditioned (the stream is idle): state freed, graphs gone, set_rhs next
+void block_drop(cgamd_solver *s);
 // (solver_precond.cpp) the matrix behind a preconditioner built from it has changed: build it again -- or, where that fails, remove
 // it (the new values are in force, the old factors belong to the old ones) and fail with the build's status and text
 int rebuild_or_remove(cgamd_solver *s, const char *who);

@@ -84,6 +84,7 @@ int cgamd_solver_set_preconditioner(cgamd_solver *s, const void *m, int on_devic
     if (s->nsys && m) return batched_refuses("set_preconditioner");
     if (m)      // (removal stays served)
         if (int rc = shifts_refuse(s, "set_preconditioner")) return rc;
+    if (s->blk_pcg) return block_refuses(s, "set_preconditioner");       // (removal too: M is part of the preconditioned block's state)
     if (s->nsys && !precond_set(s)) return CGAMD_OK;      // there is none to remove
     TuneScope ts(&s->tune);       // (m == NULL also removes the per-system preconditioner of a batched handle)
     return diag_install(s, m, on_device, Precond::kCaller);
@@ -188,6 +189,10 @@ int cgamd_solver_set_preconditioner_amg(cgamd_solver *s, int passes, double stre
 int cgamd::remove_and_fail(cgamd_solver *s, int rc) {
     if (s->pre.built == Precond::kCaller) return rc;        // (one from the caller's arrays does not depend on the matrix: kept)
     const std::string why = cgamd_last_error();
+    if (s->blk_pcg) {       // preconditioned block CG goes with its M, whatever the wait returns: the mode never outlives M
+        (void)pre_begin(s);
+        block_drop(s);
+    }
     (void)diag_install(s, nullptr, 0, Precond::kCaller);
     return fail(rc, why);
 }

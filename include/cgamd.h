@@ -1217,6 +1217,55 @@ int cgamd_block_update_xw(cgamd_ctx *ctx, int dtype, int size, long long ld, int
 int cgamd_block_update_qp(cgamd_ctx *ctx, int dtype, int size, long long ld, int s, void *q, void *p, const void *tau_inv, const void *tau,
                           int init);
 
+/* ---- Preconditioned block CG: the shared Krylov space with an M in force (csrc/block_pcg.hip).  BCGrQ as above, carried in the M^-1
+ * inner product: R = Q xi with Q^T M^-1 Q = I.  The vectors carry the block as there -- x = X, r = Q, d = P, q = A P -- and q's storage
+ * also holds Z = M^-1 W, because A P is dead once W exists.  No n-sized buffer is added.  M is the preconditioner in force: diagonal,
+ * line or multigrid / AMG, whatever built it; "M^-1" below is what the scalar PCG loop applies between r and z.
+ *   At cgamd_solver_set_rhs: R0 = B - A X0 as ever; Z0 = M^-1 R0 into q; C = R0^T Z0 = L L^T; xi = L^T; Q = R0 xi^-1; P = Z0 xi^-1;
+ *   history row 0 is delta_0[j] = (R0^T R0)_jj: the history holds r.r, as on every preconditioned handle.  Iteration k, a linear chain:
+ *     1  A P                                  the handle's SpMV as it is
+ *     2  G = P^T (A P)                        the Gram launch of block CG
+ *     3  G = L L^T, alpha = G^-1, M = alpha xi        the G step of block CG
+ *     4  X += P M ; W = Q - (A P) alpha over Q        and the partials of W^T W: the launch of block CG, unchanged
+ *     5  Z = M^-1 W into q                    the V-cycle or the line sweeps; for a diagonal M NOTHING runs here
+ *     6  the partials of C = W^T Z            the Gram launch on (W, Z); for a diagonal M the weighted Gram: W read once, m once, entry
+ *                                             (i <= j) = w_i . (m w_j) with m w_j rounded once in the value type, no Z block written or read
+ *     7  the W step: both partial sets summed; delta_k[j] = (xi e_j)^T (W^T W) (xi e_j) with the OLD xi (R_k+1 = W xi_k) into the
+ *        history and through the stop test; C = L L^T, tau = L^T, tau^-1, xi <- tau xi; the breakdown record
+ *     8  Q <- W tau^-1 ; P <- Z tau^-1 + P tau^T      both in place; z_k read from Z, or m_i w_k rounded once (diagonal M)
+ *   SEVEN launches and those of step 5: cgamd_solver_loop_launches is 7 plus the launches of z = M^-1 w (0 for a diagonal M).
+ *   Orders: those of block CG (partials, their sums, the Cholesky, L^-1, alpha, M, tau xi); delta_k[j]: t_i = sum_m<=j (W^T W)_im xi_mj
+ *   for i <= j, then sum_i<=j xi_ij t_i, every sum from its first product on, ascending (at set_rhs the diagonal entry itself).  Small
+ *   matrices in double, each rounded once to the value type; vectors in the value type, one rounding per operation
+ *   (tests/block_pcg_ref.py restates every order).  Captured graphs and CGAMD_NO_GRAPH give the same bits; iterate(a); iterate(b)
+ *   gives the bits of iterate(a + b).
+ *   BREAKDOWN: the pivot rule of block CG, not v > s eps_value max_j C_jj, on G and on C = W^T Z (R0^T Z0 at set_rhs).  An M that is not
+ *   positive definite on the block therefore freezes the loop with status 2, as a dependent column does.  The history row of the
+ *   iteration is written before C is factored.  Under cgamd_solver_iterate_until the M^-1 launches run unguarded, as in the scalar
+ *   multigrid loop: what they write is read by nothing that writes.
+ * cgamd_solver_set_block_pcg: on != 0 turns the mode on, legal only WITH a preconditioner in force; on == 0 returns the handle to the
+ *   bits of the scalar PCG handle it was.  Takes effect at the next cgamd_solver_set_rhs (x0 is allowed).  Returns CGAMD_ERR_STATE,
+ *   the handle untouched, when no preconditioner is in force and on everything cgamd_solver_set_block refuses -- complex types,
+ *   batched handles, CGAMD_UNFUSED, the row-major layout, nRHS outside 2 ... 16, shifts in force -- and on CGAMD_HERMITIAN.
+ *   cgamd_solver_set_block and cgamd_solver_set_block_pcg exclude each other: each refuses a handle the other has turned on.  While on,
+ *   CGAMD_ERR_STATE from the entries block CG refuses, and from EVERY cgamd_solver_set_preconditioner* entry, removal with NULL
+ *   too, because M is part of the state.  cgamd_solver_set_rhs_projected stays served.  cgamd_solver_refresh_values and
+ *   cgamd_solver_reload_matrix keep the setting and rebuild an M that was built from the matrix (where that rebuild fails and M is
+ *   removed, the mode goes with it).
+ * cgamd_solver_block_status serves both modes: info[0] is 2 for the preconditioned one; status 2 means the second factorisation
+ *   failed, here W^T Z (R0^T Z0 at iteration 0).  cgamd_solver_block_state: which = 7 is W^T Z as summed; 4 stays W^T W.
+ * Byte models, vector passes per right-hand side beside the matrix: SpMV 2, Gram 2, step 4: 6, then for a diagonal M the weighted
+ *   Gram 1 and step 8: 4 (15, and m read twice); for a line or multigrid M Gram (W, Z) 2 and step 8: 5 (17, and the preconditioner's
+ *   own bytes as the scalar loop's model prices them).
+ * Development entries (same standing as cgamd_block_gram): cgamd_block_gram_weighted: partials of w_i . (m w_j), m: `size` values
+ *   shared by all columns.  cgamd_block_update_qp_z: q_j = (..(w_0 ti_0j + w_1 ti_1j) + ..) + w_j ti_jj (w: q on entry) and y_j the same
+ *   expression over z_k; p_j = (..(y_j + p_j tau_jj) + ..) + p_s-1 tau_j,s-1 (init != 0: p_j = y_j); exactly one of z (the block) and m
+ *   (z_k = m_i w_k rounded once) is non-NULL. */
+int cgamd_solver_set_block_pcg(cgamd_solver *s, int on);
+int cgamd_block_gram_weighted(cgamd_ctx *ctx, int dtype, int size, long long ld, int s, const void *w, const void *m, void *partials);
+int cgamd_block_update_qp_z(cgamd_ctx *ctx, int dtype, int size, long long ld, int s, void *q, void *p, const void *z, const void *m,
+                            const void *tau_inv, const void *tau, int init);
+
 #ifdef __cplusplus
 }
 #endif
